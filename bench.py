@@ -628,6 +628,23 @@ def sor_only(ctx, B, rank):
     return n1, ms1, by1, n2, ms2, by2
 
 
+DUMP_WINDOWS = 16      # 16 windows x (u, v) x 1024 x 436 fp32 = 57 MB: under the 64 MB a dump may take
+
+
+def dump_outputs(d, jobs, B, BL):
+    """--dump-outputs: the outputs of the last timed step for a fixed sample of the batch (the windows' inputs are seeded by their index, so
+    the same arguments give the same inputs in every run): flow_u / flow_v (n, H, W) float32, the returned change
+    (n, 2) float64 (mean |du|, mean |dv| of the last update, include/slowflow_amd.h), and window_index (n,) float64, the sampled windows in increasing order"""
+    idx = np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_WINDOWS), replace=False))
+    u, v, ch = np.zeros((len(idx), H, W), np.float32), np.zeros((len(idx), H, W), np.float32), np.zeros((len(idx), 2), np.float64)
+    for i, b in enumerate(int(x) for x in idx):
+        gx, gy, c = jobs[b // BL].download(b % BL)
+        u[i], v[i], ch[i] = gx[:, :W], gy[:, :W], c
+    os.makedirs(d, exist_ok=True)
+    for name, a in (("flow_u", u), ("flow_v", v), ("change", ch), ("window_index", idx.astype(np.float64))):
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -700,7 +717,11 @@ def main():
                                                               "every kernel launch of the process is a launch of the timed workload (the kernel-stats pass of profiles/collect.sh)")
     ap.add_argument("--selftest-launch", action="store_true", help="CPU rehearsal of the multi-rank launch and exchange (gloo); prints a selftest line, never a result")
     ap.add_argument("--no-strong", action="store_true", help="skip the config-4 strong-scaling section (128 windows in total under the cfg schedule)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (the flow fields of a fixed, "
+                    "seeded sample of %d windows and their last change (mean |du|, |dv|), as a caller of the job receives them) to DIR/<name>.npy; rank 0 only" % DUMP_WINDOWS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.bench_only:
         args.path_only = True
 
@@ -811,6 +832,8 @@ def main():
     for b in par_idx:
         gx, gy, _ = jobs[b // BL].download(b % BL)
         gpu_flows[b] = (gx[:, :W].copy(), gy[:, :W].copy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, jobs, B, BL)
     from slowflow_amd import shard
     if dist is not None:
         dist.barrier()

@@ -20,10 +20,10 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reflib():
+    """the reference's compiled C (oracle/_ref) where it was built, else its recorded answers (tests/golden/ref_pin.npz, ref_replay.py)"""
     import oracle as orc
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref/libslowflow_ref.so not built (needs /root/reference)")
-    return orc.RefLib()
+    import ref_replay
+    return ref_replay.library("ref_pin", orc.RefLib, orc.ref_available())
 
 
 class _Switches:

@@ -1,7 +1,8 @@
 """EpicFlow's sparse-to-dense interpolation (the initialisation of the path with deep_matching 1): slowflow_amd/host/epic.cpp against
 the reference's own epic() compiled by oracle/Makefile (oracle/_ref/libslowflow_ref_epic.so; unmodified sources, LAPACK = the OpenBLAS inside the scipy wheel).
 The Nadaraya-Watson route (distance transform, neighbourhood graph, graph search, kernel sums) must agree bit for bit; the locally-weighted affine route solves its
-least-squares problems with an own routine instead of sgels and agrees to 1e-3 px; the saliency filter runs its filters on the GPU (-m gpu)."""
+least-squares problems with an own routine instead of sgels and agrees to 1e-3 px; the saliency filter runs its filters on the GPU (-m gpu).
+Where that library was not built, `refepic` answers with the reference's recorded outputs (tests/golden/ref_epic.npz, tests/ref_replay.py)."""
 import ctypes as C
 import os
 import subprocess
@@ -23,18 +24,53 @@ class color_image_t(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("stride", C.c_int), ("c1", _f), ("c2", _f), ("c3", _f)]
 
 
+class RefEpic:
+    """the reference's epic.cpp / image.c entry points the tests compare against (oracle/_ref/libslowflow_ref_epic.so)"""
+
+    def __init__(self):
+        self.L = L = C.CDLL(REF_EPIC)
+        L.rgb_to_lab.restype = C.POINTER(color_image_t)
+        L.saliency.restype = C.POINTER(image_t)
+        L.saliency.argtypes = [C.POINTER(color_image_t), C.c_float, C.c_float]
+
+    def lab(self, rgb, w, h):
+        st = stride_of(w)
+        rgb = np.ascontiguousarray(rgb)
+        im = color_image_t(w, h, st, rgb[0].ctypes.data_as(_f), rgb[1].ctypes.data_as(_f), rgb[2].ctypes.data_as(_f))
+        res = self.L.rgb_to_lab(C.byref(im)).contents
+        return np.stack([np.ctypeslib.as_array(p, shape=(h, st)).copy() for p in (res.c1, res.c2, res.c3)])
+
+    def saliency(self, lab, w, h, sigma_image=0.8, sigma_matrix=1.0):
+        st = stride_of(w)
+        lab = np.ascontiguousarray(lab)
+        im = color_image_t(w, h, st, lab[0].ctypes.data_as(_f), lab[1].ctypes.data_as(_f), lab[2].ctypes.data_as(_f))
+        rs = self.L.saliency(C.byref(im), sigma_image, sigma_matrix).contents
+        return np.ctypeslib.as_array(rs.data, shape=(h, st)).copy()
+
+    def epic(self, lab, edges, m, w, h, method, sal, pref_nn, nn, coef=0.8, euc=0.001):
+        st = stride_of(w)
+        fx, fy = np.zeros((h, st), np.float32), np.zeros((h, st), np.float32)
+        lab = np.ascontiguousarray(lab); e = np.ascontiguousarray(edges).copy(); mm = np.ascontiguousarray(m).copy()
+        self.L.ref_epic(fx.ctypes.data_as(_f), fy.ctypes.data_as(_f), w, h, st, lab.ctypes.data_as(_f), mm.ctypes.data_as(_f), len(mm), e.ctypes.data_as(_f),
+                        method.encode(), C.c_float(sal), pref_nn, C.c_float(5.0), nn, C.c_float(coef), C.c_float(euc))
+        return fx, fy
+
+
+def _ref_epic_loads():
+    if not os.path.exists(REF_EPIC):
+        return False
+    try:
+        C.CDLL(REF_EPIC)
+    except OSError:
+        return False
+    return True
+
+
 @pytest.fixture(scope="module")
 def refepic():
-    if not os.path.exists(REF_EPIC):
-        pytest.skip("oracle/_ref/libslowflow_ref_epic.so not built (needs /root/reference and a LAPACK)")
-    try:
-        L = C.CDLL(REF_EPIC)
-    except OSError as e:
-        pytest.skip("reference epic library does not load here: %s" % e)
-    L.rgb_to_lab.restype = C.POINTER(color_image_t)
-    L.saliency.restype = C.POINTER(image_t)
-    L.saliency.argtypes = [C.POINTER(color_image_t), C.c_float, C.c_float]
-    return L
+    """the compiled reference where it was built and loads, else its recorded answers (tests/golden/ref_epic.npz, ref_replay.py)"""
+    import ref_replay
+    return ref_replay.library("ref_epic", RefEpic, _ref_epic_loads())
 
 
 @pytest.fixture(scope="module")
@@ -91,20 +127,11 @@ def run_tool(tool, d, rgb, edges, m, w, h, method, sal, pref_nn, nn, gpu=False, 
 
 
 def run_ref(L, lab, edges, m, w, h, method, sal, pref_nn, nn, coef=0.8, euc=0.001):
-    st = stride_of(w)
-    fx, fy = np.zeros((h, st), np.float32), np.zeros((h, st), np.float32)
-    lab = np.ascontiguousarray(lab); e = np.ascontiguousarray(edges).copy(); mm = np.ascontiguousarray(m).copy()
-    L.ref_epic(fx.ctypes.data_as(_f), fy.ctypes.data_as(_f), w, h, st, lab.ctypes.data_as(_f), mm.ctypes.data_as(_f), len(mm), e.ctypes.data_as(_f), method.encode(),
-               C.c_float(sal), pref_nn, C.c_float(5.0), nn, C.c_float(coef), C.c_float(euc))
-    return fx, fy
+    return L.epic(lab, edges, m, w, h, method, sal, pref_nn, nn, coef, euc)
 
 
 def ref_lab(L, rgb, w, h):
-    st = stride_of(w)
-    rgb = np.ascontiguousarray(rgb)
-    im = color_image_t(w, h, st, rgb[0].ctypes.data_as(_f), rgb[1].ctypes.data_as(_f), rgb[2].ctypes.data_as(_f))
-    res = L.rgb_to_lab(C.byref(im)).contents
-    return np.stack([np.ctypeslib.as_array(p, shape=(h, st)).copy() for p in (res.c1, res.c2, res.c3)])
+    return L.lab(rgb, w, h)
 
 
 @pytest.mark.parametrize("w,h,seed", [(96, 64, 0), (131, 77, 1)])
@@ -156,17 +183,15 @@ def test_epic_with_saliency_filter_gpu(tool, refepic, tmp_path):
     w, h = 131, 77
     rgb, edges, m = scene(w, h, 5, n_matches=600)
     rgb[:, :30, :40] = 128.0                                          # a textureless corner: matches from there are dropped by the saliency filter
+    rl = ref_lab(refepic, rgb, w, h)                                  # the reference's answers first: none of them needs the GPU
+    rsal = refepic.saliency(rl, w, h, 0.8, 1.0)
+    rx, ry = run_ref(refepic, rl, edges, m, w, h, "NW", 0.045, 25, 100)
+    ra, rb = run_ref(refepic, rl, edges, m, w, h, "LA", 0.045, 25, 100)
     fx, fy, lab = run_tool(tool, str(tmp_path), rgb, edges, m, w, h, "NW", 0.045, 25, 100, gpu=True)
     st = stride_of(w)
     sal = np.fromfile(str(tmp_path / "epic_sal.bin"), dtype=np.float32).reshape(h, st)
-    rl = ref_lab(refepic, rgb, w, h)
-    im = color_image_t(w, h, st, rl[0].ctypes.data_as(_f), rl[1].ctypes.data_as(_f), rl[2].ctypes.data_as(_f))
-    rs = refepic.saliency(C.byref(im), 0.8, 1.0).contents
-    rsal = np.ctypeslib.as_array(rs.data, shape=(h, st)).copy()
     assert np.array_equal(sal[:, :w], rsal[:, :w])
     assert (sal[:25, :35] < 0.045).all() and (sal[:, :w] >= 0.045).mean() > 0.3    # the threshold does select
-    rx, ry = run_ref(refepic, rl, edges, m, w, h, "NW", 0.045, 25, 100)
     assert np.array_equal(fx[:, :w], rx[:, :w]) and np.array_equal(fy[:, :w], ry[:, :w])
     fa, fb, _ = run_tool(tool, str(tmp_path), rgb, edges, m, w, h, "LA", 0.045, 25, 100, gpu=True)
-    ra, rb = run_ref(refepic, rl, edges, m, w, h, "LA", 0.045, 25, 100)
     assert max(np.abs(fa[:, :w] - ra[:, :w]).max(), np.abs(fb[:, :w] - rb[:, :w]).max()) <= 1e-3
