@@ -105,6 +105,21 @@ int sfa_variational(sfa_ctx *ctx, const sfa_params *p, float *wx, float *wy, int
  * plane of 3.  Pinned end to end, bit for bit, against the compiled reference.  p == NULL: variational_params_default. */
 int sfa_variational_2frame(sfa_ctx *ctx, float *wx, float *wy, int w, int h, int stride, const float *im1, const float *im2, const sfa_params_2frame *p);
 void sfa_params_2frame_default(sfa_params_2frame *p);          /* variational.c:86-98 */
+/* n independent pairs of one size (1 <= n <= 128), one parameter set, refined in place in one launch sequence on the context's stream: pair i
+ * (wx[i], wy[i], im1[i], im2[i], each laid out as for sfa_variational_2frame) comes out bit-identical to sfa_variational_2frame on that pair alone,
+ * whatever n and its position.  The adaptiveFR program refines its samples through this. */
+int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *const *wy, int w, int h, int stride, const float *const *im1,
+                                 const float *const *im2, const sfa_params_2frame *p);
+/* adaptiveFR's flow-magnitude quantile (adaptiveFR.cpp:644-668) on the GPU.  n host fields (u[i], v[i]: w x h, row stride `stride`); every value is scaled
+ * by flow_scale first (one fp32 multiply, image_mul_scalar), m = sqrtf(u*u + v*v) in IEEE fp32; the order statistics are found by an exact radix select
+ * over the bit patterns of m.  NaN magnitudes sort above +Inf (their bit order; std::sort has no defined order for them), Inf where it belongs.
+ * *quantile = the rank rule below on the sorted m (as doubles), *max_magnitude = the largest m.  Same bits on every run. */
+int sfa_flow_magnitude_quantile(sfa_ctx *ctx, int n, const float *const *u, const float *const *v, int w, int h, int stride, float flow_scale, float q,
+                                double *quantile, double *max_magnitude);
+/* The rank rule of adaptiveFR.cpp:660-666 for N sorted values, host only: np = q * (float)N - 1 (N goes through float: exact up to 2^24);
+ * np < (float)(N - 1) and fmodf(np, 2) == 0 -> *average = 1, the mean of ranks *k0 = (int)np and *k1 = *k0 + 1; else *average = 0, *k0 = *k1 = (int)ceilf(np).
+ * SFA_ERR_ARG for N == 0, q outside (0, 1] and an N, q whose rank falls outside the N values (the reference reads past its array there). */
+int sfa_quantile_ranks(size_t N, float q, size_t *k0, size_t *k1, int *average);
 /* The reference's own symbol and signature (variational.h:34), for relinking callers such as adaptiveFR / EpicFlow's refinement
  * step: runs on device 0 with a process-wide context; aborts with a message on error like the reference does. */
 void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params);

@@ -64,7 +64,7 @@ class Params2f(C.Structure):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_params_2frame_default", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
@@ -111,6 +111,18 @@ def pyramid_sizes(w, h, layers, p_scale):
     ws, hs = (C.c_int * 64)(), (C.c_int * 64)()
     n = lib().sfa_pyramid_sizes(int(w), int(h), int(layers), C.c_float(p_scale), ws, hs)
     return list(ws[:n]), list(hs[:n])
+
+
+def quantile_ranks(N, q):
+    """the rank rule of adaptiveFR.cpp:660-666 (sfa_quantile_ranks; host only, no GPU): (k0, k1, average) -- the quantile is the mean of the sorted
+    values k0 and k1 when average, else value k0"""
+    L = lib()
+    L.sfa_quantile_ranks.argtypes = [C.c_size_t, C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    k0, k1, av = C.c_size_t(), C.c_size_t(), C.c_int()
+    rc = L.sfa_quantile_ranks(int(N), q, C.byref(k0), C.byref(k1), C.byref(av))
+    if rc != 0:
+        raise SlowflowError("sfa_quantile_ranks(%d, %r): %s" % (N, q, L.sfa_last_error(None).decode()))
+    return k0.value, k1.value, bool(av.value)
 
 
 def default_params():
@@ -304,6 +316,38 @@ class Context:
         h, stride = wx.shape
         self._ck(lib().sfa_variational_2frame(self.h, fptr(wx), fptr(wy), w, h, stride, fptr(im1), fptr(im2), C.byref(p) if p is not None else None),
                  "sfa_variational_2frame")
+
+    def variational_2frame_batch(self, wxs, wys, im1s, im2s, w, p=None):
+        """n pairs of one size through one launch sequence (sfa_variational_2frame_batch), each refined in place; pair i comes out bit-identical to
+        variational_2frame on that pair alone"""
+        n = len(wxs)
+        h, stride = wxs[0].shape if n else (0, 0)
+        for a in list(wxs) + list(wys):
+            assert a.shape == (h, stride), "every flow plane of the batch has one shape"
+        for a in list(im1s) + list(im2s):
+            assert a.shape == (3, h, stride), "every frame of the batch is 3 planes of the flow's shape"
+        assert len(wys) == n and len(im1s) == n and len(im2s) == n, "one wx, wy, im1, im2 per pair"
+        L = lib()
+        L.sfa_variational_2frame_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(_f), C.POINTER(_f), C.c_int, C.c_int, C.c_int, C.POINTER(_f),
+                                                   C.POINTER(_f), C.c_void_p]
+        arrs = [(_f * max(n, 1))(*[fptr(a) for a in group]) for group in (wxs, wys, im1s, im2s)]
+        self._ck(L.sfa_variational_2frame_batch(self.h, n, arrs[0], arrs[1], w, h, stride, arrs[2], arrs[3], C.byref(p) if p is not None else None),
+                 "sfa_variational_2frame_batch")
+
+    def flow_magnitude_quantile(self, us, vs, w, flow_scale, q):
+        """adaptiveFR's quantile (sfa_flow_magnitude_quantile): the fields' magnitudes after scaling by flow_scale, the rank rule of
+        quantile_ranks; returns (quantile, maximum) as floats (doubles)"""
+        n = len(us)
+        h, stride = us[0].shape if n else (1, max(int(w), 1))
+        for a in list(us) + list(vs):
+            assert a.shape == (h, stride), "every plane has one shape"
+        L = lib()
+        L.sfa_flow_magnitude_quantile.argtypes = [C.c_void_p, C.c_int, C.POINTER(_f), C.POINTER(_f), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        ua, va = (_f * max(n, 1))(*[fptr(a) for a in us]), (_f * max(n, 1))(*[fptr(a) for a in vs])
+        qv, mv = C.c_double(), C.c_double()
+        self._ck(L.sfa_flow_magnitude_quantile(self.h, n, ua, va, w, h, stride, flow_scale, q, C.byref(qv), C.byref(mv)), "sfa_flow_magnitude_quantile")
+        return qv.value, mv.value
 
     def compute_one_level(self, p, wx, wy, frames, w, chw=None, want_occ=False):
         return self._run(lib().sfa_compute_one_level, "sfa_compute_one_level", p, wx, wy, frames, w, chw, want_occ)

@@ -1029,6 +1029,55 @@ int sfa_variational_2frame(sfa_ctx *ctx, float *wx, float *wy, int w, int h, int
     return sfa_ctx_sync(ctx);
 }
 
+// n pairs of one size through the launch sequence above at once: pair i owns planes [i * NPL, (i + 1) * NPL) of one allocation, so that every launcher
+// reaches it `es` = NPL planes further along (grid z = pair).  Every launch of the single call, checked for that batch stride:
+//   launch_dpsis (its im_es), launch_warp (src_es; dst, mask, wx, wy at g.es), launch_deriv_stack (es1, es2; out at g.es), launch_zero_planes (g.es),
+//   launch_copy_planes (dst_es, src_es -- the single call passes 0, 0), launch_smoothness_2f / launch_data_2f (g.es throughout), sor_run (a workspace of
+//   g.nb systems, operands and results at g.es), launch_update_inner (g.es; its change norms land in ctx->d_red[2 b], unused here, and its per-block partials
+//   -- 2 x nb x ceil(w / 64) x 16 doubles -- behind them: the kRedDoubles check below, as in sfa_job_create).
+// Same kernels, same per-pixel arithmetic, no cross-pair reduction that feeds back: pair i is bit-identical to sfa_variational_2frame on pair i alone.
+int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *const *wy, int w, int h, int stride, const float *const *im1,
+                                 const float *const *im2, const sfa_params_2frame *pp) {
+    CHECK_ARGS(ctx && wx && wy && im1 && im2 && w >= 2 && h >= 5 && stride >= w, "bad arguments (h >= 5, w >= 2)");
+    CHECK_ARGS(n >= 1 && n <= kMaxBatch, "n out of range (1 .. 128 pairs)");
+    CHECK_ARGS(2L * kMaxBatch + 2L * n * ((w + 63) / 64) * 16 <= kRedDoubles, "n x width beyond the change norms' scratch (sfa_internal.h: kRedDoubles)");
+    for (int i = 0; i < n; i++) CHECK_ARGS(wx[i] && wy[i] && im1[i] && im2[i], "null plane");
+    sfa_params_2frame p;
+    if (pp) p = *pp; else sfa_params_2frame_default(&p);
+    const float half_alpha = 0.5f * p.alpha, hg = p.gamma * 0.5f / 3.0f, hd = p.delta * 0.5f / 3.0f;   // variational.c:113-115
+    enum { WX, WY, UU, VV, DU, DV, SH, SV, A11, A12, A22, B1, B2, MASK, DPS, IM1, IM2 = IM1 + 3, WIM2 = IM2 + 3, STACK = WIM2 + 3, NPL = STACK + 24 };
+    Staging s;
+    SFA_TRY(s.init(ctx, w, h, n * NPL));
+    const long es = NPL * s.pl;
+    for (int i = 0; i < n; i++) {
+        const int b = i * NPL;
+        SFA_TRY(s.up(b + WX, wx[i], stride)); SFA_TRY(s.up(b + WY, wy[i], stride));
+        SFA_TRY(s.up(b + IM1, im1[i], stride, 3)); SFA_TRY(s.up(b + IM2, im2[i], stride, 3));
+    }
+    const Geo g{w, h, s.pitch, s.pl, es, n, WMask::first(n), nullptr};
+    const float zero3[3] = {0, 0, 0}, one3[3] = {1, 1, 1};
+    launch_dpsis(ctx, g, s.plane(DPS), s.plane(IM1), es, 5.0f, zero3, one3, 0);                          // :35
+    SorWorkspace ws;
+    for (int outer = 0; outer < p.niter_outer; outer++) {
+        launch_warp(ctx, g, s.plane(WIM2), s.plane(MASK), s.plane(IM2), s.plane(WX), s.plane(WY), 1, es);  // :41
+        launch_deriv_stack(ctx, g, s.plane(STACK), s.plane(WIM2), s.plane(IM1), es, es);                 // :43
+        launch_zero_planes(ctx, g, s.plane(DU), 2);                                                      // :45-46
+        launch_copy_planes(ctx, g, s.plane(UU), s.plane(WX), 2, es, es);                                 // :48-49
+        for (int inner = 0; inner < p.niter_inner; inner++) {
+            launch_smoothness_2f(ctx, g, s.plane(SH), s.plane(SV), s.plane(UU), s.plane(VV), s.plane(DPS), half_alpha);   // :54
+            launch_data_2f(ctx, g, s.plane(STACK), s.plane(MASK), s.plane(DU), s.plane(DV), s.plane(A11), s.plane(A12), s.plane(A22), s.plane(B1), s.plane(B2),
+                           s.plane(WX), s.plane(WY), s.plane(SH), s.plane(SV), hd, hg);                  // :55-57
+            SFA_TRY(sor_run(ctx, ws, g, s.plane(DU), s.plane(DV), s.plane(A11), s.plane(A12), s.plane(A22), s.plane(B1), s.plane(B2), s.plane(SH), s.plane(SV),
+                            p.niter_solver, p.sor_omega, false));                                       // :59
+            launch_update_inner(ctx, g, s.plane(UU), s.plane(VV), s.plane(WX), s.plane(WY), s.plane(DU), s.plane(DV), s.plane(DU), s.plane(DV), ctx->d_red);   // :62-67
+        }
+        launch_copy_planes(ctx, g, s.plane(WX), s.plane(UU), 2, es, es);                                 // :70-71
+    }
+    SFA_TRY(check_device_error(ctx));
+    for (int i = 0; i < n; i++) { SFA_TRY(s.down(wx[i], stride, i * NPL + WX)); SFA_TRY(s.down(wy[i], stride, i * NPL + WY)); }
+    return sfa_ctx_sync(ctx);
+}
+
 void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params) {
     static std::mutex mu;
     static sfa_ctx *def = nullptr;
