@@ -120,6 +120,19 @@ int sfa_flow_magnitude_quantile(sfa_ctx *ctx, int n, const float *const *u, cons
  * np < (float)(N - 1) and fmodf(np, 2) == 0 -> *average = 1, the mean of ranks *k0 = (int)np and *k1 = *k0 + 1; else *average = 0, *k0 = *k1 = (int)ceilf(np).
  * SFA_ERR_ARG for N == 0, q outside (0, 1] and an N, q whose rank falls outside the N values (the reference reads past its array there). */
 int sfa_quantile_ranks(size_t N, float q, size_t *k0, size_t *k1, int *average);
+/* dense_tracking's first stage, accumulateConsistentBatches (utils/utils.cpp:517-617, with bilinearInterp<double>, utils/utils.h:182-217), for n
+ * independent segments of FF steps in one launch.  Segment s, step f reads the host planes fwd_u/fwd_v/bwd_u/bwd_v[s * FF + f] (w x h, row stride
+ * `stride` floats; widened to double exactly, as readGTMiddlebury's CV_64FC2) and, where masks != NULL, masks[s * FF + f] (uint8, row stride `stride`
+ * bytes; 0 = occluded, the reference's value after 255 - x).  The grid is sfa_accumulate_grid(w, h, skip).  Outputs (host, packed): acc_u, acc_v
+ * [n][S][gh][gw] doubles with S = FF (all_steps != 0) or 1 (the last step only), tracked [n][gh][gw] (FF = fully tracked; else the first inconsistent
+ * step + 1, or 0 with discard).  IEEE fp64 without contraction: bit-identical to a plain restatement of the reference's statements. */
+int sfa_accumulate_consistent(sfa_ctx *ctx, int n, int FF, int w, int h, int stride, const float *const *fwd_u, const float *const *fwd_v,
+                              const float *const *bwd_u, const float *const *bwd_v, const unsigned char *const *masks, double epsilon, int skip, int discard,
+                              int all_steps, double *acc_u, double *acc_v, int *tracked);
+/* The accumulation grid of utils.cpp:522-526, host only: xy_incr = skip + 1, xy_start = (int)(0.5f * skip), *gh = floor((1.0f * h) / xy_incr),
+ * *gw = floor((1.0f * w) / xy_incr); grid pixel (x, y) sits on image pixel (x * xy_incr + xy_start, y * xy_incr + xy_start).
+ * SFA_ERR_ARG for w, h < 1, skip < 0 and an empty grid. */
+int sfa_accumulate_grid(int w, int h, int skip, int *gw, int *gh);
 /* The reference's own symbol and signature (variational.h:34), for relinking callers such as adaptiveFR / EpicFlow's refinement
  * step: runs on device 0 with a process-wide context; aborts with a message on error like the reference does. */
 void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params);

@@ -64,7 +64,7 @@ class Params2f(C.Structure):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
@@ -123,6 +123,18 @@ def quantile_ranks(N, q):
     if rc != 0:
         raise SlowflowError("sfa_quantile_ranks(%d, %r): %s" % (N, q, L.sfa_last_error(None).decode()))
     return k0.value, k1.value, bool(av.value)
+
+
+def accumulate_grid(w, h, skip):
+    """the accumulation grid of utils.cpp:522-526 (sfa_accumulate_grid; host only, no GPU): (gw, gh); grid pixel (x, y) sits on image pixel
+    (x * (skip + 1) + int(0.5 * skip), y * (skip + 1) + int(0.5 * skip))"""
+    L = lib()
+    L.sfa_accumulate_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    gw, gh = C.c_int(), C.c_int()
+    rc = L.sfa_accumulate_grid(int(w), int(h), int(skip), C.byref(gw), C.byref(gh))
+    if rc != 0:
+        raise SlowflowError("sfa_accumulate_grid(%d, %d, %d): %s" % (w, h, skip, L.sfa_last_error(None).decode()))
+    return gw.value, gh.value
 
 
 def default_params():
@@ -348,6 +360,34 @@ class Context:
         qv, mv = C.c_double(), C.c_double()
         self._ck(L.sfa_flow_magnitude_quantile(self.h, n, ua, va, w, h, stride, flow_scale, q, C.byref(qv), C.byref(mv)), "sfa_flow_magnitude_quantile")
         return qv.value, mv.value
+
+    def accumulate_consistent(self, fwd_u, fwd_v, bwd_u, bwd_v, w, epsilon, skip, discard, all_steps=True, masks=None):
+        """dense_tracking's accumulateConsistentBatches (sfa_accumulate_consistent) for n segments of FF steps in one call.  fwd_u .. bwd_v: fp32
+        arrays (n, FF, h, stride), only the w valid columns read; masks: uint8 (n, FF, h, stride), 0 = occluded, or None.  Returns (acc_u, acc_v,
+        tracked): float64 (n, S, gh, gw) with S = FF (all_steps) or 1 (the last step), int32 (n, gh, gw)"""
+        planes = [np.ascontiguousarray(a, dtype=np.float32) for a in (fwd_u, fwd_v, bwd_u, bwd_v)]
+        assert planes[0].ndim == 4, "flows are (n, FF, h, stride)"
+        n, FF, h, stride = planes[0].shape
+        for a in planes:
+            assert a.shape == (n, FF, h, stride), "every flow array has one shape"
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.uint8)
+            assert masks.shape == (n, FF, h, stride), "masks have the flows' shape"
+        gw, gh = accumulate_grid(w, h, skip) if n and FF else (1, 1)
+        S = FF if all_steps else 1
+        acc_u, acc_v = np.zeros((n, S, gh, gw), np.float64), np.zeros((n, S, gh, gw), np.float64)
+        tracked = np.zeros((n, gh, gw), np.int32)
+        L = lib()
+        _u8 = C.POINTER(C.c_ubyte)
+        L.sfa_accumulate_consistent.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(_f)] * 4 + [
+            C.POINTER(_u8), C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        k = max(n * FF, 1)
+        ptrs = [(_f * k)(*[fptr(a[s, f]) for s in range(n) for f in range(FF)]) for a in planes]
+        mp = (_u8 * k)(*[masks[s, f].ctypes.data_as(_u8) for s in range(n) for f in range(FF)]) if masks is not None else None
+        self._ck(L.sfa_accumulate_consistent(self.h, n, FF, w, h, stride, ptrs[0], ptrs[1], ptrs[2], ptrs[3], mp, C.c_double(epsilon), int(skip),
+                                             int(bool(discard)), int(bool(all_steps)), acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data),
+                 "sfa_accumulate_consistent")
+        return acc_u, acc_v, tracked
 
     def compute_one_level(self, p, wx, wy, frames, w, chw=None, want_occ=False):
         return self._run(lib().sfa_compute_one_level, "sfa_compute_one_level", p, wx, wy, frames, w, chw, want_occ)

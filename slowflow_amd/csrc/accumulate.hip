@@ -1,0 +1,165 @@
+// accumulate.hip -- the first stage of dense_tracking (step 3 of the pipeline): accumulateConsistentBatches (utils/utils.cpp:517-617) with the
+// bilinearInterp<double> it calls (utils/utils.h:182-217), on the GPU.
+//
+// Every pixel of the output grid follows the FF forward flows of its segment, interpolated bilinearly in fp64, checks each step against the backward
+// flow, falls back to constant velocity where the check fails and records how many steps stayed consistent.  Pure fp64 arithmetic plus one sqrt, built
+// with -ffp-contract=off: the same bits as a plain restatement of the reference's statements in their order (tests/accum_ref.py).
+//
+// Shape: one thread per (segment, grid pixel), looping over f inside it; the segment is blockIdx.y, so n independent segments (the reference's start_jet
+// loop, dense_tracking.cpp:726, and its rates) cost one launch.  Each step gathers the forward flow at the tracked point and the backward flow at its
+// target: 4 + 4 taps of (u, v), which the upload interleaves into float2 so that a tap is one 8-byte load.  The flows are read where the trajectories
+// go, so the work is bound by these gathers (not by the fp64 arithmetic: about 60 fp64 operations per step).
+#include "sfa_device.h"
+
+#pragma clang fp contract(off)
+
+namespace sfa {
+
+constexpr int kAccThreads = 256;
+
+// bilinearInterp<double>(x, y, fct, c) (utils.h:182-217) for both channels of one float2 plane (.x = u, .y = v), w x h packed.  The caller has checked
+// 0 <= x < w and 0 <= y < h (utils.h:189-190 would throw otherwise).  Widening fp32 to double is exact: readGTMiddlebury's CV_64FC2 (utils.cpp:365).
+__device__ __forceinline__ void bilinear2(const float2 *__restrict__ p, int w, int h, double x, double y, double &ru, double &rv) {
+    const int y0 = (int)y, x0 = (int)x;                                          // :192-193, truncation of a non-negative double
+    int y1 = y0, x1 = x0;                                                       // :194-195
+    double wx = 0, wy = 0;                                                      // quirk: the weight is 0 on the last column and row (:198-209)
+    if (x0 + 1 < w) { wx = x - x0; x1++; }
+    if (y0 + 1 < h) { wy = y - y0; y1++; }
+    const float2 a = p[(size_t)y0 * w + x0], b = p[(size_t)y0 * w + x1];        // :211-214
+    const float2 c = p[(size_t)y1 * w + x0], d = p[(size_t)y1 * w + x1];
+    // :216, left to right: ((1-wy)(1-wx) f00 + (1-wy) wx f10) + wy (1-wx) f01 + wy wx f11, every product and sum rounded on its own
+    ru = (1 - wy) * (1 - wx) * (double)a.x + (1 - wy) * wx * (double)b.x + wy * (1 - wx) * (double)c.x + wy * wx * (double)d.x;
+    rv = (1 - wy) * (1 - wx) * (double)a.y + (1 - wy) * wx * (double)b.y + wy * (1 - wx) * (double)c.y + wy * wx * (double)d.y;
+}
+
+// fwd, bwd: n * FF float2 planes of w x h (segment s, step f at plane s * FF + f); masks: the same count of uint8 planes or null (0 = occluded, the
+// reference's value after 255 - x, dense_tracking.cpp:1192).  acc_u, acc_v: n * S planes of gw x gh doubles, S = FF (all_steps) or 1 (the last step);
+// tracked: n planes of gw x gh.  The reference's Vec2d holds (y, x) = (v, u): channel 0 is v (utils.cpp:364-369); here each channel has its name.
+__global__ void __launch_bounds__(kAccThreads) k_accumulate(const float2 *__restrict__ fwd, const float2 *__restrict__ bwd, const unsigned char *__restrict__ masks,
+                                                            int FF, int w, int h, int gw, int gh, int xy_incr, int xy_start, double epsilon, int discard, int all_steps,
+                                                            double *__restrict__ acc_u, double *__restrict__ acc_v, int *__restrict__ tracked) {
+    const int i = blockIdx.x * kAccThreads + threadIdx.x;
+    if (i >= gw * gh) return;
+    const int s = blockIdx.y, gx = i % gw, gy = i / gw;
+    const size_t pl = (size_t)w * h, gpl = (size_t)gw * gh;
+    const int oy = gy * xy_incr + xy_start, ox = gx * xy_incr + xy_start;      // on the image: checked by the host (sfa_accumulate_grid)
+    const float2 *F = fwd + (size_t)s * FF * pl, *B = bwd + (size_t)s * FF * pl;
+    const unsigned char *M = masks ? masks + (size_t)s * FF * pl : nullptr;
+    // quirk: last_flow starts as forward[0] AT the grid point, not zero (utils.cpp:530-535: "avoid zero flow if directly occluded")
+    const float2 f0 = F[(size_t)oy * w + ox];
+    double last_u = f0.x, last_v = f0.y;
+    double prev_u = 0, prev_v = 0;                                              // acc_forward[f - 1]
+    bool occluded = false;                                                      // :537
+    int tr = FF;                                                                // :538, "fully tracked"
+    const int S = all_steps ? FF : 1;
+    double *AU = acc_u + (size_t)s * S * gpl + i, *AV = acc_v + (size_t)s * S * gpl + i;
+    for (int f = 0; f < FF; f++) {
+        // quirk: acc_forward[f] starts at zero (:541), and an occluded pixel `continue`s (:547-548): its acc stays ZERO for every later f, it does not
+        // carry its last value
+        double au = 0, av = 0;
+        if (!occluded) {
+            double cy = oy, cx = ox;                                            // :550, f_corr = (y, x) of the grid point
+            if (f > 0) { cy += prev_v; cx += prev_u; au = prev_u; av = prev_v; }   // :551-554
+            bool fail;
+            // quirk: the in-image test is >= 0 && < h on the doubles (:556), so a NaN position fails it
+            if (cy >= 0 && cy < h && cx >= 0 && cx < w) {
+                // quirk: the occlusion lookup truncates the double coordinates (at<uchar>(double, double) -> int, :557)
+                if (M && M[(size_t)f * pl + (size_t)(int)cy * w + (int)cx] == 0) {
+                    occluded = true;                                            // :558; this step is still accumulated below
+                    if (tr == FF) tr = discard ? 0 : f + 1;                     // quirk: tracked changes once (:561-566)
+                }
+                double vu, vv;
+                bilinear2(F + (size_t)f * pl, w, h, cx, cy, vu, vv);            // :570-571
+                const double ny = cy + vv, nx = cx + vu;                        // :573
+                // quirk: when the target leaves the image, diff = vec - last_flow (:574, "OUT OF IMAGE CONFIDENCE (FOR NOW CONSTANT VEL)")
+                double dv = vv - last_v, du = vu - last_u;
+                if (ny >= 0 && ny < h && nx >= 0 && nx < w) {                   // :575-576
+                    double bu, bv;
+                    bilinear2(B + (size_t)f * pl, w, h, nx, ny, bu, bv);
+                    dv = vv + bv; du = vu + bu;
+                }
+                const double err = sqrt(dv * dv + du * du);                     // :579, sqrt(dy^2 + dx^2) in that order
+                fail = err > epsilon;                                           // :581, NaN passes as consistent
+                if (fail) { au += last_u; av += last_v; }                       // :583, constant velocity
+                else { au += vu; av += vv; last_u = vu; last_v = vv; }          // :593-595
+            } else {
+                au += last_u; av += last_v;                                     // :598-599, constant velocity
+                fail = true;
+            }
+            if (fail && tr == FF) tr = discard ? 0 : f + 1;                     // :586-591, :602-607: changes once
+            prev_u = au; prev_v = av;
+        }
+        if (all_steps) { AU[(size_t)f * gpl] = au; AV[(size_t)f * gpl] = av; }
+        else if (f == FF - 1) { AU[0] = au; AV[0] = av; }
+    }
+    tracked[(size_t)s * gpl + i] = tr;
+}
+
+// (u, v) planes -> float2 planes, n planes of pl values each
+__global__ void __launch_bounds__(kAccThreads) k_interleave(const float *__restrict__ u, const float *__restrict__ v, float2 *__restrict__ out, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * kAccThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kAccThreads) out[i] = make_float2(u[i], v[i]);
+}
+
+}  // namespace sfa
+
+using namespace sfa;
+
+// utils.cpp:522-526 in its own arithmetic: xy_incr = skip + 1, xy_start = (int)(0.5f * skip), floor of float quotients
+int sfa_accumulate_grid(int w, int h, int skip, int *gw, int *gh) {
+    if (!gw || !gh) return set_error(nullptr, SFA_ERR_ARG, "sfa_accumulate_grid: null output");
+    if (w < 1 || h < 1 || skip < 0 || skip >= w || skip >= h)
+        return set_error(nullptr, SFA_ERR_ARG, "sfa_accumulate_grid: %d x %d with skip %d gives an empty grid (w, h >= 1, 0 <= skip < min(w, h))", w, h, skip);
+    const int xy_incr = skip + 1, xy_start = (int)(0.5f * skip);
+    const unsigned H = (unsigned)floorf((1.0f * h) / xy_incr), W = (unsigned)floorf((1.0f * w) / xy_incr);
+    if (H < 1 || W < 1 || (long)(H - 1) * xy_incr + xy_start >= h || (long)(W - 1) * xy_incr + xy_start >= w)
+        return set_error(nullptr, SFA_ERR_ARG, "sfa_accumulate_grid: %d x %d with skip %d: grid off the image", w, h, skip);
+    *gw = (int)W;
+    *gh = (int)H;
+    return SFA_OK;
+}
+
+int sfa_accumulate_consistent(sfa_ctx *ctx, int n, int FF, int w, int h, int stride, const float *const *fwd_u, const float *const *fwd_v,
+                              const float *const *bwd_u, const float *const *bwd_v, const unsigned char *const *masks, double epsilon, int skip, int discard,
+                              int all_steps, double *acc_u, double *acc_v, int *tracked) {
+    if (!(ctx && fwd_u && fwd_v && bwd_u && bwd_v && acc_u && acc_v && tracked))
+        return set_error(ctx, SFA_ERR_ARG, "sfa_accumulate_consistent: null argument");
+    if (!(n >= 1 && n <= 65535 && FF >= 1 && w >= 1 && h >= 1 && stride >= w))
+        return set_error(ctx, SFA_ERR_ARG, "sfa_accumulate_consistent: bad sizes (1 <= n <= 65535 segments, FF >= 1, w, h >= 1, stride >= w)");
+    int gw, gh;
+    if (sfa_accumulate_grid(w, h, skip, &gw, &gh) != SFA_OK) return set_error(ctx, SFA_ERR_ARG, "%s", sfa_last_error(nullptr));
+    const size_t np = (size_t)n * FF, pl = (size_t)w * h;
+    for (size_t k = 0; k < np; k++)
+        if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k] || (masks && !masks[k])) return set_error(ctx, SFA_ERR_ARG, "sfa_accumulate_consistent: null plane %zu", k);
+    const int S = all_steps ? FF : 1;
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    DevMem dfw, dbw, dstage, dm, dau, dav, dtr;
+    SFA_TRY(dfw.alloc(ctx, np * pl * 8)); SFA_TRY(dbw.alloc(ctx, np * pl * 8)); SFA_TRY(dstage.alloc(ctx, np * pl * 8));
+    if (masks) SFA_TRY(dm.alloc(ctx, np * pl));
+    const size_t gpl = (size_t)gw * gh;
+    SFA_TRY(dau.alloc(ctx, (size_t)n * S * gpl * 8)); SFA_TRY(dav.alloc(ctx, (size_t)n * S * gpl * 8)); SFA_TRY(dtr.alloc(ctx, (size_t)n * gpl * 4));
+    float *su = dstage.f(), *sv = dstage.f() + np * pl;
+    const int iblocks = (int)std::min<size_t>((np * pl + kAccThreads - 1) / kAccThreads, (size_t)ctx->cu_count * 8);
+    for (int dir = 0; dir < 2; dir++) {                                         // the valid columns of each plane, packed, then interleaved
+        const float *const *U = dir ? bwd_u : fwd_u, *const *V = dir ? bwd_v : fwd_v;
+        for (size_t k = 0; k < np; k++) {
+            SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)w * 4, U[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
+            SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, V[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
+        }
+        hipLaunchKernelGGL(k_interleave, dim3(iblocks), dim3(kAccThreads), 0, ctx->stream, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), np * pl);
+    }
+    if (masks)
+        for (size_t k = 0; k < np; k++)
+            SFA_HIP(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dm.p) + k * pl, (size_t)w, masks[k], (size_t)stride, (size_t)w, h, hipMemcpyHostToDevice,
+                                          ctx->stream));
+    const int xy_incr = skip + 1, xy_start = (int)(0.5f * skip);
+    hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((gpl + kAccThreads - 1) / kAccThreads), (unsigned)n), dim3(kAccThreads), 0, ctx->stream,
+                       static_cast<const float2 *>(dfw.p), static_cast<const float2 *>(dbw.p), masks ? static_cast<const unsigned char *>(dm.p) : nullptr, FF, w, h, gw,
+                       gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, static_cast<double *>(dau.p), static_cast<double *>(dav.p),
+                       static_cast<int *>(dtr.p));
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, hipMemcpyAsync(acc_u, dau.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SFA_HIP(ctx, hipMemcpyAsync(acc_v, dav.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SFA_HIP(ctx, hipMemcpyAsync(tracked, dtr.p, (size_t)n * gpl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SFA_OK;
+}
