@@ -133,6 +133,35 @@ int sfa_accumulate_consistent(sfa_ctx *ctx, int n, int FF, int w, int h, int str
  * *gw = floor((1.0f * w) / xy_incr); grid pixel (x, y) sits on image pixel (x * xy_incr + xy_start, y * xy_incr + xy_start).
  * SFA_ERR_ARG for w, h < 1, skip < 0 and an empty grid. */
 int sfa_accumulate_grid(int w, int h, int skip, int *gw, int *gh);
+/* dense_tracking's unary energies (dense_tracking.cpp:1219-1257): the cfg keys of setDefault (:118-165) with the C types the reference reads them in
+ * (:606-623, :489-495, :661-675).  sfa_energy_params_default fills setDefault's values, weight 0 and skip 1. */
+typedef struct sfa_energy_params {
+    float  acc_jc;                  /* acc_jet_consistency ("1.0") */
+    float  acc_bc;                  /* acc_brightness_constancy ("0.1") */
+    float  acc_gc;                  /* acc_gradient_constancy ("1.0") */
+    float  acc_occ;                 /* acc_occlusion_penalty ("500.0") */
+    double acc_cv;                  /* acc_cv ("0.0") */
+    double acc_temporal_occ;        /* acc_temporal_occ ("10.0") */
+    float  occlusion_threshold;     /* acc_occlusion_threshold ("5.0") */
+    float  occlusion_fb_threshold;  /* acc_occlusion_fb_threshold ("5.0") */
+    int    penalty;                 /* acc_penalty_fct_data ("1"): 0 quadratic, 1 modified L1, anything else Lorentzian */
+    double penalty_eps;             /* acc_penalty_fct_data_eps ("0.001"); the penalty's constructor takes it as float */
+    float  weight;                  /* weight_jet_estimation[r]: jet_weight[r], or r where none is given */
+    int    skip;                    /* acc_skip_pixel: the grid of sfa_accumulate_grid and addBCGC's radius (int)(0.5f * (skip + 1)) */
+} sfa_energy_params;
+void sfa_energy_params_default(sfa_energy_params *p);
+/* The energy of every hypothesis of n segments of one rate: adaptFPS(Jets), setOcclusions, addJC + addBCGC + addOC + weight (utils/hypothesis.h:136-175,
+ * utils/hypothesis.cpp:172-215, dense_tracking.cpp:176-365).  acc_u, acc_v, tracked: as sfa_accumulate_consistent returns them for FF = r_Jets and
+ * all_steps = 1 ([n][r_Jets][gh][gw] doubles, [n][gh][gw]); a hypothesis exists where tracked == r_Jets.  frames[s * (Jets + 1) + f]: the first plane of
+ * 3 (c1, c2, c3, each h * stride floats) of normalised colour frame f of segment s; dx, dy are derived on the GPU.  fwd_u .. bwd_v[s * Jets + t]: rate
+ * acc_min_fps's flows (w x h, row stride `stride`), or all four NULL for the empty Mats a rate before acc_min_fps sees (every step t >= 1 occluded).
+ * Outputs [n][gh][gw]: energy (the fp32 sum as a double; +Inf where there is no hypothesis) and occ_bits (bit t = occluded(t), t = 0 .. Jets; 0 where
+ * there is no hypothesis).  1 <= Jets <= 32, h >= 4 (the reference's vertical 5-tap derivative is undefined below), n (Jets + 1) <= 21845.  IEEE fp64
+ * without contraction: bit-identical to a plain restatement (the Lorentzian's fp64 log is the device's, not glibc's; equal after the fp32 rounding
+ * wherever it has been compared). */
+int sfa_hypothesis_energies(sfa_ctx *ctx, const sfa_energy_params *p, int n, int r_Jets, int Jets, int w, int h, int stride, const double *acc_u,
+                            const double *acc_v, const int *tracked, const float *const *frames, const float *const *fwd_u, const float *const *fwd_v,
+                            const float *const *bwd_u, const float *const *bwd_v, double *energy, unsigned long long *occ_bits);
 /* The reference's own symbol and signature (variational.h:34), for relinking callers such as adaptiveFR / EpicFlow's refinement
  * step: runs on device 0 with a process-wide context; aborts with a message on error like the reference does. */
 void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params);

@@ -62,9 +62,26 @@ class Params2f(C.Structure):
                 ("niter_outer", C.c_int), ("niter_inner", C.c_int), ("niter_solver", C.c_int), ("sor_omega", C.c_float)]
 
 
+class EnergyParams(C.Structure):
+    """sfa_energy_params: dense_tracking's energy keys (setDefault, dense_tracking.cpp:118-165) in the C types the reference reads them in"""
+    _fields_ = [("acc_jc", C.c_float), ("acc_bc", C.c_float), ("acc_gc", C.c_float), ("acc_occ", C.c_float), ("acc_cv", C.c_double),
+                ("acc_temporal_occ", C.c_double), ("occlusion_threshold", C.c_float), ("occlusion_fb_threshold", C.c_float), ("penalty", C.c_int),
+                ("penalty_eps", C.c_double), ("weight", C.c_float), ("skip", C.c_int)]
+
+
+def energy_params(**kw):
+    """sfa_energy_params_default (setDefault's values, weight 0, skip 1) with the given fields replaced"""
+    p = EnergyParams()
+    lib().sfa_energy_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
@@ -388,6 +405,36 @@ class Context:
                                              int(bool(discard)), int(bool(all_steps)), acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data),
                  "sfa_accumulate_consistent")
         return acc_u, acc_v, tracked
+
+    def hypothesis_energies(self, p, r_Jets, acc_u, acc_v, tracked, frames, w, flows=None):
+        """dense_tracking's unary energies (sfa_hypothesis_energies) of every hypothesis of n segments of one rate.  p: EnergyParams; acc_u, acc_v:
+        float64 (n, r_Jets, gh, gw) and tracked int32 (n, gh, gw), as accumulate_consistent(all_steps=True) returns them; frames: fp32 (n, Jets + 1,
+        3, h, stride) normalised colour frames (c1, c2, c3); flows: None or (fwd_u, fwd_v, bwd_u, bwd_v), fp32 (n, Jets, h, stride) each, rate
+        acc_min_fps's flows.  Returns energy float64 (n, gh, gw), +Inf where tracked != r_Jets, and occ_bits uint64 (n, gh, gw), bit t = occluded(t)"""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        assert frames.ndim == 5 and frames.shape[2] == 3, "frames are (n, Jets + 1, 3, h, stride)"
+        n, J1, _, h, stride = frames.shape
+        Jets = J1 - 1
+        acc_u, acc_v = np.ascontiguousarray(acc_u, dtype=np.float64), np.ascontiguousarray(acc_v, dtype=np.float64)
+        tracked = np.ascontiguousarray(tracked, dtype=np.int32)
+        gh, gw = tracked.shape[1:]
+        assert tracked.shape == (n, gh, gw) and acc_u.shape == (n, r_Jets, gh, gw) and acc_v.shape == acc_u.shape, "acc_u, acc_v, tracked shapes"
+        L = lib()
+        L.sfa_hypothesis_energies.argtypes = [C.c_void_p, C.POINTER(EnergyParams)] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.POINTER(_f)] * 5 + [
+            C.c_void_p, C.c_void_p]
+        fp = (_f * max(n * J1, 1))(*[fptr(frames[s, f]) for s in range(n) for f in range(J1)])
+        if flows is not None:
+            flows = [np.ascontiguousarray(a, dtype=np.float32) for a in flows]
+            for a in flows:
+                assert a.shape == (n, Jets, h, stride), "flows are (n, Jets, h, stride)"
+            fl = [(_f * max(n * Jets, 1))(*[fptr(a[s, t]) for s in range(n) for t in range(Jets)]) for a in flows]
+        else:
+            fl = [None] * 4
+        energy = np.zeros((n, gh, gw), np.float64)
+        occ = np.zeros((n, gh, gw), np.uint64)
+        self._ck(L.sfa_hypothesis_energies(self.h, C.byref(p), n, int(r_Jets), Jets, w, h, stride, acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data,
+                                           fp, fl[0], fl[1], fl[2], fl[3], energy.ctypes.data, occ.ctypes.data), "sfa_hypothesis_energies")
+        return energy, occ
 
     def compute_one_level(self, p, wx, wy, frames, w, chw=None, want_occ=False):
         return self._run(lib().sfa_compute_one_level, "sfa_compute_one_level", p, wx, wy, frames, w, chw, want_occ)

@@ -7,6 +7,11 @@
 //                                                                 end at), rounded to fp32 as writeFlowMiddlebury rounds it (utils.cpp:333)
 //   <output>/accumulated/<r>/tracked_<sequence_start>.pgm         255 where tracked == FF, else 255 * tracked / FF
 // and <output>/accumulated/run.json: per segment the created and rejected hypotheses (:1353), plus timings.
+// With -energies it also scores every hypothesis as dense_tracking does before its fusion (:1219-1257; sfa_hypothesis_energies) and writes
+//   <output>/accumulated/<r>/energy_<sequence_start>.pfm          the energy per grid pixel, fp32 (exact: the reference sums four floats), +Inf without one
+//   <output>/accumulated/<r>/occluded_<sequence_start>.pgm        the number of occluded frames of the hypothesis (0 without one)
+//   <output>/accumulated/best_<sequence_start>.pgm                the rate of lowest energy (ties: the lower r; 255: none) -- the first element of the
+//                                                                 reference's sort by compareHypotheses (:1401), NOT the TRW-S result
 //
 // Out of scope (TRW-S, FLANN, GSL, OpenCV are not in this tree): the fusion of the hypotheses, EpicFlow's fill-in, removeSmallSegments, cropping and the
 // rescaling of flows of another size (:1131-1146; such flows are refused).
@@ -27,6 +32,7 @@
 #include <vector>
 
 #include "image.h"
+#include "ingest.h"
 #include "io.h"
 #include "parameter_list.h"
 #include "../../include/slowflow_amd.h"
@@ -36,7 +42,7 @@ using std::vector;
 
 static void usage() {
     printf("usage:\n");
-    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume\n");
+    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies\n");
     printf("    ./accumulate -decode_occlusion [occlusion .pgm / .pbm] [mask .pgm]   (the mask this program uses: median 3x3, 255 - x; 0 = occluded)\n");
     printf("\n");
     printf("Runs dense_tracking's first stage only: consistent accumulation of the jets (accumulateConsistentBatches).  cfg keys read: jet_estimation\n");
@@ -44,6 +50,21 @@ static void usage() {
     printf("(or acc_occlusion), acc_discard_inconsistent, acc_consistency_threshold, output, sintel, subframes.  Not done: flows of a size other than\n");
     printf("the first flow's are refused (no rescaling), and the TRW-S fusion, EpicFlow fill-in and removeSmallSegments are left out.\n");
     printf("A missing input file exits with status 2.\n");
+    printf("\n");
+    printf("-energies: also reads the Jets + 1 frames of each start_jet (cfg `file`, the driver's ingest: scale, raw, raw_demosaicing 0 / 2), normalises\n");
+    printf("them and writes each hypothesis' unary energy (energy_<start>.pfm), its occluded frames (occluded_<start>.pgm) and the lowest-energy rate\n");
+    printf("(best_<start>.pgm).  Keys: acc_jet_consistency, acc_brightness_constancy, acc_gradient_constancy, acc_occlusion_penalty, acc_temporal_occ,\n");
+    printf("acc_cv, acc_occlusion_threshold, acc_occlusion_fb_threshold, acc_penalty_fct_data, acc_penalty_fct_data_eps.  Refused: acc_occlusion 1,\n");
+    printf("grayscale 1, raw_demosaicing 1, center / extent, Jets > 32.\n");
+}
+
+// little-endian PFM (Pf, scale -1), rows bottom to top: what io.cpp's reader expects
+static bool write_pfm(const string &file, int w, int h, const float *px) {
+    FILE *f = fopen(file.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "Pf\n%d %d\n-1.0\n", w, h);
+    for (int y = h - 1; y >= 0; y--) fwrite(px + (size_t)y * w, sizeof(float), (size_t)w, f);
+    return fclose(f) == 0;
 }
 
 static bool file_exists(const string &f) { return access(f.c_str(), F_OK) != -1; }
@@ -148,6 +169,217 @@ struct Segment {
     int created = 0, rejected = 0;
 };
 
+// read a segment's flows (and masks) into host images; false with a message on failure
+struct SegmentInput {
+    vector<image_t **> fl;                                                // forward, backward per step
+    vector<const float *> fu, fv, bu, bv;
+    vector<vector<unsigned char>> mbuf;
+    vector<const unsigned char *> mp;
+    ~SegmentInput() { for (image_t **c : fl) { image_delete(c[0]); image_delete(c[1]); free(c); } }
+};
+static bool read_segment(const Segment &s, bool use_occ, int &width, int &height, SegmentInput &in) {
+    for (int f = 0; f < s.FF; f++) {
+        image_t **a = readFlowFile(s.fwd[f].c_str()), **b = readFlowFile(s.bwd[f].c_str());
+        if (a) in.fl.push_back(a);
+        if (b) in.fl.push_back(b);
+        if (!a || !b) { std::cerr << "cannot read " << (a ? s.bwd[f] : s.fwd[f]) << " as a .flo" << std::endl; return false; }
+        if (width == 0) { width = a[0]->width; height = a[0]->height; }
+        for (image_t **c : {a, b})
+            if (c[0]->width != width || c[0]->height != height) {
+                std::cerr << (c == a ? s.fwd[f] : s.bwd[f]) << " is " << c[0]->width << " x " << c[0]->height << ", not " << width << " x " << height
+                          << ": rescaling is not implemented" << std::endl;
+                return false;
+            }
+        in.fu.push_back(a[0]->data); in.fv.push_back(a[1]->data); in.bu.push_back(b[0]->data); in.bv.push_back(b[1]->data);
+        if (use_occ) {
+            int ow, oh;
+            vector<unsigned char> g;
+            if (!read_pnm8(s.occ[f], ow, oh, g)) { std::cerr << s.occ[f] << ": not a binary PGM (maxval 255) or PBM" << std::endl; return false; }
+            if (ow != width || oh != height) { std::cerr << s.occ[f] << " is not " << width << " x " << height << std::endl; return false; }
+            in.mbuf.emplace_back((size_t)a[0]->stride * height, 0);
+            decode_occlusion(g, width, height, a[0]->stride, in.mbuf.back().data());
+        }
+    }
+    for (auto &m : in.mbuf) in.mp.push_back(m.data());
+    return true;
+}
+
+// one frame as dense_tracking ingests it (:793-905): decoded, demosaiced (raw_demosaicing 0 / 2) or taken as RGB, rescaled where scale != 1
+static color_image_t *ingest_frame(ParameterList &params, sfa_ctx *ctx, const string &name) {
+    int maxval = 255;
+    color_image_t *img = color_image_load(name.c_str(), &maxval);
+    if (!img) { std::cerr << "cannot read frame " << name << " (PNG, TIFF or binary PPM/PGM/PFM expected)" << std::endl; return nullptr; }
+    if (params.exists("raw") && params.parameter<bool>("raw")) {
+        vector<int> red_loc;
+        std::stringstream ss(params.parameter<string>("raw_red_loc", "0,0"));
+        for (string t; std::getline(ss, t, ',');) red_loc.push_back(atoi(t.c_str()));
+        image_t mosaic = {img->width, img->height, img->stride, img->c1};
+        color_image_t *rgb = color_image_new(img->width, img->height);
+        color_image_erase(rgb);
+        const int rx = red_loc.size() > 0 ? red_loc[0] : 0, ry = red_loc.size() > 1 ? red_loc[1] : 0;
+        if (params.parameter<int>("raw_demosaicing", "0") == 2) bayer2rgb_cv8u(&mosaic, rgb, rx, ry);
+        else bayer2rgbGR(&mosaic, rgb, rx, ry);
+        color_image_delete(img);
+        img = rgb;
+    }
+    const float scale = (float)params.parameter<double>("scale", "1.0");
+    if (scale != 1) {                                                     // GaussianBlur + resize against aliasing (:863-868)
+        color_image_t *small = color_image_rescale(ctx, img, scale);
+        color_image_delete(img);
+        if (!small) std::cerr << "rescaling " << name << " failed: " << sfa_last_error(ctx) << std::endl;
+        img = small;
+    }
+    return img;
+}
+
+// -energies: per start_jet the frames, then for every rate in cfg order the accumulation (all steps) and the hypotheses' energies (:1100-1257)
+static int run_energies(ParameterList &params, const string &cfg, const string &acc_dir, vector<Segment> &segs, const vector<string> &skipped,
+                        const std::map<unsigned, vector<string>> &frame_files, unsigned rates, int min_fps_idx, unsigned Jets, int steps, int skip,
+                        int skip_pixel, double threshold, bool discard, bool use_occ, const vector<string> &jets, const vector<int> &jet_S,
+                        const vector<int> &jet_fps, const vector<double> &jet_weight) {
+    sfa_energy_params ep;
+    sfa_energy_params_default(&ep);                                       // setDefault (:118-165), in the types of :606-623 and :661-675
+    ep.acc_jc = params.parameter<float>("acc_jet_consistency", "1.0");
+    ep.acc_bc = params.parameter<float>("acc_brightness_constancy", "0.1");
+    ep.acc_gc = params.parameter<float>("acc_gradient_constancy", "1.0");
+    ep.acc_occ = params.parameter<float>("acc_occlusion_penalty", "500.0");
+    ep.acc_temporal_occ = params.parameter<double>("acc_temporal_occ", "10.0");
+    ep.acc_cv = params.parameter<double>("acc_cv", "0.0");
+    ep.occlusion_threshold = params.parameter<float>("acc_occlusion_threshold", "5.0");
+    ep.occlusion_fb_threshold = params.parameter<float>("acc_occlusion_fb_threshold", "5.0");
+    ep.penalty = params.parameter<int>("acc_penalty_fct_data", "1");
+    ep.penalty_eps = params.parameter<double>("acc_penalty_fct_data_eps", "0.001");
+    ep.skip = skip_pixel;
+    sfa_ctx *ctx = nullptr;
+    if (!segs.empty() && sfa_ctx_create(0, &ctx) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; return 1; }
+    double t_frames = 0, t_acc = 0, t_energy = 0, t_io = 0;
+    const double t0 = now_s();
+    int width = 0, height = 0, status = 0;
+    vector<int> hyps(segs.size(), 0);
+    for (auto it = frame_files.begin(); it != frame_files.end() && status == 0; ++it) {
+        const unsigned seq_start = it->first;
+        vector<size_t> mine;                                              // this start_jet's segments, in rate order
+        for (size_t i = 0; i < segs.size(); i++)
+            if (segs[i].seq_start == seq_start) mine.push_back(i);
+        // rate acc_min_fps's flows: forward_flow / backward_flow of the reference (:1148-1151)
+        double ta = now_s();
+        SegmentInput minf;
+        size_t mi = mine.size();
+        for (size_t k = 0; k < mine.size(); k++)
+            if (segs[mine[k]].r == min_fps_idx) mi = k;
+        if (mi == mine.size() || !read_segment(segs[mine[mi]], false, width, height, minf)) { status = 1; break; }
+        vector<color_image_t *> fr;
+        for (const string &name : it->second) {
+            color_image_t *img = ingest_frame(params, ctx, name);
+            if (!img) { status = 1; break; }
+            fr.push_back(img);
+            if (img->width != width || img->height != height) {
+                std::cerr << name << " is " << img->width << " x " << img->height << ", the flows " << width << " x " << height << std::endl;
+                status = 1;
+                break;
+            }
+        }
+        const int stride = fr.empty() ? 0 : fr[0]->stride;
+        vector<float *> fp;
+        for (color_image_t *c : fr) fp.push_back(c->c1);
+        double avg[3], sd[3];
+        if (status == 0 && sfa_normalize(ctx, fp.data(), (int)fp.size(), width, height, stride, avg, sd) != SFA_OK) {   // normalize(data, Jets + 1) (:916)
+            std::cerr << sfa_last_error(ctx) << std::endl;
+            status = 1;
+        }
+        t_frames += now_s() - ta;
+        int gw = 0, gh = 0;
+        if (status == 0 && sfa_accumulate_grid(width, height, skip_pixel, &gw, &gh) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; status = 1; }
+        const size_t gpl = (size_t)gw * gh;
+        vector<float> best_e(gpl, INFINITY);
+        vector<unsigned char> best(gpl, 255);
+        vector<const float *> cfp(fp.begin(), fp.end());
+        for (size_t k = 0; k < mine.size() && status == 0; k++) {
+            Segment &s = segs[mine[k]];
+            double tb = now_s();
+            SegmentInput in;
+            if (!read_segment(s, use_occ, width, height, in) || in.fu.empty()) { status = 1; break; }
+            if (in.fl[0][0]->stride != stride || minf.fl[0][0]->stride != stride) { std::cerr << "frames and flows differ in row stride" << std::endl; status = 1; break; }
+            const int fstride = in.fl[0][0]->stride;
+            vector<double> au((size_t)s.FF * gpl), av(au.size());
+            vector<int> tracked(gpl);
+            if (sfa_accumulate_consistent(ctx, 1, s.FF, width, height, fstride, in.fu.data(), in.fv.data(), in.bu.data(), in.bv.data(),
+                                          use_occ ? in.mp.data() : nullptr, threshold, skip_pixel, discard, 1, au.data(), av.data(), tracked.data()) != SFA_OK) {
+                std::cerr << sfa_last_error(ctx) << std::endl;
+                status = 1;
+                break;
+            }
+            double tc = now_s();
+            t_acc += tc - tb;
+            // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
+            const bool flows = s.r >= min_fps_idx;
+            ep.weight = jet_weight.size() > (size_t)s.r ? (float)jet_weight[s.r] : (float)s.r;   // weight_jet_estimation, vector<float> (:489-495)
+            vector<double> energy(gpl);
+            vector<unsigned long long> occ(gpl);
+            if (sfa_hypothesis_energies(ctx, &ep, 1, s.FF, (int)Jets, width, height, stride, au.data(), av.data(), tracked.data(), cfp.data(),
+                                        flows ? minf.fu.data() : nullptr, flows ? minf.fv.data() : nullptr, flows ? minf.bu.data() : nullptr,
+                                        flows ? minf.bv.data() : nullptr, energy.data(), occ.data()) != SFA_OK) {
+                std::cerr << sfa_last_error(ctx) << std::endl;
+                status = 1;
+                break;
+            }
+            double td = now_s();
+            t_energy += td - tc;
+            image_t *u = image_new(gw, gh), *v = image_new(gw, gh);
+            vector<unsigned char> tp(gpl), oc(gpl);
+            vector<float> ef(gpl);
+            for (int y = 0; y < gh; y++)
+                for (int x = 0; x < gw; x++) {
+                    const size_t i = (size_t)y * gw + x, last = (size_t)(s.FF - 1) * gpl + i;
+                    u->data[(size_t)y * u->stride + x] = (float)au[last];
+                    v->data[(size_t)y * v->stride + x] = (float)av[last];
+                    const int t = tracked[i];
+                    if (t == s.FF) s.created++; else s.rejected++;
+                    tp[i] = (unsigned char)(t == s.FF ? 255 : 255 * t / s.FF);
+                    ef[i] = (float)energy[i];                                 // an fp32 sum stored in a double: exact
+                    oc[i] = (unsigned char)__builtin_popcountll(occ[i]);
+                    if (ef[i] < best_e[i]) { best_e[i] = ef[i]; best[i] = (unsigned char)s.r; }   // strict: ties keep the lower r
+                }
+            hyps[mine[k]] = s.created;
+            const string dir = acc_dir + std::to_string(s.r) + "/";
+            if (writeFlowFile(s.out_flo.c_str(), u, v) != 0 || !write_pgm8(s.out_tracked, gw, gh, tp.data(), gw) ||
+                !write_pfm(dir + "energy_" + std::to_string(seq_start) + ".pfm", gw, gh, ef.data()) ||
+                !write_pgm8(dir + "occluded_" + std::to_string(seq_start) + ".pgm", gw, gh, oc.data(), gw)) {
+                std::cerr << "cannot write the outputs of rate " << s.r << " under " << dir << std::endl;
+                status = 1;
+            }
+            image_delete(u); image_delete(v);
+            t_io += now_s() - td;
+            std::cout << "rate " << s.r << ", start " << s.seq_start << ": " << s.created << " trajectory hypotheses generated! (" << s.rejected
+                      << " rejected)" << std::endl;                                               // :1353
+        }
+        for (color_image_t *c : fr) color_image_delete(c);
+        if (status == 0 && !write_pgm8(acc_dir + "best_" + std::to_string(seq_start) + ".pgm", gw, gh, best.data(), gw)) {
+            std::cerr << "cannot write " << acc_dir << "best_" << seq_start << ".pgm" << std::endl;
+            status = 1;
+        }
+    }
+    if (ctx) sfa_ctx_destroy(ctx);
+    if (status) return status;
+    std::ofstream js((acc_dir + "run.json").c_str());
+    js << "{\n  \"cfg\": \"" << cfg << "\",\n  \"energies\": true, \"Jets\": " << Jets << ", \"steps\": " << steps << ", \"skip\": " << skip
+       << ", \"acc_skip_pixel\": " << skip_pixel << ", \"width\": " << width << ", \"height\": " << height << ",\n  \"rates\": [";
+    for (unsigned r = 0; r < rates; r++)
+        js << (r ? ", " : "") << "{\"jet_estimation\": \"" << jets[r] << "\", \"jet_S\": " << jet_S[r] << ", \"jet_fps\": " << jet_fps[r]
+           << ", \"jet_weight\": " << (jet_weight.size() > r ? (double)(float)jet_weight[r] : (double)r) << "}";
+    js << "],\n  \"segments\": [";
+    for (size_t i = 0; i < segs.size(); i++)
+        js << (i ? ",\n    " : "\n    ") << "{\"rate\": " << segs[i].r << ", \"start_jet\": " << segs[i].start_jet << ", \"sequence_start\": " << segs[i].seq_start
+           << ", \"FF\": " << segs[i].FF << ", \"created\": " << segs[i].created << ", \"rejected\": " << segs[i].rejected << ", \"hypotheses\": " << hyps[i]
+           << ", \"flo\": \"" << segs[i].out_flo << "\"}";
+    js << "],\n  \"skipped\": [";
+    for (size_t i = 0; i < skipped.size(); i++) js << (i ? ", " : "") << "\"" << skipped[i] << "\"";
+    js << "],\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc << ", \"energy_call\": " << t_energy << ", \"write\": " << t_io
+       << ", \"total\": " << now_s() - t0 << "}\n}\n";
+    std::cout << "wrote the energies of " << segs.size() << " segment(s) to " << acc_dir << std::endl;
+    return js.good() ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "-decode_occlusion")) {
         if (argc != 4) { usage(); return 1; }
@@ -163,12 +395,13 @@ int main(int argc, char **argv) {
     if (!file_exists(cfg)) { usage(); return 1; }
     printf("using parameters %s\n", cfg.c_str());
     unsigned selected = 0, selected_end = 0;
-    bool resume = false;
+    bool resume = false, energies = false;
     for (int i = 2; i < argc; i++) {                                     // :449-476
         const char *a = argv[i];
         if (a[0] != '-') continue;
         if (!strcmp(a, "-h") || !strcmp(a, "-help")) usage();
         else if (!strcmp(a, "-resume")) resume = true;
+        else if (!strcmp(a, "-energies")) energies = true;
         else if (!strcmp(a, "-select") && i + 1 < argc) { selected = (unsigned)atoi(argv[++i]); selected_end = selected + 1; }
         else { fprintf(stderr, "unknown argument %s\n", a); usage(); return 1; }
     }
@@ -216,6 +449,17 @@ int main(int argc, char **argv) {
     const unsigned Jets = (unsigned)(jet_fps[min_fps_idx] / (1.0f * ref_fps * steps));     // :564, float -> u_int32_t
     const int skip = (int)((1.0f * max_fps) / jet_fps[min_fps_idx]);    // :571
     if (Jets < 1) { std::cerr << "Jets = jet_fps / (ref_fps * steps) is 0" << std::endl; return 1; }
+    if (energies) {
+        // acc_occlusion 1 makes addBCGC read occlusion_masks[Jets], one past the Mat[Jets] array (:784, :289): undefined in the reference
+        const char *refused = params.parameter<bool>("acc_occlusion", "0") ? "acc_occlusion 1 (addBCGC reads occlusion_masks[Jets], past the array)"
+                              : params.parameter<bool>("grayscale", "0") ? "grayscale 1"
+                              : (params.exists("raw") && params.parameter<bool>("raw") && params.parameter<int>("raw_demosaicing", "0") == 1)
+                                  ? "raw_demosaicing 1 (Hamilton-Adams, third-party, not here)"
+                              : (params.extent.x > 0 || params.extent.y > 0 || params.center.x > 0) ? "cropping (center / extent)"
+                              : Jets > 32 ? "Jets > 32" : nullptr;
+        if (refused) { std::cerr << "-energies: " << refused << " is not supported" << std::endl; return 1; }
+        if (params.file.empty()) { std::cerr << "-energies: `file` (the frames) missing from " << cfg << std::endl; return 1; }
+    }
     if (selected_end == 0) selected_end = (unsigned)ref_fps_F;           // :722-723
     unsigned sequence_start = params.sequence_start;
     if (sintel && !subframes) sequence_start *= 1000;                    // :716-717
@@ -238,6 +482,10 @@ int main(int argc, char **argv) {
     vector<string> skipped;
     for (unsigned start_jet = selected; start_jet < selected_end; start_jet++) {
         const unsigned seq_start = sequence_start + start_jet * Jets * steps * skip;   // :735
+        if (energies) {                                                  // with the energies a start_jet is done as a whole: all its rates are compared
+            const string best = acc_dir + "best_" + std::to_string(seq_start) + ".pgm";
+            if (file_exists(best)) { std::cout << "Energy file " << best << " already exists!" << std::endl; skipped.push_back(best); continue; }
+        }
         for (unsigned r = 0; r < rates; r++) {
             Segment s;
             s.r = (int)r; s.start_jet = start_jet; s.seq_start = seq_start;
@@ -248,7 +496,7 @@ int main(int argc, char **argv) {
             const string dir = acc_dir + std::to_string(r) + "/";
             s.out_flo = dir + (sintel ? fmt2("s" + flow_format, (int)seq_start, 0) : fmt1(flow_format, (int)seq_start)) + ".flo";
             s.out_tracked = dir + "tracked_" + std::to_string(seq_start) + ".pgm";
-            if (file_exists(s.out_flo)) { std::cout << "Flow file " << s.out_flo << " already exists!" << std::endl; skipped.push_back(s.out_flo); continue; }
+            if (!energies && file_exists(s.out_flo)) { std::cout << "Flow file " << s.out_flo << " already exists!" << std::endl; skipped.push_back(s.out_flo); continue; }
             if (s.FF < 1) { std::cerr << "rate " << r << ": r_Jets = " << s.FF << ", nothing to accumulate" << std::endl; return 1; }
             for (int f = 0; f < s.FF; f++) {
                 const int a = (int)seq_start + f * r_steps * r_skip;
@@ -270,8 +518,32 @@ int main(int argc, char **argv) {
                 else { std::cerr << s.occ[f] << ".pgm does not exist (nor " << s.occ[f] << ".pbm)!" << std::endl; return 2; }
             }
         }
+    // the frames of each start_jet (:793-810): sequence_start + f * steps * skip, f = 0 .. Jets
+    std::map<unsigned, vector<string>> frame_files;
+    if (energies) {
+        const size_t sf = params.file.find_last_of('/') + 1;             // :740-751 (npos + 1 == 0: no folder)
+        string sequence_path = params.file.substr(0, sf);
+        const string format = params.file.substr(sf);
+        if (!sequence_path.empty() && sequence_path.back() != '/') sequence_path += "/";
+        for (const Segment &s : segs) {
+            vector<string> &names = frame_files[s.seq_start];
+            if (!names.empty()) continue;
+            for (unsigned f = 0; f <= Jets; f++) {
+                if (!sintel) names.push_back(fmt1(sequence_path + format, (int)(s.seq_start + f * steps * skip)));
+                else {
+                    int sintel_frame = (int)s.seq_start / 1000, hfr = (int)(f * steps * skip) + (int)(s.seq_start % 1000);
+                    while (hfr < 0) { sintel_frame--; hfr += 42; }
+                    while (hfr > 41) { sintel_frame++; hfr -= 42; }
+                    names.push_back(fmt2(sequence_path + format, sintel_frame, hfr));
+                }
+                if (!file_exists(names.back())) { std::cerr << names.back() << " does not exist!" << std::endl; return 2; }
+            }
+        }
+    }
     mkdirs(acc_dir);
     for (unsigned r = 0; r < rates; r++) mkdirs(acc_dir + std::to_string(r) + "/");
+    if (energies) return run_energies(params, cfg, acc_dir, segs, skipped, frame_files, rates, min_fps_idx, Jets, steps, skip, skip_pixel, threshold, discard,
+                                      use_occ, jets, jet_S, jet_fps, jet_weight);
 
     sfa_ctx *ctx = nullptr;
     if (!segs.empty() && sfa_ctx_create(0, &ctx) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; return 1; }
