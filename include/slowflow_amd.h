@@ -162,6 +162,43 @@ void sfa_energy_params_default(sfa_energy_params *p);
 int sfa_hypothesis_energies(sfa_ctx *ctx, const sfa_energy_params *p, int n, int r_Jets, int Jets, int w, int h, int stride, const double *acc_u,
                             const double *acc_v, const int *tracked, const float *const *frames, const float *const *fwd_u, const float *const *fwd_v,
                             const float *const *bwd_u, const float *const *bwd_v, double *energy, unsigned long long *occ_bits);
+/* The same, and where adapted_u, adapted_v are given (both or neither) every hypothesis' flows after adaptFPS(Jets), the flows the energy was computed
+ * from, as [n][Jets][gh][gw] doubles (0 where there is no hypothesis).  sfa_hypothesis_energies is this call with both NULL. */
+int sfa_hypothesis_energies_ex(sfa_ctx *ctx, const sfa_energy_params *p, int n, int r_Jets, int Jets, int w, int h, int stride, const double *acc_u,
+                               const double *acc_v, const int *tracked, const float *const *frames, const float *const *fwd_u, const float *const *fwd_v,
+                               const float *const *bwd_u, const float *const *bwd_v, double *energy, unsigned long long *occ_bits, double *adapted_u,
+                               double *adapted_v);
+/* dense_tracking's computeSmoothnessWeight (dense_tracking.cpp:367-405, called at :969-981 with coef 5.0): the luminance
+ * (0.299f (c1 std_1 + avg_1) + 0.587f (...) + 0.114f (...)) / 255.0f (/ 65535.0f with hbit), its 5-tap {0, -8/12, 1/12} derivatives, then
+ * 0.5f * expf(-coef * sqrtf(lx^2 + ly^2)), all in fp32 without contraction.  The formula is the first output of Variational_AUX_MT::compute_dpsis_weight
+ * (sfa_dpsis_weight) and runs through the same pinned kernel; expf is glibc's algorithm restated on the device (see sfa_dpsis_weight).  frame0: the first
+ * of 3 planes of h * stride floats; out: a PACKED [h][w] plane.  h >= 4 (the vertical 5-tap). */
+int sfa_dt_smoothness_weight(sfa_ctx *ctx, int w, int h, int stride, const float *frame0, float coef, const float avg[3], const float std_dev[3], int hbit,
+                             float *out);
+/* dense_tracking's fusion of the hypotheses (dense_tracking.cpp:1588-1905): non-maximum suppression, the pairwise MRF and TRW-S.  The cfg keys with the
+ * C types the reference reads them in (:605-625, :660-661); sfa_fuse_params_default fills setDefault's values (:136-152) and skip 1. */
+typedef struct sfa_fuse_params {
+    double acc_beta;                /* acc_beta ("10.0") */
+    double acc_spatial_occ;         /* acc_spatial_occ (10.0; setDefault's key is misspelt acc_satial_occ and never read) */
+    int    traj_sim_method;         /* acc_traj_sim_method ("1"): 0 ADJ, 1 ACC; 2 FINAL is refused (it reads flow_y[Jets], past the array) */
+    double traj_sim_thres;          /* acc_traj_sim_thres ("0.1") */
+    double trws_eps;                /* acc_trws_eps ("1e-5") */
+    int    trws_max_iter;           /* acc_trws_max_iter ("10") */
+    int    skip;                    /* acc_skip_pixel: the grid of sfa_accumulate_grid, xy_incr = skip + 1, xy_start = (int)(0.5f * skip) */
+} sfa_fuse_params;
+void sfa_fuse_params_default(sfa_fuse_params *p);
+/* n segments (start_jets) of gw x gh grid pixels with K label slots each (1 <= K <= 16, the rates), 1 <= Jets <= 32.  Inputs: U, V [n][K][Jets][gh][gw]
+ * adapted flows (sfa_hypothesis_energies_ex), energy [n][K][gh][gw] (+Inf: no hypothesis in that slot), occ_bits [n][K][gh][gw] (bit t = occluded(t)),
+ * weight [n][h][w] packed smoothness weights (sfa_dt_smoothness_weight).  Per pixel: the present slots sorted by (float) energy, ties to the lower slot,
+ * then the NMS of :1592-1630 with its `break`; a pixel left without a hypothesis is no node and its edges are dropped.  Right and down edges cost
+ * P = (w[o1] + w[o2]) * (acc_beta * (float) distance + acc_spatial_occ * smooth_occ) (:1716-1797).  TRW-S in sequential raster order, fp64 without
+ * contraction (INTEGRATION.md 4c defines it; the bound is the reparametrisation bound, not the MRF library's tree bound).  Outputs [n][gh][gw]: slot (-1 =
+ * none), flow_u, flow_v = u(Jets - 1) / xy_incr, v(Jets - 1) / xy_incr (:1856-1857; 1e10 = UNKNOWN_FLOW where there is no node), occ = max_t occluded(t),
+ * t = 0 .. Jets (:1859-1863); per segment: seg_energy (of the labelling returned, the lowest over the iterations), seg_bound (after the last iteration),
+ * seg_iters.  stage_ms: NULL or 4 floats, the milliseconds of the label, pairwise, TRW-S and output kernels of the call (HIP events). */
+int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, const double *U, const double *V, const double *energy,
+                        const unsigned long long *occ_bits, const float *weight, int *slot, double *flow_u, double *flow_v, unsigned char *occ,
+                        double *seg_energy, double *seg_bound, int *seg_iters, float *stage_ms);
 /* The reference's own symbol and signature (variational.h:34), for relinking callers such as adaptiveFR / EpicFlow's refinement
  * step: runs on device 0 with a process-wide context; aborts with a message on error like the reference does. */
 void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params);

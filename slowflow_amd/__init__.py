@@ -79,9 +79,25 @@ def energy_params(**kw):
     return p
 
 
+class FuseParams(C.Structure):
+    """sfa_fuse_params: dense_tracking's fusion keys (setDefault, dense_tracking.cpp:136-152) in the C types the reference reads them in"""
+    _fields_ = [("acc_beta", C.c_double), ("acc_spatial_occ", C.c_double), ("traj_sim_method", C.c_int), ("traj_sim_thres", C.c_double),
+                ("trws_eps", C.c_double), ("trws_max_iter", C.c_int), ("skip", C.c_int)]
+
+
+def fuse_params(**kw):
+    """sfa_fuse_params_default (setDefault's values, skip 1) with the given fields replaced"""
+    p = FuseParams()
+    lib().sfa_fuse_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
@@ -406,11 +422,12 @@ class Context:
                  "sfa_accumulate_consistent")
         return acc_u, acc_v, tracked
 
-    def hypothesis_energies(self, p, r_Jets, acc_u, acc_v, tracked, frames, w, flows=None):
+    def hypothesis_energies(self, p, r_Jets, acc_u, acc_v, tracked, frames, w, flows=None, adapted=False):
         """dense_tracking's unary energies (sfa_hypothesis_energies) of every hypothesis of n segments of one rate.  p: EnergyParams; acc_u, acc_v:
         float64 (n, r_Jets, gh, gw) and tracked int32 (n, gh, gw), as accumulate_consistent(all_steps=True) returns them; frames: fp32 (n, Jets + 1,
         3, h, stride) normalised colour frames (c1, c2, c3); flows: None or (fwd_u, fwd_v, bwd_u, bwd_v), fp32 (n, Jets, h, stride) each, rate
-        acc_min_fps's flows.  Returns energy float64 (n, gh, gw), +Inf where tracked != r_Jets, and occ_bits uint64 (n, gh, gw), bit t = occluded(t)"""
+        acc_min_fps's flows.  Returns energy float64 (n, gh, gw), +Inf where tracked != r_Jets, and occ_bits uint64 (n, gh, gw), bit t = occluded(t);
+        with adapted=True also the flows after adaptFPS(Jets), float64 (n, Jets, gh, gw) each (sfa_hypothesis_energies_ex; 0 without a hypothesis)"""
         frames = np.ascontiguousarray(frames, dtype=np.float32)
         assert frames.ndim == 5 and frames.shape[2] == 3, "frames are (n, Jets + 1, 3, h, stride)"
         n, J1, _, h, stride = frames.shape
@@ -432,9 +449,51 @@ class Context:
             fl = [None] * 4
         energy = np.zeros((n, gh, gw), np.float64)
         occ = np.zeros((n, gh, gw), np.uint64)
-        self._ck(L.sfa_hypothesis_energies(self.h, C.byref(p), n, int(r_Jets), Jets, w, h, stride, acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data,
-                                           fp, fl[0], fl[1], fl[2], fl[3], energy.ctypes.data, occ.ctypes.data), "sfa_hypothesis_energies")
-        return energy, occ
+        if not adapted:
+            self._ck(L.sfa_hypothesis_energies(self.h, C.byref(p), n, int(r_Jets), Jets, w, h, stride, acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data,
+                                               fp, fl[0], fl[1], fl[2], fl[3], energy.ctypes.data, occ.ctypes.data), "sfa_hypothesis_energies")
+            return energy, occ
+        L.sfa_hypothesis_energies_ex.argtypes = L.sfa_hypothesis_energies.argtypes + [C.c_void_p, C.c_void_p]
+        au, av = np.zeros((n, Jets, gh, gw), np.float64), np.zeros((n, Jets, gh, gw), np.float64)
+        self._ck(L.sfa_hypothesis_energies_ex(self.h, C.byref(p), n, int(r_Jets), Jets, w, h, stride, acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data,
+                                              fp, fl[0], fl[1], fl[2], fl[3], energy.ctypes.data, occ.ctypes.data, au.ctypes.data, av.ctypes.data),
+                 "sfa_hypothesis_energies_ex")
+        return energy, occ, au, av
+
+    def smoothness_weight(self, frame0, w, avg=(0, 0, 0), std=(1, 1, 1), hbit=0, coef=5.0):
+        """dense_tracking's computeSmoothnessWeight (sfa_dt_smoothness_weight) of one fp32 (3, h, stride) frame: a packed fp32 (h, w) plane"""
+        frame0 = np.ascontiguousarray(frame0, dtype=np.float32)
+        _, h, stride = frame0.shape
+        out = np.zeros((h, w), np.float32)
+        L = lib()
+        L.sfa_dt_smoothness_weight.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _f, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, _f]
+        a, s = (C.c_float * 3)(*avg), (C.c_float * 3)(*std)
+        self._ck(L.sfa_dt_smoothness_weight(self.h, int(w), h, stride, fptr(frame0), C.c_float(coef), a, s, int(hbit), fptr(out)), "sfa_dt_smoothness_weight")
+        return out
+
+    def fuse_hypotheses(self, p, U, V, energy, occ_bits, weight, w, h, stage_ms=False):
+        """dense_tracking's fusion (sfa_fuse_hypotheses) of n segments with K slots.  p: FuseParams; U, V float64 (n, K, Jets, gh, gw) adapted flows;
+        energy float64 (n, K, gh, gw), +Inf = no hypothesis; occ_bits uint64 (n, K, gh, gw); weight fp32 (n, h, w) smoothness weights.  Returns a dict:
+        slot int32, u, v float64, occ uint8 (n, gh, gw); energy, bound float64 (n,); iters int32 (n,); with stage_ms the 4 kernel stages' ms."""
+        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
+        energy = np.ascontiguousarray(energy, dtype=np.float64)
+        occ_bits = np.ascontiguousarray(occ_bits, dtype=np.uint64)
+        weight = np.ascontiguousarray(weight, dtype=np.float32)
+        n, K, Jets, gh, gw = U.shape
+        assert V.shape == U.shape and energy.shape == (n, K, gh, gw) and occ_bits.shape == energy.shape and weight.shape == (n, h, w), "shapes"
+        assert accumulate_grid(w, h, p.skip) == (gw, gh), "U, V, energy, occ_bits are not on the grid of (w, h, p.skip)"
+        out = dict(slot=np.zeros((n, gh, gw), np.int32), u=np.zeros((n, gh, gw), np.float64), v=np.zeros((n, gh, gw), np.float64),
+                   occ=np.zeros((n, gh, gw), np.uint8), energy=np.zeros(n, np.float64), bound=np.zeros(n, np.float64), iters=np.zeros(n, np.int32))
+        ms = np.zeros(4, np.float32)
+        L = lib()
+        L.sfa_fuse_hypotheses.argtypes = [C.c_void_p, C.POINTER(FuseParams)] + [C.c_int] * 5 + [C.c_void_p] * 13
+        self._ck(L.sfa_fuse_hypotheses(self.h, C.byref(p), n, K, Jets, int(w), int(h), U.ctypes.data, V.ctypes.data, energy.ctypes.data, occ_bits.ctypes.data,
+                                       weight.ctypes.data, out["slot"].ctypes.data, out["u"].ctypes.data, out["v"].ctypes.data, out["occ"].ctypes.data,
+                                       out["energy"].ctypes.data, out["bound"].ctypes.data, out["iters"].ctypes.data, ms.ctypes.data if stage_ms else None),
+                 "sfa_fuse_hypotheses")
+        if stage_ms:
+            out["stage_ms"] = ms
+        return out
 
     def compute_one_level(self, p, wx, wy, frames, w, chw=None, want_occ=False):
         return self._run(lib().sfa_compute_one_level, "sfa_compute_one_level", p, wx, wy, frames, w, chw, want_occ)

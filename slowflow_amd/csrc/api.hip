@@ -737,6 +737,18 @@ int sfa_dpsis_weight(sfa_ctx *ctx, float *dst, const float *im3, int w, int h, i
     return sfa_ctx_sync(ctx);
 }
 
+// computeSmoothnessWeight (dense_tracking.cpp:367-405) is compute_dpsis_weight's first output statement for statement: the same kernel
+int sfa_dt_smoothness_weight(sfa_ctx *ctx, int w, int h, int stride, const float *frame0, float coef, const float avg[3], const float std_dev[3], int hbit,
+                             float *out) {
+    CHECK_ARGS(ctx && frame0 && avg && std_dev && out && w > 0 && h >= 4 && stride >= w, "bad arguments (w >= 1, h >= 4, stride >= w)");
+    Staging s;
+    SFA_TRY(s.init(ctx, w, h, 4));
+    SFA_TRY(s.up(0, frame0, stride, 3));
+    launch_dpsis(ctx, s.geo(), s.plane(3), s.plane(0), 0, coef, avg, std_dev, hbit);
+    SFA_TRY(s.down(out, w, 3));
+    return sfa_ctx_sync(ctx);
+}
+
 int sfa_smoothness(sfa_ctx *ctx, int method, float *dst_horiz, float *dst_vert, const float *uu, const float *vv, const float *dpsis, int w, int h,
                    int stride, float alpha, const sfa_penalty *reg) {
     CHECK_ARGS(ctx && dst_horiz && dst_vert && uu && vv && dpsis && reg && w > 0 && h >= 2 && stride >= w, "bad arguments");

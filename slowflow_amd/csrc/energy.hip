@@ -248,6 +248,20 @@ __global__ void __launch_bounds__(kBcThreads) k_hyp_bcgc(const float4 *__restric
     ep[si * NN + k] = e_p;
 }
 
+// the adapted flows of k_hyp_serial ([n][gpl][J]) in the layout [n][J][gpl] the fusion reads, 0 where there is no hypothesis
+__global__ void __launch_bounds__(kEnThreads) k_hyp_adapted(const int *__restrict__ tracked, const double *__restrict__ U, const double *__restrict__ V, int rJ,
+                                                            int J, int gpl, double *__restrict__ out_u, double *__restrict__ out_v) {
+    const int i = blockIdx.x * kEnThreads + threadIdx.x;
+    if (i >= gpl) return;
+    const size_t si = (size_t)blockIdx.y * gpl + i;
+    const bool have = tracked[si] == rJ;
+    for (int t = 0; t < J; t++) {
+        const size_t o = ((size_t)blockIdx.y * J + t) * gpl + i;
+        out_u[o] = have ? U[si * J + t] : 0.0;
+        out_v[o] = have ? V[si * J + t] : 0.0;
+    }
+}
+
 // wenergy over the neighbours in order, / neighs (:332-346), and the energy: ((JC + BCGC) + OC) + weight in fp32 (:1250-1253)
 __global__ void __launch_bounds__(kEnThreads) k_hyp_sum(const int *__restrict__ tracked, const unsigned long long *__restrict__ occ_bits,
                                                         const float *__restrict__ jc, const float *__restrict__ oc, const double *__restrict__ ep, int rJ, int w, int h,
@@ -302,7 +316,16 @@ void sfa_energy_params_default(sfa_energy_params *p) {
 int sfa_hypothesis_energies(sfa_ctx *ctx, const sfa_energy_params *p, int n, int r_Jets, int Jets, int w, int h, int stride, const double *acc_u,
                             const double *acc_v, const int *tracked, const float *const *frames, const float *const *fwd_u, const float *const *fwd_v,
                             const float *const *bwd_u, const float *const *bwd_v, double *energy, unsigned long long *occ_bits) {
+    return sfa_hypothesis_energies_ex(ctx, p, n, r_Jets, Jets, w, h, stride, acc_u, acc_v, tracked, frames, fwd_u, fwd_v, bwd_u, bwd_v, energy, occ_bits,
+                                      nullptr, nullptr);
+}
+
+int sfa_hypothesis_energies_ex(sfa_ctx *ctx, const sfa_energy_params *p, int n, int r_Jets, int Jets, int w, int h, int stride, const double *acc_u,
+                               const double *acc_v, const int *tracked, const float *const *frames, const float *const *fwd_u, const float *const *fwd_v,
+                               const float *const *bwd_u, const float *const *bwd_v, double *energy, unsigned long long *occ_bits, double *adapted_u,
+                               double *adapted_v) {
     if (!(ctx && p && acc_u && acc_v && tracked && frames && energy && occ_bits)) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: null argument");
+    if ((adapted_u != nullptr) != (adapted_v != nullptr)) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies_ex: adapted_u and adapted_v are both given or both null");
     const bool flows = fwd_u != nullptr;
     if (flows != (fwd_v != nullptr) || flows != (bwd_u != nullptr) || flows != (bwd_v != nullptr))
         return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: the four flow arrays are all given or all null");
@@ -400,6 +423,16 @@ int sfa_hypothesis_energies(sfa_ctx *ctx, const sfa_energy_params *p, int n, int
     SFA_HIP(ctx, hipGetLastError());
     SFA_HIP(ctx, hipMemcpyAsync(energy, den.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(occ_bits, docc_out.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (adapted_u) {                                                            // k_hyp_serial's adaptFPS(Jets), transposed for the fusion
+        DevMem dad;
+        SFA_TRY(dad.alloc(ctx, 2 * nj * gpl * 8));
+        double *du = static_cast<double *>(dad.p), *dv = du + nj * gpl;
+        hipLaunchKernelGGL(k_hyp_adapted, pix, dim3(kEnThreads), 0, ctx->stream, dt, dUp, dVp, r_Jets, Jets, (int)gpl, du, dv);
+        SFA_HIP(ctx, hipGetLastError());
+        SFA_HIP(ctx, hipMemcpyAsync(adapted_u, du, nj * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SFA_HIP(ctx, hipMemcpyAsync(adapted_v, dv, nj * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
+        SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                        // before dad is released
+    }
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;
 }

@@ -13,7 +13,14 @@
 //   <output>/accumulated/best_<sequence_start>.pgm                the rate of lowest energy (ties: the lower r; 255: none) -- the first element of the
 //                                                                 reference's sort by compareHypotheses (:1401), NOT the TRW-S result
 //
-// Out of scope (TRW-S, FLANN, GSL, OpenCV are not in this tree): the fusion of the hypotheses, EpicFlow's fill-in, removeSmallSegments, cropping and the
+// With -fuse (implies -energies) it fuses every start_jet's rates as dense_tracking does (:1588-1905): the smoothness weight of normalised frame 0
+// (sfa_dt_smoothness_weight), NMS, the pairwise MRF and TRW-S in raster order (sfa_fuse_hypotheses), and writes
+//   <output>/accumulated/<flow_format % sequence_start>.flo       the fused flow on the grid, u(Jets - 1) / xy_incr; UNKNOWN_FLOW (1e10) without a node
+//   <output>/accumulated/<...>_vis.png                            its colour coding
+//   <output>/accumulated/occlusions/frame_<sequence_start>.pgm    max_t occluded(t) of the chosen hypothesis, 0 / 255
+//   <output>/accumulated/labels_<sequence_start>.pgm              the chosen rate (255: none)
+//
+// Out of scope (FLANN, GSL, OpenCV are not in this tree): EpicFlow's fill-in and the neighbour proposals, removeSmallSegments, cropping and the
 // rescaling of flows of another size (:1131-1146; such flows are refused).
 #include <sys/stat.h>
 #include <unistd.h>
@@ -31,6 +38,7 @@
 #include <string>
 #include <vector>
 
+#include "flow_vis.h"
 #include "image.h"
 #include "ingest.h"
 #include "io.h"
@@ -42,7 +50,7 @@ using std::vector;
 
 static void usage() {
     printf("usage:\n");
-    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies\n");
+    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies -fuse\n");
     printf("    ./accumulate -decode_occlusion [occlusion .pgm / .pbm] [mask .pgm]   (the mask this program uses: median 3x3, 255 - x; 0 = occluded)\n");
     printf("\n");
     printf("Runs dense_tracking's first stage only: consistent accumulation of the jets (accumulateConsistentBatches).  cfg keys read: jet_estimation\n");
@@ -56,6 +64,11 @@ static void usage() {
     printf("(best_<start>.pgm).  Keys: acc_jet_consistency, acc_brightness_constancy, acc_gradient_constancy, acc_occlusion_penalty, acc_temporal_occ,\n");
     printf("acc_cv, acc_occlusion_threshold, acc_occlusion_fb_threshold, acc_penalty_fct_data, acc_penalty_fct_data_eps.  Refused: acc_occlusion 1,\n");
     printf("grayscale 1, raw_demosaicing 1, center / extent, Jets > 32.\n");
+    printf("\n");
+    printf("-fuse: implies -energies, then fuses all rates of each start_jet with TRW-S (raster order) into <flow_format %% start>.flo, _vis.png,\n");
+    printf("occlusions/frame_<start>.pgm and labels_<start>.pgm.  Keys: acc_beta, acc_spatial_occ, acc_traj_sim_method, acc_traj_sim_thres, acc_trws_eps,\n");
+    printf("acc_trws_max_iter, 16bit, img_norm_avg_*, img_norm_std_*.  Refused: acc_approach 1, acc_traj_sim_method 2, a width that is not a multiple\n");
+    printf("of 4, more than 16 rates.  EpicFlow's fill-in and the neighbour proposals (acc_epic_interpolation) are not run.\n");
 }
 
 // little-endian PFM (Pf, scale -1), rows bottom to top: what io.cpp's reader expects
@@ -236,7 +249,7 @@ static color_image_t *ingest_frame(ParameterList &params, sfa_ctx *ctx, const st
 static int run_energies(ParameterList &params, const string &cfg, const string &acc_dir, vector<Segment> &segs, const vector<string> &skipped,
                         const std::map<unsigned, vector<string>> &frame_files, unsigned rates, int min_fps_idx, unsigned Jets, int steps, int skip,
                         int skip_pixel, double threshold, bool discard, bool use_occ, const vector<string> &jets, const vector<int> &jet_S,
-                        const vector<int> &jet_fps, const vector<double> &jet_weight) {
+                        const vector<int> &jet_fps, const vector<double> &jet_weight, bool fuse, const string &flow_format, bool sintel) {
     sfa_energy_params ep;
     sfa_energy_params_default(&ep);                                       // setDefault (:118-165), in the types of :606-623 and :661-675
     ep.acc_jc = params.parameter<float>("acc_jet_consistency", "1.0");
@@ -250,6 +263,26 @@ static int run_energies(ParameterList &params, const string &cfg, const string &
     ep.penalty = params.parameter<int>("acc_penalty_fct_data", "1");
     ep.penalty_eps = params.parameter<double>("acc_penalty_fct_data_eps", "0.001");
     ep.skip = skip_pixel;
+    sfa_fuse_params fup;
+    sfa_fuse_params_default(&fup);                                         // setDefault (:136-152), read as at :605-625, :660-661
+    fup.acc_beta = params.parameter<double>("acc_beta", "10.0");
+    fup.acc_spatial_occ = params.parameter<double>("acc_spatial_occ", "10.0");   // setDefault's "acc_satial_occ" never reaches this key
+    fup.traj_sim_method = params.parameter<int>("acc_traj_sim_method", "1");
+    fup.traj_sim_thres = params.parameter<double>("acc_traj_sim_thres", "0.1");
+    fup.trws_eps = params.parameter<double>("acc_trws_eps", "1e-5");
+    fup.trws_max_iter = params.parameter<int>("acc_trws_max_iter", "10");
+    fup.skip = skip_pixel;
+    // the statistics the smoothness weight de-normalises with: the reference reads img_norm_* (defaults 0 / 1, :971-972), keys normalize() does not
+    // publish (it writes slow_flow_img_norm_*), so by default the weight is taken from the normalised frame itself
+    float nav[3], nsd[3];
+    for (int k = 0; k < 3; k++) {
+        nav[k] = (float)params.parameter<double>("img_norm_avg_" + std::to_string(k + 1), "0");
+        nsd[k] = (float)params.parameter<double>("img_norm_std_" + std::to_string(k + 1), "1");
+    }
+    const int hbit = params.parameter<bool>("16bit", "0") ? 1 : 0;
+    struct Fused { unsigned seq_start; int nodes, iters; double energy, bound, t_weight, t_fuse; float stage_ms[4]; };
+    vector<Fused> fused;
+    double t_fuse = 0;
     sfa_ctx *ctx = nullptr;
     if (!segs.empty() && sfa_ctx_create(0, &ctx) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; return 1; }
     double t_frames = 0, t_acc = 0, t_energy = 0, t_io = 0;
@@ -294,6 +327,16 @@ static int run_energies(ParameterList &params, const string &cfg, const string &
         vector<float> best_e(gpl, INFINITY);
         vector<unsigned char> best(gpl, 255);
         vector<const float *> cfp(fp.begin(), fp.end());
+        if (status == 0 && fuse && width % 4 != 0) {
+            // the reference indexes its stride-pitched weight image as (y * xy_incr + xy_start) * owidth + ... (:1722, 1733, 1737): exact only where
+            // stride == width
+            std::cerr << "-fuse: width " << width << " is not a multiple of 4 (the reference's smoothness-weight index reads padding)" << std::endl;
+            status = 1;
+        }
+        const size_t K = mine.size();
+        vector<double> fU, fV, fE;                                        // [K][Jets][gpl], [K][gpl]: the fusion's inputs, slot k = rate mine[k]
+        vector<unsigned long long> fO;
+        if (fuse) { fU.assign(K * Jets * gpl, 0); fV.assign(fU.size(), 0); fE.assign(K * gpl, 0); fO.assign(K * gpl, 0); }
         for (size_t k = 0; k < mine.size() && status == 0; k++) {
             Segment &s = segs[mine[k]];
             double tb = now_s();
@@ -316,15 +359,20 @@ static int run_energies(ParameterList &params, const string &cfg, const string &
             ep.weight = jet_weight.size() > (size_t)s.r ? (float)jet_weight[s.r] : (float)s.r;   // weight_jet_estimation, vector<float> (:489-495)
             vector<double> energy(gpl);
             vector<unsigned long long> occ(gpl);
-            if (sfa_hypothesis_energies(ctx, &ep, 1, s.FF, (int)Jets, width, height, stride, au.data(), av.data(), tracked.data(), cfp.data(),
-                                        flows ? minf.fu.data() : nullptr, flows ? minf.fv.data() : nullptr, flows ? minf.bu.data() : nullptr,
-                                        flows ? minf.bv.data() : nullptr, energy.data(), occ.data()) != SFA_OK) {
+            if (sfa_hypothesis_energies_ex(ctx, &ep, 1, s.FF, (int)Jets, width, height, stride, au.data(), av.data(), tracked.data(), cfp.data(),
+                                           flows ? minf.fu.data() : nullptr, flows ? minf.fv.data() : nullptr, flows ? minf.bu.data() : nullptr,
+                                           flows ? minf.bv.data() : nullptr, energy.data(), occ.data(), fuse ? fU.data() + k * Jets * gpl : nullptr,
+                                           fuse ? fV.data() + k * Jets * gpl : nullptr) != SFA_OK) {
                 std::cerr << sfa_last_error(ctx) << std::endl;
                 status = 1;
                 break;
             }
             double td = now_s();
             t_energy += td - tc;
+            if (fuse) {
+                std::copy(energy.begin(), energy.end(), fE.begin() + k * gpl);
+                std::copy(occ.begin(), occ.end(), fO.begin() + k * gpl);
+            }
             image_t *u = image_new(gw, gh), *v = image_new(gw, gh);
             vector<unsigned char> tp(gpl), oc(gpl);
             vector<float> ef(gpl);
@@ -353,6 +401,55 @@ static int run_energies(ParameterList &params, const string &cfg, const string &
             std::cout << "rate " << s.r << ", start " << s.seq_start << ": " << s.created << " trajectory hypotheses generated! (" << s.rejected
                       << " rejected)" << std::endl;                                               // :1353
         }
+        if (status == 0 && fuse) {
+            // ---- the fusion of all rates (:1588-1905): the smoothness weight of normalised frame 0 (:969-981), then NMS, pairwise terms, TRW-S
+            const double te = now_s();
+            Fused fu{};
+            fu.seq_start = seq_start;
+            vector<float> weight((size_t)width * height);
+            if (sfa_dt_smoothness_weight(ctx, width, height, stride, fp[0], 5.0f, nav, nsd, hbit, weight.data()) != SFA_OK) {
+                std::cerr << sfa_last_error(ctx) << std::endl;
+                status = 1;
+            }
+            const double tf = now_s();
+            vector<int> slot(gpl);
+            vector<double> flu(gpl), flv(gpl);
+            vector<unsigned char> oc(gpl);
+            if (status == 0 && sfa_fuse_hypotheses(ctx, &fup, 1, (int)K, (int)Jets, width, height, fU.data(), fV.data(), fE.data(), fO.data(), weight.data(),
+                                                   slot.data(), flu.data(), flv.data(), oc.data(), &fu.energy, &fu.bound, &fu.iters, fu.stage_ms) != SFA_OK) {
+                std::cerr << sfa_last_error(ctx) << std::endl;
+                status = 1;
+            }
+            const double tg = now_s();
+            fu.t_weight = tf - te;
+            fu.t_fuse = tg - tf;
+            t_fuse += tg - te;
+            if (status == 0) {
+                image_t *u = image_new(gw, gh), *v = image_new(gw, gh);
+                vector<unsigned char> lp(gpl), op(gpl);
+                for (int y = 0; y < gh; y++)
+                    for (int x = 0; x < gw; x++) {
+                        const size_t i = (size_t)y * gw + x;
+                        u->data[(size_t)y * u->stride + x] = (float)flu[i];   // writeFlowMiddlebury's fp32 (utils.cpp:333); 1e10 without a node
+                        v->data[(size_t)y * v->stride + x] = (float)flv[i];
+                        lp[i] = slot[i] < 0 ? 255 : (unsigned char)segs[mine[slot[i]]].r;
+                        op[i] = oc[i] ? 255 : 0;                                // convertTo(CV_8UC1, 255) (:1893)
+                        fu.nodes += slot[i] >= 0;
+                    }
+                const string base = acc_dir + (sintel ? fmt2(flow_format, (int)seq_start, 0) : fmt1(flow_format, (int)seq_start));   // :1895-1898
+                mkdirs(acc_dir + "occlusions/");
+                if (writeFlowFile((base + ".flo").c_str(), u, v) != 0 || !png_write((base + "_vis.png").c_str(), flowColorImg(u, v, 0)) ||
+                    !write_pgm8(acc_dir + "occlusions/frame_" + std::to_string(seq_start) + ".pgm", gw, gh, op.data(), gw) ||
+                    !write_pgm8(acc_dir + "labels_" + std::to_string(seq_start) + ".pgm", gw, gh, lp.data(), gw)) {
+                    std::cerr << "cannot write the fused outputs of start " << seq_start << " under " << acc_dir << std::endl;
+                    status = 1;
+                }
+                image_delete(u); image_delete(v);
+                std::cout << "start " << seq_start << ": fused " << K << " rate(s) over " << fu.nodes << " nodes, energy " << fu.energy << ", lower bound "
+                          << fu.bound << ", " << fu.iters << " TRW-S iteration(s)" << std::endl;
+                fused.push_back(fu);
+            }
+        }
         for (color_image_t *c : fr) color_image_delete(c);
         if (status == 0 && !write_pgm8(acc_dir + "best_" + std::to_string(seq_start) + ".pgm", gw, gh, best.data(), gw)) {
             std::cerr << "cannot write " << acc_dir << "best_" << seq_start << ".pgm" << std::endl;
@@ -362,6 +459,7 @@ static int run_energies(ParameterList &params, const string &cfg, const string &
     if (ctx) sfa_ctx_destroy(ctx);
     if (status) return status;
     std::ofstream js((acc_dir + "run.json").c_str());
+    js.precision(17);
     js << "{\n  \"cfg\": \"" << cfg << "\",\n  \"energies\": true, \"Jets\": " << Jets << ", \"steps\": " << steps << ", \"skip\": " << skip
        << ", \"acc_skip_pixel\": " << skip_pixel << ", \"width\": " << width << ", \"height\": " << height << ",\n  \"rates\": [";
     for (unsigned r = 0; r < rates; r++)
@@ -374,8 +472,21 @@ static int run_energies(ParameterList &params, const string &cfg, const string &
            << ", \"flo\": \"" << segs[i].out_flo << "\"}";
     js << "],\n  \"skipped\": [";
     for (size_t i = 0; i < skipped.size(); i++) js << (i ? ", " : "") << "\"" << skipped[i] << "\"";
-    js << "],\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc << ", \"energy_call\": " << t_energy << ", \"write\": " << t_io
-       << ", \"total\": " << now_s() - t0 << "}\n}\n";
+    js << "]";
+    if (fuse) {
+        js << ",\n  \"fused\": true, \"epic_interpolation\": false, \"neighbour_proposals\": false, \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": "
+           << fup.acc_spatial_occ << ", \"acc_traj_sim_method\": " << fup.traj_sim_method << ", \"acc_traj_sim_thres\": " << fup.traj_sim_thres
+           << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter << ",\n  \"fusion\": [";
+        for (size_t i = 0; i < fused.size(); i++)
+            js << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << fused[i].seq_start << ", \"nodes\": " << fused[i].nodes << ", \"energy\": " << fused[i].energy
+               << ", \"lower_bound\": " << fused[i].bound << ", \"iterations\": " << fused[i].iters << ", \"weight_s\": " << fused[i].t_weight
+               << ", \"fuse_call_s\": " << fused[i].t_fuse << ", \"kernels_ms\": {\"labels\": " << fused[i].stage_ms[0] << ", \"pairwise\": "
+               << fused[i].stage_ms[1] << ", \"trws\": " << fused[i].stage_ms[2] << ", \"output\": " << fused[i].stage_ms[3] << "}}";
+        js << "]";
+    }
+    js << ",\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc << ", \"energy_call\": " << t_energy << ", \"write\": " << t_io;
+    if (fuse) js << ", \"fuse\": " << t_fuse;
+    js << ", \"total\": " << now_s() - t0 << "}\n}\n";
     std::cout << "wrote the energies of " << segs.size() << " segment(s) to " << acc_dir << std::endl;
     return js.good() ? 0 : 1;
 }
@@ -395,13 +506,14 @@ int main(int argc, char **argv) {
     if (!file_exists(cfg)) { usage(); return 1; }
     printf("using parameters %s\n", cfg.c_str());
     unsigned selected = 0, selected_end = 0;
-    bool resume = false, energies = false;
+    bool resume = false, energies = false, fuse = false;
     for (int i = 2; i < argc; i++) {                                     // :449-476
         const char *a = argv[i];
         if (a[0] != '-') continue;
         if (!strcmp(a, "-h") || !strcmp(a, "-help")) usage();
         else if (!strcmp(a, "-resume")) resume = true;
         else if (!strcmp(a, "-energies")) energies = true;
+        else if (!strcmp(a, "-fuse")) fuse = energies = true;
         else if (!strcmp(a, "-select") && i + 1 < argc) { selected = (unsigned)atoi(argv[++i]); selected_end = selected + 1; }
         else { fprintf(stderr, "unknown argument %s\n", a); usage(); return 1; }
     }
@@ -460,6 +572,17 @@ int main(int argc, char **argv) {
         if (refused) { std::cerr << "-energies: " << refused << " is not supported" << std::endl; return 1; }
         if (params.file.empty()) { std::cerr << "-energies: `file` (the frames) missing from " << cfg << std::endl; return 1; }
     }
+    if (fuse) {
+        const int method = params.parameter<int>("acc_traj_sim_method", "1");
+        const char *refused = params.parameter<int>("acc_approach", "0") == 1 ? "acc_approach 1 (BP)"
+                              : method == 2 ? "acc_traj_sim_method 2 (FINAL reads flow_y[Jets], past the adapted array)"
+                              : (method != 0 && method != 1) ? "an acc_traj_sim_method other than 0 or 1"
+                              : rates > 16 ? "more than 16 rates" : nullptr;
+        if (refused) { std::cerr << "-fuse: " << refused << " is not supported" << std::endl; return 1; }
+        if (params.parameter<bool>("acc_epic_interpolation", "1"))
+            std::cout << "-fuse: acc_epic_interpolation 1, but EpicFlow's fill-in and the neighbour proposals are not run (pixels without a hypothesis "
+                         "stay UNKNOWN_FLOW)" << std::endl;
+    }
     if (selected_end == 0) selected_end = (unsigned)ref_fps_F;           // :722-723
     unsigned sequence_start = params.sequence_start;
     if (sintel && !subframes) sequence_start *= 1000;                    // :716-717
@@ -482,7 +605,10 @@ int main(int argc, char **argv) {
     vector<string> skipped;
     for (unsigned start_jet = selected; start_jet < selected_end; start_jet++) {
         const unsigned seq_start = sequence_start + start_jet * Jets * steps * skip;   // :735
-        if (energies) {                                                  // with the energies a start_jet is done as a whole: all its rates are compared
+        if (fuse) {                                                      // the fused flow is the start_jet's product
+            const string flo = acc_dir + (sintel ? fmt2(flow_format, (int)seq_start, 0) : fmt1(flow_format, (int)seq_start)) + ".flo";
+            if (file_exists(flo)) { std::cout << "Flow file " << flo << " already exists!" << std::endl; skipped.push_back(flo); continue; }
+        } else if (energies) {                                           // with the energies a start_jet is done as a whole: all its rates are compared
             const string best = acc_dir + "best_" + std::to_string(seq_start) + ".pgm";
             if (file_exists(best)) { std::cout << "Energy file " << best << " already exists!" << std::endl; skipped.push_back(best); continue; }
         }
@@ -543,7 +669,7 @@ int main(int argc, char **argv) {
     mkdirs(acc_dir);
     for (unsigned r = 0; r < rates; r++) mkdirs(acc_dir + std::to_string(r) + "/");
     if (energies) return run_energies(params, cfg, acc_dir, segs, skipped, frame_files, rates, min_fps_idx, Jets, steps, skip, skip_pixel, threshold, discard,
-                                      use_occ, jets, jet_S, jet_fps, jet_weight);
+                                      use_occ, jets, jet_S, jet_fps, jet_weight, fuse, flow_format, sintel);
 
     sfa_ctx *ctx = nullptr;
     if (!segs.empty() && sfa_ctx_create(0, &ctx) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; return 1; }
