@@ -7,15 +7,18 @@ stacks, data-term assembly, SOR solves, flow updates) of one resident batch of s
 config 2: 1024x436, S=2 (3 frames), 5 pyramid levels, 5 outer x 1 inner x 30 SOR sweeps per level.  Inputs are
 uploaded to HBM before the timed region.  value = (sum over all ranks and SOR solves of w*h*K) / wall time / 1e6.
 
-  python bench.py --gpus N --steps K --warmup W [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--full]
 N > 1 runs one rank per GPU over RCCL: either the caller starts the ranks (`python -m torch.distributed.run ... bench.py
 --gpus N ...`: RANK / WORLD_SIZE are in the environment) or, when they are not, bench.py starts them itself as a CHILD
 torch.distributed.run process before anything touches the GPU and relays its output and exit code (launch_ranks).  Frame
 windows shard across ranks with no data-path collective (weak scaling); the only exchange is a gather of per-rank timings.
 
 The JSON line also carries `roofline` (SOR solve kernel: algorithmic bytes / HIP-event duration over the timed
-region) and, on rank 0 at N=1, `cpu_baseline` (the reference's own sor_coupled from oracle/_ref, or the oracle port,
-timed on one host core over a bounded sample).
+region).  A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  `--full` adds the
+sections that take runs of their own -- the SOR-only launches, the strong-scaling configs 4 and 5, the one-window latency
+and the labelled red-black mode, the cfg-schedule sample, the HBM triad -- and, on rank 0 at N=1, `cpu_baseline` (the
+reference's own sor_coupled from oracle/_ref, or the oracle port, timed on one host core over a bounded sample) with the
+`parity` of the timed job against the oracle.
 """
 import argparse
 import json
@@ -203,6 +206,16 @@ def synth_window(seed, w=W, h=H, n=3):
             f[c, :, :w] = np.round(v).astype(np.float32)
         frames.append(f)
     return frames
+
+
+def synth_windows(seeds):
+    """[synth_window(s) for s in seeds] on up to 16 host threads: the 128 windows of the timed job take half a minute on one core, and numpy and
+    scipy release the GIL in the array work.  Every window draws from its own generator, so the frames are the serial loop's bit for bit."""
+    from concurrent.futures import ThreadPoolExecutor
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    threads = max(1, min(16, cpus // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))))      # the ranks of a node share its cores
+    with ThreadPoolExecutor(threads) as ex:
+        return list(ex.map(synth_window, seeds))
 
 
 def bench_params():
@@ -711,17 +724,22 @@ def main():
                     "(the reference drives its windows from OpenMP threads, slow_flow.cpp:706).  Default since round 5: ONE group of 128 windows (a job holds up to 128 "
                     "since the window set became two mask words): the solver's launches then fill whole rounds of the 256 CUs at every pyramid level -- 115.8 ms per "
                     "step against 117.4-117.9 for two groups of 64 on two streams, same box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--path-only", action="store_true", help="skip the SOR-only section (used for the PMC passes: every SOR dispatch then belongs to the path)")
-    ap.add_argument("--bench-only", action="store_true", help="--path-only and none of the reported extras either (one-window latency, labelled modes, cfg-schedule sample, triad): "
-                                                              "every kernel launch of the process is a launch of the timed workload (the kernel-stats pass of profiles/collect.sh)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the SOR-only section, the strong-scaling sections (configs 4 "
+                    "and 5), the one-window latency and labelled modes, the cfg-schedule sample, the HBM triad, and at N = 1 the CPU baseline with the parity of the "
+                    "timed job against the oracle.  The four options below narrow it; a plain run is --full --bench-only --no-cpu-baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no parity check")
+    ap.add_argument("--path-only", action="store_true", help="with --full: skip the SOR-only and strong-scaling sections (used for the PMC passes: every SOR dispatch then belongs to the path)")
+    ap.add_argument("--bench-only", action="store_true", help="with --full: --path-only and none of the reported extras either (one-window latency, labelled modes, cfg-schedule "
+                                                              "sample, triad): every kernel launch of the process is a launch of the timed workload")
     ap.add_argument("--selftest-launch", action="store_true", help="CPU rehearsal of the multi-rank launch and exchange (gloo); prints a selftest line, never a result")
-    ap.add_argument("--no-strong", action="store_true", help="skip the config-4 strong-scaling section (128 windows in total under the cfg schedule)")
+    ap.add_argument("--no-strong", action="store_true", help="with --full: skip the strong-scaling sections (configs 4 and 5)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (the flow fields of a fixed, "
                     "seeded sample of %d windows and their last change (mean |du|, |dv|), as a caller of the job receives them) to DIR/<name>.npy; rank 0 only" % DUMP_WINDOWS)
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                                 # a plain run: the timed workload and nothing beside it
+        args.bench_only = args.no_cpu_baseline = True
     if args.bench_only:
         args.path_only = True
 
@@ -767,7 +785,7 @@ def main():
     ctx = ctxs[0]
     p = bench_params()
     # one normalisation for the whole sequence, as the driver does (slow_flow.cpp:673)
-    windows = [synth_window(1000 * rank + b) for b in range(B)]
+    windows = synth_windows([1000 * rank + b for b in range(B)])
     allf = [f for wdw in windows for f in wdw]
     # parity of the timed workload (rank 0, N = 1, with the CPU leg): the windows PARITY_WINDOWS of the timed job are refined by the oracle from the same
     # normalised frames and statistics after the bench, and normalize() itself is checked against a numpy evaluation of the reference's statistics on the raw frames
@@ -1022,7 +1040,7 @@ def main():
                              "mean_flow_px": [round(float(np.mean([gpu_flows[b][0].mean() for b in par_idx])), 4), round(float(np.mean([gpu_flows[b][1].mean() for b in par_idx])), 4)],
                              "normalisation": norm_check}
         else:
-            out["parity"] = None                                  # (N > 1 or --no-cpu-baseline: no CPU leg in this run; tests/test_gpu_parity.py::test_bench_job_128_windows_against_the_oracle)
+            out["parity"] = None                                  # (N > 1, a plain run or --no-cpu-baseline: no CPU leg in this run; tests/test_gpu_parity.py::test_bench_job_128_windows_against_the_oracle)
         print(json.dumps(out), flush=True)
     for job in jobs:
         job.close()

@@ -47,6 +47,16 @@ def test_world_size_mismatch_is_refused():
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stdout + r.stderr)
 
 
+def test_windows_on_threads_are_the_serial_windows():
+    """the timed job's inputs are synthesised on several host threads: same windows, same order, same bits as one synth_window call after the other"""
+    import numpy as np
+    import bench
+    seeds = [1000, 1001, 1063, 1]
+    for a, b in zip(bench.synth_windows(seeds), [bench.synth_window(s) for s in seeds]):
+        assert len(a) == len(b) == 3
+        assert all(x.dtype == y.dtype and np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(a, b))
+
+
 import pytest
 
 
@@ -83,7 +93,7 @@ def test_two_ranks_for_real_on_one_gpu():
     """the whole N = 2 path of the real bench -- child launch, two ranks with two contexts each, the timed region, max over ranks, the gather of the
     per-window timings, rank 0's line -- with both ranks on the one GPU of this box and the exchange over gloo (SFA_BENCH_BACKEND=gloo: a rehearsal
     switch; the line says so and is never a result).  Two processes on the card: within the box's limit."""
-    out = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"], {"SFA_BENCH_BACKEND": "gloo"})
+    out = _run(["--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline"], {"SFA_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["steps"] == 1
     assert out["config"]["frame_windows_per_gpu"] == 8
     assert out["seconds_per_window"]["n"] == 16                         # both ranks' windows arrived
@@ -110,7 +120,7 @@ def test_one_rank_over_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SFA_BENCH_BACKEND")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["TORCH_DISTRIBUTED_DEBUG"] = "DETAIL"                           # every collective is logged and checked
-    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"], bench.free_port())
+    cmd = bench.launch_command(1, ["--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline"], bench.free_port())
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -125,6 +135,18 @@ def test_one_rank_over_rccl():
         st = out[key]
         assert "error" not in st, st
         assert st["windows_all_ranks"] == total and len(st["seconds_per_rank"]) == 1 and st["seconds"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_timed_workload_alone():
+    """without --full the bench sets up, warms up, times the steps and prints the headline line: none of the sections that take runs of their own"""
+    out = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "8"])
+    assert out["n_gpus"] == 1 and out["steps"] == 1 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["unit"] == "Mpix*solver-iters/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    for key in ("cpu_baseline", "config4_strong", "config5_strong", "labelled_modes", "cfg_schedule_with_thresholds"):
+        assert key not in out, key
+    assert out["parity"] is None and out["latency_one_window_ms"] is None and out["roofline"]["measured_triad_gbs"] is None
+    assert not any(k.startswith("sor_1024x436") for k in out["roofline"])
 
 
 @pytest.mark.gpu
