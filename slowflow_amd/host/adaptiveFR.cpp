@@ -10,8 +10,6 @@
 // adaptiveFR/tmp/matches_<a>_<b>.dat and edges_<n>.dat, a second run refines.  The flow of a sample whose .flo exists is read back, not recomputed,
 // unless -overwrite is given; it counts toward the quantile either way.
 #include <dirent.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cmath>
@@ -31,6 +29,7 @@
 #include "io.h"
 #include "parameter_list.h"
 #include "png.h"
+#include "util.h"
 
 using std::string;
 
@@ -41,18 +40,6 @@ static void usage() {
            "-quantil [q (0.9)] -append [file] -overwrite -sintel -subframes -raw -threads\n");
     printf("\n");
 }
-
-static bool file_exists(const string &f) { return access(f.c_str(), F_OK) != -1; }
-static bool is_dir(const string &f) { struct stat st; return stat(f.c_str(), &st) == 0 && S_ISDIR(st.st_mode); }
-static void mkdirs(const string &path) {
-    string cur;
-    for (size_t i = 0; i <= path.size(); i++) {
-        if ((i == path.size() || path[i] == '/') && !cur.empty()) mkdir(cur.c_str(), 0777);
-        if (i < path.size()) cur.push_back(path[i]);
-    }
-}
-static string fmt1(const string &format, int a) { char b[1024]; snprintf(b, sizeof b, format.c_str(), a); return b; }
-static string fmt2(const string &format, int a, int c) { char b[1024]; snprintf(b, sizeof b, format.c_str(), a, c); return b; }
 
 // 8-bit RGB planes (values 0..255) -> PNG
 static bool write_rgb8(const string &file, const color_image_t *im) {
@@ -191,31 +178,17 @@ int main(int argc, char **argv) {
             smp->first = (int)first;
             bool ok = true;
             for (int f = 0; f < all_frames && ok; f++) {
-                string name;                                                                // :336-352
-                if (!sintel) name = fmt1(S->path + format, (int)first + f * skip);
-                else {
-                    int sintel_frame = (int)first / 1000, hfr = f * skip + (int)(first % 1000);
-                    while (hfr < 0) { sintel_frame--; hfr += 42; }
-                    while (hfr > 41) { sintel_frame++; hfr -= 42; }
-                    name = fmt2(S->path + format, sintel_frame, hfr);
-                }
+                const string name = sequence_frame_name(S->path + format, (int)first, f * skip, sintel);   // :336-352
                 if (!file_exists(name)) { std::cerr << "Could not find " << name << "!" << std::endl; ok = false; break; }
                 std::cout << "Reading " << name << "..." << std::endl;
                 int maxval = 255;
-                color_image_t *img = color_image_load(name.c_str(), &maxval);
-                if (!img) { std::cerr << "cannot read frame " << name << " (PNG, TIFF or binary PPM/PGM/PFM expected)" << std::endl; ok = false; break; }
+                string error;                                                               // raw: :376-418, bilinear demosaicing of the mosaic,
+                color_image_t *img = load_frame(name, raw, 0, 1, 0, &maxval, &error);       // raw_red_loc default "1,0" (:326)
+                if (!img) { std::cerr << error << std::endl; ok = false; break; }
                 // The reference takes norm = 1/255 for a single-channel 16-bit image (img.type() == CV_16UC1) and keeps it for every later frame;
                 // 16-bit colour frames would be saturated at norm 1 there.  Here every 16-bit frame sets it: the loader replicates grey into 3 planes.
                 if (maxval > 255) is16 = true;
                 const float norm = is16 ? 1.0f / 255 : 1.0f;
-                if (raw) {                                                                  // :376-418, bilinear demosaicing of the mosaic
-                    image_t mosaic = {img->width, img->height, img->stride, img->c1};
-                    color_image_t *rgb = color_image_new(img->width, img->height);
-                    color_image_erase(rgb);
-                    bayer2rgbGR(&mosaic, rgb, 1, 0);                                        // raw_red_loc default "1,0" (:326)
-                    color_image_delete(img);
-                    img = rgb;
-                }
                 if (scale != 1) {                                                           // :431-434, on the GPU
                     color_image_t *small = color_image_rescale(ctx, img, (float)scale);
                     color_image_delete(img);

@@ -1,6 +1,7 @@
 // ingest.cpp -- see ingest.h.  Restated from the reference's driver utilities; those live in utils.cpp, which needs OpenCV and
 // cannot be built here: parity unpinned (tests/test_host.py checks the defining properties).
 #include "ingest.h"
+#include "io.h"
 
 #include <cmath>
 #include <cstring>
@@ -96,6 +97,19 @@ void bayer2rgb_cv8u(const image_t *src, color_image_t *dst, int red_x, int red_y
         copy(y, W - 1, y, W - 2);
     }
     for (int x = 0; x < W; x++) { copy(0, x, 1, x); copy(H - 1, x, H - 2, x); }
+}
+
+color_image_t *load_frame(const std::string &file, bool raw, int demosaicing, int red_x, int red_y, int *maxval, std::string *error) {
+    color_image_t *img = color_image_load(file.c_str(), maxval);
+    if (!img) { *error = "cannot read frame " + file + " (PNG, TIFF or binary PPM/PGM/PFM expected)"; return nullptr; }
+    if (!raw) return img;
+    image_t mosaic = {img->width, img->height, img->stride, img->c1};
+    color_image_t *rgb = color_image_new(img->width, img->height);
+    color_image_erase(rgb);
+    if (demosaicing == 2) bayer2rgb_cv8u(&mosaic, rgb, red_x, red_y);
+    else bayer2rgbGR(&mosaic, rgb, red_x, red_y);
+    color_image_delete(img);
+    return rgb;
 }
 
 color_image_t *color_image_crop(const color_image_t *img, int cx, int cy, int ex, int ey) {

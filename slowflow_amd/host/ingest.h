@@ -4,6 +4,8 @@
 #ifndef SLOWFLOW_AMD_HOST_INGEST_H
 #define SLOWFLOW_AMD_HOST_INGEST_H
 
+#include <string>
+
 #include "../../include/slowflow_amd.h"
 #include "image.h"
 
@@ -18,6 +20,10 @@ void bayer2rgbGR(const image_t *src, color_image_t *dst, int red_x, int red_y);
  * (4 diagonals + 2) >> 2, at a green site each colour = (its 2 neighbours + 1) >> 1; the outermost rows and columns repeat their inner neighbours.
  * OpenCV is not in this image: the arithmetic is restated from its documented bilinear Bayer conversion, parity unpinned.  dst: R, G, B planes, 0..255 */
 void bayer2rgb_cv8u(const image_t *src, color_image_t *dst, int red_x, int red_y);
+/* a frame file decoded (color_image_load; *maxval as it sets it) and, where `raw`, demosaiced from its grey mosaic whose first red pixel sits at
+ * (red_x, red_y): demosaicing 2 is bayer2rgb_cv8u, any other value bayer2rgbGR.  NULL on failure, with the message in *error.  No shared
+ * state and no printing of its own: the driver's decoding tasks call it in parallel */
+color_image_t *load_frame(const std::string &file, bool raw, int demosaicing, int red_x, int red_y, int *maxval, std::string *error);
 /* img.rowRange / colRange of slow_flow.cpp:543-546; returns a new image (caller frees) */
 color_image_t *color_image_crop(const color_image_t *img, int center_x, int center_y, int extent_x, int extent_y);
 /* slow_flow.cpp:550-553: GaussianBlur(sigma = 1/sqrt(2*scale), BORDER_REPLICATE) then resize(Size(0,0), scale, scale,

@@ -147,3 +147,41 @@ int writePGM(const char *filename, const image_t *img, float offset, float scale
         }
     return fclose(f) == 0 ? 0 : -1;
 }
+
+bool read_pnm8(const std::string &file, int &w, int &h, std::vector<unsigned char> &px) {
+    FILE *f = fopen(file.c_str(), "rb");
+    if (!f) return false;
+    std::string magic, sw, sh, smax;
+    bool ok = next_token(f, magic) && (magic == "P5" || magic == "P4") && next_token(f, sw) && next_token(f, sh) && (magic == "P4" || next_token(f, smax));
+    if (ok) { w = atoi(sw.c_str()); h = atoi(sh.c_str()); ok = w > 0 && h > 0 && w <= 65535 && h <= 65535 && (magic == "P4" || atoi(smax.c_str()) == 255); }
+    if (ok) {
+        px.assign((size_t)w * h, 0);
+        if (magic == "P5") ok = fread(px.data(), 1, px.size(), f) == px.size();
+        else {
+            const size_t rb = (size_t)(w + 7) / 8;
+            std::vector<unsigned char> row(rb);
+            for (int y = 0; ok && y < h; y++) {
+                ok = fread(row.data(), 1, rb, f) == rb;
+                for (int x = 0; ok && x < w; x++) px[(size_t)y * w + x] = ((row[x >> 3] >> (7 - (x & 7))) & 1) ? 0 : 255;
+            }
+        }
+    }
+    fclose(f);
+    return ok;
+}
+
+bool write_pgm8(const std::string &file, int w, int h, const unsigned char *px, int stride) {
+    FILE *f = fopen(file.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "P5\n%d %d\n255\n", w, h);
+    for (int y = 0; y < h; y++) fwrite(px + (size_t)y * stride, 1, w, f);
+    return fclose(f) == 0;
+}
+
+bool write_pfm(const std::string &file, int w, int h, const float *px) {
+    FILE *f = fopen(file.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "Pf\n%d %d\n-1.0\n", w, h);
+    for (int y = h - 1; y >= 0; y--) fwrite(px + (size_t)y * w, sizeof(float), (size_t)w, f);
+    return fclose(f) == 0;
+}

@@ -13,7 +13,6 @@
 // New, additive keys: gpus (default: all visible; gpu_oversubscribe 1 lets it exceed them: a rehearsal of the multi-GPU path), gpu_batch (windows refined in lockstep per job, default 32), gpu_streams
 // (default 2), gpu_device (first device, default 0), io_threads (decode / output pool, default min(16, cores)),
 // adaptive_fr_file (default: adaptiveFR.dat next to the executable, the reference's SOURCE_PATH).
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <atomic>
@@ -37,6 +36,7 @@
 #include "io.h"
 #include "parameter_list.h"
 #include "shard.h"
+#include "util.h"
 #include "variational_mt.h"
 
 using std::string;
@@ -64,18 +64,6 @@ static void setDefault(ParameterList &p) {        // slow_flow.cpp:64-128
     for (auto &e : kv) p.insert(e[0], e[1], true);
 }
 
-static bool file_exists(const string &f) { return access(f.c_str(), F_OK) != -1; }
-static void mkdirs(const string &path) {
-    string cur;
-    for (size_t i = 0; i <= path.size(); i++) {
-        if (i == path.size() || path[i] == '/') {
-            if (!cur.empty()) mkdir(cur.c_str(), 0777);
-        }
-        if (i < path.size()) cur.push_back(path[i]);
-    }
-}
-static string fmt1(const string &format, int a) { char b[1024]; snprintf(b, sizeof b, format.c_str(), a); return b; }
-static string fmt2(const string &format, int a, int c) { char b[1024]; snprintf(b, sizeof b, format.c_str(), a, c); return b; }
 static string exe_dir() {
     char buf[4096];
     const ssize_t n = readlink("/proc/self/exe", buf, sizeof buf - 1);
@@ -126,6 +114,7 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     const auto t_begin = std::chrono::steady_clock::now();
     const bool raw = params.exists("raw") && params.parameter<bool>("raw");
     const std::vector<int> red_loc = params.splitParameter<int>("raw_red_loc", "0,0");   // :439
+    const int red_x = red_loc.size() > 0 ? red_loc[0] : 0, red_y = red_loc.size() > 1 ? red_loc[1] : 0;
     const int demosaicing = params.parameter<int>("raw_demosaicing", "0");
     const float scale = params.parameter<float>("scale", "1.0");
     const int steps = params.parameter<int>("slow_flow_S") - 1, ref = steps;         // :208-209
@@ -344,13 +333,7 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     //      io pool, one frame per task ----------------------------------------------------------------------------------------------
     std::vector<string> names(frames);
     for (unsigned f = start_f; f < end_f; f++) {
-        if (!sintel) names[f] = fmt1(sequence_path + format, (int)start - ref * skip + (int)f * skip);
-        else {
-            int sintel_frame = start / 1000, hfr = (int)f * skip - ref * skip + (int)(start % 1000);
-            while (hfr < 0) { sintel_frame--; hfr += 42; }
-            while (hfr > 41) { sintel_frame++; hfr -= 42; }
-            names[f] = fmt2(sequence_path + format, sintel_frame, hfr);
-        }
+        names[f] = sequence_frame_name(sequence_path + format, (int)start, (int)f * skip - ref * skip, sintel);
         std::cout << "Reading " << names[f] << "..." << std::endl;
     }
     const bool preprocess = !params.exists("raw") || params.parameter<float>("raw_weight", "1.0") == 1.0f;   // :531
@@ -362,18 +345,9 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
         for (unsigned f = start_f; f < end_f; f++)
             pool.submit([&, f] {
                 int maxval = 255;
-                color_image_t *img = color_image_load(names[f].c_str(), &maxval);
-                if (!img) { std::lock_guard<std::mutex> l(err_mu); if (load_error.empty()) load_error = "cannot read frame " + names[f] + " (PNG, TIFF or binary PPM/PGM/PFM expected)"; return; }
-                if (raw) {                                                           // demosaicing (:482-527): the mosaic is the grey image
-                    image_t mosaic = {img->width, img->height, img->stride, img->c1};
-                    color_image_t *rgb = color_image_new(img->width, img->height);
-                    color_image_erase(rgb);
-                    const int rx = red_loc.size() > 0 ? red_loc[0] : 0, ry = red_loc.size() > 1 ? red_loc[1] : 0;
-                    if (demosaicing == 2) bayer2rgb_cv8u(&mosaic, rgb, rx, ry);          // :502-520
-                    else bayer2rgbGR(&mosaic, rgb, rx, ry);                             // :488-491
-                    color_image_delete(img);
-                    img = rgb;
-                }
+                string error;                                                        // demosaicing (:482-527): the mosaic is the grey image
+                color_image_t *img = load_frame(names[f], raw, demosaicing, red_x, red_y, &maxval, &error);
+                if (!img) { std::lock_guard<std::mutex> l(err_mu); if (load_error.empty()) load_error = error; return; }
                 if (preprocess && (extent.x > 0 || extent.y > 0)) {                  // use only a part of the images (:533-536)
                     color_image_t *part = color_image_crop(img, center.x, center.y, extent.x, extent.y);
                     if (!part) {
@@ -416,21 +390,14 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     if (seq[start_f]->width != width || seq[start_f]->height != height) { std::cerr << "frames of different sizes" << std::endl; abort_ingest(); return 3; }
     color_image_t *channel_weights = color_image_new(width, height);                 // :597-598 (all ones without raw weighting)
     for (size_t i = 0; i < (size_t)3 * channel_weights->stride * height; i++) channel_weights->c1[i] = 1.0f;
-    if (raw) rawWeighting(channel_weights, red_loc.size() > 0 ? red_loc[0] : 0, red_loc.size() > 1 ? red_loc[1] : 0, params.parameter<float>("raw_weight", "1.0"));   // :599-600
+    if (raw) rawWeighting(channel_weights, red_x, red_y, params.parameter<float>("raw_weight", "1.0"));   // :599-600
 
     // ---- ground truth, if the cfg names it (:603-661): .flo -> crop -> nearest resize * scale -> gt/flow_%05i.{png,flo} --------
     std::vector<image_t **> gt(params.Jets, nullptr);
     if (!params.file_gt.empty()) {
         mkdirs(params.output + "gt/");
         for (unsigned j = start_j; j < end_j; j++) {
-            string path;
-            if (!sintel) path = fmt1(params.file_gt, (int)start + (int)j * steps);
-            else {
-                int sintel_frame = start / 1000, hfr = (int)j * steps + (int)(start % 1000);
-                while (hfr < 0) { sintel_frame--; hfr += 42; }
-                while (hfr > 41) { sintel_frame++; hfr -= 42; }
-                path = fmt2(params.file_gt, sintel_frame, hfr);
-            }
+            const string path = sequence_frame_name(params.file_gt, (int)start, (int)j * steps, sintel);
             std::cout << path << std::endl;
             if (!file_exists(path)) continue;
             image_t **g = readFlowFile(path.c_str());

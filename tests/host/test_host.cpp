@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -17,6 +18,7 @@
 #include "png.h"
 #include "tiff.h"
 #include "shard.h"
+#include "util.h"
 #include "variational_mt.h"
 
 static int fails = 0;
@@ -406,6 +408,71 @@ int main(int argc, char **argv) {
                 std::ofstream ob((tmp + "/" + name + ".bin").c_str(), std::ios::binary);
                 ob.write(reinterpret_cast<const char *>(t.samples.data()), (std::streamsize)(t.samples.size() * sizeof(uint16_t)));
             }
+        }
+    }
+    // ---- util.h: sequence frame names and the repeated cfg keys; io.h: 8-bit PGM / PBM and PFM ----------------------------------------------
+    {
+        CHECK(sequence_frame_name("f_%03i.png", 10, 5, false) == "f_015.png");
+        CHECK(sequence_frame_name("f_%03i.png", 10, -4, false) == "f_006.png");
+        CHECK(sequence_frame_name("f_%03i.png", 3040, 5, false) == "f_3045.png");          // no wrap without sintel
+        const std::string sf = "s%d/f_%02d.png";                                          // Sintel: scene * 1000 + frame, 42 frames a scene
+        CHECK(sequence_frame_name(sf, 3040, 0, true) == "s3/f_40.png");
+        CHECK(sequence_frame_name(sf, 3000, 41, true) == "s3/f_41.png");
+        CHECK(sequence_frame_name(sf, 3000, 42, true) == "s4/f_00.png");
+        CHECK(sequence_frame_name(sf, 3040, 5, true) == "s4/f_03.png");
+        CHECK(sequence_frame_name(sf, 3040, 90, true) == "s6/f_04.png");                   // two wraps forward
+        CHECK(sequence_frame_name(sf, 3002, -3, true) == "s2/f_41.png");
+        CHECK(sequence_frame_name(sf, 3002, -50, true) == "s1/f_36.png");                  // two wraps back
+        const std::string cfg = tmp + "/repeated.cfg";
+        std::ofstream f(cfg.c_str(), std::ios::binary);
+        f << "# rates\n"
+          << "jet_estimation\t\t/a/\n"
+          << "jet_estimation\t#/b/\n"
+          << "jet_estimation\t/c/\t\t# comment\r\n"
+          << "jet_S\t3\r\n"
+          << "jet_estimation\r\n"
+          << "xjet_estimation\t/d/\n"
+          << "jet_estimation\t\t\t/e/\r\n";
+        f.close();
+        const std::vector<std::string> jets = repeated(cfg, "jet_estimation"), js = repeated(cfg, "jet_S");
+        CHECK(jets.size() == 3 && jets[0] == "/a/" && jets[1] == "/c/" && jets[2] == "/e/");
+        CHECK(js.size() == 1 && js[0] == "3");
+        CHECK(repeated(cfg, "jet_fps").empty() && repeated(tmp + "/no_such.cfg", "jet_S").empty());
+
+        int w = 0, h = 0;
+        std::vector<unsigned char> px;
+        const std::string p5 = tmp + "/t5.pgm", p4 = tmp + "/t4.pbm", p16 = tmp + "/t16.pgm";
+        std::ofstream(p5.c_str(), std::ios::binary) << "P5\n# made by hand\n3 2\n255\n" << std::string("\x00\x01\x02\xfa\xfe\xff", 6);
+        CHECK(read_pnm8(p5, w, h, px) && w == 3 && h == 2 && px == std::vector<unsigned char>({0, 1, 2, 250, 254, 255}));
+        std::ofstream(p4.c_str(), std::ios::binary) << "P4\n10 2\n" << std::string("\xb0\x40\xff\xc0", 4);   // bit 1 = black = 0
+        CHECK(read_pnm8(p4, w, h, px) && w == 10 && h == 2);
+        CHECK(px == std::vector<unsigned char>({0, 255, 0, 0, 255, 255, 255, 255, 255, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}));
+        std::ofstream(p16.c_str(), std::ios::binary) << "P5\n1 1\n65535\n" << std::string("\x01\x02", 2);
+        CHECK(!read_pnm8(p16, w, h, px) && !read_pnm8(tmp + "/no_such.pgm", w, h, px));   // maxval 255 only
+
+        const unsigned char strided[2 * 6] = {1, 2, 3, 4, 99, 99, 5, 6, 7, 8, 99, 99};
+        const std::string g8 = tmp + "/strided.pgm";
+        CHECK(write_pgm8(g8, 4, 2, strided, 6));
+        std::ifstream gi(g8.c_str(), std::ios::binary);
+        const std::string gbytes((std::istreambuf_iterator<char>(gi)), std::istreambuf_iterator<char>());
+        CHECK(gbytes == std::string("P5\n4 2\n255\n\x01\x02\x03\x04\x05\x06\x07\x08", 19));
+        CHECK(read_pnm8(g8, w, h, px) && w == 4 && h == 2 && px == std::vector<unsigned char>({1, 2, 3, 4, 5, 6, 7, 8}));
+
+        const float pf[6] = {1.0f, -2.5f, 3.25f, 4.0f, 5.5e-3f, 6.0e7f};
+        const std::string pfm = tmp + "/t.pfm";
+        CHECK(write_pfm(pfm, 3, 2, pf));
+        int maxval = 0;
+        color_image_t *im = color_image_load(pfm.c_str(), &maxval);
+        CHECK(im && im->width == 3 && im->height == 2 && maxval == 1);
+        if (im) {
+            bool same = true;
+            for (int y = 0; y < 2; y++)
+                for (int x = 0; x < 3; x++) {
+                    const size_t o = (size_t)y * im->stride + x;
+                    same = same && im->c1[o] == pf[y * 3 + x] && im->c2[o] == pf[y * 3 + x] && im->c3[o] == pf[y * 3 + x];
+                }
+            CHECK(same);
+            color_image_delete(im);
         }
     }
     printf(fails ? "host tests FAILED (%d)\n" : "host tests OK\n", fails);
