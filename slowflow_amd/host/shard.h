@@ -1,5 +1,5 @@
 // shard.h -- the pure host logic of the driver that decides who does what: the split of a sequence's frame windows over
-// GPUs and streams (the reference's OpenMP loop over jets, slow_flow.cpp:706), the adaptive frame-rate selection
+// GPUs and streams (the reference's OpenMP loop over jets, slow_flow.cpp:706), the frames each jet's windows read, the adaptive frame-rate selection
 // (slow_flow.cpp:277-357) and a small task pool for frame decoding and result output.  Header-only so that
 // tests/host/test_host.cpp exercises exactly the code the driver runs.
 #ifndef SLOWFLOW_AMD_HOST_SHARD_H
@@ -64,6 +64,36 @@ inline std::vector<FrameRange> plan_frames(const std::vector<std::pair<int, int>
     }
     if (prev >= 0) r[(size_t)prev].hi = n_frames;                                    // ... and behind the last one
     return r;
+}
+
+// The frames and jets one pass loads: jet j reads the frames j*steps .. j*steps + 3*steps, so Jets jets read 1 + (Jets + 2) * steps frames (slow_flow.cpp:411);
+// `-resume -jet k` narrows both to jet k (:418-424).  A jet past the last leaves start_j >= end_j (no windows), one far past it start_f > end_f (nothing to load).
+struct SequenceLayout { int frames; unsigned start_f, end_f, start_j, end_j; };
+inline SequenceLayout plan_sequence(unsigned jets, int steps, bool resume, int selected_jet) {
+    const int frames = 1 + ((int)jets + 2) * steps, k = selected_jet;
+    if (!resume || k < 0) return SequenceLayout{frames, 0, (unsigned)frames, 0, jets};
+    return SequenceLayout{frames, (unsigned)(k * steps), (unsigned)std::min(frames, 1 + (k + 3) * steps), (unsigned)k, (unsigned)std::min((int)jets, k + 1)};
+}
+
+// The inclusive frame span of jet j's forward or backward window (:721-724, :590-591; ref = steps), counted from frame `first`: what plan_frames takes
+inline std::pair<int, int> window_span(unsigned jet, bool backward, int steps, int first) {
+    const int f = (int)jet * steps - first;
+    return backward ? std::make_pair(f + steps, f + 3 * steps) : std::make_pair(f, f + 2 * steps);
+}
+
+// The frame tap k (0 .. 2*steps) of jet j's window reads, counted from frame `first`: forward j*steps + k; backward seq_back[frames - 1 - j*steps - 3*steps + k]
+// = seq[j*steps + 3*steps - k] (:590-591, :721-724).  Tap `steps` is the window's reference frame.
+inline int window_tap(unsigned jet, bool backward, int steps, int k, int first) {
+    const int f = (int)jet * steps;
+    return (backward ? f + 3 * steps - k : f + k) - first;
+}
+
+// The sequence frame numbers of jet j's outputs and messages: `from` names the forward flow and its images, `to`, steps * skip later, the backward flow.
+// `listed_from` is the forward flow's first frame as the reference's -resume message prints it: without the skip (:712-716).
+struct JetFrames { int from, to, listed_from; };
+inline JetFrames jet_frames(unsigned start, unsigned jet, int steps, int skip) {
+    const int from = (int)start + (int)jet * steps * skip;
+    return JetFrames{from, from + steps * skip, (int)start + (int)jet * steps};
 }
 
 // Adaptive frame rates (slow_flow.cpp:322-352).  quantil = 0.99-quantile of the flow magnitude per frame at max_fps

@@ -16,7 +16,6 @@
 #include <unistd.h>
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -73,6 +72,26 @@ static string exe_dir() {
     return s.substr(0, s.find_last_of('/'));
 }
 
+// owners of the library's and the image module's objects: every exit releases what it holds
+template <typename T, void (*Free)(T *)> struct Release { void operator()(T *p) const { Free(p); } };
+typedef std::unique_ptr<image_t, Release<image_t, image_delete>> Image;
+typedef std::unique_ptr<color_image_t, Release<color_image_t, color_image_delete>> ColorImage;
+typedef std::unique_ptr<sfa_ctx, Release<sfa_ctx, sfa_ctx_destroy>> Ctx;
+typedef std::unique_ptr<sfa_job, Release<sfa_job, sfa_job_destroy>> Job;
+typedef std::unique_ptr<sfa_sequence, Release<sfa_sequence, sfa_sequence_destroy>> DeviceSequence;
+typedef std::pair<Image, Image> Flow;
+
+static Image zero_image(int w, int h) {
+    Image im(image_new(w, h));
+    image_erase(im.get());
+    return im;
+}
+static Ctx new_ctx(int device) {                 // null on failure (sfa_last_error(nullptr))
+    sfa_ctx *c = nullptr;
+    sfa_ctx_create(device, &c);
+    return Ctx(c);
+}
+
 struct Window {
     unsigned jet; bool backward; string out; double seconds; int gpu; double epe, aae;   // epe/aae < 0: no ground truth
     Window(unsigned j, bool b, const string &o) : jet(j), backward(b), out(o), seconds(0), gpu(-1), epe(-1), aae(-1) {}
@@ -96,650 +115,601 @@ struct RunOptions {
     int selected_jet = -1;
 };
 
-// everything a finished window hands to the output pool
-struct WindowResult {
-    size_t index = 0;                            // into todo
-    image_t *wx = nullptr, *wy = nullptr, *occ = nullptr;
-    std::vector<image_t *> alt_occ;              // labels after alternation 1 .. niter_alter-1 (WRITE_FILES verbosity)
-    ~WindowResult() {
-        if (wx) image_delete(wx);
-        if (wy) image_delete(wy);
-        if (occ) image_delete(occ);
-        for (auto *o : alt_occ) image_delete(o);
-    }
-};
-
-// One pass over the sequence at one frame rate: the body of the reference's adFR loop (slow_flow.cpp:367-1060).
-static int run_sequence(ParameterList &params, const string &sequence_path, const string &format, int skip, const RunOptions &opt) {
-    const auto t_begin = std::chrono::steady_clock::now();
-    const bool raw = params.exists("raw") && params.parameter<bool>("raw");
-    const std::vector<int> red_loc = params.splitParameter<int>("raw_red_loc", "0,0");   // :439
+// the settings of one pass, read once from the cfg (the body of the reference's adFR loop, slow_flow.cpp:367-1060)
+struct Run {
+    Run(const ParameterList &params, const string &format, int skip_, const RunOptions &opt)
+        : p(params), format_flow(format.substr(0, format.find_last_of('.'))), skip(skip_), layout(plan_sequence(params.Jets, steps, opt.resume_frame, opt.selected_jet)) {}
+    const ParameterList &p;                                                         // (the members below are read from it in this order)
+    const string output = p.output, format_flow, file_gt = p.file_gt;
+    const bool raw = p.exists("raw") && p.parameter<bool>("raw");
+    const std::vector<int> red_loc = p.splitParameter<int>("raw_red_loc", "0,0");   // :439
     const int red_x = red_loc.size() > 0 ? red_loc[0] : 0, red_y = red_loc.size() > 1 ? red_loc[1] : 0;
-    const int demosaicing = params.parameter<int>("raw_demosaicing", "0");
-    const float scale = params.parameter<float>("scale", "1.0");
-    const int steps = params.parameter<int>("slow_flow_S") - 1, ref = steps;         // :208-209
-    const bool sintel = params.parameter<bool>("sintel", "0");
-    const unsigned start = params.sequence_start;
-    const string format_flow = format.substr(0, format.find_last_of('.'));
-    const int io_threads = std::max(1, std::min(64, params.parameter<int>("io_threads", std::to_string(std::max(1u, std::min(16u, std::thread::hardware_concurrency()))))));
-
-    {                                                                                // a job's windows-still-iterating mask is two 64-bit words: refused by name, not clamped
-        const int gpu_batch = params.parameter<int>("gpu_batch", "32");
-        if (gpu_batch < 1 || gpu_batch > 128) {
-            std::cerr << "gpu_batch " << gpu_batch << " is out of range: a lockstep job takes 1 .. 128 windows (more windows run as several jobs: gpu_streams, batches per worker)" << std::endl;
-            return 2;
-        }
-    }
-    mkdirs(params.output);
-
-    const int frames = 1 + (params.Jets + 2) * steps;                                // :411
-    unsigned start_f = 0, end_f = frames, start_j = 0, end_j = params.Jets;
-    if (opt.resume_frame && opt.selected_jet >= 0) {                                 // :418-424
-        start_f = opt.selected_jet * steps;
-        end_f = std::min(frames, 1 + (opt.selected_jet + 3) * steps);
-        start_j = opt.selected_jet;
-        end_j = std::min((int)params.Jets, opt.selected_jet + 1);
-    }
-    if (start_f > end_f) return 0;
-
-    // the two output files of jet j, and whether the jet still has work (-resume skips existing flows, :712-716 / :934-938)
-    auto flow_files = [&](unsigned j, string &fwd, string &bwd) {
-        const int f = j * steps;
-        fwd = sintel ? fmt2(params.output + format_flow + ".flo", start + f * skip, 0) : fmt1(params.output + format_flow + ".flo", start + f * skip);
-        bwd = sintel ? fmt2(params.output + format_flow + "_back.flo", start + f * skip + steps * skip, 0)
-                     : fmt1(params.output + format_flow + "_back.flo", start + f * skip + steps * skip);
-    };
-    auto jet_pending = [&](unsigned j) {
-        if (!opt.resume_frame) return true;
-        string fwd, bwd;
-        flow_files(j, fwd, bwd);
-        return !file_exists(fwd) || !file_exists(bwd);
-    };
-    // ---- deep_matching 1 (:744-863): the flow is initialised by EpicFlow's interpolation (epic.h) of DeepMatching matches along SED edges.  The reference starts
-    //      both tools with system() (MATLAB + a binary, third-party); this build reads their outputs from the reference's own locations and says so if they are missing.
-    const bool verbose_changes = params.verbosity(VER_CMD);       // the library prints the reference's "inner it / outer it ... avg change" lines (variational_mt.cpp:404-405, 431-432): per worker context
-    const bool enable_dm = params.parameter<bool>("deep_matching");
+    const int demosaicing = p.parameter<int>("raw_demosaicing", "0");
+    const float raw_weight = p.parameter<float>("raw_weight", "1.0"), scale = p.parameter<float>("scale", "1.0");
+    const bool preprocess = !p.exists("raw") || raw_weight == 1.0f;                 // :531
+    const bool rescale = preprocess && scale != 1;
+    const int steps = p.parameter<int>("slow_flow_S") - 1, skip;                    // :208-209 (ref = steps)
+    const bool sintel = p.parameter<bool>("sintel", "0");
+    const unsigned start = p.sequence_start;
+    const Point center = p.center, extent = p.extent;
+    const int io_threads = std::max(1, std::min(64, p.parameter<int>("io_threads", std::to_string(std::max(1u, std::min(16u, std::thread::hardware_concurrency()))))));
+    const SequenceLayout layout;
+    // gpu_oversubscribe 1: `gpus` may exceed the devices of the box, GPU g then runs on device g mod devices -- the multi-GPU code path (one resident
+    // sequence, one set of workers and one statistics slot per GPU) rehearsed on fewer cards than it is written for; never a way to get speed
+    const bool oversubscribe = p.parameter<bool>("gpu_oversubscribe", "0");
+    const int dev0 = p.parameter<int>("gpu_device", "0"), batch = p.parameter<int>("gpu_batch", "32");
+    // the GPUs, chosen before anything is read so that the HIP runtime starts up -- 0.35 s for the first context of a process -- beside the decoding
+    const int ndev = sfa_device_count();
+    const int gpus = !p.exists("gpus") ? ndev : std::max(1, oversubscribe ? std::min(16, p.parameter<int>("gpus")) : std::min(ndev, p.parameter<int>("gpus")));
+    const int ngpu = oversubscribe ? gpus : std::max(1, std::min(gpus, ndev - dev0));   // devices dev0 .. ndev-1 exist; asking for more would only fail after all frames are decoded
+    // `gpu_streams` workers per GPU (default 2), each with its own context = HIP stream: two lockstep groups fill each other's
+    // ramp-up / drain phases (the reference runs its windows from `threads` OpenMP threads the same way, slow_flow.cpp:706)
+    const int streams = std::max(1, std::min(4, p.parameter<int>("gpu_streams", "2")));
+    const bool deep_matching = p.parameter<bool>("deep_matching");
     // dm_scale (:396-402, :571-586, :801-843): DeepMatching and the edge detector ran on frames blurred (sigma = 1 / sqrt(2 dm_scale)) and resized by dm_scale; the
     // interpolation then runs at that resolution (the saliency image, the edge map, the matches' coordinates) and its flow is resized to the frames and multiplied by the
     // INTEGER ratio of the widths (:827-828: `float fx = im[ref]->width / wx->width` divides two ints).  dm_scale_run = dm_scale, halved by main() when max_flow > 150
-    const double dm_scale = params.exists("dm_scale_run") ? params.parameter<double>("dm_scale_run") : (double)params.parameter<float>("dm_scale", "1.0");
-    auto edges_file = [&](int frame_number) { return params.output + "tmp/edges_" + std::to_string(frame_number) + ".dat"; };                    // :740-741
-    auto matches_file = [&](int a, int b) { return params.output + "tmp/matches_" + std::to_string(a) + "_" + std::to_string(b) + ".dat"; };    // :742-743
-    if (enable_dm) {
-        for (unsigned j = start_j; j < end_j; j++) {
-            if (!jet_pending(j)) continue;                                           // -resume: a jet whose two flows exist is skipped below and needs no inputs
-            const int a = (int)params.sequence_start + (int)j * steps * skip, b = a + ref * skip;
-            const string need[4] = {edges_file(a), edges_file(b), matches_file(a, b), matches_file(b, a)};
-            for (const string &f : need)
-                if (!file_exists(f)) {
-                    std::cerr << "deep_matching 1: " << f << " is missing. The matches come from DeepMatching and the edge maps from the SED detector (matlab/detect_edges.m), "
-                                 "third-party programs this build does not start; place their outputs there (raw float edge map of the frame size; one match 'x1 y1 x2 y2 ...' per line) "
-                                 "and run with -resume or -overwrite, or set deep_matching 0" << std::endl;
-                    return 2;
-                }
-        }
-    }
+    const double dm_scale = p.exists("dm_scale_run") ? p.parameter<double>("dm_scale_run") : (double)p.parameter<float>("dm_scale", "1.0");
+    const bool verbose_changes = p.verbosity(VER_CMD);  // the library prints the reference's "inner it / outer it ... avg change" lines (variational_mt.cpp:404-405, 431-432): per worker context
+    const bool write_files = p.verbosity(WRITE_FILES);
+    const bool forward_only = p.exists("method") && p.parameter("method") == "forward";              // :1019-1020
+    const bool out_occ = p.parameter<bool>("slow_flow_output_occlusions", "0");                      // :892
+    // the per-alternation labels (:878-884: <output>tmp/frame_<n>_<alter>.png), with WRITE_FILES verbosity only
+    const bool out_alt_occ = out_occ && p.parameter<bool>("slow_flow_occlusion_reasoning", "0") && write_files && p.parameter<int>("slow_flow_niter_alter", "1") > 1;
+    int device_of(int g) const { return oversubscribe ? (dev0 + g) % ndev : dev0 + g; }
+};
 
-    std::vector<color_image_t *> seq(frames, nullptr), seq_back(frames, nullptr);
-    std::vector<int> seq_maxval(frames, 255);            // 255 / 65535 per frame: the 8-bit copy EpicFlow's saliency works on divides 16-bit samples by 255 (:472-474, :578)
-    // ---- the GPUs (chosen before anything is read, so that the HIP runtime starts up -- 0.35 s for the first context of a process -- beside the decoding) ----
-    const int ndev = sfa_device_count();
-    int ngpu = ndev;
-    if (ngpu <= 0) { std::cerr << "no HIP device: slowflow_amd has no CPU fallback" << std::endl; return 4; }
-    // gpu_oversubscribe 1: `gpus` may exceed the devices of the box, GPU g then runs on device g mod devices -- the multi-GPU code path (one resident
-    // sequence, one set of workers and one statistics slot per GPU) rehearsed on fewer cards than it is written for; never a way to get speed
-    const bool oversubscribe = params.parameter<bool>("gpu_oversubscribe", "0");
-    if (params.exists("gpus")) ngpu = std::max(1, oversubscribe ? std::min(16, params.parameter<int>("gpus")) : std::min(ngpu, params.parameter<int>("gpus")));
-    const int dev0 = params.parameter<int>("gpu_device", "0");
-    if (!oversubscribe) ngpu = std::max(1, std::min(ngpu, ndev - dev0));             // devices dev0 .. ndev-1 exist; asking for more would only fail after all frames are decoded
-    if (!oversubscribe && dev0 >= ndev) { std::cerr << "gpu_device " << dev0 << " does not exist (" << ndev << " device(s))" << std::endl; return 4; }
-    auto device_of = [&](int g) { return oversubscribe ? (dev0 + g) % ndev : dev0 + g; };
-    const int n_loaded = (int)(end_f - start_f);
+static string flow_file(const Run &run, unsigned jet, bool backward) {
+    const JetFrames n = jet_frames(run.start, jet, run.steps, run.skip);
+    const string pattern = run.output + run.format_flow + (backward ? "_back.flo" : ".flo");
+    return run.sintel ? fmt2(pattern, backward ? n.to : n.from, 0) : fmt1(pattern, backward ? n.to : n.from);
+}
+static string edges_file(const Run &run, int frame_number) { return run.output + "tmp/edges_" + std::to_string(frame_number) + ".dat"; }              // :740-741
+static string matches_file(const Run &run, int a, int b) { return run.output + "tmp/matches_" + std::to_string(a) + "_" + std::to_string(b) + ".dat"; }   // :742-743
 
-    // ---- the windows to refine: forward and backward of every jet (:706-1047), and who refines them -- known before a frame is read, so that every GPU is sent
-    //      only the frames ITS windows read (until round 4 every GPU received and normalised the whole sequence) ----------------------------------
+// the windows to refine: forward and backward of every jet (:706-1047); -resume skips existing flows (:712-716 / :934-938)
+static std::vector<Window> windows_to_refine(const Run &run, bool resume) {
     std::vector<Window> todo;
-    for (unsigned j = start_j; j < end_j; j++) {
-        const int f = j * steps;
-        string fwd, bwd;
-        flow_files(j, fwd, bwd);
-        if (!opt.resume_frame || !file_exists(fwd)) todo.push_back(Window(j, false, fwd));
-        else std::cout << "Forward flow from frame " << start + f << " to " << start + f * skip + steps * skip << " already exist!" << std::endl;
-        if (!opt.resume_frame || !file_exists(bwd)) todo.push_back(Window(j, true, bwd));
-        else std::cout << "Backward flow from frame " << start + f * skip << " to " << start + f * skip + steps * skip << " already exist!" << std::endl;
-    }
-    // `gpu_streams` workers per GPU (default 2), each with its own context = HIP stream: two lockstep groups fill each other's
-    // ramp-up / drain phases (the reference runs its windows from `threads` OpenMP threads the same way, slow_flow.cpp:706)
-    const int streams = std::max(1, std::min(4, params.parameter<int>("gpu_streams", "2")));
-    const std::vector<WorkerPlan> plan = plan_workers(todo.size(), ngpu, streams);
-    std::vector<std::pair<int, int>> window_frames;                                  // relative to the loaded range [start_f, end_f)
-    for (const Window &wd : todo) {
-        const int f = (int)wd.jet * steps - (int)start_f;
-        window_frames.push_back(wd.backward ? std::make_pair(f + steps, f + 3 * steps) : std::make_pair(f, f + 2 * ref));   // :721-724, :590-591
-    }
-    const std::vector<FrameRange> gpu_frames = plan_frames(window_frames, plan, ngpu, n_loaded);
-
-    std::vector<sfa_ctx *> seq_ctx(ngpu, nullptr);
-    std::vector<sfa_sequence *> seq_dev(ngpu, nullptr);
-    std::vector<string> seq_err(ngpu);
-    // The frames go to the GPUs once and are normalised there (:673; the three parts of sfa_sequence_normalize: same kernels, same statistics as the host-plane
-    // normalize() of variational_mt.h).  GPU g holds the frames gpu_frames[g] of its own windows (+ the halo its boundary jets share with the neighbour): about 1 / N
-    // of the sequence.  The statistics are those of ALL loaded frames: every GPU forms the six fp64 sums of the frames it holds (a deterministic kernel: a frame two
-    // GPUs hold gets the same bits from both), the sums are collected per frame on the host, and the moment the last frame's sums are in, the statistics are formed
-    // from them in frame order -- one set of doubles for every GPU.  One thread per GPU: it creates the context while the io pool decodes, uploads each of its frames the
-    // moment its decode task has finished (`ready`), normalises its frames once the statistics are known and releases its workers (`gpu_ready`); no GPU waits for
-    // another GPU's uploads beyond the sums of the frames it does not hold itself.
-    std::mutex ready_mu;
-    std::condition_variable ready_cv;
-    std::vector<char> frame_ready(frames, 0);
-    bool ingest_abort = false, size_known = false;
-    int width = 0, height = 0;
-    std::vector<double> frame_sums((size_t)6 * n_loaded, 0.0);
-    std::vector<char> have_sums(n_loaded, 0), gpu_ready(ngpu, 0);
-    int n_have = 0;
-    bool stats_known = false;
-    double stat_avg[3] = {0, 0, 0}, stat_std[3] = {1, 1, 1};
-    std::vector<double> upload_bytes(ngpu, 0.0), upload_done_s(ngpu, 0.0), ready_s(ngpu, 0.0);
-    auto seconds_since_begin = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); };
-    const bool upload_while_decoding = !(((!params.exists("raw") || params.parameter<float>("raw_weight", "1.0") == 1.0f)) && scale != 1);   // a rescaled sequence exists only after all frames are in
-    std::vector<std::thread> up;
-    for (int g = 0; g < ngpu; g++)
-        up.emplace_back([&, g] {
-            const FrameRange fr = gpu_frames[g];
-            const int n_mine = fr.hi - fr.lo;
-            int rc = sfa_ctx_create(device_of(g), &seq_ctx[g]);
-            auto fail = [&] {                                                         // nobody may wait for this GPU's sums or readiness
-                seq_err[g] = seq_ctx[g] ? sfa_last_error(seq_ctx[g]) : sfa_last_error(nullptr);
-                { std::lock_guard<std::mutex> l(ready_mu); ingest_abort = true; }
-                ready_cv.notify_all();
-            };
-            if (rc != SFA_OK) { fail(); return; }
-            if (n_mine <= 0) return;                                                 // more GPUs than windows
-            {
-                std::unique_lock<std::mutex> l(ready_mu);
-                ready_cv.wait(l, [&] { return size_known || ingest_abort; });
-                if (ingest_abort) return;
-            }
-            rc = sfa_sequence_create(seq_ctx[g], width, height, n_mine, &seq_dev[g]);
-            for (int f = fr.lo; f < fr.hi && rc == SFA_OK; f++) {
-                {
-                    std::unique_lock<std::mutex> l(ready_mu);
-                    ready_cv.wait(l, [&] { return frame_ready[start_f + f] || ingest_abort; });
-                    if (ingest_abort) return;
-                }
-                rc = sfa_sequence_upload(seq_dev[g], f - fr.lo, seq[start_f + f]->c1, seq[start_f + f]->stride);
-            }
-            std::vector<double> mine((size_t)6 * n_mine);
-            if (rc == SFA_OK) rc = sfa_sequence_frame_sums(seq_dev[g], 0, n_mine, mine.data());      // (waits for the uploads: one stream)
-            if (rc != SFA_OK) { fail(); return; }
-            {
-                std::unique_lock<std::mutex> l(ready_mu);
-                upload_bytes[g] = (double)n_mine * 3 * width * height * sizeof(float);
-                upload_done_s[g] = seconds_since_begin();
-                for (int f = fr.lo; f < fr.hi; f++)
-                    if (!have_sums[f]) {                                             // a halo frame: whoever is first; the other GPU's sums are the same bits
-                        std::copy(mine.begin() + 6 * (f - fr.lo), mine.begin() + 6 * (f - fr.lo) + 6, frame_sums.begin() + 6 * f);
-                        have_sums[f] = 1;
-                        n_have++;
-                    }
-                if (n_have == n_loaded && !stats_known) {                            // variational_mt.cpp:41-52 over all loaded frames, in frame order
-                    (void)sfa_normalize_statistics(frame_sums.data(), n_loaded, width, height, stat_avg, stat_std);
-                    stats_known = true;
-                }
-                ready_cv.notify_all();
-                ready_cv.wait(l, [&] { return stats_known || ingest_abort; });
-                if (ingest_abort) return;
-            }
-            rc = sfa_sequence_apply_normalization(seq_dev[g], 0, n_mine, stat_avg, stat_std);
-            if (rc != SFA_OK) { fail(); return; }
-            { std::lock_guard<std::mutex> l(ready_mu); gpu_ready[g] = 1; ready_s[g] = seconds_since_begin(); }
-            ready_cv.notify_all();
-        });
-    auto release_sequences = [&] {
-        for (int g = 0; g < ngpu; g++) {
-            if (seq_dev[g]) sfa_sequence_destroy(seq_dev[g]);
-            if (seq_ctx[g]) sfa_ctx_destroy(seq_ctx[g]);
-            seq_dev[g] = nullptr; seq_ctx[g] = nullptr;
+    for (unsigned j = run.layout.start_j; j < run.layout.end_j; j++) {
+        const JetFrames n = jet_frames(run.start, j, run.steps, run.skip);
+        for (int backward = 0; backward < 2; backward++) {
+            const string out = flow_file(run, j, backward);
+            if (!resume || !file_exists(out)) todo.push_back(Window(j, backward, out));
+            else std::cout << (backward ? "Backward" : "Forward") << " flow from frame " << (backward ? n.from : n.listed_from) << " to " << n.to << " already exist!" << std::endl;
         }
-    };
-    auto abort_ingest = [&] {
-        { std::lock_guard<std::mutex> l(ready_mu); ingest_abort = true; }
-        ready_cv.notify_all();
-        for (auto &t : up) t.join();
-        release_sequences();
-    };
+    }
+    return todo;
+}
+
+// ---- deep_matching 1 (:744-863): the flow is initialised by EpicFlow's interpolation (epic.h) of DeepMatching matches along SED edges.  The reference starts
+//      both tools with system() (MATLAB + a binary, third-party); this build reads their outputs from the reference's own locations and says so if they are missing.
+static bool deep_matching_inputs_exist(const Run &run, bool resume) {
+    for (unsigned j = run.layout.start_j; j < run.layout.end_j; j++) {
+        if (resume && file_exists(flow_file(run, j, false)) && file_exists(flow_file(run, j, true))) continue;   // -resume: a jet whose two flows exist is skipped and needs no inputs
+        const JetFrames n = jet_frames(run.start, j, run.steps, run.skip);
+        const string need[4] = {edges_file(run, n.from), edges_file(run, n.to), matches_file(run, n.from, n.to), matches_file(run, n.to, n.from)};
+        for (const string &f : need)
+            if (!file_exists(f)) {
+                std::cerr << "deep_matching 1: " << f << " is missing. The matches come from DeepMatching and the edge maps from the SED detector (matlab/detect_edges.m), "
+                             "third-party programs this build does not start; place their outputs there (raw float edge map of the frame size; one match 'x1 y1 x2 y2 ...' per line) "
+                             "and run with -resume or -overwrite, or set deep_matching 0" << std::endl;
+                return false;
+            }
+    }
+    return true;
+}
+
+// The loaded sequence and its way onto the GPUs.  The frames go to the GPUs once and are normalised there (:673; the three parts of sfa_sequence_normalize: same kernels,
+// same statistics as the host-plane normalize() of variational_mt.h).  GPU g holds the frames gpu_frames[g] of its own windows (+ the halo its boundary jets share with
+// the neighbour): about 1 / N of the sequence.  The statistics are those of ALL loaded frames: every GPU forms the six fp64 sums of the frames it holds (a deterministic
+// kernel: a frame two GPUs hold gets the same bits from both), the sums are collected per frame on the host, and the moment the last frame's sums are in, the statistics
+// are formed from them in frame order -- one set of doubles for every GPU.  One thread per GPU: it creates the context while the io pool decodes, uploads each of its
+// frames the moment it is published, normalises its frames once the statistics are known and releases that GPU's workers; no GPU waits for another GPU's uploads beyond
+// the sums of the frames it does not hold itself.  A GPU without windows only creates its context: with nothing to refine nobody waits for statistics.
+class Sequence {
+public:
+    struct Gpu { Ctx ctx; DeviceSequence resident; string err; bool ready = false; double upload_bytes = 0, upload_done_s = 0, ready_s = 0, first_refine_s = -1; };   // (resident goes before ctx; s since the run began)
+    std::vector<ColorImage> frames;              // by frame of the pass (only [start_f, end_f) is loaded); width x height: published with the first frame
+    std::vector<int> maxval;                     // 255 / 65535 per frame: the 8-bit copy EpicFlow's saliency works on divides 16-bit samples by 255 (:472-474, :578)
+    int width = 0, height = 0;
+    const std::vector<FrameRange> &gpu_frames;
+    Sequence(const Run &run, const std::vector<FrameRange> &gpu_frames_, double t_begin)
+        : frames(run.layout.frames), maxval(run.layout.frames, 255), gpu_frames(gpu_frames_), run_(run), t_begin_(t_begin), n_loaded_((int)(run.layout.end_f - run.layout.start_f)),
+          frame_ready_(run.layout.frames, 0), have_sums_(n_loaded_, 0), frame_sums_((size_t)6 * n_loaded_, 0.0), gpus_(run.ngpu) {
+        for (int g = 0; g < run.ngpu; g++) up_.emplace_back(&Sequence::upload, this, g);
+    }
+    ~Sequence() { abort(); join(); }
     // frames [f0, f1) are final: publish the size once, then the frames.  Every frame is held against the published size BEFORE it is marked ready: the uploaders copy
     // width x height of the published size out of each frame's buffer, so a smaller frame in the middle of the sequence would be read beyond its end; it is
-    // left unpublished and reported through `size_mismatch` instead (the uploaders are then released by abort_ingest)
-    string size_mismatch;
-    auto frames_are = [&](unsigned f0, unsigned f1) {
+    // left unpublished and reported through size_mismatch() instead
+    void publish(unsigned f0, unsigned f1) {
         {
-            std::lock_guard<std::mutex> l(ready_mu);
-            if (!size_known) { width = seq[f0]->width; height = seq[f0]->height; size_known = true; }
+            std::lock_guard<std::mutex> l(mu_);
             for (unsigned f = f0; f < f1; f++) {
-                if (seq[f]->width != width || seq[f]->height != height) {
-                    if (size_mismatch.empty())
-                        size_mismatch = "frames of different sizes: frame " + std::to_string(f) + " of the sequence is " + std::to_string(seq[f]->width) + "x" + std::to_string(seq[f]->height) + ", the sequence " +
-                                        std::to_string(width) + "x" + std::to_string(height);
+                const color_image_t *im = frames[f].get();
+                if (!size_known_) { width = im->width; height = im->height; size_known_ = true; }
+                if (im->width != width || im->height != height) {
+                    if (size_mismatch_.empty())
+                        size_mismatch_ = "frames of different sizes: frame " + std::to_string(f) + " of the sequence is " + std::to_string(im->width) + "x" + std::to_string(im->height) +
+                                         ", the sequence " + std::to_string(width) + "x" + std::to_string(height);
                     continue;
                 }
-                frame_ready[f] = 1;
+                frame_ready_[f] = 1;
             }
         }
-        ready_cv.notify_all();
-    };
+        cv_.notify_all();
+    }
+    string size_mismatch() { std::lock_guard<std::mutex> l(mu_); return size_mismatch_; }
+    bool wait_statistics(double avg[3], double sd[3]) {
+        const bool ok = wait([&] { return stats_known_; });
+        std::copy(avg_, avg_ + 3, avg); std::copy(std_, std_ + 3, sd);
+        return ok;
+    }
+    bool wait_gpu(int g) {                                                           // GPU g's frames are resident and normalised; false if aborted first
+        if (!wait([&] { return gpus_[g].ready; })) return false;
+        std::lock_guard<std::mutex> l(mu_);
+        if (gpus_[g].first_refine_s < 0) gpus_[g].first_refine_s = now_s() - t_begin_;
+        return true;
+    }
+    const Gpu &gpu(int g) const { return gpus_[g]; }                              // resident: after wait_gpu(g); times: once the threads have ended
+    bool report_errors() {                                                           // joins the uploaders, prints each GPU's error; true if there was one
+        join();
+        bool any = false;
+        for (int g = 0; g < run_.ngpu; g++)
+            if (!gpus_[g].err.empty()) { std::cerr << "GPU " << run_.device_of(g) << ": " << gpus_[g].err << std::endl; any = true; }
+        return any;
+    }
 
-    // ---- read the image sequence (:447-592, without OpenCV: PNG, binary PPM / PGM / PFM): decoded, demosaiced and cropped by the
-    //      io pool, one frame per task ----------------------------------------------------------------------------------------------
-    std::vector<string> names(frames);
-    for (unsigned f = start_f; f < end_f; f++) {
-        names[f] = sequence_frame_name(sequence_path + format, (int)start, (int)f * skip - ref * skip, sintel);
+private:
+    template <typename Ready> bool wait(Ready ready) {                               // false once aborted
+        std::unique_lock<std::mutex> l(mu_);
+        cv_.wait(l, [&] { return ready() || aborted_; });
+        return !aborted_;
+    }
+    void abort() {
+        { std::lock_guard<std::mutex> l(mu_); aborted_ = true; }
+        cv_.notify_all();
+    }
+    void join() { for (auto &t : up_) if (t.joinable()) t.join(); }
+    void fail(int g) {                                                               // nobody may wait for this GPU's sums or readiness
+        gpus_[g].err = sfa_last_error(gpus_[g].ctx.get());
+        abort();
+    }
+    // GPU g's thread: context, uploads as frames are published, the frames' sums, then the normalisation with the statistics of all frames
+    void upload(int g) {
+        const FrameRange fr = gpu_frames[g];
+        const int n_mine = fr.hi - fr.lo, start_f = (int)run_.layout.start_f;
+        Gpu &gpu = gpus_[g];
+        gpu.ctx = new_ctx(run_.device_of(g));
+        if (!gpu.ctx) return fail(g);
+        if (n_mine <= 0 || !wait([&] { return size_known_; })) return;             // more GPUs than windows, or aborted
+        sfa_sequence *s = nullptr;
+        int rc = sfa_sequence_create(gpu.ctx.get(), width, height, n_mine, &s);
+        gpu.resident.reset(s);
+        for (int f = fr.lo; f < fr.hi && rc == SFA_OK; f++) {
+            if (!wait([&] { return frame_ready_[start_f + f] != 0; })) return;
+            rc = sfa_sequence_upload(s, f - fr.lo, frames[start_f + f]->c1, frames[start_f + f]->stride);
+        }
+        std::vector<double> mine((size_t)6 * n_mine);
+        if (rc == SFA_OK) rc = sfa_sequence_frame_sums(s, 0, n_mine, mine.data());  // (waits for the uploads: one stream)
+        if (rc != SFA_OK) return fail(g);
+        {
+            std::lock_guard<std::mutex> l(mu_);
+            gpu.upload_bytes = (double)n_mine * 3 * width * height * sizeof(float);
+            gpu.upload_done_s = now_s() - t_begin_;
+            for (int f = fr.lo; f < fr.hi; f++)
+                if (!have_sums_[f]) {                                                // a halo frame: whoever is first; the other GPU's sums are the same bits
+                    std::copy(mine.begin() + 6 * (f - fr.lo), mine.begin() + 6 * (f - fr.lo) + 6, frame_sums_.begin() + 6 * f);
+                    have_sums_[f] = 1;
+                    n_have_++;
+                }
+            if (n_have_ == n_loaded_ && !stats_known_) {                             // variational_mt.cpp:41-52 over all loaded frames, in frame order
+                (void)sfa_normalize_statistics(frame_sums_.data(), n_loaded_, width, height, avg_, std_);
+                stats_known_ = true;
+            }
+        }
+        cv_.notify_all();
+        if (!wait([&] { return stats_known_; })) return;
+        if (sfa_sequence_apply_normalization(s, 0, n_mine, avg_, std_) != SFA_OK) return fail(g);
+        { std::lock_guard<std::mutex> l(mu_); gpu.ready = true; gpu.ready_s = now_s() - t_begin_; }
+        cv_.notify_all();
+    }
+
+    const Run &run_;
+    const double t_begin_;
+    const int n_loaded_;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    bool size_known_ = false, stats_known_ = false, aborted_ = false;
+    int n_have_ = 0;
+    string size_mismatch_;
+    std::vector<char> frame_ready_, have_sums_;
+    std::vector<double> frame_sums_;
+    double avg_[3] = {0, 0, 0}, std_[3] = {1, 1, 1};
+    std::vector<Gpu> gpus_;
+    std::vector<std::thread> up_;
+};
+
+// ---- read the image sequence (:447-592, without OpenCV: PNG, binary PPM / PGM / PFM): decoded, demosaiced and cropped by the io pool, one frame per task, each published
+//      as it is done unless rescaled (blur + resize against aliasing, :550-553, on the GPU: only once all frames are in).  0 or the exit code; decoded_at: end of decoding
+static int read_frames(const Run &run, const string &sequence_path, const string &format, Sequence &seq, double &decoded_at) {
+    std::vector<string> names(run.layout.frames);
+    for (unsigned f = run.layout.start_f; f < run.layout.end_f; f++) {
+        names[f] = sequence_frame_name(sequence_path + format, (int)run.start, (int)f * run.skip - run.steps * run.skip, run.sintel);
         std::cout << "Reading " << names[f] << "..." << std::endl;
     }
-    const bool preprocess = !params.exists("raw") || params.parameter<float>("raw_weight", "1.0") == 1.0f;   // :531
-    const Point center = params.center, extent = params.extent;
     std::mutex err_mu;
     string load_error;
     {
-        TaskPool pool(io_threads);
-        for (unsigned f = start_f; f < end_f; f++)
+        TaskPool pool(run.io_threads);
+        for (unsigned f = run.layout.start_f; f < run.layout.end_f; f++)
             pool.submit([&, f] {
                 int maxval = 255;
                 string error;                                                        // demosaicing (:482-527): the mosaic is the grey image
-                color_image_t *img = load_frame(names[f], raw, demosaicing, red_x, red_y, &maxval, &error);
-                if (!img) { std::lock_guard<std::mutex> l(err_mu); if (load_error.empty()) load_error = error; return; }
-                if (preprocess && (extent.x > 0 || extent.y > 0)) {                  // use only a part of the images (:533-536)
-                    color_image_t *part = color_image_crop(img, center.x, center.y, extent.x, extent.y);
-                    if (!part) {
-                        std::lock_guard<std::mutex> l(err_mu);
-                        if (load_error.empty()) load_error = "center / extent do not fit the " + std::to_string(img->width) + "x" + std::to_string(img->height) + " frames";
-                        color_image_delete(img);
-                        return;
-                    }
-                    color_image_delete(img);
-                    img = part;
+                ColorImage img(load_frame(names[f], run.raw, run.demosaicing, run.red_x, run.red_y, &maxval, &error));
+                if (img && run.preprocess && (run.extent.x > 0 || run.extent.y > 0)) {   // use only a part of the images (:533-536)
+                    ColorImage part(color_image_crop(img.get(), run.center.x, run.center.y, run.extent.x, run.extent.y));
+                    if (!part) error = "center / extent do not fit the " + std::to_string(img->width) + "x" + std::to_string(img->height) + " frames";
+                    img = std::move(part);
                 }
-                seq[f] = img;
-                seq_maxval[f] = maxval;
-                if (upload_while_decoding) frames_are(f, f + 1);
+                if (!img) { std::lock_guard<std::mutex> l(err_mu); if (load_error.empty()) load_error = error; return; }
+                seq.frames[f] = std::move(img);
+                seq.maxval[f] = maxval;
+                if (!run.rescale) seq.publish(f, f + 1);
             });
         pool.wait_all();
     }
-    if (!load_error.empty()) { std::cerr << load_error << std::endl; abort_ingest(); return 3; }
-    { std::lock_guard<std::mutex> l(ready_mu); if (!size_mismatch.empty()) load_error = size_mismatch; }
-    if (!load_error.empty()) { std::cerr << load_error << std::endl; abort_ingest(); return 3; }
-    const double decode_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    if (preprocess && scale != 1) {                                                  // blur + resize against aliasing (:550-553), on the GPU
-        sfa_ctx *ingest_ctx = nullptr;
-        if (sfa_ctx_create(params.parameter<int>("gpu_device", "0"), &ingest_ctx) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; abort_ingest(); return 4; }
-        for (unsigned f = start_f; f < end_f; f++) {
-            color_image_t *small = color_image_rescale(ingest_ctx, seq[f], scale);
-            if (!small) { std::cerr << "rescaling failed: " << sfa_last_error(ingest_ctx) << std::endl; sfa_ctx_destroy(ingest_ctx); abort_ingest(); return 4; }
-            color_image_delete(seq[f]);
-            seq[f] = small;
-        }
-        sfa_ctx_destroy(ingest_ctx);
+    if (load_error.empty()) load_error = seq.size_mismatch();
+    if (!load_error.empty()) { std::cerr << load_error << std::endl; return 3; }
+    decoded_at = now_s();
+    if (!run.rescale) return 0;
+    Ctx ctx = new_ctx(run.dev0);
+    if (!ctx) { std::cerr << sfa_last_error(nullptr) << std::endl; return 4; }
+    for (unsigned f = run.layout.start_f; f < run.layout.end_f; f++) {
+        ColorImage small(color_image_rescale(ctx.get(), seq.frames[f].get(), run.scale));
+        if (!small) { std::cerr << "rescaling failed: " << sfa_last_error(ctx.get()) << std::endl; return 4; }
+        seq.frames[f] = std::move(small);
     }
-    if (!upload_while_decoding) {
-        frames_are(start_f, end_f);
-        std::lock_guard<std::mutex> l(ready_mu);
-        load_error = size_mismatch;
-    }
-    if (!load_error.empty()) { std::cerr << load_error << std::endl; abort_ingest(); return 3; }
-    for (unsigned f = start_f; f < end_f; f++) seq_back[frames - 1 - f] = seq[f];    // :590-591
-    if (seq[start_f]->width != width || seq[start_f]->height != height) { std::cerr << "frames of different sizes" << std::endl; abort_ingest(); return 3; }
-    color_image_t *channel_weights = color_image_new(width, height);                 // :597-598 (all ones without raw weighting)
-    for (size_t i = 0; i < (size_t)3 * channel_weights->stride * height; i++) channel_weights->c1[i] = 1.0f;
-    if (raw) rawWeighting(channel_weights, red_x, red_y, params.parameter<float>("raw_weight", "1.0"));   // :599-600
+    seq.publish(run.layout.start_f, run.layout.end_f);
+    load_error = seq.size_mismatch();
+    if (!load_error.empty()) { std::cerr << load_error << std::endl; return 3; }
+    return 0;
+}
 
-    // ---- ground truth, if the cfg names it (:603-661): .flo -> crop -> nearest resize * scale -> gt/flow_%05i.{png,flo} --------
-    std::vector<image_t **> gt(params.Jets, nullptr);
-    if (!params.file_gt.empty()) {
-        mkdirs(params.output + "gt/");
-        for (unsigned j = start_j; j < end_j; j++) {
-            const string path = sequence_frame_name(params.file_gt, (int)start, (int)j * steps, sintel);
-            std::cout << path << std::endl;
-            if (!file_exists(path)) continue;
-            image_t **g = readFlowFile(path.c_str());
-            if (!g) { std::cout << "No gt flow for frame " << std::endl; continue; }
-            if (params.center.x > 0) {                                               // crop like the frames (:634-637)
-                for (int c = 0; c < 2; c++) {
-                    const int x0 = params.center.x - params.extent.x / 2, y0 = params.center.y - params.extent.y / 2;
-                    const int cw = 2 * (params.extent.x / 2), chh = 2 * (params.extent.y / 2);
-                    if (x0 < 0 || y0 < 0 || x0 + cw > g[c]->width || y0 + chh > g[c]->height) { std::cerr << "center / extent do not fit the ground truth" << std::endl; abort_ingest(); return 3; }
-                    image_t *part = image_new(cw, chh);
-                    image_erase(part);
-                    for (int y = 0; y < chh; y++) memcpy(part->data + (size_t)y * part->stride, g[c]->data + (size_t)(y0 + y) * g[c]->stride + x0, sizeof(float) * cw);
-                    image_delete(g[c]);
-                    g[c] = part;
-                }
+// ---- ground truth, if the cfg names it (:603-661): .flo -> crop -> nearest resize * scale -> gt/flow_%05i.{png,flo}; 0 or the exit code
+static int load_ground_truth(const Run &run, std::vector<Flow> &gt) {
+    mkdirs(run.output + "gt/");
+    for (unsigned j = run.layout.start_j; j < run.layout.end_j; j++) {
+        const string path = sequence_frame_name(run.file_gt, (int)run.start, (int)j * run.steps, run.sintel);
+        std::cout << path << std::endl;
+        if (!file_exists(path)) continue;
+        image_t **g = readFlowFile(path.c_str());
+        if (!g) { std::cout << "No gt flow for frame " << std::endl; continue; }
+        gt[j] = Flow(Image(g[0]), Image(g[1]));
+        free(g);
+        for (Image *c : {&gt[j].first, &gt[j].second}) {
+            if (run.center.x > 0) {                                                  // crop like the frames (:634-637)
+                const int x0 = run.center.x - run.extent.x / 2, y0 = run.center.y - run.extent.y / 2;
+                const int cw = 2 * (run.extent.x / 2), chh = 2 * (run.extent.y / 2);
+                if (x0 < 0 || y0 < 0 || x0 + cw > (*c)->width || y0 + chh > (*c)->height) { std::cerr << "center / extent do not fit the ground truth" << std::endl; return 3; }
+                Image part = zero_image(cw, chh);
+                for (int y = 0; y < chh; y++) memcpy(part->data + (size_t)y * part->stride, (*c)->data + (size_t)(y0 + y) * (*c)->stride + x0, sizeof(float) * cw);
+                *c = std::move(part);
             }
-            for (int c = 0; c < 2; c++) {                                            // nearest, not linear: motion discontinuities (:640-641)
-                image_t *r = flow_resize_nearest(g[c], scale);
-                image_delete(g[c]);
-                g[c] = r;
-            }
-            gt[j] = g;
-            const string base = params.output + "gt/" + fmt1("flow_%05i", (int)params.sequence_start + (int)j * steps);
-            png_write((base + ".png").c_str(), flowColorImg(g[0], g[1], params.verbosity(VER_CMD)));
-            writeFlowFile((base + ".flo").c_str(), g[0], g[1]);
+            c->reset(flow_resize_nearest(c->get(), run.scale));                      // nearest, not linear: motion discontinuities (:640-641)
+        }
+        const string base = run.output + "gt/" + fmt1("flow_%05i", (int)run.start + (int)j * run.steps);
+        png_write((base + ".png").c_str(), flowColorImg(gt[j].first.get(), gt[j].second.get(), run.verbose_changes));
+        writeFlowFile((base + ".flo").c_str(), gt[j].first.get(), gt[j].second.get());
+    }
+    return 0;
+}
+
+// EpicFlow's interpolation of the matches of one window (:801-863 / :960-1004), per single frame step, into wx, wy; SFA_OK or the error
+static int interpolate_matches(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, Image &wx, Image &wy) {
+    const int width = seq.width, height = seq.height;
+    const double dm_scale = run.dm_scale;
+    const JetFrames n = jet_frames(run.start, wd.jet, run.steps, run.skip);
+    const int a = n.from, b = n.to, fi = window_tap(wd.jet, wd.backward, run.steps, run.steps, 0);   // fi: un_im[ref] / un_im_back[ref], the reference frame, not normalised
+    const color_image_t *un_ref = seq.frames[fi].get();
+    epic_matches mt;
+    epic_edges ed;
+    epic_params_t ep;
+    epic_params_default(&ep);
+    ep.pref_nn = 25; ep.nn = 160; ep.coef_kernel = 1.1f;         // :271-275
+    // the resolution the interpolation runs at: cv::resize(img, img, Size(0, 0), dm_scale, dm_scale) makes cvRound(cols * dm_scale) x cvRound(rows * dm_scale)
+    const int ew = dm_scale != 1 ? (int)std::lrint(width * dm_scale) : width, eh = dm_scale != 1 ? (int)std::lrint(height * dm_scale) : height;
+    // ... while the reference allocates un_seq / wx and sizes the edge file with the TRUNCATED product (`color_image_new(width*dm_scale, height*dm_scale)`,
+    // slow_flow.cpp:584, :801-806).  Where the two differ (1023 * 0.5: 512 against 511) the reference copies a 512-wide image into a 511-wide one -- no defined
+    // result, and edge / match files laid out for either width would be misread by the other: refused by name
+    if (dm_scale != 1 && (ew != (int)(width * dm_scale) || eh != (int)(height * dm_scale))) {
+        std::lock_guard<std::mutex> l(io_mu);
+        std::cerr << "dm_scale " << dm_scale << ": " << width << " x " << height << " frames give a rescaled image of " << ew << " x " << eh << " (cv::resize rounds) but buffers and edge files of "
+                  << (int)(width * dm_scale) << " x " << (int)(height * dm_scale) << " (slow_flow.cpp:584 truncates): the reference has no defined result here; crop the frames to a multiple of 1 / dm_scale"
+                  << std::endl;
+        return SFA_ERR_ARG;
+    }
+    if (ew < 1 || eh < 1 || !read_matches((wd.backward ? matches_file(run, b, a) : matches_file(run, a, b)).c_str(), mt) ||
+        !read_edges((wd.backward ? edges_file(run, b) : edges_file(run, a)).c_str(), ew, eh, ed)) return SFA_ERR_ARG;
+    // the reference hands epic() un_seq: the frame after img.convertTo(CV_8U, norm), i.e. rounded to nearest and saturated to 0..255,
+    // 16-bit samples scaled by 1/255 first (slow_flow.cpp:472-474, :578-586) -- not the float frame the refinement reads
+    // :571-573: GaussianBlur(sigma = 1 / sqrt(2 dm_scale), BORDER_REPLICATE) then resize by dm_scale, on the float frame (the pyramid's two
+    // operators: sfa_gaussian_blur, sfa_resize_linear_fx with cv::resize's fx / fy form of the coordinate scale)
+    ColorImage small;
+    if (dm_scale != 1) {
+        small.reset(color_image_new(ew, eh));
+        std::vector<float> tmp((size_t)un_ref->stride * un_ref->height);
+        const float sigma = (float)(1 / sqrt(2 * dm_scale));
+        float *src3[3] = {un_ref->c1, un_ref->c2, un_ref->c3}, *dst3[3] = {small->c1, small->c2, small->c3};
+        for (int ch = 0; ch < 3; ch++) {
+            int rc = sfa_gaussian_blur(ctx, tmp.data(), src3[ch], un_ref->width, un_ref->height, un_ref->stride, sigma);
+            if (rc == SFA_OK) rc = sfa_resize_linear_fx(ctx, dst3[ch], ew, eh, small->stride, tmp.data(), un_ref->width, un_ref->height, un_ref->stride, dm_scale, dm_scale);
+            if (rc != SFA_OK) return rc;
         }
     }
-
-    // ---- the GPU threads started above have been uploading beside the decoding; what is left of the ingest is the normalisation ------------------
-    const auto t_norm = std::chrono::steady_clock::now();
-    auto ingest_failed = [&]() -> bool {
-        bool any = false;
-        for (int g = 0; g < ngpu; g++)
-            if (!seq_err[g].empty()) { std::cerr << "GPU " << device_of(g) << ": " << seq_err[g] << std::endl; any = true; }
-        return any;
-    };
-    if (todo.empty()) {                                                              // nothing to refine (-resume over finished jets): the statistics are not needed either
-        std::lock_guard<std::mutex> l(ready_mu);
-        ingest_abort = true;
-    } else {
-        std::unique_lock<std::mutex> l(ready_mu);                                    // the GPU threads uploaded their frames as they were decoded; the last frame's sums make the statistics
-        ready_cv.wait(l, [&] { return stats_known || ingest_abort; });
+    const color_image_t *un_src = small ? small.get() : un_ref;
+    ColorImage un8(color_image_new(un_src->width, un_src->height));
+    const float norm = seq.maxval[fi] > 255 ? 1.0f / 255 : 1.0f;
+    for (size_t i = 0; i < (size_t)3 * un_src->stride * un_src->height; i++) {
+        const float v = nearbyintf(un_src->c1[i] * norm);                          // cvRound: to nearest, ties to even
+        un8->c1[i] = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);                   // saturate_cast<uchar>
     }
-    ready_cv.notify_all();
-    if (ingest_abort) {
-        for (auto &t : up) t.join();
-        const bool err = ingest_failed();
-        release_sequences();
-        if (err) return 4;
+    const ColorImage lab(rgb_to_lab(un8.get()));
+    wx = zero_image(ew, eh); wy = zero_image(ew, eh);
+    const int er = epic(ctx, wx.get(), wy.get(), lab.get(), mt, ed, &ep);
+    if (er < 0) return SFA_ERR_HIP;
+    if (er > 0) { image_erase(wx.get()); image_erase(wy.get()); }                   // no usable match: start from zero like deep_matching 0
+    // :826-843: rescale flow.  fx, fy are quotients of ints; only when fx != 1 is the field resized (cv::resize to the frame's size: the ratio form)
+    const float fx = (float)(width / ew), fy = (float)(height / eh);
+    if (fx != 1) {
+        Image fwx(image_new(width, height)), fwy(image_new(width, height));
+        int rc = sfa_resize_linear(ctx, fwx->data, width, height, fwx->stride, wx->data, ew, eh, wx->stride);
+        if (rc == SFA_OK) rc = sfa_resize_linear(ctx, fwy->data, width, height, fwy->stride, wy->data, ew, eh, wy->stride);
+        if (rc != SFA_OK) return rc;
+        wx = std::move(fwx); wy = std::move(fwy);
+    } else if (ew != width || eh != height) {
+        // the reference would hand a field of the reduced size to a solver of the frames' size here (1 < width ratio < 2): it has no defined result
+        std::lock_guard<std::mutex> l(io_mu);
+        std::cerr << "dm_scale " << dm_scale << ": the frames are " << width << " wide, the interpolation " << ew << " -- the reference rescales by the integer ratio "
+                  << width / ew << " (slow_flow.cpp:827) and would keep the reduced field; use a dm_scale of 1 / n" << std::endl;
+        return SFA_ERR_ARG;
     }
-    if (!todo.empty()) publish_normalization(params, stat_avg, stat_std);            // the slow_flow_img_norm_* parameters (variational_mt.cpp:71-84)
-    const double normalize_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_norm).count();
-    {
-        std::ofstream infos((params.output + "config.cfg").c_str());                 // :684-688
-        infos << "# SlowFlow variational estimation\n" << params;
+    image_mul_scalar(wx.get(), fx / run.steps);                                      // :842-843
+    image_mul_scalar(wy.get(), fy / run.steps);
+    if (run.write_files && !wd.backward)                                             // :845-858
+        png_write((run.output + "tmp/frame_" + std::to_string(a) + "_INIT.png").c_str(), flowColorImg(wx.get(), wy.get(), 0));
+    return SFA_OK;
+}
+
+struct EpicInit { Image wx, wy; int rc = SFA_OK; };     // the initial flow of one window (deep_matching 1)
+// everything a finished window hands to the output pool
+struct WindowResult {
+    size_t index = 0;                            // into todo
+    Image wx, wy, occ;
+    std::vector<Image> alt_occ;                  // labels after alternation 1 .. niter_alter-1 (WRITE_FILES verbosity)
+};
+
+// a finished window, off the GPU worker's thread: flow * steps -> .flo, colour PNG, EPE / AAE against a ground truth of the frames' size, occlusion images; false on a write error
+static bool emit(const Run &run, Window &wd, WindowResult &r, const Flow &gt, int width, int height) {
+    image_mul_scalar(r.wx.get(), (float)run.steps);                                  // :908-909
+    image_mul_scalar(r.wy.get(), (float)run.steps);
+    bool ok = writeFlowFile(wd.out.c_str(), r.wx.get(), r.wy.get()) == 0;
+    const string fnum = std::to_string(jet_frames(run.start, wd.jet, run.steps, run.skip).from);
+    if (ok && !wd.backward) {                                                        // the flow as a colour image next to the .flo (:913-925)
+        ok = png_write((run.output + "frame_" + fnum + ".png").c_str(), flowColorImg(r.wx.get(), r.wy.get(), 0));
+        if (gt.first && gt.first->width == width && gt.first->height == height) {    // additive: error against the ground truth, reported in timings.json
+            wd.epe = computeEPE(r.wx.get(), r.wy.get(), gt.first.get(), gt.second.get());
+            wd.aae = computeAAE(r.wx.get(), r.wy.get(), gt.first.get(), gt.second.get());
+        }
     }
-    const double ingest_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    // the occlusion estimate of the forward window (:892-905; the reference writes a binary PXM named .pbm through OpenCV, here the
+    // same 8-bit grey map as PGM) and, with WRITE_FILES verbosity, the labels after every alternation (:878-884 -> variational_mt.cpp:275-285)
+    if (ok && r.occ) ok = writePGM((run.output + "occlusion/frame_" + fnum + ".pgm").c_str(), r.occ.get(), 1.0f, 127.5f) == 0;
+    for (size_t a = 0; ok && a < r.alt_occ.size(); a++)
+        ok = png_write((run.output + "tmp/frame_" + fnum + "_" + std::to_string(a + 1) + ".png").c_str(), occlusion_image(r.alt_occ[a].get()));
+    return ok;
+}
 
-    const int batch = params.parameter<int>("gpu_batch", "32");                      // 1 .. 128: checked before anything was read
-    const int F = 2 * ref + 1;
-    const bool backward_forward_only = params.exists("method") && params.parameter("method") == "forward";   // :1019-1020
-    const bool occ_on = params.parameter<bool>("slow_flow_occlusion_reasoning", "0");
-    const bool out_occ = params.parameter<bool>("slow_flow_output_occlusions", "0");                          // :892
-    // the per-alternation labels (:878-884: <output>tmp/frame_<n>_<alter>.png), with WRITE_FILES verbosity only
-    const bool out_alt_occ = out_occ && occ_on && params.verbosity(WRITE_FILES) && params.parameter<int>("slow_flow_niter_alter", "1") > 1;
-    if (out_occ) mkdirs(params.output + "occlusion/");                               // :676-677
-    if (out_alt_occ || enable_dm) mkdirs(params.output + "tmp/");
-
+// what the refinement workers and the output pool share: the pass's inputs, the window list they fill in, and where they report
+struct Refinement {
+    const Run &run;
+    Sequence &seq;
+    const color_image_t *channel_weights;
+    const std::vector<Flow> &gt;
+    std::vector<Window> &todo;
+    TaskPool &out_pool;
     std::mutex io_mu;
-    std::atomic<bool> failed(false);
-    TaskPool out_pool(io_threads);
-    std::vector<double> first_refine_s(ngpu, -1.0);                                  // when the first worker of a GPU started refining (seconds since the run began)
-
-    // what happens to a finished window off the GPU worker's thread: flow * steps -> .flo, colour PNG, EPE / AAE, occlusion images
-    auto emit = [&](std::shared_ptr<WindowResult> r) {
-        Window &wd = todo[r->index];
-        image_mul_scalar(r->wx, (float)steps);                                       // :908-909
-        image_mul_scalar(r->wy, (float)steps);
-        bool ok = writeFlowFile(wd.out.c_str(), r->wx, r->wy) == 0;
-        const int fnum = (int)start + (int)wd.jet * steps * skip;
-        if (ok && !wd.backward) {                                                    // the flow as a colour image next to the .flo (:913-925)
-            ok = png_write((params.output + "frame_" + std::to_string(fnum) + ".png").c_str(), flowColorImg(r->wx, r->wy, 0));
-            image_t **g = gt[wd.jet];
-            if (g && g[0]->width == width && g[0]->height == height) {               // additive: error against the ground truth, reported in timings.json
-                wd.epe = computeEPE(r->wx, r->wy, g[0], g[1]);
-                wd.aae = computeAAE(r->wx, r->wy, g[0], g[1]);
-            }
-        }
-        // the occlusion estimate of the forward window (:892-905; the reference writes a binary PXM named .pbm through OpenCV, here the
-        // same 8-bit grey map as PGM) and, with WRITE_FILES verbosity, the labels after every alternation (:878-884 -> variational_mt.cpp:275-285)
-        if (ok && r->occ) ok = writePGM((params.output + "occlusion/frame_" + std::to_string(fnum) + ".pgm").c_str(), r->occ, 1.0f, 127.5f) == 0;
-        for (size_t a = 0; ok && a < r->alt_occ.size(); a++)
-            ok = png_write((params.output + "tmp/frame_" + std::to_string(fnum) + "_" + std::to_string(a + 1) + ".png").c_str(), occlusion_image(r->alt_occ[a]));
-        if (!ok) {
-            std::lock_guard<std::mutex> l(io_mu);
-            std::cerr << "cannot write the results of " << wd.out << std::endl;
-            failed = true;
-        }
-    };
-
-    auto worker = [&](const WorkerPlan &wp) {
-        if (wp.lo >= wp.hi) return;
-        const int device = device_of(wp.gpu);
-        sfa_ctx *ctx = nullptr;
-        if (sfa_ctx_create(device, &ctx) != SFA_OK) { std::lock_guard<std::mutex> l(io_mu); std::cerr << sfa_last_error(nullptr) << std::endl; failed = true; return; }
-        sfa_ctx *ectx = nullptr;                                                     // the EpicFlow helper's context (deep_matching 1 only)
-        if (enable_dm && sfa_ctx_create(device, &ectx) != SFA_OK) { std::lock_guard<std::mutex> l(io_mu); std::cerr << sfa_last_error(nullptr) << std::endl; failed = true; sfa_ctx_destroy(ctx); return; }
-        (void)sfa_ctx_set_verbose(ctx, verbose_changes ? 1 : 0);
-        {                                                                            // this GPU's frames are resident and normalised
-            std::unique_lock<std::mutex> l(ready_mu);
-            ready_cv.wait(l, [&] { return gpu_ready[wp.gpu] || ingest_abort; });
-            if (ingest_abort) { failed = true; if (ectx) sfa_ctx_destroy(ectx); sfa_ctx_destroy(ctx); return; }
-            if (first_refine_s[wp.gpu] < 0) first_refine_s[wp.gpu] = seconds_since_begin();
-        }
-        const int frame0 = gpu_frames[wp.gpu].lo;                                    // the GPU's resident sequence starts at this frame of the loaded range
-        ParameterList tp(params);                                                    // one copy per thread (:708)
-        // EpicFlow's interpolation of the matches of one window (:801-863 / :960-1004), per single frame step.  It runs on a helper thread with a context of its
-        // own (the library's contexts are thread-compatible, not thread-safe), one batch ahead of the refinement: while the GPU refines batch n the host prepares
-        // the initial flows of batch n + 1 (round 3 ran it inside the worker thread, in front of every batch -- ADVICE r2)
-        struct EpicInit { image_t *wx = nullptr, *wy = nullptr; int rc = SFA_OK; };
-        auto epic_init = [&](const Window &wd, sfa_ctx *ctx, EpicInit &out) {
-            int rc = SFA_OK;
-            image_t *iwx = nullptr, *iwy = nullptr;
-            const int f = wd.jet * steps;
-            {
-                const int a = (int)params.sequence_start + f * skip, b = a + ref * skip;
-                const color_image_t *un_ref = seq[wd.backward ? f + 2 * ref : f + ref];      // un_im[ref] / un_im_back[ref]: the window's reference frame, not normalised
-                epic_matches mt;
-                epic_edges ed;
-                epic_params_t ep;
-                epic_params_default(&ep);
-                ep.pref_nn = 25; ep.nn = 160; ep.coef_kernel = 1.1f;         // :271-275
-                // the resolution the interpolation runs at: cv::resize(img, img, Size(0, 0), dm_scale, dm_scale) makes cvRound(cols * dm_scale) x cvRound(rows * dm_scale)
-                const int ew = dm_scale != 1 ? (int)std::lrint(width * dm_scale) : (int)width, eh = dm_scale != 1 ? (int)std::lrint(height * dm_scale) : (int)height;
-                // ... while the reference allocates un_seq / wx and sizes the edge file with the TRUNCATED product (`color_image_new(width*dm_scale, height*dm_scale)`,
-                // slow_flow.cpp:584, :801-806).  Where the two differ (1023 * 0.5: 512 against 511) the reference copies a 512-wide image into a 511-wide one -- no defined
-                // result, and edge / match files laid out for either width would be misread by the other: refused by name
-                if (dm_scale != 1 && (ew != (int)(width * dm_scale) || eh != (int)(height * dm_scale))) {
-                    std::lock_guard<std::mutex> l(io_mu);
-                    std::cerr << "dm_scale " << dm_scale << ": " << width << " x " << height << " frames give a rescaled image of " << ew << " x " << eh << " (cv::resize rounds) but buffers and edge files of "
-                              << (int)(width * dm_scale) << " x " << (int)(height * dm_scale) << " (slow_flow.cpp:584 truncates): the reference has no defined result here; crop the frames to a multiple of 1 / dm_scale"
-                              << std::endl;
-                    rc = SFA_ERR_ARG;
-                } else
-                if (ew < 1 || eh < 1 || !read_matches((wd.backward ? matches_file(b, a) : matches_file(a, b)).c_str(), mt) ||
-                    !read_edges((wd.backward ? edges_file(b) : edges_file(a)).c_str(), ew, eh, ed)) rc = SFA_ERR_ARG;
-                else {
-                    // the reference hands epic() un_seq: the frame after img.convertTo(CV_8U, norm), i.e. rounded to nearest and saturated to 0..255,
-                    // 16-bit samples scaled by 1/255 first (slow_flow.cpp:472-474, :578-586) -- not the float frame the refinement reads
-                    const int fi = wd.backward ? f + 2 * ref : f + ref;
-                    // :571-573: GaussianBlur(sigma = 1 / sqrt(2 dm_scale), BORDER_REPLICATE) then resize by dm_scale, on the float frame (the pyramid's two
-                    // operators: sfa_gaussian_blur, sfa_resize_linear_fx with cv::resize's fx / fy form of the coordinate scale)
-                    color_image_t *small = nullptr;
-                    if (dm_scale != 1) {
-                        small = color_image_new(ew, eh);
-                        std::vector<float> tmp((size_t)un_ref->stride * un_ref->height);
-                        const float sigma = (float)(1 / sqrt(2 * dm_scale));
-                        float *src3[3] = {un_ref->c1, un_ref->c2, un_ref->c3}, *dst3[3] = {small->c1, small->c2, small->c3};
-                        for (int ch = 0; ch < 3 && rc == SFA_OK; ch++) {
-                            rc = sfa_gaussian_blur(ctx, tmp.data(), src3[ch], un_ref->width, un_ref->height, un_ref->stride, sigma);
-                            if (rc == SFA_OK) rc = sfa_resize_linear_fx(ctx, dst3[ch], ew, eh, small->stride, tmp.data(), un_ref->width, un_ref->height, un_ref->stride, dm_scale, dm_scale);
-                        }
-                    }
-                    const color_image_t *un_src = small ? small : un_ref;
-                    color_image_t *un8 = color_image_new(un_src->width, un_src->height);
-                    {
-                        const float norm = seq_maxval[fi] > 255 ? 1.0f / 255 : 1.0f;
-                        const size_t n3 = (size_t)3 * un_src->stride * un_src->height;
-                        for (size_t i = 0; i < n3; i++) {
-                            const float v = nearbyintf(un_src->c1[i] * norm);              // cvRound: to nearest, ties to even
-                            un8->c1[i] = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);       // saturate_cast<uchar>
-                        }
-                    }
-                    if (small) color_image_delete(small);
-                    color_image_t *lab = rgb_to_lab(un8);
-                    color_image_delete(un8);
-                    iwx = image_new(ew, eh); iwy = image_new(ew, eh);
-                    image_erase(iwx); image_erase(iwy);
-                    const int er = rc == SFA_OK ? epic(ctx, iwx, iwy, lab, mt, ed, &ep) : -1;
-                    color_image_delete(lab);
-                    if (er < 0) rc = rc == SFA_OK ? SFA_ERR_HIP : rc;
-                    else if (er > 0) { image_erase(iwx); image_erase(iwy); }  // no usable match: start from zero like deep_matching 0
-                    // :826-843: rescale flow.  fx, fy are quotients of ints; only when fx != 1 is the field resized (cv::resize to the frame's size: the ratio form)
-                    const float fx = (float)((int)width / ew), fy = (float)((int)height / eh);
-                    if (rc == SFA_OK && fx != 1) {
-                        image_t *fwx = image_new(width, height), *fwy = image_new(width, height);
-                        rc = sfa_resize_linear(ctx, fwx->data, width, height, fwx->stride, iwx->data, ew, eh, iwx->stride);
-                        if (rc == SFA_OK) rc = sfa_resize_linear(ctx, fwy->data, width, height, fwy->stride, iwy->data, ew, eh, iwy->stride);
-                        image_delete(iwx); image_delete(iwy);
-                        iwx = fwx; iwy = fwy;
-                    } else if (rc == SFA_OK && (ew != (int)width || eh != (int)height)) {
-                        // the reference would hand a field of the reduced size to a solver of the frames' size here (1 < width ratio < 2): it has no defined result
-                        std::lock_guard<std::mutex> l(io_mu);
-                        std::cerr << "dm_scale " << dm_scale << ": the frames are " << width << " wide, the interpolation " << ew << " -- the reference rescales by the integer ratio "
-                                  << (int)width / ew << " (slow_flow.cpp:827) and would keep the reduced field; use a dm_scale of 1 / n" << std::endl;
-                        rc = SFA_ERR_ARG;
-                    }
-                    image_mul_scalar(iwx, fx / steps);                      // :842-843
-                    image_mul_scalar(iwy, fy / steps);
-                    if (rc == SFA_OK && params.verbosity(WRITE_FILES) && !wd.backward)     // :845-858
-                        png_write((params.output + "tmp/frame_" + std::to_string(a) + "_INIT.png").c_str(), flowColorImg(iwx, iwy, 0));
-                }
-                if (rc != SFA_OK) { std::lock_guard<std::mutex> l(io_mu); std::cerr << "EpicFlow initialisation of jet " << wd.jet << " failed" << std::endl; }
-            }
-            out.wx = iwx; out.wy = iwy; out.rc = rc;
-        };
-        // forward and backward windows share one lockstep job (the channel weights are per window) unless the backward solver runs with
-        // different parameters ("method forward", :1019-1020): then one pass per direction
-        for (int dirpass = 0; dirpass < (backward_forward_only ? 2 : 1) && !failed; dirpass++) {
-            std::vector<size_t> mine;
-            for (size_t i = wp.lo; i < wp.hi; i++)
-                if (!backward_forward_only || (int)todo[i].backward == dirpass) mine.push_back(i);
-            if (mine.empty()) continue;
-            sfa_params sp = sfa_params_from_cfg(tp, dirpass == 1 ? backward_forward_only : false);
-            // one resident job for every full batch of this worker; a shorter last batch gets its own
-            sfa_job *job = nullptr;
-            int job_nb = 0;
-            int rc = SFA_OK;
-            auto batch_inits = [&](size_t b0) {
-                const int nb = (int)std::min((size_t)batch, mine.size() - b0);
-                std::vector<EpicInit> v(nb);
-                for (int e = 0; e < nb; e++) epic_init(todo[mine[b0 + e]], ectx, v[e]);
-                return v;
-            };
-            std::future<std::vector<EpicInit>> next_inits;
-            if (enable_dm) next_inits = std::async(std::launch::async, batch_inits, (size_t)0);
-            for (size_t b0 = 0; b0 < mine.size() && rc == SFA_OK && !failed; b0 += batch) {
-                const int nb = (int)std::min((size_t)batch, mine.size() - b0);
-                std::vector<EpicInit> inits;
-                if (enable_dm) {
-                    inits = next_inits.get();
-                    if (b0 + batch < mine.size()) next_inits = std::async(std::launch::async, batch_inits, b0 + batch);
-                }
-                const auto t0 = std::chrono::steady_clock::now();
-                if (!job || job_nb != nb) {
-                    if (job) sfa_job_destroy(job);
-                    job = nullptr;
-                    rc = sfa_job_create(ctx, &sp, width, height, nb, &job);
-                    job_nb = nb;
-                    if (rc == SFA_OK && out_alt_occ) rc = sfa_job_keep_alternation_occlusions(job, 1);
-                }
-                for (int e = 0; e < nb && rc == SFA_OK; e++) {
-                    const Window &wd = todo[mine[b0 + e]];
-                    const int f = wd.jet * steps;
-                    // the window's frames in the loaded sequence: forward seq[f + k]; backward seq_back[frames - 1 - f - 3*steps + k] = seq[f + 3*steps - k] (:590-591, :721-724)
-                    std::vector<int> idx(F);
-                    for (int k = 0; k < F; k++) idx[k] = (wd.backward ? f + 3 * steps - k : f + k) - (int)start_f - frame0;
-                    const float *chw[3] = {channel_weights->c1, channel_weights->c2, channel_weights->c3};
-                    image_t *iwx = enable_dm ? inits[e].wx : nullptr, *iwy = enable_dm ? inits[e].wy : nullptr;
-                    if (enable_dm && inits[e].rc != SFA_OK) rc = inits[e].rc;
-                    // only the forward solver gets the channel weights (:876 vs :1018); without raw weighting they are all ones (:597-598), which is
-                    // what a NULL pointer means to the library (x * 1.0f is exact: same bits, three planes less to read per pixel)
-                    if (rc == SFA_OK)
-                        rc = sfa_job_upload_resident(job, e, seq_dev[wp.gpu], idx.data(), F, iwx ? iwx->data : nullptr, iwy ? iwy->data : nullptr, seq[start_f]->stride,
-                                                     (wd.backward || !raw) ? nullptr : chw);
-                }
-                for (EpicInit &ei : inits) { if (ei.wx) image_delete(ei.wx); if (ei.wy) image_delete(ei.wy); }
-                if (rc == SFA_OK) rc = sfa_job_run(job);
-                std::vector<std::shared_ptr<WindowResult>> results;
-                for (int e = 0; e < nb && rc == SFA_OK; e++) {
-                    const Window &wd = todo[mine[b0 + e]];
-                    std::shared_ptr<WindowResult> r(new WindowResult());
-                    r->index = mine[b0 + e];
-                    r->wx = image_new(width, height); r->wy = image_new(width, height);
-                    image_erase(r->wx); image_erase(r->wy);
-                    float change[2];
-                    rc = sfa_job_download(job, e, r->wx->data, r->wy->data, r->wx->stride, change);
-                    if (rc == SFA_OK && out_occ && !wd.backward) {                   // getOcclusions() of the forward solver (:893)
-                        r->occ = image_new(width, height);
-                        image_erase(r->occ);
-                        rc = sfa_job_download_occlusions(job, e, r->occ->data, r->occ->stride);
-                    }
-                    for (int a = 1; a < sp.niter_alter && rc == SFA_OK && out_alt_occ && !wd.backward; a++) {
-                        image_t *o = image_new(width, height);
-                        image_erase(o);
-                        r->alt_occ.push_back(o);
-                        rc = sfa_job_download_alternation_occlusions(job, e, a, o->data, o->stride);
-                    }
-                    results.push_back(r);
-                }
-                const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                if (rc == SFA_OK)
-                    for (auto &r : results) {
-                        todo[r->index].seconds = secs / nb;
-                        todo[r->index].gpu = device;
-                        out_pool.submit([&emit, r] { emit(r); });
-                    }
-                std::lock_guard<std::mutex> l(io_mu);
-                if (rc != SFA_OK) { std::cerr << "GPU " << device << ": " << sfa_last_error(ctx) << std::endl; failed = true; }
-                else for (int e = 0; e < nb; e++) {
-                    const Window &wd = todo[mine[b0 + e]];
-                    const int f = wd.jet * steps;
-                    std::cout << (wd.backward ? "Backward" : "Forward") << " flow from frame " << start + f * skip << " to " << start + f * skip + steps * skip
-                              << " finished! (GPU " << wp.gpu << " = device " << device << ", " << secs / nb << " s per window in a batch of " << nb << ")" << std::endl;
-                }
-            }
-            if (next_inits.valid())                                                  // left early: the batch prepared ahead is not used
-                for (EpicInit &ei : next_inits.get()) { if (ei.wx) image_delete(ei.wx); if (ei.wy) image_delete(ei.wy); }
-            if (job) sfa_job_destroy(job);
-        }
-        if (ectx) sfa_ctx_destroy(ectx);
-        sfa_ctx_destroy(ctx);
-    };
-    const auto t_compute = std::chrono::steady_clock::now();
-    std::vector<std::thread> th;
-    for (const WorkerPlan &wp : plan) th.emplace_back(worker, wp);
-    for (auto &t : th) t.join();
-    const double compute_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_compute).count();
-    for (auto &t : up) if (t.joinable()) t.join();
-    if (ingest_failed()) failed = true;
-    out_pool.wait_all();
-    const double total_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-
-    // the gathered per-window timings (the only cross-GPU exchange of the path) and where the wall time of the run went
-    {
-        std::ofstream tj((params.output + "timings.json").c_str());
-        tj << "[";
-        for (size_t i = 0; i < todo.size(); i++)
-            tj << (i ? "," : "") << "\n  {\"jet\": " << todo[i].jet << ", \"direction\": \"" << (todo[i].backward ? "backward" : "forward") << "\", \"gpu\": " << todo[i].gpu
-               << ", \"seconds\": " << todo[i].seconds << ", \"flo\": \"" << todo[i].out << "\""
-               << (todo[i].epe >= 0 ? ", \"epe\": " + std::to_string(todo[i].epe) + ", \"aae\": " + std::to_string(todo[i].aae) : string()) << "}";
-        tj << "\n]\n";
-        std::ofstream rj((params.output + "run.json").c_str());
-        rj << "{\"windows\": " << todo.size() << ", \"gpus\": " << ngpu << ", \"streams\": " << streams << ", \"batch\": " << batch << ", \"io_threads\": " << io_threads
-           << ", \"decode_seconds\": " << decode_seconds << ", \"normalize_seconds\": " << normalize_seconds << ", \"ingest_seconds\": " << ingest_seconds << ", \"refine_seconds\": " << compute_seconds << ", \"total_seconds\": " << total_seconds;
-        // per GPU: the frames it was sent (its windows' frames + halo), when the last of them had arrived, when its frames were normalised and when its first worker
-        // began to refine -- all in seconds since the run began.  The whole sequence is "sequence_bytes"
-        double last_upload = 0, first_refine = -1;
-        rj << ", \"sequence_bytes\": " << (double)n_loaded * 3 * width * height * sizeof(float) << ", \"per_gpu\": [";
-        for (int g = 0; g < ngpu; g++) {
-            rj << (g ? ", " : "") << "{\"gpu\": " << g << ", \"device\": " << device_of(g) << ", \"frames\": [" << gpu_frames[g].lo << ", " << gpu_frames[g].hi << "], \"upload_bytes\": " << upload_bytes[g]
-               << ", \"upload_done_s\": " << upload_done_s[g] << ", \"ready_s\": " << ready_s[g] << ", \"first_refine_s\": " << first_refine_s[g] << "}";
-            last_upload = std::max(last_upload, upload_done_s[g]);
-            if (first_refine_s[g] >= 0 && (first_refine < 0 || first_refine_s[g] < first_refine)) first_refine = first_refine_s[g];
-        }
-        rj << "], \"first_refine_s\": " << first_refine << ", \"last_upload_done_s\": " << last_upload << "}\n";
+    std::atomic<bool> failed;
+    void fail(const string &message) {           // on stderr; the pass ends with exit code 5
+        std::lock_guard<std::mutex> l(io_mu);
+        std::cerr << message << std::endl;
+        failed = true;
     }
-    release_sequences();
-    for (unsigned f = start_f; f < end_f; f++) color_image_delete(seq[f]);
-    for (auto g : gt) if (g) { image_delete(g[0]); image_delete(g[1]); free(g); }
-    color_image_delete(channel_weights);
-    return failed ? 5 : 0;
+};
+
+// the windows `mine` of one worker in lockstep batches of gpu_batch on ONE resident job (re-created only for a shorter last batch); with deep_matching 1 the initial flows are
+// prepared one batch ahead on a helper thread (ectx: the library's contexts are thread-compatible, not thread-safe); the results go to the output pool meanwhile
+static void refine_windows(Refinement &rf, const WorkerPlan &wp, sfa_ctx *ctx, sfa_ctx *ectx, const sfa_params &sp, const std::vector<size_t> &mine) {
+    const Run &run = rf.run;
+    const int device = run.device_of(wp.gpu), width = rf.seq.width, height = rf.seq.height, F = 2 * run.steps + 1;
+    const int first = (int)run.layout.start_f + rf.seq.gpu_frames[wp.gpu].lo;       // the GPU's resident sequence starts at this frame
+    Job job;
+    int job_nb = 0, rc = SFA_OK;
+    auto batch_inits = [&](size_t b0) {
+        std::vector<EpicInit> v(std::min((size_t)run.batch, mine.size() - b0));
+        for (size_t e = 0; e < v.size(); e++)
+            if ((v[e].rc = interpolate_matches(run, rf.seq, rf.todo[mine[b0 + e]], ectx, rf.io_mu, v[e].wx, v[e].wy)) != SFA_OK) {
+                std::lock_guard<std::mutex> l(rf.io_mu);
+                std::cerr << "EpicFlow initialisation of jet " << rf.todo[mine[b0 + e]].jet << " failed" << std::endl;
+            }
+        return v;
+    };
+    std::future<std::vector<EpicInit>> next_inits;                                   // (a batch prepared ahead and not used is released with it)
+    if (run.deep_matching) next_inits = std::async(std::launch::async, batch_inits, (size_t)0);
+    for (size_t b0 = 0; b0 < mine.size() && rc == SFA_OK && !rf.failed; b0 += run.batch) {
+        const int nb = (int)std::min((size_t)run.batch, mine.size() - b0);
+        std::vector<EpicInit> inits;
+        if (run.deep_matching) {
+            inits = next_inits.get();
+            if (b0 + run.batch < mine.size()) next_inits = std::async(std::launch::async, batch_inits, b0 + run.batch);
+        }
+        const double t0 = now_s();
+        if (!job || job_nb != nb) {
+            job.reset();
+            sfa_job *j = nullptr;
+            rc = sfa_job_create(ctx, &sp, width, height, nb, &j);
+            job.reset(j);
+            job_nb = nb;
+            if (rc == SFA_OK && run.out_alt_occ) rc = sfa_job_keep_alternation_occlusions(j, 1);
+        }
+        for (int e = 0; e < nb && rc == SFA_OK; e++) {
+            const Window &wd = rf.todo[mine[b0 + e]];
+            std::vector<int> idx(F);
+            for (int k = 0; k < F; k++) idx[k] = window_tap(wd.jet, wd.backward, run.steps, k, first);
+            const float *chw[3] = {rf.channel_weights->c1, rf.channel_weights->c2, rf.channel_weights->c3};
+            const image_t *iwx = run.deep_matching ? inits[e].wx.get() : nullptr, *iwy = run.deep_matching ? inits[e].wy.get() : nullptr;
+            if (run.deep_matching) rc = inits[e].rc;
+            // only the forward solver gets the channel weights (:876 vs :1018); without raw weighting they are all ones (:597-598), which is
+            // what a NULL pointer means to the library (x * 1.0f is exact: same bits, three planes less to read per pixel)
+            if (rc == SFA_OK)
+                rc = sfa_job_upload_resident(job.get(), e, rf.seq.gpu(wp.gpu).resident.get(), idx.data(), F, iwx ? iwx->data : nullptr, iwy ? iwy->data : nullptr,
+                                             rf.seq.frames[run.layout.start_f]->stride, (wd.backward || !run.raw) ? nullptr : chw);
+        }
+        if (rc == SFA_OK) rc = sfa_job_run(job.get());
+        std::vector<std::shared_ptr<WindowResult>> results;
+        for (int e = 0; e < nb && rc == SFA_OK; e++) {
+            const bool forward = !rf.todo[mine[b0 + e]].backward;
+            std::shared_ptr<WindowResult> r(new WindowResult());
+            r->index = mine[b0 + e];
+            r->wx = zero_image(width, height); r->wy = zero_image(width, height);
+            float change[2];
+            rc = sfa_job_download(job.get(), e, r->wx->data, r->wy->data, r->wx->stride, change);
+            if (rc == SFA_OK && run.out_occ && forward) {                           // getOcclusions() of the forward solver (:893)
+                r->occ = zero_image(width, height);
+                rc = sfa_job_download_occlusions(job.get(), e, r->occ->data, r->occ->stride);
+            }
+            for (int a = 1; a < sp.niter_alter && rc == SFA_OK && run.out_alt_occ && forward; a++) {
+                r->alt_occ.push_back(zero_image(width, height));
+                rc = sfa_job_download_alternation_occlusions(job.get(), e, a, r->alt_occ.back()->data, r->alt_occ.back()->stride);
+            }
+            results.push_back(r);
+        }
+        const double secs = now_s() - t0;
+        if (rc != SFA_OK) { rf.fail("GPU " + std::to_string(device) + ": " + sfa_last_error(ctx)); break; }
+        for (auto &r : results) {
+            Window &wd = rf.todo[r->index];
+            wd.seconds = secs / nb;
+            wd.gpu = device;
+            rf.out_pool.submit([&rf, &wd, r] { if (!emit(rf.run, wd, *r, rf.gt[wd.jet], rf.seq.width, rf.seq.height)) rf.fail("cannot write the results of " + wd.out); });
+        }
+        std::lock_guard<std::mutex> l(rf.io_mu);
+        for (int e = 0; e < nb; e++) {
+            const Window &wd = rf.todo[mine[b0 + e]];
+            const JetFrames n = jet_frames(run.start, wd.jet, run.steps, run.skip);
+            std::cout << (wd.backward ? "Backward" : "Forward") << " flow from frame " << n.from << " to " << n.to
+                      << " finished! (GPU " << wp.gpu << " = device " << device << ", " << secs / nb << " s per window in a batch of " << nb << ")" << std::endl;
+        }
+    }
+}
+
+// one worker: its contexts, then its windows once its GPU's frames are resident -- forward and backward windows share one lockstep job (the channel weights
+// are per window) unless the backward solver runs with different parameters ("method forward", :1019-1020): then one pass per direction
+static void refine_worker(Refinement &rf, const WorkerPlan &wp) {
+    if (wp.lo >= wp.hi) return;
+    const Run &run = rf.run;
+    const Ctx ctx = new_ctx(run.device_of(wp.gpu));
+    const Ctx ectx = ctx && run.deep_matching ? new_ctx(run.device_of(wp.gpu)) : Ctx();   // the EpicFlow helper's context (deep_matching 1 only)
+    if (!ctx || (run.deep_matching && !ectx)) return rf.fail(sfa_last_error(nullptr));
+    (void)sfa_ctx_set_verbose(ctx.get(), run.verbose_changes ? 1 : 0);
+    if (!rf.seq.wait_gpu(wp.gpu)) { rf.failed = true; return; }
+    ParameterList tp(run.p);                                                         // one copy per thread (:708), with the published normalisation
+    for (int dirpass = 0; dirpass < (run.forward_only ? 2 : 1) && !rf.failed; dirpass++) {
+        std::vector<size_t> mine;
+        for (size_t i = wp.lo; i < wp.hi; i++)
+            if (!run.forward_only || (int)rf.todo[i].backward == dirpass) mine.push_back(i);
+        if (!mine.empty()) refine_windows(rf, wp, ctx.get(), ectx.get(), sfa_params_from_cfg(tp, dirpass == 1), mine);
+    }
+}
+
+// the gathered per-window timings (the only cross-GPU exchange of the path) and where the wall time of the run went (seconds)
+static void write_timings(const Run &run, const std::vector<Window> &todo, const Sequence &seq, double decode, double normalize, double ingest, double refine, double total) {
+    std::ofstream tj((run.output + "timings.json").c_str());
+    tj << "[";
+    for (size_t i = 0; i < todo.size(); i++)
+        tj << (i ? "," : "") << "\n  {\"jet\": " << todo[i].jet << ", \"direction\": \"" << (todo[i].backward ? "backward" : "forward") << "\", \"gpu\": " << todo[i].gpu
+           << ", \"seconds\": " << todo[i].seconds << ", \"flo\": \"" << todo[i].out << "\""
+           << (todo[i].epe >= 0 ? ", \"epe\": " + std::to_string(todo[i].epe) + ", \"aae\": " + std::to_string(todo[i].aae) : string()) << "}";
+    tj << "\n]\n";
+    std::ofstream rj((run.output + "run.json").c_str());
+    rj << "{\"windows\": " << todo.size() << ", \"gpus\": " << run.ngpu << ", \"streams\": " << run.streams << ", \"batch\": " << run.batch << ", \"io_threads\": " << run.io_threads
+       << ", \"decode_seconds\": " << decode << ", \"normalize_seconds\": " << normalize << ", \"ingest_seconds\": " << ingest << ", \"refine_seconds\": " << refine << ", \"total_seconds\": " << total;
+    // per GPU: the frames it was sent (its windows' frames + halo), when the last of them had arrived, when its frames were normalised and when its first worker
+    // began to refine -- all in seconds since the run began.  The whole sequence is "sequence_bytes"
+    double last_upload = 0, first_refine = -1;
+    rj << ", \"sequence_bytes\": " << (double)(run.layout.end_f - run.layout.start_f) * 3 * seq.width * seq.height * sizeof(float) << ", \"per_gpu\": [";
+    for (int g = 0; g < run.ngpu; g++) {
+        const Sequence::Gpu &t = seq.gpu(g);
+        rj << (g ? ", " : "") << "{\"gpu\": " << g << ", \"device\": " << run.device_of(g) << ", \"frames\": [" << seq.gpu_frames[g].lo << ", " << seq.gpu_frames[g].hi << "], \"upload_bytes\": " << t.upload_bytes
+           << ", \"upload_done_s\": " << t.upload_done_s << ", \"ready_s\": " << t.ready_s << ", \"first_refine_s\": " << t.first_refine_s << "}";
+        last_upload = std::max(last_upload, t.upload_done_s);
+        if (t.first_refine_s >= 0 && (first_refine < 0 || t.first_refine_s < first_refine)) first_refine = t.first_refine_s;
+    }
+    rj << "], \"first_refine_s\": " << first_refine << ", \"last_upload_done_s\": " << last_upload << "}\n";
+}
+
+// One pass over the sequence at one frame rate: the body of the reference's adFR loop (slow_flow.cpp:367-1060), stage by stage
+static int run_sequence(ParameterList &params, const string &sequence_path, const string &format, int skip, const RunOptions &opt) {
+    const double t_begin = now_s();
+    const Run run(params, format, skip, opt);
+    if (run.batch < 1 || run.batch > 128) {                                          // a job's windows-still-iterating mask is two 64-bit words: refused by name, not clamped
+        std::cerr << "gpu_batch " << run.batch << " is out of range: a lockstep job takes 1 .. 128 windows (more windows run as several jobs: gpu_streams, batches per worker)" << std::endl;
+        return 2;
+    }
+    mkdirs(run.output);
+    if (run.layout.start_f > run.layout.end_f) return 0;
+    if (run.deep_matching && !deep_matching_inputs_exist(run, opt.resume_frame)) return 2;
+    if (run.ndev <= 0) { std::cerr << "no HIP device: slowflow_amd has no CPU fallback" << std::endl; return 4; }
+    if (!run.oversubscribe && run.dev0 >= run.ndev) { std::cerr << "gpu_device " << run.dev0 << " does not exist (" << run.ndev << " device(s))" << std::endl; return 4; }
+
+    // the windows and who refines them -- known before a frame is read, so that every GPU is sent only the frames ITS windows read
+    std::vector<Window> todo = windows_to_refine(run, opt.resume_frame);
+    const std::vector<WorkerPlan> plan = plan_workers(todo.size(), run.ngpu, run.streams);
+    std::vector<std::pair<int, int>> spans;                                          // relative to the loaded range [start_f, end_f)
+    for (const Window &wd : todo) spans.push_back(window_span(wd.jet, wd.backward, run.steps, (int)run.layout.start_f));
+    const std::vector<FrameRange> gpu_frames = plan_frames(spans, plan, run.ngpu, (int)(run.layout.end_f - run.layout.start_f));
+
+    Sequence seq(run, gpu_frames, t_begin);                                          // one uploader thread per GPU, from now on
+    double decoded_at = 0;
+    if (const int rc = read_frames(run, sequence_path, format, seq, decoded_at)) return rc;
+    ColorImage channel_weights(color_image_new(seq.width, seq.height));              // :597-598 (all ones without raw weighting)
+    std::fill(channel_weights->c1, channel_weights->c1 + (size_t)3 * channel_weights->stride * seq.height, 1.0f);
+    if (run.raw) rawWeighting(channel_weights.get(), run.red_x, run.red_y, run.raw_weight);   // :599-600
+    std::vector<Flow> gt(params.Jets);
+    if (!run.file_gt.empty())
+        if (const int rc = load_ground_truth(run, gt)) return rc;
+
+    // the uploaders have been uploading beside the decoding; what is left of the ingest is the normalisation (not needed when -resume left nothing to refine)
+    const double t_norm = now_s();
+    double avg[3], sd[3];
+    if ((todo.empty() || !seq.wait_statistics(avg, sd)) && seq.report_errors()) return 4;
+    if (!todo.empty()) publish_normalization(params, avg, sd);                       // the slow_flow_img_norm_* parameters (variational_mt.cpp:71-84)
+    const double normalize_seconds = now_s() - t_norm;
+    std::ofstream((run.output + "config.cfg").c_str()) << "# SlowFlow variational estimation\n" << params;   // :684-688
+    const double ingest_seconds = now_s() - t_begin;
+
+    if (run.out_occ) mkdirs(run.output + "occlusion/");                              // :676-677
+    if (run.out_alt_occ || run.deep_matching) mkdirs(run.output + "tmp/");
+    TaskPool out_pool(run.io_threads);
+    Refinement rf{run, seq, channel_weights.get(), gt, todo, out_pool, {}, {false}};
+    const double t_compute = now_s();
+    std::vector<std::thread> th;
+    for (const WorkerPlan &wp : plan) th.emplace_back(refine_worker, std::ref(rf), wp);
+    for (auto &t : th) t.join();
+    const double compute_seconds = now_s() - t_compute;
+    if (seq.report_errors()) rf.failed = true;
+    out_pool.wait_all();
+    write_timings(run, todo, seq, decoded_at - t_begin, normalize_seconds, ingest_seconds, compute_seconds, now_s() - t_begin);
+    return rf.failed ? 5 : 0;
 }
 
 int main(int argc, char **argv) {

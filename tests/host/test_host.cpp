@@ -326,6 +326,47 @@ int main(int argc, char **argv) {
         const std::vector<FrameRange> none = plan_frames({}, plan_workers(0, 4, 2), 4, n_frames);
         for (const FrameRange &f : none) CHECK(f.lo == f.hi);
     }
+    // ---- shard.h: the frames and jets a pass loads and the frames each window reads (slow_flow.cpp:411, :418-424, :590-591, :721-724), by hand ------
+    {
+        auto same = [](const SequenceLayout &l, int frames, unsigned f0, unsigned f1, unsigned j0, unsigned j1) {
+            return l.frames == frames && l.start_f == f0 && l.end_f == f1 && l.start_j == j0 && l.end_j == j1;
+        };
+        // S = 2 (steps 1), 4 jets: 1 + (4 + 2) * 1 = 7 frames
+        CHECK(same(plan_sequence(4, 1, false, -1), 7, 0, 7, 0, 4));
+        CHECK(same(plan_sequence(4, 1, true, -1), 7, 0, 7, 0, 4));               // -resume alone loads everything
+        CHECK(same(plan_sequence(4, 1, false, 2), 7, 0, 7, 0, 4));               // a jet without -resume narrows nothing
+        CHECK(same(plan_sequence(4, 1, true, 2), 7, 2, 6, 2, 3));                // -jet 2: frames 2 .. 1 + 5 - 1
+        CHECK(same(plan_sequence(4, 1, true, 3), 7, 3, 7, 3, 4));                // the last jet: min(7, 1 + 6)
+        CHECK(same(plan_sequence(4, 1, true, 4), 7, 4, 7, 4, 4));                // past the last jet: no windows, frames 4 .. 6 still load
+        CHECK(same(plan_sequence(4, 1, true, 7), 7, 7, 7, 7, 4));                // start_f == end_f: nothing loaded
+        CHECK(plan_sequence(4, 1, true, 8).start_f > plan_sequence(4, 1, true, 8).end_f);   // 8 > 7: the pass returns at once
+        // S = 3 (steps 2), 5 jets: 1 + 7 * 2 = 15 frames
+        CHECK(same(plan_sequence(5, 2, false, -1), 15, 0, 15, 0, 5));
+        CHECK(same(plan_sequence(5, 2, true, 1), 15, 2, 9, 1, 2));               // min(15, 1 + 4 * 2)
+        CHECK(same(plan_sequence(5, 2, true, 4), 15, 8, 15, 4, 5));              // the last jet: min(15, 1 + 7 * 2)
+        CHECK(same(plan_sequence(5, 2, true, 5), 15, 10, 15, 5, 5));             // past the last jet: empty jet range
+        CHECK(plan_sequence(5, 2, true, 8).start_f == 16 && plan_sequence(5, 2, true, 8).end_f == 15);
+        // inclusive spans as plan_frames takes them: forward j*steps .. +2*steps, backward j*steps + steps .. +3*steps, from frame `first`
+        CHECK(window_span(3, false, 1, 0) == std::make_pair(3, 5) && window_span(3, true, 1, 0) == std::make_pair(4, 6));
+        CHECK(window_span(1, false, 2, 0) == std::make_pair(2, 6) && window_span(1, true, 2, 0) == std::make_pair(4, 8));
+        CHECK(window_span(1, false, 2, 2) == std::make_pair(0, 4) && window_span(1, true, 2, 2) == std::make_pair(2, 6));   // -jet 1 loads 2 .. 8
+        // the frame of each tap: forward ascending, backward descending from the end of the jet; tap `steps` is the reference frame
+        const int fwd2[5] = {2, 3, 4, 5, 6}, bwd2[5] = {8, 7, 6, 5, 4}, fwd1[3] = {3, 4, 5}, bwd1[3] = {6, 5, 4};
+        for (int k = 0; k < 5; k++) CHECK(window_tap(1, false, 2, k, 0) == fwd2[k] && window_tap(1, true, 2, k, 0) == bwd2[k]);
+        for (int k = 0; k < 5; k++) CHECK(window_tap(1, false, 2, k, 2) == fwd2[k] - 2 && window_tap(1, true, 2, k, 3) == bwd2[k] - 3);
+        for (int k = 0; k < 3; k++) CHECK(window_tap(3, false, 1, k, 0) == fwd1[k] && window_tap(3, true, 1, k, 0) == bwd1[k]);
+        CHECK(window_tap(1, false, 2, 2, 0) == 4 && window_tap(1, true, 2, 2, 0) == 6);
+        for (int k = 0; k < 5; k++) {                                             // every tap lies in the window's span
+            const std::pair<int, int> f = window_span(1, false, 2, 0), b = window_span(1, true, 2, 0);
+            CHECK(f.first <= window_tap(1, false, 2, k, 0) && window_tap(1, false, 2, k, 0) <= f.second);
+            CHECK(b.first <= window_tap(1, true, 2, k, 0) && window_tap(1, true, 2, k, 0) <= b.second);
+        }
+        // the sequence frame numbers of a jet's outputs: start + j*steps*skip and steps*skip later
+        CHECK(jet_frames(10, 3, 2, 4).from == 34 && jet_frames(10, 3, 2, 4).to == 42);
+        CHECK(jet_frames(1, 0, 1, 1).from == 1 && jet_frames(1, 0, 1, 1).to == 2);
+        CHECK(jet_frames(3000, 2, 1, 3).from == 3006 && jet_frames(3000, 2, 1, 3).to == 3009);
+        CHECK(jet_frames(10, 3, 2, 4).listed_from == 16 && jet_frames(3000, 2, 1, 3).listed_from == 3002);   // the -resume message's frame: no skip (:712-716)
+    }
     // ---- shard.h: adaptive frame rates (slow_flow.cpp:322-352), evaluated by hand from the reference's text -----------------------------
     {
         AdaptiveRates r = adaptive_rates(1.0, 2.0, 4, 10, 1);      // hfr = round(2/1) = 2 (10 % 2 == 0); lfr = min(10, 8) = 8 -> 9 -> 10; min(10/1, 10)
