@@ -317,6 +317,51 @@ int  sfa_job_download_alternation_occlusions(sfa_job *job, int b, int alter, flo
 double sfa_job_mpix_iters(const sfa_job *job);       /* sum over the job's SOR solves of w*h*K / 1e6, per run */
 double sfa_job_device_bytes(const sfa_job *job);     /* device memory the job holds right now (arena + solver workspaces shaped so far) */
 
+/* ---- the device seam: frames, initial flow and results that already live in the job's GPU memory ---------------------------------
+ * Everything above takes HOST planes: sfa_job_upload / sfa_sequence_upload copy pageable host memory at a host stride and wait for the stream,
+ * sfa_job_upload_resident still takes the initial flow from the host, sfa_job_download* copy plane by plane and wait.  The entry points below take
+ * DEVICE pointers of the context's GPU (a decoder's output, a network's flow, a torch tensor's data_ptr) and move the data with one kernel launch per
+ * call (csrc/device_io.hip).  They are asynchronous on the context's stream and never wait for it; order them against the caller's own stream with
+ * sfa_ctx_wait_stream / sfa_ctx_signal_stream.  They only convert ((float) of the element, no scaling) and move: a job filled through them gives the
+ * bits of the same job filled through the host entry points.
+ * Refused with SFA_ERR_ARG, by the argument's name and before anything is launched: a pointer that hipPointerGetAttributes does not report as
+ * device memory of the context's GPU (host and managed memory, other GPUs) or whose view leaves its allocation, an unknown element type, a column
+ * stride < 1, any negative stride, windows outside the batch, and download destinations that the checks below cannot prove free of overlap.
+ * sfa_job_run takes its break decisions on the host, so none of this can be captured into a HIP graph; nothing here attempts it. */
+typedef enum { SFA_DEV_F32 = 0, SFA_DEV_U8 = 1, SFA_DEV_U16 = 2 } sfa_dev_dtype;
+/* Where element (window, frame, channel, row, column) of the caller's frames lies: strides in ELEMENTS of `dtype`, 64-bit.  Planar [B,F,3,H,W],
+ * interleaved [B,F,H,W,3] (channel 1, column 3), a crop of a larger tensor (row > width) and frames shared by windows (window < F frames, or 0)
+ * are all this one description. */
+typedef struct sfa_dev_layout { int dtype; long long window, frame, channel, row, column; } sfa_dev_layout;
+/* contiguous planar fp32 [n][n_frames][3][h][w] */
+void sfa_dev_layout_default(sfa_dev_layout *l, int w, int h, int n_frames);
+/* Replaces sfa_job_upload's frame copies (3 F hipMemcpy2DAsync per window + hipStreamSynchronize) for the windows [b0, b0 + n): one launch of
+ * k_pack_frames.  Columns >= width of the job's planes are not written.  chw: NULL (ones) or 3 HOST planes of h * stride floats,
+ * stride = 4 * ceil(w / 4) as color_image_new lays them out, attached to every window of the call (they go through a pinned staging copy).
+ * Unlike sfa_job_upload with wx = wy = NULL this call leaves the windows' initial flow as it is: on a job that held other windows before, follow it
+ * with sfa_job_set_flow_device (NULL for zeros), or the run starts from the flow uploaded for the previous windows. */
+int  sfa_job_upload_device(sfa_job *job, int b0, int n, const void *frames_dev, const sfa_dev_layout *layout, const float *const chw[3]);
+/* Replaces the wx / wy arguments of sfa_job_upload and sfa_job_upload_resident (which may be called with NULL, NULL before): the initial flow of
+ * the windows [b0, b0 + n) from fp32 device memory, strides[4] = element strides of (window, u|v, row, column); flow_dev NULL = zeros (strides
+ * ignored).  One launch of k_pack_flow. */
+int  sfa_job_set_flow_device(sfa_job *job, int b0, int n, const float *flow_dev, const long long strides[4]);
+/* Replaces sfa_job_download + sfa_job_download_occlusions (2 + 1 hipMemcpy2DAsync per window + a stream wait each): (u, v) of the windows
+ * [b0, b0 + n) into flow_dev (strides[4] as above) and, where occ_dev != NULL, getOcclusions() into occ_dev (occ_strides[3] = window, row, column),
+ * one launch of k_unpack_planes.  Accepted destinations: every (window, plane) occupies a byte range of its own, or flow and occlusions lie apart and
+ * each is a layout whose strides, sorted, each exceed the extent of the smaller ones (a slice of a larger tensor, channels-last ...). */
+int  sfa_job_download_device(sfa_job *job, int b0, int n, float *flow_dev, const long long strides[4], float *occ_dev, const long long occ_strides[3]);
+/* The change norms sfa_job_download returns, for the windows [b0, b0 + n) of the last run: out[2 i], out[2 i + 1].  Host record, no copy, no wait. */
+int  sfa_job_changes(const sfa_job *job, int b0, int n, float *out);
+/* Replaces sfa_sequence_upload for the frames [f0, f0 + n): frame i at frames_dev + i * layout->frame (layout->window is not used). */
+int  sfa_sequence_upload_device(sfa_sequence *seq, int f0, int n, const void *frames_dev, const sfa_dev_layout *layout);
+/* Ordering against a stream of the caller (a hipStream_t; NULL = the device's null stream, which is torch's default stream).  wait: the context's
+ * stream waits for everything submitted to `stream` so far; signal: `stream` waits for everything submitted to the context's stream so far.  Both
+ * record an event and return at once.  With wait before the first and signal after the last call that touches a buffer, work the caller submits to
+ * its stream afterwards -- a free or reuse by a stream-ordered allocator included -- is ordered after the library's last access.  The context keeps
+ * its own stream; one context per host thread, as before.  `stream` must be a stream of the context's GPU: the handle is not checked. */
+int  sfa_ctx_wait_stream(sfa_ctx *ctx, void *stream);
+int  sfa_ctx_signal_stream(sfa_ctx *ctx, void *stream);
+
 /* SOR-only resident batch: `batch` independent systems of one size */
 typedef struct sfa_sor_batch sfa_sor_batch;
 int  sfa_sor_batch_create(sfa_ctx *ctx, int w, int h, int batch, sfa_sor_batch **out);

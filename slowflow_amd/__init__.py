@@ -102,6 +102,7 @@ EXPORTS = [
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
     "sfa_job_create", "sfa_job_destroy", "sfa_job_upload", "sfa_job_upload_resident", "sfa_job_reset_flow", "sfa_job_run", "sfa_job_download", "sfa_job_download_occlusions", "sfa_job_keep_alternation_occlusions", "sfa_job_download_alternation_occlusions", "sfa_job_mpix_iters", "sfa_job_device_bytes",
+    "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
@@ -238,6 +239,17 @@ class Context:
 
     def sync(self):
         self._ck(lib().sfa_ctx_sync(self.h), "sfa_ctx_sync")
+
+    # ---- ordering against a stream of the caller (slowflow_amd/device.py) ------------------------
+    def wait_stream(self, stream=None):
+        """the context's stream waits for what `stream` holds now (None / 0: the null stream; an int handle; a torch.cuda.Stream)"""
+        from . import device
+        device.wait_stream(self, stream)
+
+    def signal_stream(self, stream=None):
+        """`stream` waits for what the context's stream holds now"""
+        from . import device
+        device.signal_stream(self, stream)
 
     # ---- stage entry points (host planes) -------------------------------------------------------
     def image_warp(self, src3, wx, wy, w, factor, want_mask=True):
@@ -550,6 +562,7 @@ class Job:
 
     def __init__(self, ctx, params, w, h, batch=1):
         self.ctx, self.w, self.h, self.batch = ctx, w, h, batch
+        self.n_frames = 2 * (params.S - 1) + 1
         self.h_ = C.c_void_p()
         ctx._ck(lib().sfa_job_create(ctx.h, C.byref(params), w, h, batch, C.byref(self.h_)), "sfa_job_create")
         ctx._children.add(self)
@@ -566,6 +579,27 @@ class Job:
         cw = (_f * 3)(fptr(chw[0]), fptr(chw[1]), fptr(chw[2])) if chw is not None else None
         self.ctx._ck(lib().sfa_job_upload_resident(self.h_, b, seq.h_, idx, len(frame_index), fptr(wx) if wx is not None else None,
                                                    fptr(wy) if wy is not None else None, stride_of(self.w), cw), "sfa_job_upload_resident")
+
+    # ---- the device seam (slowflow_amd/device.py): objects with __cuda_array_interface__, asynchronous on the context's stream ----
+    def upload_device(self, frames, b0=0, chw=None, channels_last=None):
+        """frames [B,F,3,H,W] or [B,F,H,W,3] (fp32 / uint8 / uint16, any strides) in device memory -> windows b0 .. b0 + B - 1"""
+        from . import device
+        device.job_upload_device(self, frames, b0, chw, channels_last)
+
+    def set_flow_device(self, flow, b0=0, n=None):
+        """the initial flow of windows b0 .. from an fp32 device array [B,2,H,W]; None: zeros for n windows (default: all from b0)"""
+        from . import device
+        device.job_set_flow_device(self, flow, b0, n)
+
+    def download_device(self, out_flow, out_occ=None, b0=0):
+        """(u, v) of windows b0 .. b0 + B - 1 into the fp32 device array out_flow [B,2,H,W], the occlusion labels into out_occ [B,H,W]"""
+        from . import device
+        device.job_download_device(self, out_flow, out_occ, b0)
+
+    def changes(self, b0=0, n=None):
+        """the change norms of the last run as a numpy array (n, 2): what download() returns per window, without a download"""
+        from . import device
+        return device.job_changes(self, b0, n)
 
     def run(self):
         self.ctx._ck(lib().sfa_job_run(self.h_), "sfa_job_run")
@@ -632,6 +666,11 @@ class Sequence:
 
     def upload(self, f, frame3):
         self.ctx._ck(lib().sfa_sequence_upload(self.h_, f, fptr(frame3), frame3.shape[2]), "sfa_sequence_upload")
+
+    def upload_device(self, frames, f0=0, channels_last=None):
+        """frames [N,3,H,W] or [N,H,W,3] in device memory -> sequence frames f0 .. f0 + N - 1 (slowflow_amd/device.py); asynchronous"""
+        from . import device
+        device.sequence_upload_device(self, frames, f0, channels_last)
 
     def download(self, f):
         a = np.zeros((3, self.h, stride_of(self.w)), np.float32)

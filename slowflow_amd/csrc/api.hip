@@ -492,6 +492,10 @@ struct sfa_job {
     WMask presmoothed = WMask::none();    // windows whose level-0 frames already hold the presmoothed images (cfg sigma > 0): smoothing is applied once per upload
     bool keep_alt_occ = false;         // record the occlusion labels of every alternation (slow_flow_occlusions_output, variational_mt.cpp:275-285)
     DevMem occ_log;                    // [nb][niter_alter][pl(level 0)]
+    // sfa_job_upload_device: the caller's host channel weights go through a pinned copy, so that the call need not wait for the stream; ev_chw says the copies
+    // out of it have been made
+    float *chw_stage = nullptr;
+    hipEvent_t ev_chw = nullptr;
 };
 
 extern "C" {
@@ -525,6 +529,8 @@ int sfa_ctx_create(int device, sfa_ctx **out) {
     SFA_HIP(c.get(), hipMemset(c->d_err, 0, 64));
     SFA_HIP(c.get(), hipEventCreate(&c->t0));
     SFA_HIP(c.get(), hipEventCreate(&c->t1));
+    SFA_HIP(c.get(), hipEventCreateWithFlags(&c->ev_wait, hipEventDisableTiming));
+    SFA_HIP(c.get(), hipEventCreateWithFlags(&c->ev_signal, hipEventDisableTiming));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->cu_count = prop.multiProcessorCount;
     *out = c.release();
@@ -539,6 +545,8 @@ void sfa_ctx_destroy(sfa_ctx *c) {
     for (auto e : c->ev2) (void)hipEventDestroy(e);
     if (c->t0) (void)hipEventDestroy(c->t0);
     if (c->t1) (void)hipEventDestroy(c->t1);
+    if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
+    if (c->ev_signal) (void)hipEventDestroy(c->ev_signal);
     if (c->d_red) (void)hipFree(c->d_red);
     if (c->h_red) (void)hipHostFree(c->h_red);
     if (c->d_err) (void)hipFree(c->d_err);
@@ -1251,6 +1259,8 @@ void sfa_job_destroy(sfa_job *j) {
     if (!j) return;
     (void)hipSetDevice(j->ctx->device);
     (void)hipStreamSynchronize(j->ctx->stream);
+    if (j->ev_chw) (void)hipEventDestroy(j->ev_chw);
+    if (j->chw_stage) (void)hipHostFree(j->chw_stage);
     delete j;
 }
 double sfa_job_mpix_iters(const sfa_job *j) { return j ? j->mpix_iters : 0; }
@@ -1437,6 +1447,219 @@ int sfa_job_download_occlusions(sfa_job *j, int b, float *occ, int stride) {
     Level L0 = j->level(0);
     SFA_TRY(download_plane(ctx, occ, stride, L0.plane(P_OCC) + b * j->es, L0.pitch, j->w, j->h));
     return sfa_ctx_sync(ctx);
+}
+
+// ---- the device seam (include/slowflow_amd.h; kernels: device_io.hip) ---------------------------------------------------------------
+// Every check below is taken on the host before anything is launched; a refusal names the argument.
+#define REFUSE(...) return set_error(ctx, SFA_ERR_ARG, __VA_ARGS__)
+
+// `p` must be device memory of the context's GPU, and the view (its last element `last` elements of `elem` bytes further) must lie inside p's allocation
+static int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        REFUSE("%s: %s is not device memory (hipPointerGetAttributes does not know the pointer: a host pointer?)", fn, arg);
+    }
+    if (at.type != hipMemoryTypeDevice) REFUSE("%s: %s is not device memory (host, managed or unregistered memory)", fn, arg);
+    if (at.device != ctx->device) REFUSE("%s: %s lives on GPU %d, the job's context on GPU %d", fn, arg, at.device, ctx->device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        REFUSE("%s: the allocation %s lies in is unknown to hipMemGetAddressRange: the extent of the view cannot be checked", fn, arg);
+    }
+    const unsigned long long room = (unsigned long long)(static_cast<const char *>(base) + size - static_cast<const char *>(p));
+    if ((unsigned long long)last >= room / elem) REFUSE("%s: the view of %s (%lld elements to its last one) ends beyond its allocation (%llu bytes from the pointer)", fn, arg, last, room);
+    return SFA_OK;
+}
+
+// *acc += steps * stride without wrapping; false: the sum leaves the signed 64-bit range (a view no allocation can hold)
+static bool extent_add(long long *acc, long long steps, long long stride) {
+    long long t;
+    return !__builtin_mul_overflow(steps, stride, &t) && !__builtin_add_overflow(*acc, t, acc);
+}
+
+static size_t dev_elem_size(int dtype) { return dtype == SFA_DEV_F32 ? 4 : dtype == SFA_DEV_U16 ? 2 : 1; }
+
+// the frames of `nwin` windows (or sequence frames) of F frames each: layout and pointer
+static int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h) {
+    if (!l) REFUSE("%s: layout is null", fn);
+    if (l->dtype != SFA_DEV_F32 && l->dtype != SFA_DEV_U8 && l->dtype != SFA_DEV_U16) REFUSE("%s: layout.dtype %d is no element type (fp32 0, u8 1, u16 2)", fn, l->dtype);
+    if (l->column < 1) REFUSE("%s: layout.column = %lld: the column stride must be >= 1", fn, l->column);
+    if (win_stride < 0 || l->frame < 0 || l->channel < 0 || l->row < 0) REFUSE("%s: layout holds a negative stride (window %lld, frame %lld, channel %lld, row %lld)", fn, win_stride, l->frame, l->channel, l->row);
+    if (!frames_dev) REFUSE("%s: frames_dev is null", fn);
+    long long last = 0;
+    if (!extent_add(&last, nwin - 1, win_stride) || !extent_add(&last, F - 1, l->frame) || !extent_add(&last, 2, l->channel) || !extent_add(&last, h - 1, l->row) ||
+        !extent_add(&last, w - 1, l->column))
+        REFUSE("%s: the strides of layout reach beyond the 64-bit range: the view of frames_dev cannot lie inside an allocation", fn);
+    return check_device_pointer(ctx, fn, "frames_dev", frames_dev, last, dev_elem_size(l->dtype));
+}
+
+// a strided fp32 field of `nd` dimensions (sizes n[], strides st[], the last one the column): the pointer and the strides' signs
+static int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd) {
+    if (!st) REFUSE("%s: the strides of %s are null", fn, arg);
+    if (st[nd - 1] < 1) REFUSE("%s: the column stride of %s is %lld: it must be >= 1", fn, arg, st[nd - 1]);
+    long long last = 0;
+    for (int i = 0; i < nd; i++) {
+        if (st[i] < 0) REFUSE("%s: stride %d of %s is negative (%lld)", fn, i, arg, st[i]);
+        if (!extent_add(&last, n[i] - 1, st[i])) REFUSE("%s: the strides of %s reach beyond the 64-bit range: the view cannot lie inside an allocation", fn, arg);
+    }
+    return check_device_pointer(ctx, fn, arg, p, last, sizeof(float));
+}
+
+// strides sorted, each larger than the extent of all smaller ones: no two elements of the field share an address (dimensions of size 1 do not count)
+static bool strides_nest(const long long *st, const int *n, int nd) {
+    std::vector<std::pair<long long, int>> d;
+    for (int i = 0; i < nd; i++) if (n[i] > 1) d.emplace_back(st[i], n[i]);
+    std::sort(d.begin(), d.end());
+    long long extent = 0;                                  // offset of the last element of the dimensions so far
+    for (auto &e : d) {
+        if (e.first <= extent) return false;
+        extent += (e.second - 1) * e.first;
+    }
+    return true;
+}
+
+static int job_windows(sfa_ctx *ctx, const char *fn, const sfa_job *j, int b0, int n) {
+    if (b0 < 0 || n < 1 || (long)b0 + n > j->nb) REFUSE("%s: windows b0 = %d, n = %d lie outside the job's batch of %d", fn, b0, n, j->nb);
+    return SFA_OK;
+}
+
+void sfa_dev_layout_default(sfa_dev_layout *l, int w, int h, int n_frames) {
+    if (!l) return;
+    l->dtype = SFA_DEV_F32;
+    l->column = 1; l->row = w; l->channel = (long long)w * h; l->frame = 3 * l->channel; l->window = (long long)n_frames * l->frame;
+}
+
+int sfa_job_upload_device(sfa_job *j, int b0, int n, const void *frames_dev, const sfa_dev_layout *l, const float *const chw[3]) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(job_windows(ctx, __func__, j, b0, n));
+    SFA_TRY(check_frames_source(ctx, __func__, frames_dev, l, l ? l->window : 0, n, j->F, j->w, j->h));
+    const int stride = host_stride(j->w);
+    if (chw) {
+        CHECK_ARGS(chw[0] && chw[1] && chw[2], "chw holds a null weight plane");
+        CHECK_ARGS(!j->has_chw || j->chw_stride0 == stride, "chw: the job already holds channel weights of another stride");
+    }
+    Level L0 = j->level(0);
+    j->host_stride0 = stride;
+    for (int b = b0; b < b0 + n; b++) j->presmoothed.clear(b);
+    const PackSrc src{frames_dev, l->dtype, l->window, l->frame, l->channel, l->row, l->column};
+    launch_pack_frames(ctx, L0.frame(0) + (long)b0 * j->es, j->es, L0.pl, L0.pitch, j->w, j->h, n, j->F, src);
+    if (chw) {
+        const size_t plane = (size_t)stride * j->h;
+        if (!j->chw_stage) {
+            SFA_HIP(ctx, hipHostMalloc((void **)&j->chw_stage, 3 * plane * sizeof(float), hipHostMallocDefault));
+            SFA_HIP(ctx, hipEventCreateWithFlags(&j->ev_chw, hipEventDisableTiming));
+        } else {
+            SFA_HIP(ctx, hipEventSynchronize(j->ev_chw));      // the copies of an earlier call out of the staging planes (not the stream's other work)
+        }
+        for (int k = 0; k < 3; k++) memcpy(j->chw_stage + k * plane, chw[k], plane * sizeof(float));
+        const float *const staged[3] = {j->chw_stage, j->chw_stage + plane, j->chw_stage + 2 * plane};
+        for (int b = b0; b < b0 + n; b++) SFA_TRY(job_set_channel_weights(j, b, stride, staged));
+        SFA_HIP(ctx, hipEventRecord(j->ev_chw, ctx->stream));
+    } else {
+        for (int b = b0; b < b0 + n; b++) SFA_TRY(job_set_channel_weights(j, b, stride, nullptr));
+    }
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_job_set_flow_device(sfa_job *j, int b0, int n, const float *flow_dev, const long long strides[4]) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(job_windows(ctx, __func__, j, b0, n));
+    if (flow_dev) {
+        const int sizes[4] = {n, 2, j->h, j->w};
+        SFA_TRY(check_field(ctx, __func__, "flow_dev", flow_dev, strides, sizes, 4));
+    }
+    Level L0 = j->level(0);
+    launch_pack_flow(ctx, j->init_flow.f() + (long)b0 * 2 * L0.pl, 2 * L0.pl, L0.pl, L0.pitch, j->w, j->h, n, flow_dev, strides);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_job_download_device(sfa_job *j, int b0, int n, float *flow_dev, const long long strides[4], float *occ_dev, const long long occ_strides[3]) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(job_windows(ctx, __func__, j, b0, n));
+    CHECK_ARGS(flow_dev, "flow_dev is null");
+    const int fsz[4] = {n, 2, j->h, j->w}, osz[3] = {n, j->h, j->w};
+    SFA_TRY(check_field(ctx, __func__, "flow_dev", flow_dev, strides, fsz, 4));
+    if (occ_dev) SFA_TRY(check_field(ctx, __func__, "occ_dev", occ_dev, occ_strides, osz, 3));
+    // overlap.  (1) every (window, plane) in a byte range of its own, and each plane free of overlap in itself; else (2) flow and occlusions apart, and each a
+    // layout of nested strides.  Both are sufficient conditions: what neither proves is refused.
+    {
+        const uintptr_t f0 = reinterpret_cast<uintptr_t>(flow_dev), o0 = reinterpret_cast<uintptr_t>(occ_dev);
+        const long long fspan = (j->h - 1) * strides[2] + (j->w - 1) * strides[3];
+        const long long ospan = occ_dev ? (j->h - 1) * occ_strides[1] + (j->w - 1) * occ_strides[2] : 0;
+        bool ok = strides_nest(strides + 2, fsz + 2, 2) && (!occ_dev || strides_nest(occ_strides + 1, osz + 1, 2));
+        if (ok) {
+            std::vector<std::pair<uintptr_t, uintptr_t>> r;       // [first byte, last byte] of every plane
+            for (int i = 0; i < n; i++) {
+                for (int p = 0; p < 2; p++) { const uintptr_t a = f0 + 4 * (uintptr_t)(i * strides[0] + p * strides[1]); r.emplace_back(a, a + 4 * (uintptr_t)fspan + 3); }
+                if (occ_dev) { const uintptr_t a = o0 + 4 * (uintptr_t)(i * occ_strides[0]); r.emplace_back(a, a + 4 * (uintptr_t)ospan + 3); }
+            }
+            std::sort(r.begin(), r.end());
+            for (size_t i = 1; i < r.size() && ok; i++) ok = r[i].first > r[i - 1].second;
+        }
+        if (!ok) {
+            ok = strides_nest(strides, fsz, 4) && (!occ_dev || strides_nest(occ_strides, osz, 3));
+            if (ok && occ_dev) {
+                const uintptr_t fe = f0 + 4 * (uintptr_t)((n - 1) * strides[0] + strides[1] + fspan) + 3, oe = o0 + 4 * (uintptr_t)((n - 1) * occ_strides[0] + ospan) + 3;
+                ok = fe < o0 || oe < f0;
+            }
+        }
+        if (!ok) REFUSE("%s: the destinations overlap: windows or planes of flow_dev%s share memory (or lie interleaved in a way the check cannot clear)", __func__, occ_dev ? " / occ_dev" : "");
+    }
+    Level L0 = j->level(0);
+    launch_unpack_planes(ctx, L0.plane(P_WX) + (long)b0 * j->es, L0.plane(P_WY) + (long)b0 * j->es, L0.plane(P_OCC) + (long)b0 * j->es, j->es, L0.pitch, j->w, j->h, n,
+                         flow_dev, strides, occ_dev, occ_strides);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_job_changes(const sfa_job *j, int b0, int n, float *out) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j && out, "job or out is null");
+    SFA_TRY(job_windows(ctx, __func__, j, b0, n));
+    for (int i = 0; i < 2 * n; i++) out[i] = j->change[2 * b0 + i];
+    return SFA_OK;
+}
+
+int sfa_sequence_upload_device(sfa_sequence *q, int f0, int n, const void *frames_dev, const sfa_dev_layout *l) {
+    sfa_ctx *ctx = q ? q->ctx : nullptr;
+    CHECK_ARGS(q, "seq is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    if (f0 < 0 || n < 1 || (long)f0 + n > q->n) REFUSE("%s: frames f0 = %d, n = %d lie outside the sequence of %d", __func__, f0, n, q->n);
+    SFA_TRY(check_frames_source(ctx, __func__, frames_dev, l, l ? l->frame : 0, n, 1, q->w, q->h));
+    const size_t elem = dev_elem_size(l->dtype);
+    const int chunk = 16384;                                // 3 planes per frame in the grid's z: below 65536
+    for (int i = 0; i < n; i += chunk) {
+        const PackSrc src{static_cast<const char *>(frames_dev) + (size_t)i * l->frame * elem, l->dtype, l->frame, 0, l->channel, l->row, l->column};
+        launch_pack_frames(ctx, q->frame(f0 + i), 3 * q->pl, q->pl, q->pitch, q->w, q->h, std::min(chunk, n - i), 1, src);
+    }
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_ctx_wait_stream(sfa_ctx *ctx, void *stream) {
+    CHECK_ARGS(ctx, "ctx is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_HIP(ctx, hipEventRecord(ctx->ev_wait, static_cast<hipStream_t>(stream)));
+    SFA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_wait, 0));
+    return SFA_OK;
+}
+int sfa_ctx_signal_stream(sfa_ctx *ctx, void *stream) {
+    CHECK_ARGS(ctx, "ctx is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_HIP(ctx, hipEventRecord(ctx->ev_signal, ctx->stream));
+    SFA_HIP(ctx, hipStreamWaitEvent(static_cast<hipStream_t>(stream), ctx->ev_signal, 0));
+    return SFA_OK;
 }
 
 // ---- host-plane convenience entry points ------------------------------------------------------------------------

@@ -94,6 +94,7 @@ struct sfa_ctx {
     void *rb_tmp = nullptr;       // labelled red-black mode: scratch (du, dv) pair the tile visits ping-pong with, grown on demand
     size_t rb_tmp_bytes = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;
+    hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // sfa_ctx_wait_stream / sfa_ctx_signal_stream: recorded on the caller's / the context's stream
     // the reference's per-iteration "avg change" lines (variational_mt.cpp:404-405, 431-432): sfa_ctx_set_verbose; costs a host round trip per iteration
     bool verbose_changes = false;
     // default-ctx bookkeeping
@@ -300,6 +301,17 @@ bool launch_pyr_down(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dp
 void launch_presmooth(sfa_ctx *c, const Geo &g, float *dst, float *tmp, const float *src, int nplanes, float sigma);
 void launch_normalize_sums(sfa_ctx *c, const Geo &g, const float *frames3, double *red /* [3][2] */);
 void launch_normalize_apply(sfa_ctx *c, const Geo &g, float *frames3, const double avg[3], const double stdv[3]);
+
+// ---- device_io.hip: the device seam (sfa_job_upload_device ...): conversions and moves only ---------------------------------------------
+// A strided source of colour frames in device memory: element (window, frame, channel, row, column) at p + the strides, in elements of dtype (sfa_dev_dtype)
+struct PackSrc { const void *p; int dtype; long long sw, sf, sc, sr, sx; };
+// dst = plane 0 of frame 0 of the first window; window i lies dst_es floats further, frame f 3 pl, channel c pl.  Columns >= w are not written.
+void launch_pack_frames(sfa_ctx *c, float *dst, long dst_es, long pl, int pitch, int w, int h, int nwin, int F, const PackSrc &s);
+// dst = u plane of the first window (v one pl further, the next window dst_es); src null: zeros.  st = element strides of (window, u|v, row, column)
+void launch_pack_flow(sfa_ctx *c, float *dst, long dst_es, long pl, int pitch, int w, int h, int nwin, const float *src, const long long st[4]);
+// the planes wx, wy (and occ, or null) of nwin windows src_es floats apart -> flow (st[4]) and occ_dst (ost[3] = window, row, column)
+void launch_unpack_planes(sfa_ctx *c, const float *wx, const float *wy, const float *occ, long src_es, int pitch, int w, int h, int nwin, float *flow,
+                          const long long st[4], float *occ_dst, const long long ost[3]);
 
 // ---------------------------------------------------------------------------------------------------
 // SOR (sor.hip)

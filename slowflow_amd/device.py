@@ -1,0 +1,279 @@
+"""slowflow_amd.device -- the device seam of the C-ABI (include/slowflow_amd.h: sfa_job_upload_device ...) for Python callers: frames, initial flow
+and results that live in GPU memory go in and out of a job without a host copy.
+
+The core takes any object with `__cuda_array_interface__` (torch-ROCm tensors, cupy arrays ...) and needs no torch; `import slowflow_amd` does not
+import this module, and this module imports torch only inside refine(), to allocate the outputs and to find the caller's current stream.
+
+Stream contract: the library works on the context's own stream.  Context.wait_stream(s) before the first call makes that stream wait for what the
+caller has submitted to s; Context.signal_stream(s) after the last makes s wait for the library.  refine() does both.  With the two in place a tensor
+freed or reused on s is ordered after the library's last access, so torch's caching allocator needs no record_stream.
+"""
+import ctypes as C
+import sys
+from collections import OrderedDict
+
+import numpy as np
+
+import slowflow_amd as sfa
+
+MAX_BATCH = 128                                   # windows of one job (csrc/sfa_internal.h: kMaxBatch)
+DTYPES = {"f4": 0, "u1": 1, "u2": 2}              # sfa_dev_dtype by typestr kind + size
+
+
+class DevLayout(C.Structure):
+    """sfa_dev_layout: element type and element strides of (window, frame, channel, row, column)"""
+    _fields_ = [("dtype", C.c_int), ("window", C.c_longlong), ("frame", C.c_longlong), ("channel", C.c_longlong), ("row", C.c_longlong),
+                ("column", C.c_longlong)]
+
+
+class DeviceView:
+    """pointer, element type (sfa_dev_dtype), shape and ELEMENT strides of a device array"""
+
+    def __init__(self, ptr, dtype, itemsize, shape, strides, owner=None):
+        self.ptr, self.dtype, self.itemsize, self.shape, self.strides, self.owner = ptr, dtype, itemsize, tuple(shape), tuple(strides), owner
+
+    def sub(self, start, n):
+        """elements [start, start + n) of the first dimension"""
+        assert 0 <= start and n >= 1 and start + n <= self.shape[0]
+        return DeviceView(self.ptr + start * self.strides[0] * self.itemsize, self.dtype, self.itemsize, (n,) + self.shape[1:], self.strides, self.owner)
+
+
+def device_view(obj, writable=False, name="array", ndim=None):
+    """obj.__cuda_array_interface__ -> DeviceView.  Refuses (SlowflowError naming `name`): objects without the interface (host arrays), element types
+    other than fp32 / u8 / u16, non-native byte order, byte strides that are no multiple of the item size, a read-only object asked for as an output,
+    and a rank other than `ndim`.  Whether the pointer is device memory of the job's GPU is the library's check, made before anything is launched."""
+    if isinstance(obj, DeviceView):
+        v = obj
+    else:
+        cai = getattr(obj, "__cuda_array_interface__", None)
+        if cai is None:
+            raise sfa.SlowflowError(f"{name}: {type(obj).__name__} has no __cuda_array_interface__ (a host array? the device entry points take device memory)")
+        typestr = cai["typestr"]
+        order, kind = typestr[0], typestr[1:]
+        native = "<" if sys.byteorder == "little" else ">"
+        if order not in (native, "|", "="):
+            raise sfa.SlowflowError(f"{name}: byte order of typestr {typestr!r} is not the machine's")
+        if kind not in DTYPES:
+            raise sfa.SlowflowError(f"{name}: element type {typestr!r} is not supported (fp32, uint8 and uint16 are; fp16, bf16, fp64 and signed integers are not)")
+        item = int(kind[1:])
+        shape = tuple(int(s) for s in cai["shape"])
+        ptr, readonly = cai["data"]
+        if writable and readonly:
+            raise sfa.SlowflowError(f"{name}: the object is read-only and cannot be an output")
+        if writable and kind != "f4":
+            raise sfa.SlowflowError(f"{name}: outputs are fp32, not {typestr!r}")
+        bst = cai.get("strides")
+        if bst is None:
+            st, acc = [], 1
+            for s in reversed(shape):
+                st.append(acc)
+                acc *= s
+            st = tuple(reversed(st))
+        else:
+            if any(int(b) % item for b in bst):
+                raise sfa.SlowflowError(f"{name}: byte strides {tuple(bst)} are not multiples of the item size {item}")
+            st = tuple(int(b) // item for b in bst)
+        if any(s == 0 for s in shape):
+            raise sfa.SlowflowError(f"{name}: empty array, shape {shape}")
+        v = DeviceView(int(ptr or 0), DTYPES[kind], item, shape, st, obj)
+    if ndim is not None and len(v.shape) != ndim:
+        raise sfa.SlowflowError(f"{name}: rank {len(v.shape)}, shape {v.shape}; {ndim} dimensions expected")
+    return v
+
+
+def frames_layout(v, w, h, F, channels_last=None, name="frames"):
+    """[B,F,3,H,W] (planar) or [B,F,H,W,3] (interleaved) -> (B, DevLayout).  channels_last None: told from the shape, planar where both fit."""
+    planar, inter = v.shape[1:] == (F, 3, h, w), v.shape[1:] == (F, h, w, 3)
+    if channels_last is None:
+        channels_last = inter and not planar
+    if not (inter if channels_last else planar):
+        raise sfa.SlowflowError(f"{name}: shape {v.shape} is neither [B,{F},3,{h},{w}] nor [B,{F},{h},{w},3]")
+    s = v.strides
+    lay = DevLayout(v.dtype, s[0], s[1], s[4], s[2], s[3]) if channels_last else DevLayout(v.dtype, s[0], s[1], s[2], s[3], s[4])
+    return v.shape[0], lay
+
+
+_LL4, _LL3 = C.c_longlong * 4, C.c_longlong * 3
+_bound = False
+
+
+def _lib():
+    global _bound
+    L = sfa.lib()
+    if not _bound:
+        L.sfa_job_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DevLayout), C.c_void_p]
+        L.sfa_job_set_flow_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.sfa_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sfa_job_changes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.sfa_sequence_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DevLayout)]
+        L.sfa_ctx_wait_stream.argtypes = [C.c_void_p, C.c_void_p]
+        L.sfa_ctx_signal_stream.argtypes = [C.c_void_p, C.c_void_p]
+        L.sfa_dev_layout_default.argtypes = [C.POINTER(DevLayout), C.c_int, C.c_int, C.c_int]
+        L.sfa_dev_layout_default.restype = None
+        _bound = True
+    return L
+
+
+def default_layout(w, h, n_frames):
+    """sfa_dev_layout_default: contiguous planar fp32 [n][n_frames][3][h][w]"""
+    lay = DevLayout()
+    _lib().sfa_dev_layout_default(C.byref(lay), int(w), int(h), int(n_frames))
+    return lay
+
+
+def stream_handle(stream):
+    """None / 0: the device's null stream (torch's default stream); an int: a hipStream_t; else an object with .cuda_stream (torch.cuda.Stream)"""
+    if stream is None:
+        return 0
+    if isinstance(stream, int):
+        return stream
+    return int(stream.cuda_stream)
+
+
+def wait_stream(ctx, stream=None):
+    ctx._ck(_lib().sfa_ctx_wait_stream(ctx.h, C.c_void_p(stream_handle(stream))), "sfa_ctx_wait_stream")
+
+
+def signal_stream(ctx, stream=None):
+    ctx._ck(_lib().sfa_ctx_signal_stream(ctx.h, C.c_void_p(stream_handle(stream))), "sfa_ctx_signal_stream")
+
+
+def job_upload_device(job, frames, b0=0, chw=None, channels_last=None):
+    F = job.n_frames
+    v = device_view(frames, name="frames", ndim=5)
+    n, lay = frames_layout(v, job.w, job.h, F, channels_last)
+    cw = None
+    keep = None
+    if chw is not None:
+        keep = [np.ascontiguousarray(c, np.float32) for c in chw]
+        assert all(c.shape == (job.h, sfa.stride_of(job.w)) for c in keep), "channel weights are 3 host planes (h, stride_of(w))"
+        cw = (C.c_void_p * 3)(*[c.ctypes.data for c in keep])
+    job.ctx._ck(_lib().sfa_job_upload_device(job.h_, int(b0), n, C.c_void_p(v.ptr), C.byref(lay), cw), "sfa_job_upload_device")
+
+
+def job_set_flow_device(job, flow, b0=0, n=None):
+    if flow is None:
+        n = job.batch - b0 if n is None else n
+        job.ctx._ck(_lib().sfa_job_set_flow_device(job.h_, int(b0), int(n), None, None), "sfa_job_set_flow_device")
+        return
+    v = device_view(flow, name="flow", ndim=4)
+    if v.dtype != DTYPES["f4"] or v.shape[1:] != (2, job.h, job.w):
+        raise sfa.SlowflowError(f"flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
+    job.ctx._ck(_lib().sfa_job_set_flow_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), "sfa_job_set_flow_device")
+
+
+def job_download_device(job, out_flow, out_occ=None, b0=0):
+    v = device_view(out_flow, writable=True, name="out_flow", ndim=4)
+    if v.shape[1:] != (2, job.h, job.w):
+        raise sfa.SlowflowError(f"out_flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
+    optr, ost = None, None
+    if out_occ is not None:
+        o = device_view(out_occ, writable=True, name="out_occ", ndim=3)
+        if o.shape != (v.shape[0], job.h, job.w):
+            raise sfa.SlowflowError(f"out_occ: fp32 [{v.shape[0]},{job.h},{job.w}] expected, got shape {o.shape}")
+        optr, ost = C.c_void_p(o.ptr), _LL3(*o.strides)
+    job.ctx._ck(_lib().sfa_job_download_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides), optr, ost), "sfa_job_download_device")
+
+
+def job_changes(job, b0=0, n=None):
+    n = job.batch - b0 if n is None else n
+    out = np.zeros((max(n, 0), 2), np.float32)
+    job.ctx._ck(_lib().sfa_job_changes(job.h_, int(b0), int(n), C.c_void_p(out.ctypes.data)), "sfa_job_changes")
+    return out
+
+
+def sequence_upload_device(seq, frames, f0=0, channels_last=None):
+    v = device_view(frames, name="frames", ndim=4)
+    # a sequence's frames are the windows of a [N,1,...] array
+    v5 = DeviceView(v.ptr, v.dtype, v.itemsize, (v.shape[0], 1) + v.shape[1:], (v.strides[0], 0) + v.strides[1:], v.owner)
+    n, lay = frames_layout(v5, seq.w, seq.h, 1, channels_last)
+    lay.frame, lay.window = lay.window, 0                       # sfa_sequence_upload_device steps by layout.frame
+    seq.ctx._ck(_lib().sfa_sequence_upload_device(seq.h_, int(f0), n, C.c_void_p(v.ptr), C.byref(lay)), "sfa_sequence_upload_device")
+
+
+def _job_for(ctx, params, w, h, nb):
+    """a job of this shape, kept on the context from call to call (two shapes at most: a batch beyond MAX_BATCH splits into at most two sizes)"""
+    cache = ctx.__dict__.setdefault("_refine_jobs", OrderedDict())
+    key = (bytes(params), w, h, nb)
+    job = cache.get(key)
+    if job is not None and job.h_:
+        cache.move_to_end(key)
+        return job
+    while len(cache) >= 2:
+        cache.popitem(last=False)[1].close()
+    job = cache[key] = sfa.Job(ctx, params, w, h, nb)
+    return job
+
+
+def release_jobs(ctx):
+    """closes the jobs refine() keeps on the context (they hold their device memory between calls)"""
+    for job in ctx.__dict__.pop("_refine_jobs", {}).values():
+        job.close()
+
+
+def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, stream=None, channels_last=None):
+    """Refine the flow of B frame windows that live on the context's GPU: frames = a torch tensor [B,F,3,H,W] or [B,F,H,W,3] (fp32, uint8 or uint16;
+    any strides with a positive column stride), F = 2 (S - 1) + 1; flow = None (zeros) or an fp32 tensor [B,2,H,W].  Returns (flow [B,2,H,W], occlusions
+    [B,H,W] or None, change norms as a numpy array [B,2]), the tensors on the frames' device.  The work is ordered after what `stream` (default:
+    torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call itself returns when the refinement has run (sfa_job_run
+    takes its break decisions on the host).  B > 128 is split into jobs of equal or nearly equal size.
+    normalize=True: the frames go through a Sequence first -- normalize() over the B x F frames as passed, the bits of Sequence.normalize -- and the
+    statistics replace params.norm_avg / norm_std (of a copy), as the driver does.  Without it the frames are taken as they are.
+    The jobs stay on the context for the next call of the same shape and parameters (release_jobs(ctx) or ctx.close() frees them); with normalize=True
+    the statistics are part of the parameters, so that mode creates its jobs per call and closes them before it returns."""
+    import torch
+    F = 2 * (params.S - 1) + 1
+    fv = device_view(frames, name="frames", ndim=5)
+    last = (fv.shape[2] != 3 and fv.shape[4] == 3) if channels_last is None else channels_last
+    h, w = (fv.shape[2], fv.shape[3]) if last else (fv.shape[3], fv.shape[4])
+    B, _ = frames_layout(fv, w, h, F, channels_last)
+    flv = None
+    if flow is not None:
+        flv = device_view(flow, name="flow", ndim=4)
+        if flv.shape != (B, 2, h, w):
+            raise sfa.SlowflowError(f"flow: [{B},2,{h},{w}] expected, got shape {flv.shape}")
+    if stream is None:
+        stream = torch.cuda.current_stream(frames.device)
+    with torch.cuda.stream(stream):                              # the outputs belong to the caller's stream
+        out = torch.empty((B, 2, h, w), dtype=torch.float32, device=frames.device)
+        occ = torch.empty((B, h, w), dtype=torch.float32, device=frames.device) if want_occ else None
+    ov, cv = device_view(out, writable=True, name="out_flow"), (device_view(occ, writable=True, name="out_occ") if want_occ else None)
+    change = np.zeros((B, 2), np.float32)
+    pieces = -(-B // MAX_BATCH)
+    sizes = [B // pieces + (1 if i < B % pieces else 0) for i in range(pieces)]
+    wait_stream(ctx, stream)
+    seq = None
+    try:
+        if normalize:
+            params = type(params).from_buffer_copy(params)
+            seq = sfa.Sequence(ctx, w, h, B * F)
+            for b in range(B):                                   # window-major: sequence frame b F + f
+                _, lay = frames_layout(fv.sub(b, 1), w, h, F, channels_last)
+                lay.window = 0
+                ctx._ck(_lib().sfa_sequence_upload_device(seq.h_, b * F, F, C.c_void_p(fv.ptr + b * fv.strides[0] * fv.itemsize), C.byref(lay)),
+                        "sfa_sequence_upload_device")
+            avg, std = seq.normalize()
+            for k in range(3):
+                params.norm_avg[k], params.norm_std[k] = avg[k], std[k]
+        b0 = 0
+        for n in sizes:
+            # the statistics of normalize=True are part of a job's parameters and differ from call to call: such a job is not kept
+            job = _job_for(ctx, params, w, h, n) if seq is None else sfa.Job(ctx, params, w, h, n)
+            if seq is not None:
+                for b in range(n):
+                    job.upload_resident(b, seq, [(b0 + b) * F + f for f in range(F)])
+            else:
+                job_upload_device(job, fv.sub(b0, n), channels_last=channels_last)
+            job_set_flow_device(job, flv.sub(b0, n) if flv is not None else None, 0, n)
+            job.run()
+            job_download_device(job, ov.sub(b0, n), cv.sub(b0, n) if want_occ else None)
+            change[b0:b0 + n] = job_changes(job, 0, n)
+            b0 += n
+            if seq is not None:
+                signal_stream(ctx, stream)
+                job.close()
+    finally:
+        signal_stream(ctx, stream)
+        if seq is not None:
+            seq.close()
+    return out, occ, change
