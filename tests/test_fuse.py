@@ -108,12 +108,15 @@ def test_chains_reach_the_viterbi_optimum_after_two_iterations(seed, vertical):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # synthetic hypotheses
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-def synth(rng, K, J, w, h, skip=1, holes=0.2, n=1):
-    """n segments: U, V (n, K, J, gh, gw), energy (n, K, gh, gw), occ (n, K, gh, gw), weight (n, h, w).  Slots near a copy of slot 0 (NMS active)."""
+def synth(rng, K, J, w, h, skip=1, holes=0.2, n=1, spread=0.0):
+    """n segments: U, V (n, K, J, gh, gw), energy (n, K, gh, gw), occ (n, K, gh, gw), weight (n, h, w).  Slots near a copy of slot 0 (NMS active);
+    spread adds spread * k to slot k's u, which moves the slots apart so that the NMS keeps them (same random draws with and without it)."""
     gw, gh, _, _ = grid(w, h, skip)
     base = np.cumsum(rng.normal(0, 1, (n, 1, J, gh, gw)), 2)
     scale = rng.choice([1e-3, 0.05, 1.0], (n, K, 1, gh, gw))
     U = base + np.cumsum(rng.normal(0, 1, (n, K, J, gh, gw)), 2) * scale
+    if spread:
+        U = U + spread * np.arange(K).reshape(1, K, 1, 1, 1)
     V = base[..., ::-1, :] + np.cumsum(rng.normal(0, 1, (n, K, J, gh, gw)), 2) * scale
     energy = rng.uniform(0, 50, (n, K, gh, gw)).astype(F32).astype(np.float64)
     energy[rng.random(energy.shape) < holes] = np.inf
