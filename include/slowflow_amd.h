@@ -199,6 +199,21 @@ void sfa_fuse_params_default(sfa_fuse_params *p);
 int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, const double *U, const double *V, const double *energy,
                         const unsigned long long *occ_bits, const float *weight, int *slot, double *flow_u, double *flow_v, unsigned char *occ,
                         double *seg_energy, double *seg_bound, int *seg_iters, float *stage_ms);
+/* ---- resident pair jobs: the two-frame refinement of pairs that stay in GPU memory ----------------------------------------------------
+ * A pair job owns the planes of n pairs of one size (24 per pair: those of sfa_variational_2frame without its 24-plane derivative stack) and one solver
+ * workspace, across any number of uploads and runs.  sfa_pair_job_run enqueues variational()'s launch sequence (variational.c:19-82) for all n pairs on the
+ * context's stream and RETURNS WITHOUT WAITING -- the two-frame path has no break decision, so nothing needs the host: the one refinement entry point of
+ * the library that is fully asynchronous.  sfa_pair_job_download and sfa_ctx_sync are the waits (and report a solver wait that gave up).  The derivatives
+ * and the data term are formed in one kernel (k_data_2f_fused); pair b comes out bit-identical to sfa_variational_2frame on that pair alone, whatever n and
+ * b.  A run refines the flow the job holds: after a run without a new upload the next run refines the result further.
+ * Refused with SFA_ERR_ARG: w < 2, h < 5, n outside 1 .. 128, n x width beyond the change norms' scratch, a null plane, stride < w, b outside the job.
+ * p == NULL: sfa_params_2frame_default.  upload: host planes as for sfa_variational_2frame (im1, im2: first plane of 3); it waits for its copies. */
+typedef struct sfa_pair_job sfa_pair_job;
+int  sfa_pair_job_create(sfa_ctx *ctx, const sfa_params_2frame *p, int w, int h, int n, sfa_pair_job **out);
+void sfa_pair_job_destroy(sfa_pair_job *job);
+int  sfa_pair_job_upload(sfa_pair_job *job, int b, const float *wx, const float *wy, int stride, const float *im1, const float *im2);
+int  sfa_pair_job_run(sfa_pair_job *job);
+int  sfa_pair_job_download(sfa_pair_job *job, int b, float *wx, float *wy, int stride);
 /* The reference's own symbol and signature (variational.h:34), for relinking callers such as adaptiveFR / EpicFlow's refinement
  * step: runs on device 0 with a process-wide context; aborts with a message on error like the reference does. */
 void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params);
@@ -354,6 +369,12 @@ int  sfa_job_download_device(sfa_job *job, int b0, int n, float *flow_dev, const
 int  sfa_job_changes(const sfa_job *job, int b0, int n, float *out);
 /* Replaces sfa_sequence_upload for the frames [f0, f0 + n): frame i at frames_dev + i * layout->frame (layout->window is not used). */
 int  sfa_sequence_upload_device(sfa_sequence *seq, int f0, int n, const void *frames_dev, const sfa_dev_layout *layout);
+/* The same seam for resident pair jobs, the pairs [b0, b0 + n): the same kernels, one launch per call, no host copy, no wait, columns >= width never
+ * written, and the same refusals by the same checks.  frames_dev holds two frames per pair: the layout's frame index 0 is im1, 1 is im2 (layout->window
+ * steps from pair to pair).  flow_dev NULL in set_flow: zeros.  upload_device leaves the pairs' flow as it is, like sfa_job_upload_device. */
+int  sfa_pair_job_upload_device(sfa_pair_job *job, int b0, int n, const void *frames_dev, const sfa_dev_layout *layout);
+int  sfa_pair_job_set_flow_device(sfa_pair_job *job, int b0, int n, const float *flow_dev, const long long strides[4]);
+int  sfa_pair_job_download_device(sfa_pair_job *job, int b0, int n, float *flow_dev, const long long strides[4]);
 /* Ordering against a stream of the caller (a hipStream_t; NULL = the device's null stream, which is torch's default stream).  wait: the context's
  * stream waits for everything submitted to `stream` so far; signal: `stream` waits for everything submitted to the context's stream so far.  Both
  * record an event and return at once.  With wait before the first and signal after the last call that touches a buffer, work the caller submits to
@@ -386,6 +407,12 @@ int  sfa_ctx_set_wait_bound(sfa_ctx *ctx, unsigned spins);
  * host round trip per iteration. */
 int  sfa_debug_set(const char *name, const char *value);
 int  sfa_ctx_set_verbose(sfa_ctx *ctx, int on);
+
+/* ---- test hook: the linear system of a pair job --------------------------------------------------------------------------------------
+ * a11, a12, a22, b1, b2 of pair b as the last data-term launch of the last run left them (host planes, row stride `stride`); waits for the stream.  The
+ * switch SFA_PAIR_UNFUSED=1 (sfa_debug_set) makes a pair job run the stored derivative stack and k_data_2f instead of k_data_2f_fused, on a stack it
+ * allocates at the first such run: the parity test compares the two systems plane by plane. */
+int  sfa_pair_job_download_system(sfa_pair_job *job, int b, float *a11, float *a12, float *a22, float *b1, float *b2, int stride);
 
 /* ---- test hook: the division of the normalised data terms --------------------------------------------------------------------
  * The cfg-default instance of the fused assembly kernel forms the quotients r^2 / n and t / n of variational_aux_mt.cpp:240-250, 333-347, 479-490, 556-572

@@ -97,12 +97,12 @@ def fuse_params(**kw):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
     "sfa_job_create", "sfa_job_destroy", "sfa_job_upload", "sfa_job_upload_resident", "sfa_job_reset_flow", "sfa_job_run", "sfa_job_download", "sfa_job_download_occlusions", "sfa_job_keep_alternation_occlusions", "sfa_job_download_alternation_occlusions", "sfa_job_mpix_iters", "sfa_job_device_bytes",
-    "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
+    "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_pair_job_upload_device", "sfa_pair_job_set_flow_device", "sfa_pair_job_download_device", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
@@ -124,7 +124,7 @@ def lib():
         L.sfa_job_mpix_iters.argtypes = [C.c_void_p]
         L.sfa_job_device_bytes.restype = C.c_double
         L.sfa_job_device_bytes.argtypes = [C.c_void_p]
-        for name in ("sfa_ctx_destroy", "sfa_job_destroy", "sfa_sor_batch_destroy", "sfa_sequence_destroy"):
+        for name in ("sfa_ctx_destroy", "sfa_job_destroy", "sfa_pair_job_destroy", "sfa_sor_batch_destroy", "sfa_sequence_destroy"):
             getattr(L, name).restype = None
             getattr(L, name).argtypes = [C.c_void_p]
         _lib = L
@@ -636,6 +636,73 @@ class Job:
         if self.h_:
             if self.ctx.h:                      # a context finalised first (cyclic garbage, interpreter shutdown) took its stream along: nothing to call into
                 lib().sfa_job_destroy(self.h_)
+            self.h_ = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PairJob:
+    """sfa_pair_job: n frame pairs of one size resident in HBM for the two-frame refinement (variational.c).  run() only enqueues and returns at once;
+    download() and Context.sync() wait.  Pair b comes out bit-identical to Context.variational_2frame on that pair alone."""
+
+    def __init__(self, ctx, w, h, n=1, params=None):
+        self.ctx, self.w, self.h, self.n = ctx, w, h, n
+        self.h_ = C.c_void_p()
+        L = lib()
+        L.sfa_pair_job_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.sfa_pair_job_upload.argtypes = [C.c_void_p, C.c_int, _f, _f, C.c_int, _f, _f]
+        L.sfa_pair_job_run.argtypes = [C.c_void_p]
+        L.sfa_pair_job_download.argtypes = [C.c_void_p, C.c_int, _f, _f, C.c_int]
+        L.sfa_pair_job_download_system.argtypes = [C.c_void_p, C.c_int, _f, _f, _f, _f, _f, C.c_int]
+        ctx._ck(L.sfa_pair_job_create(ctx.h, C.byref(params) if params is not None else None, int(w), int(h), int(n), C.byref(self.h_)), "sfa_pair_job_create")
+        ctx._children.add(self)
+
+    def upload(self, b, wx, wy, im1, im2):
+        """host planes as for Context.variational_2frame: wx, wy (h, stride), im1, im2 (3, h, stride), one stride"""
+        h, stride = wx.shape
+        assert h == self.h and wy.shape == (h, stride) and im1.shape == (3, h, stride) and im2.shape == (3, h, stride), "planes of one (h, stride)"
+        self.ctx._ck(lib().sfa_pair_job_upload(self.h_, int(b), fptr(wx), fptr(wy), stride, fptr(im1), fptr(im2)), "sfa_pair_job_upload")
+
+    def run(self):
+        self.ctx._ck(lib().sfa_pair_job_run(self.h_), "sfa_pair_job_run")
+
+    def download(self, b, stride=None):
+        stride = stride_of(self.w) if stride is None else stride
+        wx, wy = np.zeros((self.h, stride), np.float32), np.zeros((self.h, stride), np.float32)
+        self.ctx._ck(lib().sfa_pair_job_download(self.h_, int(b), fptr(wx), fptr(wy), stride), "sfa_pair_job_download")
+        return wx, wy
+
+    def download_system(self, b):
+        """test hook: (a11, a12, a22, b1, b2) of pair b as the last run's last data-term launch left them"""
+        stride = stride_of(self.w)
+        out = [np.zeros((self.h, stride), np.float32) for _ in range(5)]
+        self.ctx._ck(lib().sfa_pair_job_download_system(self.h_, int(b), *[fptr(a) for a in out], stride), "sfa_pair_job_download_system")
+        return out
+
+    # ---- the device seam (slowflow_amd/device.py): objects with __cuda_array_interface__, asynchronous on the context's stream ----
+    def upload_device(self, frames, b0=0, channels_last=None):
+        """frames [B,2,3,H,W] or [B,2,H,W,3] (fp32 / uint8 / uint16, any strides) in device memory -> pairs b0 .. b0 + B - 1 (frame 0 = im1)"""
+        from . import device
+        device.pair_job_upload_device(self, frames, b0, channels_last)
+
+    def set_flow_device(self, flow, b0=0, n=None):
+        """the flow of pairs b0 .. from an fp32 device array [B,2,H,W]; None: zeros for n pairs (default: all from b0)"""
+        from . import device
+        device.pair_job_set_flow_device(self, flow, b0, n)
+
+    def download_device(self, out_flow, b0=0):
+        """(u, v) of pairs b0 .. b0 + B - 1 into the fp32 device array out_flow [B,2,H,W]"""
+        from . import device
+        device.pair_job_download_device(self, out_flow, b0)
+
+    def close(self):
+        if self.h_:
+            if self.ctx.h:                      # a context finalised first (cyclic garbage, interpreter shutdown) took its stream along: nothing to call into
+                lib().sfa_pair_job_destroy(self.h_)
             self.h_ = C.c_void_p()
 
     def __del__(self):

@@ -24,7 +24,7 @@ static const char *const kSwitchNames[Switches::N] = {
     "SFA_SOR_CHAIN", "SFA_SOR_BAND", "SFA_SOR_F", "SFA_SOR_CH", "SFA_SOR_LEAD", "SFA_CHAIN_LDS", "SFA_RB_TILE", "SFA_WARP_ALLJ", "SFA_NO_WARP_SMOOTH",
     "SFA_ASSEMBLE_GENERIC", "SFA_EXACT_DIV", "SFA_ASM_XCD", "SFA_NO_DIRECT_OPERANDS", "SFA_NO_UV_ALIAS", "SFA_DEBUG_ACTIVE", "SFA_UNFUSED", "SFA_SHARE_SOR",
     "SFA_PYRAMID_UNFUSED", "SFA_CUT_DISCHARGE", "SFA_CUT_INNER", "SFA_CUT_SUPER", "SFA_CUT_TAIL_INNER", "SFA_CUT_PER", "SFA_CUT_TAIL_PER", "SFA_CUT_TAIL_SUPER",
-    "SFA_CUT_DEBUG", "SFA_CUT_NO_TAIL", "SFA_CUT_TAIL", "SFA_NO_EXACT_BREAK"};
+    "SFA_CUT_DEBUG", "SFA_CUT_NO_TAIL", "SFA_CUT_TAIL", "SFA_NO_EXACT_BREAK", "SFA_PAIR_UNFUSED"};
 static int set_switch(const char *name, const char *value) {
     for (int i = 0; i < Switches::N; i++)
         if (!strcmp(name, kSwitchNames[i])) {
@@ -1098,6 +1098,111 @@ int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *c
     return sfa_ctx_sync(ctx);
 }
 
+// ---- resident pair jobs: the two-frame refinement of n pairs that stay in HBM (struct: sfa_internal.h) ------------------------------------------
+// The launch sequence of sfa_variational_2frame_batch on planes the job owns, with launch_deriv_stack + launch_data_2f replaced by k_data_2f_fused: 24 planes
+// per pair, no stack.  Same per-pixel arithmetic (kernels.hip: data_2f_pixel), same taps: pair b is bit-identical to sfa_variational_2frame on that pair alone.
+// The solver workspace is shaped at creation, so that sfa_pair_job_run only enqueues: the two-frame path has no break decision, nothing needs the host.
+int sfa_pair_job_create(sfa_ctx *ctx, const sfa_params_2frame *pp, int w, int h, int n, sfa_pair_job **out) {
+    CHECK_ARGS(ctx && out, "ctx or out is null");
+    CHECK_ARGS(w >= 2 && h >= 5, "bad arguments (h >= 5, w >= 2)");
+    CHECK_ARGS(n >= 1 && n <= kMaxBatch, "n out of range (1 .. 128 pairs)");
+    CHECK_ARGS(2L * kMaxBatch + 2L * n * ((w + 63) / 64) * 16 <= kRedDoubles, "n x width beyond the change norms' scratch (sfa_internal.h: kRedDoubles)");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<sfa_pair_job> j(new sfa_pair_job());
+    j->ctx = ctx; j->w = w; j->h = h; j->n = n; j->pitch = dev_pitch(w);
+    j->pl = (long)j->pitch * h; j->es = sfa_pair_job::NPL * j->pl;
+    if (pp) j->p = *pp; else sfa_params_2frame_default(&j->p);
+    SFA_TRY(j->mem.alloc(ctx, (size_t)n * j->es * sizeof(float)));
+    SFA_HIP(ctx, hipMemsetAsync(j->mem.p, 0, (size_t)n * j->es * sizeof(float), ctx->stream));
+    if (j->p.niter_solver >= 1) SFA_TRY(j->ws.configure(ctx, w, h, j->p.niter_solver, n));     // (waits for the stream once, here and not in the first run)
+    *out = j.release();
+    return SFA_OK;
+}
+void sfa_pair_job_destroy(sfa_pair_job *j) {
+    if (!j) return;
+    (void)hipSetDevice(j->ctx->device);
+    (void)hipStreamSynchronize(j->ctx->stream);
+    delete j;
+}
+int sfa_pair_job_upload(sfa_pair_job *j, int b, const float *wx, const float *wy, int stride, const float *im1, const float *im2) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    CHECK_ARGS(b >= 0 && b < j->n, "b outside the job");
+    CHECK_ARGS(wx && wy && im1 && im2, "null plane");
+    CHECK_ARGS(stride >= j->w, "stride below the width");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::WX), j->pitch, wx, stride, j->w, j->h));
+    SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::WY), j->pitch, wy, stride, j->w, j->h));
+    for (int k = 0; k < 3; k++) {
+        SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::IM1 + k), j->pitch, im1 + (size_t)k * stride * j->h, stride, j->w, j->h));
+        SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::IM2 + k), j->pitch, im2 + (size_t)k * stride * j->h, stride, j->w, j->h));
+    }
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the copies read the caller's pageable memory (like sfa_job_upload)
+    return SFA_OK;
+}
+int sfa_pair_job_run(sfa_pair_job *j) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    typedef sfa_pair_job J;
+    const sfa_params_2frame &p = j->p;
+    const float half_alpha = 0.5f * p.alpha, hg = p.gamma * 0.5f / 3.0f, hd = p.delta * 0.5f / 3.0f;   // variational.c:113-115
+    const long es = j->es;
+    const Geo g = j->geo();
+    auto P = [&](int i) { return j->plane(0, i); };
+    const bool unfused = sw_int(Switches::PAIR_UNFUSED, 0) != 0;      // cross-check: the stored stack and k_data_2f (the release build: constant false)
+    if (unfused) {
+        // pair b's stack lies J::NPL planes after pair b - 1's, as every plane of the job does (launch_data_2f knows one batch stride): 24 = 8 derivatives x 3 channels
+        static_assert(J::NPL == 24, "the lazily allocated stack shares the job's pair stride");
+        SFA_TRY(j->stack.alloc(ctx, (size_t)j->n * es * sizeof(float)));
+    }
+    const float zero3[3] = {0, 0, 0}, one3[3] = {1, 1, 1};
+    launch_dpsis(ctx, g, P(J::DPS), P(J::IM1), es, 5.0f, zero3, one3, 0);                                // :35
+    for (int outer = 0; outer < p.niter_outer; outer++) {
+        launch_warp(ctx, g, P(J::WIM2), P(J::MASK), P(J::IM2), P(J::WX), P(J::WY), 1, es);               // :41
+        if (unfused) launch_deriv_stack(ctx, g, j->stack.f(), P(J::WIM2), P(J::IM1), es, es);            // :43
+        launch_zero_planes(ctx, g, P(J::DU), 2);                                                         // :45-46
+        launch_copy_planes(ctx, g, P(J::UU), P(J::WX), 2, es, es);                                       // :48-49
+        for (int inner = 0; inner < p.niter_inner; inner++) {
+            launch_smoothness_2f(ctx, g, P(J::SH), P(J::SV), P(J::UU), P(J::VV), P(J::DPS), half_alpha);   // :54
+            if (unfused)
+                launch_data_2f(ctx, g, j->stack.f(), P(J::MASK), P(J::DU), P(J::DV), P(J::A11), P(J::A12), P(J::A22), P(J::B1), P(J::B2), P(J::WX), P(J::WY), P(J::SH),
+                               P(J::SV), hd, hg);
+            else
+                launch_data_2f_fused(ctx, g, P(J::WIM2), P(J::IM1), P(J::MASK), P(J::DU), P(J::DV), P(J::A11), P(J::A12), P(J::A22), P(J::B1), P(J::B2), P(J::WX),
+                                     P(J::WY), P(J::SH), P(J::SV), hd, hg);                              // :43 + :55-57
+            SFA_TRY(sor_run(ctx, j->ws, g, P(J::DU), P(J::DV), P(J::A11), P(J::A12), P(J::A22), P(J::B1), P(J::B2), P(J::SH), P(J::SV), p.niter_solver, p.sor_omega,
+                            false));                                                                     // :59
+            launch_update_inner(ctx, g, P(J::UU), P(J::VV), P(J::WX), P(J::WY), P(J::DU), P(J::DV), P(J::DU), P(J::DV), ctx->d_red);   // :62-67
+        }
+        launch_copy_planes(ctx, g, P(J::WX), P(J::UU), 2, es, es);                                       // :70-71
+    }
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+int sfa_pair_job_download(sfa_pair_job *j, int b, float *wx, float *wy, int stride) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    CHECK_ARGS(b >= 0 && b < j->n, "b outside the job");
+    CHECK_ARGS(wx && wy, "null plane");
+    CHECK_ARGS(stride >= j->w, "stride below the width");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(download_plane(ctx, wx, stride, j->plane(b, sfa_pair_job::WX), j->pitch, j->w, j->h));
+    SFA_TRY(download_plane(ctx, wy, stride, j->plane(b, sfa_pair_job::WY), j->pitch, j->w, j->h));
+    return sfa_ctx_sync(ctx);
+}
+int sfa_pair_job_download_system(sfa_pair_job *j, int b, float *a11, float *a12, float *a22, float *b1, float *b2, int stride) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    CHECK_ARGS(b >= 0 && b < j->n, "b outside the job");
+    CHECK_ARGS(a11 && a12 && a22 && b1 && b2, "null plane");
+    CHECK_ARGS(stride >= j->w, "stride below the width");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    float *dst[5] = {a11, a12, a22, b1, b2};
+    for (int i = 0; i < 5; i++) SFA_TRY(download_plane(ctx, dst[i], stride, j->plane(b, sfa_pair_job::A11 + i), j->pitch, j->w, j->h));
+    return sfa_ctx_sync(ctx);
+}
+
 void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params) {
     static std::mutex mu;
     static sfa_ctx *def = nullptr;
@@ -1452,6 +1557,9 @@ int sfa_job_download_occlusions(sfa_job *j, int b, float *occ, int stride) {
 // ---- the device seam (include/slowflow_amd.h; kernels: device_io.hip) ---------------------------------------------------------------
 // Every check below is taken on the host before anything is launched; a refusal names the argument.
 #define REFUSE(...) return set_error(ctx, SFA_ERR_ARG, __VA_ARGS__)
+}  // extern "C"
+
+namespace sfa {      // the checks: shared with the pair jobs' seam in device_io.hip (declared in sfa_internal.h)
 
 // `p` must be device memory of the context's GPU, and the view (its last element `last` elements of `elem` bytes further) must lie inside p's allocation
 static int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem) {
@@ -1483,7 +1591,7 @@ static bool extent_add(long long *acc, long long steps, long long stride) {
 static size_t dev_elem_size(int dtype) { return dtype == SFA_DEV_F32 ? 4 : dtype == SFA_DEV_U16 ? 2 : 1; }
 
 // the frames of `nwin` windows (or sequence frames) of F frames each: layout and pointer
-static int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h) {
+int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h) {
     if (!l) REFUSE("%s: layout is null", fn);
     if (l->dtype != SFA_DEV_F32 && l->dtype != SFA_DEV_U8 && l->dtype != SFA_DEV_U16) REFUSE("%s: layout.dtype %d is no element type (fp32 0, u8 1, u16 2)", fn, l->dtype);
     if (l->column < 1) REFUSE("%s: layout.column = %lld: the column stride must be >= 1", fn, l->column);
@@ -1497,7 +1605,7 @@ static int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_
 }
 
 // a strided fp32 field of `nd` dimensions (sizes n[], strides st[], the last one the column): the pointer and the strides' signs
-static int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd) {
+int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd) {
     if (!st) REFUSE("%s: the strides of %s are null", fn, arg);
     if (st[nd - 1] < 1) REFUSE("%s: the column stride of %s is %lld: it must be >= 1", fn, arg, st[nd - 1]);
     long long last = 0;
@@ -1521,10 +1629,47 @@ static bool strides_nest(const long long *st, const int *n, int nd) {
     return true;
 }
 
-static int job_windows(sfa_ctx *ctx, const char *fn, const sfa_job *j, int b0, int n) {
-    if (b0 < 0 || n < 1 || (long)b0 + n > j->nb) REFUSE("%s: windows b0 = %d, n = %d lie outside the job's batch of %d", fn, b0, n, j->nb);
+int check_batch_range(sfa_ctx *ctx, const char *fn, const char *what, int b0, int n, int nb) {
+    if (b0 < 0 || n < 1 || (long)b0 + n > nb) REFUSE("%s: %s b0 = %d, n = %d lie outside the job's batch of %d", fn, what, b0, n, nb);
     return SFA_OK;
 }
+static int job_windows(sfa_ctx *ctx, const char *fn, const sfa_job *j, int b0, int n) { return check_batch_range(ctx, fn, "windows", b0, n, j->nb); }
+
+// overlap.  (1) every (window, plane) in a byte range of its own, and each plane free of overlap in itself; else (2) flow and occlusions apart, and each a
+// layout of nested strides.  Both are sufficient conditions: what neither proves is refused.
+int check_download_destination(sfa_ctx *ctx, const char *fn, int n, int w, int h, float *flow_dev, const long long strides[4], float *occ_dev,
+                               const long long occ_strides[3]) {
+    if (!flow_dev) REFUSE("%s: flow_dev is null", fn);
+    const int fsz[4] = {n, 2, h, w}, osz[3] = {n, h, w};
+    SFA_TRY(check_field(ctx, fn, "flow_dev", flow_dev, strides, fsz, 4));
+    if (occ_dev) SFA_TRY(check_field(ctx, fn, "occ_dev", occ_dev, occ_strides, osz, 3));
+    const uintptr_t f0 = reinterpret_cast<uintptr_t>(flow_dev), o0 = reinterpret_cast<uintptr_t>(occ_dev);
+    const long long fspan = (h - 1) * strides[2] + (w - 1) * strides[3];
+    const long long ospan = occ_dev ? (h - 1) * occ_strides[1] + (w - 1) * occ_strides[2] : 0;
+    bool ok = strides_nest(strides + 2, fsz + 2, 2) && (!occ_dev || strides_nest(occ_strides + 1, osz + 1, 2));
+    if (ok) {
+        std::vector<std::pair<uintptr_t, uintptr_t>> r;       // [first byte, last byte] of every plane
+        for (int i = 0; i < n; i++) {
+            for (int p = 0; p < 2; p++) { const uintptr_t a = f0 + 4 * (uintptr_t)(i * strides[0] + p * strides[1]); r.emplace_back(a, a + 4 * (uintptr_t)fspan + 3); }
+            if (occ_dev) { const uintptr_t a = o0 + 4 * (uintptr_t)(i * occ_strides[0]); r.emplace_back(a, a + 4 * (uintptr_t)ospan + 3); }
+        }
+        std::sort(r.begin(), r.end());
+        for (size_t i = 1; i < r.size() && ok; i++) ok = r[i].first > r[i - 1].second;
+    }
+    if (!ok) {
+        ok = strides_nest(strides, fsz, 4) && (!occ_dev || strides_nest(occ_strides, osz, 3));
+        if (ok && occ_dev) {
+            const uintptr_t fe = f0 + 4 * (uintptr_t)((n - 1) * strides[0] + strides[1] + fspan) + 3, oe = o0 + 4 * (uintptr_t)((n - 1) * occ_strides[0] + ospan) + 3;
+            ok = fe < o0 || oe < f0;
+        }
+    }
+    if (!ok) REFUSE("%s: the destinations overlap: windows or planes of flow_dev%s share memory (or lie interleaved in a way the check cannot clear)", fn, occ_dev ? " / occ_dev" : "");
+    return SFA_OK;
+}
+
+}  // namespace sfa
+
+extern "C" {
 
 void sfa_dev_layout_default(sfa_dev_layout *l, int w, int h, int n_frames) {
     if (!l) return;
@@ -1587,35 +1732,7 @@ int sfa_job_download_device(sfa_job *j, int b0, int n, float *flow_dev, const lo
     CHECK_ARGS(j, "job is null");
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     SFA_TRY(job_windows(ctx, __func__, j, b0, n));
-    CHECK_ARGS(flow_dev, "flow_dev is null");
-    const int fsz[4] = {n, 2, j->h, j->w}, osz[3] = {n, j->h, j->w};
-    SFA_TRY(check_field(ctx, __func__, "flow_dev", flow_dev, strides, fsz, 4));
-    if (occ_dev) SFA_TRY(check_field(ctx, __func__, "occ_dev", occ_dev, occ_strides, osz, 3));
-    // overlap.  (1) every (window, plane) in a byte range of its own, and each plane free of overlap in itself; else (2) flow and occlusions apart, and each a
-    // layout of nested strides.  Both are sufficient conditions: what neither proves is refused.
-    {
-        const uintptr_t f0 = reinterpret_cast<uintptr_t>(flow_dev), o0 = reinterpret_cast<uintptr_t>(occ_dev);
-        const long long fspan = (j->h - 1) * strides[2] + (j->w - 1) * strides[3];
-        const long long ospan = occ_dev ? (j->h - 1) * occ_strides[1] + (j->w - 1) * occ_strides[2] : 0;
-        bool ok = strides_nest(strides + 2, fsz + 2, 2) && (!occ_dev || strides_nest(occ_strides + 1, osz + 1, 2));
-        if (ok) {
-            std::vector<std::pair<uintptr_t, uintptr_t>> r;       // [first byte, last byte] of every plane
-            for (int i = 0; i < n; i++) {
-                for (int p = 0; p < 2; p++) { const uintptr_t a = f0 + 4 * (uintptr_t)(i * strides[0] + p * strides[1]); r.emplace_back(a, a + 4 * (uintptr_t)fspan + 3); }
-                if (occ_dev) { const uintptr_t a = o0 + 4 * (uintptr_t)(i * occ_strides[0]); r.emplace_back(a, a + 4 * (uintptr_t)ospan + 3); }
-            }
-            std::sort(r.begin(), r.end());
-            for (size_t i = 1; i < r.size() && ok; i++) ok = r[i].first > r[i - 1].second;
-        }
-        if (!ok) {
-            ok = strides_nest(strides, fsz, 4) && (!occ_dev || strides_nest(occ_strides, osz, 3));
-            if (ok && occ_dev) {
-                const uintptr_t fe = f0 + 4 * (uintptr_t)((n - 1) * strides[0] + strides[1] + fspan) + 3, oe = o0 + 4 * (uintptr_t)((n - 1) * occ_strides[0] + ospan) + 3;
-                ok = fe < o0 || oe < f0;
-            }
-        }
-        if (!ok) REFUSE("%s: the destinations overlap: windows or planes of flow_dev%s share memory (or lie interleaved in a way the check cannot clear)", __func__, occ_dev ? " / occ_dev" : "");
-    }
+    SFA_TRY(check_download_destination(ctx, __func__, n, j->w, j->h, flow_dev, strides, occ_dev, occ_strides));
     Level L0 = j->level(0);
     launch_unpack_planes(ctx, L0.plane(P_WX) + (long)b0 * j->es, L0.plane(P_WY) + (long)b0 * j->es, L0.plane(P_OCC) + (long)b0 * j->es, j->es, L0.pitch, j->w, j->h, n,
                          flow_dev, strides, occ_dev, occ_strides);

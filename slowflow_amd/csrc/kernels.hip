@@ -664,27 +664,15 @@ void launch_smoothness_2f(sfa_ctx *c, const Geo &g, float *sh, float *sv, const 
     dim3 grid((g.pitch + BX - 1) / BX, (g.h + BY - 1) / BY, g.nb);
     hipLaunchKernelGGL(k_smoothness_2f, grid, block2d(), 0, c->stream, sh, sv, uu, vv, dpsis, g, half_alpha);
 }
-// compute_data_and_match (variational_aux.c:215-302) followed by both sub_laplacian calls (variational.c:56-57, on wx / wy)
-__global__ void __launch_bounds__(BX *BY) k_data_2f(const float *__restrict__ D, const float *__restrict__ mask, const float *__restrict__ du, const float *__restrict__ dv,
-                                                     float *__restrict__ a11, float *__restrict__ a12, float *__restrict__ a22, float *__restrict__ b1, float *__restrict__ b2,
-                                                     const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ sh, const float *__restrict__ sv,
-                                                     Geo g, float hd, float hg) {
-    const int b = blockIdx.z;
-    const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
-    if (x >= g.w || y >= g.h) return;
-    const long eb = b * g.es;
-    const size_t o = (size_t)y * g.pitch + x;
-    const float *S = D + eb + o;
-    float ix[3], iy[3], iz[3], ixx[3], ixy[3], iyy[3], ixz[3], iyz[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        ix[k] = S[(0 * 3 + k) * g.pl]; iy[k] = S[(1 * 3 + k) * g.pl]; iz[k] = S[(2 * 3 + k) * g.pl];
-        ixx[k] = S[(3 * 3 + k) * g.pl]; ixy[k] = S[(4 * 3 + k) * g.pl]; iyy[k] = S[(5 * 3 + k) * g.pl];
-        ixz[k] = S[(6 * 3 + k) * g.pl]; iyz[k] = S[(7 * 3 + k) * g.pl];
-    }
-    const float u = du[eb + o], v = dv[eb + o], m = mask[eb + o];
+// compute_data_and_match (variational_aux.c:215-302) followed by both sub_laplacian calls (variational.c:56-57, on wx / wy): the system of ONE pixel from its 24
+// derivative values.  k_data_2f takes them from the stored stack, k_data_2f_fused from the LDS tiles it formed them in; both call this one body, so that the
+// two give the same bits by construction (no contraction, no SLP pairing in this translation unit).
+struct Deriv2f { float ix[3], iy[3], iz[3], ixx[3], ixy[3], iyy[3], ixz[3], iyz[3]; };
+__device__ __forceinline__ void data_2f_pixel(const Deriv2f &D, float u, float v, float m, float hd, float hg, const PlaneAcc &U, const PlaneAcc &V, const PlaneAcc &H,
+                                              const PlaneAcc &W, int x, int y, int w, int h, float &A11, float &A12, float &A22, float &B1, float &B2) {
+    const float *ix = D.ix, *iy = D.iy, *iz = D.iz, *ixx = D.ixx, *ixy = D.ixy, *iyy = D.iyy, *ixz = D.ixz, *iyz = D.iyz;
     const float dn = 0.1f * 0.1f;                                                        // datanorm (:10)
-    float A11 = 0.0f, A12 = 0.0f, A22 = 0.0f, B1 = 0.0f, B2 = 0.0f;
+    A11 = 0.0f; A12 = 0.0f; A22 = 0.0f; B1 = 0.0f; B2 = 0.0f;
     if (hd) {                                                                            // :245-269
         float t[3], n[3];
 #pragma unroll
@@ -716,14 +704,106 @@ __global__ void __launch_bounds__(BX *BY) k_data_2f(const float *__restrict__ D,
         B1 -= ta * ixx[k] * ixz[k] + tb * ixy[k] * iyz[k];
         B2 -= tb * iyy[k] * iyz[k] + ta * ixy[k] * ixz[k];
     }
+    B1 = laplacian_gather(B1, U, H, W, x, y, w, h);
+    B2 = laplacian_gather(B2, V, H, W, x, y, w, h);
+}
+__global__ void __launch_bounds__(BX *BY) k_data_2f(const float *__restrict__ D, const float *__restrict__ mask, const float *__restrict__ du, const float *__restrict__ dv,
+                                                     float *__restrict__ a11, float *__restrict__ a12, float *__restrict__ a22, float *__restrict__ b1, float *__restrict__ b2,
+                                                     const float *__restrict__ wx, const float *__restrict__ wy, const float *__restrict__ sh, const float *__restrict__ sv,
+                                                     Geo g, float hd, float hg) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+    if (x >= g.w || y >= g.h) return;
+    const long eb = b * g.es;
+    const size_t o = (size_t)y * g.pitch + x;
+    const float *S = D + eb + o;
+    Deriv2f d;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        d.ix[k] = S[(0 * 3 + k) * g.pl]; d.iy[k] = S[(1 * 3 + k) * g.pl]; d.iz[k] = S[(2 * 3 + k) * g.pl];
+        d.ixx[k] = S[(3 * 3 + k) * g.pl]; d.ixy[k] = S[(4 * 3 + k) * g.pl]; d.iyy[k] = S[(5 * 3 + k) * g.pl];
+        d.ixz[k] = S[(6 * 3 + k) * g.pl]; d.iyz[k] = S[(7 * 3 + k) * g.pl];
+    }
+    const float u = du[eb + o], v = dv[eb + o], m = mask[eb + o];
     PlaneAcc U{wx + eb, g.pitch}, V{wy + eb, g.pitch}, H{sh + eb, g.pitch}, W{sv + eb, g.pitch};
-    B1 = laplacian_gather(B1, U, H, W, x, y, g.w, g.h);
-    B2 = laplacian_gather(B2, V, H, W, x, y, g.w, g.h);
+    float A11, A12, A22, B1, B2;
+    data_2f_pixel(d, u, v, m, hd, hg, U, V, H, W, x, y, g.w, g.h, A11, A12, A22, B1, B2);
     a11[eb + o] = A11; a12[eb + o] = A12; a22[eb + o] = A22; b1[eb + o] = B1; b2[eb + o] = B2;
 }
 void launch_data_2f(sfa_ctx *c, const Geo &g, const float *D, const float *mask, const float *du, const float *dv, float *a11, float *a12, float *a22, float *b1,
                     float *b2, const float *wx, const float *wy, const float *sh, const float *sv, float hd, float hg) {
     hipLaunchKernelGGL(k_data_2f, grid2d(g), block2d(), 0, c->stream, D, mask, du, dv, a11, a12, a22, b1, b2, wx, wy, sh, sv, g, hd, hg);
+}
+
+// The same system straight from the image pair: get_derivatives' eight filters (k_deriv_stack's two stages, tile and halo) and data_2f_pixel in one pass, so that
+// the 24-plane stack of a pair is neither written nor read back.  One block = one DT_X x DT_Y tile of one pair; the three channels go through the same four LDS
+// tiles one after the other (4 x 24 x 72 floats = 27 648 bytes), a thread keeps the eight values of its DF_ROWS pixels and the channel in registers, and
+// once all 24 are there it forms the pixel's system.  Taps through d5x / d5y on TileAcc exactly as k_deriv_stack takes them: a clamped tap lies inside the image,
+// hence inside the staged halo; tile cells outside the image are neither written nor read.
+constexpr int DF_NT = 256, DF_ROWS = DT_Y / (DF_NT / DT_X);
+__global__ void __launch_bounds__(DF_NT) k_data_2f_fused(const float *__restrict__ I1, const float *__restrict__ I2, const float *__restrict__ mask,
+                                                         const float *__restrict__ du, const float *__restrict__ dv, float *__restrict__ a11, float *__restrict__ a12,
+                                                         float *__restrict__ a22, float *__restrict__ b1, float *__restrict__ b2, const float *__restrict__ wx,
+                                                         const float *__restrict__ wy, const float *__restrict__ sh, const float *__restrict__ sv, Geo g, float hd, float hg) {
+    __shared__ float sM[DT_R * DT_W], sZ[DT_R * DT_W], sX[DT_R * DT_W], sY[DT_R * DT_W];
+    const int b = blockIdx.z;
+    const long eb = b * g.es;
+    const int x0 = blockIdx.x * DT_X - DT_H, y0 = blockIdx.y * DT_Y - DT_H;
+    const int x = x0 + DT_H + (threadIdx.x & (DT_X - 1)), yt = y0 + DT_H + threadIdx.x / DT_X;      // the thread's pixels: (x, yt + r * DF_NT / DT_X)
+    const bool col = x < g.w;
+    Deriv2f d[DF_ROWS];
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const float *a = I1 + eb + ch * g.pl, *bb = I2 + eb + ch * g.pl;
+        if (ch) __syncthreads();                                      // the previous channel's taps have been taken
+        for (int i = threadIdx.x; i < DT_R * DT_W; i += DF_NT) {
+            const int sx = x0 + i % DT_W, sy = y0 + i / DT_W;
+            if (sx >= 0 && sx < g.w && sy >= 0 && sy < g.h) {
+                const size_t o = (size_t)sy * g.pitch + sx;
+                const float va = a[o], vb = bb[o];
+                sM[i] = 0.5f * (vb + va);                             // variational_aux.c get_derivatives: the mean of both images
+                sZ[i] = va - vb;                                      // Iz
+            }
+        }
+        __syncthreads();
+        const TileAcc m{sM, x0, y0};
+        constexpr int W1 = DT_X + 4, R1 = DT_Y + 4;                   // halo of 2
+        for (int i = threadIdx.x; i < R1 * W1; i += DF_NT) {
+            const int lx = 2 + i % W1, ly = 2 + i / W1;
+            const int sx = x0 + lx, sy = y0 + ly;
+            if (sx >= 0 && sx < g.w && sy >= 0 && sy < g.h) {
+                sX[ly * DT_W + lx] = d5x(m, sx, sy, g.w);             // Ix
+                sY[ly * DT_W + lx] = d5y(m, sx, sy, g.h);             // Iy
+            }
+        }
+        __syncthreads();
+        const TileAcc ix{sX, x0, y0}, iy{sY, x0, y0}, iz{sZ, x0, y0};
+#pragma unroll
+        for (int r = 0; r < DF_ROWS; r++) {
+            const int y = yt + r * (DF_NT / DT_X);
+            if (col && y < g.h) {
+                d[r].ix[ch] = ix(x, y); d[r].iy[ch] = iy(x, y); d[r].iz[ch] = iz(x, y);
+                d[r].ixx[ch] = d5x(ix, x, y, g.w); d[r].ixy[ch] = d5y(ix, x, y, g.h); d[r].iyy[ch] = d5y(iy, x, y, g.h);
+                d[r].ixz[ch] = d5x(iz, x, y, g.w); d[r].iyz[ch] = d5y(iz, x, y, g.h);
+            }
+        }
+    }
+    if (!col) return;
+    PlaneAcc U{wx + eb, g.pitch}, V{wy + eb, g.pitch}, H{sh + eb, g.pitch}, W{sv + eb, g.pitch};
+#pragma unroll
+    for (int r = 0; r < DF_ROWS; r++) {
+        const int y = yt + r * (DF_NT / DT_X);
+        if (y >= g.h) break;
+        const size_t o = (size_t)y * g.pitch + x;
+        float A11, A12, A22, B1, B2;
+        data_2f_pixel(d[r], du[eb + o], dv[eb + o], mask[eb + o], hd, hg, U, V, H, W, x, y, g.w, g.h, A11, A12, A22, B1, B2);
+        a11[eb + o] = A11; a12[eb + o] = A12; a22[eb + o] = A22; b1[eb + o] = B1; b2[eb + o] = B2;
+    }
+}
+void launch_data_2f_fused(sfa_ctx *c, const Geo &g, const float *I1, const float *I2, const float *mask, const float *du, const float *dv, float *a11, float *a12,
+                          float *a22, float *b1, float *b2, const float *wx, const float *wy, const float *sh, const float *sv, float hd, float hg) {
+    hipLaunchKernelGGL(k_data_2f_fused, dim3((g.w + DT_X - 1) / DT_X, (g.h + DT_Y - 1) / DT_Y, g.nb), dim3(DF_NT), 0, c->stream, I1, I2, mask, du, dv, a11, a12, a22, b1,
+                       b2, wx, wy, sh, sv, g, hd, hg);
 }
 
 // ---------------------------------------------------------------------------------------------------

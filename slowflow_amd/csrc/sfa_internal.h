@@ -117,7 +117,7 @@ struct Switches {
     enum Id {
         SOR_CHAIN, SOR_BAND, SOR_F, SOR_CH, SOR_LEAD, CHAIN_LDS, RB_TILE, WARP_ALLJ, NO_WARP_SMOOTH, ASSEMBLE_GENERIC, EXACT_DIV, ASM_XCD, NO_DIRECT_OPERANDS,
         NO_UV_ALIAS, DEBUG_ACTIVE, UNFUSED, SHARE_SOR, PYRAMID_UNFUSED, CUT_DISCHARGE, CUT_INNER, CUT_SUPER, CUT_TAIL_INNER, CUT_PER, CUT_TAIL_PER, CUT_TAIL_SUPER,
-        CUT_DEBUG, CUT_NO_TAIL, CUT_TAIL, NO_EXACT_BREAK, N
+        CUT_DEBUG, CUT_NO_TAIL, CUT_TAIL, NO_EXACT_BREAK, PAIR_UNFUSED, N
     };
     bool given[N] = {};
     int value[N] = {};
@@ -255,6 +255,9 @@ int launch_assemble_images(sfa_ctx *c, const Geo &g, const AssembleArgs &a, cons
 void launch_smoothness_2f(sfa_ctx *c, const Geo &g, float *sh, float *sv, const float *uu, const float *vv, const float *dpsis, float half_alpha);
 void launch_data_2f(sfa_ctx *c, const Geo &g, const float *D, const float *mask, const float *du, const float *dv, float *a11, float *a12, float *a22, float *b1,
                     float *b2, const float *wx, const float *wy, const float *sh, const float *sv, float hd, float hg);
+// launch_deriv_stack(I1, I2) + launch_data_2f in one kernel: the stack stays in LDS and registers (k_data_2f_fused); every plane at g.es
+void launch_data_2f_fused(sfa_ctx *c, const Geo &g, const float *I1, const float *I2, const float *mask, const float *du, const float *dv, float *a11, float *a12,
+                          float *a22, float *b1, float *b2, const float *wx, const float *wy, const float *sh, const float *sv, float hd, float hg);
 
 // ---- occlusion.hip: optimizeOcc (variational_aux_mt.cpp:758-887) ----------------------------------------------------
 struct OccSlot {
@@ -339,4 +342,32 @@ int sor_rb_run(sfa_ctx *c, const Geo &g, float *du, float *dv, float *a11, float
 int sor_run(sfa_ctx *c, SorWorkspace &ws, const Geo &g, float *du, float *dv, float *a11, float *a12, float *a22, const float *b1, const float *b2,
             const float *sh, const float *sv, int K, float omega, bool inv_out);
 
+// ---- the device seam's argument checks (api.hip), shared by sfa_job_*_device and sfa_pair_job_*_device (device_io.hip).  Each refuses with SFA_ERR_ARG and a
+// message that names `fn` and the argument; nothing is launched on a refusal ----------------------------------------------------------------------------
+// the frames of `nwin` windows (or pairs, or sequence frames) of F frames each: layout and pointer
+int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h);
+// a strided fp32 field of `nd` dimensions (sizes n[], strides st[], the last one the column): the pointer and the strides' signs
+int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd);
+// download destinations: flow [n][2][h][w] at `strides`, occlusions [n][h][w] at `occ_strides` (or null): pointers, strides, and freedom from overlap
+int check_download_destination(sfa_ctx *ctx, const char *fn, int n, int w, int h, float *flow_dev, const long long strides[4], float *occ_dev,
+                               const long long occ_strides[3]);
+// elements [b0, b0 + n) of a batch of nb (`what`: "windows", "pairs")
+int check_batch_range(sfa_ctx *ctx, const char *fn, const char *what, int b0, int n, int nb);
+
 }  // namespace sfa
+
+// ---- sfa_pair_job: n frame pairs of one size resident in HBM for the two-frame refinement (api.hip: sfa_pair_job_run; device_io.hip: its device seam) ----------
+// Pair b owns the planes [b * NPL, (b + 1) * NPL) of one allocation: the planes of sfa_variational_2frame without the derivative stack.  IM1 and IM2 lie next
+// to each other (launch_pack_frames fills them as frames 0 and 1 of a window), so do WX and WY (launch_pack_flow, launch_unpack_planes).
+struct sfa_pair_job {
+    enum { WX, WY, UU, VV, DU, DV, SH, SV, A11, A12, A22, B1, B2, MASK, DPS, IM1, IM2 = IM1 + 3, WIM2 = IM2 + 3, NPL = WIM2 + 3 };
+    sfa_ctx *ctx = nullptr;
+    int w = 0, h = 0, n = 0, pitch = 0;
+    long pl = 0, es = 0;
+    sfa_params_2frame p;
+    sfa::DevMem mem;
+    sfa::DevMem stack;               // SFA_PAIR_UNFUSED=1 only: 24 planes per pair, allocated by the first such run
+    sfa::SorWorkspace ws;
+    float *plane(int b, int i) const { return mem.f() + b * es + (long)i * pl; }
+    sfa::Geo geo() const { return sfa::Geo{w, h, pitch, pl, es, n, sfa::WMask::first(n), nullptr}; }
+};

@@ -2,10 +2,11 @@
 and results that live in GPU memory go in and out of a job without a host copy.
 
 The core takes any object with `__cuda_array_interface__` (torch-ROCm tensors, cupy arrays ...) and needs no torch; `import slowflow_amd` does not
-import this module, and this module imports torch only inside refine(), to allocate the outputs and to find the caller's current stream.
+import this module, and this module imports torch only inside refine() and refine_pairs(), to allocate the outputs and to find the caller's current
+stream.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which never waits for the GPU.
 
 Stream contract: the library works on the context's own stream.  Context.wait_stream(s) before the first call makes that stream wait for what the
-caller has submitted to s; Context.signal_stream(s) after the last makes s wait for the library.  refine() does both.  With the two in place a tensor
+caller has submitted to s; Context.signal_stream(s) after the last makes s wait for the library.  refine() and refine_pairs() do both.  With the two in place a tensor
 freed or reused on s is ordered after the library's last access, so torch's caching allocator needs no record_stream.
 """
 import ctypes as C
@@ -106,6 +107,9 @@ def _lib():
         L.sfa_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sfa_job_changes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.sfa_sequence_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DevLayout)]
+        L.sfa_pair_job_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(DevLayout)]
+        L.sfa_pair_job_set_flow_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.sfa_pair_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.sfa_ctx_wait_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.sfa_ctx_signal_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.sfa_dev_layout_default.argtypes = [C.POINTER(DevLayout), C.c_int, C.c_int, C.c_int]
@@ -206,8 +210,10 @@ def _job_for(ctx, params, w, h, nb):
 
 
 def release_jobs(ctx):
-    """closes the jobs refine() keeps on the context (they hold their device memory between calls)"""
+    """closes the jobs refine() and refine_pairs() keep on the context (they hold their device memory between calls)"""
     for job in ctx.__dict__.pop("_refine_jobs", {}).values():
+        job.close()
+    for job in ctx.__dict__.pop("_refine_pair_jobs", {}).values():
         job.close()
 
 
@@ -277,3 +283,98 @@ def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, s
         if seq is not None:
             seq.close()
     return out, occ, change
+
+
+# ---- resident pair jobs (sfa_pair_job): the two-frame refinement -------------------------------------------------------------------------------
+def pair_job_upload_device(job, frames, b0=0, channels_last=None):
+    v = device_view(frames, name="frames", ndim=5)
+    n, lay = frames_layout(v, job.w, job.h, 2, channels_last)
+    job.ctx._ck(_lib().sfa_pair_job_upload_device(job.h_, int(b0), n, C.c_void_p(v.ptr), C.byref(lay)), "sfa_pair_job_upload_device")
+
+
+def pair_job_set_flow_device(job, flow, b0=0, n=None):
+    if flow is None:
+        n = job.n - b0 if n is None else n
+        job.ctx._ck(_lib().sfa_pair_job_set_flow_device(job.h_, int(b0), int(n), None, None), "sfa_pair_job_set_flow_device")
+        return
+    v = device_view(flow, name="flow", ndim=4)
+    if v.dtype != DTYPES["f4"] or v.shape[1:] != (2, job.h, job.w):
+        raise sfa.SlowflowError(f"flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
+    job.ctx._ck(_lib().sfa_pair_job_set_flow_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), "sfa_pair_job_set_flow_device")
+
+
+def pair_job_download_device(job, out_flow, b0=0):
+    v = device_view(out_flow, writable=True, name="out_flow", ndim=4)
+    if v.shape[1:] != (2, job.h, job.w):
+        raise sfa.SlowflowError(f"out_flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
+    job.ctx._ck(_lib().sfa_pair_job_download_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), "sfa_pair_job_download_device")
+
+
+def pair_sizes(B):
+    """a batch of B pairs as jobs of at most MAX_BATCH pairs, of equal or nearly equal size (the split refine() uses)"""
+    pieces = -(-B // MAX_BATCH)
+    return [B // pieces + (1 if i < B % pieces else 0) for i in range(pieces)]
+
+
+def pair_geometry(fv, channels_last=None):
+    """frames [B,2,3,H,W] or [B,2,H,W,3] as a DeviceView -> (B, h, w); SlowflowError naming `frames` for anything else (three frames, a wrong rank ...)"""
+    if len(fv.shape) != 5:
+        raise sfa.SlowflowError(f"frames: rank {len(fv.shape)}, shape {fv.shape}; 5 dimensions expected")
+    if fv.shape[1] != 2:
+        raise sfa.SlowflowError(f"frames: shape {fv.shape} holds {fv.shape[1]} frames per pair; [B,2,3,H,W] or [B,2,H,W,3] expected")
+    last = (fv.shape[2] != 3 and fv.shape[4] == 3) if channels_last is None else channels_last
+    h, w = (fv.shape[2], fv.shape[3]) if last else (fv.shape[3], fv.shape[4])
+    B, _ = frames_layout(fv, w, h, 2, channels_last)
+    return B, h, w
+
+
+def _pair_job_for(ctx, params, w, h, n):
+    """a pair job of this shape and these parameters, kept on the context from call to call (two at most, like refine()'s jobs)"""
+    cache = ctx.__dict__.setdefault("_refine_pair_jobs", OrderedDict())
+    key = (w, h, n, bytes(params) if params is not None else None)
+    job = cache.get(key)
+    if job is not None and job.h_:
+        cache.move_to_end(key)
+        return job
+    while len(cache) >= 2:
+        cache.popitem(last=False)[1].close()
+    job = cache[key] = sfa.PairJob(ctx, w, h, n, params)
+    return job
+
+
+def refine_pairs(ctx, frames, flow0=None, params=None, *, stream=None, channels_last=None):
+    """The two-frame refinement (variational.c) of B frame pairs that live on the context's GPU: frames = a torch tensor [B,2,3,H,W] or [B,2,H,W,3] (fp32,
+    uint8 or uint16; any strides with a positive column stride), frame 0 = im1, frame 1 = im2; flow0 = None (zeros) or an fp32 tensor [B,2,H,W]; params =
+    None (variational_params_default) or a Params2f.  Returns a new fp32 tensor [B,2,H,W] on the frames' device.  The work is ordered after what `stream`
+    (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues and never waits for the GPU (a
+    pair job of a new shape is created first, which does).  B > 128 is split into jobs of equal or nearly equal size.  The jobs stay on the context per
+    (w, h, n, params) for the next call (release_jobs(ctx) or ctx.close() frees them)."""
+    import torch
+    fv = device_view(frames, name="frames")
+    B, h, w = pair_geometry(fv, channels_last)
+    flv = None
+    if flow0 is not None:
+        flv = device_view(flow0, name="flow0", ndim=4)
+        if flv.dtype != DTYPES["f4"] or flv.shape != (B, 2, h, w):
+            raise sfa.SlowflowError(f"flow0: fp32 [{B},2,{h},{w}] expected, got shape {flv.shape}")
+    if stream is None:
+        stream = torch.cuda.current_stream(frames.device)
+    with torch.cuda.stream(stream):                              # the output belongs to the caller's stream
+        out = torch.empty((B, 2, h, w), dtype=torch.float32, device=frames.device)
+    ov = device_view(out, writable=True, name="out_flow")
+    sizes = pair_sizes(B)
+    jobs = [_pair_job_for(ctx, params, w, h, n) for n in sorted(set(sizes), reverse=True)]      # creating a job waits for the context's stream: before the bracket
+    by_size = {j.n: j for j in jobs}
+    wait_stream(ctx, stream)
+    try:
+        b0 = 0
+        for n in sizes:
+            job = by_size[n]
+            pair_job_upload_device(job, fv.sub(b0, n), channels_last=channels_last)
+            pair_job_set_flow_device(job, flv.sub(b0, n) if flv is not None else None, 0, n)
+            job.run()
+            pair_job_download_device(job, ov.sub(b0, n))
+            b0 += n
+    finally:
+        signal_stream(ctx, stream)
+    return out
