@@ -107,7 +107,8 @@ int sfa_variational_2frame(sfa_ctx *ctx, float *wx, float *wy, int w, int h, int
 void sfa_params_2frame_default(sfa_params_2frame *p);          /* variational.c:86-98 */
 /* n independent pairs of one size (1 <= n <= 128), one parameter set, refined in place in one launch sequence on the context's stream: pair i
  * (wx[i], wy[i], im1[i], im2[i], each laid out as for sfa_variational_2frame) comes out bit-identical to sfa_variational_2frame on that pair alone,
- * whatever n and its position.  The adaptiveFR program refines its samples through this. */
+ * whatever n and its position.  The adaptiveFR program refines its samples through this.  (csrc/two_frame.hip: the single call is this one with n = 1, and
+ * both run the launch sequence of the resident pair jobs below on a pair job that lives for the call, with the stored derivative stack.) */
 int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *const *wy, int w, int h, int stride, const float *const *im1,
                                  const float *const *im2, const sfa_params_2frame *p);
 /* adaptiveFR's flow-magnitude quantile (adaptiveFR.cpp:644-668) on the GPU.  n host fields (u[i], v[i]: w x h, row stride `stride`); every value is scaled
@@ -199,7 +200,7 @@ void sfa_fuse_params_default(sfa_fuse_params *p);
 int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, const double *U, const double *V, const double *energy,
                         const unsigned long long *occ_bits, const float *weight, int *slot, double *flow_u, double *flow_v, unsigned char *occ,
                         double *seg_energy, double *seg_bound, int *seg_iters, float *stage_ms);
-/* ---- resident pair jobs: the two-frame refinement of pairs that stay in GPU memory ----------------------------------------------------
+/* ---- resident pair jobs: the two-frame refinement of pairs that stay in GPU memory (csrc/two_frame.hip) -------------------------------
  * A pair job owns the planes of n pairs of one size (24 per pair: those of sfa_variational_2frame without its 24-plane derivative stack) and one solver
  * workspace, across any number of uploads and runs.  sfa_pair_job_run enqueues variational()'s launch sequence (variational.c:19-82) for all n pairs on the
  * context's stream and RETURNS WITHOUT WAITING -- the two-frame path has no break decision, so nothing needs the host: the one refinement entry point of
@@ -369,7 +370,7 @@ int  sfa_job_download_device(sfa_job *job, int b0, int n, float *flow_dev, const
 int  sfa_job_changes(const sfa_job *job, int b0, int n, float *out);
 /* Replaces sfa_sequence_upload for the frames [f0, f0 + n): frame i at frames_dev + i * layout->frame (layout->window is not used). */
 int  sfa_sequence_upload_device(sfa_sequence *seq, int f0, int n, const void *frames_dev, const sfa_dev_layout *layout);
-/* The same seam for resident pair jobs, the pairs [b0, b0 + n): the same kernels, one launch per call, no host copy, no wait, columns >= width never
+/* The same seam for resident pair jobs (csrc/two_frame.hip), the pairs [b0, b0 + n): the same kernels, one launch per call, no host copy, no wait, columns >= width never
  * written, and the same refusals by the same checks.  frames_dev holds two frames per pair: the layout's frame index 0 is im1, 1 is im2 (layout->window
  * steps from pair to pair).  flow_dev NULL in set_flow: zeros.  upload_device leaves the pairs' flow as it is, like sfa_job_upload_device. */
 int  sfa_pair_job_upload_device(sfa_pair_job *job, int b0, int n, const void *frames_dev, const sfa_dev_layout *layout);

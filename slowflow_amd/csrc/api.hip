@@ -700,7 +700,6 @@ struct Staging {
         return SFA_OK;
     }
 };
-#define CHECK_ARGS(cond, msg) do { if (!(cond)) return set_error(ctx, SFA_ERR_ARG, "%s: %s", __func__, msg); } while (0)
 
 int sfa_image_warp(sfa_ctx *ctx, float *dst3, float *mask, const float *src3, const float *wx, const float *wy, int w, int h, int stride, int factor) {
     CHECK_ARGS(ctx && dst3 && src3 && wx && wy && w > 0 && h > 0 && stride >= w, "bad arguments");
@@ -1003,220 +1002,6 @@ void sor_coupled(sfa_image *du, sfa_image *dv, sfa_image *a11, sfa_image *a12, s
     }
     if (sfa_sor_coupled(def, du, dv, a11, a12, a22, b1, b2, dpsis_horiz, dpsis_vert, iterations, omega) != SFA_OK) {
         fprintf(stderr, "error in sor_coupled(): %s\n", sfa_last_error(def));
-        exit(1);
-    }
-}
-
-// ---- the original two-frame refinement (variational.c:19-143) --------------------------------------------------
-void sfa_params_2frame_default(sfa_params_2frame *p) {                                   // variational.c:86-98
-    if (!p) return;
-    p->alpha = 1.0f; p->gamma = 0.71f; p->delta = 0.0f; p->sigma = 1.00f;
-    p->niter_outer = 5; p->niter_inner = 1; p->niter_solver = 30; p->sor_omega = 1.9f;
-}
-
-int sfa_variational_2frame(sfa_ctx *ctx, float *wx, float *wy, int w, int h, int stride, const float *im1, const float *im2, const sfa_params_2frame *pp) {
-    CHECK_ARGS(ctx && wx && wy && im1 && im2 && w >= 2 && h >= 5 && stride >= w, "bad arguments (h >= 5, w >= 2)");
-    sfa_params_2frame p;
-    if (pp) p = *pp; else sfa_params_2frame_default(&p);
-    const float half_alpha = 0.5f * p.alpha, hg = p.gamma * 0.5f / 3.0f, hd = p.delta * 0.5f / 3.0f;   // :113-115
-    enum { WX, WY, UU, VV, DU, DV, SH, SV, A11, A12, A22, B1, B2, MASK, DPS, IM1, IM2 = IM1 + 3, WIM2 = IM2 + 3, STACK = WIM2 + 3, NPL = STACK + 24 };
-    Staging s;
-    SFA_TRY(s.init(ctx, w, h, NPL));
-    SFA_TRY(s.up(WX, wx, stride)); SFA_TRY(s.up(WY, wy, stride));
-    SFA_TRY(s.up(IM1, im1, stride, 3)); SFA_TRY(s.up(IM2, im2, stride, 3));
-    const Geo g = s.geo();
-    const float zero3[3] = {0, 0, 0}, one3[3] = {1, 1, 1};
-    launch_dpsis(ctx, g, s.plane(DPS), s.plane(IM1), 0, 5.0f, zero3, one3, 0);                           // :35
-    SorWorkspace ws;
-    for (int outer = 0; outer < p.niter_outer; outer++) {
-        launch_warp(ctx, g, s.plane(WIM2), s.plane(MASK), s.plane(IM2), s.plane(WX), s.plane(WY), 1, 0);   // :41
-        launch_deriv_stack(ctx, g, s.plane(STACK), s.plane(WIM2), s.plane(IM1), 0, 0);                   // :43 (mean of both, dt = im2 - im1)
-        launch_zero_planes(ctx, g, s.plane(DU), 2);                                                      // :45-46
-        launch_copy_planes(ctx, g, s.plane(UU), s.plane(WX), 2, 0, 0);                                   // :48-49
-        for (int inner = 0; inner < p.niter_inner; inner++) {
-            launch_smoothness_2f(ctx, g, s.plane(SH), s.plane(SV), s.plane(UU), s.plane(VV), s.plane(DPS), half_alpha);   // :54
-            launch_data_2f(ctx, g, s.plane(STACK), s.plane(MASK), s.plane(DU), s.plane(DV), s.plane(A11), s.plane(A12), s.plane(A22), s.plane(B1), s.plane(B2),
-                           s.plane(WX), s.plane(WY), s.plane(SH), s.plane(SV), hd, hg);                  // :55-57
-            SFA_TRY(sor_run(ctx, ws, g, s.plane(DU), s.plane(DV), s.plane(A11), s.plane(A12), s.plane(A22), s.plane(B1), s.plane(B2), s.plane(SH), s.plane(SV),
-                            p.niter_solver, p.sor_omega, false));                                       // :59
-            // uu = wx + du, vv = wy + dv (:62-67); the change norms of the shared kernel are not used here
-            launch_update_inner(ctx, g, s.plane(UU), s.plane(VV), s.plane(WX), s.plane(WY), s.plane(DU), s.plane(DV), s.plane(DU), s.plane(DV), ctx->d_red);
-        }
-        launch_copy_planes(ctx, g, s.plane(WX), s.plane(UU), 2, 0, 0);                                   // :70-71
-    }
-    SFA_TRY(check_device_error(ctx));
-    SFA_TRY(s.down(wx, stride, WX)); SFA_TRY(s.down(wy, stride, WY));
-    return sfa_ctx_sync(ctx);
-}
-
-// n pairs of one size through the launch sequence above at once: pair i owns planes [i * NPL, (i + 1) * NPL) of one allocation, so that every launcher
-// reaches it `es` = NPL planes further along (grid z = pair).  Every launch of the single call, checked for that batch stride:
-//   launch_dpsis (its im_es), launch_warp (src_es; dst, mask, wx, wy at g.es), launch_deriv_stack (es1, es2; out at g.es), launch_zero_planes (g.es),
-//   launch_copy_planes (dst_es, src_es -- the single call passes 0, 0), launch_smoothness_2f / launch_data_2f (g.es throughout), sor_run (a workspace of
-//   g.nb systems, operands and results at g.es), launch_update_inner (g.es; its change norms land in ctx->d_red[2 b], unused here, and its per-block partials
-//   -- 2 x nb x ceil(w / 64) x 16 doubles -- behind them: the kRedDoubles check below, as in sfa_job_create).
-// Same kernels, same per-pixel arithmetic, no cross-pair reduction that feeds back: pair i is bit-identical to sfa_variational_2frame on pair i alone.
-int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *const *wy, int w, int h, int stride, const float *const *im1,
-                                 const float *const *im2, const sfa_params_2frame *pp) {
-    CHECK_ARGS(ctx && wx && wy && im1 && im2 && w >= 2 && h >= 5 && stride >= w, "bad arguments (h >= 5, w >= 2)");
-    CHECK_ARGS(n >= 1 && n <= kMaxBatch, "n out of range (1 .. 128 pairs)");
-    CHECK_ARGS(2L * kMaxBatch + 2L * n * ((w + 63) / 64) * 16 <= kRedDoubles, "n x width beyond the change norms' scratch (sfa_internal.h: kRedDoubles)");
-    for (int i = 0; i < n; i++) CHECK_ARGS(wx[i] && wy[i] && im1[i] && im2[i], "null plane");
-    sfa_params_2frame p;
-    if (pp) p = *pp; else sfa_params_2frame_default(&p);
-    const float half_alpha = 0.5f * p.alpha, hg = p.gamma * 0.5f / 3.0f, hd = p.delta * 0.5f / 3.0f;   // variational.c:113-115
-    enum { WX, WY, UU, VV, DU, DV, SH, SV, A11, A12, A22, B1, B2, MASK, DPS, IM1, IM2 = IM1 + 3, WIM2 = IM2 + 3, STACK = WIM2 + 3, NPL = STACK + 24 };
-    Staging s;
-    SFA_TRY(s.init(ctx, w, h, n * NPL));
-    const long es = NPL * s.pl;
-    for (int i = 0; i < n; i++) {
-        const int b = i * NPL;
-        SFA_TRY(s.up(b + WX, wx[i], stride)); SFA_TRY(s.up(b + WY, wy[i], stride));
-        SFA_TRY(s.up(b + IM1, im1[i], stride, 3)); SFA_TRY(s.up(b + IM2, im2[i], stride, 3));
-    }
-    const Geo g{w, h, s.pitch, s.pl, es, n, WMask::first(n), nullptr};
-    const float zero3[3] = {0, 0, 0}, one3[3] = {1, 1, 1};
-    launch_dpsis(ctx, g, s.plane(DPS), s.plane(IM1), es, 5.0f, zero3, one3, 0);                          // :35
-    SorWorkspace ws;
-    for (int outer = 0; outer < p.niter_outer; outer++) {
-        launch_warp(ctx, g, s.plane(WIM2), s.plane(MASK), s.plane(IM2), s.plane(WX), s.plane(WY), 1, es);  // :41
-        launch_deriv_stack(ctx, g, s.plane(STACK), s.plane(WIM2), s.plane(IM1), es, es);                 // :43
-        launch_zero_planes(ctx, g, s.plane(DU), 2);                                                      // :45-46
-        launch_copy_planes(ctx, g, s.plane(UU), s.plane(WX), 2, es, es);                                 // :48-49
-        for (int inner = 0; inner < p.niter_inner; inner++) {
-            launch_smoothness_2f(ctx, g, s.plane(SH), s.plane(SV), s.plane(UU), s.plane(VV), s.plane(DPS), half_alpha);   // :54
-            launch_data_2f(ctx, g, s.plane(STACK), s.plane(MASK), s.plane(DU), s.plane(DV), s.plane(A11), s.plane(A12), s.plane(A22), s.plane(B1), s.plane(B2),
-                           s.plane(WX), s.plane(WY), s.plane(SH), s.plane(SV), hd, hg);                  // :55-57
-            SFA_TRY(sor_run(ctx, ws, g, s.plane(DU), s.plane(DV), s.plane(A11), s.plane(A12), s.plane(A22), s.plane(B1), s.plane(B2), s.plane(SH), s.plane(SV),
-                            p.niter_solver, p.sor_omega, false));                                       // :59
-            launch_update_inner(ctx, g, s.plane(UU), s.plane(VV), s.plane(WX), s.plane(WY), s.plane(DU), s.plane(DV), s.plane(DU), s.plane(DV), ctx->d_red);   // :62-67
-        }
-        launch_copy_planes(ctx, g, s.plane(WX), s.plane(UU), 2, es, es);                                 // :70-71
-    }
-    SFA_TRY(check_device_error(ctx));
-    for (int i = 0; i < n; i++) { SFA_TRY(s.down(wx[i], stride, i * NPL + WX)); SFA_TRY(s.down(wy[i], stride, i * NPL + WY)); }
-    return sfa_ctx_sync(ctx);
-}
-
-// ---- resident pair jobs: the two-frame refinement of n pairs that stay in HBM (struct: sfa_internal.h) ------------------------------------------
-// The launch sequence of sfa_variational_2frame_batch on planes the job owns, with launch_deriv_stack + launch_data_2f replaced by k_data_2f_fused: 24 planes
-// per pair, no stack.  Same per-pixel arithmetic (kernels.hip: data_2f_pixel), same taps: pair b is bit-identical to sfa_variational_2frame on that pair alone.
-// The solver workspace is shaped at creation, so that sfa_pair_job_run only enqueues: the two-frame path has no break decision, nothing needs the host.
-int sfa_pair_job_create(sfa_ctx *ctx, const sfa_params_2frame *pp, int w, int h, int n, sfa_pair_job **out) {
-    CHECK_ARGS(ctx && out, "ctx or out is null");
-    CHECK_ARGS(w >= 2 && h >= 5, "bad arguments (h >= 5, w >= 2)");
-    CHECK_ARGS(n >= 1 && n <= kMaxBatch, "n out of range (1 .. 128 pairs)");
-    CHECK_ARGS(2L * kMaxBatch + 2L * n * ((w + 63) / 64) * 16 <= kRedDoubles, "n x width beyond the change norms' scratch (sfa_internal.h: kRedDoubles)");
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<sfa_pair_job> j(new sfa_pair_job());
-    j->ctx = ctx; j->w = w; j->h = h; j->n = n; j->pitch = dev_pitch(w);
-    j->pl = (long)j->pitch * h; j->es = sfa_pair_job::NPL * j->pl;
-    if (pp) j->p = *pp; else sfa_params_2frame_default(&j->p);
-    SFA_TRY(j->mem.alloc(ctx, (size_t)n * j->es * sizeof(float)));
-    SFA_HIP(ctx, hipMemsetAsync(j->mem.p, 0, (size_t)n * j->es * sizeof(float), ctx->stream));
-    if (j->p.niter_solver >= 1) SFA_TRY(j->ws.configure(ctx, w, h, j->p.niter_solver, n));     // (waits for the stream once, here and not in the first run)
-    *out = j.release();
-    return SFA_OK;
-}
-void sfa_pair_job_destroy(sfa_pair_job *j) {
-    if (!j) return;
-    (void)hipSetDevice(j->ctx->device);
-    (void)hipStreamSynchronize(j->ctx->stream);
-    delete j;
-}
-int sfa_pair_job_upload(sfa_pair_job *j, int b, const float *wx, const float *wy, int stride, const float *im1, const float *im2) {
-    sfa_ctx *ctx = j ? j->ctx : nullptr;
-    CHECK_ARGS(j, "job is null");
-    CHECK_ARGS(b >= 0 && b < j->n, "b outside the job");
-    CHECK_ARGS(wx && wy && im1 && im2, "null plane");
-    CHECK_ARGS(stride >= j->w, "stride below the width");
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::WX), j->pitch, wx, stride, j->w, j->h));
-    SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::WY), j->pitch, wy, stride, j->w, j->h));
-    for (int k = 0; k < 3; k++) {
-        SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::IM1 + k), j->pitch, im1 + (size_t)k * stride * j->h, stride, j->w, j->h));
-        SFA_TRY(upload_plane(ctx, j->plane(b, sfa_pair_job::IM2 + k), j->pitch, im2 + (size_t)k * stride * j->h, stride, j->w, j->h));
-    }
-    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the copies read the caller's pageable memory (like sfa_job_upload)
-    return SFA_OK;
-}
-int sfa_pair_job_run(sfa_pair_job *j) {
-    sfa_ctx *ctx = j ? j->ctx : nullptr;
-    CHECK_ARGS(j, "job is null");
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    typedef sfa_pair_job J;
-    const sfa_params_2frame &p = j->p;
-    const float half_alpha = 0.5f * p.alpha, hg = p.gamma * 0.5f / 3.0f, hd = p.delta * 0.5f / 3.0f;   // variational.c:113-115
-    const long es = j->es;
-    const Geo g = j->geo();
-    auto P = [&](int i) { return j->plane(0, i); };
-    const bool unfused = sw_int(Switches::PAIR_UNFUSED, 0) != 0;      // cross-check: the stored stack and k_data_2f (the release build: constant false)
-    if (unfused) {
-        // pair b's stack lies J::NPL planes after pair b - 1's, as every plane of the job does (launch_data_2f knows one batch stride): 24 = 8 derivatives x 3 channels
-        static_assert(J::NPL == 24, "the lazily allocated stack shares the job's pair stride");
-        SFA_TRY(j->stack.alloc(ctx, (size_t)j->n * es * sizeof(float)));
-    }
-    const float zero3[3] = {0, 0, 0}, one3[3] = {1, 1, 1};
-    launch_dpsis(ctx, g, P(J::DPS), P(J::IM1), es, 5.0f, zero3, one3, 0);                                // :35
-    for (int outer = 0; outer < p.niter_outer; outer++) {
-        launch_warp(ctx, g, P(J::WIM2), P(J::MASK), P(J::IM2), P(J::WX), P(J::WY), 1, es);               // :41
-        if (unfused) launch_deriv_stack(ctx, g, j->stack.f(), P(J::WIM2), P(J::IM1), es, es);            // :43
-        launch_zero_planes(ctx, g, P(J::DU), 2);                                                         // :45-46
-        launch_copy_planes(ctx, g, P(J::UU), P(J::WX), 2, es, es);                                       // :48-49
-        for (int inner = 0; inner < p.niter_inner; inner++) {
-            launch_smoothness_2f(ctx, g, P(J::SH), P(J::SV), P(J::UU), P(J::VV), P(J::DPS), half_alpha);   // :54
-            if (unfused)
-                launch_data_2f(ctx, g, j->stack.f(), P(J::MASK), P(J::DU), P(J::DV), P(J::A11), P(J::A12), P(J::A22), P(J::B1), P(J::B2), P(J::WX), P(J::WY), P(J::SH),
-                               P(J::SV), hd, hg);
-            else
-                launch_data_2f_fused(ctx, g, P(J::WIM2), P(J::IM1), P(J::MASK), P(J::DU), P(J::DV), P(J::A11), P(J::A12), P(J::A22), P(J::B1), P(J::B2), P(J::WX),
-                                     P(J::WY), P(J::SH), P(J::SV), hd, hg);                              // :43 + :55-57
-            SFA_TRY(sor_run(ctx, j->ws, g, P(J::DU), P(J::DV), P(J::A11), P(J::A12), P(J::A22), P(J::B1), P(J::B2), P(J::SH), P(J::SV), p.niter_solver, p.sor_omega,
-                            false));                                                                     // :59
-            launch_update_inner(ctx, g, P(J::UU), P(J::VV), P(J::WX), P(J::WY), P(J::DU), P(J::DV), P(J::DU), P(J::DV), ctx->d_red);   // :62-67
-        }
-        launch_copy_planes(ctx, g, P(J::WX), P(J::UU), 2, es, es);                                       // :70-71
-    }
-    SFA_HIP(ctx, hipGetLastError());
-    return SFA_OK;
-}
-int sfa_pair_job_download(sfa_pair_job *j, int b, float *wx, float *wy, int stride) {
-    sfa_ctx *ctx = j ? j->ctx : nullptr;
-    CHECK_ARGS(j, "job is null");
-    CHECK_ARGS(b >= 0 && b < j->n, "b outside the job");
-    CHECK_ARGS(wx && wy, "null plane");
-    CHECK_ARGS(stride >= j->w, "stride below the width");
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    SFA_TRY(download_plane(ctx, wx, stride, j->plane(b, sfa_pair_job::WX), j->pitch, j->w, j->h));
-    SFA_TRY(download_plane(ctx, wy, stride, j->plane(b, sfa_pair_job::WY), j->pitch, j->w, j->h));
-    return sfa_ctx_sync(ctx);
-}
-int sfa_pair_job_download_system(sfa_pair_job *j, int b, float *a11, float *a12, float *a22, float *b1, float *b2, int stride) {
-    sfa_ctx *ctx = j ? j->ctx : nullptr;
-    CHECK_ARGS(j, "job is null");
-    CHECK_ARGS(b >= 0 && b < j->n, "b outside the job");
-    CHECK_ARGS(a11 && a12 && a22 && b1 && b2, "null plane");
-    CHECK_ARGS(stride >= j->w, "stride below the width");
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    float *dst[5] = {a11, a12, a22, b1, b2};
-    for (int i = 0; i < 5; i++) SFA_TRY(download_plane(ctx, dst[i], stride, j->plane(b, sfa_pair_job::A11 + i), j->pitch, j->w, j->h));
-    return sfa_ctx_sync(ctx);
-}
-
-void variational(sfa_image *wx, sfa_image *wy, const sfa_color_image *im1, const sfa_color_image *im2, sfa_params_2frame *params) {
-    static std::mutex mu;
-    static sfa_ctx *def = nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!def && sfa_ctx_create(0, &def) != SFA_OK) {
-        fprintf(stderr, "error in variational(): %s\n", sfa_last_error(nullptr));
-        exit(1);
-    }
-    const bool ok = wx && wy && im1 && im2 && wx->data && wy->data && im1->c1 && im2->c1 && wy->width == wx->width && wy->height == wx->height &&
-                    wy->stride == wx->stride && im1->width == wx->width && im1->height == wx->height && im1->stride == wx->stride &&
-                    im2->width == wx->width && im2->height == wx->height && im2->stride == wx->stride &&
-                    im1->c2 == im1->c1 + (size_t)im1->stride * im1->height && im2->c2 == im2->c1 + (size_t)im2->stride * im2->height;
-    if (!ok || sfa_variational_2frame(def, wx->data, wy->data, wx->width, wx->height, wx->stride, im1->c1, im2->c1, params) != SFA_OK) {
-        fprintf(stderr, "error in variational(): %s\n", ok ? sfa_last_error(def) : "images must share one geometry (color_image_new layout)");
         exit(1);
     }
 }
@@ -1559,7 +1344,7 @@ int sfa_job_download_occlusions(sfa_job *j, int b, float *occ, int stride) {
 #define REFUSE(...) return set_error(ctx, SFA_ERR_ARG, __VA_ARGS__)
 }  // extern "C"
 
-namespace sfa {      // the checks: shared with the pair jobs' seam in device_io.hip (declared in sfa_internal.h)
+namespace sfa {      // the checks: shared with the pair jobs' seam in two_frame.hip (declared in sfa_internal.h)
 
 // `p` must be device memory of the context's GPU, and the view (its last element `last` elements of `elem` bytes further) must lie inside p's allocation
 static int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem) {

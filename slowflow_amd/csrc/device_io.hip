@@ -9,7 +9,6 @@
 //     path, and its neighbours gained more than it did),
 //   - a thread issues the loads of its four rows before the first store, so that no load queues behind a store in the wave's in-order memory counter.
 // The checks of the arguments (device pointers of this GPU, strides, overlap) are api.hip's: nothing here is launched on a refused argument.
-// At the end of the file: the same seam for resident pair jobs (sfa_pair_job_*_device), on the same kernels and the same checks.
 #include "sfa_internal.h"
 
 namespace sfa {
@@ -198,49 +197,3 @@ void launch_unpack_planes(sfa_ctx *c, const float *wx, const float *wy, const fl
 }
 
 }  // namespace sfa
-
-// ---- the device seam of the resident pair jobs (include/slowflow_amd.h) -----------------------------------------------------------------
-// A pair is a window of two frames for k_pack_frames (IM1, IM2 lie next to each other in the job), its flow the planes WX, WY for k_pack_flow and
-// k_unpack_planes: no kernel of its own.  One launch per call, nothing waits.
-using namespace sfa;
-
-extern "C" {
-
-int sfa_pair_job_upload_device(sfa_pair_job *j, int b0, int n, const void *frames_dev, const sfa_dev_layout *l) {
-    sfa_ctx *ctx = j ? j->ctx : nullptr;
-    if (!j) return set_error(nullptr, SFA_ERR_ARG, "%s: job is null", __func__);
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    SFA_TRY(check_batch_range(ctx, __func__, "pairs", b0, n, j->n));
-    SFA_TRY(check_frames_source(ctx, __func__, frames_dev, l, l ? l->window : 0, n, 2, j->w, j->h));
-    const PackSrc src{frames_dev, l->dtype, l->window, l->frame, l->channel, l->row, l->column};
-    launch_pack_frames(ctx, j->plane(b0, sfa_pair_job::IM1), j->es, j->pl, j->pitch, j->w, j->h, n, 2, src);
-    SFA_HIP(ctx, hipGetLastError());
-    return SFA_OK;
-}
-
-int sfa_pair_job_set_flow_device(sfa_pair_job *j, int b0, int n, const float *flow_dev, const long long strides[4]) {
-    sfa_ctx *ctx = j ? j->ctx : nullptr;
-    if (!j) return set_error(nullptr, SFA_ERR_ARG, "%s: job is null", __func__);
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    SFA_TRY(check_batch_range(ctx, __func__, "pairs", b0, n, j->n));
-    if (flow_dev) {
-        const int sizes[4] = {n, 2, j->h, j->w};
-        SFA_TRY(check_field(ctx, __func__, "flow_dev", flow_dev, strides, sizes, 4));
-    }
-    launch_pack_flow(ctx, j->plane(b0, sfa_pair_job::WX), j->es, j->pl, j->pitch, j->w, j->h, n, flow_dev, strides);
-    SFA_HIP(ctx, hipGetLastError());
-    return SFA_OK;
-}
-
-int sfa_pair_job_download_device(sfa_pair_job *j, int b0, int n, float *flow_dev, const long long strides[4]) {
-    sfa_ctx *ctx = j ? j->ctx : nullptr;
-    if (!j) return set_error(nullptr, SFA_ERR_ARG, "%s: job is null", __func__);
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    SFA_TRY(check_batch_range(ctx, __func__, "pairs", b0, n, j->n));
-    SFA_TRY(check_download_destination(ctx, __func__, n, j->w, j->h, flow_dev, strides, nullptr, nullptr));
-    launch_unpack_planes(ctx, j->plane(b0, sfa_pair_job::WX), j->plane(b0, sfa_pair_job::WY), nullptr, j->es, j->pitch, j->w, j->h, n, flow_dev, strides, nullptr, nullptr);
-    SFA_HIP(ctx, hipGetLastError());
-    return SFA_OK;
-}
-
-}  // extern "C"

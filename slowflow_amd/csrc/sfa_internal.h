@@ -154,6 +154,10 @@ inline int sw_int(Switches::Id i, int dflt) { return g_switches.given[i] ? g_swi
         if (_rc != SFA_OK) return _rc; \
     } while (0)
 
+// argument checks of the entry points: refuse with "<function>: <msg>" on the context `ctx` of the scope (a helper names its caller in `fn`)
+#define CHECK_ARGS_FN(fn, cond, msg) do { if (!(cond)) return sfa::set_error(ctx, SFA_ERR_ARG, "%s: %s", fn, msg); } while (0)
+#define CHECK_ARGS(cond, msg) CHECK_ARGS_FN(__func__, cond, msg)
+
 inline int round_up(int a, int m) { return (a + m - 1) / m * m; }
 inline int host_stride(int w) { return ((w + 3) / 4) * 4; }     // image.c:25
 #ifndef SFA_PITCH_ODD
@@ -342,7 +346,7 @@ int sor_rb_run(sfa_ctx *c, const Geo &g, float *du, float *dv, float *a11, float
 int sor_run(sfa_ctx *c, SorWorkspace &ws, const Geo &g, float *du, float *dv, float *a11, float *a12, float *a22, const float *b1, const float *b2,
             const float *sh, const float *sv, int K, float omega, bool inv_out);
 
-// ---- the device seam's argument checks (api.hip), shared by sfa_job_*_device and sfa_pair_job_*_device (device_io.hip).  Each refuses with SFA_ERR_ARG and a
+// ---- the device seam's argument checks (api.hip), shared by sfa_job_*_device and sfa_pair_job_*_device (two_frame.hip).  Each refuses with SFA_ERR_ARG and a
 // message that names `fn` and the argument; nothing is launched on a refusal ----------------------------------------------------------------------------
 // the frames of `nwin` windows (or pairs, or sequence frames) of F frames each: layout and pointer
 int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h);
@@ -356,17 +360,18 @@ int check_batch_range(sfa_ctx *ctx, const char *fn, const char *what, int b0, in
 
 }  // namespace sfa
 
-// ---- sfa_pair_job: n frame pairs of one size resident in HBM for the two-frame refinement (api.hip: sfa_pair_job_run; device_io.hip: its device seam) ----------
-// Pair b owns the planes [b * NPL, (b + 1) * NPL) of one allocation: the planes of sfa_variational_2frame without the derivative stack.  IM1 and IM2 lie next
-// to each other (launch_pack_frames fills them as frames 0 and 1 of a window), so do WX and WY (launch_pack_flow, launch_unpack_planes).
+// ---- sfa_pair_job: n frame pairs of one size in HBM for the two-frame refinement (two_frame.hip: the one launch sequence, the resident jobs, the host calls) ----
+// Pair b owns the planes [b * NPL, (b + 1) * NPL) of one allocation; this enum is the only statement of the plane list.  IM1 and IM2 lie next to each other
+// (launch_pack_frames fills them as frames 0 and 1 of a window), so do WX and WY (launch_pack_flow, launch_unpack_planes).
 struct sfa_pair_job {
     enum { WX, WY, UU, VV, DU, DV, SH, SV, A11, A12, A22, B1, B2, MASK, DPS, IM1, IM2 = IM1 + 3, WIM2 = IM2 + 3, NPL = WIM2 + 3 };
     sfa_ctx *ctx = nullptr;
     int w = 0, h = 0, n = 0, pitch = 0;
     long pl = 0, es = 0;
     sfa_params_2frame p;
+    bool stored_stack = false;       // the data term reads a stored derivative stack (the host calls): 24 planes per pair, behind the n x NPL planes of `mem`
     sfa::DevMem mem;
-    sfa::DevMem stack;               // SFA_PAIR_UNFUSED=1 only: 24 planes per pair, allocated by the first such run
+    sfa::DevMem stack;               // SFA_PAIR_UNFUSED=1 on a job without a stored stack: 24 planes per pair, allocated by the first such run
     sfa::SorWorkspace ws;
     float *plane(int b, int i) const { return mem.f() + b * es + (long)i * pl; }
     sfa::Geo geo() const { return sfa::Geo{w, h, pitch, pl, es, n, sfa::WMask::first(n), nullptr}; }

@@ -155,28 +155,40 @@ def job_upload_device(job, frames, b0=0, chw=None, channels_last=None):
     job.ctx._ck(_lib().sfa_job_upload_device(job.h_, int(b0), n, C.c_void_p(v.ptr), C.byref(lay), cw), "sfa_job_upload_device")
 
 
-def job_set_flow_device(job, flow, b0=0, n=None):
+def _set_flow_device(job, fn, size, flow, b0, n):
+    """the start flow of a job or a pair job: `fn` the C function, `size` the attribute that holds the job's batch size"""
     if flow is None:
-        n = job.batch - b0 if n is None else n
-        job.ctx._ck(_lib().sfa_job_set_flow_device(job.h_, int(b0), int(n), None, None), "sfa_job_set_flow_device")
+        n = getattr(job, size) - b0 if n is None else n
+        job.ctx._ck(getattr(_lib(), fn)(job.h_, int(b0), int(n), None, None), fn)
         return
     v = device_view(flow, name="flow", ndim=4)
     if v.dtype != DTYPES["f4"] or v.shape[1:] != (2, job.h, job.w):
         raise sfa.SlowflowError(f"flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
-    job.ctx._ck(_lib().sfa_job_set_flow_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), "sfa_job_set_flow_device")
+    job.ctx._ck(getattr(_lib(), fn)(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), fn)
 
 
-def job_download_device(job, out_flow, out_occ=None, b0=0):
+def _download_device(job, fn, out_flow, b0, takes_occ=False, out_occ=None):
+    """the flow of a job or a pair job: `fn` the C function; takes_occ: it has the two arguments of an optional occlusion destination"""
     v = device_view(out_flow, writable=True, name="out_flow", ndim=4)
     if v.shape[1:] != (2, job.h, job.w):
         raise sfa.SlowflowError(f"out_flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
-    optr, ost = None, None
+    args = [job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)]
     if out_occ is not None:
         o = device_view(out_occ, writable=True, name="out_occ", ndim=3)
         if o.shape != (v.shape[0], job.h, job.w):
             raise sfa.SlowflowError(f"out_occ: fp32 [{v.shape[0]},{job.h},{job.w}] expected, got shape {o.shape}")
-        optr, ost = C.c_void_p(o.ptr), _LL3(*o.strides)
-    job.ctx._ck(_lib().sfa_job_download_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides), optr, ost), "sfa_job_download_device")
+        args += [C.c_void_p(o.ptr), _LL3(*o.strides)]
+    elif takes_occ:
+        args += [None, None]
+    job.ctx._ck(getattr(_lib(), fn)(*args), fn)
+
+
+def job_set_flow_device(job, flow, b0=0, n=None):
+    _set_flow_device(job, "sfa_job_set_flow_device", "batch", flow, b0, n)
+
+
+def job_download_device(job, out_flow, out_occ=None, b0=0):
+    _download_device(job, "sfa_job_download_device", out_flow, b0, True, out_occ)
 
 
 def job_changes(job, b0=0, n=None):
@@ -195,18 +207,28 @@ def sequence_upload_device(seq, frames, f0=0, channels_last=None):
     seq.ctx._ck(_lib().sfa_sequence_upload_device(seq.h_, int(f0), n, C.c_void_p(v.ptr), C.byref(lay)), "sfa_sequence_upload_device")
 
 
-def _job_for(ctx, params, w, h, nb):
-    """a job of this shape, kept on the context from call to call (two shapes at most: a batch beyond MAX_BATCH splits into at most two sizes)"""
-    cache = ctx.__dict__.setdefault("_refine_jobs", OrderedDict())
-    key = (bytes(params), w, h, nb)
+def pair_sizes(B):
+    """a batch of B windows or pairs as jobs of at most MAX_BATCH each, of equal or nearly equal size: the split of refine() and refine_pairs()"""
+    pieces = -(-B // MAX_BATCH)
+    return [B // pieces + (1 if i < B % pieces else 0) for i in range(pieces)]
+
+
+def _cached_job(ctx, cache_name, key, create):
+    """the job kept on the context under `key` from call to call, or create() in its place (two per cache at most: a batch beyond MAX_BATCH splits into at
+    most two sizes)"""
+    cache = ctx.__dict__.setdefault(cache_name, OrderedDict())
     job = cache.get(key)
     if job is not None and job.h_:
         cache.move_to_end(key)
         return job
     while len(cache) >= 2:
         cache.popitem(last=False)[1].close()
-    job = cache[key] = sfa.Job(ctx, params, w, h, nb)
+    job = cache[key] = create()
     return job
+
+
+def _job_for(ctx, params, w, h, nb):
+    return _cached_job(ctx, "_refine_jobs", (bytes(params), w, h, nb), lambda: sfa.Job(ctx, params, w, h, nb))
 
 
 def release_jobs(ctx):
@@ -245,8 +267,7 @@ def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, s
         occ = torch.empty((B, h, w), dtype=torch.float32, device=frames.device) if want_occ else None
     ov, cv = device_view(out, writable=True, name="out_flow"), (device_view(occ, writable=True, name="out_occ") if want_occ else None)
     change = np.zeros((B, 2), np.float32)
-    pieces = -(-B // MAX_BATCH)
-    sizes = [B // pieces + (1 if i < B % pieces else 0) for i in range(pieces)]
+    sizes = pair_sizes(B)
     wait_stream(ctx, stream)
     seq = None
     try:
@@ -293,27 +314,11 @@ def pair_job_upload_device(job, frames, b0=0, channels_last=None):
 
 
 def pair_job_set_flow_device(job, flow, b0=0, n=None):
-    if flow is None:
-        n = job.n - b0 if n is None else n
-        job.ctx._ck(_lib().sfa_pair_job_set_flow_device(job.h_, int(b0), int(n), None, None), "sfa_pair_job_set_flow_device")
-        return
-    v = device_view(flow, name="flow", ndim=4)
-    if v.dtype != DTYPES["f4"] or v.shape[1:] != (2, job.h, job.w):
-        raise sfa.SlowflowError(f"flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
-    job.ctx._ck(_lib().sfa_pair_job_set_flow_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), "sfa_pair_job_set_flow_device")
+    _set_flow_device(job, "sfa_pair_job_set_flow_device", "n", flow, b0, n)
 
 
 def pair_job_download_device(job, out_flow, b0=0):
-    v = device_view(out_flow, writable=True, name="out_flow", ndim=4)
-    if v.shape[1:] != (2, job.h, job.w):
-        raise sfa.SlowflowError(f"out_flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
-    job.ctx._ck(_lib().sfa_pair_job_download_device(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), "sfa_pair_job_download_device")
-
-
-def pair_sizes(B):
-    """a batch of B pairs as jobs of at most MAX_BATCH pairs, of equal or nearly equal size (the split refine() uses)"""
-    pieces = -(-B // MAX_BATCH)
-    return [B // pieces + (1 if i < B % pieces else 0) for i in range(pieces)]
+    _download_device(job, "sfa_pair_job_download_device", out_flow, b0)
 
 
 def pair_geometry(fv, channels_last=None):
@@ -329,17 +334,7 @@ def pair_geometry(fv, channels_last=None):
 
 
 def _pair_job_for(ctx, params, w, h, n):
-    """a pair job of this shape and these parameters, kept on the context from call to call (two at most, like refine()'s jobs)"""
-    cache = ctx.__dict__.setdefault("_refine_pair_jobs", OrderedDict())
-    key = (w, h, n, bytes(params) if params is not None else None)
-    job = cache.get(key)
-    if job is not None and job.h_:
-        cache.move_to_end(key)
-        return job
-    while len(cache) >= 2:
-        cache.popitem(last=False)[1].close()
-    job = cache[key] = sfa.PairJob(ctx, w, h, n, params)
-    return job
+    return _cached_job(ctx, "_refine_pair_jobs", (w, h, n, bytes(params) if params is not None else None), lambda: sfa.PairJob(ctx, w, h, n, params))
 
 
 def refine_pairs(ctx, frames, flow0=None, params=None, *, stream=None, channels_last=None):

@@ -194,6 +194,35 @@ def test_reuse_across_runs_and_uploads(ctx):
         job.close()
 
 
+def test_host_calls_between_the_runs_of_a_live_job(ctx):
+    """The host calls build and free a pair job of their own on the caller's context: a single call and a batch of other sizes between two runs of a live
+    job leave that job's planes, parameters and solver workspace alone.  The second run has nothing uploaded before it, so it refines the first run's
+    result further (run() updates the resident flow in place, as test_reuse_across_runs_and_uploads holds): its outcome is compared with the single call
+    on (frames, first result), not with the first result itself."""
+    w, h, B = 65, 17, 3
+    frames, flow = make_pairs(w, h, B, 12)
+    small, sflow = make_pairs(7, 5, 1, 13)
+    wide, wflow = make_pairs(131, 37, 2, 14)
+    job = sfa.PairJob(ctx, w, h, B)
+    try:
+        upload(job, frames, flow)
+        job.run()
+        first = download(job)
+        single(ctx, small[0], sflow[0])
+        st = sfa.stride_of(131)
+        fl, fr = padded(wflow, st), padded(wide, st)
+        ctx.variational_2frame_batch([fl[i, 0] for i in range(2)], [fl[i, 1] for i in range(2)], [fr[i, 0] for i in range(2)], [fr[i, 1] for i in range(2)], 131)
+        job.run()
+        second = download(job)
+        for b in range(B):
+            assert same(first[b], single(ctx, frames[b], flow[b])), b
+            assert same(second[b], single(ctx, frames[b], first[b])), b
+        for i in range(2):
+            assert same(fl[i, :, :, :131], single(ctx, wide[i], wflow[i])), i
+    finally:
+        job.close()
+
+
 # ---- 7. the device seam -------------------------------------------------------------------------------------------------------------------------
 torch = None
 
