@@ -376,6 +376,41 @@ int  sfa_sequence_upload_device(sfa_sequence *seq, int f0, int n, const void *fr
 int  sfa_pair_job_upload_device(sfa_pair_job *job, int b0, int n, const void *frames_dev, const sfa_dev_layout *layout);
 int  sfa_pair_job_set_flow_device(sfa_pair_job *job, int b0, int n, const float *flow_dev, const long long strides[4]);
 int  sfa_pair_job_download_device(sfa_pair_job *job, int b0, int n, float *flow_dev, const long long strides[4]);
+/* ---- raw Bayer ingest on the GPU (csrc/mosaic.hip) -----------------------------------------------------------------------------------------
+ * The driver's camera path (cfg raw 1): a frame arrives as a one-channel Bayer mosaic, is demosaiced (raw_demosaicing 0: bayer2rgbGR, utils/utils.cpp:
+ * 1242-1334; 2: cv::cvtColor(CV_Bayer*2RGB) on 8-bit data, slow_flow.cpp:502-520), cropped (center / extent) and rescaled (scale).  The calls below do
+ * that on mosaics in GPU memory, in the arithmetic of the host routines (slowflow_amd/host/ingest.cpp): the frames hold the same bits as frames demosaiced
+ * on the host and uploaded.  method = the cfg's raw_demosaicing (0 or 2; 1, Hamilton-Adams, is third-party code the reference does not ship: refused),
+ * (red_x, red_y) = raw_red_loc, each 0 or 1.
+ * A mosaic descriptor: element type, 64-bit ELEMENT strides of (frame, row, column), the size W x H of the full mosaic and the origin (x0, y0) of the crop
+ * to produce; the crop's size is the destination's w x h.  Without a crop x0 = y0 = 0 and W, H = w, h.  The colour of a site follows from its
+ * coordinates in the full mosaic, and so do the mirrored borders of method 0 and the repeated outer ring of method 2: a crop is the full result, sliced.
+ * Refused with SFA_ERR_ARG, by the argument's name and before anything is launched: method other than 0 or 2, red_x / red_y outside {0, 1}, W < 2 or H < 2
+ * with method 0 (the reference reads outside the image there), a crop that leaves the mosaic, every pointer or view the seam above refuses (the view of
+ * mosaic_dev is the whole W x H of its n frames), a destination that overlaps itself or the source. */
+typedef struct sfa_mosaic_desc { int dtype; long long frame, row, column; int W, H, x0, y0; } sfa_mosaic_desc;
+/* n mosaics -> fp32 RGB at dst_dev, dst_strides[4] = element strides of (frame, channel, row, column); one launch of k_demosaic_gr / k_demosaic_cv8u per
+ * 32768 frames; asynchronous on the context's stream, never waits. */
+int  sfa_demosaic_device(sfa_ctx *ctx, int n, const void *mosaic_dev, const sfa_mosaic_desc *desc, int method, int red_x, int red_y, float *dst_dev,
+                         const long long dst_strides[4], int w, int h);
+/* The same kernel with the sequence's frames [f0, f0 + n) as the destination (w, h = the sequence's size). */
+int  sfa_sequence_upload_mosaic_device(sfa_sequence *seq, int f0, int n, const void *mosaic_dev, const sfa_mosaic_desc *desc, int method, int red_x, int red_y);
+/* The host-pointer form (the driver's, cfg gpu_ingest 1): a W x H mosaic of `dtype` elements, `host_stride` elements per row, goes through a pinned
+ * staging copy to the GPU as it is (1, 2 or 4 bytes per pixel instead of 12) and through the same kernel into frame f.  Asynchronous on the context's
+ * stream: the caller's buffer is free on return, the call waits only for the copy of the previous call out of the staging buffer. */
+int  sfa_sequence_upload_mosaic(sfa_sequence *seq, int f, const void *mosaic_host, int dtype, long long host_stride, int W, int H, int x0, int y0, int method,
+                                int red_x, int red_y);
+/* rawWeighting (utils.cpp:1336-1374) of the windows [b0, b0 + n), formed on the GPU in the job's channel-weight planes (allocated at the first use, as by a
+ * chw argument): the bits of passing rawWeighting's planes as chw to sfa_job_upload* -- which this call FOLLOWS: an upload with chw == NULL sets the
+ * window's weights back to ones.  The planes take the stride of that upload (any stride >= w), as chw planes given to it would; a job that already holds
+ * weights of another stride refuses.  Asynchronous. */
+int  sfa_job_set_raw_weights(sfa_job *job, int b0, int n, int red_x, int red_y, float weight);
+/* The driver's input rescaling (slow_flow.cpp:550-553; host form: color_image_rescale of ingest.cpp) of resident frames: src_seq's frames [f_src, f_src + n),
+ * blurred with sigma = 1 / sqrt(2 scale) and resized by `scale`, become dst_seq's frames [f_dst, f_dst + n).  The kernels behind sfa_gaussian_blur and
+ * sfa_resize_linear_fx, device to device: bit-equal to those two calls per channel.  Both sequences on one context; dst_seq of lrint(w scale) x lrint(h scale)
+ * (SFA_ERR_ARG naming dst_seq otherwise); scale > 0 with a blur of at most 17 taps (scale >= 0.125).  Asynchronous. */
+int  sfa_sequence_rescale(sfa_sequence *dst_seq, int f_dst, sfa_sequence *src_seq, int f_src, int n, float scale);
+
 /* Ordering against a stream of the caller (a hipStream_t; NULL = the device's null stream, which is torch's default stream).  wait: the context's
  * stream waits for everything submitted to `stream` so far; signal: `stream` waits for everything submitted to the context's stream so far.  Both
  * record an event and return at once.  With wait before the first and signal after the last call that touches a buffer, work the caller submits to

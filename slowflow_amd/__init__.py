@@ -14,6 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFA_LIB") or os.path.join(_HERE, "libslowflow_amd.so")     # SFA_LIB: an experimental build of the same C-ABI (tuning only)
 MAX_REF = 8
+MOSAIC_TILE = (64, 16)                          # csrc/mosaic.hip: MOS_TX x MOS_TY, the demosaicing kernels' tile of the destination (columns, rows)
+MOSAIC_DTYPES = {"float32": 0, "uint8": 1, "uint16": 2}     # sfa_dev_dtype of a host mosaic
 
 _f = C.POINTER(C.c_float)
 
@@ -103,6 +105,7 @@ EXPORTS = [
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
     "sfa_job_create", "sfa_job_destroy", "sfa_job_upload", "sfa_job_upload_resident", "sfa_job_reset_flow", "sfa_job_run", "sfa_job_download", "sfa_job_download_occlusions", "sfa_job_keep_alternation_occlusions", "sfa_job_download_alternation_occlusions", "sfa_job_mpix_iters", "sfa_job_device_bytes",
     "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_pair_job_upload_device", "sfa_pair_job_set_flow_device", "sfa_pair_job_download_device", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
+    "sfa_demosaic_device", "sfa_sequence_upload_mosaic_device", "sfa_sequence_upload_mosaic", "sfa_job_set_raw_weights", "sfa_sequence_rescale",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
@@ -601,6 +604,14 @@ class Job:
         from . import device
         return device.job_changes(self, b0, n)
 
+    def set_raw_weights(self, red, weight, b0=0, n=None):
+        """rawWeighting (utils.cpp:1336-1374) for the windows b0 .. b0 + n - 1 (default: all from b0), formed on the GPU: the bits of passing its planes as
+        chw.  red = (red_x, red_y), the cfg's raw_red_loc.  Call it AFTER the window's upload: an upload without chw sets the weights back to ones."""
+        n = self.batch - b0 if n is None else n
+        L = lib()
+        L.sfa_job_set_raw_weights.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]
+        self.ctx._ck(L.sfa_job_set_raw_weights(self.h_, int(b0), int(n), int(red[0]), int(red[1]), float(weight)), "sfa_job_set_raw_weights")
+
     def run(self):
         self.ctx._ck(lib().sfa_job_run(self.h_), "sfa_job_run")
 
@@ -738,6 +749,30 @@ class Sequence:
         """frames [N,3,H,W] or [N,H,W,3] in device memory -> sequence frames f0 .. f0 + N - 1 (slowflow_amd/device.py); asynchronous"""
         from . import device
         device.sequence_upload_device(self, frames, f0, channels_last)
+
+    def upload_mosaic(self, f, mosaic, red=(1, 0), method=0, origin=(0, 0)):
+        """a HOST Bayer mosaic (numpy [H,W], float32 / uint8 / uint16, rows contiguous) -> sequence frame f, demosaiced on the GPU (method 0: bayer2rgbGR,
+        2: the 8-bit OpenCV conversion; red = raw_red_loc).  origin = (x0, y0) of the crop of the sequence's size inside the mosaic.  Asynchronous."""
+        m = np.asarray(mosaic)
+        if m.ndim != 2 or m.dtype.name not in MOSAIC_DTYPES or m.strides[1] != m.itemsize or m.strides[0] % m.itemsize or m.strides[0] < 0:
+            raise SlowflowError(f"mosaic: a [H,W] float32 / uint8 / uint16 array with contiguous rows expected, got {m.dtype} {m.shape} strides {m.strides}")
+        L = lib()
+        L.sfa_sequence_upload_mosaic.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong] + [C.c_int] * 7
+        self.ctx._ck(L.sfa_sequence_upload_mosaic(self.h_, int(f), C.c_void_p(m.ctypes.data), MOSAIC_DTYPES[m.dtype.name], m.strides[0] // m.itemsize, m.shape[1],
+                                                  m.shape[0], int(origin[0]), int(origin[1]), int(method), int(red[0]), int(red[1])), "sfa_sequence_upload_mosaic")
+
+    def upload_mosaic_device(self, mosaic, red=(1, 0), method=0, f0=0, origin=(0, 0), size=None):
+        """mosaics [N,H,W] in device memory (any object with __cuda_array_interface__) -> sequence frames f0 .. f0 + N - 1 (slowflow_amd/device.py); asynchronous"""
+        from . import device
+        device.sequence_upload_mosaic_device(self, mosaic, red, method, f0, origin, size)
+
+    def rescale_from(self, src, scale, f_dst=0, f_src=0, n=None):
+        """the driver's input rescaling of resident frames (sfa_sequence_rescale): src's frames f_src .. blurred (sigma = 1 / sqrt(2 scale)) and resized by
+        `scale` into this sequence's frames f_dst ..; this sequence is lrint(w scale) x lrint(h scale).  Asynchronous; both sequences on one context."""
+        n = src.n - f_src if n is None else n
+        L = lib()
+        L.sfa_sequence_rescale.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float]
+        self.ctx._ck(L.sfa_sequence_rescale(self.h_, int(f_dst), src.h_, int(f_src), int(n), float(scale)), "sfa_sequence_rescale")
 
     def download(self, f):
         a = np.zeros((3, self.h, stride_of(self.w)), np.float32)

@@ -1013,6 +1013,13 @@ struct sfa_sequence {
     long pl = 0;
     DevMem mem;                        // n x 3 planes at the device pitch
     DevMem sums;                       // n x 6 doubles: per frame and channel sum(I), sum(I*I)
+    // sfa_sequence_upload_mosaic: the caller's mosaic goes through a pinned copy into mos_dev, the demosaicing kernel's source; ev_mos says the copy out of
+    // the pinned buffer has been made (the device buffer is reused in stream order)
+    void *mos_stage = nullptr;
+    size_t mos_stage_bytes = 0;
+    hipEvent_t ev_mos = nullptr;
+    DevMem mos_dev;
+    DevMem rescale_tmp;                // sfa_sequence_rescale into this sequence: the blurred frames of a chunk and the row pass's scratch
     float *frame(int f) const { return mem.f() + (long)f * 3 * pl; }
     Geo geo() const { return Geo{w, h, pitch, pl, 0, 1, WMask::first(1), nullptr}; }
 };
@@ -1032,6 +1039,8 @@ void sfa_sequence_destroy(sfa_sequence *q) {
     if (!q) return;
     (void)hipSetDevice(q->ctx->device);
     (void)hipStreamSynchronize(q->ctx->stream);
+    if (q->ev_mos) (void)hipEventDestroy(q->ev_mos);
+    if (q->mos_stage) (void)hipHostFree(q->mos_stage);
     delete q;
 }
 int sfa_sequence_upload(sfa_sequence *q, int f, const float *frame3, int stride) {
@@ -1544,6 +1553,179 @@ int sfa_sequence_upload_device(sfa_sequence *q, int f0, int n, const void *frame
     for (int i = 0; i < n; i += chunk) {
         const PackSrc src{static_cast<const char *>(frames_dev) + (size_t)i * l->frame * elem, l->dtype, l->frame, 0, l->channel, l->row, l->column};
         launch_pack_frames(ctx, q->frame(f0 + i), 3 * q->pl, q->pl, q->pitch, q->w, q->h, std::min(chunk, n - i), 1, src);
+    }
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+// ---- raw Bayer ingest (include/slowflow_amd.h; kernels: mosaic.hip) ------------------------------------------------------------------------
+}  // extern "C"
+
+namespace sfa {
+
+static int check_mosaic_method(sfa_ctx *ctx, const char *fn, int method, int red_x, int red_y) {
+    if (method != 0 && method != 2)
+        REFUSE("%s: method %d: 0 (bayer2rgbGR) and 2 (the 8-bit OpenCV conversion) exist; 1, Hamilton-Adams, is third-party code the reference does not ship", fn, method);
+    if (red_x != 0 && red_x != 1) REFUSE("%s: red_x = %d: the red site's column parity is 0 or 1", fn, red_x);
+    if (red_y != 0 && red_y != 1) REFUSE("%s: red_y = %d: the red site's row parity is 0 or 1", fn, red_y);
+    return SFA_OK;
+}
+// the descriptor against the crop's size w x h; the pointer itself is check_mosaic_pointer's
+static int check_mosaic_geometry(sfa_ctx *ctx, const char *fn, int dtype, int W, int H, int x0, int y0, int w, int h, int method) {
+    if (dtype != SFA_DEV_F32 && dtype != SFA_DEV_U8 && dtype != SFA_DEV_U16) REFUSE("%s: desc.dtype %d is no element type (fp32 0, u8 1, u16 2)", fn, dtype);
+    if (w < 1 || h < 1) REFUSE("%s: w = %d, h = %d: the destination is empty", fn, w, h);
+    if (W < 1 || H < 1) REFUSE("%s: desc.W = %d, desc.H = %d: the mosaic is empty", fn, W, H);
+    if (method == 0 && (W < 2 || H < 2)) REFUSE("%s: desc.W = %d, desc.H = %d with method 0: the mirrored neighbours need W >= 2 and H >= 2 (the reference reads outside the image)", fn, W, H);
+    if (x0 < 0 || y0 < 0 || (long)x0 + w > W || (long)y0 + h > H)
+        REFUSE("%s: the crop desc.x0 = %d, desc.y0 = %d of %d x %d leaves the mosaic of desc.W = %d, desc.H = %d", fn, x0, y0, w, h, W, H);
+    return SFA_OK;
+}
+// the view of mosaic_dev: all W x H elements of its n frames (the kernels read up to two pixels beyond the crop)
+static int check_mosaic_pointer(sfa_ctx *ctx, const char *fn, const void *mosaic_dev, const sfa_mosaic_desc *d, int n, long long *last_out) {
+    if (d->column < 1) REFUSE("%s: desc.column = %lld: the column stride must be >= 1", fn, d->column);
+    if (d->frame < 0 || d->row < 0) REFUSE("%s: desc holds a negative stride (frame %lld, row %lld)", fn, d->frame, d->row);
+    if (!mosaic_dev) REFUSE("%s: mosaic_dev is null", fn);
+    long long last = 0;
+    if (!extent_add(&last, n - 1, d->frame) || !extent_add(&last, d->H - 1, d->row) || !extent_add(&last, d->W - 1, d->column))
+        REFUSE("%s: the strides of desc reach beyond the 64-bit range: the view of mosaic_dev cannot lie inside an allocation", fn);
+    *last_out = last;
+    return check_device_pointer(ctx, fn, "mosaic_dev", mosaic_dev, last, dev_elem_size(d->dtype));
+}
+
+}  // namespace sfa
+
+extern "C" {
+
+int sfa_demosaic_device(sfa_ctx *ctx, int n, const void *mosaic_dev, const sfa_mosaic_desc *d, int method, int red_x, int red_y, float *dst_dev,
+                        const long long st[4], int w, int h) {
+    CHECK_ARGS(ctx, "ctx is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    if (n < 1) REFUSE("%s: n = %d frames", __func__, n);
+    if (!d) REFUSE("%s: desc is null", __func__);
+    SFA_TRY(check_mosaic_method(ctx, __func__, method, red_x, red_y));
+    SFA_TRY(check_mosaic_geometry(ctx, __func__, d->dtype, d->W, d->H, d->x0, d->y0, w, h, method));
+    long long slast = 0;
+    SFA_TRY(check_mosaic_pointer(ctx, __func__, mosaic_dev, d, n, &slast));
+    if (!dst_dev) REFUSE("%s: dst_dev is null", __func__);
+    const int sizes[4] = {n, 3, h, w};
+    SFA_TRY(check_field(ctx, __func__, "dst_dev", dst_dev, st, sizes, 4));
+    if (!strides_nest(st, sizes, 4)) REFUSE("%s: dst_strides let frames, channels or rows of dst_dev share memory (or interleave them in a way the check cannot clear)", __func__);
+    const long long dlast = (n - 1) * st[0] + 2 * st[1] + (h - 1) * st[2] + (w - 1) * st[3];
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(mosaic_dev), s1 = s0 + (uintptr_t)slast * dev_elem_size(d->dtype) + dev_elem_size(d->dtype) - 1;
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_dev), d1 = d0 + (uintptr_t)dlast * 4 + 3;
+    if (!(s1 < d0 || d1 < s0)) REFUSE("%s: dst_dev overlaps mosaic_dev: the kernel reads a pixel's neighbours after other blocks have written theirs", __func__);
+    const MosaicSrc src{mosaic_dev, d->dtype, d->frame, d->row, d->column, d->W, d->H, d->x0, d->y0};
+    const MosaicDst dst{dst_dev, st[0], st[1], st[2], st[3], w, h};
+    launch_demosaic(ctx, src, dst, n, method, red_x, red_y);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_sequence_upload_mosaic_device(sfa_sequence *q, int f0, int n, const void *mosaic_dev, const sfa_mosaic_desc *d, int method, int red_x, int red_y) {
+    sfa_ctx *ctx = q ? q->ctx : nullptr;
+    CHECK_ARGS(q, "seq is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    if (f0 < 0 || n < 1 || (long)f0 + n > q->n) REFUSE("%s: frames f0 = %d, n = %d lie outside the sequence of %d", __func__, f0, n, q->n);
+    if (!d) REFUSE("%s: desc is null", __func__);
+    SFA_TRY(check_mosaic_method(ctx, __func__, method, red_x, red_y));
+    SFA_TRY(check_mosaic_geometry(ctx, __func__, d->dtype, d->W, d->H, d->x0, d->y0, q->w, q->h, method));
+    long long slast = 0;
+    SFA_TRY(check_mosaic_pointer(ctx, __func__, mosaic_dev, d, n, &slast));
+    const MosaicSrc src{mosaic_dev, d->dtype, d->frame, d->row, d->column, d->W, d->H, d->x0, d->y0};
+    const MosaicDst dst{q->frame(f0), 3 * (long long)q->pl, q->pl, q->pitch, 1, q->w, q->h};
+    launch_demosaic(ctx, src, dst, n, method, red_x, red_y);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_sequence_upload_mosaic(sfa_sequence *q, int f, const void *mosaic_host, int dtype, long long host_stride, int W, int H, int x0, int y0, int method,
+                               int red_x, int red_y) {
+    sfa_ctx *ctx = q ? q->ctx : nullptr;
+    CHECK_ARGS(q, "seq is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    if (f < 0 || f >= q->n) REFUSE("%s: frame f = %d lies outside the sequence of %d", __func__, f, q->n);
+    if (!mosaic_host) REFUSE("%s: mosaic_host is null", __func__);
+    SFA_TRY(check_mosaic_method(ctx, __func__, method, red_x, red_y));
+    SFA_TRY(check_mosaic_geometry(ctx, __func__, dtype, W, H, x0, y0, q->w, q->h, method));
+    if (host_stride < W) REFUSE("%s: host_stride = %lld is below W = %d", __func__, host_stride, W);
+    const size_t elem = dev_elem_size(dtype), row = (size_t)W * elem, bytes = row * H;
+    if (bytes > q->mos_stage_bytes) {                        // (a larger mosaic than before: the stream may still read the old buffers)
+        SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        q->mos_stage_bytes = 0;                              // (stays 0 until all three exist: a failure here sends the next call through this branch again)
+        if (q->mos_stage) { (void)hipHostFree(q->mos_stage); q->mos_stage = nullptr; }
+        SFA_HIP(ctx, hipHostMalloc(&q->mos_stage, bytes, hipHostMallocDefault));
+        SFA_TRY(q->mos_dev.alloc(ctx, bytes));
+        if (!q->ev_mos) SFA_HIP(ctx, hipEventCreateWithFlags(&q->ev_mos, hipEventDisableTiming));
+        q->mos_stage_bytes = bytes;
+    } else {
+        SFA_HIP(ctx, hipEventSynchronize(q->ev_mos));        // the previous call's copy out of the pinned buffer (not the stream's other work)
+    }
+    for (int y = 0; y < H; y++) memcpy(static_cast<char *>(q->mos_stage) + y * row, static_cast<const char *>(mosaic_host) + (size_t)y * host_stride * elem, row);
+    SFA_HIP(ctx, hipMemcpyAsync(q->mos_dev.p, q->mos_stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+    SFA_HIP(ctx, hipEventRecord(q->ev_mos, ctx->stream));
+    const MosaicSrc src{q->mos_dev.p, dtype, (long long)W * H, W, 1, W, H, x0, y0};
+    const MosaicDst dst{q->frame(f), 3 * (long long)q->pl, q->pl, q->pitch, 1, q->w, q->h};
+    launch_demosaic(ctx, src, dst, 1, method, red_x, red_y);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_job_set_raw_weights(sfa_job *j, int b0, int n, int red_x, int red_y, float weight) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(job_windows(ctx, __func__, j, b0, n));
+    SFA_TRY(check_mosaic_method(ctx, __func__, 0, red_x, red_y));
+    if (!(weight == weight)) REFUSE("%s: weight is NaN", __func__);
+    // the planes keep the level-0 host geometry of the job's uploads (the stride the last sfa_job_upload* gave; host_stride(w) before any), as chw planes
+    // passed to that upload would: the data term indexes them by y * host_stride0 + x
+    const int stride = j->host_stride0, cp = dev_pitch(stride);
+    CHECK_ARGS((long)stride * j->h < (1L << 31), "channel weights: the linear pixel index must fit 31 bits");
+    if (!j->has_chw) {                                       // as job_set_channel_weights: every window's weights are ones until set
+        SFA_TRY(j->chw.alloc(ctx, (size_t)j->nb * 3 * cp * j->h * sizeof(float)));
+        launch_fill(ctx, j->chw.f(), (size_t)j->nb * 3 * cp * j->h, 1.0f);
+        j->has_chw = true;
+        j->chw_stride0 = stride;
+    }
+    if (j->chw_stride0 != stride)
+        REFUSE("%s: the job holds channel weights of stride %d and its frames were uploaded with stride %d: one job keeps one stride", __func__, j->chw_stride0, stride);
+    const long pl = (long)cp * j->h;
+    launch_raw_weights(ctx, j->chw.f() + (long)b0 * 3 * pl, 3 * pl, pl, cp, stride, j->w, j->h, n, red_x, red_y, weight);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_sequence_rescale(sfa_sequence *dq, int f_dst, sfa_sequence *sq, int f_src, int n, float scale) {
+    sfa_ctx *ctx = dq ? dq->ctx : (sq ? sq->ctx : nullptr);
+    CHECK_ARGS(dq, "dst_seq is null");
+    CHECK_ARGS(sq, "src_seq is null");
+    if (sq->ctx != ctx) REFUSE("%s: src_seq lives on another context than dst_seq: one stream orders the blur before the resize", __func__);
+    if (sq == dq) REFUSE("%s: src_seq is dst_seq", __func__);
+    if (!(scale > 0)) REFUSE("%s: scale = %g must be positive", __func__, (double)scale);
+    if (n < 1 || f_src < 0 || (long)f_src + n > sq->n) REFUSE("%s: frames f_src = %d, n = %d lie outside src_seq of %d", __func__, f_src, n, sq->n);
+    if (f_dst < 0 || (long)f_dst + n > dq->n) REFUSE("%s: frames f_dst = %d, n = %d lie outside dst_seq of %d", __func__, f_dst, n, dq->n);
+    const int w = sq->w, h = sq->h;
+    const int dw = (int)lrint((double)w * scale), dh = (int)lrint((double)h * scale);   // saturate_cast<int>(src.cols * fx) (ingest.cpp: color_image_rescale)
+    if (dq->w != dw || dq->h != dh)
+        REFUSE("%s: dst_seq is %d x %d; src_seq's %d x %d frames at scale %g give lrint(w scale) x lrint(h scale) = %d x %d", __func__, dq->w, dq->h, w, h, (double)scale, dw, dh);
+    const float sigma = (float)(1 / sqrt(2 * scale));                                   // slow_flow.cpp:551
+    float taps[64];
+    if (!(sigma * 8 + 1 < 33)) REFUSE("%s: scale = %g: sigma too large", __func__, (double)scale);
+    const int r = cv_gauss_taps(sigma, taps);
+    if (r > 8) REFUSE("%s: scale = %g needs a blur of %d taps; the blur kernel holds 17 (scale >= 0.125)", __func__, (double)scale, 2 * r + 1);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const int chunk = std::min(n, 8);                       // frames blurred per launch pair: bounds the scratch to 2 x 8 frames
+    const size_t frame_floats = (size_t)3 * sq->pl;
+    if ((size_t)2 * chunk * frame_floats * sizeof(float) > dq->rescale_tmp.bytes) {
+        SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        SFA_TRY(dq->rescale_tmp.alloc(ctx, (size_t)2 * chunk * frame_floats * sizeof(float)));
+    }
+    float *blur = dq->rescale_tmp.f(), *tmp = blur + (size_t)chunk * frame_floats;
+    for (int i = 0; i < n; i += chunk) {
+        const int m = std::min(chunk, n - i);
+        launch_gauss_blur(ctx, sq->geo(), blur, tmp, sq->frame(f_src + i), 3 * m, taps, r);
+        launch_resize_scaled(ctx, dq->frame(f_dst + i), dw, dh, dq->pitch, dq->pl, 0, blur, w, h, sq->pitch, sq->pl, 0, 3 * m, 1, 1.0f, 1.0 / (double)scale,
+                             1.0 / (double)scale);
     }
     SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;

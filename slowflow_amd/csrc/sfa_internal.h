@@ -320,6 +320,16 @@ void launch_pack_flow(sfa_ctx *c, float *dst, long dst_es, long pl, int pitch, i
 void launch_unpack_planes(sfa_ctx *c, const float *wx, const float *wy, const float *occ, long src_es, int pitch, int w, int h, int nwin, float *flow,
                           const long long st[4], float *occ_dst, const long long ost[3]);
 
+// ---- mosaic.hip: raw Bayer ingest (sfa_demosaic_device, sfa_sequence_upload_mosaic*, sfa_job_set_raw_weights) -----------------------------
+// n one-channel mosaics of W x H elements of dtype in device memory, element (frame, row, column) at p + the strides; the crop starts at (x0, y0)
+struct MosaicSrc { const void *p; int dtype; long long sf, sr, sx; int W, H, x0, y0; };
+// n fp32 RGB frames of w x h (the crop's size), element (frame, channel, row, column) at p + the strides
+struct MosaicDst { float *p; long long sf, sc, sr, sx; int w, h; };
+// method 0: bayer2rgbGR, 2: the 8-bit OpenCV conversion; one launch per 32768 frames
+void launch_demosaic(sfa_ctx *c, const MosaicSrc &src, const MosaicDst &dst, int n, int method, int red_x, int red_y);
+// rawWeighting into the weight planes of nwin windows: chw = plane 0 of the first, planes pl apart, windows es apart, rows of `stride` floats at pitch cp
+void launch_raw_weights(sfa_ctx *c, float *chw, long es, long pl, int cp, int stride, int w, int h, int nwin, int red_x, int red_y, float weight);
+
 // ---------------------------------------------------------------------------------------------------
 // SOR (sor.hip)
 // ---------------------------------------------------------------------------------------------------

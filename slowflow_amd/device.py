@@ -94,6 +94,12 @@ def frames_layout(v, w, h, F, channels_last=None, name="frames"):
     return v.shape[0], lay
 
 
+class MosaicDesc(C.Structure):
+    """sfa_mosaic_desc: element type, element strides of (frame, row, column), the full mosaic's size and the crop's origin"""
+    _fields_ = [("dtype", C.c_int), ("frame", C.c_longlong), ("row", C.c_longlong), ("column", C.c_longlong), ("W", C.c_int), ("H", C.c_int), ("x0", C.c_int),
+                ("y0", C.c_int)]
+
+
 _LL4, _LL3 = C.c_longlong * 4, C.c_longlong * 3
 _bound = False
 
@@ -114,6 +120,8 @@ def _lib():
         L.sfa_ctx_signal_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.sfa_dev_layout_default.argtypes = [C.POINTER(DevLayout), C.c_int, C.c_int, C.c_int]
         L.sfa_dev_layout_default.restype = None
+        L.sfa_demosaic_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MosaicDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.sfa_sequence_upload_mosaic_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(MosaicDesc), C.c_int, C.c_int, C.c_int]
         _bound = True
     return L
 
@@ -207,6 +215,47 @@ def sequence_upload_device(seq, frames, f0=0, channels_last=None):
     seq.ctx._ck(_lib().sfa_sequence_upload_device(seq.h_, int(f0), n, C.c_void_p(v.ptr), C.byref(lay)), "sfa_sequence_upload_device")
 
 
+def mosaic_desc(v, origin=(0, 0), size=None):
+    """a DeviceView of mosaics [N,H,W] -> (N, MosaicDesc, (w, h)): the crop of `size` = (w, h) at `origin` = (x0, y0); size None: the rest of the mosaic"""
+    N, H, W = v.shape
+    x0, y0 = int(origin[0]), int(origin[1])
+    w, h = (W - x0, H - y0) if size is None else (int(size[0]), int(size[1]))
+    return N, MosaicDesc(v.dtype, v.strides[0], v.strides[1], v.strides[2], W, H, x0, y0), (w, h)
+
+
+def sequence_upload_mosaic_device(seq, mosaic, red=(1, 0), method=0, f0=0, origin=(0, 0), size=None):
+    v = device_view(mosaic, name="mosaic", ndim=3)
+    n, desc, (w, h) = mosaic_desc(v, origin, size if size is not None else (seq.w, seq.h))
+    if (w, h) != (seq.w, seq.h):
+        raise sfa.SlowflowError(f"size: the crop is {w} x {h}, the sequence {seq.w} x {seq.h}")
+    seq.ctx._ck(_lib().sfa_sequence_upload_mosaic_device(seq.h_, int(f0), n, C.c_void_p(v.ptr), C.byref(desc), int(method), int(red[0]), int(red[1])),
+                "sfa_sequence_upload_mosaic_device")
+
+
+def demosaic(ctx, mosaic, red=(1, 0), method=0, origin=(0, 0), size=None, *, stream=None):
+    """Demosaic N Bayer mosaics that live on the context's GPU: mosaic = a torch tensor [N,H,W] (fp32, uint8 or uint16; any strides with a positive column
+    stride); red = (red_x, red_y), the cfg's raw_red_loc; method 0 (bayer2rgbGR) or 2 (the 8-bit OpenCV conversion); origin / size = the crop (x0, y0) /
+    (w, h) inside the mosaic (default: all of it).  Returns a new fp32 tensor [N,3,h,w] with the bits of the host routines.  Ordered after what `stream`
+    (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues."""
+    import torch
+    v = device_view(mosaic, name="mosaic", ndim=3)
+    n, desc, (w, h) = mosaic_desc(v, origin, size)
+    if w < 1 or h < 1:
+        raise sfa.SlowflowError(f"size: the crop {w} x {h} at origin {tuple(origin)} of the {v.shape[2]} x {v.shape[1]} mosaic is empty")
+    if stream is None:
+        stream = torch.cuda.current_stream(mosaic.device)
+    with torch.cuda.stream(stream):                              # the output belongs to the caller's stream
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=mosaic.device)
+    ov = device_view(out, writable=True, name="out")
+    wait_stream(ctx, stream)
+    try:
+        ctx._ck(_lib().sfa_demosaic_device(ctx.h, n, C.c_void_p(v.ptr), C.byref(desc), int(method), int(red[0]), int(red[1]), C.c_void_p(ov.ptr), _LL4(*ov.strides),
+                                           w, h), "sfa_demosaic_device")
+    finally:
+        signal_stream(ctx, stream)
+    return out
+
+
 def pair_sizes(B):
     """a batch of B windows or pairs as jobs of at most MAX_BATCH each, of equal or nearly equal size: the split of refine() and refine_pairs()"""
     pieces = -(-B // MAX_BATCH)
@@ -239,7 +288,7 @@ def release_jobs(ctx):
         job.close()
 
 
-def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, stream=None, channels_last=None):
+def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, stream=None, channels_last=None, raw_weights=None):
     """Refine the flow of B frame windows that live on the context's GPU: frames = a torch tensor [B,F,3,H,W] or [B,F,H,W,3] (fp32, uint8 or uint16;
     any strides with a positive column stride), F = 2 (S - 1) + 1; flow = None (zeros) or an fp32 tensor [B,2,H,W].  Returns (flow [B,2,H,W], occlusions
     [B,H,W] or None, change norms as a numpy array [B,2]), the tensors on the frames' device.  The work is ordered after what `stream` (default:
@@ -248,7 +297,8 @@ def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, s
     normalize=True: the frames go through a Sequence first -- normalize() over the B x F frames as passed, the bits of Sequence.normalize -- and the
     statistics replace params.norm_avg / norm_std (of a copy), as the driver does.  Without it the frames are taken as they are.
     The jobs stay on the context for the next call of the same shape and parameters (release_jobs(ctx) or ctx.close() frees them); with normalize=True
-    the statistics are part of the parameters, so that mode creates its jobs per call and closes them before it returns."""
+    the statistics are part of the parameters, so that mode creates its jobs per call and closes them before it returns.
+    raw_weights = (red_x, red_y, weight): every window runs with rawWeighting's channel weights (the cfg's raw_red_loc and raw_weight), formed on the GPU."""
     import torch
     F = 2 * (params.S - 1) + 1
     fv = device_view(frames, name="frames", ndim=5)
@@ -292,6 +342,8 @@ def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, s
             else:
                 job_upload_device(job, fv.sub(b0, n), channels_last=channels_last)
             job_set_flow_device(job, flv.sub(b0, n) if flv is not None else None, 0, n)
+            if raw_weights is not None:                          # after the uploads: they set the windows' weights to ones
+                job.set_raw_weights((raw_weights[0], raw_weights[1]), raw_weights[2], 0, n)
             job.run()
             job_download_device(job, ov.sub(b0, n), cv.sub(b0, n) if want_occ else None)
             change[b0:b0 + n] = job_changes(job, 0, n)

@@ -112,6 +112,33 @@ color_image_t *load_frame(const std::string &file, bool raw, int demosaicing, in
     return rgb;
 }
 
+bool load_mosaic(const std::string &file, Mosaic *out, std::string *error) {
+    int maxval = 255;
+    color_image_t *img = color_image_load(file.c_str(), &maxval);
+    if (!img) { *error = "cannot read frame " + file + " (PNG, TIFF or binary PPM/PGM/PFM expected)"; return false; }
+    const int W = img->width, H = img->height;
+    out->width = W; out->height = H; out->maxval = maxval;
+    // the narrowest element type that holds every sample exactly
+    bool integral = maxval == 255 || maxval == 65535;
+    for (int y = 0; y < H && integral; y++)
+        for (int x = 0; x < W; x++) {
+            const float v = img->c1[(size_t)y * img->stride + x];
+            if (!(v >= 0 && v <= (float)maxval && v == (float)(int)v)) { integral = false; break; }
+        }
+    out->dtype = !integral ? SFA_DEV_F32 : maxval == 255 ? SFA_DEV_U8 : SFA_DEV_U16;
+    const size_t elem = out->dtype == SFA_DEV_F32 ? 4 : out->dtype == SFA_DEV_U16 ? 2 : 1;
+    out->data.resize((size_t)W * H * elem);
+    for (int y = 0; y < H; y++) {
+        const float *row = img->c1 + (size_t)y * img->stride;
+        unsigned char *dst = out->data.data() + (size_t)y * W * elem;
+        if (out->dtype == SFA_DEV_F32) memcpy(dst, row, (size_t)W * 4);
+        else if (out->dtype == SFA_DEV_U16) for (int x = 0; x < W; x++) reinterpret_cast<unsigned short *>(dst)[x] = (unsigned short)row[x];
+        else for (int x = 0; x < W; x++) dst[x] = (unsigned char)row[x];
+    }
+    color_image_delete(img);
+    return true;
+}
+
 color_image_t *color_image_crop(const color_image_t *img, int cx, int cy, int ex, int ey) {
     const int x0 = cx - ex / 2, x1 = cx + ex / 2, y0 = cy - ey / 2, y1 = cy + ey / 2;    // Range(center - extent/2, center + extent/2)
     if (x0 < 0 || y0 < 0 || x1 > img->width || y1 > img->height || x1 <= x0 || y1 <= y0) return nullptr;

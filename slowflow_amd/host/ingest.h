@@ -5,6 +5,7 @@
 #define SLOWFLOW_AMD_HOST_INGEST_H
 
 #include <string>
+#include <vector>
 
 #include "../../include/slowflow_amd.h"
 #include "image.h"
@@ -24,6 +25,13 @@ void bayer2rgb_cv8u(const image_t *src, color_image_t *dst, int red_x, int red_y
  * (red_x, red_y): demosaicing 2 is bayer2rgb_cv8u, any other value bayer2rgbGR.  NULL on failure, with the message in *error.  No shared
  * state and no printing of its own: the driver's decoding tasks call it in parallel */
 color_image_t *load_frame(const std::string &file, bool raw, int demosaicing, int red_x, int red_y, int *maxval, std::string *error);
+/* gpu_ingest 1: a frame file decoded to its one-channel mosaic only (the first plane color_image_load returns, what load_frame demosaics), rows packed.
+ * Samples of an integer format travel as uint8 / uint16 (sfa_dev_dtype; (float) of them is the plane's value exactly), anything else as fp32 */
+struct Mosaic {
+    int width = 0, height = 0, dtype = SFA_DEV_F32, maxval = 255;
+    std::vector<unsigned char> data;
+};
+bool load_mosaic(const std::string &file, Mosaic *out, std::string *error);
 /* img.rowRange / colRange of slow_flow.cpp:543-546; returns a new image (caller frees) */
 color_image_t *color_image_crop(const color_image_t *img, int center_x, int center_y, int extent_x, int extent_y);
 /* slow_flow.cpp:550-553: GaussianBlur(sigma = 1/sqrt(2*scale), BORDER_REPLICATE) then resize(Size(0,0), scale, scale,

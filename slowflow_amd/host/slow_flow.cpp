@@ -11,7 +11,8 @@
 // (DeepMatching, the MATLAB SED detector) and the third-party Hamilton-Adams demosaicer (raw_demosaicing 1) are outside this build and reported as such.
 //
 // New, additive keys: gpus (default: all visible; gpu_oversubscribe 1 lets it exceed them: a rehearsal of the multi-GPU path), gpu_batch (windows refined in lockstep per job, default 32), gpu_streams
-// (default 2), gpu_device (first device, default 0), io_threads (decode / output pool, default min(16, cores)),
+// (default 2), gpu_device (first device, default 0), io_threads (decode / output pool, default min(16, cores)), gpu_ingest (default 0; 1 with raw 1: the
+// mosaics go to the GPU as they are and are demosaiced, cropped and rescaled there, sfa_sequence_upload_mosaic / sfa_sequence_rescale; same output files),
 // adaptive_fr_file (default: adaptiveFR.dat next to the executable, the reference's SOURCE_PATH).
 #include <unistd.h>
 
@@ -128,6 +129,8 @@ struct Run {
     const float raw_weight = p.parameter<float>("raw_weight", "1.0"), scale = p.parameter<float>("scale", "1.0");
     const bool preprocess = !p.exists("raw") || raw_weight == 1.0f;                 // :531
     const bool rescale = preprocess && scale != 1;
+    const bool crop = preprocess && (p.extent.x > 0 || p.extent.y > 0);             // :533-536
+    const bool gpu_ingest = p.parameter<bool>("gpu_ingest", "0");                   // additive: raw frames are demosaiced, cropped and rescaled on the GPU
     const int steps = p.parameter<int>("slow_flow_S") - 1, skip;                    // :208-209 (ref = steps)
     const bool sintel = p.parameter<bool>("sintel", "0");
     const unsigned start = p.sequence_start;
@@ -211,10 +214,11 @@ public:
     struct Gpu { Ctx ctx; DeviceSequence resident; string err; bool ready = false; double upload_bytes = 0, upload_done_s = 0, ready_s = 0, first_refine_s = -1; };   // (resident goes before ctx; s since the run began)
     std::vector<ColorImage> frames;              // by frame of the pass (only [start_f, end_f) is loaded); width x height: published with the first frame
     std::vector<int> maxval;                     // 255 / 65535 per frame: the 8-bit copy EpicFlow's saliency works on divides 16-bit samples by 255 (:472-474, :578)
-    int width = 0, height = 0;
+    std::vector<Mosaic> mosaics;                 // gpu_ingest 1: the decoded mosaics instead of `frames`; the GPUs demosaic, crop and rescale them
+    int width = 0, height = 0, stride = 0;       // the frames the solver sees (after crop and rescale), and the row stride of their host images
     const std::vector<FrameRange> &gpu_frames;
     Sequence(const Run &run, const std::vector<FrameRange> &gpu_frames_, double t_begin)
-        : frames(run.layout.frames), maxval(run.layout.frames, 255), gpu_frames(gpu_frames_), run_(run), t_begin_(t_begin), n_loaded_((int)(run.layout.end_f - run.layout.start_f)),
+        : frames(run.layout.frames), maxval(run.layout.frames, 255), mosaics(run.gpu_ingest ? run.layout.frames : 0), gpu_frames(gpu_frames_), run_(run), t_begin_(t_begin), n_loaded_((int)(run.layout.end_f - run.layout.start_f)),
           frame_ready_(run.layout.frames, 0), have_sums_(n_loaded_, 0), frame_sums_((size_t)6 * n_loaded_, 0.0), gpus_(run.ngpu) {
         for (int g = 0; g < run.ngpu; g++) up_.emplace_back(&Sequence::upload, this, g);
     }
@@ -227,7 +231,7 @@ public:
             std::lock_guard<std::mutex> l(mu_);
             for (unsigned f = f0; f < f1; f++) {
                 const color_image_t *im = frames[f].get();
-                if (!size_known_) { width = im->width; height = im->height; size_known_ = true; }
+                if (!size_known_) { width = im->width; height = im->height; stride = im->stride; size_known_ = true; }
                 if (im->width != width || im->height != height) {
                     if (size_mismatch_.empty())
                         size_mismatch_ = "frames of different sizes: frame " + std::to_string(f) + " of the sequence is " + std::to_string(im->width) + "x" + std::to_string(im->height) +
@@ -236,6 +240,33 @@ public:
                 }
                 frame_ready_[f] = 1;
             }
+        }
+        cv_.notify_all();
+    }
+    // gpu_ingest 1: mosaic f is final.  The first one fixes the geometry of the pass: the crop (color_image_crop's ranges) and the rescaled size
+    // (color_image_rescale's) follow from the mosaic's size as they do on the host; a mosaic of another size is left unpublished like a frame of another size
+    void publish_mosaic(unsigned f) {
+        {
+            std::lock_guard<std::mutex> l(mu_);
+            const Mosaic &m = mosaics[f];
+            if (!size_known_ && size_mismatch_.empty()) {
+                int cw = m.width, ch = m.height;
+                if (run_.crop) {
+                    const int x0 = run_.center.x - run_.extent.x / 2, x1 = run_.center.x + run_.extent.x / 2, y0 = run_.center.y - run_.extent.y / 2, y1 = run_.center.y + run_.extent.y / 2;
+                    if (x0 < 0 || y0 < 0 || x1 > m.width || y1 > m.height || x1 <= x0 || y1 <= y0)
+                        size_mismatch_ = "center / extent do not fit the " + std::to_string(m.width) + "x" + std::to_string(m.height) + " frames";
+                    crop_x0_ = x0; crop_y0_ = y0; cw = x1 - x0; ch = y1 - y0;
+                }
+                src_width_ = cw; src_height_ = ch;
+                if (run_.rescale) { cw = (int)lrint((double)cw * run_.scale); ch = (int)lrint((double)ch * run_.scale); }
+                if (size_mismatch_.empty() && (cw < 1 || ch < 1)) size_mismatch_ = "scale " + std::to_string(run_.scale) + " leaves no pixel of the frames";
+                if (size_mismatch_.empty()) { mosaic_width_ = m.width; mosaic_height_ = m.height; width = cw; height = ch; stride = ((cw + 3) / 4) * 4; size_known_ = true; }
+            }
+            if (size_known_ && (m.width != mosaic_width_ || m.height != mosaic_height_)) {
+                if (size_mismatch_.empty())
+                    size_mismatch_ = "frames of different sizes: frame " + std::to_string(f) + " of the sequence is " + std::to_string(m.width) + "x" + std::to_string(m.height) +
+                                     ", the sequence " + std::to_string(mosaic_width_) + "x" + std::to_string(mosaic_height_);
+            } else if (size_known_) frame_ready_[f] = 1;
         }
         cv_.notify_all();
     }
@@ -286,16 +317,34 @@ private:
         sfa_sequence *s = nullptr;
         int rc = sfa_sequence_create(gpu.ctx.get(), width, height, n_mine, &s);
         gpu.resident.reset(s);
+        // gpu_ingest 1: the mosaic as it is, demosaiced into the crop (host order: demosaic, crop, rescale); where the frames are rescaled, into a one-frame
+        // sequence of the crop's size that sfa_sequence_rescale reads -- one stream, so the next mosaic overwrites it only after that
+        DeviceSequence full;
+        if (run_.gpu_ingest && run_.rescale && rc == SFA_OK) {
+            sfa_sequence *t = nullptr;
+            rc = sfa_sequence_create(gpu.ctx.get(), src_width_, src_height_, 1, &t);
+            full.reset(t);
+        }
+        double sent = 0;
         for (int f = fr.lo; f < fr.hi && rc == SFA_OK; f++) {
             if (!wait([&] { return frame_ready_[start_f + f] != 0; })) return;
-            rc = sfa_sequence_upload(s, f - fr.lo, frames[start_f + f]->c1, frames[start_f + f]->stride);
+            if (run_.gpu_ingest) {
+                const Mosaic &m = mosaics[start_f + f];
+                rc = sfa_sequence_upload_mosaic(full ? full.get() : s, full ? 0 : f - fr.lo, m.data.data(), m.dtype, m.width, m.width, m.height, crop_x0_, crop_y0_, run_.demosaicing,
+                                                run_.red_x, run_.red_y);
+                if (rc == SFA_OK && full) rc = sfa_sequence_rescale(s, f - fr.lo, full.get(), 0, 1, run_.scale);
+                sent += (double)m.data.size();
+            } else {
+                rc = sfa_sequence_upload(s, f - fr.lo, frames[start_f + f]->c1, frames[start_f + f]->stride);
+                sent += (double)3 * width * height * sizeof(float);
+            }
         }
         std::vector<double> mine((size_t)6 * n_mine);
         if (rc == SFA_OK) rc = sfa_sequence_frame_sums(s, 0, n_mine, mine.data());  // (waits for the uploads: one stream)
         if (rc != SFA_OK) return fail(g);
         {
             std::lock_guard<std::mutex> l(mu_);
-            gpu.upload_bytes = (double)n_mine * 3 * width * height * sizeof(float);
+            gpu.upload_bytes = sent;
             gpu.upload_done_s = now_s() - t_begin_;
             for (int f = fr.lo; f < fr.hi; f++)
                 if (!have_sums_[f]) {                                                // a halo frame: whoever is first; the other GPU's sums are the same bits
@@ -323,6 +372,7 @@ private:
     bool size_known_ = false, stats_known_ = false, aborted_ = false;
     int n_have_ = 0;
     string size_mismatch_;
+    int mosaic_width_ = 0, mosaic_height_ = 0, crop_x0_ = 0, crop_y0_ = 0, src_width_ = 0, src_height_ = 0;   // gpu_ingest 1: the mosaics, the crop's origin, the frames before the rescaling
     std::vector<char> frame_ready_, have_sums_;
     std::vector<double> frame_sums_;
     double avg_[3] = {0, 0, 0}, std_[3] = {1, 1, 1};
@@ -346,6 +396,12 @@ static int read_frames(const Run &run, const string &sequence_path, const string
             pool.submit([&, f] {
                 int maxval = 255;
                 string error;                                                        // demosaicing (:482-527): the mosaic is the grey image
+                if (run.gpu_ingest) {                                                // ... and goes to the GPUs as it is
+                    if (!load_mosaic(names[f], &seq.mosaics[f], &error)) { std::lock_guard<std::mutex> l(err_mu); if (load_error.empty()) load_error = error; return; }
+                    seq.maxval[f] = seq.mosaics[f].maxval;
+                    seq.publish_mosaic(f);
+                    return;
+                }
                 ColorImage img(load_frame(names[f], run.raw, run.demosaicing, run.red_x, run.red_y, &maxval, &error));
                 if (img && run.preprocess && (run.extent.x > 0 || run.extent.y > 0)) {   // use only a part of the images (:533-536)
                     ColorImage part(color_image_crop(img.get(), run.center.x, run.center.y, run.extent.x, run.extent.y));
@@ -362,7 +418,7 @@ static int read_frames(const Run &run, const string &sequence_path, const string
     if (load_error.empty()) load_error = seq.size_mismatch();
     if (!load_error.empty()) { std::cerr << load_error << std::endl; return 3; }
     decoded_at = now_s();
-    if (!run.rescale) return 0;
+    if (!run.rescale || run.gpu_ingest) return 0;
     Ctx ctx = new_ctx(run.dev0);
     if (!ctx) { std::cerr << sfa_last_error(nullptr) << std::endl; return 4; }
     for (unsigned f = run.layout.start_f; f < run.layout.end_f; f++) {
@@ -566,14 +622,18 @@ static void refine_windows(Refinement &rf, const WorkerPlan &wp, sfa_ctx *ctx, s
             const Window &wd = rf.todo[mine[b0 + e]];
             std::vector<int> idx(F);
             for (int k = 0; k < F; k++) idx[k] = window_tap(wd.jet, wd.backward, run.steps, k, first);
-            const float *chw[3] = {rf.channel_weights->c1, rf.channel_weights->c2, rf.channel_weights->c3};
+            const color_image_t *cw = rf.channel_weights;                            // (null with gpu_ingest 1)
+            const float *chw[3] = {cw ? cw->c1 : nullptr, cw ? cw->c2 : nullptr, cw ? cw->c3 : nullptr};
             const image_t *iwx = run.deep_matching ? inits[e].wx.get() : nullptr, *iwy = run.deep_matching ? inits[e].wy.get() : nullptr;
             if (run.deep_matching) rc = inits[e].rc;
             // only the forward solver gets the channel weights (:876 vs :1018); without raw weighting they are all ones (:597-598), which is
             // what a NULL pointer means to the library (x * 1.0f is exact: same bits, three planes less to read per pixel)
             if (rc == SFA_OK)
                 rc = sfa_job_upload_resident(job.get(), e, rf.seq.gpu(wp.gpu).resident.get(), idx.data(), F, iwx ? iwx->data : nullptr, iwy ? iwy->data : nullptr,
-                                             rf.seq.frames[run.layout.start_f]->stride, (wd.backward || !run.raw) ? nullptr : chw);
+                                             rf.seq.stride, (wd.backward || !run.raw || run.gpu_ingest) ? nullptr : chw);
+            // gpu_ingest 1: the same weights, formed on the GPU (after the upload, which sets the window's weights to ones).  raw_weight 1 gives
+            // all ones (rawWeighting: weight 1, the others 0.5 * (3 - 1)), which is what the NULL above already means: no planes, same bits
+            if (rc == SFA_OK && run.gpu_ingest && !wd.backward && run.raw_weight != 1.0f) rc = sfa_job_set_raw_weights(job.get(), e, 1, run.red_x, run.red_y, run.raw_weight);
         }
         if (rc == SFA_OK) rc = sfa_job_run(job.get());
         std::vector<std::shared_ptr<WindowResult>> results;
@@ -637,16 +697,16 @@ static void write_timings(const Run &run, const std::vector<Window> &todo, const
     tj << "[";
     for (size_t i = 0; i < todo.size(); i++)
         tj << (i ? "," : "") << "\n  {\"jet\": " << todo[i].jet << ", \"direction\": \"" << (todo[i].backward ? "backward" : "forward") << "\", \"gpu\": " << todo[i].gpu
-           << ", \"seconds\": " << todo[i].seconds << ", \"flo\": \"" << todo[i].out << "\""
+           << ", \"seconds\": " << todo[i].seconds << ", \"ingest\": \"" << (run.gpu_ingest ? "gpu" : "host") << "\", \"flo\": \"" << todo[i].out << "\""
            << (todo[i].epe >= 0 ? ", \"epe\": " + std::to_string(todo[i].epe) + ", \"aae\": " + std::to_string(todo[i].aae) : string()) << "}";
     tj << "\n]\n";
     std::ofstream rj((run.output + "run.json").c_str());
     rj << "{\"windows\": " << todo.size() << ", \"gpus\": " << run.ngpu << ", \"streams\": " << run.streams << ", \"batch\": " << run.batch << ", \"io_threads\": " << run.io_threads
-       << ", \"decode_seconds\": " << decode << ", \"normalize_seconds\": " << normalize << ", \"ingest_seconds\": " << ingest << ", \"refine_seconds\": " << refine << ", \"total_seconds\": " << total;
+       << ", \"ingest_path\": \"" << (run.gpu_ingest ? "gpu" : "host") << "\", \"decode_seconds\": " << decode << ", \"normalize_seconds\": " << normalize << ", \"ingest_seconds\": " << ingest << ", \"refine_seconds\": " << refine << ", \"total_seconds\": " << total;
     // per GPU: the frames it was sent (its windows' frames + halo), when the last of them had arrived, when its frames were normalised and when its first worker
     // began to refine -- all in seconds since the run began.  The whole sequence is "sequence_bytes"
     double last_upload = 0, first_refine = -1;
-    rj << ", \"sequence_bytes\": " << (double)(run.layout.end_f - run.layout.start_f) * 3 * seq.width * seq.height * sizeof(float) << ", \"per_gpu\": [";
+    rj << ", \"sequence_bytes\": " << (double)(run.layout.end_f - run.layout.start_f) * 3 * seq.width * seq.height * sizeof(float) << ", \"per_gpu\": [";   // (resident; gpu_ingest 1 sends less: upload_bytes)
     for (int g = 0; g < run.ngpu; g++) {
         const Sequence::Gpu &t = seq.gpu(g);
         rj << (g ? ", " : "") << "{\"gpu\": " << g << ", \"device\": " << run.device_of(g) << ", \"frames\": [" << seq.gpu_frames[g].lo << ", " << seq.gpu_frames[g].hi << "], \"upload_bytes\": " << t.upload_bytes
@@ -665,6 +725,13 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
         std::cerr << "gpu_batch " << run.batch << " is out of range: a lockstep job takes 1 .. 128 windows (more windows run as several jobs: gpu_streams, batches per worker)" << std::endl;
         return 2;
     }
+    if (run.gpu_ingest) {                                                            // the runs that need the RGB frames on the host: refused by name, never a silent host path
+        const char *why = !run.raw ? "raw 0: the frames are no mosaics, there is nothing to demosaic on the GPU"
+                          : run.deep_matching ? "deep_matching 1: EpicFlow's initialisation reads the RGB frames on the host"
+                          : run.write_files ? "verbose: this verbosity writes sequence/frame_*.png and the tmp/ images from the RGB frames on the host"
+                                            : nullptr;
+        if (why) { std::cerr << "gpu_ingest 1 is refused with " << why << "; set gpu_ingest 0" << std::endl; return 1; }
+    }
     mkdirs(run.output);
     if (run.layout.start_f > run.layout.end_f) return 0;
     if (run.deep_matching && !deep_matching_inputs_exist(run, opt.resume_frame)) return 2;
@@ -681,9 +748,11 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     Sequence seq(run, gpu_frames, t_begin);                                          // one uploader thread per GPU, from now on
     double decoded_at = 0;
     if (const int rc = read_frames(run, sequence_path, format, seq, decoded_at)) return rc;
-    ColorImage channel_weights(color_image_new(seq.width, seq.height));              // :597-598 (all ones without raw weighting)
-    std::fill(channel_weights->c1, channel_weights->c1 + (size_t)3 * channel_weights->stride * seq.height, 1.0f);
-    if (run.raw) rawWeighting(channel_weights.get(), run.red_x, run.red_y, run.raw_weight);   // :599-600
+    ColorImage channel_weights(run.gpu_ingest ? nullptr : color_image_new(seq.width, seq.height));   // :597-598 (all ones without raw weighting); gpu_ingest 1: the GPUs form them
+    if (channel_weights) {
+        std::fill(channel_weights->c1, channel_weights->c1 + (size_t)3 * channel_weights->stride * seq.height, 1.0f);
+        if (run.raw) rawWeighting(channel_weights.get(), run.red_x, run.red_y, run.raw_weight);   // :599-600
+    }
     std::vector<Flow> gt(params.Jets);
     if (!run.file_gt.empty())
         if (const int rc = load_ground_truth(run, gt)) return rc;
