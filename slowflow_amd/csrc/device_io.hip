@@ -2,7 +2,7 @@
 // sfa_job_set_flow_device, sfa_job_download_device, sfa_sequence_upload_device).  Three kernels that convert ((float) of the element) and move, nothing
 // else: a job filled by them holds the bits of the same job filled by the host copies.  One launch per call instead of a copy per plane.
 //   - the caller's side is addressed with 64-bit element strides (a view into a large tensor can lie beyond 2^31 elements); the job's side with the
-//     offsets the job itself uses (pitch, pl, element stride es: api.hip Level::layout),
+//     offsets the job itself uses (pitch, pl, element stride es: job.hip Level::layout),
 //   - columns >= width of the job's planes are never written (the project's rule for padding lanes: they keep what the job put there),
 //   - the job reads the packed planes only later (the pyramid of the next sfa_job_run, after every window of the call has been packed: 2 GB at
 //     128 windows), so they leave as non-temporal stores -- what k_warp_smooth's warped images taught (the kernel waited for its write

@@ -37,7 +37,7 @@ struct WMask {
     static WMask one(int b) { WMask r = none(); r.w[b >> 6] = 1ull << (b & 63); return r; }
 };
 constexpr int kMaxTerms = 4 * SFA_MAX_REF;
-// What ctx->d_last holds (ONE definition for api.hip and kernels.hip -- ADVICE r5: the layout was repeated by hand in four places): the norms of every window's
+// What ctx->d_last holds (ONE definition for job.hip and kernels.hip -- ADVICE r5: the layout was repeated by hand in four places): the norms of every window's
 // last outer iteration, the windows' finished-block counters of k_update_outer_x, the windows k_outer_threshold could not decide, the exact norms of
 // launch_exact_norms.  The pinned mirror ctx->h_red is at least this large (the exact norms are read back into ITS `exact` member, never into pageable memory).
 struct LastBlock {
@@ -57,7 +57,7 @@ __host__ __device__ inline double break_band(int w, int h) {
     return bound > 1e-3 ? bound : 1e-3;
 }
 
-// device-side outer break (api.hip run_level): the host reads the mask of kMaskLag iterations ago from a ring of kMaskRing pinned words
+// device-side outer break (job.hip: struct OuterBreak): the host reads the mask of kMaskLag iterations ago from a ring of kMaskRing pinned words
 constexpr int kMaskLag = 2, kMaskRing = 4;
 static_assert(kMaskLag < kMaskRing, "a ring slot is rewritten kMaskRing iterations after it was read kMaskLag iterations late");
 
@@ -157,6 +157,8 @@ inline int sw_int(Switches::Id i, int dflt) { return g_switches.given[i] ? g_swi
 // argument checks of the entry points: refuse with "<function>: <msg>" on the context `ctx` of the scope (a helper names its caller in `fn`)
 #define CHECK_ARGS_FN(fn, cond, msg) do { if (!(cond)) return sfa::set_error(ctx, SFA_ERR_ARG, "%s: %s", fn, msg); } while (0)
 #define CHECK_ARGS(cond, msg) CHECK_ARGS_FN(__func__, cond, msg)
+// the same with a message of the caller's own making (the device seam, the mosaic entry points: a refusal names the argument)
+#define REFUSE(...) return sfa::set_error(ctx, SFA_ERR_ARG, __VA_ARGS__)
 
 inline int round_up(int a, int m) { return (a + m - 1) / m * m; }
 inline int host_stride(int w) { return ((w + 3) / 4) * 4; }     // image.c:25
@@ -194,6 +196,7 @@ int download_plane(sfa_ctx *ctx, float *host, int stride, const float *dev, int 
 struct Geo { int w, h, pitch; long pl; long es; int nb; WMask active; const unsigned long long *amask; };
 
 struct PenaltyDev { int id; float eps, trunc; };
+inline PenaltyDev pen(const sfa_penalty &p) { return PenaltyDev{p.id, p.eps, p.trunc}; }
 
 // several warps (factor != 0) of one flow field in one pass; offsets are arena offsets of element 0 like Term::i1_off, mask_off < 0: no mask
 struct WarpJob { long src_off, dst_off, mask_off; int factor; };
@@ -308,6 +311,8 @@ bool launch_pyr_down(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dp
 void launch_presmooth(sfa_ctx *c, const Geo &g, float *dst, float *tmp, const float *src, int nplanes, float sigma);
 void launch_normalize_sums(sfa_ctx *c, const Geo &g, const float *frames3, double *red /* [3][2] */);
 void launch_normalize_apply(sfa_ctx *c, const Geo &g, float *frames3, const double avg[3], const double stdv[3]);
+// cv::getGaussianKernel's taps for cv::GaussianBlur(Size(0,0), sigma) on CV_32F (api.hip); returns the radius.  Hidden: job.hip's use adds no export
+__attribute__((visibility("hidden"))) int cv_gauss_taps(float sigma, float *k);
 
 // ---- device_io.hip: the device seam (sfa_job_upload_device ...): conversions and moves only ---------------------------------------------
 // A strided source of colour frames in device memory: element (window, frame, channel, row, column) at p + the strides, in elements of dtype (sfa_dev_dtype)
@@ -356,7 +361,7 @@ int sor_rb_run(sfa_ctx *c, const Geo &g, float *du, float *dv, float *a11, float
 int sor_run(sfa_ctx *c, SorWorkspace &ws, const Geo &g, float *du, float *dv, float *a11, float *a12, float *a22, const float *b1, const float *b2,
             const float *sh, const float *sv, int K, float omega, bool inv_out);
 
-// ---- the device seam's argument checks (api.hip), shared by sfa_job_*_device and sfa_pair_job_*_device (two_frame.hip).  Each refuses with SFA_ERR_ARG and a
+// ---- the device seam's argument checks (api.hip), shared by sfa_job_*_device (job.hip) and sfa_pair_job_*_device (two_frame.hip).  Each refuses with SFA_ERR_ARG and a
 // message that names `fn` and the argument; nothing is launched on a refusal ----------------------------------------------------------------------------
 // the frames of `nwin` windows (or pairs, or sequence frames) of F frames each: layout and pointer
 int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h);
@@ -367,6 +372,8 @@ int check_download_destination(sfa_ctx *ctx, const char *fn, int n, int w, int h
                                const long long occ_strides[3]);
 // elements [b0, b0 + n) of a batch of nb (`what`: "windows", "pairs")
 int check_batch_range(sfa_ctx *ctx, const char *fn, const char *what, int b0, int n, int nb);
+// the demosaicing method and the red site's parities of the raw-ingest entry points (and of sfa_job_set_raw_weights: method 0)
+__attribute__((visibility("hidden"))) int check_mosaic_method(sfa_ctx *ctx, const char *fn, int method, int red_x, int red_y);
 
 }  // namespace sfa
 
@@ -385,4 +392,22 @@ struct sfa_pair_job {
     sfa::SorWorkspace ws;
     float *plane(int b, int i) const { return mem.f() + b * es + (long)i * pl; }
     sfa::Geo geo() const { return sfa::Geo{w, h, pitch, pl, es, n, sfa::WMask::first(n), nullptr}; }
+};
+
+// ---- sfa_sequence: n colour frames of one size resident in HBM (api.hip: the entry points; job.hip: sfa_job_upload_resident copies windows out of one) ----
+struct sfa_sequence {
+    sfa_ctx *ctx = nullptr;
+    int w = 0, h = 0, n = 0, pitch = 0;
+    long pl = 0;
+    sfa::DevMem mem;                        // n x 3 planes at the device pitch
+    sfa::DevMem sums;                       // n x 6 doubles: per frame and channel sum(I), sum(I*I)
+    // sfa_sequence_upload_mosaic: the caller's mosaic goes through a pinned copy into mos_dev, the demosaicing kernel's source; ev_mos says the copy out of
+    // the pinned buffer has been made (the device buffer is reused in stream order)
+    void *mos_stage = nullptr;
+    size_t mos_stage_bytes = 0;
+    hipEvent_t ev_mos = nullptr;
+    sfa::DevMem mos_dev;
+    sfa::DevMem rescale_tmp;                // sfa_sequence_rescale into this sequence: the blurred frames of a chunk and the row pass's scratch
+    float *frame(int f) const { return mem.f() + (long)f * 3 * pl; }
+    sfa::Geo geo() const { return sfa::Geo{w, h, pitch, pl, 0, 1, sfa::WMask::first(1), nullptr}; }
 };

@@ -501,6 +501,36 @@ def test_fused_assembly_is_the_unfused_pipeline(ctx, oracle, switches, kw, w, h)
     assert np.allclose(out[0][2], out[1][2], rtol=1e-6, atol=0)
 
 
+@pytest.mark.parametrize("name,kw", [("SFA_NO_DIRECT_OPERANDS", dict()), ("SFA_NO_DIRECT_OPERANDS", dict(niter_inner=2)), ("SFA_NO_UV_ALIAS", dict())])
+def test_level_without_direct_operands_or_uv_alias(ctx, oracle, switches, name, kw):
+    """the two cross-check forms of the fused level that nothing else runs: SFA_NO_DIRECT_OPERANDS (the fused assembly leaves the a11 .. b2 planes, the solver prepares its
+    own operands, the flow update reads du / dv planes) and SFA_NO_UV_ALIAS (one inner iteration with uu / vv planes of their own).  Both are the default form's arithmetic
+    on other storage: the same flow bit for bit for both windows of a lockstep job (the change norms are fp64 sums in another order), and the default form is held to the
+    oracle like test_level_variants"""
+    w, h = 67, 45
+    frames, af, sf = normalized_frames(oracle, w, h, 3, seed=7)
+    wins = [frames, frames[::-1]]
+    po, ps = mk_params(oracle, S=2, rho=[1], omega=[0], norm_avg=af, norm_std=sf, niter_outer=2, layers=1, **kw)
+    runs = []
+    for value in ("1", None):
+        switches.set(name, value)
+        job = sfa.Job(ctx, ps, w, h, len(wins))
+        for b, f in enumerate(wins):
+            job.upload(b, [c_(x) for x in f])
+        job.run()
+        runs.append([job.download(b) for b in range(len(wins))])
+        job.close()
+    for b, f in enumerate(wins):
+        (sx, sy, sch), (gx, gy, gch) = runs[0][b], runs[1][b]
+        assert np.array_equal(sx, gx) and np.array_equal(sy, gy), (name, b)
+        assert np.allclose(sch, gch, rtol=1e-6, atol=0), (name, b, sch, gch)
+        wxo, wyo = orc.plane(h, orc.stride_of(w)), orc.plane(h, orc.stride_of(w))
+        rc, _, _ = oracle.compute_one_level(po, wxo, wyo, f, w)
+        d = max(np.abs(valid(wxo, w) - valid(gx, w)).max(), np.abs(valid(wyo, w) - valid(gy, w)).max())
+        print(f"{name} {kw} window {b}: max|d(u,v)| against the oracle = {d:.3g}")
+        assert rc == 0 and d <= TOL_LEVEL, (name, b, d)
+
+
 def test_level_channel_weights_and_initial_flow(ctx, oracle):
     w, h = 67, 45
     frames, af, sf = normalized_frames(oracle, w, h, 3, seed=9)
