@@ -134,6 +134,39 @@ int sfa_accumulate_consistent(sfa_ctx *ctx, int n, int FF, int w, int h, int str
  * *gw = floor((1.0f * w) / xy_incr); grid pixel (x, y) sits on image pixel (x * xy_incr + xy_start, y * xy_incr + xy_start).
  * SFA_ERR_ARG for w, h < 1, skip < 0 and an empty grid. */
 int sfa_accumulate_grid(int w, int h, int skip, int *gw, int *gh);
+/* Where a rate's jet files sit relative to the tracking frames (dense_tracking.cpp:1134-1146, :1171-1177): the planes as read, the crop of
+ * utils.cpp:308-318 and the factor the reference resizes by.  The target is lrint(cw * (double)rescale) x lrint(ch * (double)rescale) (cvRound:
+ * halves to even) and must be the w x h of the call.  A source without a crop, of the target's size and with rescale 1 is the identity: it is not
+ * resampled (the reference's identity resize can only turn -0.0 into +0.0).  sfa_jet_source_default fills the identity of a w x h plane. */
+typedef struct sfa_jet_source {
+    int sw, sh, stride;     /* the planes as read; row stride in elements */
+    int x0, y0, cw, ch;     /* crop: columns x0 .. x0+cw-1, rows y0 .. y0+ch-1 (utils.cpp:308-318); 0, 0, sw, sh = none */
+    float rescale;          /* (1.0f * w) / cw, dense_tracking.cpp:1142 */
+} sfa_jet_source;
+void sfa_jet_source_default(sfa_jet_source *src, int w, int h, int stride);
+/* Stage binding: n flow fields u[k], v[k] (host float planes as src describes them; stride padding is never read) cropped, resized as
+ * cv::resize(src, dst, Size(0, 0), rescale, rescale, INTER_LINEAR) resizes CV_64FC2 and multiplied by (double)rescale (:1143-1146), on the GPU.
+ * The source coordinate is (float)((d + 0.5) * (1.0 / (double)rescale) - 0.5), its floor the left tap, taps clamped at the border with weight 0; the
+ * weights 1.f - f and f are floats, samples, products and sums fp64 without contraction, rows first, then columns (OpenCV's
+ * HResizeLinear<double, double, float>).  OpenCV is not in the tree: parity unpinned, pinned to tests/jet_resample_ref.py.  Always resamples, the
+ * identity included.  out_u, out_v: packed [n][h][w] doubles.  SFA_ERR_ARG, naming the argument: a target other than w x h (both sizes are named), a
+ * crop outside the planes, rescale <= 0. */
+int sfa_jet_flow_resample(sfa_ctx *ctx, int n, const sfa_jet_source *src, const float *const *u, const float *const *v, int w, int h, double *out_u,
+                          double *out_v);
+/* Stage binding: n raw 8-bit occlusion images (row stride src->stride bytes) -> packed [n][h][w] masks, 0 = occluded: cv::resize(..., INTER_CUBIC) on
+ * 8-bit (taps floor(f) - 1 .. floor(f) + 2 with clamped indices, Keys' cubic with A = -0.75 in fp32, each coefficient rounded to a 16-bit integer at 11
+ * fractional bits, integer row sums, columns ending in (sum + 2^21) >> 22 saturated to 0 .. 255), the 3 x 3 median with a replicated border, 255 - x
+ * (:1177-1189).  With rescale 1 the cubic is the identity.  Parity unpinned, as the median: OpenCV's SIMD build rounds the column pass in float, which can
+ * differ by one grey level within two source pixels of a label edge.  A crop is refused by name (the reference's crop() reads the 8-bit Mat through
+ * at<Vec2d>: undefined). */
+int sfa_jet_occlusion_decode(sfa_ctx *ctx, int n, const sfa_jet_source *src, const unsigned char *const *occ, int w, int h, unsigned char *mask);
+/* sfa_accumulate_consistent for jets of another size: the flows are the planes src describes and are brought to w x h on the GPU as
+ * sfa_jet_flow_resample does it; occ (or NULL) are the RAW occlusion images as read, decoded on the GPU as sfa_jet_occlusion_decode does it.  The
+ * resampled flows are doubles, and the kernel gathers them as such.  An identity source runs sfa_accumulate_consistent's float path: the same kernel,
+ * the same bits.  stage_ms: NULL or 2 floats, the milliseconds of the resampling / interleaving kernels and of the accumulation kernel (HIP events). */
+int sfa_accumulate_consistent_scaled(sfa_ctx *ctx, int n, int FF, int w, int h, const sfa_jet_source *src, const float *const *fwd_u,
+                                     const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v, const unsigned char *const *occ,
+                                     double epsilon, int skip, int discard, int all_steps, double *acc_u, double *acc_v, int *tracked, float *stage_ms);
 /* dense_tracking's unary energies (dense_tracking.cpp:1219-1257): the cfg keys of setDefault (:118-165) with the C types the reference reads them in
  * (:606-623, :489-495, :661-675).  sfa_energy_params_default fills setDefault's values, weight 0 and skip 1. */
 typedef struct sfa_energy_params {
@@ -169,6 +202,13 @@ int sfa_hypothesis_energies_ex(sfa_ctx *ctx, const sfa_energy_params *p, int n, 
                                const double *acc_v, const int *tracked, const float *const *frames, const float *const *fwd_u, const float *const *fwd_v,
                                const float *const *bwd_u, const float *const *bwd_v, double *energy, unsigned long long *occ_bits, double *adapted_u,
                                double *adapted_v);
+/* sfa_hypothesis_energies_ex with rate acc_min_fps's flows described by flow_src (the planes of fwd_u .. bwd_v; `stride` stays the frames') and
+ * brought to w x h on the GPU as sfa_jet_flow_resample does it: forward_flow[f] = r_forward_flow[f] (dense_tracking.cpp:1148-1151) are the rescaled
+ * doubles.  flow_src is ignored where the four flow arrays are NULL; an identity source runs sfa_hypothesis_energies_ex's float path. */
+int sfa_hypothesis_energies_scaled(sfa_ctx *ctx, const sfa_energy_params *p, int n, int r_Jets, int Jets, int w, int h, int stride, const double *acc_u,
+                                   const double *acc_v, const int *tracked, const float *const *frames, const sfa_jet_source *flow_src,
+                                   const float *const *fwd_u, const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v,
+                                   double *energy, unsigned long long *occ_bits, double *adapted_u, double *adapted_v);
 /* dense_tracking's computeSmoothnessWeight (dense_tracking.cpp:367-405, called at :969-981 with coef 5.0): the luminance
  * (0.299f (c1 std_1 + avg_1) + 0.587f (...) + 0.114f (...)) / 255.0f (/ 65535.0f with hbit), its 5-tap {0, -8/12, 1/12} derivatives, then
  * 0.5f * expf(-coef * sqrtf(lx^2 + ly^2)), all in fp32 without contraction.  The formula is the first output of Variational_AUX_MT::compute_dpsis_weight

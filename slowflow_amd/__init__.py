@@ -81,6 +81,26 @@ def energy_params(**kw):
     return p
 
 
+class JetSource(C.Structure):
+    """sfa_jet_source: where a rate's jet files sit relative to the tracking frames (the planes as read, the crop, the resize factor)"""
+    _fields_ = [("sw", C.c_int), ("sh", C.c_int), ("stride", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("cw", C.c_int), ("ch", C.c_int),
+                ("rescale", C.c_float)]
+
+    def target(self):
+        """(w, h) = (lrint(cw * (double)rescale), lrint(ch * (double)rescale)), halves to even (cvRound)"""
+        r = np.float64(np.float32(self.rescale))
+        return int(np.rint(np.float64(self.cw) * r)), int(np.rint(np.float64(self.ch) * r))
+
+
+def jet_source(sw, sh, stride=None, crop=None, rescale=None, w=None):
+    """a JetSource of sw x sh planes (row stride `stride` elements, default sw); crop: None or (x0, y0, cw, ch) (utils.cpp:308-318); the factor is
+    `rescale`, or (1.0f * w) / cw for the target width w (dense_tracking.cpp:1142), or 1"""
+    x0, y0, cw, ch = crop if crop is not None else (0, 0, sw, sh)
+    if rescale is None:
+        rescale = np.float32(w) / np.float32(cw) if w is not None else 1.0
+    return JetSource(int(sw), int(sh), int(sw if stride is None else stride), int(x0), int(y0), int(cw), int(ch), float(np.float32(rescale)))
+
+
 class FuseParams(C.Structure):
     """sfa_fuse_params: dense_tracking's fusion keys (setDefault, dense_tracking.cpp:136-152) in the C types the reference reads them in"""
     _fields_ = [("acc_beta", C.c_double), ("acc_spatial_occ", C.c_double), ("traj_sim_method", C.c_int), ("traj_sim_thres", C.c_double),
@@ -99,7 +119,7 @@ def fuse_params(**kw):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
@@ -409,18 +429,54 @@ class Context:
         self._ck(L.sfa_flow_magnitude_quantile(self.h, n, ua, va, w, h, stride, flow_scale, q, C.byref(qv), C.byref(mv)), "sfa_flow_magnitude_quantile")
         return qv.value, mv.value
 
-    def accumulate_consistent(self, fwd_u, fwd_v, bwd_u, bwd_v, w, epsilon, skip, discard, all_steps=True, masks=None):
+    def jet_flow_resample(self, u, v, source):
+        """sfa_jet_flow_resample: n flow fields u, v, fp32 (n, sh, stride) as `source` (a JetSource) describes them, cropped, resized by
+        source.rescale (INTER_LINEAR on doubles) and multiplied by it, on the GPU.  Returns (u, v): float64 (n, h, w), (w, h) = source.target()"""
+        u, v = (np.ascontiguousarray(a, dtype=np.float32) for a in (u, v))
+        assert u.ndim == 3 and u.shape == v.shape and u.shape[1:] == (source.sh, source.stride), "flows are (n, sh, stride)"
+        n = u.shape[0]
+        w, h = source.target()
+        out_u, out_v = np.zeros((n, h, w), np.float64), np.zeros((n, h, w), np.float64)
+        L = lib()
+        L.sfa_jet_flow_resample.argtypes = [C.c_void_p, C.c_int, C.POINTER(JetSource), C.POINTER(_f), C.POINTER(_f), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        up, vp = ((_f * max(n, 1))(*[fptr(a[k]) for k in range(n)]) for a in (u, v))
+        self._ck(L.sfa_jet_flow_resample(self.h, n, C.byref(source), up, vp, w, h, out_u.ctypes.data, out_v.ctypes.data), "sfa_jet_flow_resample")
+        return out_u, out_v
+
+    def jet_occlusion_decode(self, occ, source):
+        """sfa_jet_occlusion_decode: n raw occlusion images, uint8 (n, sh, stride), -> masks uint8 (n, h, w), 0 = occluded: INTER_CUBIC resize by
+        source.rescale, 3 x 3 median, 255 - x, on the GPU"""
+        occ = np.ascontiguousarray(occ, dtype=np.uint8)
+        assert occ.ndim == 3 and occ.shape[1:] == (source.sh, source.stride), "occlusion images are (n, sh, stride)"
+        n = occ.shape[0]
+        w, h = source.target()
+        mask = np.zeros((n, h, w), np.uint8)
+        L = lib()
+        _u8 = C.POINTER(C.c_ubyte)
+        L.sfa_jet_occlusion_decode.argtypes = [C.c_void_p, C.c_int, C.POINTER(JetSource), C.POINTER(_u8), C.c_int, C.c_int, C.c_void_p]
+        op = (_u8 * max(n, 1))(*[occ[k].ctypes.data_as(_u8) for k in range(n)])
+        self._ck(L.sfa_jet_occlusion_decode(self.h, n, C.byref(source), op, w, h, mask.ctypes.data), "sfa_jet_occlusion_decode")
+        return mask
+
+    def accumulate_consistent(self, fwd_u, fwd_v, bwd_u, bwd_v, w, epsilon, skip, discard, all_steps=True, masks=None, source=None, stage_ms=None):
         """dense_tracking's accumulateConsistentBatches (sfa_accumulate_consistent) for n segments of FF steps in one call.  fwd_u .. bwd_v: fp32
         arrays (n, FF, h, stride), only the w valid columns read; masks: uint8 (n, FF, h, stride), 0 = occluded, or None.  Returns (acc_u, acc_v,
-        tracked): float64 (n, S, gh, gw) with S = FF (all_steps) or 1 (the last step), int32 (n, gh, gw)"""
+        tracked): float64 (n, S, gh, gw) with S = FF (all_steps) or 1 (the last step), int32 (n, gh, gw).
+        source: a JetSource (sfa_accumulate_consistent_scaled): the flows are (n, FF, sh, source.stride) planes of another size, brought to w x h =
+        source.target() on the GPU, and masks are the RAW occlusion images of that shape (decoded on the GPU).  stage_ms: with a source, a list that
+        receives the milliseconds of the resampling kernels and of the accumulation kernel"""
         planes = [np.ascontiguousarray(a, dtype=np.float32) for a in (fwd_u, fwd_v, bwd_u, bwd_v)]
         assert planes[0].ndim == 4, "flows are (n, FF, h, stride)"
         n, FF, h, stride = planes[0].shape
+        if source is not None:
+            assert (h, stride) == (source.sh, source.stride), "flows are (n, FF, source.sh, source.stride)"
+            tw, h = source.target()
+            assert tw == w, "source.target() is %d wide, not %d" % (tw, w)
         for a in planes:
-            assert a.shape == (n, FF, h, stride), "every flow array has one shape"
+            assert a.shape == planes[0].shape, "every flow array has one shape"
         if masks is not None:
             masks = np.ascontiguousarray(masks, dtype=np.uint8)
-            assert masks.shape == (n, FF, h, stride), "masks have the flows' shape"
+            assert masks.shape == planes[0].shape, "masks have the flows' shape"
         gw, gh = accumulate_grid(w, h, skip) if n and FF else (1, 1)
         S = FF if all_steps else 1
         acc_u, acc_v = np.zeros((n, S, gh, gw), np.float64), np.zeros((n, S, gh, gw), np.float64)
@@ -432,17 +488,29 @@ class Context:
         k = max(n * FF, 1)
         ptrs = [(_f * k)(*[fptr(a[s, f]) for s in range(n) for f in range(FF)]) for a in planes]
         mp = (_u8 * k)(*[masks[s, f].ctypes.data_as(_u8) for s in range(n) for f in range(FF)]) if masks is not None else None
+        if source is not None:
+            L.sfa_accumulate_consistent_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JetSource)] + [C.POINTER(_f)] * 4 + [
+                C.POINTER(_u8), C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+            ms = (C.c_float * 2)()
+            self._ck(L.sfa_accumulate_consistent_scaled(self.h, n, FF, w, h, C.byref(source), ptrs[0], ptrs[1], ptrs[2], ptrs[3], mp, C.c_double(epsilon),
+                                                        int(skip), int(bool(discard)), int(bool(all_steps)), acc_u.ctypes.data, acc_v.ctypes.data,
+                                                        tracked.ctypes.data, ms if stage_ms is not None else None), "sfa_accumulate_consistent_scaled")
+            if stage_ms is not None:
+                stage_ms[:] = [ms[0], ms[1]]
+            return acc_u, acc_v, tracked
         self._ck(L.sfa_accumulate_consistent(self.h, n, FF, w, h, stride, ptrs[0], ptrs[1], ptrs[2], ptrs[3], mp, C.c_double(epsilon), int(skip),
                                              int(bool(discard)), int(bool(all_steps)), acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data),
                  "sfa_accumulate_consistent")
         return acc_u, acc_v, tracked
 
-    def hypothesis_energies(self, p, r_Jets, acc_u, acc_v, tracked, frames, w, flows=None, adapted=False):
+    def hypothesis_energies(self, p, r_Jets, acc_u, acc_v, tracked, frames, w, flows=None, adapted=False, flow_source=None):
         """dense_tracking's unary energies (sfa_hypothesis_energies) of every hypothesis of n segments of one rate.  p: EnergyParams; acc_u, acc_v:
         float64 (n, r_Jets, gh, gw) and tracked int32 (n, gh, gw), as accumulate_consistent(all_steps=True) returns them; frames: fp32 (n, Jets + 1,
         3, h, stride) normalised colour frames (c1, c2, c3); flows: None or (fwd_u, fwd_v, bwd_u, bwd_v), fp32 (n, Jets, h, stride) each, rate
         acc_min_fps's flows.  Returns energy float64 (n, gh, gw), +Inf where tracked != r_Jets, and occ_bits uint64 (n, gh, gw), bit t = occluded(t);
-        with adapted=True also the flows after adaptFPS(Jets), float64 (n, Jets, gh, gw) each (sfa_hypothesis_energies_ex; 0 without a hypothesis)"""
+        with adapted=True also the flows after adaptFPS(Jets), float64 (n, Jets, gh, gw) each (sfa_hypothesis_energies_ex; 0 without a hypothesis).
+        flow_source: a JetSource (sfa_hypothesis_energies_scaled): the flows are (n, Jets, sh, flow_source.stride) planes of another size, brought
+        to the frames' size on the GPU"""
         frames = np.ascontiguousarray(frames, dtype=np.float32)
         assert frames.ndim == 5 and frames.shape[2] == 3, "frames are (n, Jets + 1, 3, h, stride)"
         n, J1, _, h, stride = frames.shape
@@ -458,12 +526,21 @@ class Context:
         if flows is not None:
             flows = [np.ascontiguousarray(a, dtype=np.float32) for a in flows]
             for a in flows:
-                assert a.shape == (n, Jets, h, stride), "flows are (n, Jets, h, stride)"
+                assert a.shape == ((n, Jets, h, stride) if flow_source is None else (n, Jets, flow_source.sh, flow_source.stride)), "flows are (n, Jets, h, stride)"
             fl = [(_f * max(n * Jets, 1))(*[fptr(a[s, t]) for s in range(n) for t in range(Jets)]) for a in flows]
         else:
             fl = [None] * 4
         energy = np.zeros((n, gh, gw), np.float64)
         occ = np.zeros((n, gh, gw), np.uint64)
+        if flow_source is not None:
+            L.sfa_hypothesis_energies_scaled.argtypes = [C.c_void_p, C.POINTER(EnergyParams)] + [C.c_int] * 6 + [C.c_void_p] * 3 + [
+                C.POINTER(_f), C.POINTER(JetSource)] + [C.POINTER(_f)] * 4 + [C.c_void_p] * 4
+            au, av = (np.zeros((n, Jets, gh, gw), np.float64), np.zeros((n, Jets, gh, gw), np.float64)) if adapted else (None, None)
+            self._ck(L.sfa_hypothesis_energies_scaled(self.h, C.byref(p), n, int(r_Jets), Jets, w, h, stride, acc_u.ctypes.data, acc_v.ctypes.data,
+                                                      tracked.ctypes.data, fp, C.byref(flow_source), fl[0], fl[1], fl[2], fl[3], energy.ctypes.data,
+                                                      occ.ctypes.data, au.ctypes.data if adapted else None, av.ctypes.data if adapted else None),
+                     "sfa_hypothesis_energies_scaled")
+            return (energy, occ, au, av) if adapted else (energy, occ)
         if not adapted:
             self._ck(L.sfa_hypothesis_energies(self.h, C.byref(p), n, int(r_Jets), Jets, w, h, stride, acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data,
                                                fp, fl[0], fl[1], fl[2], fl[3], energy.ctypes.data, occ.ctypes.data), "sfa_hypothesis_energies")

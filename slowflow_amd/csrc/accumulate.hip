@@ -7,7 +7,7 @@
 //
 // Shape: one thread per (segment, grid pixel), looping over f inside it; the segment is blockIdx.y, so n independent segments (the reference's start_jet
 // loop, dense_tracking.cpp:726, and its rates) cost one launch.  Each step gathers the forward flow at the tracked point and the backward flow at its
-// target: 4 + 4 taps of (u, v), which the upload interleaves into float2 so that a tap is one 8-byte load.  The flows are read where the trajectories
+// target: 4 + 4 taps of (u, v), interleaved into float2 (a tap is one 8-byte load; double2 for jets resampled from another size).  Read where the trajectories
 // go, so the work is bound by these gathers (not by the fp64 arithmetic: about 60 fp64 operations per step).
 #include "sfa_device.h"
 
@@ -20,7 +20,9 @@ constexpr int kAccThreads = 256;
 // fwd, bwd: n * FF float2 planes of w x h (segment s, step f at plane s * FF + f); masks: the same count of uint8 planes or null (0 = occluded, the
 // reference's value after 255 - x, dense_tracking.cpp:1192).  acc_u, acc_v: n * S planes of gw x gh doubles, S = FF (all_steps) or 1 (the last step);
 // tracked: n planes of gw x gh.  The reference's Vec2d holds (y, x) = (v, u): channel 0 is v (utils.cpp:364-369); here each channel has its name.
-__global__ void __launch_bounds__(kAccThreads) k_accumulate(const float2 *__restrict__ fwd, const float2 *__restrict__ bwd, const unsigned char *__restrict__ masks,
+// T2 = float2: the flows as read; T2 = double2: flows resampled from jets of another size (jet_resample.hip), a tap being one 16-byte load.
+template <class T2>
+__global__ void __launch_bounds__(kAccThreads) k_accumulate(const T2 *__restrict__ fwd, const T2 *__restrict__ bwd, const unsigned char *__restrict__ masks,
                                                             int FF, int w, int h, int gw, int gh, int xy_incr, int xy_start, double epsilon, int discard, int all_steps,
                                                             double *__restrict__ acc_u, double *__restrict__ acc_v, int *__restrict__ tracked) {
     const int i = blockIdx.x * kAccThreads + threadIdx.x;
@@ -28,10 +30,10 @@ __global__ void __launch_bounds__(kAccThreads) k_accumulate(const float2 *__rest
     const int s = blockIdx.y, gx = i % gw, gy = i / gw;
     const size_t pl = (size_t)w * h, gpl = (size_t)gw * gh;
     const int oy = gy * xy_incr + xy_start, ox = gx * xy_incr + xy_start;      // on the image: checked by the host (sfa_accumulate_grid)
-    const float2 *F = fwd + (size_t)s * FF * pl, *B = bwd + (size_t)s * FF * pl;
+    const T2 *F = fwd + (size_t)s * FF * pl, *B = bwd + (size_t)s * FF * pl;
     const unsigned char *M = masks ? masks + (size_t)s * FF * pl : nullptr;
     // quirk: last_flow starts as forward[0] AT the grid point, not zero (utils.cpp:530-535: "avoid zero flow if directly occluded")
-    const float2 f0 = F[(size_t)oy * w + ox];
+    const T2 f0 = F[(size_t)oy * w + ox];
     double last_u = f0.x, last_v = f0.y;
     double prev_u = 0, prev_v = 0;                                              // acc_forward[f - 1]
     bool occluded = false;                                                      // :537
@@ -103,48 +105,96 @@ int sfa_accumulate_grid(int w, int h, int skip, int *gw, int *gh) {
     return SFA_OK;
 }
 
-int sfa_accumulate_consistent(sfa_ctx *ctx, int n, int FF, int w, int h, int stride, const float *const *fwd_u, const float *const *fwd_v,
-                              const float *const *bwd_u, const float *const *bwd_v, const unsigned char *const *masks, double epsilon, int skip, int discard,
-                              int all_steps, double *acc_u, double *acc_v, int *tracked) {
-    if (!(ctx && fwd_u && fwd_v && bwd_u && bwd_v && acc_u && acc_v && tracked))
-        return set_error(ctx, SFA_ERR_ARG, "sfa_accumulate_consistent: null argument");
-    if (!(n >= 1 && n <= 65535 && FF >= 1 && w >= 1 && h >= 1 && stride >= w))
-        return set_error(ctx, SFA_ERR_ARG, "sfa_accumulate_consistent: bad sizes (1 <= n <= 65535 segments, FF >= 1, w, h >= 1, stride >= w)");
+// sfa_accumulate_consistent and sfa_accumulate_consistent_scaled: the planes src describes, as float2 where src is the identity (masks: decoded masks or,
+// with raw_occ, the occlusion images as read), else resampled to double2 (masks: raw occlusion images)
+static int accumulate_run(sfa_ctx *ctx, const char *fn, int n, int FF, int w, int h, const sfa_jet_source *src, const float *const *fwd_u, const float *const *fwd_v,
+                          const float *const *bwd_u, const float *const *bwd_v, const unsigned char *const *masks, bool raw_occ, double epsilon, int skip,
+                          int discard, int all_steps, double *acc_u, double *acc_v, int *tracked, float *stage_ms) {
+    if (!(ctx && fwd_u && fwd_v && bwd_u && bwd_v && acc_u && acc_v && tracked)) return set_error(ctx, SFA_ERR_ARG, "%s: null argument", fn);
+    if (!(n >= 1 && n <= 65535 && FF >= 1 && w >= 1 && h >= 1 && src && src->stride >= src->sw))
+        return set_error(ctx, SFA_ERR_ARG, "%s: bad sizes (1 <= n <= 65535 segments, FF >= 1, w, h >= 1, stride >= w)", fn);
+    bool identity;
+    SFA_TRY(jet_source_check(ctx, fn, src, w, h, &identity));
+    if (masks && raw_occ && (src->x0 != 0 || src->y0 != 0 || src->cw != src->sw || src->ch != src->sh))
+        return set_error(ctx, SFA_ERR_ARG, "%s: source: cropped occlusions are not supported (the reference's crop() reads the 8-bit Mat through at<Vec2d>)", fn);
     int gw, gh;
     if (sfa_accumulate_grid(w, h, skip, &gw, &gh) != SFA_OK) return set_error(ctx, SFA_ERR_ARG, "%s", sfa_last_error(nullptr));
-    const size_t np = (size_t)n * FF, pl = (size_t)w * h;
+    const size_t np = (size_t)n * FF, pl = (size_t)w * h, spl = identity ? pl : (size_t)src->cw * src->ch;
     for (size_t k = 0; k < np; k++)
-        if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k] || (masks && !masks[k])) return set_error(ctx, SFA_ERR_ARG, "sfa_accumulate_consistent: null plane %zu", k);
-    const int S = all_steps ? FF : 1;
+        if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k] || (masks && !masks[k])) return set_error(ctx, SFA_ERR_ARG, "%s: null plane %zu", fn, k);
+    const int S = all_steps ? FF : 1, stride = src->stride;
+    const size_t tap = identity ? 8 : 16;                                       // float2 or double2
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    DevMem dfw, dbw, dstage, dm, dau, dav, dtr;
-    SFA_TRY(dfw.alloc(ctx, np * pl * 8)); SFA_TRY(dbw.alloc(ctx, np * pl * 8)); SFA_TRY(dstage.alloc(ctx, np * pl * 8));
+    DevMem dfw, dbw, dstage, dm, dms, dau, dav, dtr;
+    SFA_TRY(dfw.alloc(ctx, np * pl * tap)); SFA_TRY(dbw.alloc(ctx, np * pl * tap)); SFA_TRY(dstage.alloc(ctx, np * spl * 8));
     if (masks) SFA_TRY(dm.alloc(ctx, np * pl));
+    if (masks && raw_occ) SFA_TRY(dms.alloc(ctx, np * (size_t)src->sw * src->sh));
     const size_t gpl = (size_t)gw * gh;
     SFA_TRY(dau.alloc(ctx, (size_t)n * S * gpl * 8)); SFA_TRY(dav.alloc(ctx, (size_t)n * S * gpl * 8)); SFA_TRY(dtr.alloc(ctx, (size_t)n * gpl * 4));
-    float *su = dstage.f(), *sv = dstage.f() + np * pl;
+    hipEvent_t ev[6] = {};                                                      // around the forward and the backward flows' kernel and k_accumulate
+    if (stage_ms)
+        for (auto &e : ev) SFA_HIP(ctx, hipEventCreate(&e));
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 6; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    float *su = dstage.f(), *sv = dstage.f() + np * spl;
     const int iblocks = (int)std::min<size_t>((np * pl + kAccThreads - 1) / kAccThreads, (size_t)ctx->cu_count * 8);
-    for (int dir = 0; dir < 2; dir++) {                                         // the valid columns of each plane, packed, then interleaved
+    for (int dir = 0; dir < 2; dir++) {
         const float *const *U = dir ? bwd_u : fwd_u, *const *V = dir ? bwd_v : fwd_v;
-        for (size_t k = 0; k < np; k++) {
+        if (!identity) {
+            SFA_TRY(jet_resample_flows(ctx, *src, np, U, V, w, h, dstage.f(), static_cast<double2 *>(dir ? dbw.p : dfw.p), ev[2 * dir], ev[2 * dir + 1]));
+            continue;
+        }
+        for (size_t k = 0; k < np; k++) {                                       // the valid columns of each plane, packed, then interleaved
             SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)w * 4, U[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
             SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, V[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
         }
+        if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[2 * dir], ctx->stream));
         hipLaunchKernelGGL(k_interleave, dim3(iblocks), dim3(kAccThreads), 0, ctx->stream, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), np * pl);
+        if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[2 * dir + 1], ctx->stream));
     }
-    if (masks)
+    if (masks && raw_occ)
+        SFA_TRY(jet_decode_occlusions(ctx, *src, np, masks, w, h, static_cast<unsigned char *>(dms.p), static_cast<unsigned char *>(dm.p)));
+    else if (masks)
         for (size_t k = 0; k < np; k++)
             SFA_HIP(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dm.p) + k * pl, (size_t)w, masks[k], (size_t)stride, (size_t)w, h, hipMemcpyHostToDevice,
                                           ctx->stream));
     const int xy_incr = skip + 1, xy_start = (int)(0.5f * skip);
-    hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((gpl + kAccThreads - 1) / kAccThreads), (unsigned)n), dim3(kAccThreads), 0, ctx->stream,
-                       static_cast<const float2 *>(dfw.p), static_cast<const float2 *>(dbw.p), masks ? static_cast<const unsigned char *>(dm.p) : nullptr, FF, w, h, gw,
-                       gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, static_cast<double *>(dau.p), static_cast<double *>(dav.p),
-                       static_cast<int *>(dtr.p));
+    const dim3 grid((unsigned)((gpl + kAccThreads - 1) / kAccThreads), (unsigned)n);
+    const unsigned char *dmp = masks ? static_cast<const unsigned char *>(dm.p) : nullptr;
+    double *pau = static_cast<double *>(dau.p), *pav = static_cast<double *>(dav.p);
+    if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[4], ctx->stream));
+    if (identity)
+        hipLaunchKernelGGL(k_accumulate<float2>, grid, dim3(kAccThreads), 0, ctx->stream, static_cast<const float2 *>(dfw.p), static_cast<const float2 *>(dbw.p), dmp, FF,
+                           w, h, gw, gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, pau, pav, static_cast<int *>(dtr.p));
+    else
+        hipLaunchKernelGGL(k_accumulate<double2>, grid, dim3(kAccThreads), 0, ctx->stream, static_cast<const double2 *>(dfw.p), static_cast<const double2 *>(dbw.p), dmp,
+                           FF, w, h, gw, gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, pau, pav, static_cast<int *>(dtr.p));
     SFA_HIP(ctx, hipGetLastError());
+    if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[5], ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(acc_u, dau.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(acc_v, dav.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(tracked, dtr.p, (size_t)n * gpl * 4, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stage_ms) {
+        float fw_ms = 0, bw_ms = 0;
+        SFA_HIP(ctx, hipEventElapsedTime(&fw_ms, ev[0], ev[1]));
+        SFA_HIP(ctx, hipEventElapsedTime(&bw_ms, ev[2], ev[3]));
+        SFA_HIP(ctx, hipEventElapsedTime(&stage_ms[1], ev[4], ev[5]));
+        stage_ms[0] = fw_ms + bw_ms;
+    }
     return SFA_OK;
+}
+
+int sfa_accumulate_consistent(sfa_ctx *ctx, int n, int FF, int w, int h, int stride, const float *const *fwd_u, const float *const *fwd_v,
+                              const float *const *bwd_u, const float *const *bwd_v, const unsigned char *const *masks, double epsilon, int skip, int discard,
+                              int all_steps, double *acc_u, double *acc_v, int *tracked) {
+    sfa_jet_source src;
+    sfa_jet_source_default(&src, w, h, stride);
+    return accumulate_run(ctx, __func__, n, FF, w, h, &src, fwd_u, fwd_v, bwd_u, bwd_v, masks, false, epsilon, skip, discard, all_steps, acc_u, acc_v, tracked, nullptr);
+}
+
+int sfa_accumulate_consistent_scaled(sfa_ctx *ctx, int n, int FF, int w, int h, const sfa_jet_source *src, const float *const *fwd_u,
+                                     const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v, const unsigned char *const *occ,
+                                     double epsilon, int skip, int discard, int all_steps, double *acc_u, double *acc_v, int *tracked, float *stage_ms) {
+    if (!src) return set_error(ctx, SFA_ERR_ARG, "%s: null source", __func__);
+    return accumulate_run(ctx, __func__, n, FF, w, h, src, fwd_u, fwd_v, bwd_u, bwd_v, occ, true, epsilon, skip, discard, all_steps, acc_u, acc_v, tracked, stage_ms);
 }

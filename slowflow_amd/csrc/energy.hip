@@ -12,7 +12,7 @@
 //   - params.Jets in addJC / addBCGC / addOC is the segment's Jets (:564-568): every hypothesis has Jets steps after adaptFPS(Jets).
 //
 // Shape, three launches per call (n segments = blockIdx.y):
-//   k_hyp_serial   one thread per grid pixel: adaptFPS, setOcclusions, addJC and addOC, serial over the Jets steps (6 flow gathers per step, float2 taps);
+//   k_hyp_serial   one thread per grid pixel: adaptFPS, setOcclusions, addJC and addOC, serial over the Jets steps (6 flow gathers per step, float2 / double2 taps);
 //                  writes the adapted flows, the occlusion bits and the two float terms.
 //   k_hyp_bcgc     one thread per (hypothesis, neighbour) -- the (2r+1)^2 neighbours are independent until they are summed: the thread gathers its
 //                  Jets + 1 frames x 9 values (I, dx, dy of c3, c2, c1) once into LDS, 9 (Jets + 1) doubles per lane laid out [value][frame][lane]
@@ -78,9 +78,11 @@ __global__ void __launch_bounds__(kEnThreads) k_energy_records(const float *__re
 }
 
 // adaptFPS + setOcclusions + addJC + addOC of the hypothesis at grid pixel i of segment blockIdx.y.  acc_u, acc_v: [n][r_Jets][gpl] (all_steps layout);
-// fwd, bwd: [n][J] float2 planes or null (the empty Mats of a rate processed before acc_min_fps: fw = fh = 0).  U, V: [n][gpl][J] adapted flows.
+// fwd, bwd: [n][J] planes of pairs or null (the empty Mats of a rate processed before acc_min_fps: fw = fh = 0).  U, V: [n][gpl][J] adapted flows.
+// T2 = float2: the flows as read; T2 = double2: flows resampled from jets of another size (jet_resample.hip).
+template <class T2>
 __global__ void __launch_bounds__(kEnThreads) k_hyp_serial(const double *__restrict__ acc_u, const double *__restrict__ acc_v, const int *__restrict__ tracked,
-                                                           const float2 *__restrict__ fwd, const float2 *__restrict__ bwd, int rJ, int J, int w, int h, int gw, int gpl,
+                                                           const T2 *__restrict__ fwd, const T2 *__restrict__ bwd, int rJ, int J, int w, int h, int gw, int gpl,
                                                            int incr, int start, AdaptTab tab, EnergyArgs a, double *__restrict__ U, double *__restrict__ V,
                                                            unsigned long long *__restrict__ occ_out, float *__restrict__ jc_out, float *__restrict__ oc_out) {
     const int i = blockIdx.x * kEnThreads + threadIdx.x;
@@ -106,7 +108,7 @@ __global__ void __launch_bounds__(kEnThreads) k_hyp_serial(const double *__restr
     }
     // ---- setOcclusions (hypothesis.cpp:172-215); the bounds are forward_flow[t].rows / .cols, 0 for an empty Mat
     const int fw = fwd ? w : 0, fh = fwd ? h : 0;
-    const float2 *F = fwd ? fwd + (size_t)s * J * pl : nullptr, *B = bwd ? bwd + (size_t)s * J * pl : nullptr;
+    const T2 *F = fwd ? fwd + (size_t)s * J * pl : nullptr, *B = bwd ? bwd + (size_t)s * J * pl : nullptr;
     unsigned long long occ = 0;                                                 // bit 0: always visible in the reference frame (:176)
     for (int t = 0; t < J; t++) {
         if ((occ >> t) & 1ull) { occ |= 1ull << (t + 1); continue; }           // :180-183, occluded stays occluded
@@ -324,6 +326,16 @@ int sfa_hypothesis_energies_ex(sfa_ctx *ctx, const sfa_energy_params *p, int n, 
                                const double *acc_v, const int *tracked, const float *const *frames, const float *const *fwd_u, const float *const *fwd_v,
                                const float *const *bwd_u, const float *const *bwd_v, double *energy, unsigned long long *occ_bits, double *adapted_u,
                                double *adapted_v) {
+    sfa_jet_source src;
+    sfa_jet_source_default(&src, w, h, stride);
+    return sfa_hypothesis_energies_scaled(ctx, p, n, r_Jets, Jets, w, h, stride, acc_u, acc_v, tracked, frames, &src, fwd_u, fwd_v, bwd_u, bwd_v, energy, occ_bits,
+                                          adapted_u, adapted_v);
+}
+
+int sfa_hypothesis_energies_scaled(sfa_ctx *ctx, const sfa_energy_params *p, int n, int r_Jets, int Jets, int w, int h, int stride, const double *acc_u,
+                                   const double *acc_v, const int *tracked, const float *const *frames, const sfa_jet_source *flow_src,
+                                   const float *const *fwd_u, const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v,
+                                   double *energy, unsigned long long *occ_bits, double *adapted_u, double *adapted_v) {
     if (!(ctx && p && acc_u && acc_v && tracked && frames && energy && occ_bits)) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: null argument");
     if ((adapted_u != nullptr) != (adapted_v != nullptr)) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies_ex: adapted_u and adapted_v are both given or both null");
     const bool flows = fwd_u != nullptr;
@@ -334,6 +346,8 @@ int sfa_hypothesis_energies_ex(sfa_ctx *ctx, const sfa_energy_params *p, int n, 
                          kEnMaxJets);
     if (h < 4)   // convolve_vert_fast_5 (image.c:425-458) runs its middle-row loop from height - 3 down through zero: undefined below 4 rows
         return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: h = %d; the reference's vertical 5-tap derivative needs h >= 4", h);
+    bool identity = true;                                                       // the flows are w x h float planes of the frames' stride
+    if (flows) SFA_TRY(jet_source_check(ctx, "sfa_hypothesis_energies: flow_src", flow_src, w, h, &identity));
     int gw, gh;
     if (sfa_accumulate_grid(w, h, p->skip, &gw, &gh) != SFA_OK) return set_error(ctx, SFA_ERR_ARG, "%s", sfa_last_error(nullptr));
     // adaptFPS's indices in its own float arithmetic (hypothesis.h:139-171), each checked against the F = r_Jets flows it reads
@@ -390,13 +404,19 @@ int sfa_hypothesis_energies_ex(sfa_ctx *ctx, const sfa_energy_params *p, int n, 
     hipLaunchKernelGGL(k_energy_records, dim3((unsigned)std::min<size_t>((nf * pl + kEnThreads - 1) / kEnThreads, blocks_cap)), dim3(kEnThreads), 0, ctx->stream,
                        dfr.f(), ddx, ddy, static_cast<float4 *>(drec.p), pl, nf * pl);
     if (flows) {
-        SFA_TRY(dfw.alloc(ctx, nj * pl * 8)); SFA_TRY(dbw.alloc(ctx, nj * pl * 8)); SFA_TRY(dstage.alloc(ctx, nj * pl * 8));
+        const size_t tap = identity ? 8 : 16, spl = identity ? pl : (size_t)flow_src->cw * flow_src->ch;   // float2 or double2
+        const int fstride = flow_src->stride;
+        SFA_TRY(dfw.alloc(ctx, nj * pl * tap)); SFA_TRY(dbw.alloc(ctx, nj * pl * tap)); SFA_TRY(dstage.alloc(ctx, nj * spl * 8));
         float *su = dstage.f(), *sv = dstage.f() + nj * pl;
         for (int dir = 0; dir < 2; dir++) {
             const float *const *Uh = dir ? bwd_u : fwd_u, *const *Vh = dir ? bwd_v : fwd_v;
+            if (!identity) {                                                    // r_forward_flow: resized and multiplied by rescale (:1142-1151)
+                SFA_TRY(jet_resample_flows(ctx, *flow_src, nj, Uh, Vh, w, h, dstage.f(), static_cast<double2 *>(dir ? dbw.p : dfw.p), nullptr, nullptr));
+                continue;
+            }
             for (size_t k = 0; k < nj; k++) {
-                SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)w * 4, Uh[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-                SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, Vh[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
+                SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)w * 4, Uh[k], (size_t)fstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
+                SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, Vh[k], (size_t)fstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
             }
             hipLaunchKernelGGL(k_energy_interleave, dim3((unsigned)std::min<size_t>((nj * pl + kEnThreads - 1) / kEnThreads, blocks_cap)), dim3(kEnThreads), 0,
                                ctx->stream, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), nj * pl);
@@ -410,9 +430,14 @@ int sfa_hypothesis_energies_ex(sfa_ctx *ctx, const sfa_energy_params *p, int n, 
     double *dUp = static_cast<double *>(dU.p), *dVp = static_cast<double *>(dV.p);
     unsigned long long *doccp = static_cast<unsigned long long *>(docc.p);
     const dim3 pix((unsigned)((gpl + kEnThreads - 1) / kEnThreads), (unsigned)n);
-    hipLaunchKernelGGL(k_hyp_serial, pix, dim3(kEnThreads), 0, ctx->stream, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), dt,
-                       flows ? static_cast<const float2 *>(dfw.p) : nullptr, flows ? static_cast<const float2 *>(dbw.p) : nullptr, r_Jets, Jets, w, h, gw, (int)gpl,
-                       incr, start, tab, a, dUp, dVp, doccp, djc.f(), doc.f());
+    if (identity)
+        hipLaunchKernelGGL(k_hyp_serial<float2>, pix, dim3(kEnThreads), 0, ctx->stream, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), dt,
+                           flows ? static_cast<const float2 *>(dfw.p) : nullptr, flows ? static_cast<const float2 *>(dbw.p) : nullptr, r_Jets, Jets, w, h, gw,
+                           (int)gpl, incr, start, tab, a, dUp, dVp, doccp, djc.f(), doc.f());
+    else
+        hipLaunchKernelGGL(k_hyp_serial<double2>, pix, dim3(kEnThreads), 0, ctx->stream, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), dt,
+                           static_cast<const double2 *>(dfw.p), static_cast<const double2 *>(dbw.p), r_Jets, Jets, w, h, gw, (int)gpl, incr, start, tab, a, dUp, dVp,
+                           doccp, djc.f(), doc.f());
     SFA_HIP(ctx, hipGetLastError());
     const double bcw = a.acc_bc * 0.3334, gcw = a.acc_gc * 0.3334;              // acc_bc * 0.3334 * (...) groups left to right (:318-319)
     hipLaunchKernelGGL(k_hyp_bcgc, dim3((unsigned)((gpl * NN + kBcThreads - 1) / kBcThreads), (unsigned)n), dim3(kBcThreads), lds, ctx->stream,

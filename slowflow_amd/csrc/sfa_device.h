@@ -85,16 +85,18 @@ struct PlaneAcc {
     __device__ __forceinline__ float operator()(int x, int y) const { return p[(size_t)y * pitch + x]; }
 };
 
-// bilinearInterp<double>(x, y, fct, c) (utils.h:182-217) for both channels of one float2 plane (.x = u, .y = v), w x h packed (accumulate.hip, energy.hip).
-// The caller has checked 0 <= x < w and 0 <= y < h (utils.h:189-190 would throw otherwise).  Widening fp32 to double is exact: readGTMiddlebury's CV_64FC2 (utils.cpp:365).
-__device__ __forceinline__ void bilinear2(const float2 *__restrict__ p, int w, int h, double x, double y, double &ru, double &rv) {
+// bilinearInterp<double>(x, y, fct, c) (utils.h:182-217) for both channels of one plane of pairs (.x = u, .y = v), w x h packed (accumulate.hip, energy.hip).
+// The caller has checked 0 <= x < w and 0 <= y < h (utils.h:189-190 would throw otherwise).  T2 = float2: the flows as read, and widening fp32 to double is
+// exact (readGTMiddlebury's CV_64FC2, utils.cpp:365); T2 = double2: flows resampled from jets of another size (jet_resample.hip).
+template <class T2>
+__device__ __forceinline__ void bilinear2(const T2 *__restrict__ p, int w, int h, double x, double y, double &ru, double &rv) {
     const int y0 = (int)y, x0 = (int)x;                                          // :192-193, truncation of a non-negative double
     int y1 = y0, x1 = x0;                                                       // :194-195
     double wx = 0, wy = 0;                                                      // quirk: the weight is 0 on the last column and row (:198-209)
     if (x0 + 1 < w) { wx = x - x0; x1++; }
     if (y0 + 1 < h) { wy = y - y0; y1++; }
-    const float2 a = p[(size_t)y0 * w + x0], b = p[(size_t)y0 * w + x1];        // :211-214
-    const float2 c = p[(size_t)y1 * w + x0], d = p[(size_t)y1 * w + x1];
+    const T2 a = p[(size_t)y0 * w + x0], b = p[(size_t)y0 * w + x1];            // :211-214
+    const T2 c = p[(size_t)y1 * w + x0], d = p[(size_t)y1 * w + x1];
     // :216, left to right: ((1-wy)(1-wx) f00 + (1-wy) wx f10) + wy (1-wx) f01 + wy wx f11, every product and sum rounded on its own
     ru = (1 - wy) * (1 - wx) * (double)a.x + (1 - wy) * wx * (double)b.x + wy * (1 - wx) * (double)c.x + wy * wx * (double)d.x;
     rv = (1 - wy) * (1 - wx) * (double)a.y + (1 - wy) * wx * (double)b.y + wy * (1 - wx) * (double)c.y + wy * wx * (double)d.y;

@@ -186,6 +186,16 @@ struct DevMem {
 int upload_plane(sfa_ctx *ctx, float *dev, int pitch, const float *host, int stride, int w, int h);
 int download_plane(sfa_ctx *ctx, float *host, int stride, const float *dev, int pitch, int w, int h);
 
+// jets of another size than the tracking frames (jet_resample.hip).  All three enqueue on the context's stream and return without waiting.
+// *identity: no crop, the target's size, rescale 1 -- such a source is not resampled by accumulate.hip and energy.hip.  fn names the entry point.
+int jet_source_check(sfa_ctx *ctx, const char *fn, const sfa_jet_source *src, int w, int h, bool *identity);
+// np fields u[k], v[k] -> out: np double2 planes of w x h (.x = u, .y = v).  stage: 2 * np * cw * ch floats, free again once the stream has passed.
+// before, after: null, or events recorded around the kernel (after the uploads)
+int jet_resample_flows(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const float *const *u, const float *const *v, int w, int h, float *stage, double2 *out,
+                       hipEvent_t before, hipEvent_t after);
+// np raw occlusion images -> out: np packed w x h masks (0 = occluded).  stage: np * sw * sh bytes
+int jet_decode_occlusions(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const unsigned char *const *occ, int w, int h, unsigned char *stage, unsigned char *out);
+
 // ---------------------------------------------------------------------------------------------------
 // kernel launchers (kernels.hip).  All planes are device pointers of batch element 0; element b lives
 // `es` floats further (es = 0 for a single element).  `nb` = batch size, `active` = bit mask of the

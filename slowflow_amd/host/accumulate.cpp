@@ -20,8 +20,13 @@
 //   <output>/accumulated/occlusions/frame_<sequence_start>.pgm    max_t occluded(t) of the chosen hypothesis, 0 / 255
 //   <output>/accumulated/labels_<sequence_start>.pgm              the chosen rate (255: none)
 //
-// Out of scope (FLANN, GSL, OpenCV are not in this tree): EpicFlow's fill-in and the neighbour proposals, removeSmallSegments, cropping and the
-// rescaling of flows of another size (:1131-1146; such flows are refused).
+// Jets of another size than the tracking frames (slow_flow.cfg estimates at scale 0.25, dense_tracking.cfg tracks at scale 1.0) are cropped (center /
+// extent, utils.cpp:308-318), resized by rescale = (1.0f * W) / cw and multiplied by it on the GPU, their occlusion images resized with the cubic
+// (:1134-1146, :1171-1189; sfa_accumulate_consistent_scaled, sfa_hypothesis_energies_scaled).  The target W x H is the ingested frames' size with
+// -energies / -fuse (after center / extent and scale); in the plain mode the jets' common size, or, where the rates differ, the size of the ingested
+// frame at sequence_start.  Refused: a rate whose rescaled size is not the target, a crop outside a flow, occlusions together with center.
+//
+// Out of scope (FLANN, GSL, OpenCV are not in this tree): EpicFlow's fill-in and the neighbour proposals, removeSmallSegments.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -52,15 +57,19 @@ static void usage() {
     printf("\n");
     printf("Runs dense_tracking's first stage only: consistent accumulation of the jets (accumulateConsistentBatches).  cfg keys read: jet_estimation\n");
     printf("(repeated), jet_S, jet_fps, jet_weight, flow_format, start, ref_fps, ref_fps_F, max_fps, acc_min_fps, acc_skip_pixel, acc_use_jet_occlusions\n");
-    printf("(or acc_occlusion), acc_discard_inconsistent, acc_consistency_threshold, output, sintel, subframes.  Not done: flows of a size other than\n");
-    printf("the first flow's are refused (no rescaling), and the TRW-S fusion, EpicFlow fill-in and removeSmallSegments are left out.\n");
-    printf("A missing input file exits with status 2.\n");
+    printf("(or acc_occlusion), acc_discard_inconsistent, acc_consistency_threshold, output, sintel, subframes, center, extent.  Not done: EpicFlow's\n");
+    printf("fill-in and removeSmallSegments.  A missing input file exits with status 2.\n");
+    printf("\n");
+    printf("Jets of another size than the target are cropped (center / extent), resized by (1.0f * W) / cw and multiplied by it on the GPU, as dense_tracking\n");
+    printf("does.  The target W x H: with -energies / -fuse the ingested frames' size; else the jets' common size, or where the rates differ the size of the\n");
+    printf("frame at `start` (cfg `file`, scale, center / extent).  Refused: a rate whose rescaled size is not the target, a crop outside a flow,\n");
+    printf("occlusions together with center.\n");
     printf("\n");
     printf("-energies: also reads the Jets + 1 frames of each start_jet (cfg `file`, the driver's ingest: scale, raw, raw_demosaicing 0 / 2), normalises\n");
     printf("them and writes each hypothesis' unary energy (energy_<start>.pfm), its occluded frames (occluded_<start>.pgm) and the lowest-energy rate\n");
     printf("(best_<start>.pgm).  Keys: acc_jet_consistency, acc_brightness_constancy, acc_gradient_constancy, acc_occlusion_penalty, acc_temporal_occ,\n");
     printf("acc_cv, acc_occlusion_threshold, acc_occlusion_fb_threshold, acc_penalty_fct_data, acc_penalty_fct_data_eps.  Refused: acc_occlusion 1,\n");
-    printf("grayscale 1, raw_demosaicing 1, center / extent, Jets > 32.\n");
+    printf("grayscale 1, raw_demosaicing 1, Jets > 32.\n");
     printf("\n");
     printf("-fuse: implies -energies, then fuses all rates of each start_jet with TRW-S (raster order) into <flow_format %% start>.flo, _vis.png,\n");
     printf("occlusions/frame_<start>.pgm and labels_<start>.pgm.  Keys: acc_beta, acc_spatial_occ, acc_traj_sim_method, acc_traj_sim_thres, acc_trws_eps,\n");
@@ -98,6 +107,9 @@ struct Run {
     bool discard = true, use_occ = false, sintel = false;
     bool energies = false, fuse = false;     // -energies, -fuse (implies -energies)
     string flow_format, acc_dir;             // flow_format without its extension; <output>/accumulated/
+    bool crop_flows = false, crop_frames = false;   // center.x > 0 (:1135); extent.x > 0 || extent.y > 0 (:876)
+    int cx = 0, cy = 0, ex = 0, ey = 0;      // center, extent
+    string size_frame;                       // the plain mode with rates of different sizes: the frame whose ingested size is the target
 };
 
 struct Segment {
@@ -120,35 +132,87 @@ static string fused_base(const Run &run, unsigned seq_start) {
     return run.acc_dir + (run.sintel ? fmt2(run.flow_format, (int)seq_start, 0) : fmt1(run.flow_format, (int)seq_start));
 }
 
-// segments' flows (and masks) read into host images, appended to `in`; false with a message on failure
+// the size in a .flo's header; false where the file is none
+static bool flo_size(const string &file, int &w, int &h) {
+    FILE *f = fopen(file.c_str(), "rb");
+    if (!f) return false;
+    float tag = 0;
+    int wh[2] = {0, 0};
+    const bool ok = fread(&tag, 4, 1, f) == 1 && fread(wh, 4, 2, f) == 2 && tag == 202021.25f && wh[0] >= 1 && wh[1] >= 1;
+    fclose(f);
+    w = wh[0]; h = wh[1];
+    return ok;
+}
+
+// where each rate's files sit relative to the target: the size of the rate's first flow and the crop of utils.cpp:308-318 (center.x > 0, :1135).
+// rescale and stride are filled later (fit_rates, read_segment).  1 with a message where a file is no .flo or the crop leaves the flow
+static int read_geometry(const Run &run, const vector<Segment> &segs, vector<sfa_jet_source> &geo) {
+    geo.assign(run.rates, sfa_jet_source{0, 0, 0, 0, 0, 0, 0, 1.0f});
+    for (const Segment &s : segs) {
+        sfa_jet_source &g = geo[s.r];
+        if (g.sw) continue;
+        if (!flo_size(s.fwd[0], g.sw, g.sh)) { std::cerr << "cannot read " << s.fwd[0] << " as a .flo" << std::endl; return 1; }
+        g.cw = g.sw; g.ch = g.sh;
+        if (!run.crop_flows) continue;
+        g.x0 = run.cx - run.ex / 2; g.y0 = run.cy - run.ey / 2; g.cw = run.ex; g.ch = run.ey;   // off = x - extent / 2 + center
+        if (g.x0 < 0 || g.y0 < 0 || g.cw < 1 || g.ch < 1 || g.x0 + g.cw > g.sw || g.y0 + g.ch > g.sh) {
+            std::cerr << "center " << run.cx << "," << run.cy << " / extent " << run.ex << "," << run.ey << ": the crop leaves the " << g.sw << " x " << g.sh
+                      << " flows of rate " << s.r << " (" << s.fwd[0] << "); the reference reads outside its Mat there" << std::endl;
+            return 1;
+        }
+    }
+    return 0;
+}
+
+// rescale = (1.0f * W) / cw per rate (:1142); false with a message where a rate's rescaled size, cvRound(cw * rescale) x cvRound(ch * rescale), is not W x H
+static bool fit_rates(vector<sfa_jet_source> &geo, int W, int H) {
+    for (size_t r = 0; r < geo.size(); r++) {
+        sfa_jet_source &g = geo[r];
+        if (!g.sw) continue;                                              // no segment of this rate
+        g.rescale = (1.0f * W) / g.cw;
+        const long tw = lrint((double)g.cw * (double)g.rescale), th = lrint((double)g.ch * (double)g.rescale);
+        if (tw != W || th != H) {
+            std::cerr << "rate " << r << ": its " << g.cw << " x " << g.ch << " flows rescaled by " << g.rescale << " are " << tw << " x " << th << ", not the target "
+                      << W << " x " << H << std::endl;
+            return false;
+        }
+    }
+    return true;
+}
+
+static bool same_geometry(const sfa_jet_source &a, const sfa_jet_source &b) {
+    return a.sw == b.sw && a.sh == b.sh && a.x0 == b.x0 && a.y0 == b.y0 && a.cw == b.cw && a.ch == b.ch;
+}
+
+// segments' flows (and raw occlusion images) read into host images, appended to `in`; false with a message on failure
 struct SegmentInput {
     vector<image_t **> fl;                                                // forward, backward per step
     vector<const float *> fu, fv, bu, bv;
-    vector<vector<unsigned char>> mbuf;
+    vector<vector<unsigned char>> mbuf;                                   // the occlusion images as read, rows of the flows' stride
     vector<const unsigned char *> mp;
     ~SegmentInput() { for (image_t **c : fl) { image_delete(c[0]); image_delete(c[1]); free(c); } }
 };
-static bool read_segment(const Segment &s, bool use_occ, int &width, int &height, SegmentInput &in) {
+static bool read_segment(const Segment &s, bool use_occ, sfa_jet_source &g, SegmentInput &in) {
     for (int f = 0; f < s.FF; f++) {
         image_t **a = readFlowFile(s.fwd[f].c_str()), **b = readFlowFile(s.bwd[f].c_str());
         if (a) in.fl.push_back(a);
         if (b) in.fl.push_back(b);
         if (!a || !b) { std::cerr << "cannot read " << (a ? s.bwd[f] : s.fwd[f]) << " as a .flo" << std::endl; return false; }
-        if (width == 0) { width = a[0]->width; height = a[0]->height; }
         for (image_t **c : {a, b})
-            if (c[0]->width != width || c[0]->height != height) {
-                std::cerr << (c == a ? s.fwd[f] : s.bwd[f]) << " is " << c[0]->width << " x " << c[0]->height << ", not " << width << " x " << height
-                          << ": rescaling is not implemented" << std::endl;
+            if (c[0]->width != g.sw || c[0]->height != g.sh) {
+                std::cerr << (c == a ? s.fwd[f] : s.bwd[f]) << " is " << c[0]->width << " x " << c[0]->height << ", not " << g.sw << " x " << g.sh
+                          << " like the first flow of rate " << s.r << std::endl;
                 return false;
             }
+        g.stride = a[0]->stride;
         in.fu.push_back(a[0]->data); in.fv.push_back(a[1]->data); in.bu.push_back(b[0]->data); in.bv.push_back(b[1]->data);
         if (use_occ) {
             int ow, oh;
-            vector<unsigned char> g;
-            if (!read_pnm8(s.occ[f], ow, oh, g)) { std::cerr << s.occ[f] << ": not a binary PGM (maxval 255) or PBM" << std::endl; return false; }
-            if (ow != width || oh != height) { std::cerr << s.occ[f] << " is not " << width << " x " << height << std::endl; return false; }
-            in.mbuf.emplace_back((size_t)a[0]->stride * height, 0);
-            decode_occlusion(g, width, height, a[0]->stride, in.mbuf.back().data());
+            vector<unsigned char> px;
+            if (!read_pnm8(s.occ[f], ow, oh, px)) { std::cerr << s.occ[f] << ": not a binary PGM (maxval 255) or PBM" << std::endl; return false; }
+            if (ow != g.sw || oh != g.sh) { std::cerr << s.occ[f] << " is not " << g.sw << " x " << g.sh << std::endl; return false; }
+            in.mbuf.emplace_back((size_t)g.stride * g.sh, 0);
+            for (int y = 0; y < oh; y++) memcpy(in.mbuf.back().data() + (size_t)y * g.stride, px.data() + (size_t)y * ow, (size_t)ow);
         }
     }
     in.mp.clear();
@@ -156,8 +220,9 @@ static bool read_segment(const Segment &s, bool use_occ, int &width, int &height
     return true;
 }
 
-// one frame as dense_tracking ingests it (:793-905): decoded, demosaiced (raw_demosaicing 0 / 2) or taken as RGB, rescaled where scale != 1
-static color_image_t *ingest_frame(ParameterList &params, sfa_ctx *ctx, const string &name) {
+// one frame as dense_tracking ingests it (:793-905): decoded, demosaiced (raw_demosaicing 0 / 2) or taken as RGB, cropped (center / extent), rescaled
+// where scale != 1
+static color_image_t *ingest_frame(ParameterList &params, const Run &run, sfa_ctx *ctx, const string &name) {
     vector<int> red_loc;
     std::stringstream ss(params.parameter<string>("raw_red_loc", "0,0"));
     for (string t; std::getline(ss, t, ',');) red_loc.push_back(atoi(t.c_str()));
@@ -166,6 +231,13 @@ static color_image_t *ingest_frame(ParameterList &params, sfa_ctx *ctx, const st
     color_image_t *img = load_frame(name, params.exists("raw") && params.parameter<bool>("raw"), params.parameter<int>("raw_demosaicing", "0"),
                                     red_loc.size() > 0 ? red_loc[0] : 0, red_loc.size() > 1 ? red_loc[1] : 0, &maxval, &error);
     if (!img) { std::cerr << error << std::endl; return nullptr; }
+    if (run.crop_frames) {                                                // use only a part of the images, before the rescaling (:875-886)
+        color_image_t *part = color_image_crop(img, run.cx, run.cy, run.ex, run.ey);
+        if (!part) std::cerr << "center / extent do not fit the " << img->width << " x " << img->height << " frame " << name << std::endl;
+        color_image_delete(img);
+        if (!part) return nullptr;
+        img = part;
+    }
     const float scale = (float)params.parameter<double>("scale", "1.0");
     if (scale != 1) {                                                     // GaussianBlur + resize against aliasing (:863-868)
         color_image_t *small = color_image_rescale(ctx, img, scale);
@@ -200,7 +272,8 @@ static bool write_last_step(Segment &s, const double *u, const double *v, const 
 
 // run.json: the cfg's figures, the rates, the segments and the skipped outputs, then `tail` (the mode's own fields, each after ",\n  ").
 // -energies writes 17 digits, jet_weight as the float it scores with and each segment's hypotheses; the plain run the stream's defaults
-static bool write_run_json(const Run &run, const vector<Segment> &segs, const vector<string> &skipped, int width, int height, const string &tail) {
+static bool write_run_json(const Run &run, const vector<Segment> &segs, const vector<string> &skipped, const vector<sfa_jet_source> &geo, int width, int height,
+                           const string &tail) {
     std::ofstream js((run.acc_dir + "run.json").c_str());
     if (run.energies) js.precision(17);
     js << "{\n  \"cfg\": \"" << run.cfg << "\",\n  " << (run.energies ? "\"energies\": true, " : "") << "\"Jets\": " << run.Jets << ", \"steps\": "
@@ -209,7 +282,8 @@ static bool write_run_json(const Run &run, const vector<Segment> &segs, const ve
     for (unsigned r = 0; r < run.rates; r++) {
         const double weight = run.jet_weight.size() > r ? run.jet_weight[r] : (double)r;
         js << (r ? ", " : "") << "{\"jet_estimation\": \"" << run.jets[r] << "\", \"jet_S\": " << run.jet_S[r] << ", \"jet_fps\": " << run.jet_fps[r]
-           << ", \"jet_weight\": " << (run.energies ? (double)(float)weight : weight) << "}";
+           << ", \"jet_weight\": " << (run.energies ? (double)(float)weight : weight) << ", \"source_width\": " << geo[r].sw << ", \"source_height\": " << geo[r].sh
+           << ", \"rescale\": " << (double)geo[r].rescale << "}";
     }
     js << "],\n  \"segments\": [";
     for (size_t i = 0; i < segs.size(); i++) {
@@ -224,25 +298,44 @@ static bool write_run_json(const Run &run, const vector<Segment> &segs, const ve
     return js.good();
 }
 
-// the plain run: accumulateConsistentBatches for every segment, those that share FF in one call of up to 2 GiB of input planes
-static int run_accumulate(const Run &run, vector<Segment> &segs, const vector<string> &skipped) {
+// the plain run: accumulateConsistentBatches for every segment, those that share FF and the geometry of their files in one call of up to 2 GiB of
+// device planes.  The target is the jets' common size, or the ingested size of run.size_frame where the rates differ
+static int run_accumulate(ParameterList &params, const Run &run, vector<Segment> &segs, const vector<string> &skipped, vector<sfa_jet_source> &geo) {
     sfa_ctx *ctx = nullptr;
     if (!segs.empty() && !sfa_ok(nullptr, sfa_ctx_create(0, &ctx))) return 1;
     double t_read = 0, t_gpu = 0, t_write = 0;
     const double t0 = now_s();
     int width = 0, height = 0, calls = 0, status = 0;
-    std::map<int, vector<size_t>> by_ff;
-    for (size_t i = 0; i < segs.size(); i++) by_ff[segs[i].FF].push_back(i);
-    for (auto &grp : by_ff) {
-        const int FF = grp.first;
+    if (!run.size_frame.empty()) {
+        color_image_t *img = ingest_frame(params, run, ctx, run.size_frame);
+        if (!img) status = 1;
+        else { width = img->width; height = img->height; color_image_delete(img); }
+    } else if (!segs.empty()) {
+        width = geo[segs[0].r].cw; height = geo[segs[0].r].ch;
+    }
+    if (status == 0 && !segs.empty() && !fit_rates(geo, width, height)) status = 1;
+    std::map<std::pair<int, int>, vector<size_t>> groups;                 // (FF, the first rate of the same geometry)
+    for (size_t i = 0; i < segs.size(); i++) {
+        int gi = segs[i].r;
+        for (int r = 0; r < gi; r++)
+            if (geo[r].sw && same_geometry(geo[r], geo[gi])) { gi = r; break; }
+        groups[std::make_pair(segs[i].FF, gi)].push_back(i);
+    }
+    for (auto &grp : groups) {
+        if (status) break;
+        const int FF = grp.first.first;
         const vector<size_t> &idx = grp.second;
+        sfa_jet_source &g = geo[grp.first.second];
+        const bool identity = g.x0 == 0 && g.y0 == 0 && g.cw == g.sw && g.ch == g.sh && g.sw == width && g.sh == height;
         for (size_t lo = 0, hi; lo < idx.size() && status == 0; lo = hi) {
             double ta = now_s();
             SegmentInput in;                                              // [k * FF + f]: segment k's step f
             size_t bytes = 0;
             for (hi = lo; hi < idx.size() && status == 0 && (hi == lo || bytes < (size_t)2 << 30); hi++) {
-                if (!read_segment(segs[idx[hi]], run.use_occ, width, height, in)) status = 1;
-                bytes += (size_t)FF * width * height * 17;
+                if (!read_segment(segs[idx[hi]], run.use_occ, g, in)) status = 1;
+                // what the device holds per step: the planes as read (4 floats and a byte per source pixel) and, where they are resampled, two
+                // double2 planes of the target
+                bytes += (size_t)FF * ((size_t)g.sw * g.sh * 17 + (identity ? 0 : (size_t)width * height * 32));
             }
             double tb = now_s();
             t_read += tb - ta;
@@ -254,9 +347,9 @@ static int run_accumulate(const Run &run, vector<Segment> &segs, const vector<st
             vector<double> au(n * gpl), av(au.size());
             vector<int> tracked(au.size());
             calls++;
-            if (!sfa_ok(ctx, sfa_accumulate_consistent(ctx, n, FF, width, height, in.fl[0][0]->stride, in.fu.data(), in.fv.data(), in.bu.data(), in.bv.data(),
-                                                       run.use_occ ? in.mp.data() : nullptr, run.threshold, run.skip_pixel, run.discard, 0, au.data(), av.data(),
-                                                       tracked.data()))) { status = 1; break; }
+            if (!sfa_ok(ctx, sfa_accumulate_consistent_scaled(ctx, n, FF, width, height, &g, in.fu.data(), in.fv.data(), in.bu.data(), in.bv.data(),
+                                                              run.use_occ ? in.mp.data() : nullptr, run.threshold, run.skip_pixel, run.discard, 0, au.data(),
+                                                              av.data(), tracked.data(), nullptr))) { status = 1; break; }
             double tc = now_s();
             t_gpu += tc - tb;
             for (int k = 0; k < n && status == 0; k++) {
@@ -274,7 +367,7 @@ static int run_accumulate(const Run &run, vector<Segment> &segs, const vector<st
     std::ostringstream tail;
     tail << ",\n  \"calls\": " << calls << ",\n  \"timings_s\": {\"read\": " << t_read << ", \"gpu_call\": " << t_gpu << ", \"write\": " << t_write
          << ", \"total\": " << now_s() - t0 << "}";
-    const bool ok = write_run_json(run, segs, skipped, width, height, tail.str());
+    const bool ok = write_run_json(run, segs, skipped, geo, width, height, tail.str());
     std::cout << "wrote " << segs.size() << " segment(s) to " << run.acc_dir << std::endl;
     return ok ? 0 : 1;
 }
@@ -335,7 +428,7 @@ static bool fuse_start(sfa_ctx *ctx, const Run &run, Fusion &fz, const color_ima
 
 // -energies: per start_jet the frames, then for every rate in cfg order the accumulation (all steps) and the hypotheses' energies (:1100-1257)
 static int run_energies(ParameterList &params, const Run &run, vector<Segment> &segs, const vector<string> &skipped,
-                        const std::map<unsigned, vector<string>> &frame_files) {
+                        const std::map<unsigned, vector<string>> &frame_files, vector<sfa_jet_source> &geo) {
     sfa_energy_params ep;
     sfa_energy_params_default(&ep);                                       // setDefault (:118-165), in the types of :606-623 and :661-675
     ep.acc_jc = params.parameter<float>("acc_jet_consistency", "1.0");
@@ -376,24 +469,27 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
         vector<size_t> mine;                                              // this start_jet's segments, in rate order
         for (size_t i = 0; i < segs.size(); i++)
             if (segs[i].seq_start == seq_start) mine.push_back(i);
-        // rate acc_min_fps's flows: forward_flow / backward_flow of the reference (:1148-1151)
+        // the frames set the target size (sequence[0].cols, :1142); rate acc_min_fps's flows: forward_flow / backward_flow of the reference (:1148-1151)
         double ta = now_s();
-        SegmentInput minf;
-        size_t mi = mine.size();
-        for (size_t k = 0; k < mine.size(); k++)
-            if (segs[mine[k]].r == run.min_fps_idx) mi = k;
-        if (mi == mine.size() || !read_segment(segs[mine[mi]], false, width, height, minf)) { status = 1; break; }
         vector<color_image_t *> fr;
         for (const string &name : it->second) {
-            color_image_t *img = ingest_frame(params, ctx, name);
+            color_image_t *img = ingest_frame(params, run, ctx, name);
             if (!img) { status = 1; break; }
             fr.push_back(img);
+            if (fr.size() == 1 && width == 0) { width = img->width; height = img->height; }
             if (img->width != width || img->height != height) {
-                std::cerr << name << " is " << img->width << " x " << img->height << ", the flows " << width << " x " << height << std::endl;
+                std::cerr << name << " is " << img->width << " x " << img->height << ", not " << width << " x " << height << " like the first frame" << std::endl;
                 status = 1;
                 break;
             }
         }
+        if (status == 0 && !fit_rates(geo, width, height)) status = 1;
+        SegmentInput minf;
+        size_t mi = mine.size();
+        for (size_t k = 0; k < mine.size(); k++)
+            if (segs[mine[k]].r == run.min_fps_idx) mi = k;
+        sfa_jet_source &min_geo = geo[run.min_fps_idx];
+        if (status == 0 && (mi == mine.size() || !read_segment(segs[mine[mi]], false, min_geo, minf))) status = 1;
         const int stride = fr.empty() ? 0 : fr[0]->stride;
         vector<float *> fp;
         for (color_image_t *c : fr) fp.push_back(c->c1);
@@ -418,13 +514,12 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
             Segment &s = segs[mine[k]];
             double tb = now_s();
             SegmentInput in;
-            if (!read_segment(s, run.use_occ, width, height, in) || in.fu.empty()) { status = 1; break; }
-            if (in.fl[0][0]->stride != stride || minf.fl[0][0]->stride != stride) { std::cerr << "frames and flows differ in row stride" << std::endl; status = 1; break; }
+            if (!read_segment(s, run.use_occ, geo[s.r], in) || in.fu.empty()) { status = 1; break; }
             vector<double> au((size_t)s.FF * gpl), av(au.size());
             vector<int> tracked(gpl);
-            if (!sfa_ok(ctx, sfa_accumulate_consistent(ctx, 1, s.FF, width, height, stride, in.fu.data(), in.fv.data(), in.bu.data(), in.bv.data(),
-                                                       run.use_occ ? in.mp.data() : nullptr, run.threshold, run.skip_pixel, run.discard, 1, au.data(), av.data(),
-                                                       tracked.data()))) { status = 1; break; }
+            if (!sfa_ok(ctx, sfa_accumulate_consistent_scaled(ctx, 1, s.FF, width, height, &geo[s.r], in.fu.data(), in.fv.data(), in.bu.data(), in.bv.data(),
+                                                              run.use_occ ? in.mp.data() : nullptr, run.threshold, run.skip_pixel, run.discard, 1, au.data(),
+                                                              av.data(), tracked.data(), nullptr))) { status = 1; break; }
             double tc = now_s();
             t_acc += tc - tb;
             // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
@@ -432,10 +527,13 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
             ep.weight = run.jet_weight.size() > (size_t)s.r ? (float)run.jet_weight[s.r] : (float)s.r;   // weight_jet_estimation, vector<float> (:489-495)
             vector<double> energy(gpl);
             vector<unsigned long long> occ(gpl);
-            if (!sfa_ok(ctx, sfa_hypothesis_energies_ex(ctx, &ep, 1, s.FF, (int)Jets, width, height, stride, au.data(), av.data(), tracked.data(), cfp.data(),
-                                                        flows ? minf.fu.data() : nullptr, flows ? minf.fv.data() : nullptr, flows ? minf.bu.data() : nullptr,
-                                                        flows ? minf.bv.data() : nullptr, energy.data(), occ.data(), run.fuse ? fz.U.data() + k * Jets * gpl : nullptr,
-                                                        run.fuse ? fz.V.data() + k * Jets * gpl : nullptr))) { status = 1; break; }
+            if (!sfa_ok(ctx, sfa_hypothesis_energies_scaled(ctx, &ep, 1, s.FF, (int)Jets, width, height, stride, au.data(), av.data(), tracked.data(), cfp.data(),
+                                                            &min_geo, flows ? minf.fu.data() : nullptr, flows ? minf.fv.data() : nullptr,
+                                                            flows ? minf.bu.data() : nullptr, flows ? minf.bv.data() : nullptr, energy.data(), occ.data(),
+                                                            run.fuse ? fz.U.data() + k * Jets * gpl : nullptr, run.fuse ? fz.V.data() + k * Jets * gpl : nullptr))) {
+                status = 1;
+                break;
+            }
             double td = now_s();
             t_energy += td - tc;
             if (run.fuse) {
@@ -492,7 +590,7 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     tail << ",\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc << ", \"energy_call\": " << t_energy << ", \"write\": " << t_io;
     if (run.fuse) tail << ", \"fuse\": " << t_fuse;
     tail << ", \"total\": " << now_s() - t0 << "}";
-    const bool ok = write_run_json(run, segs, skipped, width, height, tail.str());
+    const bool ok = write_run_json(run, segs, skipped, geo, width, height, tail.str());
     std::cout << "wrote the energies of " << segs.size() << " segment(s) to " << run.acc_dir << std::endl;
     return ok ? 0 : 1;
 }
@@ -543,18 +641,26 @@ static int read_run(ParameterList &params, Run &run) {
     if (run.sintel && !params.parameter<bool>("subframes", "0")) run.sequence_start *= 1000;   // :716-717
     run.flow_format = params.parameter<string>("flow_format", "frame_%i");
     run.flow_format = run.flow_format.substr(0, run.flow_format.find_last_of('.'));   // :745-746
+    run.crop_flows = params.center.x > 0;                                // :1135
+    run.crop_frames = params.extent.x > 0 || params.extent.y > 0;        // :876
+    run.cx = params.center.x; run.cy = params.center.y; run.ex = params.extent.x; run.ey = params.extent.y;
     return 0;
 }
 
 // what -energies and -fuse do not support; 1 with a message
 static int refusal(ParameterList &params, const Run &run) {
+    if (run.use_occ && run.crop_flows) {
+        // crop() reads its argument through at<Vec2d> (utils.cpp:314): on the 8-bit occlusion Mat that is undefined in the reference
+        std::cerr << "the jets' occlusions (acc_use_jet_occlusions / acc_occlusion) together with center are not supported: the reference's crop() reads "
+                     "the 8-bit image as pairs of doubles" << std::endl;
+        return 1;
+    }
     if (run.energies) {
         // acc_occlusion 1 makes addBCGC read occlusion_masks[Jets], one past the Mat[Jets] array (:784, :289): undefined in the reference
         const char *refused = params.parameter<bool>("acc_occlusion", "0") ? "acc_occlusion 1 (addBCGC reads occlusion_masks[Jets], past the array)"
                               : params.parameter<bool>("grayscale", "0") ? "grayscale 1"
                               : (params.exists("raw") && params.parameter<bool>("raw") && params.parameter<int>("raw_demosaicing", "0") == 1)
                                   ? "raw_demosaicing 1 (Hamilton-Adams, third-party, not here)"
-                              : (params.extent.x > 0 || params.extent.y > 0 || params.center.x > 0) ? "cropping (center / extent)"
                               : run.Jets > 32 ? "Jets > 32" : nullptr;
         if (refused) { std::cerr << "-energies: " << refused << " is not supported" << std::endl; return 1; }
         if (params.file.empty()) { std::cerr << "-energies: `file` (the frames) missing from " << run.cfg << std::endl; return 1; }
@@ -689,7 +795,18 @@ int main(int argc, char **argv) {
     if (int status = build_segments(run, selected, selected_end ? selected_end : run.start_jets, segs, skipped)) return status;   // :722-723
     std::map<unsigned, vector<string>> frame_files;
     if (int status = check_inputs(params, run, segs, frame_files)) return status;
+    vector<sfa_jet_source> geo;
+    if (int status = read_geometry(run, segs, geo)) return status;
+    if (!run.energies) {                                                 // rates of different sizes: the frame at sequence_start gives the target
+        bool differ = false;
+        for (const Segment &s : segs) differ = differ || geo[s.r].cw != geo[segs[0].r].cw || geo[s.r].ch != geo[segs[0].r].ch;
+        if (differ) {
+            if (params.file.empty()) { std::cerr << "the jets differ in size and `file` (the frames, whose size they are brought to) is missing from " << run.cfg << std::endl; return 1; }
+            run.size_frame = sequence_frame_name(params.file, (int)run.sequence_start, 0, run.sintel);
+            if (!file_exists(run.size_frame)) { std::cerr << run.size_frame << " does not exist!" << std::endl; return 2; }
+        }
+    }
     mkdirs(run.acc_dir);
     for (unsigned r = 0; r < run.rates; r++) mkdirs(run.acc_dir + std::to_string(r) + "/");
-    return run.energies ? run_energies(params, run, segs, skipped, frame_files) : run_accumulate(run, segs, skipped);
+    return run.energies ? run_energies(params, run, segs, skipped, frame_files, geo) : run_accumulate(params, run, segs, skipped, geo);
 }
