@@ -240,6 +240,83 @@ void sfa_fuse_params_default(sfa_fuse_params *p);
 int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, const double *U, const double *V, const double *energy,
                         const unsigned long long *occ_bits, const float *weight, int *slot, double *flow_u, double *flow_v, unsigned char *occ,
                         double *seg_energy, double *seg_bound, int *seg_iters, float *stage_ms);
+/* ---- resident track jobs: dense_tracking's accumulation, energies and fusion of start_jets that stay in GPU memory (csrc/track.hip) -----------
+ * A track job owns the device planes of up to n start_jets (segments) x K rates: the flows in the kernels' layout, the frames and their records, the
+ * accumulated trajectories, the energies, adapted flows and occlusion words in the fusion's [n][K] layout, the MRF and the fused result.  It takes the
+ * inputs once, from host planes or from GPU memory, and sfa_track_job_run enqueues frame records -> accumulation (all steps) of every rate -> energies
+ * and adapted flows of every rate, best / occluded -> smoothness weight -> labels -> pairwise -> TRW-S -> output for segments 0 .. ns-1 on the context's
+ * stream and RETURNS WITHOUT WAITING: no stage reads or writes host memory, and TRW-S's stopping rule runs inside its kernel.  The stages are the
+ * launches of sfa_accumulate_consistent_scaled (all_steps), sfa_hypothesis_energies_scaled and sfa_fuse_hypotheses over the same planes, so segment s
+ * comes out with the bits of those calls on that segment alone, whatever n, ns and s.  Slot k of the fusion is rate k.
+ * The parameters: n start_jets of capacity (1 .. 64), K rates (1 .. 16), Jets (1 .. 32), the tracking frames' w x h (h >= 4), min_fps_idx (rates before
+ * it see no flows in their energies: every step t >= 1 occluded; r_Jets[min_fps_idx] must be Jets, its flows being the Jets steps the energies read),
+ * do_fuse (0: the job stops after the energies and holds no fused result), use_occlusions (the accumulation reads the rates' occlusion images); per rate
+ * r_Jets (its steps), source (where its jet planes sit, sfa_jet_source) and weight (weight_jet_estimation[r]); the accumulation's epsilon
+ * (acc_consistency_threshold), skip (acc_skip_pixel: the one grid of all stages; energy.skip and fuse.skip are ignored) and discard; the energies' keys
+ * (energy.weight is ignored) and the fusion's; the smoothness weight's coef, avg, std_dev, hbit (sfa_dt_smoothness_weight).
+ * sfa_track_params_default: n = K = Jets = 1, do_fuse 1, epsilon 1.0, skip 1, discard 1, r_Jets 1, weight[r] = r, coef 5, avg 0, std_dev 1 and the
+ * defaults of sfa_energy_params_default / sfa_fuse_params_default; the sources are left zero and must be set. */
+typedef struct sfa_track_params {
+    int n, K, Jets, w, h, min_fps_idx, do_fuse, use_occlusions;
+    int r_Jets[16];
+    sfa_jet_source source[16];
+    float weight[16];
+    double epsilon;
+    int skip, discard;
+    sfa_energy_params energy;
+    sfa_fuse_params fuse;
+    float coef, avg[3], std_dev[3];
+    int hbit;
+} sfa_track_params;
+void sfa_track_params_default(sfa_track_params *p);
+typedef struct sfa_track_job sfa_track_job;
+/* Host only: the device bytes a job of these parameters allocates (one allocation).  Refuses what sfa_track_job_create refuses. */
+int  sfa_track_job_bytes(const sfa_track_params *p, size_t *bytes);
+/* Allocates once.  Refused with SFA_ERR_ARG, naming the argument: everything the three stages refuse (K, Jets, h < 4, an empty grid, a source whose
+ * rescaled crop is not w x h, occlusions together with a crop, adaptFPS reading past a rate's steps, fuse.traj_sim_method 2, fuse.trws_max_iter < 1), n
+ * outside 1 .. 64, min_fps_idx outside the rates, r_Jets[min_fps_idx] != Jets. */
+int  sfa_track_job_create(sfa_ctx *ctx, const sfa_track_params *p, sfa_track_job **out);
+void sfa_track_job_destroy(sfa_track_job *job);
+/* The flows of rate r of segment s: r_Jets[r] host planes per array, as source[r] describes them (identity: packed and interleaved; else cropped, resized
+ * and multiplied by rescale on the GPU, as sfa_accumulate_consistent_scaled does it).  occ: the r_Jets[r] RAW 8-bit occlusion images (decoded on the GPU)
+ * on a job with use_occlusions, else ignored (NULL).  Waits for its copies. */
+int  sfa_track_job_upload_flows(sfa_track_job *job, int s, int r, const float *const *fwd_u, const float *const *fwd_v, const float *const *bwd_u,
+                                const float *const *bwd_v, const unsigned char *const *occ);
+/* The Jets + 1 normalised colour frames of segment s: frames[f] the first plane of 3 (c1, c2, c3, each h * stride floats), as sfa_hypothesis_energies
+ * takes them.  Waits for its copies. */
+int  sfa_track_job_upload_frames(sfa_track_job *job, int s, const float *const *frames, int stride);
+/* The same from GPU memory, for segments s0 .. s0+ns-1: fwd_dev, bwd_dev fp32 [ns][r_Jets[r]][2 (u, v)][sh][sw] and frames_dev fp32
+ * [ns][Jets+1][3][h][w], element (i0, .., i4) at p + sum i_k strides[k] (64-bit element strides, >= 0, the column stride >= 1).  Read in stream order on
+ * the context's stream and without a host wait: with sfa_ctx_wait_stream / sfa_ctx_signal_stream around them the caller needs none either.  A job with
+ * use_occlusions refuses the device flows by name (its occlusion images come with sfa_track_job_upload_flows).  Refused: memory that is not the
+ * context's GPU's, a view that leaves its allocation, segments outside the job. */
+int  sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r, const float *fwd_dev, const float *bwd_dev, const long long strides[5]);
+int  sfa_track_job_upload_frames_device(sfa_track_job *job, int s0, int ns, const float *frames_dev, const long long strides[5]);
+/* Tracks, scores and (do_fuse) fuses segments 0 .. ns-1 (1 <= ns <= n) from what the job holds and returns without waiting.  Everything a run reads that
+ * an earlier run wrote (the messages, the labellings, the per-segment records) is initialised again: a job serves any number of groups. */
+int  sfa_track_job_run(sfa_track_job *job, int ns);
+/* Rate r of segment s after a run, [gh][gw] each: the last accumulated step, tracked, the energy (+Inf: no hypothesis), the occlusion word and its
+ * popcount.  NULL skips an output.  Waits for the run. */
+int  sfa_track_job_download_rate(sfa_track_job *job, int s, int r, double *acc_u_last, double *acc_v_last, int *tracked, double *energy,
+                                 unsigned long long *occ_bits, unsigned char *occluded);
+/* The fused result of segment s, [gh][gw] each, as sfa_fuse_hypotheses returns it (slot = rate, -1 none), best = the rate of the lowest fp32 energy (ties
+ * to the lower rate, 255 none), and the segment's energy, bound and iterations.  NULL skips an output.  Waits for the run.  Refused on a job with
+ * do_fuse 0. */
+int  sfa_track_job_download_fused(sfa_track_job *job, int s, int *slot, double *flow_u, double *flow_v, unsigned char *occ, unsigned char *best,
+                                  double *energy, double *bound, int *iters);
+/* best [gh][gw] of segment s alone, also on a job with do_fuse 0.  Waits for the run. */
+int  sfa_track_job_download_best(sfa_track_job *job, int s, unsigned char *best);
+/* The bytes of device memory that are free on the context's GPU now (hipMemGetInfo): what the accumulate program sizes its track job by. */
+int  sfa_ctx_free_bytes(sfa_ctx *ctx, size_t *free_bytes);
+/* The fused results of segments s0 .. s0+ns-1 into GPU memory, in stream order and without a host wait: flow_dev fp64 [ns][2 (u, v)][gh][gw] at
+ * strides[4]; packed slot_dev int32 [ns][gh][gw], occ_dev uint8 [ns][gh][gw] and stats_dev fp64 [ns][3] (energy, bound, iterations), each or NULL.
+ * Refused: strides that let two elements of the flow share an address (a zero u|v stride ...), destinations that overlap one another. */
+int  sfa_track_job_download_device(sfa_track_job *job, int s0, int ns, double *flow_dev, const long long strides[4], int *slot_dev, unsigned char *occ_dev,
+                                   double *stats_dev);
+/* The last run's kernel times in ms (HIP events; waits for the run): frame derivatives and records, accumulation, energies (with best / occluded), smoothness
+ * weight (its kernel alone), labels, pairwise, TRW-S, output; the last five are 0 on a job with do_fuse 0.  Slot 0 is NOT a pack + resample time: the flows are packed
+ * and resampled by the uploads, outside the run. */
+int  sfa_track_job_stage_ms(sfa_track_job *job, float ms[8]);
 /* ---- resident pair jobs: the two-frame refinement of pairs that stay in GPU memory (csrc/two_frame.hip) -------------------------------
  * A pair job owns the planes of n pairs of one size (24 per pair: those of sfa_variational_2frame without its 24-plane derivative stack) and one solver
  * workspace, across any number of uploads and runs.  sfa_pair_job_run enqueues variational()'s launch sequence (variational.c:19-82) for all n pairs on the

@@ -117,6 +117,55 @@ def fuse_params(**kw):
     return p
 
 
+class TrackParams(C.Structure):
+    """sfa_track_params: a resident track job's shape, its rates and the keys of the three stages (include/slowflow_amd.h)"""
+    _fields_ = [("n", C.c_int), ("K", C.c_int), ("Jets", C.c_int), ("w", C.c_int), ("h", C.c_int), ("min_fps_idx", C.c_int), ("do_fuse", C.c_int),
+                ("use_occlusions", C.c_int), ("r_Jets", C.c_int * 16), ("source", JetSource * 16), ("weight", C.c_float * 16), ("epsilon", C.c_double),
+                ("skip", C.c_int), ("discard", C.c_int), ("energy", EnergyParams), ("fuse", FuseParams), ("coef", C.c_float), ("avg", C.c_float * 3),
+                ("std_dev", C.c_float * 3), ("hbit", C.c_int)]
+
+
+def track_params(w, h, Jets, r_Jets, n=1, sources=None, weights=None, energy=None, fuse=None, avg=None, std=None, **kw):
+    """sfa_track_params_default with the job's shape filled in: frames w x h, Jets, one entry of r_Jets per rate (K = len(r_Jets)), capacity n.
+    sources: None (every rate an identity source of w x h planes with row stride stride_of(w)) or one JetSource (or None) per rate; weights: None
+    (weight[r] = r) or one float per rate; energy / fuse: EnergyParams / FuseParams (their skip is ignored: the job's `skip` rules); avg, std: the
+    smoothness weight's img_norm_*; the other fields (min_fps_idx, do_fuse, use_occlusions, epsilon, skip, discard, coef, hbit) by keyword."""
+    p = TrackParams()
+    lib().sfa_track_params_default(C.byref(p))
+    K = len(r_Jets)
+    assert 1 <= K <= 16, "1 .. 16 rates"
+    p.n, p.K, p.Jets, p.w, p.h = int(n), K, int(Jets), int(w), int(h)
+    for r in range(K):
+        p.r_Jets[r] = int(r_Jets[r])
+        src = sources[r] if sources is not None and sources[r] is not None else jet_source(w, h, stride_of(w))
+        p.source[r] = src
+        if weights is not None:
+            p.weight[r] = float(weights[r])
+    if energy is not None:
+        p.energy = energy
+    if fuse is not None:
+        p.fuse = fuse
+    for k in range(3):
+        if avg is not None:
+            p.avg[k] = avg[k]
+        if std is not None:
+            p.std_dev[k] = std[k]
+    for k, v in kw.items():
+        assert k in ("min_fps_idx", "do_fuse", "use_occlusions", "epsilon", "skip", "discard", "coef", "hbit"), k
+        setattr(p, k, v)
+    return p
+
+
+def track_job_bytes(params):
+    """sfa_track_job_bytes (host only, no GPU): the device bytes a TrackJob of these parameters allocates"""
+    L = lib()
+    L.sfa_track_job_bytes.argtypes = [C.POINTER(TrackParams), C.POINTER(C.c_size_t)]
+    b = C.c_size_t()
+    if L.sfa_track_job_bytes(C.byref(params), C.byref(b)) != 0:
+        raise SlowflowError("sfa_track_job_bytes: %s" % L.sfa_last_error(None).decode())
+    return b.value
+
+
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
     "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
@@ -127,6 +176,7 @@ EXPORTS = [
     "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_pair_job_upload_device", "sfa_pair_job_set_flow_device", "sfa_pair_job_download_device", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
     "sfa_demosaic_device", "sfa_sequence_upload_mosaic_device", "sfa_sequence_upload_mosaic", "sfa_job_set_raw_weights", "sfa_sequence_rescale",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
+    "sfa_track_params_default", "sfa_track_job_bytes", "sfa_track_job_create", "sfa_track_job_destroy", "sfa_track_job_upload_flows", "sfa_track_job_upload_frames", "sfa_track_job_upload_flows_device", "sfa_track_job_upload_frames_device", "sfa_track_job_run", "sfa_track_job_download_rate", "sfa_track_job_download_fused", "sfa_track_job_download_best", "sfa_ctx_free_bytes", "sfa_track_job_download_device", "sfa_track_job_stage_ms",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
 
@@ -147,9 +197,10 @@ def lib():
         L.sfa_job_mpix_iters.argtypes = [C.c_void_p]
         L.sfa_job_device_bytes.restype = C.c_double
         L.sfa_job_device_bytes.argtypes = [C.c_void_p]
-        for name in ("sfa_ctx_destroy", "sfa_job_destroy", "sfa_pair_job_destroy", "sfa_sor_batch_destroy", "sfa_sequence_destroy"):
-            getattr(L, name).restype = None
-            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("sfa_ctx_destroy", "sfa_job_destroy", "sfa_pair_job_destroy", "sfa_track_job_destroy", "sfa_sor_batch_destroy", "sfa_sequence_destroy"):
+            if hasattr(L, name):                # an SFA_LIB build of an earlier C-ABI (tools/bench_track.py's baseline) lacks the newest object
+                getattr(L, name).restype = None
+                getattr(L, name).argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -791,6 +842,117 @@ class PairJob:
         if self.h_:
             if self.ctx.h:                      # a context finalised first (cyclic garbage, interpreter shutdown) took its stream along: nothing to call into
                 lib().sfa_pair_job_destroy(self.h_)
+            self.h_ = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TrackJob:
+    """sfa_track_job: dense_tracking's accumulation, energies and fusion of up to params.n start_jets x params.K rates, resident in HBM.  run() only
+    enqueues the whole chain and returns at once; the downloads wait.  Segment s comes out bit-identical to Context.accumulate_consistent(all_steps) ->
+    hypothesis_energies(adapted=True) -> smoothness_weight -> fuse_hypotheses on that segment alone."""
+
+    def __init__(self, ctx, params):
+        self.ctx, self.params = ctx, TrackParams.from_buffer_copy(params)
+        self.n, self.K, self.Jets, self.w, self.h = params.n, params.K, params.Jets, params.w, params.h
+        self.h_ = C.c_void_p()
+        L = lib()
+        _pf, _u8 = C.POINTER(_f), C.POINTER(C.POINTER(C.c_ubyte))
+        L.sfa_track_job_create.argtypes = [C.c_void_p, C.POINTER(TrackParams), C.POINTER(C.c_void_p)]
+        L.sfa_track_job_upload_flows.argtypes = [C.c_void_p, C.c_int, C.c_int, _pf, _pf, _pf, _pf, _u8]
+        L.sfa_track_job_upload_frames.argtypes = [C.c_void_p, C.c_int, _pf, C.c_int]
+        L.sfa_track_job_run.argtypes = [C.c_void_p, C.c_int]
+        L.sfa_track_job_download_rate.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.sfa_track_job_download_fused.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        L.sfa_track_job_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        ctx._ck(L.sfa_track_job_create(ctx.h, C.byref(self.params), C.byref(self.h_)), "sfa_track_job_create")
+        self.gw, self.gh = accumulate_grid(self.w, self.h, params.skip)
+        ctx._children.add(self)
+
+    def upload_flows(self, s, r, fwd_u, fwd_v, bwd_u, bwd_v, occ=None):
+        """rate r of segment s: fp32 (r_Jets[r], sh, stride) arrays as params.source[r] describes them; occ: the raw uint8 occlusion images of that
+        shape on a job with use_occlusions"""
+        src, rJ = self.params.source[r], self.params.r_Jets[r]
+        planes = [np.ascontiguousarray(a, dtype=np.float32) for a in (fwd_u, fwd_v, bwd_u, bwd_v)]
+        for a in planes:
+            assert a.shape == (rJ, src.sh, src.stride), "flows are (r_Jets[r], source.sh, source.stride)"
+        ptrs = [(_f * rJ)(*[fptr(a[k]) for k in range(rJ)]) for a in planes]
+        op = None
+        if occ is not None:
+            occ = np.ascontiguousarray(occ, dtype=np.uint8)
+            assert occ.shape == (rJ, src.sh, src.stride), "occlusion images have the flows' shape"
+            _u8 = C.POINTER(C.c_ubyte)
+            op = (_u8 * rJ)(*[occ[k].ctypes.data_as(_u8) for k in range(rJ)])
+        self.ctx._ck(lib().sfa_track_job_upload_flows(self.h_, int(s), int(r), ptrs[0], ptrs[1], ptrs[2], ptrs[3], op), "sfa_track_job_upload_flows")
+
+    def upload_frames(self, s, frames):
+        """the normalised colour frames of segment s: fp32 (Jets + 1, 3, h, stride)"""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        assert frames.ndim == 4 and frames.shape[:3] == (self.Jets + 1, 3, self.h), "frames are (Jets + 1, 3, h, stride)"
+        fp = (_f * (self.Jets + 1))(*[fptr(frames[k]) for k in range(self.Jets + 1)])
+        self.ctx._ck(lib().sfa_track_job_upload_frames(self.h_, int(s), fp, frames.shape[3]), "sfa_track_job_upload_frames")
+
+    # ---- the device seam (slowflow_amd/device.py): objects with __cuda_array_interface__, asynchronous on the context's stream ----
+    def upload_flows_device(self, r, fwd, bwd, s0=0):
+        """fwd, bwd: fp32 [ns, r_Jets[r], 2, sh, sw] in device memory (any strides) -> rate r of segments s0 .. s0 + ns - 1"""
+        from . import device
+        device.track_job_upload_flows_device(self, r, fwd, bwd, s0)
+
+    def upload_frames_device(self, frames, s0=0):
+        """frames: fp32 [ns, Jets + 1, 3, h, w] in device memory (any strides) -> segments s0 .. s0 + ns - 1"""
+        from . import device
+        device.track_job_upload_frames_device(self, frames, s0)
+
+    def download_device(self, flow, slot=None, occ=None, stats=None, s0=0):
+        """the fused results of segments s0 .. into device arrays: flow float64 [ns, 2, gh, gw] (any strides); contiguous slot int32 [ns, gh, gw], occ
+        uint8 [ns, gh, gw], stats float64 [ns, 3]"""
+        from . import device
+        device.track_job_download_device(self, flow, slot, occ, stats, s0)
+
+    def run(self, ns=None):
+        self.ctx._ck(lib().sfa_track_job_run(self.h_, int(self.n if ns is None else ns)), "sfa_track_job_run")
+
+    def download_rate(self, s, r):
+        """a dict of (gh, gw) arrays: u, v float64 (the last accumulated step), tracked int32, energy float64, occ_bits uint64, occluded uint8"""
+        g = (self.gh, self.gw)
+        out = dict(u=np.zeros(g, np.float64), v=np.zeros(g, np.float64), tracked=np.zeros(g, np.int32), energy=np.zeros(g, np.float64),
+                   occ_bits=np.zeros(g, np.uint64), occluded=np.zeros(g, np.uint8))
+        self.ctx._ck(lib().sfa_track_job_download_rate(self.h_, int(s), int(r), *[out[k].ctypes.data for k in ("u", "v", "tracked", "energy", "occ_bits", "occluded")]),
+                     "sfa_track_job_download_rate")
+        return out
+
+    def download_fused(self, s):
+        """a dict: slot int32, u, v float64, occ, best uint8 (gh, gw); energy, bound (floats), iters (int)"""
+        g = (self.gh, self.gw)
+        out = dict(slot=np.zeros(g, np.int32), u=np.zeros(g, np.float64), v=np.zeros(g, np.float64), occ=np.zeros(g, np.uint8), best=np.zeros(g, np.uint8))
+        e, b, it = C.c_double(), C.c_double(), C.c_int()
+        self.ctx._ck(lib().sfa_track_job_download_fused(self.h_, int(s), *[out[k].ctypes.data for k in ("slot", "u", "v", "occ", "best")], C.addressof(e),
+                                                        C.addressof(b), C.addressof(it)), "sfa_track_job_download_fused")
+        out.update(energy=e.value, bound=b.value, iters=it.value)
+        return out
+
+    def download_best(self, s):
+        """best uint8 (gh, gw) of segment s: the rate of the lowest fp32 energy, 255 for none; also on a job with do_fuse 0"""
+        best = np.zeros((self.gh, self.gw), np.uint8)
+        L = lib()
+        L.sfa_track_job_download_best.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self.ctx._ck(L.sfa_track_job_download_best(self.h_, int(s), best.ctypes.data), "sfa_track_job_download_best")
+        return best
+
+    def stage_ms(self):
+        """the last run's kernel times in ms: records, accumulation, energies, weight, labels, pairwise, TRW-S, output (waits for the run)"""
+        ms = (C.c_float * 8)()
+        self.ctx._ck(lib().sfa_track_job_stage_ms(self.h_, ms), "sfa_track_job_stage_ms")
+        return list(ms)
+
+    def close(self):
+        if self.h_:
+            if self.ctx.h:                      # a context finalised first (cyclic garbage, interpreter shutdown) took its stream along: nothing to call into
+                lib().sfa_track_job_destroy(self.h_)
             self.h_ = C.c_void_p()
 
     def __del__(self):

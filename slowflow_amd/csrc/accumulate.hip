@@ -105,6 +105,30 @@ int sfa_accumulate_grid(int w, int h, int skip, int *gw, int *gh) {
     return SFA_OK;
 }
 
+namespace sfa {
+
+void launch_interleave(sfa_ctx *ctx, const float *u, const float *v, float2 *out, size_t n) {
+    const int blocks = (int)std::min<size_t>((n + kAccThreads - 1) / kAccThreads, (size_t)ctx->cu_count * 8);
+    hipLaunchKernelGGL(k_interleave, dim3(blocks), dim3(kAccThreads), 0, ctx->stream, u, v, out, n);
+}
+
+int accumulate_device(sfa_ctx *ctx, int n, int FF, int w, int h, int gw, int gh, int skip, bool identity, const void *fwd, const void *bwd,
+                      const unsigned char *masks, double epsilon, int discard, int all_steps, double *acc_u, double *acc_v, int *tracked) {
+    const int xy_incr = skip + 1, xy_start = (int)(0.5f * skip);
+    const size_t gpl = (size_t)gw * gh;
+    const dim3 grid((unsigned)((gpl + kAccThreads - 1) / kAccThreads), (unsigned)n);
+    if (identity)
+        hipLaunchKernelGGL(k_accumulate<float2>, grid, dim3(kAccThreads), 0, ctx->stream, static_cast<const float2 *>(fwd), static_cast<const float2 *>(bwd), masks, FF,
+                           w, h, gw, gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, acc_u, acc_v, tracked);
+    else
+        hipLaunchKernelGGL(k_accumulate<double2>, grid, dim3(kAccThreads), 0, ctx->stream, static_cast<const double2 *>(fwd), static_cast<const double2 *>(bwd), masks,
+                           FF, w, h, gw, gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, acc_u, acc_v, tracked);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+}  // namespace sfa
+
 // sfa_accumulate_consistent and sfa_accumulate_consistent_scaled: the planes src describes, as float2 where src is the identity (masks: decoded masks or,
 // with raw_occ, the occlusion images as read), else resampled to double2 (masks: raw occlusion images)
 static int accumulate_run(sfa_ctx *ctx, const char *fn, int n, int FF, int w, int h, const sfa_jet_source *src, const float *const *fwd_u, const float *const *fwd_v,
@@ -136,7 +160,6 @@ static int accumulate_run(sfa_ctx *ctx, const char *fn, int n, int FF, int w, in
         for (auto &e : ev) SFA_HIP(ctx, hipEventCreate(&e));
     struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 6; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
     float *su = dstage.f(), *sv = dstage.f() + np * spl;
-    const int iblocks = (int)std::min<size_t>((np * pl + kAccThreads - 1) / kAccThreads, (size_t)ctx->cu_count * 8);
     for (int dir = 0; dir < 2; dir++) {
         const float *const *U = dir ? bwd_u : fwd_u, *const *V = dir ? bwd_v : fwd_v;
         if (!identity) {
@@ -148,7 +171,7 @@ static int accumulate_run(sfa_ctx *ctx, const char *fn, int n, int FF, int w, in
             SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, V[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
         }
         if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[2 * dir], ctx->stream));
-        hipLaunchKernelGGL(k_interleave, dim3(iblocks), dim3(kAccThreads), 0, ctx->stream, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), np * pl);
+        launch_interleave(ctx, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), np * pl);
         if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[2 * dir + 1], ctx->stream));
     }
     if (masks && raw_occ)
@@ -157,18 +180,10 @@ static int accumulate_run(sfa_ctx *ctx, const char *fn, int n, int FF, int w, in
         for (size_t k = 0; k < np; k++)
             SFA_HIP(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dm.p) + k * pl, (size_t)w, masks[k], (size_t)stride, (size_t)w, h, hipMemcpyHostToDevice,
                                           ctx->stream));
-    const int xy_incr = skip + 1, xy_start = (int)(0.5f * skip);
-    const dim3 grid((unsigned)((gpl + kAccThreads - 1) / kAccThreads), (unsigned)n);
     const unsigned char *dmp = masks ? static_cast<const unsigned char *>(dm.p) : nullptr;
     double *pau = static_cast<double *>(dau.p), *pav = static_cast<double *>(dav.p);
     if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[4], ctx->stream));
-    if (identity)
-        hipLaunchKernelGGL(k_accumulate<float2>, grid, dim3(kAccThreads), 0, ctx->stream, static_cast<const float2 *>(dfw.p), static_cast<const float2 *>(dbw.p), dmp, FF,
-                           w, h, gw, gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, pau, pav, static_cast<int *>(dtr.p));
-    else
-        hipLaunchKernelGGL(k_accumulate<double2>, grid, dim3(kAccThreads), 0, ctx->stream, static_cast<const double2 *>(dfw.p), static_cast<const double2 *>(dbw.p), dmp,
-                           FF, w, h, gw, gh, xy_incr, xy_start, epsilon, discard ? 1 : 0, all_steps ? 1 : 0, pau, pav, static_cast<int *>(dtr.p));
-    SFA_HIP(ctx, hipGetLastError());
+    SFA_TRY(accumulate_device(ctx, n, FF, w, h, gw, gh, skip, identity, dfw.p, dbw.p, dmp, epsilon, discard, all_steps, pau, pav, static_cast<int *>(dtr.p)));
     if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[5], ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(acc_u, dau.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(acc_v, dav.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -716,7 +716,7 @@ int sfa_normalize(sfa_ctx *ctx, float *const *frames, int F, int w, int h, int s
 namespace sfa {
 
 // `p` must be device memory of the context's GPU, and the view (its last element `last` elements of `elem` bytes further) must lie inside p's allocation
-static int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem) {
+int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem) {
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof at);
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {

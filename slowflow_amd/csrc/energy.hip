@@ -38,20 +38,9 @@ constexpr int kEnThreads = 256;          // the per-pixel kernels
 constexpr int kBcThreads = 64;           // k_hyp_bcgc: one wave, LDS per lane
 constexpr int kEnMaxJets = 32;           // the LDS bound above (and the 64-bit occlusion word needs Jets + 1 <= 64)
 
-// adaptFPS(Jets) of a hypothesis of F = r_Jets steps, its float index arithmetic done once on the host (hypothesis.h:140-171)
-struct AdaptTab {
-    int off[kEnMaxJets], offm1[kEnMaxJets];
-    float skip;                          // (1.0f * F) / nF, a float
-    int up;                              // skip >= 1
-};
-
-struct EnergyArgs {
-    double acc_jc, acc_cv, acc_bc, acc_gc, acc_occ, acc_temporal_occ;   // the parameters' double types in addJC / addBCGC / addOC
-    float thr, fb_thr;                   // setOcclusions' float thresholds
-    int penalty;                         // 0 quadratic, 1 modified L1, else Lorentzian (:665-675)
-    double eps_sq;                       // (double)(e * e), e the float the penalty's constructor takes
-    float weight;                        // weight_jet_estimation[r], a float (:489)
-};
+// AdaptTab (adaptFPS(Jets) of a hypothesis of F = r_Jets steps, its float index arithmetic done once on the host, hypothesis.h:140-171) and EnergyArgs:
+// sfa_internal.h
+static_assert(sizeof(AdaptTab::off) / sizeof(int) == kEnMaxJets, "AdaptTab holds kEnMaxJets steps");
 
 // PenaltyFunction::apply(float xsq), float in, float out
 __device__ __forceinline__ float phi_apply(int kind, double eps_sq, float xsq) {
@@ -250,15 +239,15 @@ __global__ void __launch_bounds__(kBcThreads) k_hyp_bcgc(const float4 *__restric
     ep[si * NN + k] = e_p;
 }
 
-// the adapted flows of k_hyp_serial ([n][gpl][J]) in the layout [n][J][gpl] the fusion reads, 0 where there is no hypothesis
+// the adapted flows of k_hyp_serial ([n][gpl][J]) in the layout [J][gpl] the fusion reads, segment s at s * seg; 0 where there is no hypothesis
 __global__ void __launch_bounds__(kEnThreads) k_hyp_adapted(const int *__restrict__ tracked, const double *__restrict__ U, const double *__restrict__ V, int rJ,
-                                                            int J, int gpl, double *__restrict__ out_u, double *__restrict__ out_v) {
+                                                            int J, int gpl, double *__restrict__ out_u, double *__restrict__ out_v, size_t seg) {
     const int i = blockIdx.x * kEnThreads + threadIdx.x;
     if (i >= gpl) return;
     const size_t si = (size_t)blockIdx.y * gpl + i;
     const bool have = tracked[si] == rJ;
     for (int t = 0; t < J; t++) {
-        const size_t o = ((size_t)blockIdx.y * J + t) * gpl + i;
+        const size_t o = (size_t)blockIdx.y * seg + (size_t)t * gpl + i;
         out_u[o] = have ? U[si * J + t] : 0.0;
         out_v[o] = have ? V[si * J + t] : 0.0;
     }
@@ -268,13 +257,13 @@ __global__ void __launch_bounds__(kEnThreads) k_hyp_adapted(const int *__restric
 __global__ void __launch_bounds__(kEnThreads) k_hyp_sum(const int *__restrict__ tracked, const unsigned long long *__restrict__ occ_bits,
                                                         const float *__restrict__ jc, const float *__restrict__ oc, const double *__restrict__ ep, int rJ, int w, int h,
                                                         int gw, int gpl, int incr, int start, int r, float weight, double *__restrict__ energy,
-                                                        unsigned long long *__restrict__ occ_out) {
+                                                        unsigned long long *__restrict__ occ_out, size_t out_seg) {
     const int i = blockIdx.x * kEnThreads + threadIdx.x;
     if (i >= gpl) return;
-    const size_t si = (size_t)blockIdx.y * gpl + i;
+    const size_t si = (size_t)blockIdx.y * gpl + i, so = (size_t)blockIdx.y * out_seg + i;   // segment s's outputs start at s * out_seg
     if (tracked[si] != rJ) {                                                    // null hypothesis: sorted last by compareHypotheses (:172)
-        energy[si] = __longlong_as_double(0x7ff0000000000000ll);
-        occ_out[si] = 0;
+        energy[so] = __longlong_as_double(0x7ff0000000000000ll);
+        occ_out[so] = 0;
         return;
     }
     const int side = 2 * r + 1, NN = side * side;
@@ -290,8 +279,89 @@ __global__ void __launch_bounds__(kEnThreads) k_hyp_sum(const int *__restrict__ 
     float e = jc[si] + (float)wenergy;
     e = e + oc[si];
     e = e + weight;
-    energy[si] = (double)e;
-    occ_out[si] = occ_bits[si];
+    energy[so] = (double)e;
+    occ_out[so] = occ_bits[si];
+}
+
+int energy_plan(sfa_ctx *ctx, const sfa_energy_params *p, int r_Jets, int Jets, int w, int h, EnergyPlan *out) {
+    EnergyPlan &e = *out;
+    e = EnergyPlan{};
+    e.rJ = r_Jets; e.J = Jets; e.w = w; e.h = h;
+    if (sfa_accumulate_grid(w, h, p->skip, &e.gw, &e.gh) != SFA_OK) return set_error(ctx, SFA_ERR_ARG, "%s", sfa_last_error(nullptr));
+    // adaptFPS's indices in its own float arithmetic (hypothesis.h:139-171), each checked against the F = r_Jets flows it reads
+    AdaptTab &tab = e.tab;
+    tab.skip = (1.0f * r_Jets) / Jets;
+    tab.up = tab.skip >= 1;
+    for (int i = 0; i < Jets; i++) {
+        if (tab.up) tab.off[i] = (int)(i * tab.skip + (tab.skip - 1));
+        else { tab.off[i] = (int)floorf(i * tab.skip); tab.offm1[i] = (int)floorf((i - 1) * tab.skip); }
+        if (tab.off[i] < 0 || tab.off[i] >= r_Jets || (!tab.up && i > 0 && (tab.offm1[i] < 0 || tab.offm1[i] >= r_Jets)))
+            return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: adaptFPS(%d) of %d steps reads step %d", Jets, r_Jets, tab.off[i]);
+    }
+    e.r = (int)(0.5f * (p->skip + 1));                                          // :245
+    const int side = 2 * e.r + 1;
+    e.NN = side * side;
+    e.lds = (size_t)kBcThreads * 9 * (Jets + 1) * sizeof(double);
+    e.incr = p->skip + 1; e.start = (int)(0.5f * p->skip);
+    EnergyArgs &a = e.a;
+    a.acc_jc = p->acc_jc; a.acc_cv = p->acc_cv; a.acc_bc = p->acc_bc; a.acc_gc = p->acc_gc; a.acc_occ = p->acc_occ; a.acc_temporal_occ = p->acc_temporal_occ;
+    a.thr = p->occlusion_threshold; a.fb_thr = p->occlusion_fb_threshold; a.penalty = p->penalty;
+    const float eps = (float)p->penalty_eps;                                    // ModifiedL1Norm(float e) / Lorentzian(float e): epsilon_sq(e * e)
+    a.eps_sq = (double)(eps * eps);
+    a.weight = p->weight;
+    return SFA_OK;
+}
+
+// dx, dy by the 5-tap derivative launcher (color_image_convolve_hv with {0, -8/12, 1/12}, :920-925), then the records
+void energy_records_device(sfa_ctx *ctx, size_t nf, int w, int h, const float *frames, float *der, void *rec) {
+    const size_t pl = (size_t)w * h;
+    Geo g{};
+    g.w = w; g.h = h; g.pitch = w; g.pl = (long)pl; g.es = (long)pl; g.nb = (int)(nf * 3);
+    float *ddx = der, *ddy = der + nf * 3 * pl;
+    launch_convolve(ctx, g, ddx, frames, 2, 1, 1);
+    launch_convolve(ctx, g, ddy, frames, 2, 0, 1);
+    hipLaunchKernelGGL(k_energy_records, dim3((unsigned)std::min<size_t>((nf * pl + kEnThreads - 1) / kEnThreads, (size_t)ctx->cu_count * 8)), dim3(kEnThreads), 0,
+                       ctx->stream, frames, ddx, ddy, static_cast<float4 *>(rec), pl, nf * pl);
+}
+
+int energies_device(sfa_ctx *ctx, const EnergyPlan &e, int n, const double *acc_u, const double *acc_v, const int *tracked, const void *rec, bool identity,
+                    const void *fwd, const void *bwd, const EnergyWork &wk, double *energy, unsigned long long *occ_out, size_t out_seg, double *adapted_u,
+                    double *adapted_v, size_t adapted_seg) {
+    // more than 64 KiB of dynamic LDS is allowed per function and device, once (the pattern of sor_chain.hip)
+    static std::atomic<unsigned long long> attr_set{0};
+    const unsigned long long bit = (ctx->device >= 0 && ctx->device < 64) ? 1ull << ctx->device : 0ull;
+    if (e.lds > 64 * 1024 && !(attr_set.load(std::memory_order_relaxed) & bit)) {
+        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hyp_bcgc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.lds);
+        if (err != hipSuccess) return set_error(ctx, SFA_ERR_HIP, "k_hyp_bcgc: %zu bytes of LDS refused on device %d: %s", e.lds, ctx->device, hipGetErrorString(err));
+        attr_set.fetch_or(bit, std::memory_order_relaxed);
+    }
+    const size_t gpl = (size_t)e.gw * e.gh;
+    const dim3 pix((unsigned)((gpl + kEnThreads - 1) / kEnThreads), (unsigned)n);
+    if (identity)
+        hipLaunchKernelGGL(k_hyp_serial<float2>, pix, dim3(kEnThreads), 0, ctx->stream, acc_u, acc_v, tracked, static_cast<const float2 *>(fwd),
+                           static_cast<const float2 *>(bwd), e.rJ, e.J, e.w, e.h, e.gw, (int)gpl, e.incr, e.start, e.tab, e.a, wk.U, wk.V, wk.occ, wk.jc, wk.oc);
+    else
+        hipLaunchKernelGGL(k_hyp_serial<double2>, pix, dim3(kEnThreads), 0, ctx->stream, acc_u, acc_v, tracked, static_cast<const double2 *>(fwd),
+                           static_cast<const double2 *>(bwd), e.rJ, e.J, e.w, e.h, e.gw, (int)gpl, e.incr, e.start, e.tab, e.a, wk.U, wk.V, wk.occ, wk.jc, wk.oc);
+    SFA_HIP(ctx, hipGetLastError());
+    const double bcw = e.a.acc_bc * 0.3334, gcw = e.a.acc_gc * 0.3334;          // acc_bc * 0.3334 * (...) groups left to right (:318-319)
+    hipLaunchKernelGGL(k_hyp_bcgc, dim3((unsigned)((gpl * e.NN + kBcThreads - 1) / kBcThreads), (unsigned)n), dim3(kBcThreads), e.lds, ctx->stream,
+                       static_cast<const float4 *>(rec), tracked, wk.U, wk.V, wk.occ, e.rJ, e.J, e.w, e.h, e.gw, (int)gpl, e.incr, e.start, e.r, bcw, gcw, wk.ep);
+    SFA_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_hyp_sum, pix, dim3(kEnThreads), 0, ctx->stream, tracked, wk.occ, wk.jc, wk.oc, wk.ep, e.rJ, e.w, e.h, e.gw, (int)gpl, e.incr, e.start, e.r,
+                       e.a.weight, energy, occ_out, out_seg);
+    SFA_HIP(ctx, hipGetLastError());
+    if (adapted_u) SFA_TRY(energies_adapted_device(ctx, e, n, tracked, wk, adapted_u, adapted_v, adapted_seg));
+    return SFA_OK;
+}
+
+// k_hyp_serial's adaptFPS(Jets) out of the scratch of the energies_device call before it, transposed for the fusion
+int energies_adapted_device(sfa_ctx *ctx, const EnergyPlan &e, int n, const int *tracked, const EnergyWork &wk, double *adapted_u, double *adapted_v, size_t adapted_seg) {
+    const size_t gpl = (size_t)e.gw * e.gh;
+    const dim3 pix((unsigned)((gpl + kEnThreads - 1) / kEnThreads), (unsigned)n);
+    hipLaunchKernelGGL(k_hyp_adapted, pix, dim3(kEnThreads), 0, ctx->stream, tracked, wk.U, wk.V, e.rJ, e.J, (int)gpl, adapted_u, adapted_v, adapted_seg);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
 }
 
 }  // namespace sfa
@@ -348,61 +418,30 @@ int sfa_hypothesis_energies_scaled(sfa_ctx *ctx, const sfa_energy_params *p, int
         return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: h = %d; the reference's vertical 5-tap derivative needs h >= 4", h);
     bool identity = true;                                                       // the flows are w x h float planes of the frames' stride
     if (flows) SFA_TRY(jet_source_check(ctx, "sfa_hypothesis_energies: flow_src", flow_src, w, h, &identity));
-    int gw, gh;
-    if (sfa_accumulate_grid(w, h, p->skip, &gw, &gh) != SFA_OK) return set_error(ctx, SFA_ERR_ARG, "%s", sfa_last_error(nullptr));
-    // adaptFPS's indices in its own float arithmetic (hypothesis.h:139-171), each checked against the F = r_Jets flows it reads
-    AdaptTab tab{};
-    tab.skip = (1.0f * r_Jets) / Jets;
-    tab.up = tab.skip >= 1;
-    for (int i = 0; i < Jets; i++) {
-        if (tab.up) tab.off[i] = (int)(i * tab.skip + (tab.skip - 1));
-        else { tab.off[i] = (int)floorf(i * tab.skip); tab.offm1[i] = (int)floorf((i - 1) * tab.skip); }
-        if (tab.off[i] < 0 || tab.off[i] >= r_Jets || (!tab.up && i > 0 && (tab.offm1[i] < 0 || tab.offm1[i] >= r_Jets)))
-            return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: adaptFPS(%d) of %d steps reads step %d", Jets, r_Jets, tab.off[i]);
-    }
+    EnergyPlan plan;
+    SFA_TRY(energy_plan(ctx, p, r_Jets, Jets, w, h, &plan));
+    const int gw = plan.gw, gh = plan.gh, NN = plan.NN;
     const size_t nf = (size_t)n * (Jets + 1), nj = (size_t)n * Jets, pl = (size_t)w * h, gpl = (size_t)gw * gh;
     for (size_t k = 0; k < nf; k++)
         if (!frames[k]) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: null frame %zu", k);
     if (flows)
         for (size_t k = 0; k < nj; k++)
             if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k]) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: null flow plane %zu", k);
-    const int r = (int)(0.5f * (p->skip + 1)), side = 2 * r + 1, NN = side * side;                 // :245
-    const size_t lds = (size_t)kBcThreads * 9 * (Jets + 1) * sizeof(double);
-    EnergyArgs a;
-    a.acc_jc = p->acc_jc; a.acc_cv = p->acc_cv; a.acc_bc = p->acc_bc; a.acc_gc = p->acc_gc; a.acc_occ = p->acc_occ; a.acc_temporal_occ = p->acc_temporal_occ;
-    a.thr = p->occlusion_threshold; a.fb_thr = p->occlusion_fb_threshold; a.penalty = p->penalty;
-    const float e = (float)p->penalty_eps;                                      // ModifiedL1Norm(float e) / Lorentzian(float e): epsilon_sq(e * e)
-    a.eps_sq = (double)(e * e);
-    a.weight = p->weight;
 
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    // more than 64 KiB of dynamic LDS is allowed per function and device, once (the pattern of sor_chain.hip)
-    static std::atomic<unsigned long long> attr_set{0};
-    const unsigned long long bit = (ctx->device >= 0 && ctx->device < 64) ? 1ull << ctx->device : 0ull;
-    if (lds > 64 * 1024 && !(attr_set.load(std::memory_order_relaxed) & bit)) {
-        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hyp_bcgc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return set_error(ctx, SFA_ERR_HIP, "k_hyp_bcgc: %zu bytes of LDS refused on device %d: %s", lds, ctx->device, hipGetErrorString(err));
-        attr_set.fetch_or(bit, std::memory_order_relaxed);
-    }
-    DevMem dfr, dder, drec, dfw, dbw, dstage, dau, dav, dtr, dU, dV, docc, djc, doc, dep, den, docc_out;
+    DevMem dfr, dder, drec, dfw, dbw, dstage, dau, dav, dtr, dU, dV, docc, djc, doc, dep, den, docc_out, dad;
     SFA_TRY(dfr.alloc(ctx, nf * 3 * pl * 4)); SFA_TRY(dder.alloc(ctx, nf * 6 * pl * 4)); SFA_TRY(drec.alloc(ctx, nf * pl * 48));
     SFA_TRY(dau.alloc(ctx, (size_t)n * r_Jets * gpl * 8)); SFA_TRY(dav.alloc(ctx, (size_t)n * r_Jets * gpl * 8)); SFA_TRY(dtr.alloc(ctx, (size_t)n * gpl * 4));
     SFA_TRY(dU.alloc(ctx, nj * gpl * 8)); SFA_TRY(dV.alloc(ctx, nj * gpl * 8)); SFA_TRY(docc.alloc(ctx, (size_t)n * gpl * 8));
     SFA_TRY(djc.alloc(ctx, (size_t)n * gpl * 4)); SFA_TRY(doc.alloc(ctx, (size_t)n * gpl * 4)); SFA_TRY(dep.alloc(ctx, (size_t)n * gpl * NN * 8));
     SFA_TRY(den.alloc(ctx, (size_t)n * gpl * 8)); SFA_TRY(docc_out.alloc(ctx, (size_t)n * gpl * 8));
     const int blocks_cap = ctx->cu_count * 8;
-    // frames: the valid columns of each plane, packed; dx, dy by the 5-tap derivative launcher (color_image_convolve_hv with {0, -8/12, 1/12}, :920-925)
+    // frames: the valid columns of each plane, packed
     for (size_t k = 0; k < nf; k++)
         for (int c = 0; c < 3; c++)
             SFA_HIP(ctx, hipMemcpy2DAsync(dfr.f() + (k * 3 + c) * pl, (size_t)w * 4, frames[k] + (size_t)c * h * stride, (size_t)stride * 4, (size_t)w * 4, h,
                                           hipMemcpyHostToDevice, ctx->stream));
-    Geo g{};
-    g.w = w; g.h = h; g.pitch = w; g.pl = (long)pl; g.es = (long)pl; g.nb = (int)(nf * 3);
-    float *ddx = dder.f(), *ddy = dder.f() + nf * 3 * pl;
-    launch_convolve(ctx, g, ddx, dfr.f(), 2, 1, 1);
-    launch_convolve(ctx, g, ddy, dfr.f(), 2, 0, 1);
-    hipLaunchKernelGGL(k_energy_records, dim3((unsigned)std::min<size_t>((nf * pl + kEnThreads - 1) / kEnThreads, blocks_cap)), dim3(kEnThreads), 0, ctx->stream,
-                       dfr.f(), ddx, ddy, static_cast<float4 *>(drec.p), pl, nf * pl);
+    energy_records_device(ctx, nf, w, h, dfr.f(), dder.f(), drec.p);
     if (flows) {
         const size_t tap = identity ? 8 : 16, spl = identity ? pl : (size_t)flow_src->cw * flow_src->ch;   // float2 or double2
         const int fstride = flow_src->stride;
@@ -425,38 +464,20 @@ int sfa_hypothesis_energies_scaled(sfa_ctx *ctx, const sfa_energy_params *p, int
     SFA_HIP(ctx, hipMemcpyAsync(dau.p, acc_u, (size_t)n * r_Jets * gpl * 8, hipMemcpyHostToDevice, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(dav.p, acc_v, (size_t)n * r_Jets * gpl * 8, hipMemcpyHostToDevice, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(dtr.p, tracked, (size_t)n * gpl * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int incr = p->skip + 1, start = (int)(0.5f * p->skip);
-    const int *dt = static_cast<const int *>(dtr.p);
-    double *dUp = static_cast<double *>(dU.p), *dVp = static_cast<double *>(dV.p);
-    unsigned long long *doccp = static_cast<unsigned long long *>(docc.p);
-    const dim3 pix((unsigned)((gpl + kEnThreads - 1) / kEnThreads), (unsigned)n);
-    if (identity)
-        hipLaunchKernelGGL(k_hyp_serial<float2>, pix, dim3(kEnThreads), 0, ctx->stream, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), dt,
-                           flows ? static_cast<const float2 *>(dfw.p) : nullptr, flows ? static_cast<const float2 *>(dbw.p) : nullptr, r_Jets, Jets, w, h, gw,
-                           (int)gpl, incr, start, tab, a, dUp, dVp, doccp, djc.f(), doc.f());
-    else
-        hipLaunchKernelGGL(k_hyp_serial<double2>, pix, dim3(kEnThreads), 0, ctx->stream, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), dt,
-                           static_cast<const double2 *>(dfw.p), static_cast<const double2 *>(dbw.p), r_Jets, Jets, w, h, gw, (int)gpl, incr, start, tab, a, dUp, dVp,
-                           doccp, djc.f(), doc.f());
-    SFA_HIP(ctx, hipGetLastError());
-    const double bcw = a.acc_bc * 0.3334, gcw = a.acc_gc * 0.3334;              // acc_bc * 0.3334 * (...) groups left to right (:318-319)
-    hipLaunchKernelGGL(k_hyp_bcgc, dim3((unsigned)((gpl * NN + kBcThreads - 1) / kBcThreads), (unsigned)n), dim3(kBcThreads), lds, ctx->stream,
-                       static_cast<const float4 *>(drec.p), dt, dUp, dVp, doccp, r_Jets, Jets, w, h, gw, (int)gpl, incr, start, r, bcw, gcw, static_cast<double *>(dep.p));
-    SFA_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_hyp_sum, pix, dim3(kEnThreads), 0, ctx->stream, dt, doccp, djc.f(), doc.f(), static_cast<const double *>(dep.p), r_Jets, w, h, gw, (int)gpl,
-                       incr, start, r, a.weight, static_cast<double *>(den.p), static_cast<unsigned long long *>(docc_out.p));
-    SFA_HIP(ctx, hipGetLastError());
+    EnergyWork wk;
+    wk.U = static_cast<double *>(dU.p); wk.V = static_cast<double *>(dV.p); wk.occ = static_cast<unsigned long long *>(docc.p);
+    wk.jc = djc.f(); wk.oc = doc.f(); wk.ep = static_cast<double *>(dep.p);
+    SFA_TRY(energies_device(ctx, plan, n, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), static_cast<const int *>(dtr.p), drec.p, identity,
+                            flows ? dfw.p : nullptr, flows ? dbw.p : nullptr, wk, static_cast<double *>(den.p), static_cast<unsigned long long *>(docc_out.p), gpl, nullptr,
+                            nullptr, 0));
     SFA_HIP(ctx, hipMemcpyAsync(energy, den.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(occ_bits, docc_out.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (adapted_u) {                                                            // k_hyp_serial's adaptFPS(Jets), transposed for the fusion
-        DevMem dad;
+    if (adapted_u) {                                                            // allocated while the kernels above run: hipMalloc stays off the critical path
         SFA_TRY(dad.alloc(ctx, 2 * nj * gpl * 8));
         double *du = static_cast<double *>(dad.p), *dv = du + nj * gpl;
-        hipLaunchKernelGGL(k_hyp_adapted, pix, dim3(kEnThreads), 0, ctx->stream, dt, dUp, dVp, r_Jets, Jets, (int)gpl, du, dv);
-        SFA_HIP(ctx, hipGetLastError());
+        SFA_TRY(energies_adapted_device(ctx, plan, n, static_cast<const int *>(dtr.p), wk, du, dv, (size_t)Jets * gpl));
         SFA_HIP(ctx, hipMemcpyAsync(adapted_u, du, nj * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
         SFA_HIP(ctx, hipMemcpyAsync(adapted_v, dv, nj * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                        // before dad is released
     }
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;

@@ -364,6 +364,39 @@ __global__ void __launch_bounds__(kFuThreads) k_fuse_output(const double *__rest
     occ[sp] = (occ_bits[((size_t)blockIdx.y * d.K + k) * d.gpl + p] & ((2ull << d.J) - 1)) != 0;
 }
 
+// messages and labellings start at 0; then the four launches
+int fuse_device(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, int gw, int gh, const FuseWork &f, hipEvent_t *ev) {
+    FuseDims d;
+    d.n = n; d.K = K; d.J = Jets; d.gw = gw; d.gh = gh; d.gpl = gw * gh; d.w = w; d.h = h;
+    d.incr = p->skip + 1; d.start = (int)(0.5f * p->skip);                     // xy_incr, xy_start (utils.cpp:522-526)
+    const size_t gpl = (size_t)d.gpl, KK = (size_t)K * K;
+    SFA_HIP(ctx, hipMemsetAsync(f.M, 0, (size_t)n * gpl * 4 * kFuMaxK * 8, ctx->stream));
+    SFA_HIP(ctx, hipMemsetAsync(f.xcur, 0, (size_t)n * gpl, ctx->stream));
+    SFA_HIP(ctx, hipMemsetAsync(f.xbest, 0, (size_t)n * gpl, ctx->stream));
+    auto mark = [&](int i) { return ev ? hipEventRecord(ev[i], ctx->stream) : hipSuccess; };
+    const dim3 pix((unsigned)((gpl + kFuThreads - 1) / kFuThreads), (unsigned)n);
+    SFA_HIP(ctx, mark(0));
+    hipLaunchKernelGGL(k_fuse_labels, pix, dim3(kFuThreads), 0, ctx->stream, f.U, f.V, f.energy, d, p->traj_sim_method, p->traj_sim_thres, f.nl, f.lab, f.theta);
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, mark(1));
+    hipLaunchKernelGGL(k_fuse_pairwise, dim3((unsigned)((gpl * KK + kFuThreads - 1) / kFuThreads), (unsigned)(2 * n)), dim3(kFuThreads), 0, ctx->stream, f.U, f.V,
+                       f.occ, f.weight, d, p->traj_sim_method, p->acc_beta, p->acc_spatial_occ, f.nl, f.lab, f.P);
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, mark(2));
+    TrwsBufs tb;
+    tb.nl = f.nl; tb.theta = f.theta; tb.P = f.P; tb.M = f.M;
+    tb.xcur = f.xcur; tb.xbest = f.xbest; tb.seg_energy = f.seg_energy; tb.seg_bound = f.seg_bound; tb.seg_iters = f.seg_iters;
+    if (K <= 4) hipLaunchKernelGGL(k_trws<4>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
+    else if (K <= 8) hipLaunchKernelGGL(k_trws<8>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
+    else hipLaunchKernelGGL(k_trws<16>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, mark(3));
+    hipLaunchKernelGGL(k_fuse_output, pix, dim3(kFuThreads), 0, ctx->stream, f.U, f.V, f.occ, d, f.nl, f.lab, f.xbest, f.slot, f.fu, f.fv, f.out_occ);
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, mark(4));
+    return SFA_OK;
+}
+
 }  // namespace sfa
 
 using namespace sfa;
@@ -393,10 +426,7 @@ int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, in
     if (p->trws_max_iter < 1) return set_error(ctx, SFA_ERR_ARG, "sfa_fuse_hypotheses: acc_trws_max_iter %d < 1", p->trws_max_iter);
     int gw, gh;
     if (sfa_accumulate_grid(w, h, p->skip, &gw, &gh) != SFA_OK) return set_error(ctx, SFA_ERR_ARG, "%s", sfa_last_error(nullptr));
-    FuseDims d;
-    d.n = n; d.K = K; d.J = Jets; d.gw = gw; d.gh = gh; d.gpl = gw * gh; d.w = w; d.h = h;
-    d.incr = p->skip + 1; d.start = (int)(0.5f * p->skip);                     // xy_incr, xy_start (utils.cpp:522-526)
-    const size_t gpl = (size_t)d.gpl, KK = (size_t)K * K, nh = (size_t)n * K * Jets * gpl;
+    const size_t gpl = (size_t)gw * gh, KK = (size_t)K * K, nh = (size_t)n * K * Jets * gpl;
     if ((gpl * KK + kFuThreads - 1) / kFuThreads > 0x7fffffffull) return set_error(ctx, SFA_ERR_ARG, "sfa_fuse_hypotheses: grid too large");
 
     SFA_HIP(ctx, hipSetDevice(ctx->device));
@@ -412,39 +442,20 @@ int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, in
     SFA_HIP(ctx, hipMemcpyAsync(den.p, energy, (size_t)n * K * gpl * 8, hipMemcpyHostToDevice, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(docc.p, occ_bits, (size_t)n * K * gpl * 8, hipMemcpyHostToDevice, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(dw.p, weight, (size_t)n * w * h * 4, hipMemcpyHostToDevice, ctx->stream));
-    SFA_HIP(ctx, hipMemsetAsync(dM.p, 0, dM.bytes, ctx->stream));              // messages start at 0
-    SFA_HIP(ctx, hipMemsetAsync(dx.p, 0, dx.bytes, ctx->stream));
-    const double *pU = static_cast<const double *>(dU.p), *pV = static_cast<const double *>(dV.p);
-    unsigned char *pnl = static_cast<unsigned char *>(dnl.p), *plab = static_cast<unsigned char *>(dlab.p), *px = static_cast<unsigned char *>(dx.p);
     double *pseg = static_cast<double *>(dseg.p);
+    unsigned char *px = static_cast<unsigned char *>(dx.p);
+    FuseWork f;
+    f.U = static_cast<const double *>(dU.p); f.V = static_cast<const double *>(dV.p); f.energy = static_cast<const double *>(den.p);
+    f.occ = static_cast<const unsigned long long *>(docc.p); f.weight = dw.f();
+    f.nl = static_cast<unsigned char *>(dnl.p); f.lab = static_cast<unsigned char *>(dlab.p); f.theta = static_cast<double *>(dth.p);
+    f.P = static_cast<double *>(dP.p); f.M = static_cast<double *>(dM.p); f.xcur = px; f.xbest = px + (size_t)n * gpl;
+    f.slot = static_cast<int *>(dslot.p); f.fu = static_cast<double *>(dfu.p); f.fv = static_cast<double *>(dfv.p); f.out_occ = static_cast<unsigned char *>(dout_occ.p);
+    f.seg_energy = pseg; f.seg_bound = pseg + n; f.seg_iters = reinterpret_cast<int *>(pseg + 2 * n);
     hipEvent_t ev[5] = {};
     if (stage_ms)
         for (auto &e : ev) SFA_HIP(ctx, hipEventCreate(&e));
     struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 5; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
-    auto mark = [&](int i) { return stage_ms ? hipEventRecord(ev[i], ctx->stream) : hipSuccess; };
-    const dim3 pix((unsigned)((gpl + kFuThreads - 1) / kFuThreads), (unsigned)n);
-    SFA_HIP(ctx, mark(0));
-    hipLaunchKernelGGL(k_fuse_labels, pix, dim3(kFuThreads), 0, ctx->stream, pU, pV, static_cast<const double *>(den.p), d, p->traj_sim_method,
-                       p->traj_sim_thres, pnl, plab, static_cast<double *>(dth.p));
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(1));
-    hipLaunchKernelGGL(k_fuse_pairwise, dim3((unsigned)((gpl * KK + kFuThreads - 1) / kFuThreads), (unsigned)(2 * n)), dim3(kFuThreads), 0, ctx->stream, pU, pV,
-                       static_cast<const unsigned long long *>(docc.p), static_cast<const float *>(dw.p), d, p->traj_sim_method, p->acc_beta, p->acc_spatial_occ,
-                       pnl, plab, static_cast<double *>(dP.p));
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(2));
-    TrwsBufs tb;
-    tb.nl = pnl; tb.theta = static_cast<const double *>(dth.p); tb.P = static_cast<const double *>(dP.p); tb.M = static_cast<double *>(dM.p);
-    tb.xcur = px; tb.xbest = px + (size_t)n * gpl; tb.seg_energy = pseg; tb.seg_bound = pseg + n; tb.seg_iters = reinterpret_cast<int *>(pseg + 2 * n);
-    if (K <= 4) hipLaunchKernelGGL(k_trws<4>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
-    else if (K <= 8) hipLaunchKernelGGL(k_trws<8>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
-    else hipLaunchKernelGGL(k_trws<16>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(3));
-    hipLaunchKernelGGL(k_fuse_output, pix, dim3(kFuThreads), 0, ctx->stream, pU, pV, static_cast<const unsigned long long *>(docc.p), d, pnl, plab, tb.xbest,
-                       static_cast<int *>(dslot.p), static_cast<double *>(dfu.p), static_cast<double *>(dfv.p), static_cast<unsigned char *>(dout_occ.p));
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(4));
+    SFA_TRY(fuse_device(ctx, p, n, K, Jets, w, h, gw, gh, f, stage_ms ? ev : nullptr));
     SFA_HIP(ctx, hipMemcpyAsync(slot, dslot.p, (size_t)n * gpl * 4, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(flow_u, dfu.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(flow_v, dfv.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -119,6 +119,14 @@ int jet_source_check(sfa_ctx *ctx, const char *fn, const sfa_jet_source *s, int 
     return SFA_OK;
 }
 
+int launch_jet_resample(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const float *su, const float *sv, int w, int h, double2 *out) {
+    const size_t total = np * (size_t)w * h;
+    const unsigned blocks = (unsigned)std::min<size_t>((total + kJetThreads - 1) / kJetThreads, (size_t)ctx->cu_count * 16);
+    hipLaunchKernelGGL(k_jet_resample, dim3(blocks), dim3(kJetThreads), 0, ctx->stream, su, sv, s.cw, s.ch, w, h, 1.0 / (double)s.rescale, (double)s.rescale, out, total);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
 int jet_resample_flows(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const float *const *u, const float *const *v, int w, int h, float *stage, double2 *out,
                        hipEvent_t before, hipEvent_t after) {
     const size_t spl = (size_t)s.cw * s.ch, off = (size_t)s.y0 * s.stride + s.x0;
@@ -127,11 +135,8 @@ int jet_resample_flows(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const f
         SFA_HIP(ctx, hipMemcpy2DAsync(su + k * spl, (size_t)s.cw * 4, u[k] + off, (size_t)s.stride * 4, (size_t)s.cw * 4, s.ch, hipMemcpyHostToDevice, ctx->stream));
         SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * spl, (size_t)s.cw * 4, v[k] + off, (size_t)s.stride * 4, (size_t)s.cw * 4, s.ch, hipMemcpyHostToDevice, ctx->stream));
     }
-    const size_t total = np * (size_t)w * h;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + kJetThreads - 1) / kJetThreads, (size_t)ctx->cu_count * 16);
     if (before) SFA_HIP(ctx, hipEventRecord(before, ctx->stream));
-    hipLaunchKernelGGL(k_jet_resample, dim3(blocks), dim3(kJetThreads), 0, ctx->stream, su, sv, s.cw, s.ch, w, h, 1.0 / (double)s.rescale, (double)s.rescale, out, total);
-    SFA_HIP(ctx, hipGetLastError());
+    SFA_TRY(launch_jet_resample(ctx, s, np, su, sv, w, h, out));
     if (after) SFA_HIP(ctx, hipEventRecord(after, ctx->stream));
     return SFA_OK;
 }

@@ -195,6 +195,56 @@ int jet_resample_flows(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const
                        hipEvent_t before, hipEvent_t after);
 // np raw occlusion images -> out: np packed w x h masks (0 = occluded).  stage: np * sw * sh bytes
 int jet_decode_occlusions(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const unsigned char *const *occ, int w, int h, unsigned char *stage, unsigned char *out);
+// jet_resample_flows' kernel alone: su, sv are np packed cw x ch planes already in device memory
+int launch_jet_resample(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const float *su, const float *sv, int w, int h, double2 *out);
+
+// ---- dense_tracking's three stages at device level (accumulate.hip, energy.hip, fuse.hip): device pointers and a caller-owned workspace in, launches on the
+// context's stream out; no allocation, no copy, no wait.  The sfa_* entry points wrap them (allocate, upload, call, download, wait), the track job (track.hip)
+// chains them ------------------------------------------------------------------------------------------------------------------------------------------
+// n float planes u, v -> n float2 planes (total n elements)
+void launch_interleave(sfa_ctx *ctx, const float *u, const float *v, float2 *out, size_t n);
+// k_accumulate over n segments of FF steps.  fwd, bwd: [n][FF] planes of float2 (identity) or double2; masks: [n][FF] decoded masks or null;
+// acc_u, acc_v: [n][S][gpl], S = FF (all_steps) or 1; tracked: [n][gpl]
+int accumulate_device(sfa_ctx *ctx, int n, int FF, int w, int h, int gw, int gh, int skip, bool identity, const void *fwd, const void *bwd,
+                      const unsigned char *masks, double epsilon, int discard, int all_steps, double *acc_u, double *acc_v, int *tracked);
+// What the energy kernels of one (r_Jets, Jets) need besides their planes: adaptFPS's index table, the keys in the kernels' types, the grid and addBCGC's window
+struct AdaptTab {
+    int off[32], offm1[32];              // kEnMaxJets entries
+    float skip;                          // (1.0f * F) / nF, a float
+    int up;                              // skip >= 1
+};
+struct EnergyArgs {
+    double acc_jc, acc_cv, acc_bc, acc_gc, acc_occ, acc_temporal_occ;   // the parameters' double types in addJC / addBCGC / addOC
+    float thr, fb_thr;                   // setOcclusions' float thresholds
+    int penalty;                         // 0 quadratic, 1 modified L1, else Lorentzian (:665-675)
+    double eps_sq;                       // (double)(e * e), e the float the penalty's constructor takes
+    float weight;                        // weight_jet_estimation[r], a float (:489)
+};
+struct EnergyPlan { AdaptTab tab; EnergyArgs a; int rJ, J, w, h, gw, gh, incr, start, r, NN; size_t lds; };
+// the grid and adaptFPS's indices, each checked against the r_Jets flows it reads; refuses as sfa_hypothesis_energies does
+int energy_plan(sfa_ctx *ctx, const sfa_energy_params *p, int r_Jets, int Jets, int w, int h, EnergyPlan *out);
+// nf frames [nf][3][pl] packed fp32 -> dx, dy (der: 6 nf pl floats of scratch) -> rec: [nf][pl] records of 48 bytes
+void energy_records_device(sfa_ctx *ctx, size_t nf, int w, int h, const float *frames, float *der, void *rec);
+// the scratch of energies_device for n segments: U, V [n][gpl][J], occ [n][gpl], jc, oc [n][gpl], ep [n][gpl][NN]
+struct EnergyWork { double *U, *V; unsigned long long *occ; float *jc, *oc; double *ep; };
+// k_hyp_serial, k_hyp_bcgc, k_hyp_sum (and k_hyp_adapted where adapted_u is given) over n segments.  acc_u, acc_v: [n][r_Jets][gpl]; tracked: [n][gpl]; rec:
+// [n][J + 1][pl] records; fwd, bwd: [n][J] planes of float2 (identity) / double2, or null.  Segment s's energy and occlusion word go to energy / occ_out +
+// s * out_seg, its adapted flows [J][gpl] to adapted_u / adapted_v + s * adapted_seg (elements): the fusion's [n][K][gpl] and [n][K][J][gpl] take slot k at
+// base + k * gpl (k * J * gpl) with out_seg = K * gpl (adapted_seg = K * J * gpl)
+int energies_device(sfa_ctx *ctx, const EnergyPlan &pl, int n, const double *acc_u, const double *acc_v, const int *tracked, const void *rec, bool identity,
+                    const void *fwd, const void *bwd, const EnergyWork &wk, double *energy, unsigned long long *occ_out, size_t out_seg, double *adapted_u,
+                    double *adapted_v, size_t adapted_seg);
+// energies_device's last launch alone (k_hyp_adapted), for a caller that provides the adapted planes after the other kernels are enqueued
+int energies_adapted_device(sfa_ctx *ctx, const EnergyPlan &pl, int n, const int *tracked, const EnergyWork &wk, double *adapted_u, double *adapted_v, size_t adapted_seg);
+// The fusion's planes for n segments: inputs U, V [n][K][J][gpl], energy, occ [n][K][gpl], weight [n][h][w]; scratch nl [n][gpl], lab [n][gpl][16], theta
+// [n][gpl][16], P [n][2][gpl][K K], M [n][gpl][4][16], xcur, xbest [n][gpl]; outputs slot, fu, fv, out_occ [n][gpl], seg_energy, seg_bound, seg_iters [n]
+struct FuseWork {
+    const double *U, *V, *energy; const unsigned long long *occ; const float *weight;
+    unsigned char *nl, *lab; double *theta, *P, *M; unsigned char *xcur, *xbest;
+    int *slot; double *fu, *fv; unsigned char *out_occ; double *seg_energy, *seg_bound; int *seg_iters;
+};
+// zeroes the messages and labellings of the n segments, then k_fuse_labels, k_fuse_pairwise, k_trws, k_fuse_output.  ev: null or 5 events recorded around the four
+int fuse_device(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, int gw, int gh, const FuseWork &f, hipEvent_t *ev);
 
 // ---------------------------------------------------------------------------------------------------
 // kernel launchers (kernels.hip).  All planes are device pointers of batch element 0; element b lives
@@ -375,6 +425,8 @@ int sor_run(sfa_ctx *c, SorWorkspace &ws, const Geo &g, float *du, float *dv, fl
 // message that names `fn` and the argument; nothing is launched on a refusal ----------------------------------------------------------------------------
 // the frames of `nwin` windows (or pairs, or sequence frames) of F frames each: layout and pointer
 int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h);
+// p is device memory of the context's GPU, and element `last` (of `elem` bytes) lies inside its allocation
+int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem);
 // a strided fp32 field of `nd` dimensions (sizes n[], strides st[], the last one the column): the pointer and the strides' signs
 int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd);
 // download destinations: flow [n][2][h][w] at `strides`, occlusions [n][h][w] at `occ_strides` (or null): pointers, strides, and freedom from overlap

@@ -1,0 +1,538 @@
+// track.hip -- the resident track job: dense_tracking's three stages (accumulate.hip, energy.hip, fuse.hip) chained on the device for up to n start_jets of K
+// rates.  The job owns every plane between the inputs and the fused flow; sfa_track_job_run enqueues
+//     frame derivatives and records -> accumulation (all steps) per rate -> energies and adapted flows per rate, best / occluded -> smoothness weight
+//     -> labels -> pairwise -> TRW-S -> output
+// on the context's stream through the stages' device-level functions (sfa_internal.h) and returns: TRW-S's stopping rule lives inside k_trws, so nothing in
+// the chain needs a host decision, and no stage boundary crosses the host.  The flows are brought into the kernels' layout when they are uploaded (host
+// planes: a copy and the stage wrappers' kernels; device memory: the pack kernels below), so a run reads only what the job holds.
+// Segment s of a run comes out with the bits of the staged calls on that segment alone: the same kernels over the same planes, blockIdx.y = s.
+#include <algorithm>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+#include "sfa_device.h"
+
+#pragma clang fp contract(off)
+
+static_assert(sizeof(sfa_track_params) == 832, "sfa_track_params: the layout slowflow_amd/__init__.py mirrors");
+
+namespace sfa {
+
+constexpr int kTrThreads = 256;
+constexpr int kTrMaxN = 64, kTrMaxK = 16, kTrMaxJets = 32;
+
+// fp32 flows in device memory, element (segment, step, u|v, row, column) at src + the 64-bit element strides st -> float2 planes [seg][np][h][w] (the layout
+// k_accumulate and k_hyp_serial gather from).  One element per thread: two 4-byte loads, one 8-byte store.
+__global__ void __launch_bounds__(kTrThreads) k_track_pack_flow(const float *__restrict__ src, long long s_seg, long long s_step, long long s_c, long long s_row,
+                                                                long long s_col, int w, int h, int np, float2 *__restrict__ out, size_t total) {
+    const size_t i = (size_t)blockIdx.x * kTrThreads + threadIdx.x;
+    if (i >= total) return;
+    const size_t pl = (size_t)w * h, k = i / pl, p = i % pl;
+    const float *b = src + (long long)(k / np) * s_seg + (long long)(k % np) * s_step + (long long)(p / w) * s_row + (long long)(p % w) * s_col;
+    out[i] = make_float2(b[0], b[s_c]);
+}
+
+// the same source, one segment: the crop (x0, y0, cw, ch) of its np fields as packed float planes su[k], sv[k] -- what k_jet_resample reads
+__global__ void __launch_bounds__(kTrThreads) k_track_pack_planes(const float *__restrict__ src, long long s_step, long long s_c, long long s_row, long long s_col,
+                                                                  int x0, int y0, int cw, int ch, float *__restrict__ su, float *__restrict__ sv, size_t total) {
+    const size_t i = (size_t)blockIdx.x * kTrThreads + threadIdx.x;
+    if (i >= total) return;
+    const size_t spl = (size_t)cw * ch, k = i / spl, p = i % spl;
+    const float *b = src + (long long)k * s_step + (long long)(y0 + p / cw) * s_row + (long long)(x0 + p % cw) * s_col;
+    su[i] = b[0];
+    sv[i] = b[s_c];
+}
+
+// fp32 frames, element (segment, frame, channel, row, column) at src + st -> packed planes [seg][nfr][3][h][w], the planes k_energy_records reads
+__global__ void __launch_bounds__(kTrThreads) k_track_pack_frames(const float *__restrict__ src, long long s_seg, long long s_fr, long long s_c, long long s_row,
+                                                                  long long s_col, int w, int h, int nfr, float *__restrict__ out, size_t total) {
+    const size_t i = (size_t)blockIdx.x * kTrThreads + threadIdx.x;
+    if (i >= total) return;
+    const size_t pl = (size_t)w * h, k = i / pl, p = i % pl;                    // k = (seg * nfr + frame) * 3 + channel
+    const size_t fr = k / 3;
+    out[i] = src[(long long)(fr / nfr) * s_seg + (long long)(fr % nfr) * s_fr + (long long)(k % 3) * s_c + (long long)(p / w) * s_row + (long long)(p % w) * s_col];
+}
+
+// per grid pixel of segment blockIdx.y: best = the rate of the lowest fp32 energy, ties to the lower rate, 255 for none; occluded[k] = popcount of rate k's bits
+// (the host loop of the accumulate program).  E, O: [n][K][gpl]; best: [n][gpl]; occluded: [K][cap][gpl]
+__global__ void __launch_bounds__(kTrThreads) k_track_best(const double *__restrict__ E, const unsigned long long *__restrict__ O, int K, int gpl, int cap,
+                                                           unsigned char *__restrict__ best, unsigned char *__restrict__ occluded) {
+    const int i = blockIdx.x * kTrThreads + threadIdx.x;
+    if (i >= gpl) return;
+    const int s = blockIdx.y;
+    float be = __int_as_float(0x7f800000);
+    int b = 255;
+    for (int k = 0; k < K; k++) {
+        const size_t o = ((size_t)s * K + k) * gpl + i;
+        const float e = (float)E[o];                                            // an fp32 sum stored in a double: exact
+        if (e < be) { be = e; b = k; }                                          // strict: ties keep the lower rate
+        occluded[((size_t)k * cap + s) * gpl + i] = (unsigned char)__popcll(O[o]);
+    }
+    best[(size_t)s * gpl + i] = (unsigned char)b;
+}
+
+// the fused results of segments s0 .. into the caller's device memory: flow (segment, u|v, row, column) at st, packed slots, occlusions and (energy, bound,
+// iterations) per segment
+__global__ void __launch_bounds__(kTrThreads) k_track_unpack(const double *__restrict__ fu, const double *__restrict__ fv, const int *__restrict__ slot,
+                                                             const unsigned char *__restrict__ occ, const double *__restrict__ seg_energy,
+                                                             const double *__restrict__ seg_bound, const int *__restrict__ seg_iters, int gw, int gpl,
+                                                             double *__restrict__ flow, long long t_seg, long long t_c, long long t_row, long long t_col,
+                                                             int *__restrict__ slot_out, unsigned char *__restrict__ occ_out, double *__restrict__ stats) {
+    const int i = blockIdx.x * kTrThreads + threadIdx.x;
+    if (i >= gpl) return;
+    const int s = blockIdx.y;
+    const size_t si = (size_t)s * gpl + i;
+    double *f = flow + (long long)s * t_seg + (long long)(i / gw) * t_row + (long long)(i % gw) * t_col;
+    f[0] = fu[si];
+    f[t_c] = fv[si];
+    if (slot_out) slot_out[si] = slot[si];
+    if (occ_out) occ_out[si] = occ[si];
+    if (stats && i == 0) { stats[3 * s] = seg_energy[s]; stats[3 * s + 1] = seg_bound[s]; stats[3 * s + 2] = (double)seg_iters[s]; }
+}
+
+inline unsigned blocks_of(size_t total) { return (unsigned)((total + kTrThreads - 1) / kTrThreads); }
+
+}  // namespace sfa
+
+using namespace sfa;
+
+// Every plane of the job inside one allocation; this struct is the only statement of the list (sfa_track_job_bytes walks it without a device)
+struct TrackPlanes {
+    struct Rate { size_t fw, bw, mask, acc_u, acc_v, tracked; } rate[kTrMaxK];
+    size_t occluded, stage, occ_stage, frames, der, rec, wU, wV, wocc, jc, oc, ep, E, O, best;
+    size_t aU, aV, weight, nl, lab, theta, P, M, xcur, xbest, slot, fu, fv, out_occ, seg_energy, seg_bound, seg_iters;
+    size_t total;
+};
+
+struct sfa_track_job {
+    sfa_ctx *ctx = nullptr;
+    sfa_track_params p;
+    int gw = 0, gh = 0;
+    bool identity[kTrMaxK] = {};
+    EnergyPlan plan[kTrMaxK];
+    TrackPlanes at;
+    DevMem mem;
+    hipEvent_t ev[10] = {};             // [9]: after the smoothness weight, before the fusion's clears
+    bool timed = false, timed_fuse = false;
+    template <class T> T *ptr(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(mem.p) + off); }
+};
+
+// the argument checks of create and bytes (no device): everything the three stages refuse, by the name of the argument
+static int track_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, int *gw, int *gh, bool *identity, EnergyPlan *plan) {
+    if (!p) REFUSE("%s: params is null", fn);
+    if (p->n < 1 || p->n > kTrMaxN) REFUSE("%s: n = %d (1 <= n <= %d start_jets)", fn, p->n, kTrMaxN);
+    if (p->K < 1 || p->K > kTrMaxK) REFUSE("%s: K = %d (1 <= K <= %d rates)", fn, p->K, kTrMaxK);
+    if (p->Jets < 1 || p->Jets > kTrMaxJets) REFUSE("%s: Jets = %d (1 <= Jets <= %d)", fn, p->Jets, kTrMaxJets);
+    if (p->w < 1) REFUSE("%s: w = %d", fn, p->w);
+    if (p->h < 4) REFUSE("%s: h = %d; the reference's vertical 5-tap derivative needs h >= 4", fn, p->h);
+    if (p->min_fps_idx < 0 || p->min_fps_idx >= p->K) REFUSE("%s: min_fps_idx = %d names none of the %d rates", fn, p->min_fps_idx, p->K);
+    for (int r = 0; r < p->K; r++)
+        if (p->r_Jets[r] < 1) REFUSE("%s: r_Jets[%d] = %d", fn, r, p->r_Jets[r]);
+    if (p->r_Jets[p->min_fps_idx] != p->Jets)
+        REFUSE("%s: r_Jets[%d] = %d, not Jets = %d: rate min_fps_idx's flows are the Jets steps the energies read", fn, p->min_fps_idx, p->r_Jets[p->min_fps_idx], p->Jets);
+    if (p->do_fuse) {
+        if (p->fuse.traj_sim_method != 0 && p->fuse.traj_sim_method != 1)
+            REFUSE("%s: fuse.traj_sim_method %d (0 ADJ, 1 ACC; 2 FINAL reads flow_y[Jets], past the array)", fn, p->fuse.traj_sim_method);
+        if (p->fuse.trws_max_iter < 1) REFUSE("%s: fuse.trws_max_iter %d < 1", fn, p->fuse.trws_max_iter);
+    }
+    if (sfa_accumulate_grid(p->w, p->h, p->skip, gw, gh) != SFA_OK) REFUSE("%s: skip: %s", fn, sfa_last_error(nullptr));
+    if (((size_t)*gw * *gh * p->K * p->K + kTrThreads - 1) / kTrThreads > 0x7fffffffull) REFUSE("%s: grid too large", fn);
+    for (int r = 0; r < p->K; r++) {
+        char name[96];
+        snprintf(name, sizeof name, "%s: source[%d]", fn, r);
+        const sfa_jet_source &s = p->source[r];
+        SFA_TRY(jet_source_check(ctx, name, &s, p->w, p->h, &identity[r]));
+        if (p->use_occlusions && (s.x0 != 0 || s.y0 != 0 || s.cw != s.sw || s.ch != s.sh))
+            REFUSE("%s: source: cropped occlusions are not supported (the reference's crop() reads the 8-bit Mat through at<Vec2d>)", name);
+        sfa_energy_params ep = p->energy;
+        ep.skip = p->skip;
+        ep.weight = p->weight[r];
+        SFA_TRY(energy_plan(ctx, &ep, p->r_Jets[r], p->Jets, p->w, p->h, &plan[r]));
+    }
+    return SFA_OK;
+}
+
+static void track_layout(const sfa_track_params &p, int gw, int gh, const bool *identity, int NN, TrackPlanes *out) {
+    TrackPlanes &a = *out;
+    size_t top = 0;
+    auto take = [&](size_t bytes) { const size_t o = top; top += (bytes + 255) / 256 * 256; return o; };
+    const size_t n = p.n, K = p.K, J = p.Jets, pl = (size_t)p.w * p.h, gpl = (size_t)gw * gh;
+    size_t stage = 0, occ_stage = 0;
+    for (int r = 0; r < p.K; r++) {
+        const size_t rJ = p.r_Jets[r], tap = identity[r] ? 8 : 16, spl = identity[r] ? pl : (size_t)p.source[r].cw * p.source[r].ch;
+        a.rate[r].fw = take(n * rJ * pl * tap);
+        a.rate[r].bw = take(n * rJ * pl * tap);
+        a.rate[r].mask = p.use_occlusions ? take(n * rJ * pl) : 0;
+        a.rate[r].acc_u = take(n * rJ * gpl * 8);
+        a.rate[r].acc_v = take(n * rJ * gpl * 8);
+        a.rate[r].tracked = take(n * gpl * 4);
+        stage = std::max(stage, 2 * rJ * spl * 4);                              // one segment's u and v planes of one direction
+        occ_stage = std::max(occ_stage, rJ * (size_t)p.source[r].sw * p.source[r].sh);
+    }
+    a.occluded = take(K * n * gpl);                                             // [K][n][gpl]
+    a.stage = take(stage);
+    a.occ_stage = p.use_occlusions ? take(occ_stage) : 0;
+    a.frames = take(n * (J + 1) * 3 * pl * 4);
+    a.der = take(n * (J + 1) * 6 * pl * 4);
+    a.rec = take(n * (J + 1) * pl * 48);
+    a.wU = take(n * J * gpl * 8); a.wV = take(n * J * gpl * 8); a.wocc = take(n * gpl * 8);
+    a.jc = take(n * gpl * 4); a.oc = take(n * gpl * 4); a.ep = take(n * gpl * NN * 8);
+    a.E = take(n * K * gpl * 8); a.O = take(n * K * gpl * 8); a.best = take(n * gpl);
+    if (p.do_fuse) {
+        a.aU = take(n * K * J * gpl * 8); a.aV = take(n * K * J * gpl * 8); a.weight = take(n * pl * 4);
+        a.nl = take(n * gpl); a.lab = take(n * gpl * 16); a.theta = take(n * gpl * 16 * 8); a.P = take(n * 2 * gpl * K * K * 8);
+        a.M = take(n * gpl * 4 * 16 * 8); a.xcur = take(n * gpl); a.xbest = take(n * gpl);
+        a.slot = take(n * gpl * 4); a.fu = take(n * gpl * 8); a.fv = take(n * gpl * 8); a.out_occ = take(n * gpl);
+        a.seg_energy = take(n * 8); a.seg_bound = take(n * 8); a.seg_iters = take(n * 4);
+    }
+    a.total = top;
+}
+
+void sfa_track_params_default(sfa_track_params *p) {
+    if (!p) return;
+    *p = sfa_track_params{};
+    p->n = 1; p->K = 1; p->Jets = 1; p->do_fuse = 1;
+    p->epsilon = 1.0;                    // acc_consistency_threshold
+    p->skip = 1;                         // acc_skip_pixel
+    p->discard = 1;                      // acc_discard_inconsistent
+    sfa_energy_params_default(&p->energy);
+    sfa_fuse_params_default(&p->fuse);
+    p->coef = 5.0f;                      // computeSmoothnessWeight's call (dense_tracking.cpp:969-981)
+    for (int k = 0; k < 3; k++) p->std_dev[k] = 1.0f;
+    for (int r = 0; r < kTrMaxK; r++) { p->r_Jets[r] = 1; p->weight[r] = (float)r; }   // weight_jet_estimation[r] = r where none is given
+}
+
+int sfa_track_job_bytes(const sfa_track_params *p, size_t *bytes) {
+    sfa_ctx *ctx = nullptr;
+    if (!bytes) REFUSE("%s: bytes is null", __func__);
+    int gw, gh;
+    bool identity[kTrMaxK];
+    EnergyPlan plan[kTrMaxK];
+    SFA_TRY(track_check(ctx, __func__, p, &gw, &gh, identity, plan));
+    TrackPlanes at{};
+    track_layout(*p, gw, gh, identity, plan[0].NN, &at);
+    *bytes = at.total;
+    return SFA_OK;
+}
+
+int sfa_track_job_create(sfa_ctx *ctx, const sfa_track_params *p, sfa_track_job **out) {
+    if (!ctx || !out) REFUSE("%s: ctx or job is null", __func__);
+    *out = nullptr;
+    sfa_track_job *j = new sfa_track_job;
+    struct Guard { sfa_track_job *j; ~Guard() { if (j) sfa_track_job_destroy(j); } } guard{j};
+    j->ctx = ctx;
+    SFA_TRY(track_check(ctx, __func__, p, &j->gw, &j->gh, j->identity, j->plan));
+    j->p = *p;
+    j->p.energy.skip = j->p.fuse.skip = p->skip;
+    track_layout(j->p, j->gw, j->gh, j->identity, j->plan[0].NN, &j->at);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(j->mem.alloc(ctx, j->at.total));
+    SFA_HIP(ctx, hipMemsetAsync(j->mem.p, 0, j->at.total, ctx->stream));        // a run before an upload reads zeros, not another job's planes
+    for (auto &e : j->ev) SFA_HIP(ctx, hipEventCreate(&e));
+    guard.j = nullptr;
+    *out = j;
+    return SFA_OK;
+}
+
+void sfa_track_job_destroy(sfa_track_job *job) {
+    if (!job) return;
+    if (job->ctx && job->ctx->stream) (void)hipStreamSynchronize(job->ctx->stream);
+    for (auto &e : job->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete job;
+}
+
+#define TRACK_JOB(job) \
+    if (!(job)) return sfa::set_error(nullptr, SFA_ERR_ARG, "%s: job is null", __func__); \
+    sfa_ctx *ctx = (job)->ctx; \
+    const sfa_track_params &p = (job)->p; \
+    const size_t pl = (size_t)p.w * p.h, gpl = (size_t)(job)->gw * (job)->gh; \
+    (void)pl; (void)gpl
+
+static int track_range(sfa_ctx *ctx, const char *fn, const sfa_track_params &p, int s0, int ns, int r) {
+    if (s0 < 0 || ns < 1 || (long)s0 + ns > p.n) {
+        if (ns == 1) REFUSE("%s: s = %d lies outside the job's %d start_jets", fn, s0, p.n);
+        REFUSE("%s: s0 = %d, ns = %d lie outside the job's %d start_jets", fn, s0, ns, p.n);
+    }
+    if (r < 0 || r >= p.K) REFUSE("%s: r = %d names none of the job's %d rates", fn, r, p.K);
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_flows(sfa_track_job *job, int s, int r, const float *const *fwd_u, const float *const *fwd_v, const float *const *bwd_u,
+                               const float *const *bwd_v, const unsigned char *const *occ) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, r));
+    if (!(fwd_u && fwd_v && bwd_u && bwd_v)) REFUSE("%s: null flow array", __func__);
+    if (p.use_occlusions && !occ) REFUSE("%s: occ is null on a job with use_occlusions", __func__);
+    const int rJ = p.r_Jets[r];
+    for (int k = 0; k < rJ; k++)
+        if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k] || (p.use_occlusions && !occ[k])) REFUSE("%s: null plane %d", __func__, k);
+    const sfa_jet_source &src = p.source[r];
+    const bool identity = job->identity[r];
+    const size_t tap = identity ? 8 : 16, seg = (size_t)s * rJ * pl;
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    float *stage = job->ptr<float>(job->at.stage);
+    for (int dir = 0; dir < 2; dir++) {
+        const float *const *U = dir ? bwd_u : fwd_u, *const *V = dir ? bwd_v : fwd_v;
+        char *dst = job->ptr<char>(dir ? job->at.rate[r].bw : job->at.rate[r].fw) + seg * tap;
+        if (!identity) {
+            SFA_TRY(jet_resample_flows(ctx, src, (size_t)rJ, U, V, p.w, p.h, stage, reinterpret_cast<double2 *>(dst), nullptr, nullptr));
+            continue;
+        }
+        float *su = stage, *sv = stage + (size_t)rJ * pl;
+        for (int k = 0; k < rJ; k++) {                                          // the valid columns of each plane, packed, then interleaved
+            SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)p.w * 4, U[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice, ctx->stream));
+            SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)p.w * 4, V[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice, ctx->stream));
+        }
+        launch_interleave(ctx, su, sv, reinterpret_cast<float2 *>(dst), (size_t)rJ * pl);
+        SFA_HIP(ctx, hipGetLastError());
+    }
+    if (p.use_occlusions)
+        SFA_TRY(jet_decode_occlusions(ctx, src, (size_t)rJ, occ, p.w, p.h, job->ptr<unsigned char>(job->at.occ_stage),
+                                      job->ptr<unsigned char>(job->at.rate[r].mask) + seg));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // the caller's planes are free again
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_frames(sfa_track_job *job, int s, const float *const *frames, int stride) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, 0));
+    if (!frames) REFUSE("%s: frames is null", __func__);
+    if (stride < p.w) REFUSE("%s: stride = %d < w = %d", __func__, stride, p.w);
+    for (int k = 0; k <= p.Jets; k++)
+        if (!frames[k]) REFUSE("%s: null frame %d", __func__, k);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    float *dst = job->ptr<float>(job->at.frames) + (size_t)s * (p.Jets + 1) * 3 * pl;
+    for (int k = 0; k <= p.Jets; k++)
+        for (int c = 0; c < 3; c++)
+            SFA_HIP(ctx, hipMemcpy2DAsync(dst + ((size_t)k * 3 + c) * pl, (size_t)p.w * 4, frames[k] + (size_t)c * p.h * stride, (size_t)stride * 4, (size_t)p.w * 4,
+                                          p.h, hipMemcpyHostToDevice, ctx->stream));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r, const float *fwd_dev, const float *bwd_dev, const long long strides[5]) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, r));
+    if (p.use_occlusions) REFUSE("%s: the job was created with use_occlusions: its occlusion images come with sfa_track_job_upload_flows", __func__);
+    const sfa_jet_source &src = p.source[r];
+    const int rJ = p.r_Jets[r], sz[5] = {ns, rJ, 2, src.sh, src.sw};
+    if (!fwd_dev || !bwd_dev) REFUSE("%s: %s is null", __func__, fwd_dev ? "bwd_dev" : "fwd_dev");
+    SFA_TRY(check_field(ctx, __func__, "fwd_dev", fwd_dev, strides, sz, 5));
+    SFA_TRY(check_field(ctx, __func__, "bwd_dev", bwd_dev, strides, sz, 5));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const bool identity = job->identity[r];
+    const size_t tap = identity ? 8 : 16, seg = (size_t)rJ * pl;
+    for (int dir = 0; dir < 2; dir++) {
+        const float *from = dir ? bwd_dev : fwd_dev;
+        char *dst = job->ptr<char>(dir ? job->at.rate[r].bw : job->at.rate[r].fw) + (size_t)s0 * seg * tap;
+        if (identity) {
+            const size_t total = (size_t)ns * seg;
+            hipLaunchKernelGGL(k_track_pack_flow, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, from, strides[0], strides[1], strides[2], strides[3],
+                               strides[4], p.w, p.h, rJ, reinterpret_cast<float2 *>(dst), total);
+            SFA_HIP(ctx, hipGetLastError());
+            continue;
+        }
+        const size_t spl = (size_t)src.cw * src.ch, total = (size_t)rJ * spl;   // segment by segment through the one-segment stage, in stream order
+        float *su = job->ptr<float>(job->at.stage), *sv = su + total;
+        for (int s = 0; s < ns; s++) {
+            hipLaunchKernelGGL(k_track_pack_planes, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, from + (long long)s * strides[0], strides[1], strides[2],
+                               strides[3], strides[4], src.x0, src.y0, src.cw, src.ch, su, sv, total);
+            SFA_HIP(ctx, hipGetLastError());
+            SFA_TRY(launch_jet_resample(ctx, src, (size_t)rJ, su, sv, p.w, p.h, reinterpret_cast<double2 *>(dst + (size_t)s * seg * tap)));
+        }
+    }
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_frames_device(sfa_track_job *job, int s0, int ns, const float *frames_dev, const long long strides[5]) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
+    if (!frames_dev) REFUSE("%s: frames_dev is null", __func__);
+    const int sz[5] = {ns, p.Jets + 1, 3, p.h, p.w};
+    SFA_TRY(check_field(ctx, __func__, "frames_dev", frames_dev, strides, sz, 5));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t total = (size_t)ns * (p.Jets + 1) * 3 * pl;
+    hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, frames_dev, strides[0], strides[1], strides[2], strides[3],
+                       strides[4], p.w, p.h, p.Jets + 1, job->ptr<float>(job->at.frames) + (size_t)s0 * (p.Jets + 1) * 3 * pl, total);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_track_job_run(sfa_track_job *job, int ns) {
+    TRACK_JOB(job);
+    if (ns < 1 || ns > p.n) REFUSE("%s: ns = %d (1 <= ns <= n = %d, the job's start_jets)", __func__, ns, p.n);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const TrackPlanes &at = job->at;
+    const int K = p.K, J = p.Jets, mf = p.min_fps_idx;
+    hipEvent_t *ev = job->ev;
+    SFA_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+    energy_records_device(ctx, (size_t)ns * (J + 1), p.w, p.h, job->ptr<float>(at.frames), job->ptr<float>(at.der), job->ptr<void>(at.rec));
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+    for (int r = 0; r < K; r++)
+        SFA_TRY(accumulate_device(ctx, ns, p.r_Jets[r], p.w, p.h, job->gw, job->gh, p.skip, job->identity[r], job->ptr<void>(at.rate[r].fw),
+                                  job->ptr<void>(at.rate[r].bw), p.use_occlusions ? job->ptr<unsigned char>(at.rate[r].mask) : nullptr, p.epsilon, p.discard, 1,
+                                  job->ptr<double>(at.rate[r].acc_u), job->ptr<double>(at.rate[r].acc_v), job->ptr<int>(at.rate[r].tracked)));
+    SFA_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+    EnergyWork wk;
+    wk.U = job->ptr<double>(at.wU); wk.V = job->ptr<double>(at.wV); wk.occ = job->ptr<unsigned long long>(at.wocc);
+    wk.jc = job->ptr<float>(at.jc); wk.oc = job->ptr<float>(at.oc); wk.ep = job->ptr<double>(at.ep);
+    double *E = job->ptr<double>(at.E);
+    unsigned long long *O = job->ptr<unsigned long long>(at.O);
+    for (int r = 0; r < K; r++) {
+        const bool flows = r >= mf;                                             // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
+        SFA_TRY(energies_device(ctx, job->plan[r], ns, job->ptr<double>(at.rate[r].acc_u), job->ptr<double>(at.rate[r].acc_v), job->ptr<int>(at.rate[r].tracked),
+                                job->ptr<void>(at.rec), job->identity[mf], flows ? job->ptr<void>(at.rate[mf].fw) : nullptr,
+                                flows ? job->ptr<void>(at.rate[mf].bw) : nullptr, wk, E + (size_t)r * gpl, O + (size_t)r * gpl, (size_t)K * gpl,
+                                p.do_fuse ? job->ptr<double>(at.aU) + (size_t)r * J * gpl : nullptr, p.do_fuse ? job->ptr<double>(at.aV) + (size_t)r * J * gpl : nullptr,
+                                (size_t)K * J * gpl));
+    }
+    const dim3 pix(blocks_of(gpl), (unsigned)ns);
+    hipLaunchKernelGGL(k_track_best, pix, dim3(kTrThreads), 0, ctx->stream, E, O, K, (int)gpl, p.n, job->ptr<unsigned char>(at.best),
+                       job->ptr<unsigned char>(at.occluded));
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
+    job->timed = true;
+    job->timed_fuse = false;
+    if (!p.do_fuse) return SFA_OK;
+    // computeSmoothnessWeight of every segment's normalised frame 0 (sfa_dt_smoothness_weight's kernel) on the packed planes
+    Geo g{p.w, p.h, p.w, (long)pl, (long)pl, ns, WMask::first(ns), nullptr};
+    launch_dpsis(ctx, g, job->ptr<float>(at.weight), job->ptr<float>(at.frames), (long)((size_t)(J + 1) * 3 * pl), p.coef, p.avg, p.std_dev, p.hbit);
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_HIP(ctx, hipEventRecord(ev[9], ctx->stream));
+    FuseWork f;
+    f.U = job->ptr<double>(at.aU); f.V = job->ptr<double>(at.aV); f.energy = E; f.occ = O; f.weight = job->ptr<float>(at.weight);
+    f.nl = job->ptr<unsigned char>(at.nl); f.lab = job->ptr<unsigned char>(at.lab); f.theta = job->ptr<double>(at.theta); f.P = job->ptr<double>(at.P);
+    f.M = job->ptr<double>(at.M); f.xcur = job->ptr<unsigned char>(at.xcur); f.xbest = job->ptr<unsigned char>(at.xbest);
+    f.slot = job->ptr<int>(at.slot); f.fu = job->ptr<double>(at.fu); f.fv = job->ptr<double>(at.fv); f.out_occ = job->ptr<unsigned char>(at.out_occ);
+    f.seg_energy = job->ptr<double>(at.seg_energy); f.seg_bound = job->ptr<double>(at.seg_bound); f.seg_iters = job->ptr<int>(at.seg_iters);
+    SFA_TRY(fuse_device(ctx, &p.fuse, ns, K, J, p.w, p.h, job->gw, job->gh, f, ev + 4));
+    job->timed_fuse = true;
+    return SFA_OK;
+}
+
+int sfa_track_job_download_rate(sfa_track_job *job, int s, int r, double *acc_u_last, double *acc_v_last, int *tracked, double *energy,
+                                unsigned long long *occ_bits, unsigned char *occluded) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, r));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const TrackPlanes::Rate &a = job->at.rate[r];
+    const size_t last = ((size_t)s * p.r_Jets[r] + (p.r_Jets[r] - 1)) * gpl, sk = ((size_t)s * p.K + r) * gpl;
+    auto get = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
+    SFA_HIP(ctx, get(acc_u_last, job->ptr<double>(a.acc_u) + last, gpl * 8));
+    SFA_HIP(ctx, get(acc_v_last, job->ptr<double>(a.acc_v) + last, gpl * 8));
+    SFA_HIP(ctx, get(tracked, job->ptr<int>(a.tracked) + (size_t)s * gpl, gpl * 4));
+    SFA_HIP(ctx, get(energy, job->ptr<double>(job->at.E) + sk, gpl * 8));
+    SFA_HIP(ctx, get(occ_bits, job->ptr<unsigned long long>(job->at.O) + sk, gpl * 8));
+    SFA_HIP(ctx, get(occluded, job->ptr<unsigned char>(job->at.occluded) + ((size_t)r * p.n + s) * gpl, gpl));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SFA_OK;
+}
+
+int sfa_track_job_download_fused(sfa_track_job *job, int s, int *slot, double *flow_u, double *flow_v, unsigned char *occ, unsigned char *best, double *energy,
+                                 double *bound, int *iters) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, 0));
+    if (!p.do_fuse) REFUSE("%s: the job was created with do_fuse = 0: it holds no fused result", __func__);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const TrackPlanes &at = job->at;
+    const size_t o = (size_t)s * gpl;
+    auto get = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
+    SFA_HIP(ctx, get(slot, job->ptr<int>(at.slot) + o, gpl * 4));
+    SFA_HIP(ctx, get(flow_u, job->ptr<double>(at.fu) + o, gpl * 8));
+    SFA_HIP(ctx, get(flow_v, job->ptr<double>(at.fv) + o, gpl * 8));
+    SFA_HIP(ctx, get(occ, job->ptr<unsigned char>(at.out_occ) + o, gpl));
+    SFA_HIP(ctx, get(best, job->ptr<unsigned char>(at.best) + o, gpl));
+    SFA_HIP(ctx, get(energy, job->ptr<double>(at.seg_energy) + s, 8));
+    SFA_HIP(ctx, get(bound, job->ptr<double>(at.seg_bound) + s, 8));
+    SFA_HIP(ctx, get(iters, job->ptr<int>(at.seg_iters) + s, 4));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SFA_OK;
+}
+
+int sfa_track_job_download_best(sfa_track_job *job, int s, unsigned char *best) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, 0));
+    if (!best) REFUSE("%s: best is null", __func__);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_HIP(ctx, hipMemcpyAsync(best, job->ptr<unsigned char>(job->at.best) + (size_t)s * gpl, gpl, hipMemcpyDeviceToHost, ctx->stream));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SFA_OK;
+}
+
+int sfa_ctx_free_bytes(sfa_ctx *ctx, size_t *free_bytes) {
+    if (!ctx || !free_bytes) REFUSE("%s: null argument", __func__);
+    size_t total = 0;
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_HIP(ctx, hipMemGetInfo(free_bytes, &total));
+    return SFA_OK;
+}
+
+// a destination's byte range [lo, hi) and whether its strides nest: sorted by stride, each at least the extent of all smaller ones, so that no two elements
+// share an address (dimensions of size 1 do not count)
+static bool nested(const long long *st, const int *n, int nd) {
+    std::vector<std::pair<long long, int>> d;
+    for (int i = 0; i < nd; i++)
+        if (n[i] > 1) d.emplace_back(st[i], n[i]);
+    std::sort(d.begin(), d.end());
+    long long extent = 1;
+    for (auto &q : d) {
+        if (q.first < extent) return false;
+        extent = q.first * (q.second - 1) + extent;
+    }
+    return true;
+}
+
+int sfa_track_job_download_device(sfa_track_job *job, int s0, int ns, double *flow_dev, const long long strides[4], int *slot_dev, unsigned char *occ_dev,
+                                  double *stats_dev) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
+    if (!p.do_fuse) REFUSE("%s: the job was created with do_fuse = 0: it holds no fused result", __func__);
+    if (!flow_dev) REFUSE("%s: flow_dev is null", __func__);
+    if (!strides) REFUSE("%s: the strides of flow_dev are null", __func__);
+    const int sz[4] = {ns, 2, job->gh, job->gw};
+    long long last = 0;
+    for (int i = 0; i < 4; i++) {
+        if (strides[i] < (i == 3 ? 1 : 0)) REFUSE("%s: stride %d of flow_dev is %lld", __func__, i, strides[i]);
+        long long t;
+        if (__builtin_mul_overflow((long long)(sz[i] - 1), strides[i], &t) || __builtin_add_overflow(last, t, &last))
+            REFUSE("%s: the strides of flow_dev reach beyond the 64-bit range", __func__);
+    }
+    if (!nested(strides, sz, 4)) REFUSE("%s: the strides of flow_dev (%lld, %lld, %lld, %lld) let two elements of [%d][2][%d][%d] share an address", __func__,
+                                        strides[0], strides[1], strides[2], strides[3], ns, job->gh, job->gw);
+    SFA_TRY(check_device_pointer(ctx, __func__, "flow_dev", flow_dev, last, 8));
+    if (slot_dev) SFA_TRY(check_device_pointer(ctx, __func__, "slot_dev", slot_dev, (long long)((size_t)ns * gpl) - 1, 4));
+    if (occ_dev) SFA_TRY(check_device_pointer(ctx, __func__, "occ_dev", occ_dev, (long long)((size_t)ns * gpl) - 1, 1));
+    if (stats_dev) SFA_TRY(check_device_pointer(ctx, __func__, "stats_dev", stats_dev, 3ll * ns - 1, 8));
+    struct Range { const char *name; uintptr_t lo, hi; } rg[4] = {
+        {"flow_dev", reinterpret_cast<uintptr_t>(flow_dev), reinterpret_cast<uintptr_t>(flow_dev) + ((size_t)last + 1) * 8},
+        {"slot_dev", reinterpret_cast<uintptr_t>(slot_dev), reinterpret_cast<uintptr_t>(slot_dev) + (size_t)ns * gpl * 4},
+        {"occ_dev", reinterpret_cast<uintptr_t>(occ_dev), reinterpret_cast<uintptr_t>(occ_dev) + (size_t)ns * gpl},
+        {"stats_dev", reinterpret_cast<uintptr_t>(stats_dev), reinterpret_cast<uintptr_t>(stats_dev) + (size_t)ns * 24}};
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++)
+            if (rg[a].lo && rg[b].lo && rg[a].lo < rg[b].hi && rg[b].lo < rg[a].hi) REFUSE("%s: %s and %s overlap", __func__, rg[a].name, rg[b].name);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const TrackPlanes &at = job->at;
+    const size_t o = (size_t)s0 * gpl;
+    hipLaunchKernelGGL(k_track_unpack, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr<double>(at.fu) + o, job->ptr<double>(at.fv) + o,
+                       job->ptr<int>(at.slot) + o, job->ptr<unsigned char>(at.out_occ) + o, job->ptr<double>(at.seg_energy) + s0, job->ptr<double>(at.seg_bound) + s0,
+                       job->ptr<int>(at.seg_iters) + s0, job->gw, (int)gpl, flow_dev, strides[0], strides[1], strides[2], strides[3], slot_dev, occ_dev, stats_dev);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_track_job_stage_ms(sfa_track_job *job, float ms[8]) {
+    TRACK_JOB(job);
+    if (!ms) REFUSE("%s: ms is null", __func__);
+    if (!job->timed) REFUSE("%s: the job has not run", __func__);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 8; i++) ms[i] = 0;
+    const int last = job->timed_fuse ? 8 : 3;
+    for (int i = 0; i < last; i++)                                              // ms[3]: the weight kernel alone, without the fusion's clears behind it
+        SFA_HIP(ctx, hipEventElapsedTime(&ms[i], job->ev[i], job->ev[i == 3 ? 9 : i + 1]));
+    return SFA_OK;
+}

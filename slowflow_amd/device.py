@@ -2,8 +2,9 @@
 and results that live in GPU memory go in and out of a job without a host copy.
 
 The core takes any object with `__cuda_array_interface__` (torch-ROCm tensors, cupy arrays ...) and needs no torch; `import slowflow_amd` does not
-import this module, and this module imports torch only inside refine() and refine_pairs(), to allocate the outputs and to find the caller's current
-stream.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which never waits for the GPU.
+import this module, and this module imports torch only inside refine(), refine_pairs() and track(), to allocate the outputs and to find the caller's
+current stream.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which never waits for the
+GPU; track() dense_tracking's accumulation, energies and fusion on a resident track job, which does not wait either.
 
 Stream contract: the library works on the context's own stream.  Context.wait_stream(s) before the first call makes that stream wait for what the
 caller has submitted to s; Context.signal_stream(s) after the last makes s wait for the library.  refine() and refine_pairs() do both.  With the two in place a tensor
@@ -39,10 +40,11 @@ class DeviceView:
         return DeviceView(self.ptr + start * self.strides[0] * self.itemsize, self.dtype, self.itemsize, (n,) + self.shape[1:], self.strides, self.owner)
 
 
-def device_view(obj, writable=False, name="array", ndim=None):
+def device_view(obj, writable=False, name="array", ndim=None, kinds=None):
     """obj.__cuda_array_interface__ -> DeviceView.  Refuses (SlowflowError naming `name`): objects without the interface (host arrays), element types
     other than fp32 / u8 / u16, non-native byte order, byte strides that are no multiple of the item size, a read-only object asked for as an output,
-    and a rank other than `ndim`.  Whether the pointer is device memory of the job's GPU is the library's check, made before anything is launched."""
+    and a rank other than `ndim`.  kinds: the element types taken instead of those three, e.g. ("f8",) for the track job's fp64 flow (the view's
+    dtype is then None: no sfa_dev_dtype names them).  Whether the pointer is device memory of the job's GPU is the library's check, made before anything is launched."""
     if isinstance(obj, DeviceView):
         v = obj
     else:
@@ -54,14 +56,16 @@ def device_view(obj, writable=False, name="array", ndim=None):
         native = "<" if sys.byteorder == "little" else ">"
         if order not in (native, "|", "="):
             raise sfa.SlowflowError(f"{name}: byte order of typestr {typestr!r} is not the machine's")
-        if kind not in DTYPES:
+        if kinds is not None and kind not in kinds:
+            raise sfa.SlowflowError(f"{name}: element type {typestr!r}, expected {' or '.join(kinds)}")
+        if kinds is None and kind not in DTYPES:
             raise sfa.SlowflowError(f"{name}: element type {typestr!r} is not supported (fp32, uint8 and uint16 are; fp16, bf16, fp64 and signed integers are not)")
         item = int(kind[1:])
         shape = tuple(int(s) for s in cai["shape"])
         ptr, readonly = cai["data"]
         if writable and readonly:
             raise sfa.SlowflowError(f"{name}: the object is read-only and cannot be an output")
-        if writable and kind != "f4":
+        if writable and kinds is None and kind != "f4":
             raise sfa.SlowflowError(f"{name}: outputs are fp32, not {typestr!r}")
         bst = cai.get("strides")
         if bst is None:
@@ -76,7 +80,7 @@ def device_view(obj, writable=False, name="array", ndim=None):
             st = tuple(int(b) // item for b in bst)
         if any(s == 0 for s in shape):
             raise sfa.SlowflowError(f"{name}: empty array, shape {shape}")
-        v = DeviceView(int(ptr or 0), DTYPES[kind], item, shape, st, obj)
+        v = DeviceView(int(ptr or 0), DTYPES.get(kind), item, shape, st, obj)
     if ndim is not None and len(v.shape) != ndim:
         raise sfa.SlowflowError(f"{name}: rank {len(v.shape)}, shape {v.shape}; {ndim} dimensions expected")
     return v
@@ -122,6 +126,9 @@ def _lib():
         L.sfa_dev_layout_default.restype = None
         L.sfa_demosaic_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MosaicDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.sfa_sequence_upload_mosaic_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(MosaicDesc), C.c_int, C.c_int, C.c_int]
+        L.sfa_track_job_upload_flows_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sfa_track_job_upload_frames_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.sfa_track_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _bound = True
     return L
 
@@ -286,6 +293,8 @@ def release_jobs(ctx):
         job.close()
     for job in ctx.__dict__.pop("_refine_pair_jobs", {}).values():
         job.close()
+    for job in ctx.__dict__.pop("_track_jobs", {}).values():
+        job.close()
 
 
 def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, stream=None, channels_last=None, raw_weights=None):
@@ -425,3 +434,102 @@ def refine_pairs(ctx, frames, flow0=None, params=None, *, stream=None, channels_
     finally:
         signal_stream(ctx, stream)
     return out
+
+
+# ---- resident track jobs (sfa_track_job): dense_tracking's accumulation, energies and fusion -----------------------------------------------------
+_LL5 = C.c_longlong * 5
+
+
+def _fp32_view(obj, name, shape):
+    """an fp32 device array of `shape` (None: any size) as a DeviceView; other element types, host tensors and other shapes are refused by name"""
+    if getattr(obj, "is_cuda", True) is False:                  # a torch tensor on the CPU raises from its __cuda_array_interface__
+        raise sfa.SlowflowError(f"{name}: a tensor on {getattr(obj, 'device', 'the host')}, not in GPU memory (the device entry points take device memory)")
+    v = device_view(obj, name=name, ndim=len(shape), kinds=("f4",))
+    if any(want is not None and got != want for got, want in zip(v.shape, shape)):
+        raise sfa.SlowflowError(f"{name}: shape {v.shape}, expected {list(shape)} (None: any)")
+    return v
+
+
+def track_job_upload_flows_device(job, r, fwd, bwd, s0=0):
+    src, rJ = job.params.source[r], job.params.r_Jets[r]
+    fv = _fp32_view(fwd, "fwd", (None, rJ, 2, src.sh, src.sw))
+    bv = _fp32_view(bwd, "bwd", (fv.shape[0], rJ, 2, src.sh, src.sw))
+    if bv.strides != fv.strides:
+        raise sfa.SlowflowError(f"bwd: element strides {bv.strides} differ from fwd's {fv.strides}: the two directions share one layout")
+    job.ctx._ck(_lib().sfa_track_job_upload_flows_device(job.h_, int(s0), fv.shape[0], int(r), C.c_void_p(fv.ptr), C.c_void_p(bv.ptr), _LL5(*fv.strides)),
+                "sfa_track_job_upload_flows_device")
+
+
+def track_job_upload_frames_device(job, frames, s0=0):
+    v = _fp32_view(frames, "frames", (None, job.Jets + 1, 3, job.h, job.w))
+    job.ctx._ck(_lib().sfa_track_job_upload_frames_device(job.h_, int(s0), v.shape[0], C.c_void_p(v.ptr), _LL5(*v.strides)), "sfa_track_job_upload_frames_device")
+
+
+def _typed_view(obj, name, kind, shape, contiguous=True):
+    """(pointer, element strides) of a writable device array of one element type and shape, through device_view"""
+    v = device_view(obj, writable=True, name=name, ndim=len(shape), kinds=(kind,))
+    if v.shape != tuple(shape):
+        raise sfa.SlowflowError(f"{name}: shape {v.shape}, expected {tuple(shape)}")
+    dense = tuple(int(np.prod(shape[i + 1:])) for i in range(len(shape)))
+    if contiguous and v.strides != dense:
+        raise sfa.SlowflowError(f"{name}: a contiguous array expected, element strides {v.strides}")
+    return v.ptr, v.strides
+
+
+def track_job_download_device(job, flow, slot=None, occ=None, stats=None, s0=0):
+    ns = int(flow.shape[0])
+    fp, fst = _typed_view(flow, "flow", "f8", (ns, 2, job.gh, job.gw), contiguous=False)
+    ptrs = [_typed_view(a, name, t, shp)[0] if a is not None else None
+            for a, name, t, shp in ((slot, "slot", "i4", (ns, job.gh, job.gw)), (occ, "occ", "u1", (ns, job.gh, job.gw)), (stats, "stats", "f8", (ns, 3)))]
+    job.ctx._ck(_lib().sfa_track_job_download_device(job.h_, int(s0), ns, C.c_void_p(fp), _LL4(*fst), *[C.c_void_p(p) if p is not None else None for p in ptrs]),
+                "sfa_track_job_download_device")
+
+
+def _track_job_for(ctx, params):
+    cache = ctx.__dict__.setdefault("_track_jobs", OrderedDict())
+    key = bytes(params)
+    job = cache.get(key)
+    if job is not None and job.h_:
+        return job
+    while len(cache) >= 2:
+        cache.popitem(last=False)[1].close()
+    job = cache[key] = sfa.TrackJob(ctx, params)
+    return job
+
+
+def track(ctx, params, flows, frames, *, stream=None):
+    """dense_tracking's accumulation, energies and fusion of ns start_jets whose inputs live on the context's GPU.  params: sfa.track_params(...) with
+    do_fuse 1 and without occlusions, n >= ns; flows = [(fwd_r, bwd_r), ...], one pair of fp32 tensors [ns, r_Jets[r], 2, sh, sw] per rate; frames = an
+    fp32 tensor [ns, Jets + 1, 3, h, w] of normalised frames; any strides with a positive column stride.  Returns (flow [ns,2,gh,gw] float64, slot
+    [ns,gh,gw] int32, occ [ns,gh,gw] uint8, stats [ns,3] float64: energy, bound, iterations) as new tensors on that device.  The work is ordered after what
+    `stream` (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues (a job of new
+    parameters is created first, which waits).  The job stays on the context for the next call (ctx.close() frees it)."""
+    import torch
+    if len(flows) != params.K:
+        raise sfa.SlowflowError(f"flows: {len(flows)} (fwd, bwd) pairs for {params.K} rates")
+    fv = _fp32_view(frames, "frames", (None, params.Jets + 1, 3, params.h, params.w))      # every view is checked before a job is created or anything uploaded
+    ns = fv.shape[0]
+    if not 1 <= ns <= params.n:
+        raise sfa.SlowflowError(f"frames: {ns} start_jets, the parameters' capacity n is {params.n}")
+    for r, (fwd, bwd) in enumerate(flows):
+        src = params.source[r]
+        for a, nm in ((fwd, "flows[%d] fwd" % r), (bwd, "flows[%d] bwd" % r)):
+            _fp32_view(a, nm, (ns, params.r_Jets[r], 2, src.sh, src.sw))
+    job = _track_job_for(ctx, params)                           # creating a job waits for the context's stream: before the bracket
+    if stream is None:
+        stream = torch.cuda.current_stream(frames.device)
+    with torch.cuda.stream(stream):                              # the outputs belong to the caller's stream
+        flow = torch.empty((ns, 2, job.gh, job.gw), dtype=torch.float64, device=frames.device)
+        slot = torch.empty((ns, job.gh, job.gw), dtype=torch.int32, device=frames.device)
+        occ = torch.empty((ns, job.gh, job.gw), dtype=torch.uint8, device=frames.device)
+        stats = torch.empty((ns, 3), dtype=torch.float64, device=frames.device)
+    wait_stream(ctx, stream)
+    try:
+        for r, (fwd, bwd) in enumerate(flows):
+            track_job_upload_flows_device(job, r, fwd, bwd)
+        track_job_upload_frames_device(job, frames)
+        job.run(ns)
+        track_job_download_device(job, flow, slot, occ, stats)
+    finally:
+        signal_stream(ctx, stream)
+    return flow, slot, occ, stats

@@ -13,8 +13,10 @@
 //   <output>/accumulated/best_<sequence_start>.pgm                the rate of lowest energy (ties: the lower r; 255: none) -- the first element of the
 //                                                                 reference's sort by compareHypotheses (:1401), NOT the TRW-S result
 //
-// With -fuse (implies -energies) it fuses every start_jet's rates as dense_tracking does (:1588-1905): the smoothness weight of normalised frame 0
-// (sfa_dt_smoothness_weight), NMS, the pairwise MRF and TRW-S in raster order (sfa_fuse_hypotheses), and writes
+// With -fuse (implies -energies) it fuses every start_jet's rates as dense_tracking does (:1588-1905): the smoothness weight of normalised frame 0, NMS,
+// the pairwise MRF and TRW-S in raster order.  Both flags run through one resident track job (sfa_track_job): the start_jets to do
+// are uploaded in groups of acc_gpu_batch (absent: chosen from the free device memory, at most 16) and each group is tracked, scored and fused by one
+// launch sequence on the GPU.  -fuse writes
 //   <output>/accumulated/<flow_format % sequence_start>.flo       the fused flow on the grid, u(Jets - 1) / xy_incr; UNKNOWN_FLOW (1e10) without a node
 //   <output>/accumulated/<...>_vis.png                            its colour coding
 //   <output>/accumulated/occlusions/frame_<sequence_start>.pgm    max_t occluded(t) of the chosen hypothesis, 0 / 255
@@ -69,7 +71,8 @@ static void usage() {
     printf("them and writes each hypothesis' unary energy (energy_<start>.pfm), its occluded frames (occluded_<start>.pgm) and the lowest-energy rate\n");
     printf("(best_<start>.pgm).  Keys: acc_jet_consistency, acc_brightness_constancy, acc_gradient_constancy, acc_occlusion_penalty, acc_temporal_occ,\n");
     printf("acc_cv, acc_occlusion_threshold, acc_occlusion_fb_threshold, acc_penalty_fct_data, acc_penalty_fct_data_eps.  Refused: acc_occlusion 1,\n");
-    printf("grayscale 1, raw_demosaicing 1, Jets > 32.\n");
+    printf("grayscale 1, raw_demosaicing 1, Jets > 32.  acc_gpu_batch: the start_jets of one run on the GPU (1 .. 64; absent: chosen from the free device\n");
+    printf("memory, at most 16); outside 1 .. 64, or too large for the device, the program exits with status 1.\n");
     printf("\n");
     printf("-fuse: implies -energies, then fuses all rates of each start_jet with TRW-S (raster order) into <flow_format %% start>.flo, _vis.png,\n");
     printf("occlusions/frame_<start>.pgm and labels_<start>.pgm.  Keys: acc_beta, acc_spatial_occ, acc_traj_sim_method, acc_traj_sim_thres, acc_trws_eps,\n");
@@ -372,36 +375,24 @@ static int run_accumulate(ParameterList &params, const Run &run, vector<Segment>
     return ok ? 0 : 1;
 }
 
-// -fuse: the settings (setDefault :136-152, read as at :605-625, :660-661), one start_jet's inputs and the record of every fused start_jet
+// -fuse: the settings (setDefault :136-152, read as at :605-625, :660-661) and the record of every fused start_jet
 struct Fusion {
     sfa_fuse_params fup;
     float nav[3], nsd[3];                    // the statistics the smoothness weight de-normalises with (img_norm_avg_* / img_norm_std_*)
     int hbit = 0;
-    vector<double> U, V, E;                  // [K][Jets][gpl], [K][Jets][gpl], [K][gpl]: slot k = the start_jet's k-th rate
-    vector<unsigned long long> O;            // [K][gpl]
-    vector<int> rate;                        // [K]
-    struct Record { unsigned seq_start; int nodes, iters; double energy, bound, t_weight, t_fuse; float stage_ms[4]; };
+    // t_weight, t_fuse and stage_ms exist per group of start_jets only: each of its start_jets carries the group's value
+    struct Record { unsigned seq_start; int nodes, iters, group, group_size; double energy, bound, t_weight, t_fuse; float stage_ms[4]; };
     vector<Record> done;
 };
 
-// the fusion of one start_jet's rates (:1588-1905): the smoothness weight of normalised frame 0 (:969-981), then NMS, the pairwise terms and
-// TRW-S; writes the fused flow (u(Jets - 1) / xy_incr, 1e10 without a node), its colour coding, the occlusions and the labels
-static bool fuse_start(sfa_ctx *ctx, const Run &run, Fusion &fz, const color_image_t *frame0, unsigned seq_start, int gw, int gh) {
-    const double te = now_s();
-    Fusion::Record fu{};
-    fu.seq_start = seq_start;
-    const int width = frame0->width, height = frame0->height;
+// one start_jet's fused result out of the track job (:1588-1905 ran on the GPU): writes the fused flow (u(Jets - 1) / xy_incr, 1e10 without a node), its
+// colour coding, the occlusions and the labels.  fu: the record with the group's figures filled in
+static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run, Fusion &fz, Fusion::Record fu, int gw, int gh) {
     const size_t gpl = (size_t)gw * gh;
-    vector<float> weight((size_t)width * height);
-    if (!sfa_ok(ctx, sfa_dt_smoothness_weight(ctx, width, height, frame0->stride, frame0->c1, 5.0f, fz.nav, fz.nsd, fz.hbit, weight.data()))) return false;
-    const double tf = now_s();
     vector<int> slot(gpl);
     vector<double> flu(gpl), flv(gpl);
     vector<unsigned char> oc(gpl);
-    if (!sfa_ok(ctx, sfa_fuse_hypotheses(ctx, &fz.fup, 1, (int)fz.rate.size(), (int)run.Jets, width, height, fz.U.data(), fz.V.data(), fz.E.data(), fz.O.data(),
-                                         weight.data(), slot.data(), flu.data(), flv.data(), oc.data(), &fu.energy, &fu.bound, &fu.iters, fu.stage_ms))) return false;
-    fu.t_weight = tf - te;
-    fu.t_fuse = now_s() - tf;
+    if (!sfa_ok(ctx, sfa_track_job_download_fused(job, k, slot.data(), flu.data(), flv.data(), oc.data(), nullptr, &fu.energy, &fu.bound, &fu.iters))) return false;
     image_t *u = image_new(gw, gh), *v = image_new(gw, gh);
     vector<unsigned char> lp(gpl), op(gpl);
     for (int y = 0; y < gh; y++)
@@ -409,28 +400,60 @@ static bool fuse_start(sfa_ctx *ctx, const Run &run, Fusion &fz, const color_ima
             const size_t i = (size_t)y * gw + x;
             u->data[(size_t)y * u->stride + x] = (float)flu[i];   // writeFlowMiddlebury's fp32 (utils.cpp:333); 1e10 without a node
             v->data[(size_t)y * v->stride + x] = (float)flv[i];
-            lp[i] = slot[i] < 0 ? 255 : (unsigned char)fz.rate[slot[i]];
+            lp[i] = slot[i] < 0 ? 255 : (unsigned char)slot[i];     // slot k of the job is rate k
             op[i] = oc[i] ? 255 : 0;                                // convertTo(CV_8UC1, 255) (:1893)
             fu.nodes += slot[i] >= 0;
         }
-    const string base = fused_base(run, seq_start);
+    const string base = fused_base(run, fu.seq_start);
     mkdirs(run.acc_dir + "occlusions/");
     const bool ok = writeFlowFile((base + ".flo").c_str(), u, v) == 0 && png_write((base + "_vis.png").c_str(), flowColorImg(u, v, 0)) &&
-                    write_pgm8(run.acc_dir + "occlusions/frame_" + std::to_string(seq_start) + ".pgm", gw, gh, op.data(), gw) &&
-                    write_pgm8(run.acc_dir + "labels_" + std::to_string(seq_start) + ".pgm", gw, gh, lp.data(), gw);
-    if (!ok) std::cerr << "cannot write the fused outputs of start " << seq_start << " under " << run.acc_dir << std::endl;
+                    write_pgm8(run.acc_dir + "occlusions/frame_" + std::to_string(fu.seq_start) + ".pgm", gw, gh, op.data(), gw) &&
+                    write_pgm8(run.acc_dir + "labels_" + std::to_string(fu.seq_start) + ".pgm", gw, gh, lp.data(), gw);
+    if (!ok) std::cerr << "cannot write the fused outputs of start " << fu.seq_start << " under " << run.acc_dir << std::endl;
     image_delete(u); image_delete(v);
-    std::cout << "start " << seq_start << ": fused " << fz.rate.size() << " rate(s) over " << fu.nodes << " nodes, energy " << fu.energy << ", lower bound "
+    std::cout << "start " << fu.seq_start << ": fused " << run.rates << " rate(s) over " << fu.nodes << " nodes, energy " << fu.energy << ", lower bound "
               << fu.bound << ", " << fu.iters << " TRW-S iteration(s)" << std::endl;
     fz.done.push_back(fu);
     return ok;
 }
 
-// -energies: per start_jet the frames, then for every rate in cfg order the accumulation (all steps) and the hypotheses' energies (:1100-1257)
+// the track job of the run: B start_jets x all rates.  acc_gpu_batch given: that B or status 1; absent: the largest B <= 16 and <= todo whose job takes at most
+// half of the device memory that is free now
+static sfa_track_job *create_job(ParameterList &params, sfa_ctx *ctx, sfa_track_params tp, size_t todo, int &B) {
+    sfa_track_job *job = nullptr;
+    size_t bytes = 0;
+    if (params.exists("acc_gpu_batch")) {
+        tp.n = B = params.parameter<int>("acc_gpu_batch");
+        const bool sized = sfa_track_job_bytes(&tp, &bytes) == SFA_OK;
+        if (!sized || sfa_track_job_create(ctx, &tp, &job) != SFA_OK) {
+            std::cerr << "acc_gpu_batch " << B << ": the track job cannot be created";
+            if (sized) std::cerr << " (" << bytes << " bytes of device memory needed)";
+            std::cerr << ": " << sfa_last_error(sized ? ctx : nullptr) << std::endl;
+            return nullptr;
+        }
+    } else {
+        size_t free_bytes = 0;
+        if (!sfa_ok(ctx, sfa_ctx_free_bytes(ctx, &free_bytes))) return nullptr;
+        for (B = (int)std::min<size_t>(16, todo); B >= 1; B--) {
+            tp.n = B;
+            if (sfa_track_job_bytes(&tp, &bytes) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; return nullptr; }
+            if (bytes <= free_bytes / 2 || B == 1) break;
+        }
+        if (!sfa_ok(ctx, sfa_track_job_create(ctx, &tp, &job))) return nullptr;
+    }
+    std::cout << "gpu batch: " << B << " start_jet(s) per run (" << bytes << " bytes of device memory" << (params.exists("acc_gpu_batch") ? ", acc_gpu_batch" : ", chosen")
+              << ")" << std::endl;
+    return job;
+}
+
+// -energies / -fuse: the start_jets in groups of B through one resident track job (sfa_track_job): per start_jet the frames are ingested and normalised and
+// every rate's jets read and uploaded; one run accumulates (all steps), scores (:1219-1257) and, with -fuse, fuses the whole group on the GPU; then the
+// outputs of each start_jet are written in cfg order
 static int run_energies(ParameterList &params, const Run &run, vector<Segment> &segs, const vector<string> &skipped,
                         const std::map<unsigned, vector<string>> &frame_files, vector<sfa_jet_source> &geo) {
-    sfa_energy_params ep;
-    sfa_energy_params_default(&ep);                                       // setDefault (:118-165), in the types of :606-623 and :661-675
+    sfa_track_params tp;
+    sfa_track_params_default(&tp);
+    sfa_energy_params &ep = tp.energy;                                    // setDefault (:118-165), in the types of :606-623 and :661-675
     ep.acc_jc = params.parameter<float>("acc_jet_consistency", "1.0");
     ep.acc_bc = params.parameter<float>("acc_brightness_constancy", "0.1");
     ep.acc_gc = params.parameter<float>("acc_gradient_constancy", "1.0");
@@ -441,7 +464,6 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     ep.occlusion_fb_threshold = params.parameter<float>("acc_occlusion_fb_threshold", "5.0");
     ep.penalty = params.parameter<int>("acc_penalty_fct_data", "1");
     ep.penalty_eps = params.parameter<double>("acc_penalty_fct_data_eps", "0.001");
-    ep.skip = run.skip_pixel;
     Fusion fz;
     sfa_fuse_params_default(&fz.fup);
     fz.fup.acc_beta = params.parameter<double>("acc_beta", "10.0");
@@ -454,125 +476,146 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     // the reference reads img_norm_* (defaults 0 / 1, :971-972), keys normalize() does not publish (it writes slow_flow_img_norm_*), so by default
     // the weight is taken from the normalised frame itself
     for (int k = 0; k < 3; k++) {
-        fz.nav[k] = (float)params.parameter<double>("img_norm_avg_" + std::to_string(k + 1), "0");
-        fz.nsd[k] = (float)params.parameter<double>("img_norm_std_" + std::to_string(k + 1), "1");
+        fz.nav[k] = tp.avg[k] = (float)params.parameter<double>("img_norm_avg_" + std::to_string(k + 1), "0");
+        fz.nsd[k] = tp.std_dev[k] = (float)params.parameter<double>("img_norm_std_" + std::to_string(k + 1), "1");
     }
-    fz.hbit = params.parameter<bool>("16bit", "0") ? 1 : 0;
+    fz.hbit = tp.hbit = params.parameter<bool>("16bit", "0") ? 1 : 0;
+    tp.fuse = fz.fup;
+    tp.K = (int)run.rates; tp.Jets = (int)run.Jets; tp.min_fps_idx = run.min_fps_idx; tp.do_fuse = run.fuse ? 1 : 0; tp.use_occlusions = run.use_occ ? 1 : 0;
+    tp.epsilon = run.threshold; tp.skip = run.skip_pixel; tp.discard = run.discard ? 1 : 0;
+    tp.coef = 5.0f;                                                       // :969-981
     sfa_ctx *ctx = nullptr;
     if (!segs.empty() && !sfa_ok(nullptr, sfa_ctx_create(0, &ctx))) return 1;
+    sfa_track_job *job = nullptr;
     double t_frames = 0, t_acc = 0, t_energy = 0, t_io = 0, t_fuse = 0;
     const double t0 = now_s();
-    const size_t Jets = run.Jets;
-    int width = 0, height = 0, status = 0;
-    for (auto it = frame_files.begin(); it != frame_files.end() && status == 0; ++it) {
-        const unsigned seq_start = it->first;
-        vector<size_t> mine;                                              // this start_jet's segments, in rate order
-        for (size_t i = 0; i < segs.size(); i++)
-            if (segs[i].seq_start == seq_start) mine.push_back(i);
-        // the frames set the target size (sequence[0].cols, :1142); rate acc_min_fps's flows: forward_flow / backward_flow of the reference (:1148-1151)
-        double ta = now_s();
-        vector<color_image_t *> fr;
-        for (const string &name : it->second) {
-            color_image_t *img = ingest_frame(params, run, ctx, name);
-            if (!img) { status = 1; break; }
-            fr.push_back(img);
-            if (fr.size() == 1 && width == 0) { width = img->width; height = img->height; }
-            if (img->width != width || img->height != height) {
-                std::cerr << name << " is " << img->width << " x " << img->height << ", not " << width << " x " << height << " like the first frame" << std::endl;
-                status = 1;
-                break;
+    int width = 0, height = 0, status = 0, B = 0, gw = 0, gh = 0;
+    vector<unsigned> starts;                                              // the start_jets to do, in order; each has a segment of every rate
+    for (auto it = frame_files.begin(); it != frame_files.end(); ++it) starts.push_back(it->first);
+    struct Group { int size; float ms[8]; };
+    vector<Group> groups;
+    for (size_t g0 = 0; g0 < starts.size() && status == 0; g0 += (size_t)B) {
+        int ng = 0;
+        // ---- the group's inputs, one start_jet after another: ingest, normalise, read, upload
+        for (size_t q = g0; q < starts.size() && (B == 0 ? q == g0 : q < g0 + (size_t)B) && status == 0; q++, ng++) {
+            const unsigned seq_start = starts[q];
+            vector<size_t> mine;                                          // this start_jet's segments, in rate order
+            for (size_t i = 0; i < segs.size(); i++)
+                if (segs[i].seq_start == seq_start) mine.push_back(i);
+            // the frames set the target size (sequence[0].cols, :1142)
+            double ta = now_s();
+            vector<color_image_t *> fr;
+            for (const string &name : frame_files.at(seq_start)) {
+                color_image_t *img = ingest_frame(params, run, ctx, name);
+                if (!img) { status = 1; break; }
+                fr.push_back(img);
+                if (fr.size() == 1 && width == 0) { width = img->width; height = img->height; }
+                if (img->width != width || img->height != height) {
+                    std::cerr << name << " is " << img->width << " x " << img->height << ", not " << width << " x " << height << " like the first frame" << std::endl;
+                    status = 1;
+                    break;
+                }
             }
-        }
-        if (status == 0 && !fit_rates(geo, width, height)) status = 1;
-        SegmentInput minf;
-        size_t mi = mine.size();
-        for (size_t k = 0; k < mine.size(); k++)
-            if (segs[mine[k]].r == run.min_fps_idx) mi = k;
-        sfa_jet_source &min_geo = geo[run.min_fps_idx];
-        if (status == 0 && (mi == mine.size() || !read_segment(segs[mine[mi]], false, min_geo, minf))) status = 1;
-        const int stride = fr.empty() ? 0 : fr[0]->stride;
-        vector<float *> fp;
-        for (color_image_t *c : fr) fp.push_back(c->c1);
-        double avg[3], sd[3];
-        if (status == 0 && !sfa_ok(ctx, sfa_normalize(ctx, fp.data(), (int)fp.size(), width, height, stride, avg, sd))) status = 1;   // normalize(data, Jets + 1) (:916)
-        t_frames += now_s() - ta;
-        int gw = 0, gh = 0;
-        if (status == 0 && !sfa_ok(nullptr, sfa_accumulate_grid(width, height, run.skip_pixel, &gw, &gh))) status = 1;
-        const size_t gpl = (size_t)gw * gh;
-        vector<float> best_e(gpl, INFINITY);
-        vector<unsigned char> best(gpl, 255);
-        vector<const float *> cfp(fp.begin(), fp.end());
-        if (status == 0 && run.fuse && width % 4 != 0) {
-            // the reference indexes its stride-pitched weight image as (y * xy_incr + xy_start) * owidth + ... (:1722, 1733, 1737): exact only where
-            // stride == width
-            std::cerr << "-fuse: width " << width << " is not a multiple of 4 (the reference's smoothness-weight index reads padding)" << std::endl;
-            status = 1;
-        }
-        const size_t K = mine.size();
-        if (run.fuse) { fz.U.assign(K * Jets * gpl, 0); fz.V.assign(fz.U.size(), 0); fz.E.assign(K * gpl, 0); fz.O.assign(K * gpl, 0); fz.rate.assign(K, 0); }
-        for (size_t k = 0; k < K && status == 0; k++) {
-            Segment &s = segs[mine[k]];
+            if (status == 0 && !fit_rates(geo, width, height)) status = 1;
+            if (status == 0 && mine.size() != run.rates) { std::cerr << "start " << seq_start << ": " << mine.size() << " of " << run.rates << " rates to do" << std::endl; status = 1; }
+            const int stride = fr.empty() ? 0 : fr[0]->stride;
+            vector<float *> fp;
+            for (color_image_t *c : fr) fp.push_back(c->c1);
+            double avg[3], sd[3];
+            if (status == 0 && !sfa_ok(ctx, sfa_normalize(ctx, fp.data(), (int)fp.size(), width, height, stride, avg, sd))) status = 1;   // normalize(data, Jets + 1) (:916)
+            if (status == 0 && !sfa_ok(nullptr, sfa_accumulate_grid(width, height, run.skip_pixel, &gw, &gh))) status = 1;
+            if (status == 0 && run.fuse && width % 4 != 0) {
+                // the reference indexes its stride-pitched weight image as (y * xy_incr + xy_start) * owidth + ... (:1722, 1733, 1737): exact only where
+                // stride == width
+                std::cerr << "-fuse: width " << width << " is not a multiple of 4 (the reference's smoothness-weight index reads padding)" << std::endl;
+                status = 1;
+            }
+            t_frames += now_s() - ta;
+            // every rate of the start_jet is read before anything is uploaded: read_segment fills the rates' row strides, which the job's sources carry
+            vector<SegmentInput> in(mine.size());
             double tb = now_s();
-            SegmentInput in;
-            if (!read_segment(s, run.use_occ, geo[s.r], in) || in.fu.empty()) { status = 1; break; }
-            vector<double> au((size_t)s.FF * gpl), av(au.size());
-            vector<int> tracked(gpl);
-            if (!sfa_ok(ctx, sfa_accumulate_consistent_scaled(ctx, 1, s.FF, width, height, &geo[s.r], in.fu.data(), in.fv.data(), in.bu.data(), in.bv.data(),
-                                                              run.use_occ ? in.mp.data() : nullptr, run.threshold, run.skip_pixel, run.discard, 1, au.data(),
-                                                              av.data(), tracked.data(), nullptr))) { status = 1; break; }
-            double tc = now_s();
-            t_acc += tc - tb;
-            // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
-            const bool flows = s.r >= run.min_fps_idx;
-            ep.weight = run.jet_weight.size() > (size_t)s.r ? (float)run.jet_weight[s.r] : (float)s.r;   // weight_jet_estimation, vector<float> (:489-495)
-            vector<double> energy(gpl);
-            vector<unsigned long long> occ(gpl);
-            if (!sfa_ok(ctx, sfa_hypothesis_energies_scaled(ctx, &ep, 1, s.FF, (int)Jets, width, height, stride, au.data(), av.data(), tracked.data(), cfp.data(),
-                                                            &min_geo, flows ? minf.fu.data() : nullptr, flows ? minf.fv.data() : nullptr,
-                                                            flows ? minf.bu.data() : nullptr, flows ? minf.bv.data() : nullptr, energy.data(), occ.data(),
-                                                            run.fuse ? fz.U.data() + k * Jets * gpl : nullptr, run.fuse ? fz.V.data() + k * Jets * gpl : nullptr))) {
-                status = 1;
-                break;
+            for (size_t k = 0; k < mine.size() && status == 0; k++) {
+                const Segment &s = segs[mine[k]];
+                if (!read_segment(s, run.use_occ, geo[s.r], in[k]) || in[k].fu.empty()) status = 1;
             }
+            t_io += now_s() - tb;
+            if (status == 0 && !job) {
+                tp.w = width; tp.h = height;
+                for (unsigned r = 0; r < run.rates; r++) {
+                    tp.source[r] = geo[r];
+                    tp.weight[r] = run.jet_weight.size() > r ? (float)run.jet_weight[r] : (float)r;   // weight_jet_estimation, vector<float> (:489-495)
+                }
+                for (size_t m = 0; m < mine.size(); m++) tp.r_Jets[segs[mine[m]].r] = segs[mine[m]].FF;
+                job = create_job(params, ctx, tp, starts.size(), B);
+                if (!job) status = 1;
+            }
+            for (size_t k = 0; k < mine.size() && status == 0; k++)
+                if (!sfa_ok(ctx, sfa_track_job_upload_flows(job, ng, segs[mine[k]].r, in[k].fu.data(), in[k].fv.data(), in[k].bu.data(), in[k].bv.data(),
+                                                            run.use_occ ? in[k].mp.data() : nullptr)))
+                    status = 1;
+            vector<const float *> cfp(fp.begin(), fp.end());
+            if (status == 0 && !sfa_ok(ctx, sfa_track_job_upload_frames(job, ng, cfp.data(), stride))) status = 1;
+            for (color_image_t *c : fr) color_image_delete(c);
+        }
+        if (status) break;
+        // ---- one run for the group
+        Group grp{ng, {}};
+        if (!sfa_ok(ctx, sfa_track_job_run(job, ng)) || !sfa_ok(ctx, sfa_track_job_stage_ms(job, grp.ms))) { status = 1; break; }
+        groups.push_back(grp);
+        t_acc += 1e-3 * grp.ms[1];
+        t_energy += 1e-3 * (grp.ms[0] + grp.ms[2]);
+        t_fuse += 1e-3 * (grp.ms[3] + grp.ms[4] + grp.ms[5] + grp.ms[6] + grp.ms[7]);
+        // ---- the group's outputs, start_jet by start_jet in the order of the staged program
+        const size_t gpl = (size_t)gw * gh;
+        for (int k = 0; k < ng && status == 0; k++) {
+            const unsigned seq_start = starts[g0 + k];
             double td = now_s();
-            t_energy += td - tc;
-            if (run.fuse) {
-                std::copy(energy.begin(), energy.end(), fz.E.begin() + k * gpl);
-                std::copy(occ.begin(), occ.end(), fz.O.begin() + k * gpl);
-                fz.rate[k] = s.r;
+            for (size_t i = 0; i < segs.size() && status == 0; i++) {
+                Segment &s = segs[i];
+                if (s.seq_start != seq_start) continue;
+                vector<double> au(gpl), av(gpl), energy(gpl);
+                vector<int> tracked(gpl);
+                vector<unsigned char> oc(gpl);
+                if (!sfa_ok(ctx, sfa_track_job_download_rate(job, k, s.r, au.data(), av.data(), tracked.data(), energy.data(), nullptr, oc.data()))) { status = 1; break; }
+                vector<float> ef(gpl);
+                for (size_t p = 0; p < gpl; p++) ef[p] = (float)energy[p];   // an fp32 sum stored in a double: exact
+                const string dir = run.acc_dir + std::to_string(s.r) + "/";
+                if (!write_last_step(s, au.data(), av.data(), tracked.data(), gw, gh) ||
+                    !write_pfm(dir + "energy_" + std::to_string(seq_start) + ".pfm", gw, gh, ef.data()) ||
+                    !write_pgm8(dir + "occluded_" + std::to_string(seq_start) + ".pgm", gw, gh, oc.data(), gw)) {
+                    std::cerr << "cannot write the outputs of rate " << s.r << " under " << dir << std::endl;
+                    status = 1;
+                }
             }
-            vector<unsigned char> oc(gpl);
-            vector<float> ef(gpl);
-            for (size_t i = 0; i < gpl; i++) {
-                ef[i] = (float)energy[i];                                 // an fp32 sum stored in a double: exact
-                oc[i] = (unsigned char)__builtin_popcountll(occ[i]);
-                if (ef[i] < best_e[i]) { best_e[i] = ef[i]; best[i] = (unsigned char)s.r; }   // strict: ties keep the lower r
+            if (status == 0 && run.fuse) {
+                Fusion::Record fu{};
+                fu.seq_start = seq_start; fu.group = (int)groups.size() - 1; fu.group_size = ng;
+                fu.t_weight = 1e-3 * grp.ms[3];
+                fu.t_fuse = 1e-3 * (grp.ms[4] + grp.ms[5] + grp.ms[6] + grp.ms[7]);
+                for (int m = 0; m < 4; m++) fu.stage_ms[m] = grp.ms[4 + m];
+                if (!write_fused(ctx, job, k, run, fz, fu, gw, gh)) status = 1;
             }
-            const size_t last = (size_t)(s.FF - 1) * gpl;
-            const string dir = run.acc_dir + std::to_string(s.r) + "/";
-            if (!write_last_step(s, au.data() + last, av.data() + last, tracked.data(), gw, gh) ||
-                !write_pfm(dir + "energy_" + std::to_string(seq_start) + ".pfm", gw, gh, ef.data()) ||
-                !write_pgm8(dir + "occluded_" + std::to_string(seq_start) + ".pgm", gw, gh, oc.data(), gw)) {
-                std::cerr << "cannot write the outputs of rate " << s.r << " under " << dir << std::endl;
+            vector<unsigned char> best(gpl);                              // the rate of the lowest fp32 energy, ties to the lower rate, formed on the GPU
+            if (status == 0 && !sfa_ok(ctx, sfa_track_job_download_best(job, k, best.data()))) status = 1;
+            if (status == 0 && !write_pgm8(run.acc_dir + "best_" + std::to_string(seq_start) + ".pgm", gw, gh, best.data(), gw)) {
+                std::cerr << "cannot write " << run.acc_dir << "best_" << seq_start << ".pgm" << std::endl;
                 status = 1;
             }
             t_io += now_s() - td;
         }
-        if (status == 0 && run.fuse) {
-            const double te = now_s();
-            if (!fuse_start(ctx, run, fz, fr[0], seq_start, gw, gh)) status = 1;
-            t_fuse += now_s() - te;
-        }
-        for (color_image_t *c : fr) color_image_delete(c);
-        if (status == 0 && !write_pgm8(run.acc_dir + "best_" + std::to_string(seq_start) + ".pgm", gw, gh, best.data(), gw)) {
-            std::cerr << "cannot write " << run.acc_dir << "best_" << seq_start << ".pgm" << std::endl;
-            status = 1;
-        }
     }
+    if (job) sfa_track_job_destroy(job);
     if (ctx) sfa_ctx_destroy(ctx);
     if (status) return status;
     std::ostringstream tail;
     tail.precision(17);
+    tail << ",\n  \"gpu_batch\": " << B << ", \"groups\": [";
+    for (size_t i = 0; i < groups.size(); i++) {
+        tail << (i ? ", " : "") << "{\"group\": " << i << ", \"group_size\": " << groups[i].size << ", \"stage_ms\": [";
+        for (int m = 0; m < 8; m++) tail << (m ? ", " : "") << groups[i].ms[m];
+        tail << "]}";
+    }
+    tail << "]";
     if (run.fuse) {
         const sfa_fuse_params &fup = fz.fup;
         tail << ",\n  \"fused\": true, \"epic_interpolation\": false, \"neighbour_proposals\": false, \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": "
@@ -581,7 +624,8 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
         for (size_t i = 0; i < fz.done.size(); i++) {
             const Fusion::Record &f = fz.done[i];
             tail << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << f.seq_start << ", \"nodes\": " << f.nodes << ", \"energy\": " << f.energy
-                 << ", \"lower_bound\": " << f.bound << ", \"iterations\": " << f.iters << ", \"weight_s\": " << f.t_weight << ", \"fuse_call_s\": " << f.t_fuse
+                 << ", \"lower_bound\": " << f.bound << ", \"iterations\": " << f.iters << ", \"group\": " << f.group << ", \"group_size\": " << f.group_size
+                 << ", \"weight_s\": " << f.t_weight << ", \"fuse_call_s\": " << f.t_fuse
                  << ", \"kernels_ms\": {\"labels\": " << f.stage_ms[0] << ", \"pairwise\": " << f.stage_ms[1] << ", \"trws\": " << f.stage_ms[2]
                  << ", \"output\": " << f.stage_ms[3] << "}}";
         }
@@ -664,6 +708,10 @@ static int refusal(ParameterList &params, const Run &run) {
                               : run.Jets > 32 ? "Jets > 32" : nullptr;
         if (refused) { std::cerr << "-energies: " << refused << " is not supported" << std::endl; return 1; }
         if (params.file.empty()) { std::cerr << "-energies: `file` (the frames) missing from " << run.cfg << std::endl; return 1; }
+        if (params.exists("acc_gpu_batch")) {                             // the start_jets of one run of the track job; never clamped
+            const int b = params.parameter<int>("acc_gpu_batch");
+            if (b < 1 || b > 64) { std::cerr << "acc_gpu_batch " << b << " is outside 1 .. 64" << std::endl; return 1; }
+        }
     }
     if (run.fuse) {
         const int method = params.parameter<int>("acc_traj_sim_method", "1");
