@@ -121,6 +121,20 @@ int sfa_flow_magnitude_quantile(sfa_ctx *ctx, int n, const float *const *u, cons
  * np < (float)(N - 1) and fmodf(np, 2) == 0 -> *average = 1, the mean of ranks *k0 = (int)np and *k1 = *k0 + 1; else *average = 0, *k0 = *k1 = (int)ceilf(np).
  * SFA_ERR_ARG for N == 0, q outside (0, 1] and an N, q whose rank falls outside the N values (the reference reads past its array there). */
 int sfa_quantile_ranks(size_t N, float q, size_t *k0, size_t *k1, int *average);
+/* The same quantile and maximum (adaptiveFR.cpp:644-668) for G groups of flow fields that already live in GPU memory, in one launch sequence on the
+ * context's stream; nothing is copied from or to the host and the call does not wait for the GPU (pair it with sfa_ctx_wait_stream /
+ * sfa_ctx_signal_stream like the other device entry points).  Element (group g, field f, row y, column x) of u is u_dev[g strides[0] + f strides[1] +
+ * y strides[2] + x strides[3]] (element strides), the same for v_dev: planar [G][n][2][h][w] (v_dev = u_dev + the plane stride), channels-last
+ * [G][n][h][w][2] (v_dev = u_dev + 1), padded rows and slices are read in place.  Group g takes its first counts[g] fields (counts: host, G entries;
+ * NULL = all n).  out_dev[g][0] = the quantile of group g under sfa_quantile_ranks' rule over its counts[g] w h magnitudes, out_dev[g][1] their maximum:
+ * the bits sfa_flow_magnitude_quantile returns for the same values.  The scratch (4 bytes per value, the histograms) stays on the context from call
+ * to call; a call that needs more than any before it waits for the stream once, to replace it.
+ * SFA_ERR_ARG, naming the argument, before anything is launched: G outside 1..64, n < 1, w or h < 1, a count outside 1..n, u_dev / v_dev / out_dev that
+ * are not device memory of the context's GPU (or views that leave their allocation), a row or column stride < 1, a negative group or field stride,
+ * strides under which two elements of one group share an address, out_dev overlapping the flows, more than 2^32 - 1 values in a group, and whatever
+ * sfa_quantile_ranks refuses for a group (the group is named). */
+int sfa_flow_magnitude_quantiles_device(sfa_ctx *ctx, int G, int n, const int *counts, const float *u_dev, const float *v_dev, const long long strides[4],
+                                        int w, int h, float flow_scale, float q, double *out_dev);
 /* dense_tracking's first stage, accumulateConsistentBatches (utils/utils.cpp:517-617, with bilinearInterp<double>, utils/utils.h:182-217), for n
  * independent segments of FF steps in one launch.  Segment s, step f reads the host planes fwd_u/fwd_v/bwd_u/bwd_v[s * FF + f] (w x h, row stride
  * `stride` floats; widened to double exactly, as readGTMiddlebury's CV_64FC2) and, where masks != NULL, masks[s * FF + f] (uint8, row stride `stride`

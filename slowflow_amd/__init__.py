@@ -168,7 +168,7 @@ def track_job_bytes(params):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",

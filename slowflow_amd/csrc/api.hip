@@ -167,6 +167,7 @@ void sfa_ctx_destroy(sfa_ctx *c) {
     if (c->h_amask) (void)hipHostFree(c->h_amask);
     for (auto e : c->ev_mask) if (e) (void)hipEventDestroy(e);
     if (c->rb_tmp) (void)hipFree(c->rb_tmp);
+    if (c->q_tmp) (void)hipFree(c->q_tmp);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -771,7 +772,7 @@ int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, c
 }
 
 // strides sorted, each larger than the extent of all smaller ones: no two elements of the field share an address (dimensions of size 1 do not count)
-static bool strides_nest(const long long *st, const int *n, int nd) {
+bool strides_nest(const long long *st, const int *n, int nd) {
     std::vector<std::pair<long long, int>> d;
     for (int i = 0; i < nd; i++) if (n[i] > 1) d.emplace_back(st[i], n[i]);
     std::sort(d.begin(), d.end());

@@ -12,6 +12,11 @@
 //   pass 2  bits 20..10 of the keys whose bits 31..21 are the chosen prefix (one LDS histogram per rank), scan; pass 3 bits 9..0, scan.
 // After the third scan each rank's prefix IS its key.  Counts are integers, so the result does not depend on the order the adds arrive in: repeated runs
 // give the same bits.
+//
+// Groups (sfa_flow_magnitude_quantiles_device): G sets of fields that already live in GPU memory, one quantile and one maximum each.  blockIdx.y is the group;
+// a group has its own record (GroupSel: SelState, value count, which ranks answer), its own histograms and its own packed keys, so no block mixes two
+// groups in its LDS histogram.  k_group_keys_hist is pass 1 reading u and v in place through element strides; passes 2, 3 and the scans are the bodies of
+// k_digit_hist / k_select_digit on the group's pointers; k_group_result applies the rule of :663/:665/:668 and leaves {quantile, max} in GPU memory.
 #include "sfa_device.h"
 
 #pragma clang fp contract(off)
@@ -45,8 +50,8 @@ __global__ void __launch_bounds__(kQThreads) k_mag_keys_hist(const float *__rest
         if (lh[i]) atomicAdd(&hist[i], lh[i]);
 }
 
-__global__ void __launch_bounds__(kQThreads) k_digit_hist(const unsigned *__restrict__ keys, size_t N, const SelState *__restrict__ st, int level,
-                                                          unsigned *__restrict__ hist /* [kQRanks][kQBins] */) {
+__device__ __forceinline__ void digit_hist(const unsigned *__restrict__ keys, size_t N, const SelState *__restrict__ st, int level,
+                                           unsigned *__restrict__ hist /* [kQRanks][kQBins] */) {
     __shared__ unsigned lh[kQRanks * kQBins];
     const int nr = st->nr, sh = digit_shift(level), pre = sh + digit_bits(level);
     const unsigned mask = (1u << digit_bits(level)) - 1;
@@ -63,9 +68,13 @@ __global__ void __launch_bounds__(kQThreads) k_digit_hist(const unsigned *__rest
     for (int i = threadIdx.x; i < nr * kQBins; i += kQThreads)
         if (lh[i]) atomicAdd(&hist[i], lh[i]);
 }
+__global__ void __launch_bounds__(kQThreads) k_digit_hist(const unsigned *__restrict__ keys, size_t N, const SelState *__restrict__ st, int level,
+                                                          unsigned *__restrict__ hist) {
+    digit_hist(keys, N, st, level, hist);
+}
 
 // one workgroup: for each rank, the bin of the level's histogram that holds it (pass 1 has one histogram for all ranks)
-__global__ void __launch_bounds__(kQThreads) k_select_digit(const unsigned *__restrict__ hist, SelState *__restrict__ st, int level) {
+__device__ __forceinline__ void select_digit(const unsigned *__restrict__ hist, SelState *__restrict__ st, int level) {
     constexpr int per = kQBins / kQThreads;
     __shared__ unsigned part[kQThreads];
     const int nbins = 1 << digit_bits(level);
@@ -97,6 +106,69 @@ __global__ void __launch_bounds__(kQThreads) k_select_digit(const unsigned *__re
         }
         __syncthreads();
     }
+}
+__global__ void __launch_bounds__(kQThreads) k_select_digit(const unsigned *__restrict__ hist, SelState *__restrict__ st, int level) { select_digit(hist, st, level); }
+
+// ---- groups of fields in GPU memory ---------------------------------------------------------------------------------------------------------------
+constexpr int kQMaxGroups = 64;
+struct GroupSel {
+    SelState st;
+    unsigned N;                  // values of the group: its count of fields x w x h
+    unsigned char slot[3];       // the entries of st that hold rank k0, rank k1 and rank N - 1
+    unsigned char average;
+};
+// every group's record as ONE kernel argument (36 bytes x 64 at most): the launch carries it, so no host buffer has to outlive the call
+struct GroupSelAll { GroupSel g[kQMaxGroups]; };
+// u and v of (group, field, row, column) at the element strides sg, sf, sr, sc; per = w h
+struct GroupSrc { const float *u, *v; long long sg, sf, sr, sc; unsigned w, per; };
+
+__global__ void __launch_bounds__(kQThreads) k_group_init(GroupSelAll all, int G, GroupSel *__restrict__ sel) {
+    if ((int)threadIdx.x < G) sel[threadIdx.x] = all.g[threadIdx.x];
+}
+
+// pass 1 of group blockIdx.y: value i of the group is column i % w of row i % per / w of field i / per (i < 2^32: sfa_flow_magnitude_quantiles_device
+// refuses more), read where it lies; the key goes to the group's packed keys[i]
+__global__ void __launch_bounds__(kQThreads) k_group_keys_hist(GroupSrc s, float scale, const GroupSel *__restrict__ sel, unsigned *__restrict__ keys,
+                                                               size_t key_stride, unsigned *__restrict__ hist) {
+    __shared__ unsigned lh[kQBins];
+    const int g = blockIdx.y;
+    const size_t N = sel[g].N;
+    const float *__restrict__ u = s.u + (long long)g * s.sg, *__restrict__ v = s.v + (long long)g * s.sg;
+    keys += (size_t)g * key_stride;
+    hist += (size_t)g * kQRanks * kQBins;
+    for (int i = threadIdx.x; i < kQBins; i += kQThreads) lh[i] = 0;
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * kQThreads + threadIdx.x; i < N; i += (size_t)gridDim.x * kQThreads) {
+        const unsigned f = (unsigned)i / s.per, r = (unsigned)i - f * s.per, y = r / s.w, x = r - y * s.w;
+        const long long o = (long long)f * s.sf + (long long)y * s.sr + (long long)x * s.sc;
+        const float a = u[o] * scale, b = v[o] * scale;                           // as k_mag_keys_hist
+        const float m = sqrt_rn(a * a + b * b);
+        const unsigned key = __float_as_uint(m) & 0x7fffffffu;
+        keys[i] = key;
+        atomicAdd(&lh[key >> 21], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kQBins; i += kQThreads)
+        if (lh[i]) atomicAdd(&hist[i], lh[i]);
+}
+
+__global__ void __launch_bounds__(kQThreads) k_group_digit_hist(const unsigned *__restrict__ keys, size_t key_stride, const GroupSel *__restrict__ sel, int level,
+                                                                unsigned *__restrict__ hist) {
+    const int g = blockIdx.y;
+    digit_hist(keys + (size_t)g * key_stride, sel[g].N, &sel[g].st, level, hist + (size_t)g * kQRanks * kQBins);
+}
+// one workgroup per group
+__global__ void __launch_bounds__(kQThreads) k_group_select_digit(const unsigned *__restrict__ hist, GroupSel *__restrict__ sel, int level) {
+    select_digit(hist + (size_t)blockIdx.x * kQRanks * kQBins, &sel[blockIdx.x].st, level);
+}
+// one workgroup, thread g for group g: after the third scan a rank's prefix is its key
+__global__ void __launch_bounds__(kQMaxGroups) k_group_result(const GroupSel *__restrict__ sel, int G, double *__restrict__ out) {
+    const int g = threadIdx.x;
+    if (g >= G) return;
+    const GroupSel &s = sel[g];
+    const double a = (double)__uint_as_float(s.st.prefix[s.slot[0]]), b = (double)__uint_as_float(s.st.prefix[s.slot[1]]);
+    out[2 * g] = s.average ? 0.5f * (a + b) : a;                                  // :663, :665 (m[] holds doubles)
+    out[2 * g + 1] = (double)__uint_as_float(s.st.prefix[s.slot[2]]);             // :668
 }
 
 }  // namespace sfa
@@ -172,5 +244,90 @@ int sfa_flow_magnitude_quantile(sfa_ctx *ctx, int n, const float *const *u, cons
     };
     *quantile = average ? 0.5f * (value_of(k0) + value_of(k1)) : value_of(k0);  // :663, :665 (m[] holds doubles)
     *max_magnitude = value_of(N - 1);                                            // :668
+    return SFA_OK;
+}
+
+// adaptiveFR.cpp:644-668 for G groups of fields in GPU memory (include/slowflow_amd.h).  Every check, and every group's ranks (sfa_quantile_ranks), on the host
+// before the first launch; then one launch sequence on the context's stream, no copy and no wait.  The scratch lives on the context: the records of 64
+// groups, G x kQRanks histograms, G x n w h keys; a call that needs more than the context holds waits for the stream once and replaces it.
+int sfa_flow_magnitude_quantiles_device(sfa_ctx *ctx, int G, int n, const int *counts, const float *u_dev, const float *v_dev, const long long strides[4], int w,
+                                        int h, float flow_scale, float q, double *out_dev) {
+    CHECK_ARGS(ctx, "ctx is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    if (G < 1 || G > kQMaxGroups) REFUSE("%s: G = %d groups; 1 to %d are taken", __func__, G, kQMaxGroups);
+    if (n < 1) REFUSE("%s: n = %d fields per group", __func__, n);
+    if (w < 1 || h < 1) REFUSE("%s: w = %d, h = %d: the fields are empty", __func__, w, h);
+    int most = n;
+    if (counts) {
+        most = 0;
+        for (int g = 0; g < G; g++) {
+            if (counts[g] < 1 || counts[g] > n) REFUSE("%s: counts[%d] = %d lies outside 1..n = %d", __func__, g, counts[g], n);
+            most = std::max(most, counts[g]);
+        }
+    }
+    const size_t per = (size_t)w * h;
+    if (per * (size_t)most > 0xffffffffull)
+        REFUSE("%s: n = %d fields of w x h = %d x %d are %zu values in a group, beyond the 32-bit counts", __func__, most, w, h, per * (size_t)most);
+    if (!u_dev) REFUSE("%s: u_dev is null", __func__);
+    if (!v_dev) REFUSE("%s: v_dev is null", __func__);
+    if (!out_dev) REFUSE("%s: out_dev is null", __func__);
+    if (!strides) REFUSE("%s: strides is null", __func__);
+    if (strides[2] < 1 || strides[3] < 1) REFUSE("%s: strides: row stride %lld, column stride %lld; both must be >= 1", __func__, strides[2], strides[3]);
+    const int sizes[4] = {G, n, h, w};
+    SFA_TRY(check_field(ctx, __func__, "u_dev", u_dev, strides, sizes, 4));
+    SFA_TRY(check_field(ctx, __func__, "v_dev", v_dev, strides, sizes, 4));
+    if (!strides_nest(strides + 1, sizes + 1, 3))
+        REFUSE("%s: strides (field %lld, row %lld, column %lld) let two elements of one group share an address (or interleave them in a way the check cannot clear)",
+               __func__, strides[1], strides[2], strides[3]);
+    SFA_TRY(check_device_pointer(ctx, __func__, "out_dev", out_dev, 2LL * G - 1, sizeof(double)));
+    const long long last = (G - 1) * strides[0] + (n - 1) * strides[1] + (h - 1) * strides[2] + (w - 1) * strides[3];
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + (uintptr_t)G * 16 - 1;
+    for (const float *p : {u_dev, v_dev}) {
+        const uintptr_t f0 = reinterpret_cast<uintptr_t>(p), f1 = f0 + (uintptr_t)last * 4 + 3;
+        if (!(f1 < o0 || o1 < f0)) REFUSE("%s: out_dev overlaps %s: the results would be written into flows still being read", __func__, p == u_dev ? "u_dev" : "v_dev");
+    }
+    GroupSelAll all{};
+    for (int g = 0; g < G; g++) {
+        GroupSel &s = all.g[g];
+        const size_t N = per * (size_t)(counts ? counts[g] : n);
+        size_t k0, k1;
+        int average;
+        if (sfa_quantile_ranks(N, q, &k0, &k1, &average) != SFA_OK) REFUSE("%s: group %d: %s", __func__, g, sfa_last_error(nullptr));
+        const size_t want[kQRanks] = {k0, k1, N - 1};
+        for (int r = 0; r < kQRanks; r++) {                                      // distinct ranks only
+            int t = 0;
+            while (t < s.st.nr && s.st.rank[t] != (unsigned)want[r]) t++;
+            if (t == s.st.nr) s.st.rank[s.st.nr++] = (unsigned)want[r];
+            s.slot[r] = (unsigned char)t;
+        }
+        s.N = (unsigned)N;
+        s.average = (unsigned char)average;
+    }
+    constexpr size_t sel_bytes = 4096, hist_bytes = (size_t)kQRanks * kQBins * 4;
+    static_assert(sizeof(GroupSelAll) <= sel_bytes, "the records of all groups fit a kernel argument and the head of the scratch");
+    const size_t key_stride = per * (size_t)most, need = sel_bytes + G * hist_bytes + G * key_stride * 4;
+    if (need > ctx->q_tmp_bytes) {                                               // (the stream may still read the old scratch)
+        SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->q_tmp_bytes = 0;
+        if (ctx->q_tmp) { (void)hipFree(ctx->q_tmp); ctx->q_tmp = nullptr; }
+        SFA_HIP(ctx, hipMalloc(&ctx->q_tmp, need));
+        ctx->q_tmp_bytes = need;
+    }
+    GroupSel *sel = static_cast<GroupSel *>(ctx->q_tmp);
+    unsigned *hist = reinterpret_cast<unsigned *>(static_cast<char *>(ctx->q_tmp) + sel_bytes), *keys = hist + (size_t)G * kQRanks * kQBins;
+    const GroupSrc src{u_dev, v_dev, strides[0], strides[1], strides[2], strides[3], (unsigned)w, (unsigned)per};
+    // as many blocks per group as the one-group path launches in all, shared among the groups
+    const int blocks = (int)std::min<size_t>((key_stride + kQThreads - 1) / kQThreads, (size_t)std::max(1, ctx->cu_count * 4 / G));
+    hipLaunchKernelGGL(k_group_init, dim3(1), dim3(kQMaxGroups), 0, ctx->stream, all, G, sel);
+    SFA_HIP(ctx, hipMemsetAsync(hist, 0, G * hist_bytes, ctx->stream));
+    hipLaunchKernelGGL(k_group_keys_hist, dim3(blocks, G), dim3(kQThreads), 0, ctx->stream, src, flow_scale, sel, keys, key_stride, hist);
+    hipLaunchKernelGGL(k_group_select_digit, dim3(G), dim3(kQThreads), 0, ctx->stream, hist, sel, 0);
+    for (int level = 1; level < 3; level++) {
+        SFA_HIP(ctx, hipMemsetAsync(hist, 0, G * hist_bytes, ctx->stream));
+        hipLaunchKernelGGL(k_group_digit_hist, dim3(blocks, G), dim3(kQThreads), 0, ctx->stream, keys, key_stride, sel, level, hist);
+        hipLaunchKernelGGL(k_group_select_digit, dim3(G), dim3(kQThreads), 0, ctx->stream, hist, sel, level);
+    }
+    hipLaunchKernelGGL(k_group_result, dim3(1), dim3(kQMaxGroups), 0, ctx->stream, sel, G, out_dev);
+    SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;
 }

@@ -93,6 +93,8 @@ struct sfa_ctx {
     char sor_kernel[160] = {0};   // the solver kernel (shape) of the last solve launched
     void *rb_tmp = nullptr;       // labelled red-black mode: scratch (du, dv) pair the tile visits ping-pong with, grown on demand
     size_t rb_tmp_bytes = 0;
+    void *q_tmp = nullptr;        // sfa_flow_magnitude_quantiles_device (quantile.hip): group records, histograms and keys, kept from call to call, grown on demand
+    size_t q_tmp_bytes = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // sfa_ctx_wait_stream / sfa_ctx_signal_stream: recorded on the caller's / the context's stream
     // the reference's per-iteration "avg change" lines (variational_mt.cpp:404-405, 431-432): sfa_ctx_set_verbose; costs a host round trip per iteration
@@ -429,6 +431,8 @@ int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, co
 int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem);
 // a strided fp32 field of `nd` dimensions (sizes n[], strides st[], the last one the column): the pointer and the strides' signs
 int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd);
+// strides sorted, each larger than the extent of all smaller ones: no two elements of the field share an address (a sufficient condition)
+bool strides_nest(const long long *st, const int *n, int nd);
 // download destinations: flow [n][2][h][w] at `strides`, occlusions [n][h][w] at `occ_strides` (or null): pointers, strides, and freedom from overlap
 int check_download_destination(sfa_ctx *ctx, const char *fn, int n, int w, int h, float *flow_dev, const long long strides[4], float *occ_dev,
                                const long long occ_strides[3]);

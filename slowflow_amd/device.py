@@ -2,9 +2,10 @@
 and results that live in GPU memory go in and out of a job without a host copy.
 
 The core takes any object with `__cuda_array_interface__` (torch-ROCm tensors, cupy arrays ...) and needs no torch; `import slowflow_amd` does not
-import this module, and this module imports torch only inside refine(), refine_pairs() and track(), to allocate the outputs and to find the caller's
-current stream.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which never waits for the
-GPU; track() dense_tracking's accumulation, energies and fusion on a resident track job, which does not wait either.
+import this module, and this module imports torch only inside refine(), refine_pairs(), track() and flow_quantiles(), to allocate the outputs and to
+find the caller's current stream.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which
+never waits for the GPU; track() dense_tracking's accumulation, energies and fusion on a resident track job, which does not wait either;
+flow_quantiles() adaptiveFR's flow-magnitude quantile and maximum of groups of flows, left in GPU memory.
 
 Stream contract: the library works on the context's own stream.  Context.wait_stream(s) before the first call makes that stream wait for what the
 caller has submitted to s; Context.signal_stream(s) after the last makes s wait for the library.  refine() and refine_pairs() do both.  With the two in place a tensor
@@ -129,6 +130,8 @@ def _lib():
         L.sfa_track_job_upload_flows_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sfa_track_job_upload_frames_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.sfa_track_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sfa_flow_magnitude_quantiles_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                          C.c_float, C.c_float, C.c_void_p]
         _bound = True
     return L
 
@@ -533,3 +536,43 @@ def track(ctx, params, flows, frames, *, stream=None):
     finally:
         signal_stream(ctx, stream)
     return flow, slot, occ, stats
+
+
+# ---- adaptiveFR's frame-rate decision (sfa_flow_magnitude_quantiles_device): quantile and maximum of the flow magnitude, per group ------------------
+def flow_quantiles(ctx, flow, q=0.99, scale=1.0, counts=None, *, stream=None, out=None):
+    """adaptiveFR's quantile and maximum of the flow magnitude (adaptiveFR.cpp:644-668) for G groups of flow fields that live on the context's GPU: flow =
+    an fp32 tensor [G,n,2,h,w], or [n,2,h,w] as one group, with any strides whose row and column strides are positive (a permuted channels-last
+    [G,n,h,w,2], padded rows and slices are read in place); every value is multiplied by `scale` first; counts = None (all n fields) or G numbers, group
+    g then takes its first counts[g] fields.  Returns a float64 tensor [G,2] on the flow's device, row g = (quantile, maximum) of group g with the bits
+    Context.flow_magnitude_quantile gives for the same values; out = such a tensor (contiguous) to write into instead of a new one.  The work is ordered
+    after what `stream` (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues and never waits
+    for the GPU (a call that needs more scratch than the context holds replaces it first, which does)."""
+    import torch
+    if getattr(flow, "is_cuda", True) is False:                 # a torch tensor on the CPU raises from its __cuda_array_interface__
+        raise sfa.SlowflowError(f"flow: a tensor on {getattr(flow, 'device', 'the host')}, not in GPU memory (the device entry points take device memory)")
+    v = device_view(flow, name="flow", kinds=("f4",))
+    if len(v.shape) == 4:
+        v = DeviceView(v.ptr, v.dtype, v.itemsize, (1,) + v.shape, (0,) + v.strides, v.owner)
+    if len(v.shape) != 5 or v.shape[2] != 2:
+        raise sfa.SlowflowError(f"flow: shape {tuple(v.shape)}; fp32 [G,n,2,h,w] or [n,2,h,w] expected")
+    G, n, _, h, w = v.shape
+    ca = None
+    if counts is not None:
+        counts = [int(c) for c in counts]
+        if len(counts) != G:
+            raise sfa.SlowflowError(f"counts: {len(counts)} entries for {G} groups")
+        ca = (C.c_int * G)(*counts)
+    if stream is None:
+        stream = torch.cuda.current_stream(flow.device)
+    if out is None:
+        with torch.cuda.stream(stream):                          # the output belongs to the caller's stream
+            out = torch.empty((G, 2), dtype=torch.float64, device=flow.device)
+    op, _ = _typed_view(out, "out", "f8", (G, 2))
+    s = v.strides
+    wait_stream(ctx, stream)
+    try:
+        ctx._ck(_lib().sfa_flow_magnitude_quantiles_device(ctx.h, G, n, ca, C.c_void_p(v.ptr), C.c_void_p(v.ptr + s[2] * v.itemsize), _LL4(s[0], s[1], s[3], s[4]),
+                                                           w, h, float(scale), float(q), C.c_void_p(op)), "sfa_flow_magnitude_quantiles_device")
+    finally:
+        signal_stream(ctx, stream)
+    return out
