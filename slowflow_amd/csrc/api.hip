@@ -1,6 +1,6 @@
 // api.hip -- the C-ABI of include/slowflow_amd.h but for the jobs (job.hip: the multi-frame job; two_frame.hip: the pair jobs): context, debug switches and
-// profiling hooks, the single-operator entry points with their host<->HBM staging, the SOR batch, the resident sequence, the argument checks of the device seam
-// and the raw Bayer ingest.  All compute is in kernels.hip / sor*.hip / mosaic.hip; there is no CPU path.
+// profiling hooks, the single-operator entry points with their host<->HBM staging, the SOR batch, the resident sequence, the raw Bayer ingest, and the argument checks
+// of every entry point that takes device memory (check_view, check_disjoint ...: the arithmetic is dev_view.h's, what asks the HIP runtime is here).  All compute is in kernels.hip / sor*.hip / mosaic.hip; there is no CPU path.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -711,9 +711,10 @@ int sfa_normalize(sfa_ctx *ctx, float *const *frames, int F, int w, int h, int s
 
 }  // extern "C"
 
-// ---- the argument checks of the device seam (include/slowflow_amd.h; kernels: device_io.hip) and of the raw Bayer ingest -------------------
+// ---- the argument checks of the device seam (include/slowflow_amd.h; kernels: device_io.hip, mosaic.hip, track.hip, quantile.hip) -------------------
+// A view's strides, extent, nesting and byte range are dev_view.h's arithmetic; here it meets the HIP runtime (check_device_pointer) and the messages.
 // Every check is taken on the host before anything is launched; a refusal names the argument (REFUSE: sfa_internal.h).  Those declared in sfa_internal.h are
-// shared with the jobs' seam in job.hip and the pair jobs' in two_frame.hip.
+// shared with job.hip, two_frame.hip, track.hip and quantile.hip.
 namespace sfa {
 
 // `p` must be device memory of the context's GPU, and the view (its last element `last` elements of `elem` bytes further) must lie inside p's allocation
@@ -737,51 +738,44 @@ int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const vo
     return SFA_OK;
 }
 
-// *acc += steps * stride without wrapping; false: the sum leaves the signed 64-bit range (a view no allocation can hold)
-static bool extent_add(long long *acc, long long steps, long long stride) {
-    long long t;
-    return !__builtin_mul_overflow(steps, stride, &t) && !__builtin_add_overflow(*acc, t, acc);
-}
-
 static size_t dev_elem_size(int dtype) { return dtype == SFA_DEV_F32 ? 4 : dtype == SFA_DEV_U16 ? 2 : 1; }
 
-// the frames of `nwin` windows (or sequence frames) of F frames each: layout and pointer
+// a strided view (dev_view.h).  Refused in this order: a null pointer or null strides; a negative stride, an innermost stride below min_inner, an extent
+// beyond the signed 64-bit range; memory that is not the context's GPU's, or a last element outside its allocation
+int check_view(sfa_ctx *ctx, const char *fn, const View &v, long long min_inner) {
+    if (!v.p) REFUSE("%s: %s is null", fn, v.name);
+    if (!v.st) REFUSE("%s: the strides of %s are null", fn, v.name);
+    long long last;
+    int at;
+    const ViewFault fault = view_extent(v, min_inner, &last, &at);
+    if (fault == VIEW_RANGE) REFUSE("%s: the strides of %s reach beyond the 64-bit range: the view cannot lie inside an allocation", fn, v.name);
+    if (fault != VIEW_OK) {
+        char nth[24];
+        snprintf(nth, sizeof nth, "stride %d", at);
+        const char *dim = v.dim ? v.dim[at] : at == v.nd - 1 ? "the column stride" : at == v.nd - 2 ? "the row stride" : nth;
+        if (fault == VIEW_NEGATIVE) REFUSE("%s: %s of %s is a negative stride (%lld)", fn, dim, v.name, v.st[at]);
+        REFUSE("%s: %s of %s is %lld: it must be >= %lld", fn, dim, v.name, v.st[at], min_inner);
+    }
+    return check_device_pointer(ctx, fn, v.name, v.p, last, v.elem);
+}
+
+// no two of the (checked) views share a byte; null pointers, optional arguments left out, are skipped.  why: what the overlap would break, for the message
+int check_disjoint(sfa_ctx *ctx, const char *fn, std::initializer_list<View> views, const char *why) {
+    std::vector<ByteRange> r;
+    int a, b;
+    for (const View &v : views) r.push_back(byte_range(v));
+    if (!first_overlap(r.data(), (int)r.size(), &a, &b)) return SFA_OK;
+    if (why) REFUSE("%s: %s overlaps %s: %s", fn, views.begin()[a].name, views.begin()[b].name, why);
+    REFUSE("%s: %s and %s overlap", fn, views.begin()[a].name, views.begin()[b].name);
+}
+
+// the frames of `nwin` windows of F frames each (a sequence's n frames: one window of n): the layout's element type, and its view
 int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h) {
     if (!l) REFUSE("%s: layout is null", fn);
     if (l->dtype != SFA_DEV_F32 && l->dtype != SFA_DEV_U8 && l->dtype != SFA_DEV_U16) REFUSE("%s: layout.dtype %d is no element type (fp32 0, u8 1, u16 2)", fn, l->dtype);
-    if (l->column < 1) REFUSE("%s: layout.column = %lld: the column stride must be >= 1", fn, l->column);
-    if (win_stride < 0 || l->frame < 0 || l->channel < 0 || l->row < 0) REFUSE("%s: layout holds a negative stride (window %lld, frame %lld, channel %lld, row %lld)", fn, win_stride, l->frame, l->channel, l->row);
-    if (!frames_dev) REFUSE("%s: frames_dev is null", fn);
-    long long last = 0;
-    if (!extent_add(&last, nwin - 1, win_stride) || !extent_add(&last, F - 1, l->frame) || !extent_add(&last, 2, l->channel) || !extent_add(&last, h - 1, l->row) ||
-        !extent_add(&last, w - 1, l->column))
-        REFUSE("%s: the strides of layout reach beyond the 64-bit range: the view of frames_dev cannot lie inside an allocation", fn);
-    return check_device_pointer(ctx, fn, "frames_dev", frames_dev, last, dev_elem_size(l->dtype));
-}
-
-// a strided fp32 field of `nd` dimensions (sizes n[], strides st[], the last one the column): the pointer and the strides' signs
-int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd) {
-    if (!st) REFUSE("%s: the strides of %s are null", fn, arg);
-    if (st[nd - 1] < 1) REFUSE("%s: the column stride of %s is %lld: it must be >= 1", fn, arg, st[nd - 1]);
-    long long last = 0;
-    for (int i = 0; i < nd; i++) {
-        if (st[i] < 0) REFUSE("%s: stride %d of %s is negative (%lld)", fn, i, arg, st[i]);
-        if (!extent_add(&last, n[i] - 1, st[i])) REFUSE("%s: the strides of %s reach beyond the 64-bit range: the view cannot lie inside an allocation", fn, arg);
-    }
-    return check_device_pointer(ctx, fn, arg, p, last, sizeof(float));
-}
-
-// strides sorted, each larger than the extent of all smaller ones: no two elements of the field share an address (dimensions of size 1 do not count)
-bool strides_nest(const long long *st, const int *n, int nd) {
-    std::vector<std::pair<long long, int>> d;
-    for (int i = 0; i < nd; i++) if (n[i] > 1) d.emplace_back(st[i], n[i]);
-    std::sort(d.begin(), d.end());
-    long long extent = 0;                                  // offset of the last element of the dimensions so far
-    for (auto &e : d) {
-        if (e.first <= extent) return false;
-        extent += (e.second - 1) * e.first;
-    }
-    return true;
+    static const char *const dim[5] = {"layout.window", "layout.frame", "layout.channel", "layout.row", "layout.column"};
+    const long long st[5] = {win_stride, l->frame, l->channel, l->row, l->column};
+    return check_view(ctx, fn, View{"frames_dev", frames_dev, dev_elem_size(l->dtype), 5, {nwin, F, 3, h, w}, st, dim});
 }
 
 int check_batch_range(sfa_ctx *ctx, const char *fn, const char *what, int b0, int n, int nb) {
@@ -789,34 +783,26 @@ int check_batch_range(sfa_ctx *ctx, const char *fn, const char *what, int b0, in
     return SFA_OK;
 }
 
-// overlap.  (1) every (window, plane) in a byte range of its own, and each plane free of overlap in itself; else (2) flow and occlusions apart, and each a
-// layout of nested strides.  Both are sufficient conditions: what neither proves is refused.
+// download destinations: flow [n][2][h][w], occlusions [n][h][w] or null.  Each a checked view, and free of overlap by one of two sufficient conditions:
+// (1) every (window, plane) in a byte range of its own, and each plane's strides nested; else (2) flow and occlusions apart, and each a layout of nested
+// strides (which takes planes that lie interleaved).  What neither proves is refused.
 int check_download_destination(sfa_ctx *ctx, const char *fn, int n, int w, int h, float *flow_dev, const long long strides[4], float *occ_dev,
                                const long long occ_strides[3]) {
-    if (!flow_dev) REFUSE("%s: flow_dev is null", fn);
-    const int fsz[4] = {n, 2, h, w}, osz[3] = {n, h, w};
-    SFA_TRY(check_field(ctx, fn, "flow_dev", flow_dev, strides, fsz, 4));
-    if (occ_dev) SFA_TRY(check_field(ctx, fn, "occ_dev", occ_dev, occ_strides, osz, 3));
-    const uintptr_t f0 = reinterpret_cast<uintptr_t>(flow_dev), o0 = reinterpret_cast<uintptr_t>(occ_dev);
-    const long long fspan = (h - 1) * strides[2] + (w - 1) * strides[3];
-    const long long ospan = occ_dev ? (h - 1) * occ_strides[1] + (w - 1) * occ_strides[2] : 0;
-    bool ok = strides_nest(strides + 2, fsz + 2, 2) && (!occ_dev || strides_nest(occ_strides + 1, osz + 1, 2));
+    const View flow{"flow_dev", flow_dev, sizeof(float), 4, {n, 2, h, w}, strides}, occ{"occ_dev", occ_dev, sizeof(float), 3, {n, h, w}, occ_strides};
+    SFA_TRY(check_view(ctx, fn, flow));
+    if (occ_dev) SFA_TRY(check_view(ctx, fn, occ));
+    bool ok = strides_nest(strides + 2, flow.n + 2, 2) && (!occ_dev || strides_nest(occ_strides + 1, occ.n + 1, 2));
     if (ok) {
-        std::vector<std::pair<uintptr_t, uintptr_t>> r;       // [first byte, last byte] of every plane
+        std::vector<ByteRange> r;
+        r.reserve((size_t)3 * n);
         for (int i = 0; i < n; i++) {
-            for (int p = 0; p < 2; p++) { const uintptr_t a = f0 + 4 * (uintptr_t)(i * strides[0] + p * strides[1]); r.emplace_back(a, a + 4 * (uintptr_t)fspan + 3); }
-            if (occ_dev) { const uintptr_t a = o0 + 4 * (uintptr_t)(i * occ_strides[0]); r.emplace_back(a, a + 4 * (uintptr_t)ospan + 3); }
+            for (int p = 0; p < 2; p++) r.push_back(byte_range(View{"", flow_dev + i * strides[0] + p * strides[1], sizeof(float), 2, {h, w}, strides + 2}));
+            if (occ_dev) r.push_back(byte_range(View{"", occ_dev + i * occ_strides[0], sizeof(float), 2, {h, w}, occ_strides + 1}));
         }
-        std::sort(r.begin(), r.end());
-        for (size_t i = 1; i < r.size() && ok; i++) ok = r[i].first > r[i - 1].second;
+        int a, b;
+        ok = !first_overlap(r.data(), (int)r.size(), &a, &b);
     }
-    if (!ok) {
-        ok = strides_nest(strides, fsz, 4) && (!occ_dev || strides_nest(occ_strides, osz, 3));
-        if (ok && occ_dev) {
-            const uintptr_t fe = f0 + 4 * (uintptr_t)((n - 1) * strides[0] + strides[1] + fspan) + 3, oe = o0 + 4 * (uintptr_t)((n - 1) * occ_strides[0] + ospan) + 3;
-            ok = fe < o0 || oe < f0;
-        }
-    }
+    if (!ok) ok = strides_nest(strides, flow.n, 4) && (!occ_dev || (strides_nest(occ_strides, occ.n, 3) && !overlap(byte_range(flow), byte_range(occ))));
     if (!ok) REFUSE("%s: the destinations overlap: windows or planes of flow_dev%s share memory (or lie interleaved in a way the check cannot clear)", fn, occ_dev ? " / occ_dev" : "");
     return SFA_OK;
 }
@@ -829,7 +815,7 @@ int check_mosaic_method(sfa_ctx *ctx, const char *fn, int method, int red_x, int
     if (red_y != 0 && red_y != 1) REFUSE("%s: red_y = %d: the red site's row parity is 0 or 1", fn, red_y);
     return SFA_OK;
 }
-// the descriptor against the crop's size w x h; the pointer itself is check_mosaic_pointer's
+// the descriptor against the crop's size w x h; the pointer and the strides are check_view's
 static int check_mosaic_geometry(sfa_ctx *ctx, const char *fn, int dtype, int W, int H, int x0, int y0, int w, int h, int method) {
     if (dtype != SFA_DEV_F32 && dtype != SFA_DEV_U8 && dtype != SFA_DEV_U16) REFUSE("%s: desc.dtype %d is no element type (fp32 0, u8 1, u16 2)", fn, dtype);
     if (w < 1 || h < 1) REFUSE("%s: w = %d, h = %d: the destination is empty", fn, w, h);
@@ -839,16 +825,11 @@ static int check_mosaic_geometry(sfa_ctx *ctx, const char *fn, int dtype, int W,
         REFUSE("%s: the crop desc.x0 = %d, desc.y0 = %d of %d x %d leaves the mosaic of desc.W = %d, desc.H = %d", fn, x0, y0, w, h, W, H);
     return SFA_OK;
 }
-// the view of mosaic_dev: all W x H elements of its n frames (the kernels read up to two pixels beyond the crop)
-static int check_mosaic_pointer(sfa_ctx *ctx, const char *fn, const void *mosaic_dev, const sfa_mosaic_desc *d, int n, long long *last_out) {
-    if (d->column < 1) REFUSE("%s: desc.column = %lld: the column stride must be >= 1", fn, d->column);
-    if (d->frame < 0 || d->row < 0) REFUSE("%s: desc holds a negative stride (frame %lld, row %lld)", fn, d->frame, d->row);
-    if (!mosaic_dev) REFUSE("%s: mosaic_dev is null", fn);
-    long long last = 0;
-    if (!extent_add(&last, n - 1, d->frame) || !extent_add(&last, d->H - 1, d->row) || !extent_add(&last, d->W - 1, d->column))
-        REFUSE("%s: the strides of desc reach beyond the 64-bit range: the view of mosaic_dev cannot lie inside an allocation", fn);
-    *last_out = last;
-    return check_device_pointer(ctx, fn, "mosaic_dev", mosaic_dev, last, dev_elem_size(d->dtype));
+// the view of mosaic_dev: all W x H elements of its n frames (the kernels read up to two pixels beyond the crop); st: room for its strides
+static View mosaic_view(const void *mosaic_dev, const sfa_mosaic_desc *d, int n, long long st[3]) {
+    static const char *const dim[3] = {"desc.frame", "desc.row", "desc.column"};
+    st[0] = d->frame; st[1] = d->row; st[2] = d->column;
+    return View{"mosaic_dev", mosaic_dev, dev_elem_size(d->dtype), 3, {n, d->H, d->W}, st, dim};
 }
 
 }  // namespace sfa
@@ -866,7 +847,7 @@ int sfa_sequence_upload_device(sfa_sequence *q, int f0, int n, const void *frame
     CHECK_ARGS(q, "seq is null");
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     if (f0 < 0 || n < 1 || (long)f0 + n > q->n) REFUSE("%s: frames f0 = %d, n = %d lie outside the sequence of %d", __func__, f0, n, q->n);
-    SFA_TRY(check_frames_source(ctx, __func__, frames_dev, l, l ? l->frame : 0, n, 1, q->w, q->h));
+    SFA_TRY(check_frames_source(ctx, __func__, frames_dev, l, 0, 1, n, q->w, q->h));
     const size_t elem = dev_elem_size(l->dtype);
     const int chunk = 16384;                                // 3 planes per frame in the grid's z: below 65536
     for (int i = 0; i < n; i += chunk) {
@@ -886,16 +867,12 @@ int sfa_demosaic_device(sfa_ctx *ctx, int n, const void *mosaic_dev, const sfa_m
     if (!d) REFUSE("%s: desc is null", __func__);
     SFA_TRY(check_mosaic_method(ctx, __func__, method, red_x, red_y));
     SFA_TRY(check_mosaic_geometry(ctx, __func__, d->dtype, d->W, d->H, d->x0, d->y0, w, h, method));
-    long long slast = 0;
-    SFA_TRY(check_mosaic_pointer(ctx, __func__, mosaic_dev, d, n, &slast));
-    if (!dst_dev) REFUSE("%s: dst_dev is null", __func__);
-    const int sizes[4] = {n, 3, h, w};
-    SFA_TRY(check_field(ctx, __func__, "dst_dev", dst_dev, st, sizes, 4));
-    if (!strides_nest(st, sizes, 4)) REFUSE("%s: dst_strides let frames, channels or rows of dst_dev share memory (or interleave them in a way the check cannot clear)", __func__);
-    const long long dlast = (n - 1) * st[0] + 2 * st[1] + (h - 1) * st[2] + (w - 1) * st[3];
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(mosaic_dev), s1 = s0 + (uintptr_t)slast * dev_elem_size(d->dtype) + dev_elem_size(d->dtype) - 1;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_dev), d1 = d0 + (uintptr_t)dlast * 4 + 3;
-    if (!(s1 < d0 || d1 < s0)) REFUSE("%s: dst_dev overlaps mosaic_dev: the kernel reads a pixel's neighbours after other blocks have written theirs", __func__);
+    long long sst[3];
+    const View from = mosaic_view(mosaic_dev, d, n, sst), to{"dst_dev", dst_dev, sizeof(float), 4, {n, 3, h, w}, st};
+    SFA_TRY(check_view(ctx, __func__, from));
+    SFA_TRY(check_view(ctx, __func__, to));
+    if (!strides_nest(st, to.n, 4)) REFUSE("%s: dst_strides let frames, channels or rows of dst_dev share memory (or interleave them in a way the check cannot clear)", __func__);
+    SFA_TRY(check_disjoint(ctx, __func__, {to, from}, "the kernel reads a pixel's neighbours after other blocks have written theirs"));
     const MosaicSrc src{mosaic_dev, d->dtype, d->frame, d->row, d->column, d->W, d->H, d->x0, d->y0};
     const MosaicDst dst{dst_dev, st[0], st[1], st[2], st[3], w, h};
     launch_demosaic(ctx, src, dst, n, method, red_x, red_y);
@@ -911,8 +888,8 @@ int sfa_sequence_upload_mosaic_device(sfa_sequence *q, int f0, int n, const void
     if (!d) REFUSE("%s: desc is null", __func__);
     SFA_TRY(check_mosaic_method(ctx, __func__, method, red_x, red_y));
     SFA_TRY(check_mosaic_geometry(ctx, __func__, d->dtype, d->W, d->H, d->x0, d->y0, q->w, q->h, method));
-    long long slast = 0;
-    SFA_TRY(check_mosaic_pointer(ctx, __func__, mosaic_dev, d, n, &slast));
+    long long sst[3];
+    SFA_TRY(check_view(ctx, __func__, mosaic_view(mosaic_dev, d, n, sst)));
     const MosaicSrc src{mosaic_dev, d->dtype, d->frame, d->row, d->column, d->W, d->H, d->x0, d->y0};
     const MosaicDst dst{q->frame(f0), 3 * (long long)q->pl, q->pl, q->pitch, 1, q->w, q->h};
     launch_demosaic(ctx, src, dst, n, method, red_x, red_y);

@@ -8,7 +8,8 @@
 //     128 windows), so they leave as non-temporal stores -- what k_warp_smooth's warped images taught (the kernel waited for its write
 //     path, and its neighbours gained more than it did),
 //   - a thread issues the loads of its four rows before the first store, so that no load queues behind a store in the wave's in-order memory counter.
-// The checks of the arguments (device pointers of this GPU, strides, overlap) are api.hip's: nothing here is launched on a refused argument.
+// The checks of the arguments (strides, overlap: dev_view.h; device pointers of this GPU: api.hip's check_view) come first: nothing here is launched on a
+// refused argument.
 #include "sfa_internal.h"
 
 namespace sfa {

@@ -1,5 +1,5 @@
 // job.hip -- the resident multi-frame job behind the C-ABI of include/slowflow_amd.h: Variational_MT::variational and compute_one_level (variational_mt.cpp:169-493,
-// 526-784) for a batch of frame windows in lockstep.  struct sfa_job and every sfa_job_* entry point (the device seam's too: its argument checks are api.hip's, its
+// 526-784) for a batch of frame windows in lockstep.  struct sfa_job and every sfa_job_* entry point (the device seam's too: its argument checks are api.hip's on dev_view.h, its
 // kernels device_io.hip's), the pyramid geometry, and sfa_variational / sfa_compute_one_level on top.  All compute is in kernels.hip / sor*.hip / occlusion.hip.
 //
 // A job is ONE allocation of nb element arenas.  Element arena (floats, per window; the same element stride for every plane of every level), PL = pitch*h of the level:
@@ -656,7 +656,7 @@ int sfa_job_download_occlusions(sfa_job *j, int b, float *occ, int stride) {
     return sfa_ctx_sync(ctx);
 }
 
-// ---- the device seam (include/slowflow_amd.h; kernels: device_io.hip; the argument checks: api.hip, declared in sfa_internal.h) ---------------------
+// ---- the device seam (include/slowflow_amd.h; kernels: device_io.hip; the argument checks: dev_view.h and api.hip, declared in sfa_internal.h) -------
 // Every check is taken on the host before anything is launched; a refusal names the argument.
 int sfa_job_upload_device(sfa_job *j, int b0, int n, const void *frames_dev, const sfa_dev_layout *l, const float *const chw[3]) {
     sfa_ctx *ctx = j ? j->ctx : nullptr;
@@ -699,8 +699,7 @@ int sfa_job_set_flow_device(sfa_job *j, int b0, int n, const float *flow_dev, co
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     SFA_TRY(job_windows(ctx, __func__, j, b0, n));
     if (flow_dev) {
-        const int sizes[4] = {n, 2, j->h, j->w};
-        SFA_TRY(check_field(ctx, __func__, "flow_dev", flow_dev, strides, sizes, 4));
+        SFA_TRY(check_view(ctx, __func__, View{"flow_dev", flow_dev, sizeof(float), 4, {n, 2, j->h, j->w}, strides}));
     }
     Level L0 = j->level(0);
     launch_pack_flow(ctx, j->init_flow.f() + (long)b0 * 2 * L0.pl, 2 * L0.pl, L0.pl, L0.pitch, j->w, j->h, n, flow_dev, strides);

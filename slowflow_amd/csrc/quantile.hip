@@ -17,6 +17,7 @@
 // a group has its own record (GroupSel: SelState, value count, which ranks answer), its own histograms and its own packed keys, so no block mixes two
 // groups in its LDS histogram.  k_group_keys_hist is pass 1 reading u and v in place through element strides; passes 2, 3 and the scans are the bodies of
 // k_digit_hist / k_select_digit on the group's pointers; k_group_result applies the rule of :663/:665/:668 and leaves {quantile, max} in GPU memory.
+// Its pointers and strides are checked as views by check_view / check_disjoint (api.hip on dev_view.h); only the rule that rows too need a stride >= 1 is its own.
 #include "sfa_device.h"
 
 #pragma clang fp contract(off)
@@ -268,24 +269,19 @@ int sfa_flow_magnitude_quantiles_device(sfa_ctx *ctx, int G, int n, const int *c
     const size_t per = (size_t)w * h;
     if (per * (size_t)most > 0xffffffffull)
         REFUSE("%s: n = %d fields of w x h = %d x %d are %zu values in a group, beyond the 32-bit counts", __func__, most, w, h, per * (size_t)most);
-    if (!u_dev) REFUSE("%s: u_dev is null", __func__);
-    if (!v_dev) REFUSE("%s: v_dev is null", __func__);
-    if (!out_dev) REFUSE("%s: out_dev is null", __func__);
     if (!strides) REFUSE("%s: strides is null", __func__);
     if (strides[2] < 1 || strides[3] < 1) REFUSE("%s: strides: row stride %lld, column stride %lld; both must be >= 1", __func__, strides[2], strides[3]);
-    const int sizes[4] = {G, n, h, w};
-    SFA_TRY(check_field(ctx, __func__, "u_dev", u_dev, strides, sizes, 4));
-    SFA_TRY(check_field(ctx, __func__, "v_dev", v_dev, strides, sizes, 4));
-    if (!strides_nest(strides + 1, sizes + 1, 3))
+    const long long pair[2] = {2, 1};
+    const View u{"u_dev", u_dev, sizeof(float), 4, {G, n, h, w}, strides}, v{"v_dev", v_dev, sizeof(float), 4, {G, n, h, w}, strides},
+        out{"out_dev", out_dev, sizeof(double), 2, {G, 2}, pair};
+    SFA_TRY(check_view(ctx, __func__, u));
+    SFA_TRY(check_view(ctx, __func__, v));
+    if (!strides_nest(strides + 1, u.n + 1, 3))
         REFUSE("%s: strides (field %lld, row %lld, column %lld) let two elements of one group share an address (or interleave them in a way the check cannot clear)",
                __func__, strides[1], strides[2], strides[3]);
-    SFA_TRY(check_device_pointer(ctx, __func__, "out_dev", out_dev, 2LL * G - 1, sizeof(double)));
-    const long long last = (G - 1) * strides[0] + (n - 1) * strides[1] + (h - 1) * strides[2] + (w - 1) * strides[3];
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev), o1 = o0 + (uintptr_t)G * 16 - 1;
-    for (const float *p : {u_dev, v_dev}) {
-        const uintptr_t f0 = reinterpret_cast<uintptr_t>(p), f1 = f0 + (uintptr_t)last * 4 + 3;
-        if (!(f1 < o0 || o1 < f0)) REFUSE("%s: out_dev overlaps %s: the results would be written into flows still being read", __func__, p == u_dev ? "u_dev" : "v_dev");
-    }
+    SFA_TRY(check_view(ctx, __func__, out));
+    for (const View &f : {u, v})                                                // (u and v may interleave: each against out_dev alone)
+        SFA_TRY(check_disjoint(ctx, __func__, {out, f}, "the results would be written into flows still being read"));
     GroupSelAll all{};
     for (int g = 0; g < G; g++) {
         GroupSel &s = all.g[g];

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/slowflow_amd.h"
+#include "dev_view.h"
 
 #pragma clang fp contract(off)   // the reference is strict fp32 without FMA contraction (CMakeLists.txt:6)
 
@@ -423,17 +424,18 @@ int sor_rb_run(sfa_ctx *c, const Geo &g, float *du, float *dv, float *a11, float
 int sor_run(sfa_ctx *c, SorWorkspace &ws, const Geo &g, float *du, float *dv, float *a11, float *a12, float *a22, const float *b1, const float *b2,
             const float *sh, const float *sv, int K, float omega, bool inv_out);
 
-// ---- the device seam's argument checks (api.hip), shared by sfa_job_*_device (job.hip) and sfa_pair_job_*_device (two_frame.hip).  Each refuses with SFA_ERR_ARG and a
-// message that names `fn` and the argument; nothing is launched on a refusal ----------------------------------------------------------------------------
-// the frames of `nwin` windows (or pairs, or sequence frames) of F frames each: layout and pointer
+// ---- the device seam's argument checks, shared by every entry point that takes device memory (job.hip, two_frame.hip, track.hip, quantile.hip, api.hip).
+// The arithmetic -- View, the sign and extent rule, strides_nest, byte ranges and their overlap -- is dev_view.h's, host code a CPU test compiles; what asks
+// the HIP runtime is api.hip's.  Each refuses with SFA_ERR_ARG and a message that names `fn` and the argument; nothing is launched on a refusal ------------
+// a view: refuses a null pointer or null strides, then what view_extent refuses, then what check_device_pointer does
+__attribute__((visibility("hidden"))) int check_view(sfa_ctx *ctx, const char *fn, const View &v, long long min_inner = 1);
+// no two of the checked views share a byte (a null pointer is skipped); why: what an overlap would break, or null
+__attribute__((visibility("hidden"))) int check_disjoint(sfa_ctx *ctx, const char *fn, std::initializer_list<View> views, const char *why = nullptr);
+// the frames of `nwin` windows (or pairs) of F frames each, or a sequence's n frames as one window of n: the layout's element type, and its view
 int check_frames_source(sfa_ctx *ctx, const char *fn, const void *frames_dev, const sfa_dev_layout *l, long long win_stride, int nwin, int F, int w, int h);
 // p is device memory of the context's GPU, and element `last` (of `elem` bytes) lies inside its allocation
 int check_device_pointer(sfa_ctx *ctx, const char *fn, const char *arg, const void *p, long long last, size_t elem);
-// a strided fp32 field of `nd` dimensions (sizes n[], strides st[], the last one the column): the pointer and the strides' signs
-int check_field(sfa_ctx *ctx, const char *fn, const char *arg, const float *p, const long long *st, const int *n, int nd);
-// strides sorted, each larger than the extent of all smaller ones: no two elements of the field share an address (a sufficient condition)
-bool strides_nest(const long long *st, const int *n, int nd);
-// download destinations: flow [n][2][h][w] at `strides`, occlusions [n][h][w] at `occ_strides` (or null): pointers, strides, and freedom from overlap
+// download destinations: flow [n][2][h][w] at `strides`, occlusions [n][h][w] at `occ_strides` (or null): checked views, and freedom from overlap
 int check_download_destination(sfa_ctx *ctx, const char *fn, int n, int w, int h, float *flow_dev, const long long strides[4], float *occ_dev,
                                const long long occ_strides[3]);
 // elements [b0, b0 + n) of a batch of nb (`what`: "windows", "pairs")

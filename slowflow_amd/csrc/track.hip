@@ -6,10 +6,8 @@
 // the chain needs a host decision, and no stage boundary crosses the host.  The flows are brought into the kernels' layout when they are uploaded (host
 // planes: a copy and the stage wrappers' kernels; device memory: the pack kernels below), so a run reads only what the job holds.
 // Segment s of a run comes out with the bits of the staged calls on that segment alone: the same kernels over the same planes, blockIdx.y = s.
+// The device entry points describe their arguments as views and leave every check of them to check_view / check_disjoint (api.hip on dev_view.h).
 #include <algorithm>
-#include <cstdint>
-#include <utility>
-#include <vector>
 
 #include "sfa_device.h"
 
@@ -317,10 +315,9 @@ int sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r,
     SFA_TRY(track_range(ctx, __func__, p, s0, ns, r));
     if (p.use_occlusions) REFUSE("%s: the job was created with use_occlusions: its occlusion images come with sfa_track_job_upload_flows", __func__);
     const sfa_jet_source &src = p.source[r];
-    const int rJ = p.r_Jets[r], sz[5] = {ns, rJ, 2, src.sh, src.sw};
-    if (!fwd_dev || !bwd_dev) REFUSE("%s: %s is null", __func__, fwd_dev ? "bwd_dev" : "fwd_dev");
-    SFA_TRY(check_field(ctx, __func__, "fwd_dev", fwd_dev, strides, sz, 5));
-    SFA_TRY(check_field(ctx, __func__, "bwd_dev", bwd_dev, strides, sz, 5));
+    const int rJ = p.r_Jets[r];
+    SFA_TRY(check_view(ctx, __func__, View{"fwd_dev", fwd_dev, sizeof(float), 5, {ns, rJ, 2, src.sh, src.sw}, strides}));
+    SFA_TRY(check_view(ctx, __func__, View{"bwd_dev", bwd_dev, sizeof(float), 5, {ns, rJ, 2, src.sh, src.sw}, strides}));
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const bool identity = job->identity[r];
     const size_t tap = identity ? 8 : 16, seg = (size_t)rJ * pl;
@@ -349,9 +346,7 @@ int sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r,
 int sfa_track_job_upload_frames_device(sfa_track_job *job, int s0, int ns, const float *frames_dev, const long long strides[5]) {
     TRACK_JOB(job);
     SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
-    if (!frames_dev) REFUSE("%s: frames_dev is null", __func__);
-    const int sz[5] = {ns, p.Jets + 1, 3, p.h, p.w};
-    SFA_TRY(check_field(ctx, __func__, "frames_dev", frames_dev, strides, sz, 5));
+    SFA_TRY(check_view(ctx, __func__, View{"frames_dev", frames_dev, sizeof(float), 5, {ns, p.Jets + 1, 3, p.h, p.w}, strides}));
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const size_t total = (size_t)ns * (p.Jets + 1) * 3 * pl;
     hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, frames_dev, strides[0], strides[1], strides[2], strides[3],
@@ -470,50 +465,21 @@ int sfa_ctx_free_bytes(sfa_ctx *ctx, size_t *free_bytes) {
     return SFA_OK;
 }
 
-// a destination's byte range [lo, hi) and whether its strides nest: sorted by stride, each at least the extent of all smaller ones, so that no two elements
-// share an address (dimensions of size 1 do not count)
-static bool nested(const long long *st, const int *n, int nd) {
-    std::vector<std::pair<long long, int>> d;
-    for (int i = 0; i < nd; i++)
-        if (n[i] > 1) d.emplace_back(st[i], n[i]);
-    std::sort(d.begin(), d.end());
-    long long extent = 1;
-    for (auto &q : d) {
-        if (q.first < extent) return false;
-        extent = q.first * (q.second - 1) + extent;
-    }
-    return true;
-}
-
 int sfa_track_job_download_device(sfa_track_job *job, int s0, int ns, double *flow_dev, const long long strides[4], int *slot_dev, unsigned char *occ_dev,
                                   double *stats_dev) {
     TRACK_JOB(job);
     SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
     if (!p.do_fuse) REFUSE("%s: the job was created with do_fuse = 0: it holds no fused result", __func__);
-    if (!flow_dev) REFUSE("%s: flow_dev is null", __func__);
-    if (!strides) REFUSE("%s: the strides of flow_dev are null", __func__);
-    const int sz[4] = {ns, 2, job->gh, job->gw};
-    long long last = 0;
-    for (int i = 0; i < 4; i++) {
-        if (strides[i] < (i == 3 ? 1 : 0)) REFUSE("%s: stride %d of flow_dev is %lld", __func__, i, strides[i]);
-        long long t;
-        if (__builtin_mul_overflow((long long)(sz[i] - 1), strides[i], &t) || __builtin_add_overflow(last, t, &last))
-            REFUSE("%s: the strides of flow_dev reach beyond the 64-bit range", __func__);
-    }
-    if (!nested(strides, sz, 4)) REFUSE("%s: the strides of flow_dev (%lld, %lld, %lld, %lld) let two elements of [%d][2][%d][%d] share an address", __func__,
-                                        strides[0], strides[1], strides[2], strides[3], ns, job->gh, job->gw);
-    SFA_TRY(check_device_pointer(ctx, __func__, "flow_dev", flow_dev, last, 8));
-    if (slot_dev) SFA_TRY(check_device_pointer(ctx, __func__, "slot_dev", slot_dev, (long long)((size_t)ns * gpl) - 1, 4));
-    if (occ_dev) SFA_TRY(check_device_pointer(ctx, __func__, "occ_dev", occ_dev, (long long)((size_t)ns * gpl) - 1, 1));
-    if (stats_dev) SFA_TRY(check_device_pointer(ctx, __func__, "stats_dev", stats_dev, 3ll * ns - 1, 8));
-    struct Range { const char *name; uintptr_t lo, hi; } rg[4] = {
-        {"flow_dev", reinterpret_cast<uintptr_t>(flow_dev), reinterpret_cast<uintptr_t>(flow_dev) + ((size_t)last + 1) * 8},
-        {"slot_dev", reinterpret_cast<uintptr_t>(slot_dev), reinterpret_cast<uintptr_t>(slot_dev) + (size_t)ns * gpl * 4},
-        {"occ_dev", reinterpret_cast<uintptr_t>(occ_dev), reinterpret_cast<uintptr_t>(occ_dev) + (size_t)ns * gpl},
-        {"stats_dev", reinterpret_cast<uintptr_t>(stats_dev), reinterpret_cast<uintptr_t>(stats_dev) + (size_t)ns * 24}};
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++)
-            if (rg[a].lo && rg[b].lo && rg[a].lo < rg[b].hi && rg[b].lo < rg[a].hi) REFUSE("%s: %s and %s overlap", __func__, rg[a].name, rg[b].name);
+    // the fp64 flow at the caller's strides; slot, occlusions and statistics (each optional) dense
+    const long long plane[2] = {(long long)gpl, 1}, triple[2] = {3, 1};
+    const View flow{"flow_dev", flow_dev, sizeof(double), 4, {ns, 2, job->gh, job->gw}, strides}, slot{"slot_dev", slot_dev, sizeof(int), 2, {ns, (int)gpl}, plane},
+        occ{"occ_dev", occ_dev, 1, 2, {ns, (int)gpl}, plane}, stats{"stats_dev", stats_dev, sizeof(double), 2, {ns, 3}, triple};
+    SFA_TRY(check_view(ctx, __func__, flow));
+    if (!strides_nest(strides, flow.n, 4)) REFUSE("%s: the strides of flow_dev (%lld, %lld, %lld, %lld) let two elements of [%d][2][%d][%d] share an address", __func__,
+                                                 strides[0], strides[1], strides[2], strides[3], ns, job->gh, job->gw);
+    for (const View *v : {&slot, &occ, &stats})
+        if (v->p) SFA_TRY(check_view(ctx, __func__, *v));
+    SFA_TRY(check_disjoint(ctx, __func__, {flow, slot, occ, stats}));
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const TrackPlanes &at = job->at;
     const size_t o = (size_t)s0 * gpl;

@@ -216,8 +216,7 @@ int sfa_pair_job_set_flow_device(sfa_pair_job *j, int b0, int n, const float *fl
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     SFA_TRY(check_batch_range(ctx, __func__, "pairs", b0, n, j->n));
     if (flow_dev) {
-        const int sizes[4] = {n, 2, j->h, j->w};
-        SFA_TRY(check_field(ctx, __func__, "flow_dev", flow_dev, strides, sizes, 4));
+        SFA_TRY(check_view(ctx, __func__, View{"flow_dev", flow_dev, sizeof(float), 4, {n, 2, j->h, j->w}, strides}));
     }
     launch_pack_flow(ctx, j->plane(b0, J::WX), j->es, j->pl, j->pitch, j->w, j->h, n, flow_dev, strides);
     SFA_HIP(ctx, hipGetLastError());

@@ -2,8 +2,9 @@
 and results that live in GPU memory go in and out of a job without a host copy.
 
 The core takes any object with `__cuda_array_interface__` (torch-ROCm tensors, cupy arrays ...) and needs no torch; `import slowflow_amd` does not
-import this module, and this module imports torch only inside refine(), refine_pairs(), track() and flow_quantiles(), to allocate the outputs and to
-find the caller's current stream.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which
+import this module, and this module imports torch only inside demosaic(), refine(), refine_pairs(), track() and flow_quantiles(), to allocate the outputs
+and to find the caller's current stream (on_stream, the one stream bracket of the five).  device_view is the one place an argument's element type, rank
+and shape are checked.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which
 never waits for the GPU; track() dense_tracking's accumulation, energies and fusion on a resident track job, which does not wait either;
 flow_quantiles() adaptiveFR's flow-magnitude quantile and maximum of groups of flows, left in GPU memory.
 
@@ -11,6 +12,7 @@ Stream contract: the library works on the context's own stream.  Context.wait_st
 caller has submitted to s; Context.signal_stream(s) after the last makes s wait for the library.  refine() and refine_pairs() do both.  With the two in place a tensor
 freed or reused on s is ordered after the library's last access, so torch's caching allocator needs no record_stream.
 """
+import contextlib
 import ctypes as C
 import sys
 from collections import OrderedDict
@@ -21,6 +23,7 @@ import slowflow_amd as sfa
 
 MAX_BATCH = 128                                   # windows of one job (csrc/sfa_internal.h: kMaxBatch)
 DTYPES = {"f4": 0, "u1": 1, "u2": 2}              # sfa_dev_dtype by typestr kind + size
+KIND_NAMES = {"f4": "fp32", "f8": "fp64", "i4": "int32", "u1": "uint8", "u2": "uint16"}
 
 
 class DevLayout(C.Structure):
@@ -30,25 +33,34 @@ class DevLayout(C.Structure):
 
 
 class DeviceView:
-    """pointer, element type (sfa_dev_dtype), shape and ELEMENT strides of a device array"""
+    """pointer, element type (sfa_dev_dtype, or None where none names it), shape and ELEMENT strides of a device array; kind: the typestr's kind + size ("f4")"""
 
-    def __init__(self, ptr, dtype, itemsize, shape, strides, owner=None):
+    def __init__(self, ptr, dtype, itemsize, shape, strides, owner=None, kind=None):
         self.ptr, self.dtype, self.itemsize, self.shape, self.strides, self.owner = ptr, dtype, itemsize, tuple(shape), tuple(strides), owner
+        self.kind = kind if kind is not None else next((k for k, d in DTYPES.items() if d == dtype), None)
 
     def sub(self, start, n):
         """elements [start, start + n) of the first dimension"""
         assert 0 <= start and n >= 1 and start + n <= self.shape[0]
-        return DeviceView(self.ptr + start * self.strides[0] * self.itemsize, self.dtype, self.itemsize, (n,) + self.shape[1:], self.strides, self.owner)
+        return DeviceView(self.ptr + start * self.strides[0] * self.itemsize, self.dtype, self.itemsize, (n,) + self.shape[1:], self.strides, self.owner, self.kind)
 
 
-def device_view(obj, writable=False, name="array", ndim=None, kinds=None):
-    """obj.__cuda_array_interface__ -> DeviceView.  Refuses (SlowflowError naming `name`): objects without the interface (host arrays), element types
-    other than fp32 / u8 / u16, non-native byte order, byte strides that are no multiple of the item size, a read-only object asked for as an output,
-    and a rank other than `ndim`.  kinds: the element types taken instead of those three, e.g. ("f8",) for the track job's fp64 flow (the view's
-    dtype is then None: no sfa_dev_dtype names them).  Whether the pointer is device memory of the job's GPU is the library's check, made before anything is launched."""
+def device_view(obj, writable=False, name="array", ndim=None, kinds=None, shape=None, contiguous=False):
+    """obj.__cuda_array_interface__ -> DeviceView.  Refuses (SlowflowError naming `name`): a tensor on the CPU and objects without the interface (host
+    arrays), element types other than fp32 / u8 / u16, non-native byte order, byte strides that are no multiple of the item size, a read-only object asked
+    for as an output, a rank other than `ndim`, a shape other than `shape` (an entry that is None or a letter such as "B" takes any size; the rank
+    follows from it), and with `contiguous` any strides but the dense ones.  kinds: the element types taken instead of those three, e.g. ("f8",) for the
+    track job's fp64 flow (the view's dtype is then None where no sfa_dev_dtype names it).  Whether the pointer is device memory of the job's GPU is the
+    library's check, made before anything is launched."""
+    if shape is not None:
+        ndim = len(shape)
     if isinstance(obj, DeviceView):
         v = obj
+        if kinds is not None and v.kind not in kinds:           # (a view made earlier with other kinds, or by hand)
+            raise sfa.SlowflowError(f"{name}: element type {v.kind!r}, expected {' or '.join(KIND_NAMES[k] for k in kinds)}")
     else:
+        if getattr(obj, "is_cuda", True) is False:              # a torch tensor on the CPU raises from its __cuda_array_interface__
+            raise sfa.SlowflowError(f"{name}: a tensor on {getattr(obj, 'device', 'the host')}, not in GPU memory (the device entry points take device memory)")
         cai = getattr(obj, "__cuda_array_interface__", None)
         if cai is None:
             raise sfa.SlowflowError(f"{name}: {type(obj).__name__} has no __cuda_array_interface__ (a host array? the device entry points take device memory)")
@@ -58,11 +70,11 @@ def device_view(obj, writable=False, name="array", ndim=None, kinds=None):
         if order not in (native, "|", "="):
             raise sfa.SlowflowError(f"{name}: byte order of typestr {typestr!r} is not the machine's")
         if kinds is not None and kind not in kinds:
-            raise sfa.SlowflowError(f"{name}: element type {typestr!r}, expected {' or '.join(kinds)}")
+            raise sfa.SlowflowError(f"{name}: element type {typestr!r}, expected {' or '.join(KIND_NAMES[k] for k in kinds)}")
         if kinds is None and kind not in DTYPES:
             raise sfa.SlowflowError(f"{name}: element type {typestr!r} is not supported (fp32, uint8 and uint16 are; fp16, bf16, fp64 and signed integers are not)")
         item = int(kind[1:])
-        shape = tuple(int(s) for s in cai["shape"])
+        dims = tuple(int(s) for s in cai["shape"])
         ptr, readonly = cai["data"]
         if writable and readonly:
             raise sfa.SlowflowError(f"{name}: the object is read-only and cannot be an output")
@@ -71,7 +83,7 @@ def device_view(obj, writable=False, name="array", ndim=None, kinds=None):
         bst = cai.get("strides")
         if bst is None:
             st, acc = [], 1
-            for s in reversed(shape):
+            for s in reversed(dims):
                 st.append(acc)
                 acc *= s
             st = tuple(reversed(st))
@@ -79,12 +91,22 @@ def device_view(obj, writable=False, name="array", ndim=None, kinds=None):
             if any(int(b) % item for b in bst):
                 raise sfa.SlowflowError(f"{name}: byte strides {tuple(bst)} are not multiples of the item size {item}")
             st = tuple(int(b) // item for b in bst)
-        if any(s == 0 for s in shape):
-            raise sfa.SlowflowError(f"{name}: empty array, shape {shape}")
-        v = DeviceView(int(ptr or 0), DTYPES.get(kind), item, shape, st, obj)
+        if any(s == 0 for s in dims):
+            raise sfa.SlowflowError(f"{name}: empty array, shape {dims}")
+        v = DeviceView(int(ptr or 0), DTYPES.get(kind), item, dims, st, obj, kind)
     if ndim is not None and len(v.shape) != ndim:
         raise sfa.SlowflowError(f"{name}: rank {len(v.shape)}, shape {v.shape}; {ndim} dimensions expected")
+    if shape is not None and any(want is not None and not isinstance(want, str) and got != want for got, want in zip(v.shape, shape)):
+        raise sfa.SlowflowError(f"{name}: [{','.join('*' if want is None else str(want) for want in shape)}] expected, got shape {v.shape}")
+    if contiguous and v.strides != tuple(int(np.prod(v.shape[i + 1:])) for i in range(len(v.shape))):
+        raise sfa.SlowflowError(f"{name}: a contiguous array expected, element strides {v.strides}")
     return v
+
+
+def frames_size(v, channels_last=None):
+    """(h, w) of frames [B,F,3,H,W] (planar) or [B,F,H,W,3] (interleaved).  channels_last None: told from the shape, planar where both fit."""
+    last = (v.shape[2] != 3 and v.shape[4] == 3) if channels_last is None else channels_last
+    return (v.shape[2], v.shape[3]) if last else (v.shape[3], v.shape[4])
 
 
 def frames_layout(v, w, h, F, channels_last=None, name="frames"):
@@ -179,22 +201,16 @@ def _set_flow_device(job, fn, size, flow, b0, n):
         n = getattr(job, size) - b0 if n is None else n
         job.ctx._ck(getattr(_lib(), fn)(job.h_, int(b0), int(n), None, None), fn)
         return
-    v = device_view(flow, name="flow", ndim=4)
-    if v.dtype != DTYPES["f4"] or v.shape[1:] != (2, job.h, job.w):
-        raise sfa.SlowflowError(f"flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
+    v = device_view(flow, name="flow", kinds=("f4",), shape=("B", 2, job.h, job.w))
     job.ctx._ck(getattr(_lib(), fn)(job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), fn)
 
 
 def _download_device(job, fn, out_flow, b0, takes_occ=False, out_occ=None):
     """the flow of a job or a pair job: `fn` the C function; takes_occ: it has the two arguments of an optional occlusion destination"""
-    v = device_view(out_flow, writable=True, name="out_flow", ndim=4)
-    if v.shape[1:] != (2, job.h, job.w):
-        raise sfa.SlowflowError(f"out_flow: fp32 [B,2,{job.h},{job.w}] expected, got shape {v.shape}")
+    v = device_view(out_flow, writable=True, name="out_flow", shape=("B", 2, job.h, job.w))
     args = [job.h_, int(b0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)]
     if out_occ is not None:
-        o = device_view(out_occ, writable=True, name="out_occ", ndim=3)
-        if o.shape != (v.shape[0], job.h, job.w):
-            raise sfa.SlowflowError(f"out_occ: fp32 [{v.shape[0]},{job.h},{job.w}] expected, got shape {o.shape}")
+        o = device_view(out_occ, writable=True, name="out_occ", shape=(v.shape[0], job.h, job.w))
         args += [C.c_void_p(o.ptr), _LL3(*o.strides)]
     elif takes_occ:
         args += [None, None]
@@ -242,6 +258,22 @@ def sequence_upload_mosaic_device(seq, mosaic, red=(1, 0), method=0, f0=0, origi
                 "sfa_sequence_upload_mosaic_device")
 
 
+@contextlib.contextmanager
+def on_stream(torch, ctx, like, stream, alloc):
+    """The stream bracket of the public functions.  `stream` None is the current stream of the device of `like`; alloc(device) makes the outputs under that
+    stream, so that they belong to it; then the context's stream waits for it, the body enqueues, and it waits for the context -- also when the body
+    raises.  Yields (stream, the outputs)."""
+    if stream is None:
+        stream = torch.cuda.current_stream(like.device)
+    with torch.cuda.stream(stream):
+        outputs = alloc(like.device)
+    wait_stream(ctx, stream)
+    try:
+        yield stream, outputs
+    finally:
+        signal_stream(ctx, stream)
+
+
 def demosaic(ctx, mosaic, red=(1, 0), method=0, origin=(0, 0), size=None, *, stream=None):
     """Demosaic N Bayer mosaics that live on the context's GPU: mosaic = a torch tensor [N,H,W] (fp32, uint8 or uint16; any strides with a positive column
     stride); red = (red_x, red_y), the cfg's raw_red_loc; method 0 (bayer2rgbGR) or 2 (the 8-bit OpenCV conversion); origin / size = the crop (x0, y0) /
@@ -252,17 +284,10 @@ def demosaic(ctx, mosaic, red=(1, 0), method=0, origin=(0, 0), size=None, *, str
     n, desc, (w, h) = mosaic_desc(v, origin, size)
     if w < 1 or h < 1:
         raise sfa.SlowflowError(f"size: the crop {w} x {h} at origin {tuple(origin)} of the {v.shape[2]} x {v.shape[1]} mosaic is empty")
-    if stream is None:
-        stream = torch.cuda.current_stream(mosaic.device)
-    with torch.cuda.stream(stream):                              # the output belongs to the caller's stream
-        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=mosaic.device)
-    ov = device_view(out, writable=True, name="out")
-    wait_stream(ctx, stream)
-    try:
+    with on_stream(torch, ctx, mosaic, stream, lambda dev: torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)) as (_, out):
+        ov = device_view(out, writable=True, name="out")
         ctx._ck(_lib().sfa_demosaic_device(ctx.h, n, C.c_void_p(v.ptr), C.byref(desc), int(method), int(red[0]), int(red[1]), C.c_void_p(ov.ptr), _LL4(*ov.strides),
                                            w, h), "sfa_demosaic_device")
-    finally:
-        signal_stream(ctx, stream)
     return out
 
 
@@ -314,57 +339,48 @@ def refine(ctx, params, frames, flow=None, *, normalize=False, want_occ=False, s
     import torch
     F = 2 * (params.S - 1) + 1
     fv = device_view(frames, name="frames", ndim=5)
-    last = (fv.shape[2] != 3 and fv.shape[4] == 3) if channels_last is None else channels_last
-    h, w = (fv.shape[2], fv.shape[3]) if last else (fv.shape[3], fv.shape[4])
+    h, w = frames_size(fv, channels_last)
     B, _ = frames_layout(fv, w, h, F, channels_last)
-    flv = None
-    if flow is not None:
-        flv = device_view(flow, name="flow", ndim=4)
-        if flv.shape != (B, 2, h, w):
-            raise sfa.SlowflowError(f"flow: [{B},2,{h},{w}] expected, got shape {flv.shape}")
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
-    with torch.cuda.stream(stream):                              # the outputs belong to the caller's stream
-        out = torch.empty((B, 2, h, w), dtype=torch.float32, device=frames.device)
-        occ = torch.empty((B, h, w), dtype=torch.float32, device=frames.device) if want_occ else None
-    ov, cv = device_view(out, writable=True, name="out_flow"), (device_view(occ, writable=True, name="out_occ") if want_occ else None)
+    flv = device_view(flow, name="flow", kinds=("f4",), shape=(B, 2, h, w)) if flow is not None else None
     change = np.zeros((B, 2), np.float32)
-    sizes = pair_sizes(B)
-    wait_stream(ctx, stream)
     seq = None
+
+    def outputs(dev):
+        return torch.empty((B, 2, h, w), dtype=torch.float32, device=dev), (torch.empty((B, h, w), dtype=torch.float32, device=dev) if want_occ else None)
     try:
-        if normalize:
-            params = type(params).from_buffer_copy(params)
-            seq = sfa.Sequence(ctx, w, h, B * F)
-            for b in range(B):                                   # window-major: sequence frame b F + f
-                _, lay = frames_layout(fv.sub(b, 1), w, h, F, channels_last)
-                lay.window = 0
-                ctx._ck(_lib().sfa_sequence_upload_device(seq.h_, b * F, F, C.c_void_p(fv.ptr + b * fv.strides[0] * fv.itemsize), C.byref(lay)),
-                        "sfa_sequence_upload_device")
-            avg, std = seq.normalize()
-            for k in range(3):
-                params.norm_avg[k], params.norm_std[k] = avg[k], std[k]
-        b0 = 0
-        for n in sizes:
-            # the statistics of normalize=True are part of a job's parameters and differ from call to call: such a job is not kept
-            job = _job_for(ctx, params, w, h, n) if seq is None else sfa.Job(ctx, params, w, h, n)
-            if seq is not None:
-                for b in range(n):
-                    job.upload_resident(b, seq, [(b0 + b) * F + f for f in range(F)])
-            else:
-                job_upload_device(job, fv.sub(b0, n), channels_last=channels_last)
-            job_set_flow_device(job, flv.sub(b0, n) if flv is not None else None, 0, n)
-            if raw_weights is not None:                          # after the uploads: they set the windows' weights to ones
-                job.set_raw_weights((raw_weights[0], raw_weights[1]), raw_weights[2], 0, n)
-            job.run()
-            job_download_device(job, ov.sub(b0, n), cv.sub(b0, n) if want_occ else None)
-            change[b0:b0 + n] = job_changes(job, 0, n)
-            b0 += n
-            if seq is not None:
-                signal_stream(ctx, stream)
-                job.close()
-    finally:
-        signal_stream(ctx, stream)
+        with on_stream(torch, ctx, frames, stream, outputs) as (stream, (out, occ)):
+            ov, cv = device_view(out, writable=True, name="out_flow"), (device_view(occ, writable=True, name="out_occ") if want_occ else None)
+            if normalize:
+                params = type(params).from_buffer_copy(params)
+                seq = sfa.Sequence(ctx, w, h, B * F)
+                for b in range(B):                               # window-major: sequence frame b F + f
+                    _, lay = frames_layout(fv.sub(b, 1), w, h, F, channels_last)
+                    lay.window = 0
+                    ctx._ck(_lib().sfa_sequence_upload_device(seq.h_, b * F, F, C.c_void_p(fv.ptr + b * fv.strides[0] * fv.itemsize), C.byref(lay)),
+                            "sfa_sequence_upload_device")
+                avg, std = seq.normalize()
+                for k in range(3):
+                    params.norm_avg[k], params.norm_std[k] = avg[k], std[k]
+            b0 = 0
+            for n in pair_sizes(B):
+                # the statistics of normalize=True are part of a job's parameters and differ from call to call: such a job is not kept
+                job = _job_for(ctx, params, w, h, n) if seq is None else sfa.Job(ctx, params, w, h, n)
+                if seq is not None:
+                    for b in range(n):
+                        job.upload_resident(b, seq, [(b0 + b) * F + f for f in range(F)])
+                else:
+                    job_upload_device(job, fv.sub(b0, n), channels_last=channels_last)
+                job_set_flow_device(job, flv.sub(b0, n) if flv is not None else None, 0, n)
+                if raw_weights is not None:                      # after the uploads: they set the windows' weights to ones
+                    job.set_raw_weights((raw_weights[0], raw_weights[1]), raw_weights[2], 0, n)
+                job.run()
+                job_download_device(job, ov.sub(b0, n), cv.sub(b0, n) if want_occ else None)
+                change[b0:b0 + n] = job_changes(job, 0, n)
+                b0 += n
+                if seq is not None:
+                    signal_stream(ctx, stream)
+                    job.close()
+    finally:                                                     # after the bracket's signal
         if seq is not None:
             seq.close()
     return out, occ, change
@@ -391,10 +407,8 @@ def pair_geometry(fv, channels_last=None):
         raise sfa.SlowflowError(f"frames: rank {len(fv.shape)}, shape {fv.shape}; 5 dimensions expected")
     if fv.shape[1] != 2:
         raise sfa.SlowflowError(f"frames: shape {fv.shape} holds {fv.shape[1]} frames per pair; [B,2,3,H,W] or [B,2,H,W,3] expected")
-    last = (fv.shape[2] != 3 and fv.shape[4] == 3) if channels_last is None else channels_last
-    h, w = (fv.shape[2], fv.shape[3]) if last else (fv.shape[3], fv.shape[4])
-    B, _ = frames_layout(fv, w, h, 2, channels_last)
-    return B, h, w
+    h, w = frames_size(fv, channels_last)
+    return frames_layout(fv, w, h, 2, channels_last)[0], h, w
 
 
 def _pair_job_for(ctx, params, w, h, n):
@@ -411,21 +425,11 @@ def refine_pairs(ctx, frames, flow0=None, params=None, *, stream=None, channels_
     import torch
     fv = device_view(frames, name="frames")
     B, h, w = pair_geometry(fv, channels_last)
-    flv = None
-    if flow0 is not None:
-        flv = device_view(flow0, name="flow0", ndim=4)
-        if flv.dtype != DTYPES["f4"] or flv.shape != (B, 2, h, w):
-            raise sfa.SlowflowError(f"flow0: fp32 [{B},2,{h},{w}] expected, got shape {flv.shape}")
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
-    with torch.cuda.stream(stream):                              # the output belongs to the caller's stream
-        out = torch.empty((B, 2, h, w), dtype=torch.float32, device=frames.device)
-    ov = device_view(out, writable=True, name="out_flow")
+    flv = device_view(flow0, name="flow0", kinds=("f4",), shape=(B, 2, h, w)) if flow0 is not None else None
     sizes = pair_sizes(B)
-    jobs = [_pair_job_for(ctx, params, w, h, n) for n in sorted(set(sizes), reverse=True)]      # creating a job waits for the context's stream: before the bracket
-    by_size = {j.n: j for j in jobs}
-    wait_stream(ctx, stream)
-    try:
+    by_size = {n: _pair_job_for(ctx, params, w, h, n) for n in sorted(set(sizes), reverse=True)}       # creating a job waits for the context's stream: before the bracket
+    with on_stream(torch, ctx, frames, stream, lambda dev: torch.empty((B, 2, h, w), dtype=torch.float32, device=dev)) as (_, out):
+        ov = device_view(out, writable=True, name="out_flow")
         b0 = 0
         for n in sizes:
             job = by_size[n]
@@ -434,8 +438,6 @@ def refine_pairs(ctx, frames, flow0=None, params=None, *, stream=None, channels_
             job.run()
             pair_job_download_device(job, ov.sub(b0, n))
             b0 += n
-    finally:
-        signal_stream(ctx, stream)
     return out
 
 
@@ -443,20 +445,10 @@ def refine_pairs(ctx, frames, flow0=None, params=None, *, stream=None, channels_
 _LL5 = C.c_longlong * 5
 
 
-def _fp32_view(obj, name, shape):
-    """an fp32 device array of `shape` (None: any size) as a DeviceView; other element types, host tensors and other shapes are refused by name"""
-    if getattr(obj, "is_cuda", True) is False:                  # a torch tensor on the CPU raises from its __cuda_array_interface__
-        raise sfa.SlowflowError(f"{name}: a tensor on {getattr(obj, 'device', 'the host')}, not in GPU memory (the device entry points take device memory)")
-    v = device_view(obj, name=name, ndim=len(shape), kinds=("f4",))
-    if any(want is not None and got != want for got, want in zip(v.shape, shape)):
-        raise sfa.SlowflowError(f"{name}: shape {v.shape}, expected {list(shape)} (None: any)")
-    return v
-
-
 def track_job_upload_flows_device(job, r, fwd, bwd, s0=0):
     src, rJ = job.params.source[r], job.params.r_Jets[r]
-    fv = _fp32_view(fwd, "fwd", (None, rJ, 2, src.sh, src.sw))
-    bv = _fp32_view(bwd, "bwd", (fv.shape[0], rJ, 2, src.sh, src.sw))
+    fv = device_view(fwd, name="fwd", kinds=("f4",), shape=("ns", rJ, 2, src.sh, src.sw))
+    bv = device_view(bwd, name="bwd", kinds=("f4",), shape=(fv.shape[0], rJ, 2, src.sh, src.sw))
     if bv.strides != fv.strides:
         raise sfa.SlowflowError(f"bwd: element strides {bv.strides} differ from fwd's {fv.strides}: the two directions share one layout")
     job.ctx._ck(_lib().sfa_track_job_upload_flows_device(job.h_, int(s0), fv.shape[0], int(r), C.c_void_p(fv.ptr), C.c_void_p(bv.ptr), _LL5(*fv.strides)),
@@ -464,40 +456,16 @@ def track_job_upload_flows_device(job, r, fwd, bwd, s0=0):
 
 
 def track_job_upload_frames_device(job, frames, s0=0):
-    v = _fp32_view(frames, "frames", (None, job.Jets + 1, 3, job.h, job.w))
+    v = device_view(frames, name="frames", kinds=("f4",), shape=("ns", job.Jets + 1, 3, job.h, job.w))
     job.ctx._ck(_lib().sfa_track_job_upload_frames_device(job.h_, int(s0), v.shape[0], C.c_void_p(v.ptr), _LL5(*v.strides)), "sfa_track_job_upload_frames_device")
-
-
-def _typed_view(obj, name, kind, shape, contiguous=True):
-    """(pointer, element strides) of a writable device array of one element type and shape, through device_view"""
-    v = device_view(obj, writable=True, name=name, ndim=len(shape), kinds=(kind,))
-    if v.shape != tuple(shape):
-        raise sfa.SlowflowError(f"{name}: shape {v.shape}, expected {tuple(shape)}")
-    dense = tuple(int(np.prod(shape[i + 1:])) for i in range(len(shape)))
-    if contiguous and v.strides != dense:
-        raise sfa.SlowflowError(f"{name}: a contiguous array expected, element strides {v.strides}")
-    return v.ptr, v.strides
 
 
 def track_job_download_device(job, flow, slot=None, occ=None, stats=None, s0=0):
     ns = int(flow.shape[0])
-    fp, fst = _typed_view(flow, "flow", "f8", (ns, 2, job.gh, job.gw), contiguous=False)
-    ptrs = [_typed_view(a, name, t, shp)[0] if a is not None else None
-            for a, name, t, shp in ((slot, "slot", "i4", (ns, job.gh, job.gw)), (occ, "occ", "u1", (ns, job.gh, job.gw)), (stats, "stats", "f8", (ns, 3)))]
-    job.ctx._ck(_lib().sfa_track_job_download_device(job.h_, int(s0), ns, C.c_void_p(fp), _LL4(*fst), *[C.c_void_p(p) if p is not None else None for p in ptrs]),
-                "sfa_track_job_download_device")
-
-
-def _track_job_for(ctx, params):
-    cache = ctx.__dict__.setdefault("_track_jobs", OrderedDict())
-    key = bytes(params)
-    job = cache.get(key)
-    if job is not None and job.h_:
-        return job
-    while len(cache) >= 2:
-        cache.popitem(last=False)[1].close()
-    job = cache[key] = sfa.TrackJob(ctx, params)
-    return job
+    fv = device_view(flow, writable=True, name="flow", kinds=("f8",), shape=(ns, 2, job.gh, job.gw))
+    ptrs = [C.c_void_p(device_view(a, writable=True, name=name, kinds=(kind,), shape=shape, contiguous=True).ptr) if a is not None else None
+            for a, name, kind, shape in ((slot, "slot", "i4", (ns, job.gh, job.gw)), (occ, "occ", "u1", (ns, job.gh, job.gw)), (stats, "stats", "f8", (ns, 3)))]
+    job.ctx._ck(_lib().sfa_track_job_download_device(job.h_, int(s0), ns, C.c_void_p(fv.ptr), _LL4(*fv.strides), *ptrs), "sfa_track_job_download_device")
 
 
 def track(ctx, params, flows, frames, *, stream=None):
@@ -510,32 +478,25 @@ def track(ctx, params, flows, frames, *, stream=None):
     import torch
     if len(flows) != params.K:
         raise sfa.SlowflowError(f"flows: {len(flows)} (fwd, bwd) pairs for {params.K} rates")
-    fv = _fp32_view(frames, "frames", (None, params.Jets + 1, 3, params.h, params.w))      # every view is checked before a job is created or anything uploaded
+    fv = device_view(frames, name="frames", kinds=("f4",), shape=("ns", params.Jets + 1, 3, params.h, params.w))   # every view is checked before a job is created or anything uploaded
     ns = fv.shape[0]
     if not 1 <= ns <= params.n:
         raise sfa.SlowflowError(f"frames: {ns} start_jets, the parameters' capacity n is {params.n}")
     for r, (fwd, bwd) in enumerate(flows):
         src = params.source[r]
         for a, nm in ((fwd, "flows[%d] fwd" % r), (bwd, "flows[%d] bwd" % r)):
-            _fp32_view(a, nm, (ns, params.r_Jets[r], 2, src.sh, src.sw))
-    job = _track_job_for(ctx, params)                           # creating a job waits for the context's stream: before the bracket
-    if stream is None:
-        stream = torch.cuda.current_stream(frames.device)
-    with torch.cuda.stream(stream):                              # the outputs belong to the caller's stream
-        flow = torch.empty((ns, 2, job.gh, job.gw), dtype=torch.float64, device=frames.device)
-        slot = torch.empty((ns, job.gh, job.gw), dtype=torch.int32, device=frames.device)
-        occ = torch.empty((ns, job.gh, job.gw), dtype=torch.uint8, device=frames.device)
-        stats = torch.empty((ns, 3), dtype=torch.float64, device=frames.device)
-    wait_stream(ctx, stream)
-    try:
+            device_view(a, name=nm, kinds=("f4",), shape=(ns, params.r_Jets[r], 2, src.sh, src.sw))
+    job = _cached_job(ctx, "_track_jobs", bytes(params), lambda: sfa.TrackJob(ctx, params))     # creating a job waits for the context's stream: before the bracket
+    def outputs(dev):
+        return (torch.empty((ns, 2, job.gh, job.gw), dtype=torch.float64, device=dev), torch.empty((ns, job.gh, job.gw), dtype=torch.int32, device=dev),
+                torch.empty((ns, job.gh, job.gw), dtype=torch.uint8, device=dev), torch.empty((ns, 3), dtype=torch.float64, device=dev))
+    with on_stream(torch, ctx, frames, stream, outputs) as (_, out):
         for r, (fwd, bwd) in enumerate(flows):
             track_job_upload_flows_device(job, r, fwd, bwd)
         track_job_upload_frames_device(job, frames)
         job.run(ns)
-        track_job_download_device(job, flow, slot, occ, stats)
-    finally:
-        signal_stream(ctx, stream)
-    return flow, slot, occ, stats
+        track_job_download_device(job, *out)
+    return out
 
 
 # ---- adaptiveFR's frame-rate decision (sfa_flow_magnitude_quantiles_device): quantile and maximum of the flow magnitude, per group ------------------
@@ -548,13 +509,10 @@ def flow_quantiles(ctx, flow, q=0.99, scale=1.0, counts=None, *, stream=None, ou
     after what `stream` (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues and never waits
     for the GPU (a call that needs more scratch than the context holds replaces it first, which does)."""
     import torch
-    if getattr(flow, "is_cuda", True) is False:                 # a torch tensor on the CPU raises from its __cuda_array_interface__
-        raise sfa.SlowflowError(f"flow: a tensor on {getattr(flow, 'device', 'the host')}, not in GPU memory (the device entry points take device memory)")
     v = device_view(flow, name="flow", kinds=("f4",))
     if len(v.shape) == 4:
         v = DeviceView(v.ptr, v.dtype, v.itemsize, (1,) + v.shape, (0,) + v.strides, v.owner)
-    if len(v.shape) != 5 or v.shape[2] != 2:
-        raise sfa.SlowflowError(f"flow: shape {tuple(v.shape)}; fp32 [G,n,2,h,w] or [n,2,h,w] expected")
+    v = device_view(v, name="flow", shape=("G", "n", 2, "h", "w"))
     G, n, _, h, w = v.shape
     ca = None
     if counts is not None:
@@ -562,17 +520,14 @@ def flow_quantiles(ctx, flow, q=0.99, scale=1.0, counts=None, *, stream=None, ou
         if len(counts) != G:
             raise sfa.SlowflowError(f"counts: {len(counts)} entries for {G} groups")
         ca = (C.c_int * G)(*counts)
-    if stream is None:
-        stream = torch.cuda.current_stream(flow.device)
-    if out is None:
-        with torch.cuda.stream(stream):                          # the output belongs to the caller's stream
-            out = torch.empty((G, 2), dtype=torch.float64, device=flow.device)
-    op, _ = _typed_view(out, "out", "f8", (G, 2))
     s = v.strides
-    wait_stream(ctx, stream)
-    try:
+    def out_view(o):
+        return device_view(o, writable=True, name="out", kinds=("f8",), shape=(G, 2), contiguous=True)
+    given = out
+    if given is not None:
+        out_view(given)                                          # a refusal touches neither stream
+    with on_stream(torch, ctx, flow, stream, lambda dev: torch.empty((G, 2), dtype=torch.float64, device=dev) if given is None else given) as (_, out):
+        op = out_view(out).ptr
         ctx._ck(_lib().sfa_flow_magnitude_quantiles_device(ctx.h, G, n, ca, C.c_void_p(v.ptr), C.c_void_p(v.ptr + s[2] * v.itemsize), _LL4(s[0], s[1], s[3], s[4]),
                                                            w, h, float(scale), float(q), C.c_void_p(op)), "sfa_flow_magnitude_quantiles_device")
-    finally:
-        signal_stream(ctx, stream)
     return out

@@ -81,6 +81,26 @@ def test_the_seam_refuses_before_it_calls_the_library():
     refused(lambda: device.pair_job_download_device(job, Fake((4, 3, 5, 7))), "out_flow", "[B,2,5,7]")
 
 
+def test_a_device_view_made_earlier_is_checked_like_the_object_it_came_from():
+    """device_view hands a DeviceView through (refine passes .sub() views on): its element type and shape are still checked"""
+    import numpy as np
+    from slowflow_amd import device
+    job = FakeJob()
+    u8 = device.device_view(Fake((4, 2, 5, 7), "|u1"))
+    for call in (lambda: device.pair_job_set_flow_device(job, u8), lambda: device.pair_job_set_flow_device(job, u8.sub(1, 2)),
+                 lambda: device.job_set_flow_device(job, u8), lambda: device.device_view(u8.sub(0, 1), name="flow", kinds=("f4",))):
+        with pytest.raises(sfa.SlowflowError) as e:
+            call()
+        assert all(w in str(e.value) for w in ("flow", "u1", "fp32")), str(e.value)
+    f8 = device.device_view(Fake((4, 6), "<f8"), kinds=("f8",))
+    assert f8.dtype is None and device.device_view(f8.sub(1, 2), kinds=("f8",), shape=(2, 6)).kind == "f8"
+    with pytest.raises(sfa.SlowflowError, match="fp32"):
+        device.device_view(f8, kinds=("f4",))
+    with pytest.raises(sfa.SlowflowError, match=r"a: \[4,7\] expected"):                   # a numpy integer is a size, not "any"
+        device.device_view(Fake((4, 6)), name="a", shape=(4, np.int64(7)))
+    assert device.device_view(Fake((4, 6)), shape=(None, "w")).shape == (4, 6)
+
+
 def test_pair_sizes_split_like_refine():
     from slowflow_amd import device
     assert device.pair_sizes(1) == [1] and device.pair_sizes(128) == [128]
