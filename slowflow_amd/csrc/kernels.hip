@@ -5,6 +5,7 @@
 // Arithmetic is strict IEEE fp32 in the reference's association (no contraction, IEEE div/sqrt).
 // Each __global__ cites the reference operator it implements.
 #include "sfa_device.h"
+#include "sor_device.h"      // the solver's operand preparation and entry index (the fused data term writes the solver's operands)
 
 #pragma clang fp contract(off)
 
@@ -535,7 +536,7 @@ __global__ void __launch_bounds__(64 * WS_ROWS) k_warp_smooth(WarpJobs J, float 
                 // Round 6: the warped images leave as NON-TEMPORAL stores (24 of the kernel's 40 written bytes per pixel; the data-term kernel reads them back by DMA,
                 // from memory either way: 0.94 GB per 128-window launch).  Same box, whole path: 111.5 / 112.0 -> 110.6 / 110.6 ms per step together with the eight-row
                 // block below (-DSFA_WS_NT=0: plain stores).  NOT for the solver's operand tile in k_assemble_images: the solver reads that from the caches (+3-5 % of
-                // the whole path as non-temporal stores, -DSFA_ASM_NT=1)
+                // the whole path as non-temporal stores)
                 if (SFA_WS_NT) __builtin_nontemporal_store(out[ch], reinterpret_cast<float *>(reinterpret_cast<char *>(dst3 + ch * g.pl) + o4));
                 else st(dst3 + ch * g.pl, o4, out[ch]);
             }
@@ -809,17 +810,21 @@ void launch_data_2f_fused(sfa_ctx *c, const Geo &g, const float *I1, const float
 // ---------------------------------------------------------------------------------------------------
 // mask weighting by occlusion / direction (variational_mt.cpp:293-320)
 // ---------------------------------------------------------------------------------------------------
+// the weights of the forward and the backward masks of a pixel from its occlusion value
+__device__ __forceinline__ void mask_weights(float oc, float data_norm, float &fwd, float &bwd) {
+    float factor = (oc == 0.0f) ? 1.0f : 0.0f;
+    factor = (1 + factor) * data_norm;                                                   // :297
+    bwd = __fdiv_rn((oc >= 0.0f) ? 1.0f : 0.0f, factor);                                 // :302
+    fwd = __fdiv_rn((oc <= 0.0f) ? 1.0f : 0.0f, factor);                                 // :303
+}
 __global__ void k_mask_weight(float *__restrict__ masks, const float *__restrict__ occ, Geo g, float data_norm, int ref, int one_direction) {
     const int b = blockIdx.z;
     if (!elem_active(g, b)) return;
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= g.w || y >= g.h) return;
     const size_t o = (size_t)y * g.pitch + x;
-    const float oc = occ[b * g.es + o];
-    float factor = (oc == 0.0f) ? 1.0f : 0.0f;
-    factor = (1 + factor) * data_norm;                                                   // :297
-    const float backward = __fdiv_rn((oc >= 0.0f) ? 1.0f : 0.0f, factor);                // :302
-    const float forward = __fdiv_rn((oc <= 0.0f) ? 1.0f : 0.0f, factor);                 // :303
+    float forward, backward;
+    mask_weights(occ[b * g.es + o], data_norm, forward, backward);
     for (int s = one_direction ? ref : 0; s < 2 * ref; s++) {
         float *m = masks + b * g.es + s * g.pl + o;
         *m = (s < ref) ? 1.0f * backward * (*m) : 1.0f * forward * (*m);                 // :314,316
@@ -1147,6 +1152,13 @@ __device__ __forceinline__ void term_ref(Acc &A, const Px &p, float m, float u, 
     }
 }
 
+// the channel weights of pixel (x, y) of window b: the reference walks the LEVEL-0 weight planes with this level's linear index (variational_aux_mt.cpp:177,366-371)
+__device__ __forceinline__ void channel_weights(const AssembleArgs &a, int b, int x, int y, float (&wk)[3]) {
+    const unsigned lin = (unsigned)y * (unsigned)a.lstride + (unsigned)x;              // < 2^31: checked where the weights are attached
+    const unsigned r0 = lin / (unsigned)a.chw_stride0, c0 = lin % (unsigned)a.chw_stride0;
+    const float *cw = a.chw + b * a.chw_es + r0 * a.chw_pitch + c0;
+    wk[0] = cw[0]; wk[1] = cw[a.chw_pl]; wk[2] = cw[2 * a.chw_pl];
+}
 __global__ void __launch_bounds__(BX *BY) k_assemble(AssembleArgs a, const float *__restrict__ base, float *__restrict__ a11, float *__restrict__ a12,
                                                       float *__restrict__ a22, float *__restrict__ b1, float *__restrict__ b2, const float *__restrict__ du,
                                                       const float *__restrict__ dv, const float *__restrict__ uu, const float *__restrict__ vv,
@@ -1162,13 +1174,8 @@ __global__ void __launch_bounds__(BX *BY) k_assemble(AssembleArgs a, const float
     else { A.a11 = A.a12 = A.a22 = A.b1 = A.b2 = 0.0f; }                                  // image_erase, variational_mt.cpp:336-340
     const float u = du[eb + o], v = dv[eb + o];
     Px p;
-    if (a.chw) {
-        // the reference walks the LEVEL-0 weight planes with this level's linear index (variational_aux_mt.cpp:177,366-371)
-        const unsigned lin = (unsigned)y * (unsigned)a.lstride + (unsigned)x;          // < 2^31: checked where the weights are attached
-        const unsigned r0 = lin / (unsigned)a.chw_stride0, c0 = lin % (unsigned)a.chw_stride0;
-        const float *cw = a.chw + b * a.chw_es + r0 * a.chw_pitch + c0;
-        p.wk[0] = cw[0]; p.wk[1] = cw[a.chw_pl]; p.wk[2] = cw[2 * a.chw_pl];
-    } else { p.wk[0] = p.wk[1] = p.wk[2] = 1.0f; }
+    if (a.chw) channel_weights(a, b, x, y, p.wk);
+    else { p.wk[0] = p.wk[1] = p.wk[2] = 1.0f; }
     for (int t = 0; t < a.n; t++) {
         const Term &T = a.t[t];
         const float *S = base + eb + T.stack_off + o;
@@ -1201,20 +1208,8 @@ void launch_assemble(sfa_ctx *c, const Geo &g, const AssembleArgs &a, const floa
 // each thread runs the term for its pixel(s): three barriers per term.  Mask weights (variational_mt.cpp:293-320) are applied
 // on the fly from the occlusion plane.  Same operations in the same order as the unfused kernels: bit-identical.
 // ---------------------------------------------------------------------------------------------------
-constexpr int AT_W1 = DT_X + 4;                                      // halo-2 planes
-struct Tile1Acc {     // a staged plane of DT_W columns whose first entry is pixel (x0, y0)
-    const float *t; int x0, y0;
-    __device__ __forceinline__ float operator()(int x, int y) const { return t[(y - y0) * DT_W + (x - x0)]; }
-};
-struct Tile2Acc {
-    const float *t; int x0, y0;      // global coordinates of the halo-2 origin
-    __device__ __forceinline__ float operator()(int x, int y) const { return t[(y - y0) * AT_W1 + (x - x0)]; }
-};
 // interior taps at fixed LDS offsets (the generic accessors cost more in index arithmetic than the filter itself)
-template <int W>
 __device__ __forceinline__ float d5x_in(const float *t, int c) { return tap5(t[c - 2], t[c - 1], t[c], t[c + 1], t[c + 2]); }
-template <int W>
-__device__ __forceinline__ float d5y_in(const float *t, int c) { return tap5(t[c - 2 * W], t[c - W], t[c], t[c + W], t[c + 2 * W]); }
 
 // Debug instrumentation (off in the product; tools/asm_timing.py): wave cycles of k_assemble_images by phase.  AT_MARK(i) charges the time since the
 // previous mark to slot i: 0 per-pixel term arithmetic, 1 wait for the staged planes, 2 image DMA issue, 3 its vmcnt wait, 4 barrier behind it,
@@ -1245,13 +1240,8 @@ __device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
 // the same with a wave-uniform 64-bit base and a 32-bit byte offset per lane (no 64-bit address arithmetic in the vector unit)
-#if defined(SFA_ASM_DMA_NT) && SFA_ASM_DMA_NT      // what-if (round 6): the image quads as non-temporal loads (they stream through the L2 the solver's operands sit in)
-#define SFA_DMA_NT_ " nt"
-#else
-#define SFA_DMA_NT_ ""
-#endif
 __device__ __forceinline__ void dma16s(const float *sbase, unsigned voff, unsigned lds_byte) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" SFA_DMA_NT_ ::"v"(voff), "s"(sbase), "s"(lds_byte) : "memory", "m0");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_byte) : "memory", "m0");
 }
 __device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_byte) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_byte) : "memory", "m0");
@@ -1280,90 +1270,317 @@ __device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_byte) {
 #define SFA_TILE_FAST 1
 #endif
 #define SFA_PRIO(p) do { if (SFA_PRIO_STAGE) __builtin_amdgcn_s_setprio(p); } while (0)
-// Terms staged per round: 1 (48 KB of LDS: three blocks per CU = six waves per SIMD, for which the kernel stays within 80 registers -- the default since the
-// tap addresses stopped occupying 45 of them) or 2 (rounds 2-4: a pair shares one DMA wait and one barrier and an image both terms use is fetched once, but
-// 76 KB of LDS allow two blocks per CU only).  Measured, 64 windows, mean of the levels: 1 083 -> 990 us per launch
-#ifndef SFA_ASM_PAIR
-#define SFA_ASM_PAIR 0
-#endif
-#ifndef SFA_ASM_DMA_BARRIER
-#define SFA_ASM_DMA_BARRIER 1
-#endif
-#ifndef SFA_ASM_TY
-#define SFA_ASM_TY 8
-#endif
-#ifndef SFA_ASM_STAGGER
-#define SFA_ASM_STAGGER 0
-#endif
-#ifndef SFA_ASM_STAGGER_MODE
-#define SFA_ASM_STAGGER_MODE 0
-#endif
-constexpr int kAsmPair = SFA_ASM_PAIR, kAsmMinWaves = SFA_ASM_PAIR ? 4 : 6, kAsmTY = SFA_ASM_TY, kAsmNT = 64 * SFA_ASM_TY;      // tile rows, threads (one row per wave)
+// One term is staged per round: 48 KB of LDS, so three blocks per CU = six waves per SIMD, for which the kernel stays within 80 registers (since the tap addresses
+// stopped occupying 45 of them).  Rounds 2 - mid-4 staged two terms per round (a pair shares one DMA wait and one barrier and an image both terms use is fetched
+// once, but 76 KB of LDS allow two blocks per CU only).  Measured, 64 windows, mean of the levels: 1 083 us per launch with two, 990 with one
+constexpr int kAsmMinWaves = 6, kAsmTY = 8, kAsmNT = 64 * kAsmTY;      // blocks per CU x 2, tile rows, threads (one row per wave)
 struct XcdTiles { int nx, ny, chunk; };      // tile columns, tile rows, ceil(tiles of the launch / 8)
+
+// The tile's constants.  One LDS block of LDS floats: the staged planes during the terms, the operand tile of the solver afterwards
+template <int TY_, int NT_>
+struct AsmTile {
+    static constexpr int TY = TY_, NT = NT_;
+    static constexpr int TR = TY + 2 * DT_H, AT_R1 = TY + 4;          // rows of the halo-4 planes (M, Iz), of the halo-2 planes (Ix, Iy)
+    static constexpr int NR = NT / 64, NP = TY / NR;                  // rows in flight, pixels per thread
+    // Ix, Iy planes (halo 2 in y) share M's COLUMN geometry since round 4 (index j = column x0 + j, DT_W = 72 wide): stage 1 then works on M's own aligned quads and
+    // reads its column taps as aligned 16-byte rows (they were 2 x 8 bytes at half the LDS rate on planes shifted by two columns)
+    static constexpr int NM = TR * DT_W, N1 = AT_R1 * DT_W;
+    // [3 ch] M = (I1+I2)/2 at 0, [3 ch] Iz = I1-I2 at ZOFF (halo 4, aligned 16-byte rows), [3 ch] Ix at XOFF and [3 ch] Iy behind them (halo 2)
+    static constexpr int ZOFF = 3 * NM, XOFF = 2 * ZOFF, LDS = XOFF + 6 * N1;
+    // the smoothness-side operands of the epilogue (uu, vv, sh, sv with a halo of one) take the place of the M planes once the last term's Ix, Iy exist
+    static constexpr int GR = TY + 2, NGQ = 4 * GR * (DT_W / 4), NGF = 4 * GR * DT_W;
+    static constexpr int QM = DT_W / 4, Q1 = DT_W / 4;                // float4 quads per staged row: halo-4 planes, halo-2 planes
+    static constexpr int NSQ = 3 * TR * QM, NSI = (NSQ + 63) / 64;    // quads / wave-instructions per image set
+    static_assert(NGF <= ZOFF, "the epilogue's operand planes replace the M planes");
+    static_assert(NGF + TY * (67 * 8 + 69 * 2) <= LDS, "operand tile must fit the staging block");
+    static_assert(DT_W % 4 == 0 && NM % 4 == 0 && N1 % 4 == 0, "16-byte LDS rows");
+    static_assert(N1 == 4 * AT_R1 * Q1, "linear item numbering of stage 1");
+};
+// The block itself.  Every phase below names it through this function: handed down as a pointer parameter it is a generic pointer inside the phase, and the
+// compiler then paired half as many of the term loop's LDS reads (54 ds_read2_b32 against 111, with a wait more for nearly each one: 1.90 -> 2.00 ms per launch)
+template <class K>
+__device__ __forceinline__ float *asm_lds() {
+    __shared__ __attribute__((aligned(16))) float lds[K::LDS];
+    return lds;
+}
+// The operand tile.  Row strides chosen for the anti-diagonal read-out (entry 64*rl + dl of a 65-wide row puts the TY rows of a diagonal into one bank group:
+// PMC of round 2 showed 37 % of this kernel's LDS cycles in bank conflicts): with 67 float4 / 69 float2 per row the 16 lanes of a b128 pass
+// (32 of a b64 pass) land on distinct banks
+template <class K>
+struct OperandTile {
+    float4 (*A)[67], (*B)[67]; float2 (*X)[69];                       // [TY] rows each; live after the barrier behind the last term
+    __device__ __forceinline__ OperandTile() : A(reinterpret_cast<float4(*)[67]>(asm_lds<K>() + K::NGF)), B(A + K::TY), X(reinterpret_cast<float2(*)[69]>(B + K::TY)) {}
+};
+
+// Tile of this block; false: none (the rounded-up end of the XCD order).  The hardware hands consecutive workgroups of a launch to the 8 XCDs in turn (workgroup
+// i -> XCD i % 8, each with an L2 of its own), so with the plain (x, y, window) grid a tile's horizontal neighbours -- which share two of the four 128-byte lines
+// of every staged row -- and its vertical neighbours (8 of 16 staged rows) are fetched through OTHER L2s: 2.9 GB crossed the fabric per 64-window launch for
+// 1.4 GB of unique inputs.  XT: a 1-D grid whose workgroup i works on tile (i % 8) * ceil(N / 8) + i / 8 of the row-major (window, tile row, tile column) order:
+// every XCD walks a contiguous eighth of the tiles, its CUs hold neighbouring tiles at any time, and the shared lines are L2 hits.
+template <bool XT>
+__device__ __forceinline__ bool asm_block_tile(const Geo &g, const XcdTiles &xt, int &bx, int &by, int &b) {
+    int bx_, by_, b_;
+    if (XT) {
+        const unsigned nxy = (unsigned)xt.nx * (unsigned)xt.ny;
+        const unsigned j = (blockIdx.x & 7u) * (unsigned)xt.chunk + (blockIdx.x >> 3);
+        if (j >= nxy * (unsigned)g.nb) return false;
+        b_ = (int)(j / nxy);
+        const unsigned r = j - (unsigned)b_ * nxy;
+        by_ = (int)(r / (unsigned)xt.nx);
+        bx_ = (int)(r - (unsigned)by_ * (unsigned)xt.nx);
+    } else { bx_ = blockIdx.x; by_ = blockIdx.y; b_ = blockIdx.z; }
+    bx = __builtin_amdgcn_readfirstlane(bx_); by = __builtin_amdgcn_readfirstlane(by_); b = __builtin_amdgcn_readfirstlane(b_);
+    return true;
+}
+// reset the solver's progress words and ticket -- for EVERY window of the launch: the solver that follows runs all of them, also the
+// passengers whose operands this launch leaves alone (Geo::active), and draws its tickets from window 0's block whoever is active
+template <class K>
+__device__ __forceinline__ void asm_reset_progress(const SorOperandOut &op, int bx, int by, int b) {
+    if (!op.sa || bx != 0 || by != 0) return;
+    for (int i = threadIdx.x; i < op.ntasks; i += K::NT) op.flags[(size_t)b * op.ntasks + i] = 0;
+    if (b == 0 && threadIdx.x == 0) op.flags[(size_t)op.nb * op.ntasks] = 0;
+}
+// Stage 0, issue: the raw quads of the term's image pair (I1, I2: three planes each) go global -> LDS by DMA, I1 into the M planes and I2 into the Iz planes, one
+// float4 of a row per item (no register staging: at this kernel's VGPR budget a register pipeline spills, and the plain load -> convert -> store loop exposed one
+// HBM round trip per item).  A set's quad order == its LDS order, so a wave-instruction's 64 quads land on 64 consecutive 16-byte slots.  Quads that leave the
+// image are skipped: the conversion pass fetches their replicated columns itself, and rows outside are never read.
+// One wave-instruction per part and set; a part's quad -> (row, channel) arithmetic is the same for both sets, so it runs once per part (it was a third of this
+// phase's instructions when it ran per set), and the address is a wave-uniform base per set + one 32-bit lane offset
+template <class K>
+__device__ __forceinline__ void asm_issue_image_dma(const float *I1, const float *I2, const Geo &g, int x0, int y0, int tx, int ty) {
+    float *const lds = asm_lds<K>();
+    for (int part = ty; part < K::NSI; part += K::NR) {
+        const int k = part * 64 + tx;
+        const int q = k % K::QM, ly = (k / K::QM) % K::TR, ch = k / (K::QM * K::TR);
+        const int gy = y0 + ly, gx = x0 + 4 * q;
+        if (!(SFA_X_AI & 1) && k < K::NSQ && gy >= 0 && gy < g.h && gx >= 0 && gx + 3 < g.w) {
+            const unsigned po = 4u * ((unsigned)ch * (unsigned)g.pl + (unsigned)gy * (unsigned)g.pitch + (unsigned)gx);   // offset inside one image set: < 12 * plane bytes < 2^32 (launcher)
+            const unsigned ld = lds_addr(lds + 256 * part);
+            dma16s(I1, po, ld);
+            dma16s(I2, po, ld + 4u * K::ZOFF);
+        }
+    }
+}
+// Stage 0, conversion in place: (I1, I2) -> (M, Iz), one quad per item.  INTERIOR (the whole staged tile lies inside the image): a staged quad's LDS slot is
+// 16 bytes * its item number in both plane sets -- no index arithmetic at all, and Iz also on the four rows nobody reads: cheaper than knowing the row
+template <class K, bool INTERIOR>
+__device__ __forceinline__ void asm_convert(const float *I1, const float *I2, const Geo &g, int x0, int y0) {
+    float *const lds = asm_lds<K>();
+    for (int item = threadIdx.x; item < ((SFA_X_AI & 2) ? 0 : K::NSQ); item += K::NT) {
+        float4 *const m = reinterpret_cast<float4 *>(lds + 4 * item), *const z = reinterpret_cast<float4 *>(lds + K::ZOFF + 4 * item);
+        int gx = 0;
+        size_t row = 0;
+        bool staged = true, iz = true;
+        if (!INTERIOR) {
+            const int q = item % K::QM, ly = (item / K::QM) % K::TR, ch = item / (K::QM * K::TR);
+            const int gy = y0 + ly;
+            if (gy < 0 || gy >= g.h) continue;
+            gx = x0 + 4 * q;
+            row = ch * g.pl + (size_t)gy * g.pitch;
+            staged = gx >= 0 && gx + 3 < g.w;                          // (what the DMA brought)
+            iz = ly >= 2 && ly < K::TR - 2;                            // Iz is read two rows around the tile only (M four: Ix, Iy exist on the halo-2 rows)
+        }
+        float4 va, vb;
+        if (staged) { va = *m; vb = *z; }
+        else {                                                         // columns outside the image: replicated (clamped source column).  A branch with loads of its
+                                                                       // own: as one fetch through a selected LDS / global address they were flat loads
+            auto clamped = [&](const float *r) { return make_float4(r[clampi(gx, 0, g.w - 1)], r[clampi(gx + 1, 0, g.w - 1)], r[clampi(gx + 2, 0, g.w - 1)], r[clampi(gx + 3, 0, g.w - 1)]); };
+            va = clamped(I1 + row); vb = clamped(I2 + row);
+        }
+        *m = make_float4(0.5f * (vb.x + va.x), 0.5f * (vb.y + va.y), 0.5f * (vb.z + va.z), 0.5f * (vb.w + va.w));        // variational_mt.cpp:120
+        if (iz) *z = make_float4(va.x - vb.x, va.y - vb.y, va.z - vb.z, va.w - vb.w);                                    // :122
+    }
+}
+// Ix (if x_in) and Iy (if y_in) of one aligned quad of M's columns, Mq = its first entry, from taps at fixed offsets.  The row taps of the quad's four columns
+// are the 8 values around it (the two outermost quads of a row reach into the neighbouring rows' ends: their outer two columns are never read by anybody), the
+// column taps four aligned quads: tap5's own order of operations, one aligned row of the quad's columns at a time.  By value, like asm_pixel_derivatives
+struct QuadXY { float X[4], Y[4]; };
+__device__ __forceinline__ QuadXY quad_taps(const float *Mq, bool x_in, bool y_in) {
+    QuadXY d = {};
+    const float2 lo = *reinterpret_cast<const float2 *>(Mq - 2), hi = *reinterpret_cast<const float2 *>(Mq + 4);
+    const float4 mid = *reinterpret_cast<const float4 *>(Mq);
+    const float m2[8] = {lo.x, lo.y, mid.x, mid.y, mid.z, mid.w, hi.x, hi.y};               // the quad's row, two columns more on either side
+    if (x_in) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) d.X[e] = tap5(m2[e], m2[e + 1], m2[e + 2], m2[e + 3], m2[e + 4]);                    // :127
+    }
+    if (y_in) {
+        const float4 r0 = *reinterpret_cast<const float4 *>(Mq - 2 * DT_W), r1 = *reinterpret_cast<const float4 *>(Mq - DT_W);
+        const float4 r3 = *reinterpret_cast<const float4 *>(Mq + DT_W), r4 = *reinterpret_cast<const float4 *>(Mq + 2 * DT_W);
+        d.Y[0] = tap5(r0.x, r1.x, m2[2], r3.x, r4.x); d.Y[1] = tap5(r0.y, r1.y, m2[3], r3.y, r4.y);                     // :128
+        d.Y[2] = tap5(r0.z, r1.z, m2[4], r3.z, r4.z); d.Y[3] = tap5(r0.w, r1.w, m2[5], r3.w, r4.w);
+    }
+    return d;
+}
+// Stage 1: Ix, Iy on the halo-2 rows, one aligned quad of M's columns per item.  INTERIOR: items in plane-major order (channel, row, quad) -- with 72 = 4 * 18
+// columns the quad's M index is 4 * item + 2 rows + (NM - N1) * channel and its Ix / Iy index 4 * item
+template <class K, bool INTERIOR>
+__device__ __forceinline__ void asm_stage1(const Geo &g, int x0, int y0) {
+    float *const lds = asm_lds<K>();
+    float *const sX = lds + K::XOFF, *const sY = sX + 3 * K::N1;
+    for (int item = threadIdx.x; item < ((SFA_X_AI & 4) ? 0 : K::AT_R1 * 3 * K::Q1); item += K::NT) {
+        QuadXY d;
+        int out = 4 * item;                                            // the quad's index in the Ix / Iy planes
+        if (INTERIOR) {
+            const int ch = (item >= K::AT_R1 * K::Q1 ? 1 : 0) + (item >= 2 * K::AT_R1 * K::Q1 ? 1 : 0);
+            d = quad_taps(lds + 4 * item + 2 * DT_W + (K::NM - K::N1) * ch, true, true);
+        } else {
+            const int q = item % K::Q1, ch = (item / K::Q1) % 3, ly = item / (3 * K::Q1);
+            const int gy = y0 + 2 + ly, gx = x0 + 4 * q;
+            if (gy < 0 || gy >= g.h) continue;
+            const float *M = lds + ch * K::NM;
+            const int c = (ly + 2) * DT_W + 4 * q;                     // M index of column gx
+            const bool x_in = gx >= 0 && gx + 3 < g.w, y_in = gy >= 2 && gy + 2 < g.h;
+            d = quad_taps(M + c, x_in, y_in);
+            if (!x_in) {                                               // X(clamp(x), y) for the columns outside the image
+#pragma unroll
+                for (int e = 0; e < 4; e++) d.X[e] = d5x_in(M, c + e + (clampi(gx + e, 0, g.w - 1) - (gx + e)));
+            }
+            if (!y_in) {                                               // folded border rows
+                const TileAcc m4{M, x0, y0};
+#pragma unroll
+                for (int e = 0; e < 4; e++) d.Y[e] = d5y(m4, clampi(gx + e, 0, g.w - 1), gy, g.h);
+            }
+            out = ch * K::N1 + ly * DT_W + 4 * q;
+        }
+        *reinterpret_cast<float4 *>(sX + out) = make_float4(d.X[0], d.X[1], d.X[2], d.X[3]);
+        *reinterpret_cast<float4 *>(sY + out) = make_float4(d.Y[0], d.Y[1], d.Y[2], d.Y[3]);
+    }
+}
+// The derivatives of the pixel in column tx of tile row yl (image row y), from the staged Ix, Iy, Iz planes (wk is left to the caller).  Returned by value: filled
+// through a reference the three forms' last stores were merged into one store through a selected address, and the pixel's values stayed in scratch memory
+template <class K>
+__device__ __forceinline__ Px asm_pixel_derivatives(const Geo &g, int x0, int y0, int tx, int yl, int y) {
+    Px p;
+    const float *const lds = asm_lds<K>();
+    const float(*sZ)[K::NM] = reinterpret_cast<const float(*)[K::NM]>(lds + K::ZOFF);
+    const float(*sX)[K::N1] = reinterpret_cast<const float(*)[K::N1]>(lds + K::XOFF), (*sY)[K::N1] = sX + 3;
+    // The lane's column is made opaque once per term: every tap address below is then computed inside the term loop from ONE register (the planes
+    // above 64 KB -- Iy, part of Ix -- are out of reach of a 16-bit LDS offset from the block's start, and left to itself the compiler kept ~45 registers
+    // of per-plane, per-clamped-row addresses of both the interior and the border path live across the whole term loop: tools/isa_live.py), and the
+    // interior path's reads are offsets from a base in the middle of the block (cb: the Iz planes' start + the pixel), all below 48 KB
+    int txl = tx;
+    asm volatile("" : "+v"(txl));
+    const int c = (yl + 2) * DT_W + (txl + 4);                         // halo-2 rows (Ix, Iy), M's columns
+    const int cz = (yl + 4) * DT_W + (txl + 4);                        // halo-4 plane (Iz): c + 2 rows
+    int cb = K::ZOFF + c;
+    asm volatile("" : "+v"(cb));
+    const float *const pX = lds + cb + (K::XOFF - K::ZOFF), *const pY = pX + 3 * K::N1, *const pZ = lds + cb + 2 * DT_W;   // sX[0] + c, sY[0] + c, sZ[0] + cz
+    if (SFA_X_AI & 8) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            p.ixy[ch] = sX[ch][c + 1]; p.iyy[ch] = sY[ch][c + 1]; p.iyz[ch] = sZ[ch][cz + 1];
+            p.ix[ch] = sX[ch][c]; p.iy[ch] = sY[ch][c]; p.iz[ch] = sZ[ch][cz]; p.ixx[ch] = sX[ch][c - 1]; p.ixz[ch] = sZ[ch][cz - 1];
+        }
+    } else if (y >= 2 && y + 2 < g.h) {
+        // All 69 taps of the pixel (per channel: a row and a column of Ix and of Iz, a column of Iy) are READ first and the filters run behind a scheduling
+        // fence.  Left to itself the compiler read two taps, waited, used them, read the next two (82 LDS instructions per term, nearly each with a wait
+        // of its own, in a kernel with then 4 waves per SIMD): the per-pixel phase was 36 % of a wave's life, and most of that LDS latency (round-4 phase stamps).
+        // Two channels' taps in flight at most (all three at once: 69 registers of taps, spills at this kernel's 128).
+        float xr[3][5], xc[3][4], yc[3][5], zr[3][5], zc[3][4];
+        auto read_taps = [&](int ch) {
+            const float *X = pX + ch * K::N1, *Y = pY + ch * K::N1, *Z = pZ + ch * K::NM;
+#pragma unroll
+            for (int j = 0; j < 5; j++) xr[ch][j] = X[j - 2];
+            xc[ch][0] = X[-2 * DT_W]; xc[ch][1] = X[-DT_W]; xc[ch][2] = X[DT_W]; xc[ch][3] = X[2 * DT_W];
+#pragma unroll
+            for (int j = 0; j < 5; j++) yc[ch][j] = Y[(j - 2) * DT_W];
+#pragma unroll
+            for (int j = 0; j < 5; j++) zr[ch][j] = Z[j - 2];
+            zc[ch][0] = Z[-2 * DT_W]; zc[ch][1] = Z[-DT_W]; zc[ch][2] = Z[DT_W]; zc[ch][3] = Z[2 * DT_W];
+        };
+        auto filters = [&](int ch) {
+            p.ix[ch] = xr[ch][2]; p.iy[ch] = yc[ch][2]; p.iz[ch] = zr[ch][2];
+            p.ixx[ch] = tap5(xr[ch][0], xr[ch][1], xr[ch][2], xr[ch][3], xr[ch][4]);     // :129
+            p.ixy[ch] = tap5(xc[ch][0], xc[ch][1], xr[ch][2], xc[ch][2], xc[ch][3]);     // :130
+            p.iyy[ch] = tap5(yc[ch][0], yc[ch][1], yc[ch][2], yc[ch][3], yc[ch][4]);     // :131
+            p.ixz[ch] = tap5(zr[ch][0], zr[ch][1], zr[ch][2], zr[ch][3], zr[ch][4]);     // :132
+            p.iyz[ch] = tap5(zc[ch][0], zc[ch][1], zr[ch][2], zc[ch][2], zc[ch][3]);     // :133
+        };
+        read_taps(0); read_taps(1);
+        __builtin_amdgcn_sched_barrier(0);
+        filters(0);
+        __builtin_amdgcn_sched_barrier(0);
+        read_taps(2);
+        __builtin_amdgcn_sched_barrier(0);
+        filters(1); filters(2);
+    } else {                                                           // folded border rows; the columns are replicated in the planes
+        const int xl = x0 + DT_H + txl, xc_ = xl < g.w ? xl : g.w - 1;
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const TileAcc X{sX[ch], x0, y0 + 2}, Y{sY[ch], x0, y0 + 2}, Z{sZ[ch], x0, y0};
+            p.ixy[ch] = d5y(X, xc_, y, g.h);
+            p.iyy[ch] = d5y(Y, xc_, y, g.h);
+            p.iyz[ch] = d5y(Z, xc_, y, g.h);
+            p.ix[ch] = sX[ch][c]; p.iy[ch] = sY[ch][c]; p.iz[ch] = sZ[ch][cz];
+            p.ixx[ch] = d5x_in(sX[ch], c);                                  // :129
+            p.ixz[ch] = d5x_in(sZ[ch], cz);                                 // :132
+        }
+    }
+    return p;
+}
+// The epilogue of pixel (x, y), column tx of tile row yl: the smoothness term's part of the right-hand side and, where the solver's operands are wanted, the
+// pixel's entry of the operand tile -- k_sor_prepare's per-pixel part (solver.c:101-106,159,214): neighbour weights, inverted 2x2 block
+template <class K>
+__device__ __forceinline__ void asm_epilogue_pixel(const AssembleArgs &a, const Geo &g, Acc &A, float u, float v, int x0, int y0, int tx, int yl, int x, int y) {
+    const float *const lds = asm_lds<K>();
+    const int gy0 = y0 + DT_H - 1;                                     // first row of the staged uu, vv, sh, sv planes
+    const TileAcc U{lds, x0, gy0}, V{lds + K::GR * DT_W, x0, gy0}, Hh{lds + 2 * K::GR * DT_W, x0, gy0}, Wv{lds + 3 * K::GR * DT_W, x0, gy0};
+    if (a.do_laplacian) {                                                                // variational_mt.cpp:364-365
+        A.b1 = laplacian_gather(A.b1, U, Hh, Wv, x, y, g.w, g.h);
+        A.b2 = laplacian_gather(A.b2, V, Hh, Wv, x, y, g.w, g.h);
+    }
+    if (!a.op.sa) return;
+    const float hp = Hh(x, y);
+    const float hl = x > 0 ? Hh(x - 1, y) : 0.0f;                                        // f1[0] = 0, solver.c:82
+    const float vp = Wv(x, y);
+    const float vt = y > 0 ? Wv(x, y - 1) : 0.0f;
+    const PointBlock q = sor_point_block(hl, hp, vt, vp, y, g.h, A.a11, A.a12, A.a22);
+    const OperandTile<K> T;
+    T.A[yl][tx] = make_float4(q.i11, q.i12, q.i22, vt);
+    T.B[yl][tx] = make_float4(A.b1, A.b2, hp, y < g.h - 1 ? vp : 0.0f);
+    T.X[yl][tx] = make_float2(u, v);
+}
+// the tile's anti-diagonals leave: TY consecutive entries of the diagonal-major operand planes each
+template <class K>
+__device__ __forceinline__ void asm_store_operand_tile(const SorOperandOut &op, const Geo &g, int b, int c0, int r0) {
+    const OperandTile<K> T;
+    for (int item = threadIdx.x; item < (DT_X + K::TY - 1) * K::TY; item += K::NT) {
+        const int dl = item / K::TY, rl = item % K::TY, cl = dl - rl;
+        if (cl < 0 || cl >= DT_X) continue;
+        const int r = r0 + rl, c = c0 + cl;
+        if (r >= g.h || c >= g.w) continue;
+        const size_t e = diag_entry(b, op.ent, op.RP, op.G, c, r);
+        if (SFA_X_AI & 64) continue;
+        const float2 xv = T.X[rl][cl];
+        op.sa[e] = T.A[rl][cl];
+        op.sb[e] = T.B[rl][cl];
+        op.x[e] = f2u(xv.x, xv.y);
+    }
+}
+
+// The kernel, per term: image DMA, wait, barrier, conversion, barrier, stage 1, barrier, term arithmetic per pixel; then the epilogue
 template <int TY, int NT, int MINB, bool ZUV, int FAST, bool XT>
 __global__ void __launch_bounds__(NT, MINB) k_assemble_images(AssembleArgs a, const float *__restrict__ base, float *__restrict__ a11, float *__restrict__ a12,
                                                               float *__restrict__ a22, float *__restrict__ b1, float *__restrict__ b2,
                                                               const float *__restrict__ du, const float *__restrict__ dv, const float *__restrict__ uu,
                                                               const float *__restrict__ vv, const float *__restrict__ sh, const float *__restrict__ sv,
                                                               const float *__restrict__ occ, Geo g, XcdTiles xt) {
-    constexpr int TR = TY + 2 * DT_H, AT_R1 = TY + 4, NR = NT / 64, NP = TY / NR;
-    // one LDS block: staged planes during the terms, the operand tile of the solver afterwards
-    // Ix, Iy planes (halo 2 in y) share M's COLUMN geometry since round 4 (index j = column x0 + j, 72 wide): stage 1 then works on M's own aligned quads and reads
-    // its column taps as aligned 16-byte rows (they were 2 x 8 bytes at half the LDS rate on planes shifted by two columns)
-    constexpr int AW1 = DT_W;
-    constexpr int NM = TR * DT_W, N1 = AT_R1 * AW1;
-    // kAsmPair: terms are staged two at a time (one exposed global-load latency and one barrier less per pair); default: one term per round (three blocks per CU)
-    constexpr int ZOFF = kAsmPair ? 6 * NM : 3 * NM, XOFF = 2 * ZOFF;           // start of the Iz planes, of the Ix planes
-    __shared__ __attribute__((aligned(16))) float lds[XOFF + 6 * N1];
-    float(*sM2)[NM] = reinterpret_cast<float(*)[NM]>(lds);                      // [2 terms][3 ch] M  = (I1+I2)/2, halo 4 (rows x DT_W)
-    float(*sZ2)[NM] = reinterpret_cast<float(*)[NM]>(lds + ZOFF);               // [2 terms][3 ch] Iz = I1-I2, same geometry (aligned 16-byte rows)
-    float(*sX)[N1] = reinterpret_cast<float(*)[N1]>(lds + XOFF);                // Ix, Iy of the term in work: halo 2 (rows x AW1)
-    float(*sY)[N1] = reinterpret_cast<float(*)[N1]>(lds + XOFF + 3 * N1);
-    // the smoothness-side operands of the epilogue (uu, vv, sh, sv with a halo of one) take the place of the M planes once the last term's Ix, Iy exist
-    constexpr int GR = TY + 2, NGQ = 4 * GR * (DT_W / 4), NGF = 4 * GR * DT_W;
-    static_assert(NGF <= ZOFF, "the epilogue's operand planes replace the M planes");
-    static_assert(NGF + TY * (67 * 8 + 69 * 2) <= XOFF + 6 * N1, "operand tile must fit the staging block");
-    static_assert(DT_W % 4 == 0 && AW1 % 4 == 0 && NM % 4 == 0 && N1 % 4 == 0, "16-byte LDS rows");
+    using K = AsmTile<TY, NT>;
+    constexpr int NR = K::NR, NP = K::NP;
+    float *const lds = asm_lds<K>();                                            // (for the epilogue's DMA below)
 #ifdef SFA_ASM_TIMING
     unsigned long long at_acc[14] = {0}, at_t = __builtin_readcyclecounter();
 #endif
-    // Tile of this block.  The hardware hands consecutive workgroups of a launch to the 8 XCDs in turn (workgroup i -> XCD i % 8, each with an L2 of its
-    // own), so with the plain (x, y, window) grid a tile's horizontal neighbours -- which share two of the four 128-byte lines of every staged row -- and its
-    // vertical neighbours (8 of 16 staged rows) are fetched through OTHER L2s: 2.9 GB crossed the fabric per 64-window launch for 1.4 GB of unique
-    // inputs.  XT: a 1-D grid whose workgroup i works on tile (i % 8) * ceil(N / 8) + i / 8 of the row-major (window, tile row, tile column) order: every XCD
-    // walks a contiguous eighth of the tiles, its CUs hold neighbouring tiles at any time, and the shared lines are L2 hits.
-    int bx_, by_, b_;
-    if (XT) {
-        const unsigned nxy = (unsigned)xt.nx * (unsigned)xt.ny;
-        const unsigned j = (blockIdx.x & 7u) * (unsigned)xt.chunk + (blockIdx.x >> 3);
-        if (j >= nxy * (unsigned)g.nb) return;
-        b_ = (int)(j / nxy);
-        const unsigned r = j - (unsigned)b_ * nxy;
-        by_ = (int)(r / (unsigned)xt.nx);
-        bx_ = (int)(r - (unsigned)by_ * (unsigned)xt.nx);
-    } else { bx_ = blockIdx.x; by_ = blockIdx.y; b_ = blockIdx.z; }
-    const int bx = __builtin_amdgcn_readfirstlane(bx_), by = __builtin_amdgcn_readfirstlane(by_), b = __builtin_amdgcn_readfirstlane(b_);
-    // reset the solver's progress words and ticket -- for EVERY window of the launch: the solver that follows runs all of them, also the
-    // passengers whose operands this launch leaves alone (Geo::active), and draws its tickets from window 0's block whoever is active
-    if (a.op.sa && bx == 0 && by == 0) {
-        for (int i = threadIdx.x; i < a.op.ntasks; i += NT) a.op.flags[(size_t)b * a.op.ntasks + i] = 0;
-        if (b == 0 && threadIdx.x == 0) a.op.flags[(size_t)a.op.nb * a.op.ntasks] = 0;
-    }
+    int bx, by, b;
+    if (!asm_block_tile<XT>(g, xt, bx, by, b)) return;
+    asm_reset_progress<K>(a.op, bx, by, b);
     if (!elem_active(g, b)) return;
-#if SFA_ASM_STAGGER
-    // what-if (round 6): the blocks of the launch's FIRST residency round (three per CU) start a third of a block's life apart, so that one block of a CU stages
-    // while the others compute; every later block starts when an earlier one ends and inherits its phase.  SFA_ASM_STAGGER = units of ~6 400 cycles per slot
-    if (XT && blockIdx.x < 8u * 32u * 3u) {
-        const unsigned j = blockIdx.x >> 3;                                     // index inside the XCD
-        const unsigned slot = SFA_ASM_STAGGER_MODE ? j % 3u : (j >> 5) % 3u;
-        for (unsigned s_ = 0; s_ < slot * SFA_ASM_STAGGER; s_++) __builtin_amdgcn_s_sleep(100);
-    }
-#endif
     const int x0 = bx * DT_X - DT_H, y0 = by * TY - DT_H;                       // origin of the halo-4 tile
     // The whole staged tile (halo 4) lies inside the image -- no replicated columns, no folded border rows, no skipped rows: 84 % of the tiles at 1024x436.
     // The conversion pass and stage 1 then run without the per-item index arithmetic and checks (the item -> plane / row / quad divisions were a fifth of
     // their instructions): wave-uniform branch, same values
-    const bool tile_in = SFA_TILE_FAST && x0 >= 0 && x0 + DT_W <= g.w && y0 >= 0 && y0 + TR <= g.h;
+    const bool tile_in = SFA_TILE_FAST && x0 >= 0 && x0 + DT_W <= g.w && y0 >= 0 && y0 + K::TR <= g.h;
     const long eb = b * g.es;
     const int tx = threadIdx.x & 63;
     const int ty = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);            // one row per wave
@@ -1386,217 +1603,69 @@ __global__ void __launch_bounds__(NT, MINB) k_assemble_images(AssembleArgs a, co
         if (!ok[k]) continue;
         const size_t o = (size_t)y * g.pitch + x;
         if (!ZUV) { u[k] = du[eb + o]; v[k] = dv[eb + o]; }
-        if (!FAST && a.chw) {                                                          // see k_assemble
-            const unsigned lin = (unsigned)y * (unsigned)a.lstride + (unsigned)x;      // < 2^31: checked where the weights are attached
-            const unsigned r0 = lin / (unsigned)a.chw_stride0, c0 = lin % (unsigned)a.chw_stride0;
-            const float *cw = a.chw + b * a.chw_es + r0 * a.chw_pitch + c0;
-            wk[k][0] = cw[0]; wk[k][1] = cw[a.chw_pl]; wk[k][2] = cw[2 * a.chw_pl];
-        }
+        if (!FAST && a.chw) channel_weights(a, b, x, y, wk[k]);
         if (!(SFA_X_AI & 128)) oc[k] = occ[eb + o];                                   // k_mask_weight
     }
-    constexpr int QM = DT_W / 4, Q1 = AW1 / 4;                       // float4 quads per staged row
     // global -> LDS by DMA like the image quads: rows y-1 .. y+TY of the four planes, the 18 aligned quads that cover columns x0 .. x0+71.  Quads outside
     // the planes are skipped; the border rules of the gather never read them.
     const bool need_g = a.do_laplacian || a.op.sa;
     auto stage_epilogue_operands = [&]() {
         if (!need_g) return;
-        for (int i0 = 0; i0 < NGQ; i0 += NT) {
+        for (int i0 = 0; i0 < K::NGQ; i0 += NT) {
             const int item = i0 + (int)threadIdx.x;
-            const int q = item % QM, row = (item / QM) % GR, pl = item / (QM * GR);
+            const int q = item % K::QM, row = (item / K::QM) % K::GR, pl = item / (K::QM * K::GR);
             const int gy = y0 + DT_H - 1 + row, gx = x0 + 4 * q;
             const float *src = pl == 0 ? uu : pl == 1 ? vv : pl == 2 ? sh : sv;
-            if (!(SFA_X_AI & 32) && item < NGQ && gy >= 0 && gy < g.h && gx >= 0 && gx + 3 < g.pitch && (pl >= 2 || a.do_laplacian))
+            if (!(SFA_X_AI & 32) && item < K::NGQ && gy >= 0 && gy < g.h && gx >= 0 && gx + 3 < g.pitch && (pl >= 2 || a.do_laplacian))
                 dma16(src + eb + (size_t)gy * g.pitch + gx, lds_addr(lds + 4 * (i0 + 64 * ty)));
         }
     };
     AT_MARK(13);
     if (a.n == 0) stage_epilogue_operands();
-    float mk2[2][NP];                                                  // the raw warp masks of the staged pair of terms
+    float mk[NP];                                                      // the raw warp mask of the staged term
     for (int t = 0; t < a.n; t++) {
         const Term &T = a.t[t];
-        const int ub = kAsmPair ? t & 1 : 0;                       // staging buffer of this term
-        float(*sM)[NM] = sM2 + 3 * ub;
-        float(*sZ)[NM] = sZ2 + 3 * ub;
-        if (ub == 0) {
         AT_MARK(0);
         if (t > 0) __syncthreads();                                // the staged planes are free again
         AT_MARK(1);
         SFA_PRIO(SFA_PRIO_STAGE);
-        // stage 0 for this term and the next: M and Iz (halo 4) of the three channels, one float4 of a row per item; columns outside
-        // the image are replicated (clamped source column), rows outside are never read
-        // The raw image quads go global -> LDS by DMA (no register staging: at this kernel's VGPR budget a register pipeline spills, and the
-        // plain load -> convert -> store loop exposed one HBM round trip per item).  Four image sets of three planes: I1, I2 of this term into the
-        // M / Iz planes of buffer 0, those of the next term into buffer 1; a set's quad order == its LDS order, so a wave-instruction's 64 quads
-        // land on 64 consecutive 16-byte slots.  An image that both terms use (the reference frame: I2 of the backward pair is I1 of the forward
-        // pair) is fetched once.  A second pass converts in place.
-        const int npair = kAsmPair && t + 1 < a.n ? 2 : 1;
-        constexpr int NSQ = 3 * TR * QM, NSI = (NSQ + 63) / 64;        // quads / wave-instructions per image set
-        const Term &T0 = a.t[t], &T1 = a.t[t + npair - 1];
-        // where the next term's I1 / I2 come from: 0 this term's I1, 1 this term's I2, 2 own fetch
-        const int from_a = npair == 2 ? (T1.i1_off == T0.i1_off ? 0 : T1.i1_off == T0.i2_off ? 1 : 2) : 0;
-        const int from_b = npair == 2 ? (T1.i2_off == T0.i1_off ? 0 : T1.i2_off == T0.i2_off ? 1 : 2) : 0;
-        const long set_src[4] = {T0.i1_off, T0.i2_off, T1.i1_off, T1.i2_off};
-        const int set_dst[4] = {0, ZOFF, 3 * NM, ZOFF + 3 * NM};
-        // one wave-instruction per part and set; a part's quad -> (row, channel) arithmetic is the same for every set, so it runs once per part (it was a
-        // third of this phase's instructions when it ran per set), and the address is a wave-uniform base per set + one 32-bit lane offset
-        const float *set_base[4];
-#pragma unroll
-        for (int set = 0; set < 4; set++) set_base[set] = base + eb + set_src[set];
-        const bool own_a = npair == 2 && from_a == 2, own_b = npair == 2 && from_b == 2;
-        for (int part = ty; part < NSI; part += NR) {
-            const int k = part * 64 + tx;
-            const int q = k % QM, ly = (k / QM) % TR, ch = k / (QM * TR);
-            const int gy = y0 + ly, gx = x0 + 4 * q;
-            if (!(SFA_X_AI & 1) && k < NSQ && gy >= 0 && gy < g.h && gx >= 0 && gx + 3 < g.w) {
-                const unsigned po = 4u * ((unsigned)ch * (unsigned)g.pl + (unsigned)gy * (unsigned)g.pitch + (unsigned)gx);   // offset inside one image set: < 12 * plane bytes < 2^32 (launcher)
-                const unsigned ld = lds_addr(lds + 256 * part);
-                dma16s(set_base[0], po, ld + 4u * set_dst[0]);
-                dma16s(set_base[1], po, ld + 4u * set_dst[1]);
-                if (own_a) dma16s(set_base[2], po, ld + 4u * set_dst[2]);
-                if (own_b) dma16s(set_base[3], po, ld + 4u * set_dst[3]);
-            }
-        }
-        // the masks of the staged terms: issued BEHIND the DMA (the asm statements above are memory barriers to the compiler), looked at behind the one wait.
+        asm_issue_image_dma<K>(base + eb + T.i1_off, base + eb + T.i2_off, g, x0, y0, tx, ty);
+        // the mask of the staged term: issued BEHIND the DMA (the asm statements above are memory barriers to the compiler), looked at behind the one wait.
         // In front of it their destination registers were reused as the don't-care high half of a 64-bit multiply-add in the issue loop, and the wait-count
         // pass answered with an `s_waitcnt vmcnt(0)` inside the loop: a full memory round trip before the first DMA piece (12 % of the wave time in the phase stamps)
 #pragma unroll
         for (int k = 0; k < NP; k++) {
             const size_t o = (size_t)(y0 + DT_H + ty + NR * k) * g.pitch + x;
-            mk2[0][k] = ok[k] && !(SFA_X_AI & 128) ? base[eb + T0.mask_off + o] : 0.0f;
-            mk2[1][k] = npair == 2 ? (ok[k] && !(SFA_X_AI & 128) ? base[eb + T1.mask_off + o] : 0.0f) : mk2[0][k];
+            mk[k] = ok[k] && !(SFA_X_AI & 128) ? base[eb + T.mask_off + o] : 0.0f;
         }
         AT_MARK(2);
-        // everything issued so far has landed behind this wait: the DMA pieces and the prologue's / the masks' loads (tied to it through the operand list,
+        // everything issued so far has landed behind this wait: the DMA pieces and the prologue's / the mask's loads (tied to it through the operand list,
         // so that no use of them can be scheduled, and waited for, in front of the DMA issue)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
         for (int k = 0; k < NP; k++) {
-            asm volatile("" : "+v"(mk2[0][k]), "+v"(mk2[1][k]), "+v"(oc[k]));
+            asm volatile("" : "+v"(mk[k]), "+v"(oc[k]));
             if (!FAST) asm volatile("" : "+v"(wk[k][0]), "+v"(wk[k][1]), "+v"(wk[k][2]));
             if (!ZUV) asm volatile("" : "+v"(u[k]), "+v"(v[k]));
         }
         AT_MARK(3);
-        // Round 6, measured and NOT kept (-DSFA_ASM_DMA_BARRIER=0): the conversion pass below touches exactly the quads this wave's own DMA brought (a wave issues the
-        // parts ty, ty + NR, ... and converts the items ty * 64 + tx + i * NT: the same 16-byte slots, in the tile-interior path and in the border path alike), so the
-        // wave's own `s_waitcnt vmcnt(0)` above is all the conversion needs and this barrier -- one of four per term -- can go.  Bit-identical (60 parity tests) and
-        // worth nothing: 110.0 / 109.3 ms per bench step without it against 109.8 / 109.5 with it, same box: the waves of a block reach the barrier in front of
-        // stage 1 together either way.
-        if (SFA_ASM_DMA_BARRIER || kAsmPair) __syncthreads();      // the DMA of every wave has landed
+        // The DMA of every wave has landed.  The wave's own wait above would suffice (the conversion pass touches exactly the quads this wave's own DMA
+        // brought, in both of its forms), but dropping this barrier measured as no gain: the waves reach the barrier in front of stage 1 together either way
+        __syncthreads();
         AT_MARK(4);
         if (t == 0) {
 #pragma unroll
-            for (int k = 0; k < NP; k++) {                          // k_mask_weight (variational_mt.cpp:293-320)
-                float factor = (oc[k] == 0.0f) ? 1.0f : 0.0f;
-                factor = (1 + factor) * a.data_norm;
-                bwd[k] = __fdiv_rn((oc[k] >= 0.0f) ? 1.0f : 0.0f, factor);
-                fwd[k] = __fdiv_rn((oc[k] <= 0.0f) ? 1.0f : 0.0f, factor);
-            }
+            for (int k = 0; k < NP; k++) mask_weights(oc[k], a.data_norm, fwd[k], bwd[k]);
         }
-        if (tile_in) {                                             // a staged quad's LDS slot is 16 bytes * its item number in every plane set: no index arithmetic at all
-            for (int item = threadIdx.x; item < ((SFA_X_AI & 2) ? 0 : NSQ); item += NT) {
-                auto quad = [&](int lds_off) { return *reinterpret_cast<const float4 *>(lds + lds_off + 4 * item); };
-                auto convert = [&](const float4 &va, const float4 &vb, int lds_off) {       // Iz also on the four rows nobody reads: cheaper than knowing the row
-                    *reinterpret_cast<float4 *>(lds + lds_off + 4 * item) =
-                        make_float4(0.5f * (vb.x + va.x), 0.5f * (vb.y + va.y), 0.5f * (vb.z + va.z), 0.5f * (vb.w + va.w));        // variational_mt.cpp:120
-                    *reinterpret_cast<float4 *>(lds + ZOFF + lds_off + 4 * item) = make_float4(va.x - vb.x, va.y - vb.y, va.z - vb.z, va.w - vb.w);   // :122
-                };
-                const float4 a0 = quad(0), b0 = quad(ZOFF);
-                if (npair == 2) {
-                    const float4 a1 = from_a == 0 ? a0 : from_a == 1 ? b0 : quad(3 * NM);
-                    const float4 b1 = from_b == 0 ? a0 : from_b == 1 ? b0 : quad(ZOFF + 3 * NM);
-                    convert(a1, b1, 3 * NM);
-                }
-                convert(a0, b0, 0);
-            }
-        } else
-        for (int item = threadIdx.x; item < ((SFA_X_AI & 2) ? 0 : NSQ); item += NT) {     // both terms of the pair in one item: the shared image is read before it is overwritten
-            const int q = item % QM, ly = (item / QM) % TR, ch = item / (QM * TR);
-            const int gy = y0 + ly, gx = x0 + 4 * q;
-            if (gy < 0 || gy >= g.h) continue;
-            const bool interior = gx >= 0 && gx + 3 < g.w;
-            const float *row = base + eb + ch * g.pl + (size_t)gy * g.pitch;
-            auto fetch = [&](long src_off, int lds_off) {          // columns outside the image: replicated (clamped source column)
-                if (interior) return *reinterpret_cast<const float4 *>(lds + lds_off + 4 * item);
-                const float *r = row + src_off;
-                return make_float4(r[clampi(gx, 0, g.w - 1)], r[clampi(gx + 1, 0, g.w - 1)], r[clampi(gx + 2, 0, g.w - 1)], r[clampi(gx + 3, 0, g.w - 1)]);
-            };
-            auto convert = [&](const float4 &va, const float4 &vb, int lds_off) {
-                *reinterpret_cast<float4 *>(lds + lds_off + 4 * item) =
-                    make_float4(0.5f * (vb.x + va.x), 0.5f * (vb.y + va.y), 0.5f * (vb.z + va.z), 0.5f * (vb.w + va.w));        // variational_mt.cpp:120
-                if (ly >= 2 && ly < TR - 2)                         // Iz is read two rows around the tile only (M four: Ix, Iy exist on the halo-2 rows)
-                    *reinterpret_cast<float4 *>(lds + ZOFF + lds_off + 4 * item) = make_float4(va.x - vb.x, va.y - vb.y, va.z - vb.z, va.w - vb.w);   // :122
-            };
-            const float4 a0 = fetch(T0.i1_off, 0), b0 = fetch(T0.i2_off, ZOFF);
-            if (npair == 2) {
-                const float4 a1 = from_a == 0 ? a0 : from_a == 1 ? b0 : fetch(T1.i1_off, 3 * NM);
-                const float4 b1 = from_b == 0 ? a0 : from_b == 1 ? b0 : fetch(T1.i2_off, ZOFF + 3 * NM);
-                convert(a1, b1, 3 * NM);
-            }
-            convert(a0, b0, 0);
-        }
+        if (tile_in) asm_convert<K, true>(base + eb + T.i1_off, base + eb + T.i2_off, g, x0, y0);
+        else asm_convert<K, false>(base + eb + T.i1_off, base + eb + T.i2_off, g, x0, y0);
         AT_MARK(5);
-        }
         AT_MARK(0);
         __syncthreads();                                           // staged planes complete / the previous term is done with Ix, Iy
         AT_MARK(6);
         SFA_PRIO(SFA_PRIO_STAGE);
-        // stage 1: Ix, Iy on the halo-2 rows, one aligned quad of M's columns per item.  The row taps of the quad's four columns are the 8 values around it (the two
-        // outermost quads of a row reach into the neighbouring rows' ends: their outer two columns are never read by anybody), the column taps four aligned quads
-        if (tile_in) {
-            // items in plane-major order (channel, row, quad): with 72 = 4 * 18 columns the quad's M index is 4 * item + 2 rows + (NM - N1) * channel and its
-            // Ix / Iy index 4 * item
-            static_assert(DT_W == 4 * Q1 && AW1 == DT_W && N1 == 4 * AT_R1 * Q1, "linear item numbering of stage 1");
-            for (int item = threadIdx.x; item < ((SFA_X_AI & 4) ? 0 : AT_R1 * 3 * Q1); item += NT) {
-                const int ch = (item >= AT_R1 * Q1 ? 1 : 0) + (item >= 2 * AT_R1 * Q1 ? 1 : 0);
-                const float *Mq = sM[0] + 4 * item + 2 * DT_W + (NM - N1) * ch;
-                const float2 lo = *reinterpret_cast<const float2 *>(Mq - 2), hi = *reinterpret_cast<const float2 *>(Mq + 4);
-                const float4 mid = *reinterpret_cast<const float4 *>(Mq);
-                const float m2[8] = {lo.x, lo.y, mid.x, mid.y, mid.z, mid.w, hi.x, hi.y};
-                float X[4], Y[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++) X[e] = tap5(m2[e], m2[e + 1], m2[e + 2], m2[e + 3], m2[e + 4]);                      // :127
-                const float4 r0 = *reinterpret_cast<const float4 *>(Mq - 2 * DT_W), r1 = *reinterpret_cast<const float4 *>(Mq - DT_W);
-                const float4 r3 = *reinterpret_cast<const float4 *>(Mq + DT_W), r4 = *reinterpret_cast<const float4 *>(Mq + 2 * DT_W);
-                Y[0] = tap5(r0.x, r1.x, m2[2], r3.x, r4.x); Y[1] = tap5(r0.y, r1.y, m2[3], r3.y, r4.y);                         // :128
-                Y[2] = tap5(r0.z, r1.z, m2[4], r3.z, r4.z); Y[3] = tap5(r0.w, r1.w, m2[5], r3.w, r4.w);
-                *reinterpret_cast<float4 *>(&sX[0][4 * item]) = make_float4(X[0], X[1], X[2], X[3]);
-                *reinterpret_cast<float4 *>(&sY[0][4 * item]) = make_float4(Y[0], Y[1], Y[2], Y[3]);
-            }
-        } else
-        for (int item = threadIdx.x; item < ((SFA_X_AI & 4) ? 0 : AT_R1 * 3 * Q1); item += NT) {
-            const int q = item % Q1, ch = (item / Q1) % 3, ly = item / (3 * Q1);
-            const int gy = y0 + 2 + ly, gx = x0 + 4 * q;
-            if (gy < 0 || gy >= g.h) continue;
-            const float *M = sM[ch];
-            const int c = (ly + 2) * DT_W + 4 * q;                 // M index of column gx
-            const bool y_in = gy >= 2 && gy + 2 < g.h;
-            float m2[8];                                            // row gy, columns gx-2 .. gx+5
-            {
-                const float2 lo = *reinterpret_cast<const float2 *>(M + c - 2), hi = *reinterpret_cast<const float2 *>(M + c + 4);
-                const float4 mid = *reinterpret_cast<const float4 *>(M + c);
-                m2[0] = lo.x; m2[1] = lo.y; m2[2] = mid.x; m2[3] = mid.y; m2[4] = mid.z; m2[5] = mid.w; m2[6] = hi.x; m2[7] = hi.y;
-            }
-            float X[4], Y[4];
-            if (gx >= 0 && gx + 3 < g.w) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) X[e] = tap5(m2[e], m2[e + 1], m2[e + 2], m2[e + 3], m2[e + 4]);                      // :127
-            } else {                                                // X(clamp(x), y) for the columns outside the image
-#pragma unroll
-                for (int e = 0; e < 4; e++) X[e] = d5x_in<DT_W>(M, c + e + (clampi(gx + e, 0, g.w - 1) - (gx + e)));
-            }
-            if (y_in) {                                             // tap5's own order of operations, one aligned row of the quad's columns at a time  (:128)
-                const float4 r0 = *reinterpret_cast<const float4 *>(M + c - 2 * DT_W), r1 = *reinterpret_cast<const float4 *>(M + c - DT_W);
-                const float4 r3 = *reinterpret_cast<const float4 *>(M + c + DT_W), r4 = *reinterpret_cast<const float4 *>(M + c + 2 * DT_W);
-                Y[0] = tap5(r0.x, r1.x, m2[2], r3.x, r4.x); Y[1] = tap5(r0.y, r1.y, m2[3], r3.y, r4.y);
-                Y[2] = tap5(r0.z, r1.z, m2[4], r3.z, r4.z); Y[3] = tap5(r0.w, r1.w, m2[5], r3.w, r4.w);
-            } else {
-                const TileAcc m4{M, x0, y0};
-#pragma unroll
-                for (int e = 0; e < 4; e++) Y[e] = d5y(m4, clampi(gx + e, 0, g.w - 1), gy, g.h);
-            }
-            *reinterpret_cast<float4 *>(&sX[ch][ly * AW1 + 4 * q]) = make_float4(X[0], X[1], X[2], X[3]);
-            *reinterpret_cast<float4 *>(&sY[ch][ly * AW1 + 4 * q]) = make_float4(Y[0], Y[1], Y[2], Y[3]);
-        }
+        if (tile_in) asm_stage1<K, true>(g, x0, y0);
+        else asm_stage1<K, false>(g, x0, y0);
         AT_MARK(7);
         __syncthreads();
         AT_MARK(8);
@@ -1605,78 +1674,13 @@ __global__ void __launch_bounds__(NT, MINB) k_assemble_images(AssembleArgs a, co
         if (t == a.n - 1) stage_epilogue_operands();
 #pragma unroll
         for (int k = 0; k < NP; k++) {
-            const int y = y0 + DT_H + ty + NR * k;
+            const int yl = ty + NR * k, y = y0 + DT_H + yl;
             if (y >= g.h) break;
-            const bool y_in = y >= 2 && y + 2 < g.h;
-            // The lane's column is made opaque once per term: every tap address below is then computed inside the term loop from ONE register (the planes
-            // above 64 KB -- Iy, part of Ix -- are out of reach of a 16-bit LDS offset from the block's start, and left to itself the compiler kept ~45 registers
-            // of per-plane, per-clamped-row addresses of both the interior and the border path live across the whole term loop: tools/isa_live.py), and the
-            // interior path's reads are offsets from a base in the middle of the block (cb: the Iz planes' start + the pixel), all below 48 KB
-            int txl = tx;
-            asm volatile("" : "+v"(txl));
-            const int c = (ty + NR * k + 2) * AW1 + (txl + 4);    // halo-2 rows (Ix, Iy), M's columns
-            const int cz = (ty + NR * k + 4) * DT_W + (txl + 4);  // halo-4 plane (Iz)
-            static_assert(AW1 == DT_W, "cz = c + 2 rows");
-            int cb = ZOFF + c;
-            asm volatile("" : "+v"(cb));
-            const float *const pX = lds + cb + (XOFF - ZOFF), *const pY = pX + 3 * N1, *const pZ = lds + cb + 3 * ub * NM + 2 * DT_W;   // sX[0] + c, sY[0] + c, sZ[0] + cz
-            Px p;
+            Px p = asm_pixel_derivatives<K>(g, x0, y0, tx, yl, y);
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) p.wk[ch] = FAST ? 1.0f : wk[k][ch];
-            if (SFA_X_AI & 8) {
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) {
-                    p.ixy[ch] = sX[ch][c + 1]; p.iyy[ch] = sY[ch][c + 1]; p.iyz[ch] = sZ[ch][cz + 1];
-                    p.ix[ch] = sX[ch][c]; p.iy[ch] = sY[ch][c]; p.iz[ch] = sZ[ch][cz]; p.ixx[ch] = sX[ch][c - 1]; p.ixz[ch] = sZ[ch][cz - 1];
-                }
-            } else if (y_in) {
-                // All 69 taps of the pixel (per channel: a row and a column of Ix and of Iz, a column of Iy) are READ first and the filters run behind a scheduling
-                // fence.  Left to itself the compiler read two taps, waited, used them, read the next two (82 LDS instructions per term, nearly each with a wait
-                // of its own, in a kernel with then 4 waves per SIMD): the per-pixel phase was 36 % of a wave's life, and most of that LDS latency (round-4 phase stamps).
-                // Two channels' taps in flight at most (all three at once: 69 registers of taps, spills at this kernel's 128).
-                float xr[3][5], xc[3][4], yc[3][5], zr[3][5], zc[3][4];
-                auto read_taps = [&](int ch) {
-                    const float *X = pX + ch * N1, *Y = pY + ch * N1, *Z = pZ + ch * NM;
-#pragma unroll
-                    for (int j = 0; j < 5; j++) xr[ch][j] = X[j - 2];
-                    xc[ch][0] = X[-2 * AW1]; xc[ch][1] = X[-AW1]; xc[ch][2] = X[AW1]; xc[ch][3] = X[2 * AW1];
-#pragma unroll
-                    for (int j = 0; j < 5; j++) yc[ch][j] = Y[(j - 2) * AW1];
-#pragma unroll
-                    for (int j = 0; j < 5; j++) zr[ch][j] = Z[j - 2];
-                    zc[ch][0] = Z[-2 * DT_W]; zc[ch][1] = Z[-DT_W]; zc[ch][2] = Z[DT_W]; zc[ch][3] = Z[2 * DT_W];
-                };
-                auto filters = [&](int ch) {
-                    p.ix[ch] = xr[ch][2]; p.iy[ch] = yc[ch][2]; p.iz[ch] = zr[ch][2];
-                    p.ixx[ch] = tap5(xr[ch][0], xr[ch][1], xr[ch][2], xr[ch][3], xr[ch][4]);     // :129
-                    p.ixy[ch] = tap5(xc[ch][0], xc[ch][1], xr[ch][2], xc[ch][2], xc[ch][3]);     // :130
-                    p.iyy[ch] = tap5(yc[ch][0], yc[ch][1], yc[ch][2], yc[ch][3], yc[ch][4]);     // :131
-                    p.ixz[ch] = tap5(zr[ch][0], zr[ch][1], zr[ch][2], zr[ch][3], zr[ch][4]);     // :132
-                    p.iyz[ch] = tap5(zc[ch][0], zc[ch][1], zr[ch][2], zc[ch][2], zc[ch][3]);     // :133
-                };
-                read_taps(0); read_taps(1);
-                __builtin_amdgcn_sched_barrier(0);
-                filters(0);
-                __builtin_amdgcn_sched_barrier(0);
-                read_taps(2);
-                __builtin_amdgcn_sched_barrier(0);
-                filters(1); filters(2);
-            } else {
-                const int xl = x0 + DT_H + txl, xc_ = xl < g.w ? xl : g.w - 1;
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) {
-                    const Tile1Acc X{sX[ch], x0, y0 + 2}, Y{sY[ch], x0, y0 + 2};               // (DT_W wide, like M)
-                    const TileAcc Z{sZ[ch], x0, y0};
-                    p.ixy[ch] = d5y(X, xc_, y, g.h);
-                    p.iyy[ch] = d5y(Y, xc_, y, g.h);
-                    p.iyz[ch] = d5y(Z, xc_, y, g.h);
-                    p.ix[ch] = sX[ch][c]; p.iy[ch] = sY[ch][c]; p.iz[ch] = sZ[ch][cz];
-                    p.ixx[ch] = d5x_in<AW1>(sX[ch], c);                                // :129
-                    p.ixz[ch] = d5x_in<DT_W>(sZ[ch], cz);                              // :132
-                }
-            }
             if (!ok[k]) continue;
-            float m = mk2[ub][k];
+            float m = mk[k];
             if (!a.one_direction || !T.backward) m = T.backward ? 1.0f * bwd[k] * m : 1.0f * fwd[k] * m;   // :314,316
             if (SFA_X_AI & 16) {
                 for (int ch = 0; ch < 3; ch++) {
@@ -1686,12 +1690,6 @@ __global__ void __launch_bounds__(NT, MINB) k_assemble_images(AssembleArgs a, co
             else          term_succ<ZUV, FAST != 0>(A[k], p, m, u[k], v[k], T.hd, T.hg, T.s, dt_norm, pcolor, pgrad, a.chain_ok != 0);
         }
     }
-    // row strides chosen for the anti-diagonal read-out below (entry 64*rl + dl of a 65-wide row puts the TY rows of a diagonal into one bank group:
-    // PMC of round 2 showed 37 % of this kernel's LDS cycles in bank conflicts): with 67 float4 / 69 float2 per row the 16 lanes of a b128 pass
-    // (32 of a b64 pass) land on distinct banks
-    float4(*tA)[67] = reinterpret_cast<float4(*)[67]>(lds + NGF);               // [TY][67] each; live after the last barrier below
-    float4(*tB)[67] = tA + TY;
-    float2(*tX)[69] = reinterpret_cast<float2(*)[69]>(tB + TY);
     AT_MARK(0);
     if (need_g) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1699,71 +1697,33 @@ __global__ void __launch_bounds__(NT, MINB) k_assemble_images(AssembleArgs a, co
     }
     AT_MARK(9);
     SFA_PRIO(SFA_PRIO_STAGE);
-    const Tile1Acc U{lds, x0, y0 + DT_H - 1}, V{lds + GR * DT_W, x0, y0 + DT_H - 1}, Hh{lds + 2 * GR * DT_W, x0, y0 + DT_H - 1},
-        Wv{lds + 3 * GR * DT_W, x0, y0 + DT_H - 1};
 #pragma unroll
     for (int k = 0; k < NP; k++) {
         if (!ok[k]) continue;
         const int yl = ty + NR * k, y = y0 + DT_H + yl;
-        const size_t o = (size_t)y * g.pitch + x;
-        if (a.do_laplacian) {                                                            // variational_mt.cpp:364-365
-            A[k].b1 = laplacian_gather(A[k].b1, U, Hh, Wv, x, y, g.w, g.h);
-            A[k].b2 = laplacian_gather(A[k].b2, V, Hh, Wv, x, y, g.w, g.h);
-        }
+        asm_epilogue_pixel<K>(a, g, A[k], u[k], v[k], x0, y0, tx, yl, x, y);
         if (!a.op.sa) {
-            a11[eb + o] = A[k].a11; a12[eb + o] = A[k].a12; a22[eb + o] = A[k].a22; b1[eb + o] = A[k].b1; b2[eb + o] = A[k].b2;
-            continue;
+            const size_t o = eb + (size_t)y * g.pitch + x;
+            a11[o] = A[k].a11; a12[o] = A[k].a12; a22[o] = A[k].a22; b1[o] = A[k].b1; b2[o] = A[k].b2;
         }
-        // k_sor_prepare's per-pixel part (solver.c:101-106,159,214): neighbour weights, inverted 2x2 block
-        const float hp = Hh(x, y);
-        const float hl = x > 0 ? Hh(x - 1, y) : 0.0f;                                    // f1[0] = 0, solver.c:82
-        const float vp = Wv(x, y);
-        const float vt = y > 0 ? Wv(x, y - 1) : 0.0f;
-        float dpsis = hl + hp;
-        if (y > 0) dpsis = dpsis + vt;
-        if (y < g.h - 1) dpsis = dpsis + vp;
-        const float m12 = A[k].a12;
-        const float A11 = A[k].a22 + dpsis, A22 = A[k].a11 + dpsis;                      // solver.c:102
-        const float det = A11 * A22 - m12 * m12;
-        const float i11 = __fdiv_rn(A11, det), i22 = __fdiv_rn(A22, det), i12 = __fdiv_rn(m12, -det);   // solver.c:104-106
-        tA[yl][tx] = make_float4(i11, i12, i22, vt);
-        tB[yl][tx] = make_float4(A[k].b1, A[k].b2, hp, y < g.h - 1 ? vp : 0.0f);
-        tX[yl][tx] = make_float2(u[k], v[k]);
     }
     if (!a.op.sa) return;
     AT_MARK(10);
     __syncthreads();
     AT_MARK(11);
-    // the tile's anti-diagonals: TY consecutive entries of the diagonal-major operand planes each
-    const int c0 = x0 + DT_H, r0 = y0 + DT_H;
-    for (int item = threadIdx.x; item < (DT_X + TY - 1) * TY; item += NT) {
-        const int dl = item / TY, rl = item % TY, cl = dl - rl;
-        if (cl < 0 || cl >= DT_X) continue;
-        const int r = r0 + rl, c = c0 + cl;
-        if (r >= g.h || c >= g.w) continue;
-        const size_t e = (size_t)b * a.op.ent + (size_t)(c + r + a.op.G) * a.op.RP + (r + a.op.G);
-        if (SFA_X_AI & 64) continue;
-        const float2 xv = tX[rl][cl];
-        unsigned long long xu;
-        __builtin_memcpy(&xu, &xv, 8);
-#if defined(SFA_ASM_NT) && SFA_ASM_NT      // what-if (round 6): the operand tile leaves as non-temporal stores
-        typedef float v4f_ __attribute__((ext_vector_type(4)));
-        const float4 qa = tA[rl][cl], qb = tB[rl][cl];
-        __builtin_nontemporal_store((v4f_){qa.x, qa.y, qa.z, qa.w}, reinterpret_cast<v4f_ *>(a.op.sa + e));
-        __builtin_nontemporal_store((v4f_){qb.x, qb.y, qb.z, qb.w}, reinterpret_cast<v4f_ *>(a.op.sb + e));
-        __builtin_nontemporal_store(xu, a.op.x + e);
-#else
-        a.op.sa[e] = tA[rl][cl];
-        a.op.sb[e] = tB[rl][cl];
-        a.op.x[e] = xu;
-#endif
-    }
+    asm_store_operand_tile<K>(a.op, g, b, x0 + DT_H, y0 + DT_H);
 #ifdef SFA_ASM_TIMING
     AT_MARK(12);
     // a sample of the blocks only: with every wave adding its 14 slots the atomics on 14 addresses were the kernel (0.85 s per bench step instead of 0.07)
     if ((threadIdx.x & 63) == 0 && (bx + 3 * by + 7 * b) % 61 == 0)
         for (int i = 0; i < 14; i++) atomicAdd(&g_asm_timing[i], at_acc[i]);
 #endif
+}
+// the instance <ZUV, FAST> in the tile order asked for: XCD-contiguous on a 1-D grid, or the plain (x, y, window) grid
+using AsmKernel = decltype(&k_assemble_images<kAsmTY, kAsmNT, kAsmMinWaves, true, 1, true>);
+template <bool ZUV, int FAST>
+static AsmKernel asm_kernel(bool xcd) {
+    return xcd ? k_assemble_images<kAsmTY, kAsmNT, kAsmMinWaves, ZUV, FAST, true> : k_assemble_images<kAsmTY, kAsmNT, kAsmMinWaves, ZUV, FAST, false>;
 }
 int launch_assemble_images(sfa_ctx *c, const Geo &g, const AssembleArgs &a_in, const float *base, float *a11, float *a12, float *a22, float *b1, float *b2,
                            const float *du, const float *dv, const float *uu, const float *vv, const float *sh, const float *sv, const float *occ) {
@@ -1793,16 +1753,11 @@ int launch_assemble_images(sfa_ctx *c, const Geo &g, const AssembleArgs &a_in, c
     const bool xcd = xcd_env && ntiles >= 64 && ntiles < (1l << 30);
     const XcdTiles xt{(int)grid_.x, (int)grid_.y, (int)((ntiles + 7) / 8)};
     const dim3 grid1_(8u * (unsigned)xt.chunk, 1, 1);
-#define SFA_LAUNCH_AI(ZUV_, FAST_)                                                                                                                      \
-    do {                                                                                                                                                \
-        if (xcd) hipLaunchKernelGGL((k_assemble_images<kAsmTY, kAsmNT, kAsmMinWaves, ZUV_, FAST_, true>), grid1_, dim3(kAsmNT), 0, c->stream, a, base, a11, a12, a22, b1, b2, du, dv, uu, vv, sh, sv, occ, g, xt); \
-        else hipLaunchKernelGGL((k_assemble_images<kAsmTY, kAsmNT, kAsmMinWaves, ZUV_, FAST_, false>), grid_, dim3(kAsmNT), 0, c->stream, a, base, a11, a12, a22, b1, b2, du, dv, uu, vv, sh, sv, occ, g, xt); \
-    } while (0)
     // 64 x 8 tiles, 512 threads, <= 80 VGPRs and 48 KB of LDS (three blocks per CU; rounds 2 - mid-4: 128 VGPRs, 76 KB, two blocks).  Measured and dropped: 64 x 12 on 768 threads, 64 x 16 with two pixels per thread (209 VGPRs, one block per CU: slower),
     // 8 x 256 threads, 16 x 1024 threads (spills at its 128-register cap)
-    if (a.zero_duv) { if (fast == 1) SFA_LAUNCH_AI(true, 1); else if (fast == 2) SFA_LAUNCH_AI(true, 2); else SFA_LAUNCH_AI(true, 0); }
-    else            { if (fast == 1) SFA_LAUNCH_AI(false, 1); else if (fast == 2) SFA_LAUNCH_AI(false, 2); else SFA_LAUNCH_AI(false, 0); }
-#undef SFA_LAUNCH_AI
+    const AsmKernel kern = a.zero_duv ? (fast == 1 ? asm_kernel<true, 1>(xcd) : fast == 2 ? asm_kernel<true, 2>(xcd) : asm_kernel<true, 0>(xcd))
+                                      : (fast == 1 ? asm_kernel<false, 1>(xcd) : fast == 2 ? asm_kernel<false, 2>(xcd) : asm_kernel<false, 0>(xcd));
+    hipLaunchKernelGGL(kern, xcd ? grid1_ : grid_, dim3(kAsmNT), 0, c->stream, a, base, a11, a12, a22, b1, b2, du, dv, uu, vv, sh, sv, occ, g, xt);
     if (prof) {
         (void)hipEventRecord(c->ev2[c->ev2_used + 1], c->stream);
         c->ev2_used += 2;
@@ -1869,7 +1824,7 @@ __global__ void __launch_bounds__(BX *BY) k_update_inner_x(float *__restrict__ u
     if (elem_active(g, b) && x < g.w)
         for (int y = blockIdx.y * BY + threadIdx.y; y < g.h; y += gridDim.y * BY) {
             const size_t o = b * g.es + (size_t)y * g.pitch + x;
-            const unsigned long long xv = xs[(size_t)b * ent + (size_t)(x + y + G) * RP + (y + G)];
+            const unsigned long long xv = xs[diag_entry(b, ent, RP, G, x, y)];
             const float d = __uint_as_float((unsigned)(xv & 0xffffffffu)), e = __uint_as_float((unsigned)(xv >> 32));
             const float od = odu ? odu[o] : 0.0f, oe = odv ? odv[o] : 0.0f;
             sa += (double)fabsf(od - d);                                                 // :389-393
@@ -1906,7 +1861,7 @@ __global__ void __launch_bounds__(BX *BY) k_update_outer_x(float *__restrict__ u
                 const int dl = item / 16, rl = item % 16, cl = dl - rl;
                 if (cl < 0 || cl >= 64) continue;
                 const int r = r0 + rl, c = c0 + cl;
-                if (r < g.h && c < g.w) tX[rl][cl] = xs[(size_t)b * ent + (size_t)(c + r + G) * RP + (r + G)];
+                if (r < g.h && c < g.w) tX[rl][cl] = xs[diag_entry(b, ent, RP, G, c, r)];
             }
             __syncthreads();
             const int x = c0 + threadIdx.x;

@@ -705,17 +705,11 @@ __global__ void __launch_bounds__(256) k_sor_prepare(PrepArgs p) {
             const float hl = c > 0 ? p.sh[o - 1] : 0.0f;                                  // f1[0] = 0, solver.c:82
             const float vp = p.sv[o];
             const float vt = r > 0 ? p.sv[o - p.pitch] : 0.0f;
-            float dpsis = hl + hp;                                                        // solver.c:101,159,214
-            if (r > 0) dpsis = dpsis + vt;
-            if (r < p.H - 1) dpsis = dpsis + vp;
-            const float m12 = p.a12[o];
-            const float A11 = p.a22[o] + dpsis, A22 = p.a11[o] + dpsis;                   // solver.c:102
-            const float det = A11 * A22 - m12 * m12;
-            const float i11 = __fdiv_rn(A11, det), i22 = __fdiv_rn(A22, det), i12 = __fdiv_rn(m12, -det);   // solver.c:104-106
-            tA[rl][tx] = make_float4(i11, i12, i22, vt);                                  // vt = 0 at row 0
+            const PointBlock q = sor_point_block(hl, hp, vt, vp, r, p.H, p.a11[o], p.a12[o], p.a22[o]);
+            tA[rl][tx] = make_float4(q.i11, q.i12, q.i22, vt);                            // vt = 0 at row 0
             tB[rl][tx] = make_float4(p.b1[o], p.b2[o], hp, r < p.H - 1 ? vp : 0.0f);      // no bottom edge in the last row
             tX[rl][tx] = make_float2(p.du[o], p.dv[o]);
-            if (p.inv_out) { p.a11[o] = i11; p.a12[o] = i12; p.a22[o] = i22; }
+            if (p.inv_out) { p.a11[o] = q.i11; p.a12[o] = q.i12; p.a22[o] = q.i22; }
         }
     }
     __syncthreads();
@@ -725,7 +719,7 @@ __global__ void __launch_bounds__(256) k_sor_prepare(PrepArgs p) {
         if (cl < 0 || cl >= PT_C) continue;
         const int r = r0 + rl, c = c0 + cl;
         if (r >= p.H || c >= p.W) continue;
-        const size_t e = (size_t)job * p.ent + (size_t)(c + r + p.G) * p.RP + (r + p.G);
+        const size_t e = diag_entry(job, p.ent, p.RP, p.G, c, r);
         p.sa[e] = tA[rl][cl];
         p.sb[e] = tB[rl][cl];
         const float2 xv = tX[rl][cl];
@@ -738,7 +732,7 @@ __global__ void k_sor_finish(float *__restrict__ du, float *__restrict__ dv, con
     const int job = blockIdx.z;
     const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
     if (c >= W || r >= H || !elem_active(active, amask, job)) return;
-    const float2 v = u2f(x[(size_t)job * ent + (size_t)(c + r + G) * RP + (r + G)]);
+    const float2 v = u2f(x[diag_entry(job, ent, RP, G, c, r)]);
     const size_t o = (size_t)job * es + (size_t)r * pitch + c;
     du[o] = v.x;
     dv[o] = v.y;
@@ -785,13 +779,8 @@ __global__ void __launch_bounds__(256) k_rb_invert(float *__restrict__ a11, floa
     if (x >= g.w || y >= g.h) return;
     const size_t o = b * g.es + (size_t)y * g.pitch + x;
     const float hp = sh[o], hl = x > 0 ? sh[o - 1] : 0.0f;
-    float dpsis = hl + hp;                                                               // solver.c:101,159,214
-    if (y > 0) dpsis = dpsis + sv[o - g.pitch];
-    if (y < g.h - 1) dpsis = dpsis + sv[o];
-    const float m12 = a12[o];
-    const float A11 = a22[o] + dpsis, A22 = a11[o] + dpsis;                               // solver.c:102
-    const float det = A11 * A22 - m12 * m12;
-    a11[o] = __fdiv_rn(A11, det); a22[o] = __fdiv_rn(A22, det); a12[o] = __fdiv_rn(m12, -det);   // solver.c:104-106
+    const PointBlock q = sor_point_block(hl, hp, y > 0 ? sv[o - g.pitch] : 0.0f, sv[o], y, g.h, a11[o], a12[o], a22[o]);
+    a11[o] = q.i11; a22[o] = q.i22; a12[o] = q.i12;
 }
 __global__ void __launch_bounds__(256) k_rb_pass(float *__restrict__ du, float *__restrict__ dv, const float *__restrict__ i11, const float *__restrict__ i12,
                                                  const float *__restrict__ i22, const float *__restrict__ b1, const float *__restrict__ b2,

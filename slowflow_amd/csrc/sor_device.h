@@ -40,6 +40,22 @@ __device__ __forceinline__ v2f sor_point(v2f self, v2f right, v2f top, v2f botto
     return self + omega * (t - self);
 }
 
+// The per-pixel operand preparation of the first sweep (solver.c:101-106 with the row variants :159,214): the sum of the neighbour weights -- left, right, and
+// top / bottom where that row exists -- and the inverse of the 2x2 block it completes.  hl is 0 at column 0 (f1[0] = 0, solver.c:82), by the caller.
+struct PointBlock { float dpsis, i11, i12, i22; };
+__device__ __forceinline__ PointBlock sor_point_block(float hl, float hp, float vt, float vp, int r, int h, float a11, float a12, float a22) {
+    PointBlock p;
+    p.dpsis = hl + hp;                                                                    // solver.c:101,159,214
+    if (r > 0) p.dpsis = p.dpsis + vt;
+    if (r < h - 1) p.dpsis = p.dpsis + vp;
+    const float A11 = a22 + p.dpsis, A22 = a11 + p.dpsis;                                 // solver.c:102
+    const float det = A11 * A22 - a12 * a12;
+    p.i11 = __fdiv_rn(A11, det); p.i22 = __fdiv_rn(A22, det); p.i12 = __fdiv_rn(a12, -det);   // solver.c:104-106
+    return p;
+}
+// entry of pixel (column c, row r) of window b in the diagonal-major operand planes: diagonal c + r, slot r, both behind G guard entries
+__device__ __forceinline__ size_t diag_entry(int b, long ent, int RP, int G, int c, int r) { return (size_t)b * ent + (size_t)(c + r + G) * RP + (r + G); }
+
 // value of lane-1 (lane 0 receives `fill`): DPP wave_shr:1, no LDS
 __device__ __forceinline__ float lane_shr1(float v, float fill) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));

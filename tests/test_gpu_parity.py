@@ -481,11 +481,14 @@ def test_level_variants(ctx, oracle, kw):
     dict(), dict(one_direction=1), dict(dataterm_norm=0), dict(delta=0.0), dict(occlusion_reasoning=1, niter_alter=1), dict(niter_inner=3),
     dict(robust_color=(3, 0.001, 0.5), robust_grad=(4, 0.05, 0.5)),
 ])
-@pytest.mark.parametrize("w,h", [(67, 45), (200, 37), (64, 16), (129, 70)])
+@pytest.mark.parametrize("w,h", [(67, 45), (200, 37), (64, 16), (129, 70), (9, 7), (65, 9), (192, 24)])
 def test_fused_assembly_is_the_unfused_pipeline(ctx, oracle, switches, kw, w, h):
     """the image->system kernel (derivative filters in LDS, mask weights on the fly) against the materialised form
     (warp copies, 24-plane stacks, mask-weight pass, per-pixel assembly): the same bits, every term kind, with
-    channel weights, across tile borders (sizes off the 64x8 tile grid)"""
+    channel weights, across tile borders (sizes off the 64x8 tile grid).  The last three sizes are the smallest at which
+    the kernel's border and interior forms can disagree: one tile smaller than its halo in both directions; a second tile
+    column and tile row of one pixel each; exactly one fully interior tile (tile (1, 1): staged columns 60 .. 131 of 192,
+    rows 4 .. 19 of 24) among eight border tiles"""
     frames, af, sf = normalized_frames(oracle, w, h, 5, seed=3)
     rng = np.random.default_rng(1)
     chw = [noise_plane(rng, w, h, 0.5, 1.5) for _ in range(3)]
