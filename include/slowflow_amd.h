@@ -301,11 +301,20 @@ int  sfa_track_job_upload_flows(sfa_track_job *job, int s, int r, const float *c
 int  sfa_track_job_upload_frames(sfa_track_job *job, int s, const float *const *frames, int stride);
 /* The same from GPU memory, for segments s0 .. s0+ns-1: fwd_dev, bwd_dev fp32 [ns][r_Jets[r]][2 (u, v)][sh][sw] and frames_dev fp32
  * [ns][Jets+1][3][h][w], element (i0, .., i4) at p + sum i_k strides[k] (64-bit element strides, >= 0, the column stride >= 1).  Read in stream order on
- * the context's stream and without a host wait: with sfa_ctx_wait_stream / sfa_ctx_signal_stream around them the caller needs none either.  A job with
- * use_occlusions refuses the device flows by name (its occlusion images come with sfa_track_job_upload_flows).  Refused: memory that is not the
+ * the context's stream and without a host wait: with sfa_ctx_wait_stream / sfa_ctx_signal_stream around them the caller needs none either.  On a job
+ * with use_occlusions the device flows leave the rate's masks as they are: the occlusion images are an upload of their own
+ * (sfa_track_job_upload_occlusions_device, or occ of sfa_track_job_upload_flows), in any order with the flows.  Refused: memory that is not the
  * context's GPU's, a view that leaves its allocation, segments outside the job. */
 int  sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r, const float *fwd_dev, const float *bwd_dev, const long long strides[5]);
 int  sfa_track_job_upload_frames_device(sfa_track_job *job, int s0, int ns, const float *frames_dev, const long long strides[5]);
+/* The occlusion images of rate r of segments s0 .. s0+ns-1 from GPU memory: occ_dev [ns][r_Jets[r]][sh][sw] (sh x sw of source[r]) at strides[4], of
+ * dtype (sfa_dev_dtype) SFA_DEV_U8, the RAW 8-bit images that sfa_track_job_upload_flows takes as occ, or SFA_DEV_F32, the labels as
+ * sfa_job_download_device leaves them in occ_dev, turned into the grey image the driver writes by its own expression: v = (x + 1) * 0.5f * 255.0f in
+ * fp32 without contraction, nearbyint (halves to even), max(0.0f, min(255.0f, .)): -1 -> 0, 0 -> 128, +1 -> 255, NaN -> 255, -Inf -> 0, +Inf -> 255.  The
+ * images are decoded into the rate's masks like the host's (cubic resize, 3 x 3 median, 255 - x), segment by segment, in stream order on the context's
+ * stream and without a host wait.  Refused by name, with nothing launched: a job without use_occlusions, r or segments outside the job, any other
+ * dtype, memory that is not the context's GPU's, a view that leaves its allocation. */
+int  sfa_track_job_upload_occlusions_device(sfa_track_job *job, int s0, int ns, int r, const void *occ_dev, int dtype, const long long strides[4]);
 /* Tracks, scores and (do_fuse) fuses segments 0 .. ns-1 (1 <= ns <= n) from what the job holds and returns without waiting.  Everything a run reads that
  * an earlier run wrote (the messages, the labellings, the per-segment records) is initialised again: a job serves any number of groups. */
 int  sfa_track_job_run(sfa_track_job *job, int ns);
@@ -327,6 +336,14 @@ int  sfa_ctx_free_bytes(sfa_ctx *ctx, size_t *free_bytes);
  * Refused: strides that let two elements of the flow share an address (a zero u|v stride ...), destinations that overlap one another. */
 int  sfa_track_job_download_device(sfa_track_job *job, int s0, int ns, double *flow_dev, const long long strides[4], int *slot_dev, unsigned char *occ_dev,
                                    double *stats_dev);
+/* Rate r of segments s0 .. s0+ns-1 after a run into GPU memory, with the values of sfa_track_job_download_rate, in stream order and without a host wait,
+ * also on a job with do_fuse 0: acc_dev fp64 [ns][2 (u, v)][gh][gw] at strides[4], the last accumulated step; packed [ns][gh][gw] tracked_dev int32,
+ * energy_dev fp64 (the fp32 sum; +Inf: no hypothesis), occ_bits_dev uint64 and occluded_dev uint8 (its popcount).  NULL skips an output (strides may be
+ * NULL with acc_dev).  sfa_track_job_download_best_device: best uint8 [ns][gh][gw], as sfa_track_job_download_best gives it.  Refused: strides that let
+ * two elements of acc_dev share an address (a zero u|v stride ...), destinations that overlap one another, r or segments outside the job. */
+int  sfa_track_job_download_rate_device(sfa_track_job *job, int s0, int ns, int r, double *acc_dev, const long long strides[4], int *tracked_dev,
+                                        double *energy_dev, unsigned long long *occ_bits_dev, unsigned char *occluded_dev);
+int  sfa_track_job_download_best_device(sfa_track_job *job, int s0, int ns, unsigned char *best_dev);
 /* The last run's kernel times in ms (HIP events; waits for the run): frame derivatives and records, accumulation, energies (with best / occluded), smoothness
  * weight (its kernel alone), labels, pairwise, TRW-S, output; the last five are 0 on a job with do_fuse 0.  Slot 0 is NOT a pack + resample time: the flows are packed
  * and resampled by the uploads, outside the run. */

@@ -176,7 +176,7 @@ EXPORTS = [
     "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_pair_job_upload_device", "sfa_pair_job_set_flow_device", "sfa_pair_job_download_device", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
     "sfa_demosaic_device", "sfa_sequence_upload_mosaic_device", "sfa_sequence_upload_mosaic", "sfa_job_set_raw_weights", "sfa_sequence_rescale",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
-    "sfa_track_params_default", "sfa_track_job_bytes", "sfa_track_job_create", "sfa_track_job_destroy", "sfa_track_job_upload_flows", "sfa_track_job_upload_frames", "sfa_track_job_upload_flows_device", "sfa_track_job_upload_frames_device", "sfa_track_job_run", "sfa_track_job_download_rate", "sfa_track_job_download_fused", "sfa_track_job_download_best", "sfa_ctx_free_bytes", "sfa_track_job_download_device", "sfa_track_job_stage_ms",
+    "sfa_track_params_default", "sfa_track_job_bytes", "sfa_track_job_create", "sfa_track_job_destroy", "sfa_track_job_upload_flows", "sfa_track_job_upload_frames", "sfa_track_job_upload_flows_device", "sfa_track_job_upload_frames_device", "sfa_track_job_run", "sfa_track_job_download_rate", "sfa_track_job_download_fused", "sfa_track_job_download_best", "sfa_ctx_free_bytes", "sfa_track_job_download_device", "sfa_track_job_stage_ms", "sfa_track_job_upload_occlusions_device", "sfa_track_job_download_rate_device", "sfa_track_job_download_best_device",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
 
@@ -912,6 +912,23 @@ class TrackJob:
         uint8 [ns, gh, gw], stats float64 [ns, 3]"""
         from . import device
         device.track_job_download_device(self, flow, slot, occ, stats, s0)
+
+    def upload_occlusions_device(self, r, occ, s0=0):
+        """occ: [ns, r_Jets[r], sh, sw] in device memory (any strides), uint8 (the raw occlusion images) or float32 (the labels a refinement leaves,
+        turned into the driver's grey image) -> the masks of rate r of segments s0 .. s0 + ns - 1, on a job with use_occlusions"""
+        from . import device
+        device.track_job_upload_occlusions_device(self, r, occ, s0)
+
+    def download_rate_device(self, r, acc=None, tracked=None, energy=None, occ_bits=None, occluded=None, s0=0):
+        """rate r of segments s0 .. into device arrays, the values of download_rate: acc float64 [ns, 2, gh, gw] (any strides; the last accumulated
+        step); contiguous [ns, gh, gw] tracked int32, energy float64, occ_bits uint64 (or int64), occluded uint8.  None skips an output."""
+        from . import device
+        device.track_job_download_rate_device(self, r, acc, tracked, energy, occ_bits, occluded, s0)
+
+    def download_best_device(self, best, s0=0):
+        """best of segments s0 .. into a contiguous uint8 [ns, gh, gw] device array; also on a job with do_fuse 0"""
+        from . import device
+        device.track_job_download_best_device(self, best, s0)
 
     def run(self, ns=None):
         self.ctx._ck(lib().sfa_track_job_run(self.h_, int(self.n if ns is None else ns)), "sfa_track_job_run")

@@ -141,14 +141,18 @@ int jet_resample_flows(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const f
     return SFA_OK;
 }
 
-int jet_decode_occlusions(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const unsigned char *const *occ, int w, int h, unsigned char *stage, unsigned char *out) {
-    const size_t spl = (size_t)s.sw * s.sh;
-    for (size_t k = 0; k < np; k++)
-        SFA_HIP(ctx, hipMemcpy2DAsync(stage + k * spl, (size_t)s.sw, occ[k], (size_t)s.stride, (size_t)s.sw, s.sh, hipMemcpyHostToDevice, ctx->stream));
+int launch_jet_occ_decode(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const unsigned char *stage, int w, int h, unsigned char *out) {
     const dim3 grid((unsigned)((w + kOccTX - 1) / kOccTX), (unsigned)((h + kOccTY - 1) / kOccTY), (unsigned)std::min<size_t>(np, 65535));
     hipLaunchKernelGGL(k_jet_occ_decode, grid, dim3(kOccTX, kOccTY), 0, ctx->stream, stage, s.sw, s.sh, w, h, 1.0 / (double)s.rescale, (int)np, out);
     SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;
+}
+
+int jet_decode_occlusions(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const unsigned char *const *occ, int w, int h, unsigned char *stage, unsigned char *out) {
+    const size_t spl = (size_t)s.sw * s.sh;
+    for (size_t k = 0; k < np; k++)
+        SFA_HIP(ctx, hipMemcpy2DAsync(stage + k * spl, (size_t)s.sw, occ[k], (size_t)s.stride, (size_t)s.sw, s.sh, hipMemcpyHostToDevice, ctx->stream));
+    return launch_jet_occ_decode(ctx, s, np, stage, w, h, out);
 }
 
 }  // namespace sfa

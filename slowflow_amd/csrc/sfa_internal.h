@@ -200,6 +200,8 @@ int jet_resample_flows(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const
 int jet_decode_occlusions(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const unsigned char *const *occ, int w, int h, unsigned char *stage, unsigned char *out);
 // jet_resample_flows' kernel alone: su, sv are np packed cw x ch planes already in device memory
 int launch_jet_resample(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const float *su, const float *sv, int w, int h, double2 *out);
+// jet_decode_occlusions' kernel alone: stage holds np packed sw x sh images already in device memory
+int launch_jet_occ_decode(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const unsigned char *stage, int w, int h, unsigned char *out);
 
 // ---- dense_tracking's three stages at device level (accumulate.hip, energy.hip, fuse.hip): device pointers and a caller-owned workspace in, launches on the
 // context's stream out; no allocation, no copy, no wait.  The sfa_* entry points wrap them (allocate, upload, call, download, wait), the track job (track.hip)

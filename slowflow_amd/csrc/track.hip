@@ -4,7 +4,7 @@
 //     -> labels -> pairwise -> TRW-S -> output
 // on the context's stream through the stages' device-level functions (sfa_internal.h) and returns: TRW-S's stopping rule lives inside k_trws, so nothing in
 // the chain needs a host decision, and no stage boundary crosses the host.  The flows are brought into the kernels' layout when they are uploaded (host
-// planes: a copy and the stage wrappers' kernels; device memory: the pack kernels below), so a run reads only what the job holds.
+// planes: a copy and the stage wrappers' kernels; device memory: the pack kernels below; occlusion images likewise), so a run reads only what the job holds.
 // Segment s of a run comes out with the bits of the staged calls on that segment alone: the same kernels over the same planes, blockIdx.y = s.
 // The device entry points describe their arguments as views and leave every check of them to check_view / check_disjoint (api.hip on dev_view.h).
 #include <algorithm>
@@ -40,6 +40,26 @@ __global__ void __launch_bounds__(kTrThreads) k_track_pack_planes(const float *_
     const float *b = src + (long long)k * s_step + (long long)(y0 + p / cw) * s_row + (long long)(x0 + p % cw) * s_col;
     su[i] = b[0];
     sv[i] = b[s_c];
+}
+
+// the driver's grey image of an occlusion label (occlusion_image, host/slow_flow.cpp; reference variational_mt.cpp:277-279): (x + 1) / 2 * 255 in fp32 without
+// contraction, nearbyint (halves to even), then std::min(255.0f, .) and std::max(0.0f, .) as written there: NaN -> 255, -Inf -> 0, +Inf -> 255
+__device__ __forceinline__ unsigned char occ_byte(float x) {
+    const float v = (x + 1) * 0.5f * 255.0f, q = nearbyintf(v);
+    const float lo = q < 255.0f ? q : 255.0f;                                   // std::min(255.0f, q)
+    return (unsigned char)(0.0f < lo ? lo : 0.0f);                              // std::max(0.0f, lo)
+}
+__device__ __forceinline__ unsigned char occ_byte(unsigned char x) { return x; }   // the raw image as the occlusion files hold it
+
+// occlusion images of one segment in device memory, element (step, row, column) at src + the strides, raw bytes or fp32 labels -> packed bytes [np][sh][sw],
+// the planes k_jet_occ_decode reads.  One element per thread.
+template <class T>
+__global__ void __launch_bounds__(kTrThreads) k_track_pack_occ(const T *__restrict__ src, long long s_step, long long s_row, long long s_col, int sw, int sh,
+                                                               unsigned char *__restrict__ out, size_t total) {
+    const size_t i = (size_t)blockIdx.x * kTrThreads + threadIdx.x;
+    if (i >= total) return;
+    const size_t spl = (size_t)sw * sh, k = i / spl, p = i % spl;
+    out[i] = occ_byte(src[(long long)k * s_step + (long long)(p / sw) * s_row + (long long)(p % sw) * s_col]);
 }
 
 // fp32 frames, element (segment, frame, channel, row, column) at src + st -> packed planes [seg][nfr][3][h][w], the planes k_energy_records reads
@@ -87,6 +107,29 @@ __global__ void __launch_bounds__(kTrThreads) k_track_unpack(const double *__res
     if (slot_out) slot_out[si] = slot[si];
     if (occ_out) occ_out[si] = occ[si];
     if (stats && i == 0) { stats[3 * s] = seg_energy[s]; stats[3 * s + 1] = seg_bound[s]; stats[3 * s + 2] = (double)seg_iters[s]; }
+}
+
+// rate results of segments s0 .. into the caller's device memory: the last accumulated step (segment, u|v, row, column) at st, and packed tracked, energy,
+// occlusion word and one byte plane (a rate's occluded, or best); every output or null.  The sources come offset to segment s0, one segment a_seg, g_seg,
+// e_seg, b_seg elements after the other
+__global__ void __launch_bounds__(kTrThreads) k_track_unpack_rate(const double *__restrict__ au, const double *__restrict__ av, size_t a_seg,
+                                                                  const int *__restrict__ tracked, size_t g_seg, const double *__restrict__ E,
+                                                                  const unsigned long long *__restrict__ O, size_t e_seg, const unsigned char *__restrict__ bytes,
+                                                                  size_t b_seg, int gw, int gpl, double *__restrict__ acc, long long t_seg, long long t_c,
+                                                                  long long t_row, long long t_col, int *__restrict__ tracked_out, double *__restrict__ energy_out,
+                                                                  unsigned long long *__restrict__ occ_bits_out, unsigned char *__restrict__ bytes_out) {
+    const int i = blockIdx.x * kTrThreads + threadIdx.x;
+    if (i >= gpl) return;
+    const size_t s = blockIdx.y, si = s * gpl + i;
+    if (acc) {
+        double *f = acc + (long long)s * t_seg + (long long)(i / gw) * t_row + (long long)(i % gw) * t_col;
+        f[0] = au[s * a_seg + i];
+        f[t_c] = av[s * a_seg + i];
+    }
+    if (tracked_out) tracked_out[si] = tracked[s * g_seg + i];
+    if (energy_out) energy_out[si] = E[s * e_seg + i];
+    if (occ_bits_out) occ_bits_out[si] = O[s * e_seg + i];
+    if (bytes_out) bytes_out[si] = bytes[s * b_seg + i];
 }
 
 inline unsigned blocks_of(size_t total) { return (unsigned)((total + kTrThreads - 1) / kTrThreads); }
@@ -313,7 +356,6 @@ int sfa_track_job_upload_frames(sfa_track_job *job, int s, const float *const *f
 int sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r, const float *fwd_dev, const float *bwd_dev, const long long strides[5]) {
     TRACK_JOB(job);
     SFA_TRY(track_range(ctx, __func__, p, s0, ns, r));
-    if (p.use_occlusions) REFUSE("%s: the job was created with use_occlusions: its occlusion images come with sfa_track_job_upload_flows", __func__);
     const sfa_jet_source &src = p.source[r];
     const int rJ = p.r_Jets[r];
     SFA_TRY(check_view(ctx, __func__, View{"fwd_dev", fwd_dev, sizeof(float), 5, {ns, rJ, 2, src.sh, src.sw}, strides}));
@@ -339,6 +381,32 @@ int sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r,
             SFA_HIP(ctx, hipGetLastError());
             SFA_TRY(launch_jet_resample(ctx, src, (size_t)rJ, su, sv, p.w, p.h, reinterpret_cast<double2 *>(dst + (size_t)s * seg * tap)));
         }
+    }
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_occlusions_device(sfa_track_job *job, int s0, int ns, int r, const void *occ_dev, int dtype, const long long strides[4]) {
+    TRACK_JOB(job);
+    if (!p.use_occlusions) REFUSE("%s: the job was created without use_occlusions: it holds no occlusion masks", __func__);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, r));
+    if (dtype != SFA_DEV_F32 && dtype != SFA_DEV_U8)
+        REFUSE("%s: dtype %d is %s (fp32 0: the labels sfa_job_download_device leaves; u8 1: the raw images)", __func__, dtype,
+               dtype == SFA_DEV_U16 ? "u16, which occlusion images do not come in" : "no element type");
+    const sfa_jet_source &src = p.source[r];
+    const int rJ = p.r_Jets[r];
+    SFA_TRY(check_view(ctx, __func__, View{"occ_dev", occ_dev, dtype == SFA_DEV_F32 ? sizeof(float) : 1, 4, {ns, rJ, src.sh, src.sw}, strides}));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t total = (size_t)rJ * src.sw * src.sh;                          // segment by segment through the one-segment stage, in stream order
+    unsigned char *stage = job->ptr<unsigned char>(job->at.occ_stage), *mask = job->ptr<unsigned char>(job->at.rate[r].mask) + (size_t)s0 * rJ * pl;
+    for (int s = 0; s < ns; s++) {
+        if (dtype == SFA_DEV_F32)
+            hipLaunchKernelGGL(k_track_pack_occ<float>, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream,
+                               static_cast<const float *>(occ_dev) + (long long)s * strides[0], strides[1], strides[2], strides[3], src.sw, src.sh, stage, total);
+        else
+            hipLaunchKernelGGL(k_track_pack_occ<unsigned char>, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream,
+                               static_cast<const unsigned char *>(occ_dev) + (long long)s * strides[0], strides[1], strides[2], strides[3], src.sw, src.sh, stage, total);
+        SFA_HIP(ctx, hipGetLastError());
+        SFA_TRY(launch_jet_occ_decode(ctx, src, (size_t)rJ, stage, p.w, p.h, mask + (size_t)s * rJ * pl));
     }
     return SFA_OK;
 }
@@ -488,6 +556,51 @@ int sfa_track_job_download_device(sfa_track_job *job, int s0, int ns, double *fl
                        job->ptr<int>(at.seg_iters) + s0, job->gw, (int)gpl, flow_dev, strides[0], strides[1], strides[2], strides[3], slot_dev, occ_dev, stats_dev);
     SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;
+}
+
+// what the two per-rate exits share: the views of the destinations, and k_track_unpack_rate over segments s0 .. (bytes: rate r's occluded, or best)
+static int track_unpack_rate(sfa_track_job *job, const char *fn, int s0, int ns, int r, double *acc_dev, const long long *strides, int *tracked_dev,
+                             double *energy_dev, unsigned long long *occ_bits_dev, unsigned char *bytes_dev, const char *bytes_name, bool best) {
+    TRACK_JOB(job);
+    const long long plane[2] = {(long long)gpl, 1};
+    const View acc{"acc_dev", acc_dev, sizeof(double), 4, {ns, 2, job->gh, job->gw}, strides}, tracked{"tracked_dev", tracked_dev, sizeof(int), 2, {ns, (int)gpl}, plane},
+        energy{"energy_dev", energy_dev, sizeof(double), 2, {ns, (int)gpl}, plane}, bits{"occ_bits_dev", occ_bits_dev, 8, 2, {ns, (int)gpl}, plane},
+        bytes{bytes_name, bytes_dev, 1, 2, {ns, (int)gpl}, plane};
+    if (acc_dev) {
+        SFA_TRY(check_view(ctx, fn, acc));
+        if (!strides_nest(strides, acc.n, 4)) REFUSE("%s: the strides of acc_dev (%lld, %lld, %lld, %lld) let two elements of [%d][2][%d][%d] share an address", fn,
+                                                    strides[0], strides[1], strides[2], strides[3], ns, job->gh, job->gw);
+    }
+    for (const View *v : {&tracked, &energy, &bits, &bytes})
+        if (v->p) SFA_TRY(check_view(ctx, fn, *v));
+    if (!acc_dev && !tracked_dev && !energy_dev && !occ_bits_dev && !bytes_dev) return SFA_OK;
+    SFA_TRY(check_disjoint(ctx, fn, {acc, tracked, energy, bits, bytes}));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const TrackPlanes &at = job->at;
+    const TrackPlanes::Rate &a = at.rate[r];
+    const size_t rJ = p.r_Jets[r], last = ((size_t)s0 * rJ + (rJ - 1)) * gpl, sk = ((size_t)s0 * p.K + r) * gpl;
+    const unsigned char *from = best ? job->ptr<unsigned char>(at.best) + (size_t)s0 * gpl : job->ptr<unsigned char>(at.occluded) + ((size_t)r * p.n + s0) * gpl;
+    const long long none[4] = {0, 0, 0, 0}, *st = acc_dev ? strides : none;
+    hipLaunchKernelGGL(k_track_unpack_rate, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr<double>(a.acc_u) + last,
+                       job->ptr<double>(a.acc_v) + last, rJ * gpl, job->ptr<int>(a.tracked) + (size_t)s0 * gpl, gpl, job->ptr<double>(at.E) + sk,
+                       job->ptr<unsigned long long>(at.O) + sk, (size_t)p.K * gpl, from, gpl, job->gw, (int)gpl, acc_dev, st[0], st[1], st[2], st[3], tracked_dev,
+                       energy_dev, occ_bits_dev, bytes_dev);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+int sfa_track_job_download_rate_device(sfa_track_job *job, int s0, int ns, int r, double *acc_dev, const long long strides[4], int *tracked_dev, double *energy_dev,
+                                       unsigned long long *occ_bits_dev, unsigned char *occluded_dev) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, r));
+    return track_unpack_rate(job, __func__, s0, ns, r, acc_dev, strides, tracked_dev, energy_dev, occ_bits_dev, occluded_dev, "occluded_dev", false);
+}
+
+int sfa_track_job_download_best_device(sfa_track_job *job, int s0, int ns, unsigned char *best_dev) {
+    TRACK_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
+    if (!best_dev) REFUSE("%s: best_dev is null", __func__);
+    return track_unpack_rate(job, __func__, s0, ns, 0, nullptr, nullptr, nullptr, nullptr, nullptr, best_dev, "best_dev", true);
 }
 
 int sfa_track_job_stage_ms(sfa_track_job *job, float ms[8]) {

@@ -23,7 +23,7 @@ import slowflow_amd as sfa
 
 MAX_BATCH = 128                                   # windows of one job (csrc/sfa_internal.h: kMaxBatch)
 DTYPES = {"f4": 0, "u1": 1, "u2": 2}              # sfa_dev_dtype by typestr kind + size
-KIND_NAMES = {"f4": "fp32", "f8": "fp64", "i4": "int32", "u1": "uint8", "u2": "uint16"}
+KIND_NAMES = {"f4": "fp32", "f8": "fp64", "i4": "int32", "i8": "int64", "u1": "uint8", "u2": "uint16", "u8": "uint64"}
 
 
 class DevLayout(C.Structure):
@@ -152,6 +152,9 @@ def _lib():
         L.sfa_track_job_upload_flows_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sfa_track_job_upload_frames_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.sfa_track_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sfa_track_job_upload_occlusions_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.sfa_track_job_download_rate_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.sfa_track_job_download_best_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.sfa_flow_magnitude_quantiles_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                           C.c_float, C.c_float, C.c_void_p]
         _bound = True
@@ -468,16 +471,55 @@ def track_job_download_device(job, flow, slot=None, occ=None, stats=None, s0=0):
     job.ctx._ck(_lib().sfa_track_job_download_device(job.h_, int(s0), ns, C.c_void_p(fv.ptr), _LL4(*fv.strides), *ptrs), "sfa_track_job_download_device")
 
 
-def track(ctx, params, flows, frames, *, stream=None):
+def track_job_upload_occlusions_device(job, r, occ, s0=0):
+    if not 0 <= r < job.K:                          # (the shape below comes from the rate's source)
+        raise sfa.SlowflowError(f"sfa_track_job_upload_occlusions_device: r = {r} names none of the job's {job.K} rates")
+    src, rJ = job.params.source[r], job.params.r_Jets[r]
+    v = device_view(occ, name="occ", kinds=("u1", "f4"), shape=("ns", rJ, src.sh, src.sw))
+    job.ctx._ck(_lib().sfa_track_job_upload_occlusions_device(job.h_, int(s0), v.shape[0], int(r), C.c_void_p(v.ptr), DTYPES[v.kind], _LL4(*v.strides)),
+                "sfa_track_job_upload_occlusions_device")
+
+
+# the packed outputs of a rate, in the C call's order, and their element types (the occlusion word's 64 bits also into an int64 array)
+RATE_OUTPUTS = (("tracked", ("i4",)), ("energy", ("f8",)), ("occ_bits", ("u8", "i8")), ("occluded", ("u1",)))
+
+
+def track_job_download_rate_device(job, r, acc=None, tracked=None, energy=None, occ_bits=None, occluded=None, s0=0):
+    given = [a for a in (acc, tracked, energy, occ_bits, occluded) if a is not None]
+    if not given:
+        raise sfa.SlowflowError("download_rate_device: no output given")
+    ns = int(given[0].shape[0])
+    av = device_view(acc, writable=True, name="acc", kinds=("f8",), shape=(ns, 2, job.gh, job.gw)) if acc is not None else None
+    ptrs = [C.c_void_p(device_view(a, writable=True, name=name, kinds=kinds, shape=(ns, job.gh, job.gw), contiguous=True).ptr) if a is not None else None
+            for a, (name, kinds) in zip((tracked, energy, occ_bits, occluded), RATE_OUTPUTS)]
+    job.ctx._ck(_lib().sfa_track_job_download_rate_device(job.h_, int(s0), ns, int(r), C.c_void_p(av.ptr) if av else None, _LL4(*av.strides) if av else None, *ptrs),
+                "sfa_track_job_download_rate_device")
+
+
+def track_job_download_best_device(job, best, s0=0):
+    v = device_view(best, writable=True, name="best", kinds=("u1",), shape=("ns", job.gh, job.gw), contiguous=True)
+    job.ctx._ck(_lib().sfa_track_job_download_best_device(job.h_, int(s0), v.shape[0], C.c_void_p(v.ptr)), "sfa_track_job_download_best_device")
+
+
+def track(ctx, params, flows, frames, *, occlusions=None, rates=False, stream=None):
     """dense_tracking's accumulation, energies and fusion of ns start_jets whose inputs live on the context's GPU.  params: sfa.track_params(...) with
-    do_fuse 1 and without occlusions, n >= ns; flows = [(fwd_r, bwd_r), ...], one pair of fp32 tensors [ns, r_Jets[r], 2, sh, sw] per rate; frames = an
-    fp32 tensor [ns, Jets + 1, 3, h, w] of normalised frames; any strides with a positive column stride.  Returns (flow [ns,2,gh,gw] float64, slot
-    [ns,gh,gw] int32, occ [ns,gh,gw] uint8, stats [ns,3] float64: energy, bound, iterations) as new tensors on that device.  The work is ordered after what
-    `stream` (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues (a job of new
+    do_fuse 1, n >= ns; flows = [(fwd_r, bwd_r), ...], one pair of fp32 tensors [ns, r_Jets[r], 2, sh, sw] per rate; frames = an fp32 tensor
+    [ns, Jets + 1, 3, h, w] of normalised frames; any strides with a positive column stride.  occlusions: with params.use_occlusions one tensor
+    [ns, r_Jets[r], sh, sw] per rate, uint8 (the raw occlusion images) or fp32 (the labels refine() returns as occ, turned into the driver's grey image);
+    refused without it.  Returns (flow [ns,2,gh,gw] float64, slot [ns,gh,gw] int32, occ [ns,gh,gw] uint8, stats [ns,3] float64: energy, bound, iterations)
+    as new tensors on that device; with rates=True a fifth value, dict(rate=[one dict per rate of new tensors acc float64 [ns,2,gh,gw] (the last
+    accumulated step), tracked int32, energy float64 (+Inf: no hypothesis), occ_bits uint64, occluded uint8 [ns,gh,gw]], best=uint8 [ns,gh,gw]): what
+    TrackJob.download_rate and download_best give.  The work is ordered after what `stream` (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues (a job of new
     parameters is created first, which waits).  The job stays on the context for the next call (ctx.close() frees it)."""
     import torch
     if len(flows) != params.K:
         raise sfa.SlowflowError(f"flows: {len(flows)} (fwd, bwd) pairs for {params.K} rates")
+    if params.use_occlusions and occlusions is None:
+        raise sfa.SlowflowError("occlusions: None, but params.use_occlusions is set: one tensor of occlusion images per rate")
+    if occlusions is not None and not params.use_occlusions:
+        raise sfa.SlowflowError("occlusions: given, but params.use_occlusions is 0: the job would not read them")
+    if occlusions is not None and len(occlusions) != params.K:
+        raise sfa.SlowflowError(f"occlusions: {len(occlusions)} tensors for {params.K} rates")
     fv = device_view(frames, name="frames", kinds=("f4",), shape=("ns", params.Jets + 1, 3, params.h, params.w))   # every view is checked before a job is created or anything uploaded
     ns = fv.shape[0]
     if not 1 <= ns <= params.n:
@@ -486,16 +528,31 @@ def track(ctx, params, flows, frames, *, stream=None):
         src = params.source[r]
         for a, nm in ((fwd, "flows[%d] fwd" % r), (bwd, "flows[%d] bwd" % r)):
             device_view(a, name=nm, kinds=("f4",), shape=(ns, params.r_Jets[r], 2, src.sh, src.sw))
+        if occlusions is not None:
+            device_view(occlusions[r], name="occlusions[%d]" % r, kinds=("u1", "f4"), shape=(ns, params.r_Jets[r], src.sh, src.sw))
     job = _cached_job(ctx, "_track_jobs", bytes(params), lambda: sfa.TrackJob(ctx, params))     # creating a job waits for the context's stream: before the bracket
+    g = (ns, job.gh, job.gw)
     def outputs(dev):
-        return (torch.empty((ns, 2, job.gh, job.gw), dtype=torch.float64, device=dev), torch.empty((ns, job.gh, job.gw), dtype=torch.int32, device=dev),
-                torch.empty((ns, job.gh, job.gw), dtype=torch.uint8, device=dev), torch.empty((ns, 3), dtype=torch.float64, device=dev))
+        out = (torch.empty((ns, 2, job.gh, job.gw), dtype=torch.float64, device=dev), torch.empty(g, dtype=torch.int32, device=dev),
+               torch.empty(g, dtype=torch.uint8, device=dev), torch.empty((ns, 3), dtype=torch.float64, device=dev))
+        if not rates:
+            return out
+        rate = [dict(acc=torch.empty((ns, 2, job.gh, job.gw), dtype=torch.float64, device=dev), tracked=torch.empty(g, dtype=torch.int32, device=dev),
+                     energy=torch.empty(g, dtype=torch.float64, device=dev), occ_bits=torch.empty(g, dtype=torch.uint64, device=dev),
+                     occluded=torch.empty(g, dtype=torch.uint8, device=dev)) for _ in range(params.K)]
+        return out + (dict(rate=rate, best=torch.empty(g, dtype=torch.uint8, device=dev)),)
     with on_stream(torch, ctx, frames, stream, outputs) as (_, out):
         for r, (fwd, bwd) in enumerate(flows):
             track_job_upload_flows_device(job, r, fwd, bwd)
+            if occlusions is not None:
+                track_job_upload_occlusions_device(job, r, occlusions[r])
         track_job_upload_frames_device(job, frames)
         job.run(ns)
-        track_job_download_device(job, *out)
+        track_job_download_device(job, *out[:4])
+        if rates:
+            for r, d in enumerate(out[4]["rate"]):
+                track_job_download_rate_device(job, r, d["acc"], d["tracked"], d["energy"], d["occ_bits"], d["occluded"])
+            track_job_download_best_device(job, out[4]["best"])
     return out
 
 

@@ -8,7 +8,16 @@
       Each measurement runs in a child process of its own, the staged ones alternating with the job's.  --parent-lib: a build of the parent commit's
       library (the same C-ABI without the track job), loaded by the staged children through SFA_LIB: the baseline, measured three times, each time
       followed by the same sequence on this tree's library, so that the refactored wrappers are compared within the parent's own spread.  Without it
-      the staged sequence runs on this tree's library only.  Writes FILE (profiles/track_bench.txt)."""
+      the staged sequence runs on this tree's library only.  Writes FILE (profiles/track_bench.txt).
+
+  bench_track.py --occlusions [--parent-lib FILE] [--out FILE]
+      The same job with use_occlusions (one rectangle of 255 per occlusion image), at B = 1, 4 and 16, wall time per start_jet as above, with the inputs
+      (a) as host planes through upload_flows(occ=) and (b) with the flows and the 8-bit occlusion images already in GPU memory (torch tensors, one
+      start_jet's repeated B times through a zero segment stride) through upload_flows_device and upload_occlusions_device.  The frames come from the
+      host and the results go to the host in both.  Three repetitions that alternate (a) and (b), each measurement a process of its own; after its
+      timed runs a child times the uploads alone (to a synchronise).  --parent-lib: (a) also on the parent commit's library, in the same alternation:
+      the comparison point.  Writes FILE (profiles/track_occlusions_device.txt) with the medians, the ranges and the sha256 of each library."""
+import hashlib
 import json
 import os
 import subprocess
@@ -92,6 +101,92 @@ def child_job(B):
                           hypotheses=float(np.mean([np.isfinite(q["energy"]).mean() for q in rates])), bytes=sfa.track_job_bytes(p))))
 
 
+def occlusion_images():
+    """per rate raw uint8 images (r_Jets, H, W): one 128 x 64 rectangle of 255 per step, seeded"""
+    rng = np.random.default_rng(1)
+    out = []
+    for rJ in R_JETS:
+        o = np.zeros((rJ, H, W), np.uint8)
+        for k in range(rJ):
+            x0, y0 = int(rng.integers(0, W - 128)), int(rng.integers(0, H - 64))
+            o[k, y0:y0 + 64, x0:x0 + 128] = 255
+        out.append(o)
+    return out
+
+
+def child_occlusions(route, B):
+    if route == "device":
+        import torch                                # before the library is loaded, as the other tools do: one HIP runtime in the process
+    import slowflow_amd as sfa
+    ctx = sfa.Context(0)
+    flows, frames = inputs()
+    occ = occlusion_images()
+    p = sfa.track_params(W, H, JETS, R_JETS, n=B, sources=[sfa.jet_source(W, H, W)] * 2, skip=SKIP, use_occlusions=1)
+    job = sfa.TrackJob(ctx, p)
+    if route == "device":
+        dev = torch.device("cuda", 0)
+        t_flows = [tuple(torch.from_numpy(np.stack([f[a], f[a + 1]], 1)).to(dev)[None].expand(B, -1, -1, -1, -1) for a in (0, 2)) for f in flows]
+        t_occ = [torch.from_numpy(o).to(dev)[None].expand(B, -1, -1, -1) for o in occ]
+        torch.cuda.synchronize()
+
+    def uploads():
+        if route == "device":
+            for r in range(2):
+                job.upload_flows_device(r, *t_flows[r])
+                job.upload_occlusions_device(r, t_occ[r])
+        for s in range(B):
+            if route == "host":
+                for r in range(2):
+                    job.upload_flows(s, r, *flows[r], occ=occ[r])
+            job.upload_frames(s, frames)
+
+    per = []
+    for _ in range(REPS + 1):
+        ctx.sync()
+        t0 = time.perf_counter()
+        uploads()
+        job.run(B)
+        for s in range(B):
+            rates = [job.download_rate(s, r) for r in range(2)]
+            fused = job.download_fused(s)
+        ctx.sync()
+        per.append(1e3 * (time.perf_counter() - t0) / B)
+    ctx.sync()
+    t0 = time.perf_counter()
+    uploads()
+    ctx.sync()
+    up = 1e3 * (time.perf_counter() - t0) / B
+    print(json.dumps(dict(per_start_ms=float(np.median(per[1:])), upload_ms=up, stage_ms=job.stage_ms(), iters=int(fused["iters"]),
+                          tracked=[float((q["tracked"] > 0).mean()) for q in rates], sha256=hashlib.sha256(open(sfa.LIB_PATH, "rb").read()).hexdigest())))
+
+
+def main_occlusions(out, parent):
+    routes = ([("parent", "host", parent)] if parent else []) + [("a", "host", None), ("b", "device", None)]
+    got = {(name, B): [] for name, _, _ in routes for B in (1, 4, 16)}
+    for rep in range(3):
+        for B in (1, 4, 16):
+            for name, route, lib in routes:
+                got[name, B].append(spawn(["--child-occlusions", route, str(B)], lib))
+                print("repetition %d, B = %d, %s: %s" % (rep, B, name, got[name, B][-1]), flush=True)
+    first = got["a", 1][0]
+    lines = ["# tools/bench_track.py --occlusions on one MI355X (gfx950); %d x %d, acc_skip_pixel %d, K 2, Jets %d, r_Jets %s, use_occlusions 1, default keys; tracked at %s of the grid pixels, %d TRW-S iterations"
+             % (W, H, SKIP, JETS, R_JETS, " / ".join("%.1f %%" % (100 * t) for t in first["tracked"]), first["iters"]),
+             "# wall time per start_jet from the first upload to the last download, frames from the host and results to the host; each figure the median of %d runs after a warm-up in a process of its own;" % REPS,
+             "# three such processes per row, alternating: (a) flows and occlusion images as host planes (upload_flows(occ=)), (b) flows and 8-bit occlusion images already in GPU memory",
+             "# (upload_flows_device + upload_occlusions_device)%s; upload_ms: the uploads alone up to a synchronise, per start_jet" % ("; parent: (a) on the parent commit's library" if parent else ""),
+             "# library sha256: this tree %s%s" % (first["sha256"], "; parent %s" % got["parent", 1][0]["sha256"] if parent else ""),
+             "#  route   B  per_start_ms median (min .. max)   upload_ms median (min .. max)"]
+    for B in (1, 4, 16):
+        for name, _, _ in routes:
+            v, u = [g["per_start_ms"] for g in got[name, B]], [g["upload_ms"] for g in got[name, B]]
+            lines.append("%8s %3d %12.2f (%.2f .. %.2f) %16.2f (%.2f .. %.2f)" % (name, B, float(np.median(v)), min(v), max(v), float(np.median(u)), min(u), max(u)))
+        a, b = [float(np.median([g["per_start_ms"] for g in got[n, B]])) for n in ("a", "b")]
+        lines.append("#        B = %d: (b) / (a) = %.3f" % (B, b / a))
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def spawn(args, lib=None):
     env = dict(os.environ)
     if lib:
@@ -108,11 +203,15 @@ def main():
         return child_staged()
     if args[:1] == ["--child-job"]:
         return child_job(int(args[1]))
-    out, parent = os.path.join(ROOT, "profiles", "track_bench.txt"), None
+    if args[:1] == ["--child-occlusions"]:
+        return child_occlusions(args[1], int(args[2]))
+    out, parent = os.path.join(ROOT, "profiles", "track_occlusions_device.txt" if "--occlusions" in args else "track_bench.txt"), None
     if "--out" in args:
         out = args[args.index("--out") + 1]
     if "--parent-lib" in args:
         parent = os.path.abspath(args[args.index("--parent-lib") + 1])
+    if "--occlusions" in args:
+        return main_occlusions(out, parent)
     base, ours, jobs = [], [], {}
     for B in (1, 4, 16):                                            # alternating: the parent's staged sequence, this tree's, the job
         base.append(spawn(["--child-staged"], parent))
