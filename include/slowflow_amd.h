@@ -402,6 +402,10 @@ int sfa_occlusion_costs(sfa_ctx *ctx, const sfa_params *p, float *d0, float *d1,
 /* optimizeOcc, second half (:868-880): occ[p] = 2*l_p - 1 for the labelling that minimises sum_p D_{l_p}(p) + alpha * #{4-neighbour
  * pairs with different labels} -- what GCO's two-label expansion computes; exact s-t minimum cut on the GPU. */
 int sfa_grid_cut(sfa_ctx *ctx, float *occ, const float *d0, const float *d1, int w, int h, int stride, float alpha);
+/* the same cut (variational_aux_mt.cpp:868-880) of nb independent windows in the launches a lockstep batch of jobs shares: occ, d0, d1 are nb planes of
+ * h x stride each, window after window; 1 <= nb <= 128.  Each window gets the labels sfa_grid_cut gives it alone.  A refusal (SFA_ERR_ARG) names the
+ * argument and launches nothing. */
+int sfa_grid_cut_batch(sfa_ctx *ctx, float *occ, const float *d0, const float *d1, int nb, int w, int h, int stride, float alpha);
 
 /* Variational_AUX_MT::image_warp (variational_aux_mt.cpp:722-756); mask may be NULL */
 int sfa_image_warp(sfa_ctx *ctx, float *dst3, float *mask, const float *src3, const float *wx, const float *wy,

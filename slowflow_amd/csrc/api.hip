@@ -424,14 +424,33 @@ int sfa_occlusion_costs(sfa_ctx *ctx, const sfa_params *p, float *d0, float *d1,
     return sfa_ctx_sync(ctx);
 }
 
-int sfa_grid_cut(sfa_ctx *ctx, float *occ, const float *d0, const float *d1, int w, int h, int stride, float alpha) {
-    CHECK_ARGS(ctx && occ && d0 && d1 && w > 0 && h > 0 && stride >= w && alpha >= 0, "bad arguments");
+// The cut of nb windows in the launches the job uses (optimize_occlusions, job.hip): cost and work planes packed [nb][pl]; the label planes sit in slots of
+// 2 pl, as the job's sit L.es apart -- the label stride is not the plane stride.  Staged planes: [0, 2nb) label slots, then nb d0, nb d1, the work planes.
+static int grid_cut_staged(sfa_ctx *ctx, const char *fn, float *occ, const float *d0, const float *d1, int nb, int w, int h, int stride, float alpha) {
+    CHECK_ARGS_FN(fn, ctx, "ctx is null");
+    CHECK_ARGS_FN(fn, nb >= 1 && nb <= kMaxBatch, "nb out of range (1 .. 128 windows)");
+    CHECK_ARGS_FN(fn, occ, "occ is null");
+    CHECK_ARGS_FN(fn, d0, "d0 is null");
+    CHECK_ARGS_FN(fn, d1, "d1 is null");
+    CHECK_ARGS_FN(fn, w > 0 && h > 0, "w and h must be positive");
+    CHECK_ARGS_FN(fn, stride >= w, "stride is smaller than w");
+    CHECK_ARGS_FN(fn, alpha >= 0, "alpha is negative (or not a number)");
     Staging s;
-    SFA_TRY(s.init(ctx, w, h, 3 + kCutWorkPlanes));
-    SFA_TRY(s.up(1, d0, stride)); SFA_TRY(s.up(2, d1, stride));
-    SFA_TRY(run_grid_cut(ctx, s.geo(), s.plane(0), 0, s.plane(1), s.plane(2), s.plane(3), alpha));
-    SFA_TRY(s.down(occ, stride, 0));
+    SFA_TRY(s.init(ctx, w, h, nb * (4 + kCutWorkPlanes)));
+    const size_t hp = (size_t)stride * h;                        // one host plane
+    const int i_d0 = 2 * nb, i_d1 = 3 * nb, i_work = 4 * nb;
+    for (int b = 0; b < nb; b++) { SFA_TRY(s.up(i_d0 + b, d0 + b * hp, stride)); SFA_TRY(s.up(i_d1 + b, d1 + b * hp, stride)); }
+    Geo g = s.geo();
+    g.es = s.pl; g.nb = nb; g.active = WMask::first(nb);
+    SFA_TRY(run_grid_cut(ctx, g, s.plane(0), 2 * s.pl, s.plane(i_d0), s.plane(i_d1), s.plane(i_work), alpha));
+    for (int b = 0; b < nb; b++) SFA_TRY(s.down(occ + b * hp, stride, 2 * b));
     return sfa_ctx_sync(ctx);
+}
+int sfa_grid_cut(sfa_ctx *ctx, float *occ, const float *d0, const float *d1, int w, int h, int stride, float alpha) {
+    return grid_cut_staged(ctx, __func__, occ, d0, d1, 1, w, h, stride, alpha);
+}
+int sfa_grid_cut_batch(sfa_ctx *ctx, float *occ, const float *d0, const float *d1, int nb, int w, int h, int stride, float alpha) {
+    return grid_cut_staged(ctx, __func__, occ, d0, d1, nb, w, h, stride, alpha);
 }
 
 int sfa_add_data_and_match(sfa_ctx *ctx, float *a11, float *a12, float *a22, float *b1, float *b2, const float *mask, const float *du, const float *dv,

@@ -9,6 +9,7 @@ import pytest
 
 import oracle as orc
 import slowflow_amd as sfa
+from cut_inputs import cut_case as _cut_case
 from synth import copy_sys, noise_color, noise_plane, smooth_noise_color, sor_system, texture_frame
 
 pytestmark = pytest.mark.gpu
@@ -959,24 +960,6 @@ def test_occlusion_costs(ctx, oracle, pid, S, w, h):
             assert ulp.max() <= 1 and (ulp > 0).mean() < 1e-3
         else:
             assert np.array_equal(valid(a, w), valid(b, w))
-
-
-def _cut_case(rng, w, h, kind):
-    st = sfa.stride_of(w)
-    d0, d1 = np.zeros((h, st), np.float32), np.zeros((h, st), np.float32)
-    if kind == "noise":
-        d0[:, :w] = rng.uniform(0, 2, (h, w)); d1[:, :w] = rng.uniform(0, 2, (h, w))
-    elif kind == "blobs":       # the typical shape: label 0 preferred everywhere except in a few compact regions
-        d0[:, :w] = rng.uniform(0, 0.2, (h, w)); d1[:, :w] = 1.0 + rng.uniform(0, 0.2, (h, w))
-        for _ in range(6):
-            cx, cy, r = rng.integers(0, w), rng.integers(0, h), rng.integers(2, 9)
-            yy, xx = np.mgrid[0:h, 0:w]
-            d0[:, :w][(xx - cx) ** 2 + (yy - cy) ** 2 <= r * r] += rng.uniform(1.0, 4.0)
-    else:                       # "stripes": long thin structures, long residual paths
-        d0[:, :w] = 0.1; d1[:, :w] = 0.6
-        d0[::7, :w] += 3.0; d1[3::7, :w] += 3.0
-        d0[:, :w] += rng.uniform(0, 0.05, (h, w))
-    return d0, d1
 
 
 @pytest.mark.parametrize("kind", ["noise", "blobs", "stripes"])
