@@ -429,7 +429,8 @@ int sfa_add_data_and_match(sfa_ctx *ctx, float *a11, float *a12, float *a22, flo
                            const float *du, const float *dv, const float *D8x3, const float *const chw[3],
                            int w, int h, int stride, float delta_over3, float gamma_over3, float s, int ref_term,
                            int dt_norm, const sfa_penalty *color, const sfa_penalty *grad);
-/* pyramid arithmetic (cv::GaussianBlur / cv::resize as used at variational_mt.cpp:607,611,672,711) */
+/* pyramid arithmetic (cv::GaussianBlur / cv::resize as used at variational_mt.cpp:607,611,672,711); sfa_gaussian_blur: sigma * 8 + 1 < 33 (at most 33 taps,
+ * radius 16), SFA_ERR_ARG beyond */
 int sfa_gaussian_blur(sfa_ctx *ctx, float *dst, const float *src, int w, int h, int stride, float sigma);
 int sfa_resize_linear(sfa_ctx *ctx, float *dst, int dw, int dh, int dstride, const float *src, int sw, int sh, int sstride);
 /* optional presmoothing of level 0 (cfg `sigma` > 0, variational_mt.cpp:590-597): gaussian_filter (image.c:310-348) through
@@ -461,7 +462,9 @@ int  sfa_sequence_apply_normalization(sfa_sequence *seq, int f0, int n, const do
 
 /* ---- device-resident batches (measurement and the multi-pair driver) ------------------------------
  * A job = `batch` independent frame windows of identical size solved in lockstep by the same launches
- * (forward + backward of a jet, several jets ...), all inputs resident in HBM. */
+ * (forward + backward of a jet, several jets ...), all inputs resident in HBM.
+ * sfa_job_create refuses (SFA_ERR_ARG, naming p_scale) a p_scale that is NaN, <= 0 or > 1, or whose pyramid blur sigma = 1 / sqrt(2 p_scale) needs more
+ * than the 33 taps the blur kernels carry (p_scale below about 0.03). */
 typedef struct sfa_job sfa_job;
 int  sfa_job_create(sfa_ctx *ctx, const sfa_params *p, int w, int h, int batch, sfa_job **out);
 void sfa_job_destroy(sfa_job *job);
@@ -601,6 +604,21 @@ int  sfa_ctx_set_verbose(sfa_ctx *ctx, int on);
  * switch SFA_PAIR_UNFUSED=1 (sfa_debug_set) makes a pair job run the stored derivative stack and k_data_2f instead of k_data_2f_fused, on a stack it
  * allocates at the first such run: the parity test compares the two systems plane by plane. */
 int  sfa_pair_job_download_system(sfa_pair_job *job, int b, float *a11, float *a12, float *a22, float *b1, float *b2, int stride);
+
+/* ---- test hooks: the pyramid, stage by stage ------------------------------------------------------------------------------------------
+ * sfa_pyramid_down: one pyramid step (cv::GaussianBlur(sigma) then cv::resize to dw x dh, variational_mt.cpp:607,611) of nb windows of nplanes planes each,
+ * host planes src[nb][nplanes][sh][sstride] -> dst[nb][nplanes][dh][dstride], through the function sfa_job_run's pyramid calls per level: k_pyr_down where
+ * its footprint fits LDS and the radius is at most 8, else k_gauss_h / k_gauss_v + k_resize; SFA_PYRAMID_UNFUSED=1 (sfa_debug_set) forces the latter.
+ * info (may be NULL) = {1 if k_pyr_down ran else 0, its tile height td, its LDS bytes}.  sigma as for sfa_gaussian_blur: at most 33 taps.
+ * sfa_resize_flow: the flow's hand-over between two levels (variational_mt.cpp:672-680, 711-717; k_resize_flow): nb fields, host planes swx, swy
+ * [nb][sh][sstride] -> dwx, dwy [nb][dh][dstride], resized like sfa_resize_linear and multiplied by post_x / post_y.
+ * sfa_job_download_level_frame: the 3 planes of frame f (0 .. 2 (S - 1)) of window b at pyramid level `level` as the last sfa_job_run left them
+ * (level 0: the uploaded frame, presmoothed if the cfg's sigma > 0), host rows of `stride` >= the level's width floats; waits for the stream. */
+int  sfa_pyramid_down(sfa_ctx *ctx, float *dst, int dw, int dh, int dstride, const float *src, int sw, int sh, int sstride, int nplanes, int nb, float sigma,
+                      int info[3]);
+int  sfa_resize_flow(sfa_ctx *ctx, float *dwx, float *dwy, int dw, int dh, int dstride, const float *swx, const float *swy, int sw, int sh, int sstride, int nb,
+                     float post_x, float post_y);
+int  sfa_job_download_level_frame(sfa_job *job, int b, int level, int f, float *frame3, int stride);
 
 /* ---- test hook: the division of the normalised data terms --------------------------------------------------------------------
  * The cfg-default instance of the fused assembly kernel forms the quotients r^2 / n and t / n of variational_aux_mt.cpp:240-250, 333-347, 479-490, 556-572

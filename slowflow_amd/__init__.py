@@ -171,6 +171,7 @@ EXPORTS = [
     "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_grid_cut_batch", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
+    "sfa_pyramid_down", "sfa_resize_flow", "sfa_job_download_level_frame",
     "sfa_sequence_create", "sfa_sequence_destroy", "sfa_sequence_upload", "sfa_sequence_download", "sfa_sequence_normalize", "sfa_sequence_frame_sums", "sfa_normalize_statistics", "sfa_sequence_apply_normalization",
     "sfa_job_create", "sfa_job_destroy", "sfa_job_upload", "sfa_job_upload_resident", "sfa_job_reset_flow", "sfa_job_run", "sfa_job_download", "sfa_job_download_occlusions", "sfa_job_keep_alternation_occlusions", "sfa_job_download_alternation_occlusions", "sfa_job_mpix_iters", "sfa_job_device_bytes",
     "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_pair_job_upload_device", "sfa_pair_job_set_flow_device", "sfa_pair_job_download_device", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
@@ -414,6 +415,30 @@ class Context:
         dst = np.zeros((dh, stride_of(dw)), np.float32)
         self._ck(lib().sfa_resize_linear(self.h, fptr(dst), dw, dh, stride_of(dw), fptr(src), sw, sh, sstride), "sfa_resize_linear")
         return dst
+
+    def pyramid_down(self, src, sw, dw, dh, sigma):
+        """test hook (sfa_pyramid_down): one pyramid step -- blur with sigma, resize to dw x dh -- of src (nb, nplanes, sh, sstride) through the function the
+        job's pyramid runs per level.  Returns (dst (nb, nplanes, dh, stride_of(dw)), (fused, td, lds_bytes)): what k_pyr_down ran with, (0, 0, 0) for the two kernels"""
+        nb, nplanes, sh, sstride = src.shape
+        dst = np.zeros((nb, nplanes, dh, stride_of(dw)), np.float32)
+        info = (C.c_int * 3)()
+        L = lib()
+        L.sfa_pyramid_down.argtypes = [C.c_void_p, _f, C.c_int, C.c_int, C.c_int, _f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int)]
+        self._ck(L.sfa_pyramid_down(self.h, fptr(dst), int(dw), int(dh), stride_of(dw), fptr(src), int(sw), sh, sstride, nplanes, nb, float(sigma), info),
+                 "sfa_pyramid_down")
+        return dst, tuple(info)
+
+    def resize_flow(self, wx, wy, sw, dw, dh, post_x, post_y):
+        """test hook (sfa_resize_flow): the flow's hand-over between pyramid levels (k_resize_flow) on nb fields wx, wy (nb, sh, sstride): resized to dw x dh and
+        multiplied by post_x / post_y.  Returns (wx, wy), (nb, dh, stride_of(dw)) each"""
+        nb, sh, sstride = wx.shape
+        assert wy.shape == wx.shape
+        ox, oy = np.zeros((nb, dh, stride_of(dw)), np.float32), np.zeros((nb, dh, stride_of(dw)), np.float32)
+        L = lib()
+        L.sfa_resize_flow.argtypes = [C.c_void_p, _f, _f, C.c_int, C.c_int, C.c_int, _f, _f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+        self._ck(L.sfa_resize_flow(self.h, fptr(ox), fptr(oy), int(dw), int(dh), stride_of(dw), fptr(wx), fptr(wy), int(sw), sh, sstride, nb, float(post_x),
+                                   float(post_y)), "sfa_resize_flow")
+        return ox, oy
 
     def gaussian_presmooth(self, src, w, sigma):
         h, stride = src.shape
@@ -702,6 +727,7 @@ class Job:
     def __init__(self, ctx, params, w, h, batch=1):
         self.ctx, self.w, self.h, self.batch = ctx, w, h, batch
         self.n_frames = 2 * (params.S - 1) + 1
+        self.layers, self.p_scale = params.layers, params.p_scale
         self.h_ = C.c_void_p()
         ctx._ck(lib().sfa_job_create(ctx.h, C.byref(params), w, h, batch, C.byref(self.h_)), "sfa_job_create")
         ctx._children.add(self)
@@ -763,6 +789,19 @@ class Job:
         occ = np.zeros((self.h, stride), np.float32)
         self.ctx._ck(lib().sfa_job_download_occlusions(self.h_, b, fptr(occ), stride), "sfa_job_download_occlusions")
         return occ
+
+    def download_level_frame(self, b, level, f, size=None, stride=None):
+        """test hook (sfa_job_download_level_frame): frame f of window b at pyramid level `level` as the last run left it, (3, h_level, stride);
+        size = (w, h) of the level (default: pyramid_sizes of the job's parameters), stride default stride_of(w)"""
+        if size is None:
+            ws, hs = pyramid_sizes(self.w, self.h, self.layers, self.p_scale)
+            size = (ws[level], hs[level]) if 0 <= level < len(ws) else (self.w, self.h)
+        stride = stride_of(size[0]) if stride is None else stride
+        out = np.zeros((3, size[1], max(stride, 1)), np.float32)
+        L = lib()
+        L.sfa_job_download_level_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _f, C.c_int]
+        self.ctx._ck(L.sfa_job_download_level_frame(self.h_, int(b), int(level), int(f), fptr(out), int(stride)), "sfa_job_download_level_frame")
+        return out
 
     def keep_alternation_occlusions(self, on=True):
         self.ctx._ck(lib().sfa_job_keep_alternation_occlusions(self.h_, int(on)), "sfa_job_keep_alternation_occlusions")

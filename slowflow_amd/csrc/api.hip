@@ -92,8 +92,10 @@ static int check_device_error(sfa_ctx *c) {
 }
 
 // cv::getGaussianKernel(ksize, sigma, CV_32F) with ksize = cvRound(sigma*8+1)|1 (cv::GaussianBlur, Size(0,0), CV_32F)
-int cv_gauss_taps(float sigma, float *k) {
+int cv_gauss_taps(float sigma, float k[kMaxBlurTaps]) {
+    if (!(sigma > 0) || !((double)sigma * 4 * 2 + 1 < 2 * kMaxBlurTaps)) return -1;     // (NaN, inf and what lrint could not hold end here)
     const int ksize = ((int)lrint((double)sigma * 4 * 2 + 1)) | 1;
+    if (ksize > kMaxBlurTaps) return -1;
     const double scale2X = -0.5 / ((double)sigma * sigma);
     double sum = 0;
     for (int i = 0; i < ksize; i++) {
@@ -483,13 +485,14 @@ int sfa_add_data_and_match(sfa_ctx *ctx, float *a11, float *a12, float *a22, flo
 
 int sfa_gaussian_blur(sfa_ctx *ctx, float *dst, const float *src, int w, int h, int stride, float sigma) {
     CHECK_ARGS(ctx && dst && src && w > 0 && h > 0 && stride >= w && sigma > 0, "bad arguments");
-    float taps[64];
+    float taps[kMaxBlurTaps];
     CHECK_ARGS(sigma * 8 + 1 < 33, "sigma too large");
     const int r = cv_gauss_taps(sigma, taps);
+    CHECK_ARGS(r >= 0, "sigma too large");
     Staging s;
     SFA_TRY(s.init(ctx, w, h, 3));
     SFA_TRY(s.up(0, src, stride));
-    launch_gauss_blur(ctx, s.geo(), s.plane(1), s.plane(2), s.plane(0), 1, taps, r);
+    SFA_TRY(launch_gauss_blur(ctx, s.geo(), s.plane(1), s.plane(2), s.plane(0), 1, taps, r));
     SFA_TRY(s.down(dst, stride, 1));
     return sfa_ctx_sync(ctx);
 }
@@ -527,6 +530,57 @@ int sfa_resize_linear_fx(sfa_ctx *ctx, float *dst, int dw, int dh, int dstride, 
     SFA_TRY(upload_plane(ctx, a.f(), sp, src, sstride, sw, sh));
     launch_resize_scaled(ctx, b.f(), dw, dh, dp, (long)dp * dh, 0, a.f(), sw, sh, sp, (long)sp * sh, 0, 1, 1, 1.0f, 1.0 / fx, 1.0 / fy);
     SFA_TRY(download_plane(ctx, dst, dstride, b.f(), dp, dw, dh));
+    return sfa_ctx_sync(ctx);
+}
+
+// test hook: one pyramid step as sfa_job_run's pyramid takes it (pyramid_step, kernels.hip) on host planes: src[nb][nplanes][sh][sstride] -> dst[nb][nplanes][dh][dstride]
+int sfa_pyramid_down(sfa_ctx *ctx, float *dst, int dw, int dh, int dstride, const float *src, int sw, int sh, int sstride, int nplanes, int nb, float sigma,
+                     int info[3]) {
+    CHECK_ARGS(ctx && dst && src && dw > 0 && dh > 0 && sw > 0 && sh > 0 && dstride >= dw && sstride >= sw, "bad arguments");
+    CHECK_ARGS(nb >= 1 && nb <= kMaxBatch && nplanes >= 1 && (long)nb * nplanes <= 65535, "nb x nplanes out of range");
+    float taps[kMaxBlurTaps];
+    const int r = cv_gauss_taps(sigma, taps);
+    if (r < 0) REFUSE("%s: sigma = %g: not a positive number, or a blur of more than %d taps", __func__, (double)sigma, kMaxBlurTaps);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    DevMem a, b;
+    const int sp = dev_pitch(sw), dp = dev_pitch(dw);
+    const long spl = (long)sp * sh, dpl = (long)dp * dh, ses = (nplanes + 6) * spl, des = nplanes * dpl;   // a window: its planes, then pyramid_step's scratch
+    SFA_TRY(a.alloc(ctx, (size_t)nb * ses * sizeof(float))); SFA_TRY(b.alloc(ctx, (size_t)nb * des * sizeof(float)));
+    SFA_HIP(ctx, hipMemsetAsync(a.p, 0, (size_t)nb * ses * sizeof(float), ctx->stream));
+    SFA_HIP(ctx, hipMemsetAsync(b.p, 0, (size_t)nb * des * sizeof(float), ctx->stream));
+    for (int i = 0; i < nb; i++)
+        for (int k = 0; k < nplanes; k++)
+            SFA_TRY(upload_plane(ctx, a.f() + i * ses + k * spl, sp, src + ((size_t)i * nplanes + k) * sstride * sh, sstride, sw, sh));
+    PyrInfo pi;
+    SFA_TRY(pyramid_step(ctx, b.f(), dw, dh, dp, dpl, des, a.f(), sw, sh, sp, spl, ses, nplanes, nb, taps, r, a.f() + nplanes * spl, &pi));
+    for (int i = 0; i < nb; i++)
+        for (int k = 0; k < nplanes; k++)
+            SFA_TRY(download_plane(ctx, dst + ((size_t)i * nplanes + k) * dstride * dh, dstride, b.f() + i * des + k * dpl, dp, dw, dh));
+    if (info) { info[0] = pi.fused; info[1] = pi.td; info[2] = pi.lds; }
+    return sfa_ctx_sync(ctx);
+}
+
+// test hook: launch_resize_flow -- the flow's way from one pyramid level to the next, both planes, times post_x / post_y -- on host planes [nb][h][stride]
+int sfa_resize_flow(sfa_ctx *ctx, float *dwx, float *dwy, int dw, int dh, int dstride, const float *swx, const float *swy, int sw, int sh, int sstride, int nb,
+                    float post_x, float post_y) {
+    CHECK_ARGS(ctx && dwx && dwy && swx && swy && dw > 0 && dh > 0 && sw > 0 && sh > 0 && dstride >= dw && sstride >= sw, "bad arguments");
+    CHECK_ARGS(nb >= 1 && nb <= kMaxBatch, "nb out of range");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    DevMem a, b;
+    const int sp = dev_pitch(sw), dp = dev_pitch(dw);
+    const long spl = (long)sp * sh, dpl = (long)dp * dh;                                   // a window: its x plane, then its y plane
+    SFA_TRY(a.alloc(ctx, (size_t)nb * 2 * spl * sizeof(float))); SFA_TRY(b.alloc(ctx, (size_t)nb * 2 * dpl * sizeof(float)));
+    SFA_HIP(ctx, hipMemsetAsync(a.p, 0, (size_t)nb * 2 * spl * sizeof(float), ctx->stream));
+    SFA_HIP(ctx, hipMemsetAsync(b.p, 0, (size_t)nb * 2 * dpl * sizeof(float), ctx->stream));
+    for (int i = 0; i < nb; i++) {
+        SFA_TRY(upload_plane(ctx, a.f() + i * 2 * spl, sp, swx + (size_t)i * sstride * sh, sstride, sw, sh));
+        SFA_TRY(upload_plane(ctx, a.f() + i * 2 * spl + spl, sp, swy + (size_t)i * sstride * sh, sstride, sw, sh));
+    }
+    launch_resize_flow(ctx, b.f(), b.f() + dpl, dw, dh, dp, 2 * dpl, a.f(), a.f() + spl, sw, sh, sp, 2 * spl, nb, post_x, post_y);
+    for (int i = 0; i < nb; i++) {
+        SFA_TRY(download_plane(ctx, dwx + (size_t)i * dstride * dh, dstride, b.f() + i * 2 * dpl, dp, dw, dh));
+        SFA_TRY(download_plane(ctx, dwy + (size_t)i * dstride * dh, dstride, b.f() + i * 2 * dpl + dpl, dp, dw, dh));
+    }
     return sfa_ctx_sync(ctx);
 }
 
@@ -962,9 +1016,10 @@ int sfa_sequence_rescale(sfa_sequence *dq, int f_dst, sfa_sequence *sq, int f_sr
     if (dq->w != dw || dq->h != dh)
         REFUSE("%s: dst_seq is %d x %d; src_seq's %d x %d frames at scale %g give lrint(w scale) x lrint(h scale) = %d x %d", __func__, dq->w, dq->h, w, h, (double)scale, dw, dh);
     const float sigma = (float)(1 / sqrt(2 * scale));                                   // slow_flow.cpp:551
-    float taps[64];
+    float taps[kMaxBlurTaps];
     if (!(sigma * 8 + 1 < 33)) REFUSE("%s: scale = %g: sigma too large", __func__, (double)scale);
     const int r = cv_gauss_taps(sigma, taps);
+    if (r < 0) REFUSE("%s: scale = %g: sigma too large", __func__, (double)scale);
     if (r > 8) REFUSE("%s: scale = %g needs a blur of %d taps; the blur kernel holds 17 (scale >= 0.125)", __func__, (double)scale, 2 * r + 1);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const int chunk = std::min(n, 8);                       // frames blurred per launch pair: bounds the scratch to 2 x 8 frames
@@ -976,7 +1031,7 @@ int sfa_sequence_rescale(sfa_sequence *dq, int f_dst, sfa_sequence *sq, int f_sr
     float *blur = dq->rescale_tmp.f(), *tmp = blur + (size_t)chunk * frame_floats;
     for (int i = 0; i < n; i += chunk) {
         const int m = std::min(chunk, n - i);
-        launch_gauss_blur(ctx, sq->geo(), blur, tmp, sq->frame(f_src + i), 3 * m, taps, r);
+        SFA_TRY(launch_gauss_blur(ctx, sq->geo(), blur, tmp, sq->frame(f_src + i), 3 * m, taps, r));
         launch_resize_scaled(ctx, dq->frame(f_dst + i), dw, dh, dq->pitch, dq->pl, 0, blur, w, h, sq->pitch, sq->pl, 0, 3 * m, 1, 1.0f, 1.0 / (double)scale,
                              1.0 / (double)scale);
     }

@@ -391,6 +391,8 @@ struct sfa_job {
     double mpix_iters = 0;
     int host_stride0 = 0;              // the stride of the last upload's host planes (host_stride(w) before any): level 0's lstride
     bool fused = true;                 // false: SFA_UNFUSED=1 at creation (stack planes materialised; cross-check only)
+    float pyr_taps[kMaxBlurTaps] = {}; // the pyramid's blur, sigma = 1 / sqrt(2 p_scale) (:578): sfa_job_create refuses a p_scale whose taps do not fit
+    int pyr_radius = 0;
     Level level(int l) const {
         Level Lv;
         Lv.layout(arena.f() + trans_off, arena.f() + level_off[l], ws[l], hs[l], l == 0 ? host_stride0 : host_stride(ws[l]), ref, nb, es, fused);
@@ -461,23 +463,15 @@ static void job_presmooth(sfa_job *j) {                                         
     }
     j->presmoothed = all;
 }
-static void job_pyramid(sfa_job *j) {                                                  // :583-652
-    sfa_ctx *ctx = j->ctx;
-    const int nb = j->nb, F = j->F;
-    float taps[64];
-    const int radius = cv_gauss_taps(1 / sqrtf(2 * j->p.p_scale), taps);
+static int job_pyramid(sfa_job *j) {                                                   // :583-652
     for (int l = 1; l < j->L; l++) {
         const Level Lp = j->level(l - 1), Lc = j->level(l);
-        float *tmp = Lp.tmp();
-        // all F frames (3 F consecutive planes per window) in one pass: :607 + :611 fused
-        if (!sw_given(Switches::PYRAMID_UNFUSED) &&
-            launch_pyr_down(ctx, Lc.frame(0), Lc.w, Lc.h, Lc.pitch, Lc.pl, Lc.es, Lp.frame(0), Lp.w, Lp.h, Lp.pitch, Lp.pl, Lp.es, 3 * F, nb, taps, radius))
-            continue;
-        for (int f = 0; f < F; f++) {
-            launch_gauss_blur(ctx, Lp.geo(), tmp + 3 * Lp.pl, tmp, Lp.frame(f), 3, taps, radius);                   // :607
-            launch_resize(ctx, Lc.frame(f), Lc.w, Lc.h, Lc.pitch, Lc.pl, Lc.es, tmp + 3 * Lp.pl, Lp.w, Lp.h, Lp.pitch, Lp.pl, Lp.es, 3, nb, 1.0f);   // :611
-        }
+        // all F frames (3 F consecutive planes per window) in one pass where :607 + :611 fuse, else frame by frame through the level's scratch (pyramid_step).
+        // The taps are sfa_job_create's: a job whose blur the kernels do not hold is never created
+        SFA_TRY(pyramid_step(j->ctx, Lc.frame(0), Lc.w, Lc.h, Lc.pitch, Lc.pl, Lc.es, Lp.frame(0), Lp.w, Lp.h, Lp.pitch, Lp.pl, Lp.es, 3 * j->F, j->nb, j->pyr_taps,
+                             j->pyr_radius, Lp.tmp()));
     }
+    return SFA_OK;
 }
 static void job_initial_flow(sfa_job *j) {                                             // :662-681
     const Level L0 = j->level(0), Lt = j->level(j->L - 1);
@@ -500,9 +494,18 @@ int sfa_job_create(sfa_ctx *ctx, const sfa_params *p, int w, int h, int batch, s
     CHECK_ARGS(ctx && p && out && w >= 2 && h >= 5 && batch > 0 && batch <= kMaxBatch, "bad arguments (h >= 5, w >= 2)");
     CHECK_ARGS(p->S >= 2 && p->S - 1 <= SFA_MAX_REF && p->layers >= 1 && p->layers <= 64, "unsupported slow_flow_S / slow_flow_layers");
     CHECK_ARGS(2L * kMaxBatch + 2L * batch * ((w + 63) / 64) * 16 <= kRedDoubles, "batch x width beyond the change norms' scratch (sfa_internal.h: kRedDoubles)");
+    // p_scale sizes the levels (:609-611) and the pyramid's blur (:578): outside (0, 1] the levels do not shrink or sigma is no number, and a very small
+    // one asks for more taps than k_gauss_h / k_gauss_v carry
+    if (!(p->p_scale > 0) || p->p_scale > 1) REFUSE("%s: p_scale = %g must lie in (0, 1]", __func__, (double)p->p_scale);
+    float taps[kMaxBlurTaps] = {};
+    const int radius = cv_gauss_taps(1 / sqrtf(2 * p->p_scale), taps);
+    if (radius < 0)
+        REFUSE("%s: p_scale = %g: the pyramid's blur, sigma = 1 / sqrt(2 p_scale) = %g, needs more than the %d taps the blur kernels hold", __func__,
+               (double)p->p_scale, (double)(1 / sqrtf(2 * p->p_scale)), kMaxBlurTaps);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<sfa_job> j(new sfa_job());
     j->ctx = ctx; j->p = *p; j->w = w; j->h = h; j->nb = batch; j->ref = p->S - 1; j->F = 2 * j->ref + 1;
+    memcpy(j->pyr_taps, taps, sizeof taps); j->pyr_radius = radius;
     j->L = pyramid_sizes(w, h, p->layers, p->p_scale, j->ws, j->hs);
     CHECK_ARGS(j->L >= 1, "image too small for even one pyramid level");
     j->fused = sw_int(Switches::UNFUSED, 0) == 0;
@@ -591,7 +594,7 @@ int sfa_job_run(sfa_job *j) {
     CHECK_ARGS(j, "null job");
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     job_presmooth(j);
-    job_pyramid(j);
+    SFA_TRY(job_pyramid(j));
     job_initial_flow(j);
     ChannelWeights cw;
     if (j->has_chw) {
@@ -653,6 +656,22 @@ int sfa_job_download_occlusions(sfa_job *j, int b, float *occ, int stride) {
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     Level L0 = j->level(0);
     SFA_TRY(download_plane(ctx, occ, stride, L0.plane(P_OCC) + b * j->es, L0.pitch, j->w, j->h));
+    return sfa_ctx_sync(ctx);
+}
+
+// test hook: the three planes of frame f of window b at pyramid level `level`, as the last run's pyramid (level 0: the upload, presmoothed if the cfg says so) left them
+int sfa_job_download_level_frame(sfa_job *j, int b, int level, int f, float *frame3, int stride) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    CHECK_ARGS(frame3, "frame3 is null");
+    if (b < 0 || b >= j->nb) REFUSE("%s: window b = %d outside the job's %d", __func__, b, j->nb);
+    if (level < 0 || level >= j->L) REFUSE("%s: level = %d outside the job's %d pyramid levels", __func__, level, j->L);
+    if (f < 0 || f >= j->F) REFUSE("%s: frame f = %d outside the window's %d", __func__, f, j->F);
+    const Level Lv = j->level(level);
+    if (stride < Lv.w) REFUSE("%s: stride = %d below level %d's width %d", __func__, stride, level, Lv.w);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    for (int k = 0; k < 3; k++)
+        SFA_TRY(download_plane(ctx, frame3 + (size_t)k * stride * Lv.h, stride, Lv.frame(f) + b * j->es + k * Lv.pl, Lv.pitch, Lv.w, Lv.h));
     return sfa_ctx_sync(ctx);
 }
 

@@ -2134,11 +2134,13 @@ void launch_scale_plane(sfa_ctx *c, const Geo &g, float *p, float s) {
 // ---------------------------------------------------------------------------------------------------
 // K9 pyramid: cv::GaussianBlur(Size(0,0), sigma, BORDER_REPLICATE) and cv::resize(INTER_LINEAR) on CV_32F
 // (variational_mt.cpp:607,611,672-673,711-712).  OpenCV is not vendored: documented semantics restated
-// (symmetric separable fp32 taps, rows then columns; half-pixel-centre bilinear), parity unpinned.
+// (symmetric separable fp32 taps, rows then columns; half-pixel-centre bilinear), unpinned against OpenCV itself; the kernels are
+// bit-exact against the oracle's restatement, stage by stage (tests/test_pyramid_stages.py).
 // ---------------------------------------------------------------------------------------------------
-struct Taps { float k[17]; int r; };
+struct Taps { float k[17]; int r; };                                // k_pyr_down's: radius <= 8
+struct BlurTaps { float k[kMaxBlurTaps]; int r; };                   // k_gauss_h / k_gauss_v's: radius <= kMaxBlurRadius, the range of sfa_gaussian_blur
 
-__global__ void k_gauss_h(float *__restrict__ dst, const float *__restrict__ src, Geo g, int nplanes, Taps t) {
+__global__ void k_gauss_h(float *__restrict__ dst, const float *__restrict__ src, Geo g, int nplanes, BlurTaps t) {
     const int b = blockIdx.z / nplanes, pl = blockIdx.z % nplanes;
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= g.w || y >= g.h) return;
@@ -2147,7 +2149,7 @@ __global__ void k_gauss_h(float *__restrict__ dst, const float *__restrict__ src
     for (int j = 1; j <= t.r; j++) acc += t.k[t.r + j] * (s[clampi(x - j, 0, g.w - 1)] + s[clampi(x + j, 0, g.w - 1)]);
     dst[b * g.es + pl * g.pl + (size_t)y * g.pitch + x] = acc;
 }
-__global__ void k_gauss_v(float *__restrict__ dst, const float *__restrict__ src, Geo g, int nplanes, Taps t) {
+__global__ void k_gauss_v(float *__restrict__ dst, const float *__restrict__ src, Geo g, int nplanes, BlurTaps t) {
     const int b = blockIdx.z / nplanes, pl = blockIdx.z % nplanes;
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= g.w || y >= g.h) return;
@@ -2157,12 +2159,16 @@ __global__ void k_gauss_v(float *__restrict__ dst, const float *__restrict__ src
         acc += t.k[t.r + j] * (s[(size_t)clampi(y - j, 0, g.h - 1) * g.pitch + x] + s[(size_t)clampi(y + j, 0, g.h - 1) * g.pitch + x]);
     dst[b * g.es + pl * g.pl + (size_t)y * g.pitch + x] = acc;
 }
-void launch_gauss_blur(sfa_ctx *c, const Geo &g, float *dst, float *tmp, const float *src, int nplanes, const float *taps, int radius) {
-    Taps t;
+// refuses, before anything is copied or launched, a radius its tap struct does not hold
+int launch_gauss_blur(sfa_ctx *c, const Geo &g, float *dst, float *tmp, const float *src, int nplanes, const float *taps, int radius) {
+    if (radius < 0 || radius > kMaxBlurRadius)
+        return set_error(c, SFA_ERR_ARG, "Gaussian blur of %d taps: the blur kernels hold %d (radius <= %d)", 2 * radius + 1, kMaxBlurTaps, kMaxBlurRadius);
+    BlurTaps t;
     t.r = radius;
     for (int i = 0; i < 2 * radius + 1; i++) t.k[i] = taps[i];
     hipLaunchKernelGGL(k_gauss_h, grid2d(g, nplanes), block2d(), 0, c->stream, tmp, src, g, nplanes, t);
     hipLaunchKernelGGL(k_gauss_v, grid2d(g, nplanes), block2d(), 0, c->stream, dst, tmp, g, nplanes, t);
+    return SFA_OK;
 }
 
 __global__ void k_resize(float *__restrict__ dst, int dw, int dh, int dpitch, long dpl, long des, const float *__restrict__ src, int sw, int sh, int spitch,
@@ -2392,9 +2398,12 @@ __global__ void __launch_bounds__(kPyrNT) k_pyr_down(float *__restrict__ dst, in
         dst[b * des + pl * dpl + (size_t)dy * dpitch + dx] = h0 * b0 + h1 * b1;
     }
 }
-// returns false if the footprint does not fit LDS (very small p_scale): the caller then runs the separate kernels
+// returns false if the footprint does not fit LDS (very small p_scale) or the radius is not one of the instances' (1 .. 8, what Taps holds): the caller then
+// runs the separate kernels.  info (optional): what ran -- {1, td, LDS bytes}, or {0, 0, 0}
 bool launch_pyr_down(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dpl, long des, const float *src, int sw, int sh, int spitch, long spl, long ses,
-                     int nplanes, int nb, const float *taps, int radius) {
+                     int nplanes, int nb, const float *taps, int radius, PyrInfo *info) {
+    if (info) *info = PyrInfo{0, 0, 0};
+    if (radius < 1 || radius > 8) return false;                      // checked before the taps are copied: Taps holds 2 * 8 + 1
     const double scale_x = (double)sw / dw, scale_y = (double)sh / dh;
     const int CM = (((int)ceil(64 * scale_x) + 2) + 3 + 3) / 4 * 4, CS = (CM + 2 * radius + 3) / 4 * 4 + 4;   // + 3: the footprint starts at a multiple of 4
     int td = 32, RM = 0, RS = 0;
@@ -2404,7 +2413,7 @@ bool launch_pyr_down(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dp
         lds = (size_t)(RS * CS + RS * CM + 3 * td) * sizeof(float);  // the column pass writes over the staged footprint (RM * CM <= RS * CS); + the rows' sampling table
         if (lds <= 40 * 1024 || td == 8) break;                     // 40 KB: four blocks per CU
     }
-    if (lds > 60 * 1024 || radius > 8) return false;
+    if (lds > 60 * 1024) return false;
     Taps t;
     t.r = radius;
     for (int i = 0; i < 2 * radius + 1; i++) t.k[i] = taps[i];
@@ -2415,7 +2424,25 @@ bool launch_pyr_down(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dp
     default: return false;
     }
 #undef SFA_PYR
+    if (info) *info = PyrInfo{1, td, (int)lds};
     return true;
+}
+
+// One pyramid step of `nplanes` planes per window (variational_mt.cpp:607,611): k_pyr_down where launch_pyr_down takes the shape (and SFA_PYRAMID_UNFUSED is not
+// given), else k_gauss_h / k_gauss_v + k_resize on three planes at a time through `tmp`: 6 planes of the source's geometry per window, `ses` apart like the
+// source's.  sfa_job_run's pyramid and the test hook sfa_pyramid_down both run this.
+int pyramid_step(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dpl, long des, const float *src, int sw, int sh, int spitch, long spl, long ses, int nplanes,
+                 int nb, const float *taps, int radius, float *tmp, PyrInfo *info) {
+    if (info) *info = PyrInfo{0, 0, 0};
+    if (!sw_given(Switches::PYRAMID_UNFUSED) && launch_pyr_down(c, dst, dw, dh, dpitch, dpl, des, src, sw, sh, spitch, spl, ses, nplanes, nb, taps, radius, info))
+        return SFA_OK;
+    const Geo g{sw, sh, spitch, spl, ses, nb, WMask::first(nb), nullptr};
+    for (int p0 = 0; p0 < nplanes; p0 += 3) {
+        const int n = nplanes - p0 < 3 ? nplanes - p0 : 3;
+        SFA_TRY(launch_gauss_blur(c, g, tmp + 3 * spl, tmp, src + p0 * spl, n, taps, radius));                                    // :607
+        launch_resize(c, dst + p0 * dpl, dw, dh, dpitch, dpl, des, tmp + 3 * spl, sw, sh, spitch, spl, ses, n, nb, 1.0f);         // :611
+    }
+    return SFA_OK;
 }
 
 // optional level-0 Gaussian presmoothing (cfg sigma > 0, variational_mt.cpp:590-597): gaussian_filter

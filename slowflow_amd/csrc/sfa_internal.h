@@ -364,20 +364,29 @@ void launch_copy_planes(sfa_ctx *c, const Geo &g, float *dst, const float *src, 
 void launch_scale_plane(sfa_ctx *c, const Geo &g, float *p, float s);
 
 // pyramid (kernels.hip)
-void launch_gauss_blur(sfa_ctx *c, const Geo &g, float *dst, float *tmp, const float *src, int nplanes, const float *taps, int radius);
+// the widest Gaussian the blur kernels carry: cv::GaussianBlur's 33 taps (sigma * 8 + 1 rounds to at most 33), the range sfa_gaussian_blur documents.  Every
+// host buffer of taps has kMaxBlurTaps entries and is filled by cv_gauss_taps alone, which writes no more
+constexpr int kMaxBlurRadius = 16, kMaxBlurTaps = 2 * kMaxBlurRadius + 1;
+// SFA_ERR_ARG (nothing copied, nothing launched) for a radius beyond kMaxBlurRadius
+int launch_gauss_blur(sfa_ctx *c, const Geo &g, float *dst, float *tmp, const float *src, int nplanes, const float *taps, int radius);
 void launch_resize(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dpl, long des, const float *src, int sw, int sh, int spitch, long spl, long ses,
                    int nplanes, int nb, float post_scale);
 void launch_resize_flow(sfa_ctx *c, float *dstx, float *dsty, int dw, int dh, int dpitch, long des, const float *srcx, const float *srcy, int sw, int sh, int spitch,
                         long ses, int nb, float post_x, float post_y);   // both planes of a flow field, k_resize's arithmetic
 void launch_resize_scaled(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dpl, long des, const float *src, int sw, int sh, int spitch, long spl,
                           long ses, int nplanes, int nb, float post_scale, double scale_x, double scale_y);
+struct PyrInfo { int fused, td, lds; };   // what a pyramid step ran: k_pyr_down (1) with its tile height and LDS bytes, or the two kernels (0, 0, 0)
 bool launch_pyr_down(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dpl, long des, const float *src, int sw, int sh, int spitch, long spl, long ses,
-                     int nplanes, int nb, const float *taps, int radius);   // blur + resize fused; false: footprint too large, use the two kernels
+                     int nplanes, int nb, const float *taps, int radius, PyrInfo *info = nullptr);   // blur + resize fused; false: footprint too large or radius > 8, use the two kernels
+// one pyramid step, fused where launch_pyr_down accepts, else blur + resize through tmp (6 source planes per window, ses apart): kernels.hip
+int pyramid_step(sfa_ctx *c, float *dst, int dw, int dh, int dpitch, long dpl, long des, const float *src, int sw, int sh, int spitch, long spl, long ses, int nplanes,
+                 int nb, const float *taps, int radius, float *tmp, PyrInfo *info = nullptr);
 void launch_presmooth(sfa_ctx *c, const Geo &g, float *dst, float *tmp, const float *src, int nplanes, float sigma);
 void launch_normalize_sums(sfa_ctx *c, const Geo &g, const float *frames3, double *red /* [3][2] */);
 void launch_normalize_apply(sfa_ctx *c, const Geo &g, float *frames3, const double avg[3], const double stdv[3]);
-// cv::getGaussianKernel's taps for cv::GaussianBlur(Size(0,0), sigma) on CV_32F (api.hip); returns the radius.  Hidden: job.hip's use adds no export
-__attribute__((visibility("hidden"))) int cv_gauss_taps(float sigma, float *k);
+// cv::getGaussianKernel's taps for cv::GaussianBlur(Size(0,0), sigma) on CV_32F (api.hip) into k[kMaxBlurTaps]; returns the radius, or -1 (k untouched) when
+// sigma is not a positive number or the kernel has more than kMaxBlurTaps taps.  Hidden: job.hip's use adds no export
+__attribute__((visibility("hidden"))) int cv_gauss_taps(float sigma, float k[kMaxBlurTaps]);
 
 // ---- device_io.hip: the device seam (sfa_job_upload_device ...): conversions and moves only ---------------------------------------------
 // A strided source of colour frames in device memory: element (window, frame, channel, row, column) at p + the strides, in elements of dtype (sfa_dev_dtype)
