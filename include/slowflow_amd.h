@@ -111,6 +111,23 @@ void sfa_params_2frame_default(sfa_params_2frame *p);          /* variational.c:
  * both run the launch sequence of the resident pair jobs below on a pair job that lives for the call, with the stored derivative stack.) */
 int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *const *wy, int w, int h, int stride, const float *const *im1,
                                  const float *const *im2, const sfa_params_2frame *p);
+/* EpicFlow's geodesic k nearest seeds (epic_aux.cpp:44-380; host/epic.cpp: epic_nearest_seeds) for n images of one size w x h in one call, on the GPU
+ * (csrc/epic_nn.hip): the distance transform of the seeds over the cost map with label propagation, the graph of the label regions, and for every seed its
+ * nn nearest seeds on that graph.  Image i: cost[i] = w * h floats, row-major, the constant `euc` already added; seeds_xy[i] = 2 * ns[i] ints (x, y), a later
+ * seed on the same pixel wins; labels[i] (out) = w * h ints, the closest seed of every pixel, -1 where none reaches; nn_index[i], nn_dist[i] (out) =
+ * ns[i] * nn entries, seed q's neighbours in the order the reference's search finds them and their raw geodesic distances (no kernel applied), -1 /
+ * 0x7F7F7F7F where fewer than nn exist.  Every output equals the host function's bit for bit, whatever n and the image's position; costs are non-negative.
+ * Host pointers; the call waits for its results.  The batch runs in sub-batches whose device memory (planes, the border table, ns * ns floats and the
+ * search's heaps, sized from the counted graph: 1 + min((nn - 1) * largest degree, 2 * edges) entries per seed) stays within workspace_bytes (0: half of the
+ * GPU's free memory); status[i] = 0: computed, 1: image i does not fit the budget even alone -- its outputs are untouched and the caller computes it on the host.
+ * Refused with SFA_ERR_ARG, the argument named and nothing launched: n < 1, w or h < 1, nn < 1, an ns[i] < 1, a null pointer, a seed outside the image,
+ * w * h > 2^29 or ns[i] * nn > 2^31 - 1 (32-bit indices), min(w, h) > 4000 (two diagonals of the sweep live in LDS). */
+int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float *const *cost, const int *const *seeds_xy, const int *ns, int nn,
+                                 int *const *labels, int *const *nn_index, float *const *nn_dist, size_t workspace_bytes, int *status);
+/* The kernel time of the context's last sfa_epic_nearest_seeds_batch in milliseconds, from HIP events around the launches, summed over its sub-batches:
+ * ms[0] initial state and seeds, ms[1] the sweeps, ms[2] the region graph (border count, table, rows), ms[3] the graph search, ms[4] the lists.
+ * Copies, allocations and the waits between the stages are not in it (tools/bench_epic_nn.py). */
+int sfa_epic_nn_stage_ms(sfa_ctx *ctx, float ms[5]);
 /* adaptiveFR's flow-magnitude quantile (adaptiveFR.cpp:644-668) on the GPU.  n host fields (u[i], v[i]: w x h, row stride `stride`); every value is scaled
  * by flow_scale first (one fp32 multiply, image_mul_scalar), m = sqrtf(u*u + v*v) in IEEE fp32; the order statistics are found by an exact radix select
  * over the bit patterns of m.  NaN magnitudes sort above +Inf (their bit order; std::sort has no defined order for them), Inf where it belongs.

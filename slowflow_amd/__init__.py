@@ -168,7 +168,7 @@ def track_job_bytes(params):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_grid_cut_batch", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_pyramid_down", "sfa_resize_flow", "sfa_job_download_level_frame",
@@ -497,6 +497,46 @@ class Context:
         arrs = [(_f * max(n, 1))(*[fptr(a) for a in group]) for group in (wxs, wys, im1s, im2s)]
         self._ck(L.sfa_variational_2frame_batch(self.h, n, arrs[0], arrs[1], w, h, stride, arrs[2], arrs[3], C.byref(p) if p is not None else None),
                  "sfa_variational_2frame_batch")
+
+    def epic_nearest_seeds(self, costs, seeds, nn, workspace_bytes=0, with_status=False):
+        """EpicFlow's geodesic k nearest seeds of a batch (sfa_epic_nearest_seeds_batch).  costs: n fp32 (h, w) cost maps of one size, euc already added;
+        seeds: n int arrays (ns_i, 2) of (x, y); returns (labels, index, dist): lists of int32 (h, w), int32 (ns_i, nn), float32 (ns_i, nn) -- the bits of the
+        host's epic_nearest_seeds.  workspace_bytes: the device-memory budget of a sub-batch (0: half of the free memory).  An image that does not fit the
+        budget even alone raises, unless with_status: then a fourth list of ints is returned, 1 for such an image (its arrays are None)"""
+        n = len(costs)
+        costs = [np.ascontiguousarray(c, dtype=np.float32) for c in costs]
+        seeds = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 2) for s in seeds]
+        assert len(seeds) == n, "one seed array per cost map"
+        h, w = costs[0].shape if n else (0, 0)
+        for c in costs:
+            assert c.shape == (h, w), "every cost map of the batch has one shape"
+        ns = [len(s) for s in seeds]
+        labels = [np.full((h, w), -2, np.int32) for _ in range(n)]
+        index = [np.full((max(k, 0), max(int(nn), 0)), -2, np.int32) for k in ns]
+        dist = [np.zeros((max(k, 0), max(int(nn), 0)), np.float32) for k in ns]
+        L = lib()
+        _i = C.POINTER(C.c_int)
+        L.sfa_epic_nearest_seeds_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(_f), C.POINTER(_i), _i, C.c_int, C.POINTER(_i), C.POINTER(_i),
+                                                   C.POINTER(_f), C.c_size_t, _i]
+        k = max(n, 1)
+        ip = lambda a: a.ctypes.data_as(_i)
+        status = (C.c_int * k)()
+        self._ck(L.sfa_epic_nearest_seeds_batch(self.h, n, w, h, (_f * k)(*[fptr(c) for c in costs]), (_i * k)(*[ip(s) for s in seeds]), (C.c_int * k)(*ns),
+                                                int(nn), (_i * k)(*[ip(a) for a in labels]), (_i * k)(*[ip(a) for a in index]),
+                                                (_f * k)(*[fptr(a) for a in dist]), int(workspace_bytes), status), "sfa_epic_nearest_seeds_batch")
+        status = list(status[:n])
+        if with_status:
+            pick = lambda xs: [None if s else x for x, s in zip(xs, status)]
+            return pick(labels), pick(index), pick(dist), status
+        if any(status):
+            raise SlowflowError("sfa_epic_nearest_seeds_batch: images %s do not fit a workspace of %d bytes" % ([i for i, s in enumerate(status) if s], workspace_bytes))
+        return labels, index, dist
+
+    def epic_nn_stage_ms(self):
+        """the kernel milliseconds of the last epic_nearest_seeds by group (sfa_epic_nn_stage_ms): seeds, sweeps, graph, search, lists"""
+        ms = (C.c_float * 5)()
+        self._ck(lib().sfa_epic_nn_stage_ms(self.h, ms), "sfa_epic_nn_stage_ms")
+        return dict(zip(("seeds", "sweeps", "graph", "search", "lists"), [float(v) for v in ms]))
 
     def flow_magnitude_quantile(self, us, vs, w, flow_scale, q):
         """adaptiveFR's quantile (sfa_flow_magnitude_quantile): the fields' magnitudes after scaling by flow_scale, the rank rule of

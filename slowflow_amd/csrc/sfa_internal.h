@@ -96,6 +96,7 @@ struct sfa_ctx {
     size_t rb_tmp_bytes = 0;
     void *q_tmp = nullptr;        // sfa_flow_magnitude_quantiles_device (quantile.hip): group records, histograms and keys, kept from call to call, grown on demand
     size_t q_tmp_bytes = 0;
+    float epic_ms[5] = {};        // sfa_epic_nearest_seeds_batch (epic_nn.hip): the last call's kernel time by group (sfa_epic_nn_stage_ms)
     hipEvent_t t0 = nullptr, t1 = nullptr;
     hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // sfa_ctx_wait_stream / sfa_ctx_signal_stream: recorded on the caller's / the context's stream
     // the reference's per-iteration "avg change" lines (variational_mt.cpp:404-405, 431-432): sfa_ctx_set_verbose; costs a host round trip per iteration

@@ -37,7 +37,7 @@ static void usage() {
     printf("usage:\n");
     printf("    ./adaptiveFR -path [path] -folder [one sequence folder | file listing folders] -format [file format] -scale [default 0.25] "
            "-skip [target frame (2)] -samples [number of estimates (40)] -step [frames between estimates (10)] -start [first frame (0)] "
-           "-quantil [q (0.9)] -append [file] -overwrite -sintel -subframes -raw -threads\n");
+           "-quantil [q (0.9)] -append [file] -overwrite -sintel -subframes -raw -threads -gpu_epic (EpicFlow's graph searches of all pending samples on the GPU)\n");
     printf("\n");
 }
 
@@ -85,7 +85,7 @@ int main(int argc, char **argv) {
     if (argc < 2) { usage(); exit(1); }
     string format = "%07i.tif", path, folder, append;
     unsigned start = 0;
-    bool overwrite = false, sintel = false, subframes = false, raw = false;
+    bool overwrite = false, sintel = false, subframes = false, raw = false, gpu_epic = false;
     int samples = 40, sample_step = 10, skip = 2, threads = 1;
     const int all_frames = 2;
     float q = 0.90f;
@@ -113,6 +113,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "-raw")) raw = true;
         else if (!strcmp(a, "-subframes")) subframes = true;
         else if (!strcmp(a, "-format")) format = next();
+        else if (!strcmp(a, "-gpu_epic")) gpu_epic = true;
         else { fprintf(stderr, "unknown argument %s", a); usage(); exit(1); }
     }
     (void)threads;          // the reference runs sequences on OpenMP threads (:245); here they run one after the other, each sample batch fills the GPU
@@ -263,6 +264,9 @@ int main(int argc, char **argv) {
     int rc_all = 0;
     for (Sequence *S : seqs) {
         std::vector<Sample *> todo;
+        std::vector<color_image_t *> labs;                                                      // -gpu_epic: the inputs of todo's samples
+        std::vector<epic_matches> mts;
+        std::vector<epic_edges> eds;
         for (Sample *smp : S->samples) {
             if (!smp->pending) continue;
             const int w = smp->im[0]->width, h = smp->im[0]->height;
@@ -275,11 +279,30 @@ int main(int argc, char **argv) {
             color_image_t *lab = rgb_to_lab(smp->im[0]);                                        // :563
             smp->wx = image_new(w, h); smp->wy = image_new(w, h);
             image_erase(smp->wx); image_erase(smp->wy);
+            todo.push_back(smp);
+            if (gpu_epic) {                                                                     // -gpu_epic: interpolated below, up to 128 samples per epic_batch
+                labs.push_back(lab); mts.push_back(std::move(mt)); eds.push_back(std::move(ed));
+                continue;
+            }
             const int er = epic(ctx, smp->wx, smp->wy, lab, mt, ed, &ep);                       // :568
             color_image_delete(lab);
             if (er < 0) { std::cerr << "EpicFlow interpolation failed: " << sfa_last_error(ctx) << std::endl; return 4; }
             if (er > 0) { image_erase(smp->wx); image_erase(smp->wy); }                         // no usable match: start from zero
-            todo.push_back(smp);
+        }
+        for (size_t b = 0; b < labs.size(); b += 128) {
+            const int n = (int)std::min<size_t>(128, labs.size() - b);
+            std::vector<image_t *> fx(n), fy(n);
+            std::vector<const color_image_t *> lab(n);
+            std::vector<const epic_matches *> mt(n);
+            std::vector<epic_edges *> ed(n);
+            std::vector<int> er(n);
+            for (int i = 0; i < n; i++) { fx[i] = todo[b + i]->wx; fy[i] = todo[b + i]->wy; lab[i] = labs[b + i]; mt[i] = &mts[b + i]; ed[i] = &eds[b + i]; }
+            epic_batch(ctx, n, fx.data(), fy.data(), lab.data(), mt.data(), ed.data(), &ep, er.data());
+            for (int i = 0; i < n; i++) {
+                color_image_delete(labs[b + i]);
+                if (er[i] < 0) { std::cerr << "EpicFlow interpolation failed: " << sfa_last_error(ctx) << std::endl; return 4; }
+                if (er[i] > 0) { image_erase(fx[i]); image_erase(fy[i]); }
+            }
         }
         // :574 -- variational(), here for up to 128 samples at once.  The reference then runs system(epic_cmd) (:575) on a buffer it never
         // initialised; nothing of the kind is done here.

@@ -391,3 +391,150 @@ int epic(sfa_ctx *ctx, image_t *flowx, image_t *flowy, const color_image_t *im, 
     }
     return 0;
 }
+
+// ---- epic_batch: epic() for n images, its two graph searches on the GPU ---------------------------------------------------------------------------------
+namespace {
+struct BatchItem {
+    std::vector<float> m;                                                    // the matches still in play
+    std::vector<int> seeds, labels;
+    std::vector<float> vects;
+    epic_nn k;
+    int nns = 0;
+};
+
+// epic_nearest_seeds(it.seeds, edges, it.nns, it.k, it.labels) for every image listed in `which`: one sfa_epic_nearest_seeds_batch per group of one size and
+// one nn; an image the library flags as too large for its workspace goes through the host function.  false on a GPU error (sfa_last_error(ctx))
+bool nearest_seeds_batch(sfa_ctx *ctx, const std::vector<int> &which, epic_edges *const *edges, std::vector<BatchItem> &it, size_t workspace_bytes) {
+    std::vector<char> taken(which.size(), 0);
+    for (size_t a = 0; a < which.size(); a++) {
+        if (taken[a]) continue;
+        const epic_edges &ea = *edges[which[a]];
+        const int nn = it[which[a]].nns;
+        std::vector<int> group;
+        for (size_t b = a; b < which.size(); b++) {
+            const epic_edges &eb = *edges[which[b]];
+            if (taken[b] || eb.width != ea.width || eb.height != ea.height || it[which[b]].nns != nn) continue;
+            taken[b] = 1;
+            group.push_back(which[b]);
+        }
+        const size_t g = group.size();
+        std::vector<const float *> cost(g);
+        std::vector<const int *> seeds(g);
+        std::vector<int> ns(g), status(g);
+        std::vector<int *> labels(g), index(g);
+        std::vector<float *> dist(g);
+        for (size_t b = 0; b < g; b++) {
+            BatchItem &t = it[group[b]];
+            ns[b] = (int)(t.seeds.size() / 2);
+            t.labels.assign((size_t)ea.width * ea.height, -1);
+            t.k.nn = nn;
+            t.k.index.assign((size_t)ns[b] * nn, -1);
+            t.k.dist.assign((size_t)ns[b] * nn, 0.f);
+            cost[b] = edges[group[b]]->cost.data(); seeds[b] = t.seeds.data();
+            labels[b] = t.labels.data(); index[b] = t.k.index.data(); dist[b] = t.k.dist.data();
+        }
+        if (sfa_epic_nearest_seeds_batch(ctx, (int)g, ea.width, ea.height, cost.data(), seeds.data(), ns.data(), nn, labels.data(), index.data(), dist.data(), workspace_bytes,
+                                         status.data()) != SFA_OK)
+            return false;
+        for (size_t b = 0; b < g; b++)
+            if (status[b]) epic_nearest_seeds(it[group[b]].seeds, *edges[group[b]], nn, it[group[b]].k, it[group[b]].labels);
+    }
+    return true;
+}
+}  // namespace
+
+void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flowy, const color_image_t *const *im, const epic_matches *const *input,
+                epic_edges *const *edges, const epic_params_t *params, int *rc, size_t workspace_bytes) {
+    std::vector<BatchItem> it((size_t)std::max(n, 0));
+    std::vector<int> live;                                                   // images still on their way: rc[i] == 0
+    for (int i = 0; i < n; i++) {                                            // epic.cpp:15-28, :155-163, :59-74
+        rc[i] = 0;
+        const int w = im[i]->width, h = im[i]->height;
+        if (edges[i]->width != w || edges[i]->height != h) { rc[i] = 2; continue; }
+        if (!ctx) { rc[i] = -1; continue; }
+        std::vector<float> &m = it[i].m;
+        m = input[i]->m;
+        for (size_t k = 0; k + 3 < m.size(); k += 4) {
+            m[k] = std::max(0.f, std::min(m[k], (float)(w - 1)));         m[k + 1] = std::max(0.f, std::min(m[k + 1], (float)(h - 1)));
+            m[k + 2] = std::max(0.f, std::min(m[k + 2], (float)(w - 1))); m[k + 3] = std::max(0.f, std::min(m[k + 3], (float)(h - 1)));
+        }
+        if (params->verbose) printf("%d input matches\n", (int)(m.size() / 4));
+        if (params->euc) for (float &c : edges[i]->cost) c += params->euc;
+        if (params->saliency_th) {
+            image_t *s = saliency(ctx, im[i], 0.8f, 1.0f);
+            if (!s) { rc[i] = -1; continue; }
+            std::vector<float> keep;
+            for (size_t k = 0; k + 3 < m.size(); k += 4)
+                if (s->data[(int)(m[k + 1] * s->stride + m[k])] >= params->saliency_th) keep.insert(keep.end(), m.begin() + k, m.begin() + k + 4);
+            image_delete(s);
+            m.swap(keep);
+            if (params->verbose) printf("Saliency filtering, remaining %d matches\n", (int)(m.size() / 4));
+        }
+        live.push_back(i);
+    }
+    if (params->pref_nn) {                                                   // :77-123: drop matches that disagree with the estimate from their neighbours
+        const float th2 = params->pref_th * params->pref_th;
+        std::vector<int> which;
+        for (int i : live) {
+            BatchItem &t = it[i];
+            if (t.m.empty()) continue;
+            t.nns = std::min(params->pref_nn + 1, (int)(t.m.size() / 4));
+            if (t.nns != params->pref_nn + 1) fprintf(stderr, "Warning: not enough matches for prefiltering\n");
+            to_seeds_and_vects(t.m, t.seeds, t.vects);
+            which.push_back(i);
+        }
+        const bool ok = which.empty() || nearest_seeds_batch(ctx, which, edges, it, workspace_bytes);
+        for (int i : which) {
+            BatchItem &t = it[i];
+            if (!ok) { rc[i] = -1; continue; }
+            kernel(t.k, params->coef_kernel);
+            std::vector<float> est, keep;
+            fit_nadarayawatson(est, t.k, t.vects);
+            for (size_t k = 0; k < t.m.size() / 4; k++) {
+                const float ex = est[2 * k] - t.vects[2 * k], ey = est[2 * k + 1] - t.vects[2 * k + 1];
+                if (ex * ex + ey * ey < th2) keep.insert(keep.end(), t.m.begin() + 4 * k, t.m.begin() + 4 * k + 4);
+            }
+            t.m.swap(keep);
+            if (params->verbose) printf("Consistenct filter, remaining %d matches\n", (int)(t.m.size() / 4));
+        }
+    }
+    std::vector<int> which;
+    for (int i : live) {                                                     // images left without matches drop out before the call
+        BatchItem &t = it[i];
+        if (rc[i]) continue;
+        if (t.m.empty()) { rc[i] = 1; continue; }
+        t.nns = std::min(params->nn, (int)(t.m.size() / 4));
+        if (t.nns < params->nn) fprintf(stderr, "Warning: not enough matches for interpolating\n");
+        to_seeds_and_vects(t.m, t.seeds, t.vects);
+        which.push_back(i);
+    }
+    const bool ok = which.empty() || nearest_seeds_batch(ctx, which, edges, it, workspace_bytes);
+    for (int i : which) {
+        BatchItem &t = it[i];
+        if (!ok) { rc[i] = -1; continue; }
+        const int w = im[i]->width, h = im[i]->height;
+        kernel(t.k, params->coef_kernel);
+        if (!strcmp(params->method, "LA")) {                                 // :204-208, apply :479-497
+            std::vector<float> aff;
+            epic_fit_localaffine(aff, t.k, t.seeds, t.vects);
+            for (int j = 0; j < h; j++)
+                for (int x = 0; x < w; x++) {
+                    const float *a = &aff[(size_t)t.labels[(size_t)j * w + x] * 6];
+                    flowx[i]->data[(size_t)j * flowx[i]->stride + x] = a[0] * x + a[1] * j + a[2] - x;
+                    flowy[i]->data[(size_t)j * flowy[i]->stride + x] = a[3] * x + a[4] * j + a[5] - j;
+                }
+        } else if (!strcmp(params->method, "NW")) {                          // :209-213, apply :410-424
+            std::vector<float> sv;
+            fit_nadarayawatson(sv, t.k, t.vects);
+            for (int j = 0; j < h; j++)
+                for (int x = 0; x < w; x++) {
+                    const int s = t.labels[(size_t)j * w + x];
+                    flowx[i]->data[(size_t)j * flowx[i]->stride + x] = sv[2 * s];
+                    flowy[i]->data[(size_t)j * flowy[i]->stride + x] = sv[2 * s + 1];
+                }
+        } else {
+            fprintf(stderr, "method %s not recognized\n", params->method);
+            rc[i] = 3;
+        }
+    }
+}

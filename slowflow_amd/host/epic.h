@@ -46,6 +46,13 @@ image_t *saliency(sfa_ctx *ctx, const color_image_t *im, float sigma_image, floa
  * 0 on success, < 0 on a GPU error (sfa_last_error(ctx)), > 0: no usable match. */
 int epic(sfa_ctx *ctx, image_t *flowx, image_t *flowy, const color_image_t *im_lab, const epic_matches &matches, epic_edges &edges, const epic_params_t *params);
 
+/* epic() for n images at once, stage by stage over the batch: the same steps and the same results, bit for bit, with the two epic_nearest_seeds calls of
+ * every image replaced by two sfa_epic_nearest_seeds_batch calls on the GPU of ctx (images of one size and one neighbour count share a call; an image the
+ * library reports as too large for its workspace is searched by the host function).  rc[i]: what epic() returns for image i; an image left without matches
+ * drops out with 1 before the second call.  workspace_bytes: the library's device-memory budget per sub-batch (0: its default).  Needs a context (rc -1 without one). */
+void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flowy, const color_image_t *const *im_lab, const epic_matches *const *matches,
+                epic_edges *const *edges, const epic_params_t *params, int *rc, size_t workspace_bytes = 0);
+
 /* the pieces, exposed for the tests ------------------------------------------------------------------------------------------------------ */
 struct epic_nn { std::vector<int> index; std::vector<float> dist; int nn = 0; };       /* per seed: nn neighbours (-1 / huge when fewer exist) */
 /* geodesic distance transform + labels + k nearest seeds of every seed; labels: closest seed of every pixel (width*height) */

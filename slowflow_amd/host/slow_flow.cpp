@@ -149,6 +149,7 @@ struct Run {
     // ramp-up / drain phases (the reference runs its windows from `threads` OpenMP threads the same way, slow_flow.cpp:706)
     const int streams = std::max(1, std::min(4, p.parameter<int>("gpu_streams", "2")));
     const bool deep_matching = p.parameter<bool>("deep_matching");
+    const bool gpu_epic = p.parameter<bool>("gpu_epic", "0");                       // additive: deep_matching 1 interpolates a batch's matches through epic_batch (the graph searches on the GPU)
     // dm_scale (:396-402, :571-586, :801-843): DeepMatching and the edge detector ran on frames blurred (sigma = 1 / sqrt(2 dm_scale)) and resized by dm_scale; the
     // interpolation then runs at that resolution (the saliency image, the edge map, the matches' coordinates) and its flow is resized to the frames and multiplied by the
     // INTEGER ratio of the widths (:827-828: `float fx = im[ref]->width / wx->width` divides two ints).  dm_scale_run = dm_scale, halved by main() when max_flow > 150
@@ -461,18 +462,25 @@ static int load_ground_truth(const Run &run, std::vector<Flow> &gt) {
     return 0;
 }
 
-// EpicFlow's interpolation of the matches of one window (:801-863 / :960-1004), per single frame step, into wx, wy; SFA_OK or the error
-static int interpolate_matches(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, Image &wx, Image &wy) {
+struct EpicInit { Image wx, wy; int rc = SFA_OK; };     // the initial flow of one window (deep_matching 1)
+// what epic() reads for one window: the matches, the edge map and the L*a*b* frame at the interpolation's resolution ew x eh
+struct EpicInput { epic_matches mt; epic_edges ed; ColorImage lab; int ew = 0, eh = 0; };
+static epic_params_t driver_epic_params() {
+    epic_params_t ep;
+    epic_params_default(&ep);
+    ep.pref_nn = 25; ep.nn = 160; ep.coef_kernel = 1.1f;         // :271-275
+    return ep;
+}
+
+// the inputs of EpicFlow's interpolation of the matches of one window (:801-863 / :960-1004); SFA_OK or the error
+static int epic_inputs(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, EpicInput &in) {
     const int width = seq.width, height = seq.height;
     const double dm_scale = run.dm_scale;
     const JetFrames n = jet_frames(run.start, wd.jet, run.steps, run.skip);
     const int a = n.from, b = n.to, fi = window_tap(wd.jet, wd.backward, run.steps, run.steps, 0);   // fi: un_im[ref] / un_im_back[ref], the reference frame, not normalised
     const color_image_t *un_ref = seq.frames[fi].get();
-    epic_matches mt;
-    epic_edges ed;
-    epic_params_t ep;
-    epic_params_default(&ep);
-    ep.pref_nn = 25; ep.nn = 160; ep.coef_kernel = 1.1f;         // :271-275
+    epic_matches &mt = in.mt;
+    epic_edges &ed = in.ed;
     // the resolution the interpolation runs at: cv::resize(img, img, Size(0, 0), dm_scale, dm_scale) makes cvRound(cols * dm_scale) x cvRound(rows * dm_scale)
     const int ew = dm_scale != 1 ? (int)std::lrint(width * dm_scale) : width, eh = dm_scale != 1 ? (int)std::lrint(height * dm_scale) : height;
     // ... while the reference allocates un_seq / wx and sizes the edge file with the TRUNCATED product (`color_image_new(width*dm_scale, height*dm_scale)`,
@@ -510,9 +518,16 @@ static int interpolate_matches(const Run &run, const Sequence &seq, const Window
         const float v = nearbyintf(un_src->c1[i] * norm);                          // cvRound: to nearest, ties to even
         un8->c1[i] = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);                   // saturate_cast<uchar>
     }
-    const ColorImage lab(rgb_to_lab(un8.get()));
-    wx = zero_image(ew, eh); wy = zero_image(ew, eh);
-    const int er = epic(ctx, wx.get(), wy.get(), lab.get(), mt, ed, &ep);
+    in.lab.reset(rgb_to_lab(un8.get()));
+    in.ew = ew; in.eh = eh;
+    return SFA_OK;
+}
+
+// epic()'s field wx, wy (ew x eh; er: what epic() returned for it) -> the window's initial flow per single frame step; SFA_OK or the error
+static int epic_to_initial_flow(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, int er, Image &wx, Image &wy) {
+    const int width = seq.width, height = seq.height, ew = wx->width, eh = wx->height;
+    const double dm_scale = run.dm_scale;
+    const int a = jet_frames(run.start, wd.jet, run.steps, run.skip).from;
     if (er < 0) return SFA_ERR_HIP;
     if (er > 0) { image_erase(wx.get()); image_erase(wy.get()); }                   // no usable match: start from zero like deep_matching 0
     // :826-843: rescale flow.  fx, fy are quotients of ints; only when fx != 1 is the field resized (cv::resize to the frame's size: the ratio form)
@@ -537,7 +552,37 @@ static int interpolate_matches(const Run &run, const Sequence &seq, const Window
     return SFA_OK;
 }
 
-struct EpicInit { Image wx, wy; int rc = SFA_OK; };     // the initial flow of one window (deep_matching 1)
+// EpicFlow's interpolation of the matches of one window, per single frame step, into wx, wy; SFA_OK or the error
+static int interpolate_matches(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, Image &wx, Image &wy) {
+    EpicInput in;
+    const int rc = epic_inputs(run, seq, wd, ctx, io_mu, in);
+    if (rc != SFA_OK) return rc;
+    const epic_params_t ep = driver_epic_params();
+    wx = zero_image(in.ew, in.eh); wy = zero_image(in.ew, in.eh);
+    return epic_to_initial_flow(run, seq, wd, ctx, io_mu, epic(ctx, wx.get(), wy.get(), in.lab.get(), in.mt, in.ed, &ep), wx, wy);
+}
+
+// the same for the windows [b0, b0 + v.size()) of `mine` at once, through epic_batch: the graph searches of the whole batch in two GPU calls (gpu_epic 1)
+static void interpolate_matches_batch(const Run &run, const Sequence &seq, const std::vector<Window> &todo, const std::vector<size_t> &mine, size_t b0, sfa_ctx *ctx,
+                                      std::mutex &io_mu, std::vector<EpicInit> &v) {
+    std::vector<EpicInput> in(v.size());
+    std::vector<int> use;                                                            // the windows whose inputs are there
+    for (size_t e = 0; e < v.size(); e++)
+        if ((v[e].rc = epic_inputs(run, seq, todo[mine[b0 + e]], ctx, io_mu, in[e])) == SFA_OK) {
+            v[e].wx = zero_image(in[e].ew, in[e].eh); v[e].wy = zero_image(in[e].ew, in[e].eh);
+            use.push_back((int)e);
+        }
+    std::vector<image_t *> fx, fy;
+    std::vector<const color_image_t *> lab;
+    std::vector<const epic_matches *> mt;
+    std::vector<epic_edges *> ed;
+    for (int e : use) { fx.push_back(v[e].wx.get()); fy.push_back(v[e].wy.get()); lab.push_back(in[e].lab.get()); mt.push_back(&in[e].mt); ed.push_back(&in[e].ed); }
+    std::vector<int> er(use.size());
+    const epic_params_t ep = driver_epic_params();
+    epic_batch(ctx, (int)use.size(), fx.data(), fy.data(), lab.data(), mt.data(), ed.data(), &ep, er.data());
+    for (size_t k = 0; k < use.size(); k++) v[use[k]].rc = epic_to_initial_flow(run, seq, todo[mine[b0 + use[k]]], ctx, io_mu, er[k], v[use[k]].wx, v[use[k]].wy);
+}
+
 // everything a finished window hands to the output pool
 struct WindowResult {
     size_t index = 0;                            // into todo
@@ -593,8 +638,9 @@ static void refine_windows(Refinement &rf, const WorkerPlan &wp, sfa_ctx *ctx, s
     int job_nb = 0, rc = SFA_OK;
     auto batch_inits = [&](size_t b0) {
         std::vector<EpicInit> v(std::min((size_t)run.batch, mine.size() - b0));
+        if (run.gpu_epic) interpolate_matches_batch(run, rf.seq, rf.todo, mine, b0, ectx, rf.io_mu, v);
         for (size_t e = 0; e < v.size(); e++)
-            if ((v[e].rc = interpolate_matches(run, rf.seq, rf.todo[mine[b0 + e]], ectx, rf.io_mu, v[e].wx, v[e].wy)) != SFA_OK) {
+            if ((run.gpu_epic ? v[e].rc : v[e].rc = interpolate_matches(run, rf.seq, rf.todo[mine[b0 + e]], ectx, rf.io_mu, v[e].wx, v[e].wy)) != SFA_OK) {
                 std::lock_guard<std::mutex> l(rf.io_mu);
                 std::cerr << "EpicFlow initialisation of jet " << rf.todo[mine[b0 + e]].jet << " failed" << std::endl;
             }
