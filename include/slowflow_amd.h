@@ -128,6 +128,26 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
  * ms[0] initial state and seeds, ms[1] the sweeps, ms[2] the region graph (border count, table, rows), ms[3] the graph search, ms[4] the lists.
  * Copies, allocations and the waits between the stages are not in it (tools/bench_epic_nn.py). */
 int sfa_epic_nn_stage_ms(sfa_ctx *ctx, float ms[5]);
+/* EpicFlow's per-seed model fit and its dense application (epic_aux.cpp:386-497; host/epic.cpp: epic_fit_localaffine, epic_fit_nadarayawatson and the apply
+ * loops of epic()) for n images of one size w x h in one call, on the GPU (csrc/epic_fit.hip).  method 0: locally-weighted affine (LA), 1: Nadaraya-Watson
+ * (NW).  Image i: seeds_xy[i] = 2 * ns[i] ints (x, y); vects[i] = 2 * ns[i] floats; nn_index[i], nn_weight[i] = ns[i] * nn entries, the lists of
+ * sfa_epic_nearest_seeds_batch AFTER the kernel function has been applied to the distances (the epic_nn that epic_fit_localaffine takes: the library forms no
+ * exp, the weights are the caller's bits); labels[i] = w * h ints.  Out: model[i] = ns[i] * 6 (LA) or ns[i] * 2 (NW) floats, or model == NULL; flow_x[i],
+ * flow_y[i] = h rows of `stride` floats, of which columns >= w are not written.  flow_x == flow_y == NULL: only the models are computed, labels may be NULL
+ * and w, h are checked but not used.  Models and flows equal the host code's bit for bit (one lane sums one seed's list in list order; fp64 normal equations;
+ * no fused multiply-add); where NW's weights sum to 0 both give a NaN, whose sign is the platform's.
+ * List entries with an index < 0 are skipped as on the host; entries with an index >= ns[i] are skipped too, and a pixel whose label lies outside
+ * [0, ns[i]) gets 0.0f in both planes: the host code indexes out of bounds in both cases, the values are this library's choice.
+ * Sub-batches, workspace_bytes and status as for sfa_epic_nearest_seeds_batch: everything allocated for a sub-batch stays within workspace_bytes (0: half of
+ * the GPU's free memory); status[i] = 1: image i does not fit even alone, its outputs are untouched and the caller computes it on the host.
+ * Refused with SFA_ERR_ARG, the argument named and nothing launched: n < 1, w or h < 1, nn < 1, an ns[i] < 1, a method other than 0 or 1, stride < w, a null
+ * pointer that is needed (only one of flow_x / flow_y, labels with flows, model without them, any image's own pointer), w * h > 2^29, ns[i] * nn > 2^31 - 1. */
+int sfa_epic_interpolate_batch(sfa_ctx *ctx, int n, int w, int h, int method, const int *const *labels, const int *const *seeds_xy, const float *const *vects,
+                               const int *ns, int nn, const int *const *nn_index, const float *const *nn_weight, float *const *flow_x, float *const *flow_y,
+                               int stride, float *const *model, size_t workspace_bytes, int *status);
+/* The kernel time of the context's last sfa_epic_interpolate_batch in milliseconds, from HIP events, summed over its sub-batches: ms[0] the fit, ms[1] the
+ * dense application.  Copies and allocations are not in it (tools/bench_epic_fit.py). */
+int sfa_epic_fit_stage_ms(sfa_ctx *ctx, float ms[2]);
 /* adaptiveFR's flow-magnitude quantile (adaptiveFR.cpp:644-668) on the GPU.  n host fields (u[i], v[i]: w x h, row stride `stride`); every value is scaled
  * by flow_scale first (one fp32 multiply, image_mul_scalar), m = sqrtf(u*u + v*v) in IEEE fp32; the order statistics are found by an exact radix select
  * over the bit patterns of m.  NaN magnitudes sort above +Inf (their bit order; std::sort has no defined order for them), Inf where it belongs.

@@ -168,7 +168,7 @@ def track_job_bytes(params):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_grid_cut_batch", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_pyramid_down", "sfa_resize_flow", "sfa_job_download_level_frame",
@@ -537,6 +537,65 @@ class Context:
         ms = (C.c_float * 5)()
         self._ck(lib().sfa_epic_nn_stage_ms(self.h, ms), "sfa_epic_nn_stage_ms")
         return dict(zip(("seeds", "sweeps", "graph", "search", "lists"), [float(v) for v in ms]))
+
+    def epic_interpolate(self, labels, seeds, vects, index, weight, method="LA", stride=None, workspace_bytes=0, with_status=False):
+        """EpicFlow's model fit and dense application of a batch (sfa_epic_interpolate_batch).  labels: n int32 (h, w) label maps of one size, or None for
+        the models only; seeds: n int arrays (ns_i, 2); vects: n fp32 (ns_i, 2); index, weight: n arrays (ns_i, nn), the nearest-seeds lists with the kernel
+        function already applied to the distances; method "LA" or "NW".  Returns (flow_x, flow_y, model): lists of fp32 (h, stride) planes (stride: w unless
+        given; columns >= w are not written and hold NaN; None without labels) and fp32 (ns_i, 6) or (ns_i, 2) models -- the bits of the host's
+        epic_fit_localaffine / epic_fit_nadarayawatson and epic()'s apply loops.  An image that does not fit workspace_bytes even alone raises, unless
+        with_status: then a fourth list of ints is returned, 1 for such an image (its arrays are None)"""
+        if method not in ("LA", "NW"):
+            raise SlowflowError("epic_interpolate: method %r (LA or NW)" % (method,))
+        n = len(seeds)
+        seeds = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1, 2) for s in seeds]
+        vects = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 2) for v in vects]
+        index = [np.ascontiguousarray(a, dtype=np.int32) for a in index]
+        weight = [np.ascontiguousarray(a, dtype=np.float32) for a in weight]
+        assert len(vects) == n and len(index) == n and len(weight) == n, "one array of each kind per image"
+        ns = [len(s) for s in seeds]
+        nn = index[0].shape[1] if n else 0
+        for k in range(n):
+            assert len(vects[k]) == ns[k] and index[k].shape == (ns[k], nn) and weight[k].shape == (ns[k], nn), "image %d: vects (ns, 2), index and weight (ns, nn)" % k
+        h, w = 1, 1
+        if labels is not None:
+            labels = [np.ascontiguousarray(a, dtype=np.int32) for a in labels]
+            assert len(labels) == n, "one label map per image"
+            h, w = labels[0].shape if n else (0, 0)
+            for a in labels:
+                assert a.shape == (h, w), "every label map of the batch has one shape"
+        stride = w if stride is None else int(stride)
+        mf = 6 if method == "LA" else 2
+        model = [np.zeros((k, mf), np.float32) for k in ns]
+        L = lib()
+        _i = C.POINTER(C.c_int)
+        L.sfa_epic_interpolate_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f), _i, C.c_int, C.POINTER(_i),
+                                                 C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.c_int, C.POINTER(_f), C.c_size_t, _i]
+        k = max(n, 1)
+        ip = lambda a: a.ctypes.data_as(_i)
+        fx = fy = None
+        if labels is not None:
+            fx = [np.full((h, max(stride, 0)), np.nan, np.float32) for _ in range(n)]
+            fy = [np.full((h, max(stride, 0)), np.nan, np.float32) for _ in range(n)]
+        status = (C.c_int * k)()
+        self._ck(L.sfa_epic_interpolate_batch(self.h, n, w, h, 0 if method == "LA" else 1, (_i * k)(*[ip(a) for a in labels]) if labels is not None else None,
+                                              (_i * k)(*[ip(s) for s in seeds]), (_f * k)(*[fptr(v) for v in vects]), (C.c_int * k)(*ns), int(nn),
+                                              (_i * k)(*[ip(a) for a in index]), (_f * k)(*[fptr(a) for a in weight]),
+                                              (_f * k)(*[fptr(a) for a in fx]) if fx is not None else None, (_f * k)(*[fptr(a) for a in fy]) if fy is not None else None,
+                                              stride, (_f * k)(*[fptr(a) for a in model]), int(workspace_bytes), status), "sfa_epic_interpolate_batch")
+        status = list(status[:n])
+        if with_status:
+            pick = lambda xs: None if xs is None else [None if s else x for x, s in zip(xs, status)]
+            return pick(fx), pick(fy), pick(model), status
+        if any(status):
+            raise SlowflowError("sfa_epic_interpolate_batch: images %s do not fit a workspace of %d bytes" % ([i for i, s in enumerate(status) if s], workspace_bytes))
+        return fx, fy, model
+
+    def epic_fit_stage_ms(self):
+        """the kernel milliseconds of the last epic_interpolate (sfa_epic_fit_stage_ms): fit, apply"""
+        ms = (C.c_float * 2)()
+        self._ck(lib().sfa_epic_fit_stage_ms(self.h, ms), "sfa_epic_fit_stage_ms")
+        return dict(zip(("fit", "apply"), [float(v) for v in ms]))
 
     def flow_magnitude_quantile(self, us, vs, w, flow_scale, q):
         """adaptiveFR's quantile (sfa_flow_magnitude_quantile): the fields' magnitudes after scaling by flow_scale, the rank rule of

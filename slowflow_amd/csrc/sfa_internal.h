@@ -97,6 +97,7 @@ struct sfa_ctx {
     void *q_tmp = nullptr;        // sfa_flow_magnitude_quantiles_device (quantile.hip): group records, histograms and keys, kept from call to call, grown on demand
     size_t q_tmp_bytes = 0;
     float epic_ms[5] = {};        // sfa_epic_nearest_seeds_batch (epic_nn.hip): the last call's kernel time by group (sfa_epic_nn_stage_ms)
+    float epic_fit_ms[2] = {};    // sfa_epic_interpolate_batch (epic_fit.hip): the last call's fit and apply kernel time (sfa_epic_fit_stage_ms)
     hipEvent_t t0 = nullptr, t1 = nullptr;
     hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // sfa_ctx_wait_stream / sfa_ctx_signal_stream: recorded on the caller's / the context's stream
     // the reference's per-iteration "avg change" lines (variational_mt.cpp:404-405, 431-432): sfa_ctx_set_verbose; costs a host round trip per iteration
@@ -121,7 +122,7 @@ struct Switches {
     enum Id {
         SOR_CHAIN, SOR_BAND, SOR_F, SOR_CH, SOR_LEAD, CHAIN_LDS, RB_TILE, WARP_ALLJ, NO_WARP_SMOOTH, ASSEMBLE_GENERIC, EXACT_DIV, ASM_XCD, NO_DIRECT_OPERANDS,
         NO_UV_ALIAS, DEBUG_ACTIVE, UNFUSED, SHARE_SOR, PYRAMID_UNFUSED, CUT_DISCHARGE, CUT_INNER, CUT_SUPER, CUT_TAIL_INNER, CUT_PER, CUT_TAIL_PER, CUT_TAIL_SUPER,
-        CUT_DEBUG, CUT_NO_TAIL, CUT_TAIL, NO_EXACT_BREAK, PAIR_UNFUSED, N
+        CUT_DEBUG, CUT_NO_TAIL, CUT_TAIL, NO_EXACT_BREAK, PAIR_UNFUSED, EPIC_FIT_PLAIN, N
     };
     bool given[N] = {};
     int value[N] = {};

@@ -227,7 +227,7 @@ void epic_nearest_seeds(const std::vector<int> &seeds, const epic_edges &cost, i
 }
 
 // ---- models (epic_aux.cpp:386-497) ------------------------------------------------------------------------------------------------------------
-static void fit_nadarayawatson(std::vector<float> &res, const epic_nn &k, const std::vector<float> &vects) {
+void epic_fit_nadarayawatson(std::vector<float> &res, const epic_nn &k, const std::vector<float> &vects) {
     const int ns = (int)(vects.size() / 2), nn = k.nn;
     res.assign((size_t)ns * 2, 0.f);
     for (int i = 0; i < ns; i++) {
@@ -351,7 +351,7 @@ int epic(sfa_ctx *ctx, image_t *flowx, image_t *flowy, const color_image_t *im, 
         epic_nearest_seeds(seeds, edges, nns, k, labels);
         kernel(k, params->coef_kernel);
         std::vector<float> est;
-        fit_nadarayawatson(est, k, vects);
+        epic_fit_nadarayawatson(est, k, vects);
         std::vector<float> keep;
         for (size_t i = 0; i < m.size() / 4; i++) {
             const float ex = est[2 * i] - vects[2 * i], ey = est[2 * i + 1] - vects[2 * i + 1];
@@ -378,7 +378,7 @@ int epic(sfa_ctx *ctx, image_t *flowx, image_t *flowy, const color_image_t *im, 
             }
     } else if (!strcmp(params->method, "NW")) {                              // :209-213, apply :410-424
         std::vector<float> sv;
-        fit_nadarayawatson(sv, k, vects);
+        epic_fit_nadarayawatson(sv, k, vects);
         for (int j = 0; j < h; j++)
             for (int i = 0; i < w; i++) {
                 const int s = labels[(size_t)j * w + i];
@@ -392,7 +392,7 @@ int epic(sfa_ctx *ctx, image_t *flowx, image_t *flowy, const color_image_t *im, 
     return 0;
 }
 
-// ---- epic_batch: epic() for n images, its two graph searches on the GPU ---------------------------------------------------------------------------------
+// ---- epic_batch: epic() for n images, its two graph searches and its final fit and dense application on the GPU ---------------------------------------------
 namespace {
 struct BatchItem {
     std::vector<float> m;                                                    // the matches still in play
@@ -404,7 +404,9 @@ struct BatchItem {
 
 // epic_nearest_seeds(it.seeds, edges, it.nns, it.k, it.labels) for every image listed in `which`: one sfa_epic_nearest_seeds_batch per group of one size and
 // one nn; an image the library flags as too large for its workspace goes through the host function.  false on a GPU error (sfa_last_error(ctx))
-bool nearest_seeds_batch(sfa_ctx *ctx, const std::vector<int> &which, epic_edges *const *edges, std::vector<BatchItem> &it, size_t workspace_bytes) {
+// the images listed in `which` in groups of one size and one neighbour count, each group in the order of `which`: what one library call takes
+std::vector<std::vector<int>> groups_of_one_shape(const std::vector<int> &which, epic_edges *const *edges, const std::vector<BatchItem> &it) {
+    std::vector<std::vector<int>> groups;
     std::vector<char> taken(which.size(), 0);
     for (size_t a = 0; a < which.size(); a++) {
         if (taken[a]) continue;
@@ -417,6 +419,15 @@ bool nearest_seeds_batch(sfa_ctx *ctx, const std::vector<int> &which, epic_edges
             taken[b] = 1;
             group.push_back(which[b]);
         }
+        groups.push_back(group);
+    }
+    return groups;
+}
+
+bool nearest_seeds_batch(sfa_ctx *ctx, const std::vector<int> &which, epic_edges *const *edges, std::vector<BatchItem> &it, size_t workspace_bytes) {
+    for (const std::vector<int> &group : groups_of_one_shape(which, edges, it)) {
+        const epic_edges &ea = *edges[group[0]];
+        const int nn = it[group[0]].nns;
         const size_t g = group.size();
         std::vector<const float *> cost(g);
         std::vector<const int *> seeds(g);
@@ -438,6 +449,69 @@ bool nearest_seeds_batch(sfa_ctx *ctx, const std::vector<int> &which, epic_edges
             return false;
         for (size_t b = 0; b < g; b++)
             if (status[b]) epic_nearest_seeds(it[group[b]].seeds, *edges[group[b]], nn, it[group[b]].k, it[group[b]].labels);
+    }
+    return true;
+}
+
+// epic()'s last step for one image on the host: the model of every seed from the kernel-weighted lists t.k, and the dense field from the labels
+void interpolate_on_host(const BatchItem &t, bool la, image_t *flowx, image_t *flowy, int w, int h) {
+    if (la) {                                                                // :204-208, apply :479-497
+        std::vector<float> aff;
+        epic_fit_localaffine(aff, t.k, t.seeds, t.vects);
+        for (int j = 0; j < h; j++)
+            for (int x = 0; x < w; x++) {
+                const float *a = &aff[(size_t)t.labels[(size_t)j * w + x] * 6];
+                flowx->data[(size_t)j * flowx->stride + x] = a[0] * x + a[1] * j + a[2] - x;
+                flowy->data[(size_t)j * flowy->stride + x] = a[3] * x + a[4] * j + a[5] - j;
+            }
+    } else {                                                                 // :209-213, apply :410-424
+        std::vector<float> sv;
+        epic_fit_nadarayawatson(sv, t.k, t.vects);
+        for (int j = 0; j < h; j++)
+            for (int x = 0; x < w; x++) {
+                const int s = t.labels[(size_t)j * w + x];
+                flowx->data[(size_t)j * flowx->stride + x] = sv[2 * s];
+                flowy->data[(size_t)j * flowy->stride + x] = sv[2 * s + 1];
+            }
+    }
+}
+
+// interpolate_on_host for every image listed in `which`, on the GPU: one sfa_epic_interpolate_batch per group of one size and one nn (and one row stride of
+// the flow images, which the call takes once); an image the library flags as too large for its workspace, or whose two flow images differ in stride, goes
+// through the host code.  false on a GPU error (sfa_last_error(ctx))
+bool interpolate_batch(sfa_ctx *ctx, const std::vector<int> &which, epic_edges *const *edges, const std::vector<BatchItem> &it, bool la, image_t *const *flowx,
+                       image_t *const *flowy, size_t workspace_bytes) {
+    for (const std::vector<int> &group : groups_of_one_shape(which, edges, it)) {
+        const int w = edges[group[0]]->width, h = edges[group[0]]->height, nn = it[group[0]].nns;
+        std::vector<char> taken(group.size(), 0);
+        for (size_t a = 0; a < group.size(); a++) {
+            if (taken[a]) continue;
+            const int stride = flowx[group[a]]->stride;
+            std::vector<int> part;
+            for (size_t b = a; b < group.size(); b++) {
+                if (taken[b] || flowx[group[b]]->stride != stride) continue;
+                taken[b] = 1;
+                if (flowy[group[b]]->stride != stride) interpolate_on_host(it[group[b]], la, flowx[group[b]], flowy[group[b]], w, h);
+                else part.push_back(group[b]);
+            }
+            const size_t g = part.size();
+            if (!g) continue;
+            std::vector<const int *> labels(g), seeds(g), index(g);
+            std::vector<const float *> vects(g), weight(g);
+            std::vector<float *> fx(g), fy(g);
+            std::vector<int> ns(g), status(g);
+            for (size_t b = 0; b < g; b++) {
+                const BatchItem &t = it[part[b]];
+                ns[b] = (int)(t.seeds.size() / 2);
+                labels[b] = t.labels.data(); seeds[b] = t.seeds.data(); vects[b] = t.vects.data(); index[b] = t.k.index.data(); weight[b] = t.k.dist.data();
+                fx[b] = flowx[part[b]]->data; fy[b] = flowy[part[b]]->data;
+            }
+            if (sfa_epic_interpolate_batch(ctx, (int)g, w, h, la ? 0 : 1, labels.data(), seeds.data(), vects.data(), ns.data(), nn, index.data(), weight.data(), fx.data(),
+                                           fy.data(), stride, nullptr, workspace_bytes, status.data()) != SFA_OK)
+                return false;
+            for (size_t b = 0; b < g; b++)
+                if (status[b]) interpolate_on_host(it[part[b]], la, flowx[part[b]], flowy[part[b]], w, h);
+        }
     }
     return true;
 }
@@ -489,7 +563,7 @@ void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flow
             if (!ok) { rc[i] = -1; continue; }
             kernel(t.k, params->coef_kernel);
             std::vector<float> est, keep;
-            fit_nadarayawatson(est, t.k, t.vects);
+            epic_fit_nadarayawatson(est, t.k, t.vects);
             for (size_t k = 0; k < t.m.size() / 4; k++) {
                 const float ex = est[2 * k] - t.vects[2 * k], ey = est[2 * k + 1] - t.vects[2 * k + 1];
                 if (ex * ex + ey * ey < th2) keep.insert(keep.end(), t.m.begin() + 4 * k, t.m.begin() + 4 * k + 4);
@@ -509,32 +583,18 @@ void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flow
         which.push_back(i);
     }
     const bool ok = which.empty() || nearest_seeds_batch(ctx, which, edges, it, workspace_bytes);
+    const bool la = !strcmp(params->method, "LA");
+    std::vector<int> fit;                                                    // the images whose lists are ready for the models
     for (int i : which) {
-        BatchItem &t = it[i];
         if (!ok) { rc[i] = -1; continue; }
-        const int w = im[i]->width, h = im[i]->height;
-        kernel(t.k, params->coef_kernel);
-        if (!strcmp(params->method, "LA")) {                                 // :204-208, apply :479-497
-            std::vector<float> aff;
-            epic_fit_localaffine(aff, t.k, t.seeds, t.vects);
-            for (int j = 0; j < h; j++)
-                for (int x = 0; x < w; x++) {
-                    const float *a = &aff[(size_t)t.labels[(size_t)j * w + x] * 6];
-                    flowx[i]->data[(size_t)j * flowx[i]->stride + x] = a[0] * x + a[1] * j + a[2] - x;
-                    flowy[i]->data[(size_t)j * flowy[i]->stride + x] = a[3] * x + a[4] * j + a[5] - j;
-                }
-        } else if (!strcmp(params->method, "NW")) {                          // :209-213, apply :410-424
-            std::vector<float> sv;
-            fit_nadarayawatson(sv, t.k, t.vects);
-            for (int j = 0; j < h; j++)
-                for (int x = 0; x < w; x++) {
-                    const int s = t.labels[(size_t)j * w + x];
-                    flowx[i]->data[(size_t)j * flowx[i]->stride + x] = sv[2 * s];
-                    flowy[i]->data[(size_t)j * flowy[i]->stride + x] = sv[2 * s + 1];
-                }
-        } else {
+        if (!la && strcmp(params->method, "NW")) {
             fprintf(stderr, "method %s not recognized\n", params->method);
             rc[i] = 3;
+            continue;
         }
+        kernel(it[i].k, params->coef_kernel);                                // on the host: the weights are libm's expf, bit for bit
+        fit.push_back(i);
     }
+    if (!fit.empty() && !interpolate_batch(ctx, fit, edges, it, la, flowx, flowy, workspace_bytes))
+        for (int i : fit) rc[i] = -1;
 }

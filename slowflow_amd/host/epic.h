@@ -47,8 +47,10 @@ image_t *saliency(sfa_ctx *ctx, const color_image_t *im, float sigma_image, floa
 int epic(sfa_ctx *ctx, image_t *flowx, image_t *flowy, const color_image_t *im_lab, const epic_matches &matches, epic_edges &edges, const epic_params_t *params);
 
 /* epic() for n images at once, stage by stage over the batch: the same steps and the same results, bit for bit, with the two epic_nearest_seeds calls of
- * every image replaced by two sfa_epic_nearest_seeds_batch calls on the GPU of ctx (images of one size and one neighbour count share a call; an image the
- * library reports as too large for its workspace is searched by the host function).  rc[i]: what epic() returns for image i; an image left without matches
+ * every image replaced by two sfa_epic_nearest_seeds_batch calls on the GPU of ctx, and the final model fit and dense application by one
+ * sfa_epic_interpolate_batch call (images of one size and one neighbour count share a call; an image the library reports as too large for its workspace
+ * goes through the host code of that stage).  The kernel weights (expf), the consistency filter's estimate and the compaction of the matches stay on the
+ * host.  rc[i]: what epic() returns for image i; an image left without matches
  * drops out with 1 before the second call.  workspace_bytes: the library's device-memory budget per sub-batch (0: its default).  Needs a context (rc -1 without one). */
 void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flowy, const color_image_t *const *im_lab, const epic_matches *const *matches,
                 epic_edges *const *edges, const epic_params_t *params, int *rc, size_t workspace_bytes = 0);
@@ -59,5 +61,7 @@ struct epic_nn { std::vector<int> index; std::vector<float> dist; int nn = 0; };
 void epic_nearest_seeds(const std::vector<int> &seeds_xy, const epic_edges &cost, int nn, epic_nn &out, std::vector<int> &labels);
 /* least-squares affine model per seed (6 floats: flow-free mapping x' = a0 x + a1 y + a2, y' = a3 x + a4 y + a5) */
 void epic_fit_localaffine(std::vector<float> &affine, const epic_nn &nnw, const std::vector<int> &seeds_xy, const std::vector<float> &vects);
+/* kernel-regression estimate per seed (2 floats: the weighted mean of its neighbours' vectors) */
+void epic_fit_nadarayawatson(std::vector<float> &res, const epic_nn &nnw, const std::vector<float> &vects);
 
 #endif
