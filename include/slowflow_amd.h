@@ -291,6 +291,32 @@ void sfa_fuse_params_default(sfa_fuse_params *p);
 int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, const double *U, const double *V, const double *energy,
                         const unsigned long long *occ_bits, const float *weight, int *slot, double *flow_u, double *flow_v, unsigned char *occ,
                         double *seg_energy, double *seg_bound, int *seg_iters, float *stage_ms);
+/* ---- the steps around dense_tracking's EpicFlow fill-in (dense_tracking.cpp:1265-1310) for n maps of one size w x h in one call, on the GPU
+ * (csrc/fill.hip).  Host pointers; each call waits for its results.  Each refuses with SFA_ERR_ARG, the argument named and nothing launched: n, w or h < 1,
+ * a null pointer, w * h > 2^29 (32-bit pixel indices), more than 65535 maps (planes) in a call, and what is listed with it. -------------------------------
+ * removeSmallSegments(r_consistent, 0.1, 100) (utils/utils.cpp:169-284) on r_consistent = (tracked == r_Jets) (dense_tracking.cpp:1223-1226, 1265).
+ * tracked: [n][h][w] ints (sfa_accumulate_consistent*); full[n]: map i's r_Jets; mask (out): [n][h][w] bytes, 1 where tracked == full[i] and the pixel's
+ * 4-connected component of such pixels has at least min_size pixels, else 0; kept[n] (out): the number of 1s.  The reference's scan order does not matter
+ * (csrc/fill.hip says why), and the mask does not depend on the order of the kernels' atomics.  Also refused: min_size < 1. */
+int sfa_consistent_regions(sfa_ctx *ctx, int n, int w, int h, const int *tracked, const int *full, int min_size, unsigned char *mask, int *kept);
+/* The sample columns (rows) of the fill-in's matches: `for (int x = floor(0.5f * epic_skip); x < extent; x += epic_skip)` with the float epic_skip as the
+ * reference writes it (dense_tracking.cpp:1278-1279), so a non-integer step truncates after every addition.  Host only, no GPU.  out: extent ints or NULL
+ * (count only); *count: the number of samples.  Refused: extent outside 1 .. 2^23 (beyond 2^24 the fp32 sum no
+ * longer advances x), epic_skip outside 1 .. 1e6 (or NaN), count NULL. */
+int sfa_fill_samples(int extent, float epic_skip, int *out, int *count);
+/* The matches of the consistent trajectories (dense_tracking.cpp:1274-1289).  acc_u, acc_v: [n][J][h][w] doubles (sfa_accumulate_consistent* with
+ * all_steps 1; acc_u is the reference's Vec2d[1]); mask: [n][h][w] (sfa_consistent_regions); xs[nx], ys[ny]: the sample columns and rows
+ * (sfa_fill_samples); divisor: acc_skip_pixel + 1.  For map i and step j the samples (ys outer, xs inner) with a non-zero mask become the rows
+ * (float) x, (float) y, (float) (x + acc_u / divisor), (float) (y + acc_v / divisor) of matches[i][j], sum and division in fp64; count[i] (out): the rows,
+ * the same for every j.  matches: [n][J][nx * ny][4] floats, of which only the first count[i] rows of each [i][j] are written.
+ * Also refused: J < 1, nx outside 1 .. w, ny outside 1 .. h, a sample outside the map, divisor < 1. */
+int sfa_fill_matches(sfa_ctx *ctx, int n, int J, int w, int h, const double *acc_u, const double *acc_v, const unsigned char *mask, const int *xs, int nx,
+                     const int *ys, int ny, int divisor, float *matches, int *count);
+/* The interpolated planes as the trajectories of every pixel (dense_tracking.cpp:1299-1310): flow_x[i * J + j], flow_y[i * J + j] = h rows of `stride`
+ * floats, step j of map i (sfa_epic_interpolate_batch); scale: acc_skip_pixel + 1.  Out: acc_u, acc_v [n][J][h][w] = (double) (plane * (float) scale),
+ * tracked [n][h][w] = J -- the input of sfa_hypothesis_energies*.  Also refused: J < 1, n * J > 65535, stride < w, stride * h > 2^29, scale < 1. */
+int sfa_fill_trajectories(sfa_ctx *ctx, int n, int J, int w, int h, int stride, const float *const *flow_x, const float *const *flow_y, int scale,
+                          double *acc_u, double *acc_v, int *tracked);
 /* ---- resident track jobs: dense_tracking's accumulation, energies and fusion of start_jets that stay in GPU memory (csrc/track.hip) -----------
  * A track job owns the device planes of up to n start_jets (segments) x K rates: the flows in the kernels' layout, the frames and their records, the
  * accumulated trajectories, the energies, adapted flows and occlusion words in the fusion's [n][K] layout, the MRF and the fused result.  It takes the

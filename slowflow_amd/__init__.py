@@ -168,7 +168,7 @@ def track_job_bytes(params):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "sfa_consistent_regions", "sfa_fill_samples", "sfa_fill_matches", "sfa_fill_trajectories", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_grid_cut_batch", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_pyramid_down", "sfa_resize_flow", "sfa_job_download_level_frame",
@@ -244,6 +244,18 @@ def accumulate_grid(w, h, skip):
     if rc != 0:
         raise SlowflowError("sfa_accumulate_grid(%d, %d, %d): %s" % (w, h, skip, L.sfa_last_error(None).decode()))
     return gw.value, gh.value
+
+
+def fill_samples(extent, epic_skip):
+    """the sample columns (rows) of the fill-in's matches (sfa_fill_samples; host only, no GPU): the reference's loop `for (int x = floor(0.5f *
+    epic_skip); x < extent; x += epic_skip)` with its float step, as an int32 array"""
+    L = lib()
+    L.sfa_fill_samples.argtypes = [C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int)]
+    out, c = np.zeros(max(int(extent), 1), np.int32), C.c_int()
+    rc = L.sfa_fill_samples(int(extent), float(epic_skip), out.ctypes.data, C.byref(c))
+    if rc != 0:
+        raise SlowflowError("sfa_fill_samples(%d, %r): %s" % (extent, epic_skip, L.sfa_last_error(None).decode()))
+    return out[:c.value].copy()
 
 
 def default_params():
@@ -769,6 +781,59 @@ class Context:
         if stage_ms:
             out["stage_ms"] = ms
         return out
+
+    def consistent_regions(self, tracked, full, min_size=100):
+        """dense_tracking's removeSmallSegments on (tracked == r_Jets) (sfa_consistent_regions) for n maps in one call.  tracked: int32 (n, h, w);
+        full: one int per map, its r_Jets.  Returns (mask, kept): uint8 (n, h, w), 1 where tracked == full and the pixel's 4-connected component of
+        such pixels has at least min_size pixels, and int32 (n,), the number of 1s"""
+        tracked = np.ascontiguousarray(tracked, dtype=np.int32)
+        assert tracked.ndim == 3, "tracked is (n, h, w)"
+        n, h, w = tracked.shape
+        full = np.ascontiguousarray(full, dtype=np.int32).reshape(-1)
+        assert len(full) == n, "one entry of full per map"
+        mask, kept = np.zeros((n, h, w), np.uint8), np.zeros(max(n, 1), np.int32)
+        L = lib()
+        L.sfa_consistent_regions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._ck(L.sfa_consistent_regions(self.h, n, w, h, tracked.ctypes.data, full.ctypes.data, int(min_size), mask.ctypes.data, kept.ctypes.data),
+                 "sfa_consistent_regions")
+        return mask, kept[:n]
+
+    def fill_matches(self, acc_u, acc_v, mask, xs, ys, divisor=1):
+        """the fill-in's matches (sfa_fill_matches).  acc_u, acc_v: float64 (n, J, h, w) as accumulate_consistent(all_steps=True) returns them; mask:
+        uint8 (n, h, w) (consistent_regions); xs, ys: the sample columns and rows (fill_samples); divisor: acc_skip_pixel + 1.  Returns (matches,
+        count): fp32 (n, J, len(xs) * len(ys), 4), rows (x, y, x + u / divisor, y + v / divisor) of the samples with mask 1 in raster order, NaN
+        behind a map's count (those rows are not written), and int32 (n,)"""
+        acc_u, acc_v = np.ascontiguousarray(acc_u, dtype=np.float64), np.ascontiguousarray(acc_v, dtype=np.float64)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert acc_u.ndim == 4 and acc_v.shape == acc_u.shape, "acc_u, acc_v are (n, J, h, w)"
+        n, J, h, w = acc_u.shape
+        assert mask.shape == (n, h, w), "mask is (n, h, w)"
+        xs, ys = np.ascontiguousarray(xs, dtype=np.int32).reshape(-1), np.ascontiguousarray(ys, dtype=np.int32).reshape(-1)
+        matches = np.full((n, J, len(xs) * len(ys), 4), np.nan, np.float32)
+        count = np.zeros(max(n, 1), np.int32)
+        L = lib()
+        L.sfa_fill_matches.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._ck(L.sfa_fill_matches(self.h, n, J, w, h, acc_u.ctypes.data, acc_v.ctypes.data, mask.ctypes.data, xs.ctypes.data, len(xs), ys.ctypes.data,
+                                    len(ys), int(divisor), matches.ctypes.data, count.ctypes.data), "sfa_fill_matches")
+        return matches, count[:n]
+
+    def fill_trajectories(self, flow_x, flow_y, w, scale=1):
+        """the interpolated planes as trajectories (sfa_fill_trajectories).  flow_x, flow_y: fp32 (n, J, h, stride), only the w valid columns read;
+        scale: acc_skip_pixel + 1.  Returns (acc_u, acc_v, tracked): float64 (n, J, h, w) = plane * float(scale) widened, int32 (n, h, w) = J -- the
+        inputs of hypothesis_energies"""
+        flow_x, flow_y = np.ascontiguousarray(flow_x, dtype=np.float32), np.ascontiguousarray(flow_y, dtype=np.float32)
+        assert flow_x.ndim == 4 and flow_y.shape == flow_x.shape, "flow_x, flow_y are (n, J, h, stride)"
+        n, J, h, stride = flow_x.shape
+        w = int(w)
+        acc_u, acc_v = np.zeros((n, J, h, max(w, 0)), np.float64), np.zeros((n, J, h, max(w, 0)), np.float64)
+        tracked = np.zeros((n, h, max(w, 0)), np.int32)
+        L = lib()
+        L.sfa_fill_trajectories.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(_f), C.POINTER(_f), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        k = max(n * J, 1)
+        px, py = ((_f * k)(*[fptr(a[s, j]) for s in range(n) for j in range(J)]) for a in (flow_x, flow_y))
+        self._ck(L.sfa_fill_trajectories(self.h, n, J, w, h, stride, px, py, int(scale), acc_u.ctypes.data, acc_v.ctypes.data, tracked.ctypes.data),
+                 "sfa_fill_trajectories")
+        return acc_u, acc_v, tracked
 
     def compute_one_level(self, p, wx, wy, frames, w, chw=None, want_occ=False):
         return self._run(lib().sfa_compute_one_level, "sfa_compute_one_level", p, wx, wy, frames, w, chw, want_occ)

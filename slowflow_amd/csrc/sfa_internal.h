@@ -253,6 +253,21 @@ struct FuseWork {
 // zeroes the messages and labellings of the n segments, then k_fuse_labels, k_fuse_pairwise, k_trws, k_fuse_output.  ev: null or 5 events recorded around the four
 int fuse_device(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, int gw, int gh, const FuseWork &f, hipEvent_t *ev);
 
+// ---- the steps around dense_tracking's EpicFlow fill-in at device level (fill.hip), in the same form: device pointers in, launches on the context's
+// stream out; no allocation, no copy, no wait.  The sfa_consistent_regions / sfa_fill_matches / sfa_fill_trajectories entry points wrap them -------------
+// tracked: [n][h][w], full: [n] (device); scratch T, P, S: [n][h][w] ints each; mask: [n][h][w] bytes, kept: [n]
+int consistent_regions_device(sfa_ctx *ctx, int n, int w, int h, const int *tracked, const int *full, int min_size, int *T, int *P, int *S, unsigned char *mask,
+                              int *kept);
+// the entries of fill_matches_device's block_count per map
+size_t fill_matches_blocks(int nx, int ny);
+// acc_u, acc_v: [n][J][h][w]; mask: [n][h][w]; xs: [nx], ys: [ny] (device, on the map); block_count: [n][fill_matches_blocks(nx, ny)] scratch; matches:
+// [n][J][nx ny][4], of which map m's first count[m] rows of every step are written; count: [n]
+int fill_matches_device(sfa_ctx *ctx, int n, int J, int w, int h, const double *acc_u, const double *acc_v, const unsigned char *mask, const int *xs, int nx,
+                        const int *ys, int ny, int divisor, int *block_count, float *matches, int *count);
+// flow_x, flow_y: [n J][h][stride]; acc_u, acc_v: [n][J][h][w]; tracked: [n][h][w]
+int fill_trajectories_device(sfa_ctx *ctx, int n, int J, int w, int h, int stride, const float *flow_x, const float *flow_y, int scale, double *acc_u,
+                             double *acc_v, int *tracked);
+
 // ---------------------------------------------------------------------------------------------------
 // kernel launchers (kernels.hip).  All planes are device pointers of batch element 0; element b lives
 // `es` floats further (es = 0 for a single element).  `nb` = batch size, `active` = bit mask of the

@@ -28,7 +28,13 @@
 // -energies / -fuse (after center / extent and scale); in the plain mode the jets' common size, or, where the rates differ, the size of the ingested
 // frame at sequence_start.  Refused: a rate whose rescaled size is not the target, a crop outside a flow, occlusions together with center.
 //
-// Out of scope (FLANN, GSL, OpenCV are not in this tree): EpicFlow's fill-in and the neighbour proposals, removeSmallSegments.
+// With -fill (implies -fuse) every rate also gets dense_tracking's EpicFlow fill-in hypothesis (:1265-1350): the rate's consistent trajectories,
+// interpolated to every pixel at every step (epic_fill_rate, host/epic_fill.h), scored like any other hypothesis and fused with the accumulated ones in
+// the reference's push order (slot 2 r: rate r accumulated, slot 2 r + 1: rate r filled in), so that the fused flow has no holes.  It reads
+// <output>/accumulated/tmp/edges_<sequence_start>.dat (the reference's name, :945; read_edges' format) and runs start_jet by start_jet through the
+// library's stage calls, not through the track job.  acc_skip_pixel 0 only; at most 8 rates.
+//
+// Out of scope (FLANN, GSL, OpenCV are not in this tree): the neighbour proposals.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -36,11 +42,13 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <map>
 #include <sstream>
 #include <string>
 #include <vector>
 
+#include "epic_fill.h"
 #include "flow_vis.h"
 #include "image.h"
 #include "ingest.h"
@@ -54,13 +62,13 @@ using std::vector;
 
 static void usage() {
     printf("usage:\n");
-    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies -fuse\n");
+    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies -fuse -fill\n");
     printf("    ./accumulate -decode_occlusion [occlusion .pgm / .pbm] [mask .pgm]   (the mask this program uses: median 3x3, 255 - x; 0 = occluded)\n");
     printf("\n");
     printf("Runs dense_tracking's first stage only: consistent accumulation of the jets (accumulateConsistentBatches).  cfg keys read: jet_estimation\n");
     printf("(repeated), jet_S, jet_fps, jet_weight, flow_format, start, ref_fps, ref_fps_F, max_fps, acc_min_fps, acc_skip_pixel, acc_use_jet_occlusions\n");
-    printf("(or acc_occlusion), acc_discard_inconsistent, acc_consistency_threshold, output, sintel, subframes, center, extent.  Not done: EpicFlow's\n");
-    printf("fill-in and removeSmallSegments.  A missing input file exits with status 2.\n");
+    printf("(or acc_occlusion), acc_discard_inconsistent, acc_consistency_threshold, output, sintel, subframes, center, extent.  A missing input file exits\n");
+    printf("with status 2.\n");
     printf("\n");
     printf("Jets of another size than the target are cropped (center / extent), resized by (1.0f * W) / cw and multiplied by it on the GPU, as dense_tracking\n");
     printf("does.  The target W x H: with -energies / -fuse the ingested frames' size; else the jets' common size, or where the rates differ the size of the\n");
@@ -78,6 +86,12 @@ static void usage() {
     printf("occlusions/frame_<start>.pgm and labels_<start>.pgm.  Keys: acc_beta, acc_spatial_occ, acc_traj_sim_method, acc_traj_sim_thres, acc_trws_eps,\n");
     printf("acc_trws_max_iter, 16bit, img_norm_avg_*, img_norm_std_*.  Refused: acc_approach 1, acc_traj_sim_method 2, a width that is not a multiple\n");
     printf("of 4, more than 16 rates.  EpicFlow's fill-in and the neighbour proposals (acc_epic_interpolation) are not run.\n");
+    printf("\n");
+    printf("-fill: implies -fuse, and adds EpicFlow's fill-in hypothesis of every rate (removeSmallSegments on the consistent pixels, their matches at\n");
+    printf("every acc_epic_skip-th pixel, one batch of EpicFlow interpolations per rate) to the fusion: slot 2 r is rate r's accumulated hypothesis, slot\n");
+    printf("2 r + 1 its fill-in; labels_<start>.pgm holds the slot.  Reads <output>/accumulated/tmp/edges_<start>.dat (w * h floats; a missing one exits\n");
+    printf("with status 2), so the output folder exists beforehand: run it with -resume.  Key: acc_epic_skip (2).  Refused: acc_skip_pixel other than 0,\n");
+    printf("more than 8 rates, acc_epic_interpolation 0.  The neighbour proposals are not run.\n");
 }
 
 // dense_tracking.cpp:1183-1193 for a file of the flows' size: medianBlur(3) with OpenCV's border for ksize 3 (replicate; OpenCV is absent here, so this
@@ -109,6 +123,7 @@ struct Run {
     double threshold = 1;
     bool discard = true, use_occ = false, sintel = false;
     bool energies = false, fuse = false;     // -energies, -fuse (implies -energies)
+    bool fill = false;                       // -fill (implies -fuse)
     string flow_format, acc_dir;             // flow_format without its extension; <output>/accumulated/
     bool crop_flows = false, crop_frames = false;   // center.x > 0 (:1135); extent.x > 0 || extent.y > 0 (:876)
     int cx = 0, cy = 0, ex = 0, ey = 0;      // center, extent
@@ -387,12 +402,10 @@ struct Fusion {
 
 // one start_jet's fused result out of the track job (:1588-1905 ran on the GPU): writes the fused flow (u(Jets - 1) / xy_incr, 1e10 without a node), its
 // colour coding, the occlusions and the labels.  fu: the record with the group's figures filled in
-static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run, Fusion &fz, Fusion::Record fu, int gw, int gh) {
+// the fused planes of one start_jet as files; slots: the label slots of the fusion (the rates; with -fill two per rate)
+static bool write_fused_planes(const Run &run, Fusion &fz, Fusion::Record fu, int gw, int gh, int slots, const vector<int> &slot, const vector<double> &flu,
+                               const vector<double> &flv, const vector<unsigned char> &oc) {
     const size_t gpl = (size_t)gw * gh;
-    vector<int> slot(gpl);
-    vector<double> flu(gpl), flv(gpl);
-    vector<unsigned char> oc(gpl);
-    if (!sfa_ok(ctx, sfa_track_job_download_fused(job, k, slot.data(), flu.data(), flv.data(), oc.data(), nullptr, &fu.energy, &fu.bound, &fu.iters))) return false;
     image_t *u = image_new(gw, gh), *v = image_new(gw, gh);
     vector<unsigned char> lp(gpl), op(gpl);
     for (int y = 0; y < gh; y++)
@@ -400,7 +413,7 @@ static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run,
             const size_t i = (size_t)y * gw + x;
             u->data[(size_t)y * u->stride + x] = (float)flu[i];   // writeFlowMiddlebury's fp32 (utils.cpp:333); 1e10 without a node
             v->data[(size_t)y * v->stride + x] = (float)flv[i];
-            lp[i] = slot[i] < 0 ? 255 : (unsigned char)slot[i];     // slot k of the job is rate k
+            lp[i] = slot[i] < 0 ? 255 : (unsigned char)slot[i];     // slot k is rate k; with -fill rate k / 2, accumulated (even) or filled in (odd)
             op[i] = oc[i] ? 255 : 0;                                // convertTo(CV_8UC1, 255) (:1893)
             fu.nodes += slot[i] >= 0;
         }
@@ -411,10 +424,52 @@ static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run,
                     write_pgm8(run.acc_dir + "labels_" + std::to_string(fu.seq_start) + ".pgm", gw, gh, lp.data(), gw);
     if (!ok) std::cerr << "cannot write the fused outputs of start " << fu.seq_start << " under " << run.acc_dir << std::endl;
     image_delete(u); image_delete(v);
-    std::cout << "start " << fu.seq_start << ": fused " << run.rates << " rate(s) over " << fu.nodes << " nodes, energy " << fu.energy << ", lower bound "
+    std::cout << "start " << fu.seq_start << ": fused " << slots << (run.fill ? " slot(s) over " : " rate(s) over ") << fu.nodes << " nodes, energy " << fu.energy << ", lower bound "
               << fu.bound << ", " << fu.iters << " TRW-S iteration(s)" << std::endl;
     fz.done.push_back(fu);
     return ok;
+}
+
+static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run, Fusion &fz, Fusion::Record fu, int gw, int gh) {
+    const size_t gpl = (size_t)gw * gh;
+    vector<int> slot(gpl);
+    vector<double> flu(gpl), flv(gpl);
+    vector<unsigned char> oc(gpl);
+    if (!sfa_ok(ctx, sfa_track_job_download_fused(job, k, slot.data(), flu.data(), flv.data(), oc.data(), nullptr, &fu.energy, &fu.bound, &fu.iters))) return false;
+    return write_fused_planes(run, fz, fu, gw, gh, (int)run.rates, slot, flu, flv, oc);
+}
+
+// the energies' keys: setDefault (:118-165), in the types of :606-623 and :661-675
+static void read_energy_params(ParameterList &params, sfa_energy_params &ep) {
+    ep.acc_jc = params.parameter<float>("acc_jet_consistency", "1.0");
+    ep.acc_bc = params.parameter<float>("acc_brightness_constancy", "0.1");
+    ep.acc_gc = params.parameter<float>("acc_gradient_constancy", "1.0");
+    ep.acc_occ = params.parameter<float>("acc_occlusion_penalty", "500.0");
+    ep.acc_temporal_occ = params.parameter<double>("acc_temporal_occ", "10.0");
+    ep.acc_cv = params.parameter<double>("acc_cv", "0.0");
+    ep.occlusion_threshold = params.parameter<float>("acc_occlusion_threshold", "5.0");
+    ep.occlusion_fb_threshold = params.parameter<float>("acc_occlusion_fb_threshold", "5.0");
+    ep.penalty = params.parameter<int>("acc_penalty_fct_data", "1");
+    ep.penalty_eps = params.parameter<double>("acc_penalty_fct_data_eps", "0.001");
+}
+
+// the fusion's keys and the smoothness weight's statistics
+static void read_fusion(ParameterList &params, const Run &run, Fusion &fz) {
+    sfa_fuse_params_default(&fz.fup);
+    fz.fup.acc_beta = params.parameter<double>("acc_beta", "10.0");
+    fz.fup.acc_spatial_occ = params.parameter<double>("acc_spatial_occ", "10.0");   // setDefault's "acc_satial_occ" never reaches this key
+    fz.fup.traj_sim_method = params.parameter<int>("acc_traj_sim_method", "1");
+    fz.fup.traj_sim_thres = params.parameter<double>("acc_traj_sim_thres", "0.1");
+    fz.fup.trws_eps = params.parameter<double>("acc_trws_eps", "1e-5");
+    fz.fup.trws_max_iter = params.parameter<int>("acc_trws_max_iter", "10");
+    fz.fup.skip = run.skip_pixel;
+    // the reference reads img_norm_* (defaults 0 / 1, :971-972), keys normalize() does not publish (it writes slow_flow_img_norm_*), so by default
+    // the weight is taken from the normalised frame itself
+    for (int k = 0; k < 3; k++) {
+        fz.nav[k] = (float)params.parameter<double>("img_norm_avg_" + std::to_string(k + 1), "0");
+        fz.nsd[k] = (float)params.parameter<double>("img_norm_std_" + std::to_string(k + 1), "1");
+    }
+    fz.hbit = params.parameter<bool>("16bit", "0") ? 1 : 0;
 }
 
 // the track job of the run: B start_jets x all rates.  acc_gpu_batch given: that B or status 1; absent: the largest B <= 16 and <= todo whose job takes at most
@@ -453,33 +508,11 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                         const std::map<unsigned, vector<string>> &frame_files, vector<sfa_jet_source> &geo) {
     sfa_track_params tp;
     sfa_track_params_default(&tp);
-    sfa_energy_params &ep = tp.energy;                                    // setDefault (:118-165), in the types of :606-623 and :661-675
-    ep.acc_jc = params.parameter<float>("acc_jet_consistency", "1.0");
-    ep.acc_bc = params.parameter<float>("acc_brightness_constancy", "0.1");
-    ep.acc_gc = params.parameter<float>("acc_gradient_constancy", "1.0");
-    ep.acc_occ = params.parameter<float>("acc_occlusion_penalty", "500.0");
-    ep.acc_temporal_occ = params.parameter<double>("acc_temporal_occ", "10.0");
-    ep.acc_cv = params.parameter<double>("acc_cv", "0.0");
-    ep.occlusion_threshold = params.parameter<float>("acc_occlusion_threshold", "5.0");
-    ep.occlusion_fb_threshold = params.parameter<float>("acc_occlusion_fb_threshold", "5.0");
-    ep.penalty = params.parameter<int>("acc_penalty_fct_data", "1");
-    ep.penalty_eps = params.parameter<double>("acc_penalty_fct_data_eps", "0.001");
+    read_energy_params(params, tp.energy);
     Fusion fz;
-    sfa_fuse_params_default(&fz.fup);
-    fz.fup.acc_beta = params.parameter<double>("acc_beta", "10.0");
-    fz.fup.acc_spatial_occ = params.parameter<double>("acc_spatial_occ", "10.0");   // setDefault's "acc_satial_occ" never reaches this key
-    fz.fup.traj_sim_method = params.parameter<int>("acc_traj_sim_method", "1");
-    fz.fup.traj_sim_thres = params.parameter<double>("acc_traj_sim_thres", "0.1");
-    fz.fup.trws_eps = params.parameter<double>("acc_trws_eps", "1e-5");
-    fz.fup.trws_max_iter = params.parameter<int>("acc_trws_max_iter", "10");
-    fz.fup.skip = run.skip_pixel;
-    // the reference reads img_norm_* (defaults 0 / 1, :971-972), keys normalize() does not publish (it writes slow_flow_img_norm_*), so by default
-    // the weight is taken from the normalised frame itself
-    for (int k = 0; k < 3; k++) {
-        fz.nav[k] = tp.avg[k] = (float)params.parameter<double>("img_norm_avg_" + std::to_string(k + 1), "0");
-        fz.nsd[k] = tp.std_dev[k] = (float)params.parameter<double>("img_norm_std_" + std::to_string(k + 1), "1");
-    }
-    fz.hbit = tp.hbit = params.parameter<bool>("16bit", "0") ? 1 : 0;
+    read_fusion(params, run, fz);
+    for (int k = 0; k < 3; k++) { tp.avg[k] = fz.nav[k]; tp.std_dev[k] = fz.nsd[k]; }
+    tp.hbit = fz.hbit;
     tp.fuse = fz.fup;
     tp.K = (int)run.rates; tp.Jets = (int)run.Jets; tp.min_fps_idx = run.min_fps_idx; tp.do_fuse = run.fuse ? 1 : 0; tp.use_occlusions = run.use_occ ? 1 : 0;
     tp.epsilon = run.threshold; tp.skip = run.skip_pixel; tp.discard = run.discard ? 1 : 0;
@@ -639,6 +672,192 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     return ok ? 0 : 1;
 }
 
+// the edge map of a start_jet (:945)
+static string edges_file(const Run &run, unsigned seq_start) { return run.acc_dir + "tmp/edges_" + std::to_string(seq_start) + ".dat"; }
+
+// -fill: start_jet by start_jet through the stage calls.  Per rate: accumulation with all steps, the fill-in trajectories (epic_fill_rate), the energies
+// of both with the rate's weight and rate acc_min_fps's flows; then one fusion over 2 x rates slots in the reference's push order (:1242, 1322).  A rate
+// whose fill-in keeps no match leaves its odd slot empty (+Inf).  Writes what -fuse writes, and the fill-in's figures into run.json
+static int run_fill(ParameterList &params, const Run &run, vector<Segment> &segs, const vector<string> &skipped,
+                    const std::map<unsigned, vector<string>> &frame_files, vector<sfa_jet_source> &geo) {
+    sfa_energy_params ep;
+    sfa_energy_params_default(&ep);
+    read_energy_params(params, ep);
+    ep.skip = run.skip_pixel;
+    Fusion fz;
+    read_fusion(params, run, fz);
+    const float epic_skip = params.parameter<float>("acc_epic_skip", "2");   // :651
+    epic_params_t eparams;
+    epic_fill_params(&eparams);
+    sfa_ctx *ctx = nullptr;
+    if (!segs.empty() && !sfa_ok(nullptr, sfa_ctx_create(0, &ctx))) return 1;
+    struct RateFill { unsigned seq_start; int r; epic_fill_stats st; };
+    vector<RateFill> fills;
+    const int K = (int)run.rates, S = 2 * K, J = (int)run.Jets;
+    int width = 0, height = 0, status = 0, gw = 0, gh = 0;
+    double t_frames = 0, t_acc = 0, t_fill = 0, t_energy = 0, t_fuse = 0, t_io = 0;
+    const double t0 = now_s();
+    for (auto it = frame_files.begin(); it != frame_files.end() && status == 0; ++it) {
+        const unsigned seq_start = it->first;
+        vector<size_t> mine;
+        for (size_t i = 0; i < segs.size(); i++)
+            if (segs[i].seq_start == seq_start) mine.push_back(i);
+        double ta = now_s();
+        vector<color_image_t *> fr;
+        struct Frames { vector<color_image_t *> &f; color_image_t *lab; ~Frames() { for (color_image_t *c : f) color_image_delete(c); if (lab) color_image_delete(lab); } } frames{fr, nullptr};
+        for (const string &name : it->second) {
+            color_image_t *img = ingest_frame(params, run, ctx, name);
+            if (!img) { status = 1; break; }
+            fr.push_back(img);
+            if (fr.size() == 1 && width == 0) { width = img->width; height = img->height; }
+            if (img->width != width || img->height != height) {
+                std::cerr << name << " is " << img->width << " x " << img->height << ", not " << width << " x " << height << " like the first frame" << std::endl;
+                status = 1;
+                break;
+            }
+        }
+        if (status) break;
+        if (!fit_rates(geo, width, height)) { status = 1; break; }
+        if ((int)mine.size() != K) { std::cerr << "start " << seq_start << ": " << mine.size() << " of " << K << " rates to do" << std::endl; status = 1; break; }
+        if (width % 4 != 0) { std::cerr << "-fuse: width " << width << " is not a multiple of 4 (the reference's smoothness-weight index reads padding)" << std::endl; status = 1; break; }
+        frames.lab = rgb8_to_lab(fr[0], fz.hbit ? 1.0f / 255 : 1.0f);         // :931, 947-955: the 8-bit copy of frame 0, before the normalisation
+        const int stride = fr[0]->stride;
+        vector<float *> fp;
+        for (color_image_t *c : fr) fp.push_back(c->c1);
+        double avg[3], sd[3];
+        if (!sfa_ok(ctx, sfa_normalize(ctx, fp.data(), (int)fp.size(), width, height, stride, avg, sd)) ||
+            !sfa_ok(nullptr, sfa_accumulate_grid(width, height, run.skip_pixel, &gw, &gh))) { status = 1; break; }
+        vector<const float *> cfp(fp.begin(), fp.end());
+        epic_edges edges;
+        if (!read_edges(edges_file(run, seq_start).c_str(), gw, gh, edges)) {
+            std::cerr << edges_file(run, seq_start) << " does not hold " << gw << " x " << gh << " floats" << std::endl;
+            status = 2;
+            break;
+        }
+        t_frames += now_s() - ta;
+        double tb = now_s();
+        vector<SegmentInput> in(mine.size());
+        for (size_t k = 0; k < mine.size() && status == 0; k++)
+            if (!read_segment(segs[mine[k]], run.use_occ, geo[segs[mine[k]].r], in[k]) || in[k].fu.empty()) status = 1;
+        t_io += now_s() - tb;
+        if (status) break;
+        const size_t gpl = (size_t)gw * gh;
+        const double inf = std::numeric_limits<double>::infinity();
+        vector<double> U((size_t)S * J * gpl, 0.0), V((size_t)S * J * gpl, 0.0), E((size_t)S * gpl, inf);
+        vector<unsigned long long> O((size_t)S * gpl, 0);
+        const SegmentInput &mf = in[(size_t)run.min_fps_idx];                // mine is in rate order: rate acc_min_fps's flows
+        int call_index = 0;
+        for (size_t k = 0; k < mine.size() && status == 0; k++) {
+            Segment &s = segs[mine[k]];
+            const int r = s.r, FF = s.FF;
+            vector<double> au((size_t)FF * gpl), av((size_t)FF * gpl), hu((size_t)FF * gpl), hv((size_t)FF * gpl);
+            vector<int> tracked(gpl), htracked(gpl);
+            double tc = now_s();
+            if (!sfa_ok(ctx, sfa_accumulate_consistent_scaled(ctx, 1, FF, width, height, &geo[r], in[k].fu.data(), in[k].fv.data(), in[k].bu.data(), in[k].bv.data(),
+                                                              run.use_occ ? in[k].mp.data() : nullptr, run.threshold, run.skip_pixel, run.discard ? 1 : 0, 1,
+                                                              au.data(), av.data(), tracked.data(), nullptr))) { status = 1; break; }
+            t_acc += now_s() - tc;
+            tc = now_s();
+            RateFill rf{seq_start, r, {0, 0, 0}};
+            call_index = epic_fill_rate(ctx, gw, gh, FF, run.skip_pixel, epic_skip, au.data(), av.data(), tracked.data(), frames.lab, edges, &eparams, call_index,
+                                        hu.data(), hv.data(), htracked.data(), &rf.st);
+            if (call_index < 0) { std::cerr << "the fill-in of rate " << r << ", start " << seq_start << " failed: " << sfa_last_error(ctx) << std::endl; status = 1; break; }
+            fills.push_back(rf);
+            t_fill += now_s() - tc;
+            tc = now_s();
+            ep.weight = run.jet_weight.size() > (size_t)r ? (float)run.jet_weight[r] : (float)r;   // weight_jet_estimation, vector<float> (:489-495)
+            const bool flows = r >= run.min_fps_idx;                          // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
+            for (int kind = 0; kind < 2 && status == 0; kind++) {             // the accumulated hypothesis (:1242), then the fill-in (:1322)
+                if (kind == 1 && !rf.st.filled) continue;
+                const size_t slot = 2 * (size_t)r + kind;
+                if (!sfa_ok(ctx, sfa_hypothesis_energies_scaled(ctx, &ep, 1, FF, J, width, height, stride, kind ? hu.data() : au.data(), kind ? hv.data() : av.data(),
+                                                                kind ? htracked.data() : tracked.data(), cfp.data(), &geo[(size_t)run.min_fps_idx],
+                                                                flows ? mf.fu.data() : nullptr, flows ? mf.fv.data() : nullptr, flows ? mf.bu.data() : nullptr,
+                                                                flows ? mf.bv.data() : nullptr, E.data() + slot * gpl, O.data() + slot * gpl,
+                                                                U.data() + slot * J * gpl, V.data() + slot * J * gpl))) status = 1;
+            }
+            t_energy += now_s() - tc;
+            if (status) break;
+            // the rate's own files, as -energies writes them
+            double td = now_s();
+            vector<float> ef(gpl);
+            vector<unsigned char> oc(gpl);
+            for (size_t p = 0; p < gpl; p++) {
+                ef[p] = (float)E[2 * (size_t)r * gpl + p];
+                oc[p] = (unsigned char)__builtin_popcountll(O[2 * (size_t)r * gpl + p]);
+            }
+            const string dir = run.acc_dir + std::to_string(r) + "/";
+            if (!write_last_step(s, au.data() + (size_t)(FF - 1) * gpl, av.data() + (size_t)(FF - 1) * gpl, tracked.data(), gw, gh) ||
+                !write_pfm(dir + "energy_" + std::to_string(seq_start) + ".pfm", gw, gh, ef.data()) ||
+                !write_pgm8(dir + "occluded_" + std::to_string(seq_start) + ".pgm", gw, gh, oc.data(), gw)) {
+                std::cerr << "cannot write the outputs of rate " << r << " under " << dir << std::endl;
+                status = 1;
+            }
+            std::cout << "rate " << r << ", start " << seq_start << ": fill-in from " << rf.st.kept_pixels << " consistent pixels, " << rf.st.matches << " matches per step"
+                      << (rf.st.filled ? "" : ": no fill-in hypothesis") << std::endl;
+            t_io += now_s() - td;
+        }
+        if (status) break;
+        // the fusion over the 2 K slots
+        double te = now_s();
+        vector<float> weight((size_t)width * height);
+        vector<int> slot(gpl);
+        vector<double> flu(gpl), flv(gpl);
+        vector<unsigned char> foc(gpl);
+        Fusion::Record fu{};
+        fu.seq_start = seq_start; fu.group = (int)fz.done.size(); fu.group_size = 1;
+        double tw = now_s();
+        if (!sfa_ok(ctx, sfa_dt_smoothness_weight(ctx, width, height, stride, fr[0]->c1, 5.0f, fz.nav, fz.nsd, fz.hbit, weight.data()))) { status = 1; break; }
+        fu.t_weight = now_s() - tw;
+        if (!sfa_ok(ctx, sfa_fuse_hypotheses(ctx, &fz.fup, 1, S, J, width, height, U.data(), V.data(), E.data(), O.data(), weight.data(), slot.data(), flu.data(),
+                                             flv.data(), foc.data(), &fu.energy, &fu.bound, &fu.iters, fu.stage_ms))) { status = 1; break; }
+        fu.t_fuse = now_s() - te - fu.t_weight;
+        t_fuse += now_s() - te;
+        double td = now_s();
+        if (!write_fused_planes(run, fz, fu, gw, gh, S, slot, flu, flv, foc)) { status = 1; break; }
+        vector<unsigned char> best(gpl, 255);                                // the rate of the lowest fp32 energy among the accumulated hypotheses, ties to the lower
+        for (size_t p = 0; p < gpl; p++) {
+            float lowest = std::numeric_limits<float>::infinity();
+            for (int r = 0; r < K; r++) {
+                const float e = (float)E[2 * (size_t)r * gpl + p];
+                if (e < lowest) { lowest = e; best[p] = (unsigned char)r; }
+            }
+        }
+        if (!write_pgm8(run.acc_dir + "best_" + std::to_string(seq_start) + ".pgm", gw, gh, best.data(), gw)) {
+            std::cerr << "cannot write " << run.acc_dir << "best_" << seq_start << ".pgm" << std::endl;
+            status = 1;
+        }
+        t_io += now_s() - td;
+    }
+    if (ctx) sfa_ctx_destroy(ctx);
+    if (status) return status;
+    std::ostringstream tail;
+    tail.precision(17);
+    const sfa_fuse_params &fup = fz.fup;
+    tail << ",\n  \"fused\": true, \"epic_fill\": true, \"epic_interpolation\": true, \"neighbour_proposals\": false, \"acc_epic_skip\": " << (double)epic_skip
+         << ", \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": " << fup.acc_spatial_occ << ", \"acc_traj_sim_method\": " << fup.traj_sim_method
+         << ", \"acc_traj_sim_thres\": " << fup.traj_sim_thres << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter
+         << ",\n  \"slots\": [";
+    for (int k = 0; k < S; k++) tail << (k ? ", " : "") << "{\"slot\": " << k << ", \"rate\": " << k / 2 << ", \"kind\": \"" << (k % 2 ? "epic_fill" : "accumulated") << "\"}";
+    tail << "],\n  \"fill\": [";
+    for (size_t i = 0; i < fills.size(); i++)
+        tail << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << fills[i].seq_start << ", \"rate\": " << fills[i].r << ", \"kept_pixels\": " << fills[i].st.kept_pixels
+             << ", \"matches\": " << fills[i].st.matches << ", \"filled\": " << (fills[i].st.filled ? "true" : "false") << "}";
+    tail << "],\n  \"fusion\": [";
+    for (size_t i = 0; i < fz.done.size(); i++) {
+        const Fusion::Record &f = fz.done[i];
+        tail << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << f.seq_start << ", \"nodes\": " << f.nodes << ", \"energy\": " << f.energy
+             << ", \"lower_bound\": " << f.bound << ", \"iterations\": " << f.iters << ", \"weight_s\": " << f.t_weight << ", \"fuse_call_s\": " << f.t_fuse
+             << ", \"kernels_ms\": {\"labels\": " << f.stage_ms[0] << ", \"pairwise\": " << f.stage_ms[1] << ", \"trws\": " << f.stage_ms[2]
+             << ", \"output\": " << f.stage_ms[3] << "}}";
+    }
+    tail << "],\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc << ", \"epic_fill\": " << t_fill << ", \"energy_call\": " << t_energy
+         << ", \"fuse\": " << t_fuse << ", \"write\": " << t_io << ", \"total\": " << now_s() - t0 << "}";
+    const bool ok = write_run_json(run, segs, skipped, geo, width, height, tail.str());
+    std::cout << "wrote the fused flows with fill-in of " << fz.done.size() << " start_jet(s) to " << run.acc_dir << std::endl;
+    return ok ? 0 : 1;
+}
+
 // the cfg as dense_tracking reads it (:479-571, :716-746); a non-zero exit status, with a message, where it cannot be used
 static int read_run(ParameterList &params, Run &run) {
     run.jets = repeated(run.cfg, "jet_estimation");
@@ -720,7 +939,13 @@ static int refusal(ParameterList &params, const Run &run) {
                               : (method != 0 && method != 1) ? "an acc_traj_sim_method other than 0 or 1"
                               : run.rates > 16 ? "more than 16 rates" : nullptr;
         if (refused) { std::cerr << "-fuse: " << refused << " is not supported" << std::endl; return 1; }
-        if (params.parameter<bool>("acc_epic_interpolation", "1"))
+        if (run.fill) {
+            // the reference blurs and resizes its 8-bit image with OpenCV for acc_skip_pixel > 0 (:932-936), which is not restated; 16 slots = 8 rates x 2
+            refused = run.skip_pixel != 0 ? "acc_skip_pixel other than 0 (the reference's resized reference image is not restated)"
+                      : run.rates > 8 ? "more than 8 rates (jet_estimation lines; two of the 16 slots each)"
+                      : !params.parameter<bool>("acc_epic_interpolation", "1") ? "acc_epic_interpolation 0" : nullptr;
+            if (refused) { std::cerr << "-fill: " << refused << " is not supported" << std::endl; return 1; }
+        } else if (params.parameter<bool>("acc_epic_interpolation", "1"))
             std::cout << "-fuse: acc_epic_interpolation 1, but EpicFlow's fill-in and the neighbour proposals are not run (pixels without a hypothesis "
                          "stay UNKNOWN_FLOW)" << std::endl;
     }
@@ -790,6 +1015,9 @@ static int check_inputs(const ParameterList &params, const Run &run, vector<Segm
                 else { std::cerr << s.occ[f] << ".pgm does not exist (nor " << s.occ[f] << ".pbm)!" << std::endl; return 2; }
             }
         }
+    if (run.fill)
+        for (const Segment &s : segs)
+            if (!file_exists(edges_file(run, s.seq_start))) { std::cerr << edges_file(run, s.seq_start) << " does not exist!" << std::endl; return 2; }
     if (!run.energies) return 0;
     const size_t sf = params.file.find_last_of('/') + 1;                 // :740-751 (npos + 1 == 0: no folder)
     string sequence_path = params.file.substr(0, sf);
@@ -830,6 +1058,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "-resume")) resume = true;
         else if (!strcmp(a, "-energies")) run.energies = true;
         else if (!strcmp(a, "-fuse")) run.fuse = run.energies = true;
+        else if (!strcmp(a, "-fill")) run.fill = run.fuse = run.energies = true;
         else if (!strcmp(a, "-select") && i + 1 < argc) { selected = (unsigned)atoi(argv[++i]); selected_end = selected + 1; }
         else { fprintf(stderr, "unknown argument %s\n", a); usage(); return 1; }
     }
@@ -856,5 +1085,6 @@ int main(int argc, char **argv) {
     }
     mkdirs(run.acc_dir);
     for (unsigned r = 0; r < run.rates; r++) mkdirs(run.acc_dir + std::to_string(r) + "/");
+    if (run.fill) return run_fill(params, run, segs, skipped, frame_files, geo);
     return run.energies ? run_energies(params, run, segs, skipped, frame_files, geo) : run_accumulate(params, run, segs, skipped, geo);
 }

@@ -16,6 +16,17 @@ void epic_params_default(epic_params_t *p) {                                // e
     p->saliency_th = 0.045f; p->pref_nn = 25; p->pref_th = 5.0f; p->nn = 100; p->coef_kernel = 0.8f; p->euc = 0.001f; p->verbose = 0;
 }
 
+color_image_t *rgb8_to_lab(const color_image_t *rgb, float norm) {
+    color_image_t *un8 = color_image_new(rgb->width, rgb->height);
+    for (size_t i = 0; i < (size_t)3 * rgb->stride * rgb->height; i++) {
+        const float v = nearbyintf(rgb->c1[i] * norm);                           // cvRound: to nearest, ties to even
+        un8->c1[i] = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);                // saturate_cast<uchar>
+    }
+    color_image_t *lab = rgb_to_lab(un8);
+    color_image_delete(un8);
+    return lab;
+}
+
 bool read_matches(const char *filename, epic_matches &out) {                // io.c:23-47
     FILE *f = fopen(filename, "r");
     if (!f) return false;

@@ -39,6 +39,9 @@ bool read_edges(const char *filename, int width, int height, epic_edges &out);
 
 /* image.c:694-726: L*a*b* with the reference's attenuation of unreliable colours; returns a new image */
 color_image_t *rgb_to_lab(const color_image_t *im);
+/* convertTo(CV_8UC3, norm) (cvRound: to nearest, ties to even; saturate_cast<uchar>) and then rgb_to_lab: the Lab image of an 8-bit copy, as the driver
+ * (slow_flow.cpp:578) and dense_tracking (dense_tracking.cpp:931, 947-955) build it for epic().  norm: 1, or 1.0f / 255 for 16-bit samples.  A new image */
+color_image_t *rgb8_to_lab(const color_image_t *rgb, float norm);
 /* image.c:729-791: smallest eigenvalue of the smoothed autocorrelation matrix; filters on the GPU of ctx; NULL on a GPU error */
 image_t *saliency(sfa_ctx *ctx, const color_image_t *im, float sigma_image, float sigma_matrix);
 

@@ -512,13 +512,7 @@ static int epic_inputs(const Run &run, const Sequence &seq, const Window &wd, sf
         }
     }
     const color_image_t *un_src = small ? small.get() : un_ref;
-    ColorImage un8(color_image_new(un_src->width, un_src->height));
-    const float norm = seq.maxval[fi] > 255 ? 1.0f / 255 : 1.0f;
-    for (size_t i = 0; i < (size_t)3 * un_src->stride * un_src->height; i++) {
-        const float v = nearbyintf(un_src->c1[i] * norm);                          // cvRound: to nearest, ties to even
-        un8->c1[i] = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);                   // saturate_cast<uchar>
-    }
-    in.lab.reset(rgb_to_lab(un8.get()));
+    in.lab.reset(rgb8_to_lab(un_src, seq.maxval[fi] > 255 ? 1.0f / 255 : 1.0f));
     in.ew = ew; in.eh = eh;
     return SFA_OK;
 }
