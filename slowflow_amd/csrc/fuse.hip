@@ -34,7 +34,9 @@ struct FuseDims {
     int n, K, J, gw, gh, gpl, w, h, incr, start;
 };
 
-__device__ __forceinline__ bool present(double e) { return !(e == __longlong_as_double(0x7ff0000000000000ll)); }
+// +Inf marks "no hypothesis"; a NaN energy is absent too, as it is for k_track_best's `e < be` (track.hip): the reference's std::sort on a NaN score is
+// undefined, so no parity is lost
+__device__ __forceinline__ bool present(double e) { return e < __longlong_as_double(0x7ff0000000000000ll); }
 
 // hypothesis::distance (utils/hypothesis.cpp:223-285) of two hypotheses after adaptFPS (startF 0, endF Jets: first 0, length Jets, prev_flow (0, 0)).
 // a, b: the first of Jets doubles `step` apart.  ACC: sum sqrt(dx^2 + dy^2) / l; ADJ: the adjacent-step form, / length.  x - 0.0 is x, so the

@@ -13,6 +13,9 @@ The occlusion masks the reference reads (dense_tracking.cpp:1157-1199): grey fil
 import numpy as np
 
 QUIRKS = ("last_init", "occ_zero", "tracked_once", "in_image_double", "out_diff", "edge_weight", "occ_trunc", "err_l2")
+# what the reference's statements do with values no smooth flow reaches (tests/test_track_value_ranges.py pins them; the hand-worked cases of
+# test_accumulate.py cannot): a tap of weight zero is still multiplied (0 * Inf = NaN, utils.h:216), and a NaN position fails `>= 0 && < extent` (:556)
+VALUE_QUIRKS = ("zero_weight_tap", "nan_outside")
 
 
 def grid(w, h, skip):
@@ -24,9 +27,11 @@ def grid(w, h, skip):
     return gw, gh, incr, start
 
 
-def _bilinear(p, x, y, edge_weight=True):
-    """bilinearInterp<double>(x, y, p) (utils.h:182-217) at arrays of in-image points; p: (h, w) fp32"""
+def _bilinear(p, x, y, edge_weight=True, zero_taps=True):
+    """bilinearInterp<double>(x, y, p) (utils.h:182-217) at arrays of in-image points; p: (h, w) fp32.  Every index formed is asserted to lie in the plane
+    (numpy would wrap a negative one silently).  zero_taps=False: the slip that leaves a tap of weight zero out of the sum"""
     h, w = p.shape
+    assert np.all((x >= 0) & (x < w) & (y >= 0) & (y < h)), "bilinearInterp outside the plane"      # NaN fails it as well
     x0, y0 = x.astype(np.int64), y.astype(np.int64)            # (int) of non-negative doubles
     if edge_weight:                                             # the weight is 0 on the last column / row (:198-209)
         wx = np.where(x0 + 1 < w, x - x0, 0.0)
@@ -36,15 +41,23 @@ def _bilinear(p, x, y, edge_weight=True):
     else:                                                       # the slip: the neighbour wraps round to column / row 0
         wx, wy = x - x0, y - y0
         x1, y1 = (x0 + 1) % w, (y0 + 1) % h
+    assert np.all((x0 >= 0) & (x0 < w) & (x1 >= 0) & (x1 < w) & (y0 >= 0) & (y0 < h) & (y1 >= 0) & (y1 < h)), "tap outside the plane"
     d = p.astype(np.float64)
+    if not zero_taps:
+        def term(wgt, val):
+            return np.where(wgt == 0, 0.0, wgt * val)
+        return term((1 - wy) * (1 - wx), d[y0, x0]) + term((1 - wy) * wx, d[y0, x1]) + term(wy * (1 - wx), d[y1, x0]) + term(wy * wx, d[y1, x1])
     return (1 - wy) * (1 - wx) * d[y0, x0] + (1 - wy) * wx * d[y0, x1] + wy * (1 - wx) * d[y1, x0] + wy * wx * d[y1, x1]
 
 
-def accumulate(fwd_u, fwd_v, bwd_u, bwd_v, masks, epsilon, skip, discard, off=()):
+def accumulate(fwd_u, fwd_v, bwd_u, bwd_v, masks, epsilon, skip, discard, off=(), trace=None):
     """-> acc_u, acc_v (FF, gh, gw) float64 and tracked (gh, gw) int32.  masks: (FF, h, w) uint8, 0 = occluded, or None.
-    off: names from QUIRKS whose reference behaviour is replaced by the obvious alternative (tests only)."""
+    off: names from QUIRKS / VALUE_QUIRKS whose reference behaviour is replaced by the obvious alternative (tests only).
+    trace: a list that receives one dict per step: the positions tested (cy, cx; NaN where the pixel is occluded), which of them are inside, and the
+    targets tested (ny, nx; NaN where the position is not inside) -- what tests/value_ranges.py classifies"""
     off = set(off)
-    assert off <= set(QUIRKS), off
+    assert off <= set(QUIRKS) | set(VALUE_QUIRKS), off
+    zt = "zero_weight_tap" not in off
     FF, h, w = np.shape(fwd_u)
     gw, gh, incr, start = grid(w, h, skip)
     oy = (np.arange(gh) * incr + start)[:, None].repeat(gw, 1).ravel()
@@ -68,6 +81,8 @@ def accumulate(fwd_u, fwd_v, bwd_u, bwd_v, masks, epsilon, skip, discard, off=()
             tracked[once] = 0 if discard else f + 1
 
     def inside(yy, xx):
+        if "nan_outside" in off:                                # the slip: `!(outside)`, which lets a NaN position through (read at pixel 0 here)
+            return ~((yy < 0) | (yy >= h) | (xx < 0) | (xx >= w))
         if "in_image_double" in off:                            # the slip: the test on truncated coordinates
             return (np.trunc(yy) >= 0) & (yy < h) & (np.trunc(xx) >= 0) & (xx < w)
         return (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
@@ -89,6 +104,9 @@ def accumulate(fwd_u, fwd_v, bwd_u, bwd_v, masks, epsilon, skip, discard, off=()
                 rx = np.minimum(np.rint(cx[idx]).astype(np.int64), w - 1)
             else:                                               # at<uchar>(double, double) truncates (:557)
                 ry, rx = cy[idx].astype(np.int64), cx[idx].astype(np.int64)
+            if "nan_outside" in off:
+                ry, rx = np.nan_to_num(cy[idx]).astype(np.int64), np.nan_to_num(cx[idx]).astype(np.int64)
+            assert np.all((ry >= 0) & (ry < h) & (rx >= 0) & (rx < w)), "occlusion lookup outside the mask"
             occ_now = np.zeros(n, bool)
             occ_now[idx] = np.asarray(masks[f])[ry, rx] == 0
             occluded |= occ_now
@@ -96,8 +114,10 @@ def accumulate(fwd_u, fwd_v, bwd_u, bwd_v, masks, epsilon, skip, discard, off=()
         idx = np.nonzero(ins)[0]
         ew = "edge_weight" not in off
         pyc, pxc = np.maximum(cy[idx], 0), np.maximum(cx[idx], 0)   # only the "in_image_double" variant lets (-1, 0) through
-        vu = _bilinear(np.asarray(fwd_u[f]), pxc, pyc, ew)
-        vv = _bilinear(np.asarray(fwd_v[f]), pxc, pyc, ew)
+        if "nan_outside" in off:
+            pyc, pxc = np.nan_to_num(pyc), np.nan_to_num(pxc)
+        vu = _bilinear(np.asarray(fwd_u[f]), pxc, pyc, ew, zt)
+        vv = _bilinear(np.asarray(fwd_v[f]), pxc, pyc, ew, zt)
         ny, nx = cy[idx] + vv, cx[idx] + vu
         if "out_diff" in off:                                   # the slip: no backward flow -> the forward vector alone
             dv, du = vv.copy(), vu.copy()
@@ -105,8 +125,18 @@ def accumulate(fwd_u, fwd_v, bwd_u, bwd_v, masks, epsilon, skip, discard, off=()
             dv, du = vv - last_v[idx], vu - last_u[idx]
         tin = inside(ny, nx)
         t = np.nonzero(tin)[0]
-        bu = _bilinear(np.asarray(bwd_u[f]), np.maximum(nx[t], 0), np.maximum(ny[t], 0), ew)
-        bv = _bilinear(np.asarray(bwd_v[f]), np.maximum(nx[t], 0), np.maximum(ny[t], 0), ew)
+        tx, ty = np.maximum(nx[t], 0), np.maximum(ny[t], 0)
+        if "nan_outside" in off:
+            tx, ty = np.nan_to_num(tx), np.nan_to_num(ty)
+        bu = _bilinear(np.asarray(bwd_u[f]), tx, ty, ew, zt)
+        bv = _bilinear(np.asarray(bwd_v[f]), tx, ty, ew, zt)
+        if trace is not None:
+            full_ny, full_nx = np.full(n, np.nan), np.full(n, np.nan)
+            full_ny[idx], full_nx[idx] = ny, nx
+            tgt_in = np.zeros(n, bool)
+            tgt_in[idx[t]] = True
+            trace.append(dict(cy=np.where(act, cy, np.nan), cx=np.where(act, cx, np.nan), act=act.copy(), ins=ins.copy(), ny=full_ny, nx=full_nx,
+                              tgt=ins.copy(), tgt_in=tgt_in))
         dv[t] = vv[t] + bv
         du[t] = vu[t] + bu
         if "err_l2" in off:
@@ -138,6 +168,7 @@ def accumulate(fwd_u, fwd_v, bwd_u, bwd_v, masks, epsilon, skip, discard, off=()
 def _bilinear_scalar(p, x, y):
     h, w = p.shape
     y0, x0 = int(y), int(x)
+    assert 0 <= y0 < h and 0 <= x0 < w, "bilinearInterp outside the plane"
     y1, x1 = y0, x0
     wx = 0.0
     if x0 + 1 < w:

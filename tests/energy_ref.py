@@ -15,6 +15,11 @@ from accum_ref import grid
 
 QUIRKS = ("float_skip", "cv_continue", "visible_hole", "offx_outer", "empty_flows", "fp32_sum", "edge_weight", "channel_order")
 
+# what the reference's statements do with values no smooth trajectory reaches (tests/test_track_value_ranges.py pins them): a tap of weight zero is still
+# multiplied (0 * Inf = NaN, utils.h:216 / utils.cpp:441-444), addJC stops at the first step beyond UNKNOWN_FLOW_THRESH (dense_tracking.cpp:190), and a
+# NaN position fails every `>= 0 && < extent` test
+VALUE_QUIRKS = ("zero_weight_tap", "unknown_break", "nan_outside")
+
 F32 = np.float32
 
 
@@ -79,9 +84,11 @@ def phi(kind, eps, xsq):
     return F32(np.log(1 + 0.5 * np.float64(xsq) / esq))
 
 
-def _bil(p, x, y, edge_weight=True):
-    """bilinearInterp (utils.h:182-217 / utils.cpp:415-446) at arrays of in-image points of an (h, w) fp32 plane"""
+def _bil(p, x, y, edge_weight=True, zero_taps=True):
+    """bilinearInterp (utils.h:182-217 / utils.cpp:415-446) at arrays of in-image points of an (h, w) fp32 plane.  Every index formed is asserted to lie in
+    the plane (numpy would wrap a negative one silently).  zero_taps=False: the slip that leaves a tap of weight zero out of the sum"""
     h, w = p.shape
+    assert np.all((x >= 0) & (x < w) & (y >= 0) & (y < h)), "bilinearInterp outside the plane"      # NaN fails it as well
     x0, y0 = x.astype(np.int64), y.astype(np.int64)
     if edge_weight:
         wx = np.where(x0 + 1 < w, x - x0, 0.0)
@@ -91,18 +98,29 @@ def _bil(p, x, y, edge_weight=True):
     else:                                                       # the slip: the neighbour wraps round to column / row 0
         wx, wy = x - x0, y - y0
         x1, y1 = (x0 + 1) % w, (y0 + 1) % h
+    assert np.all((x0 >= 0) & (x0 < w) & (x1 >= 0) & (x1 < w) & (y0 >= 0) & (y0 < h) & (y1 >= 0) & (y1 < h)), "tap outside the plane"
     d = p.astype(np.float64)
+    if not zero_taps:
+        def term(wgt, val):
+            return np.where(wgt == 0, 0.0, wgt * val)
+        return term((1 - wy) * (1 - wx), d[y0, x0]) + term((1 - wy) * wx, d[y0, x1]) + term(wy * (1 - wx), d[y1, x0]) + term(wy * wx, d[y1, x1])
     return (1 - wy) * (1 - wx) * d[y0, x0] + (1 - wy) * wx * d[y0, x1] + wy * (1 - wx) * d[y1, x0] + wy * wx * d[y1, x1]
 
 
 def energies(p, r_Jets, acc_u, acc_v, tracked, frames, dx, dy, flows, off=()):
     """-> energy (gh, gw) float64 (+Inf where tracked != r_Jets), occ_bits (gh, gw) uint64 and a dict of intermediate terms over the hypotheses"""
     off = set(off)
-    assert off <= set(QUIRKS), off
+    assert off <= set(QUIRKS) | set(VALUE_QUIRKS), off
     J = frames.shape[0] - 1
     h, w = frames.shape[2:]
     gw, gh, incr, start = grid(w, h, p.skip)
     ew = "edge_weight" not in off
+    zt = "zero_weight_tap" not in off
+
+    def lookup(pl, x, y, ew_):                                   # every bilinearInterp below, with this call's switches
+        if "nan_outside" in off:
+            x, y = np.nan_to_num(x), np.nan_to_num(y)
+        return _bil(pl, x, y, ew_, zt)
     hy, hx = np.nonzero(tracked == r_Jets)
     H = len(hy)
     px, py = (hx * incr + start).astype(np.float64), (hy * incr + start).astype(np.float64)
@@ -126,6 +144,8 @@ def energies(p, r_Jets, acc_u, acc_v, tracked, frames, dx, dy, flows, off=()):
     occ = np.zeros((J + 1, H), bool)
 
     def inside(x, y, W, Hh):
+        if "nan_outside" in off:                                # the slip: `!(outside)`, which lets a NaN position through (read at pixel 0 here)
+            return ~((y < 0) | (y >= Hh) | (x < 0) | (x >= W)) & (W > 0)
         return (y >= 0) & (y < Hh) & (x >= 0) & (x < W)
 
     for t in range(J):
@@ -136,14 +156,14 @@ def energies(p, r_Jets, acc_u, acc_v, tracked, frames, dx, dy, flows, off=()):
         a = ~occ[t] & inside(xm, ym, fw, fh)
         if a.any():
             fu, fv, bu, bv = (q[t] for q in flows)
-            Fx, Fy = _bil(fu, xm[a], ym[a], ew), _bil(fv, xm[a], ym[a], ew)
+            Fx, Fy = lookup(fu, xm[a], ym[a], ew), lookup(fv, xm[a], ym[a], ew)
             ysq = V[t][a] - v_tm1[a] - Fy
             xsq = U[t][a] - u_tm1[a] - Fx
             xt, yt = px[a] + U[t][a], py[a] + V[t][a]
             b = inside(xt, yt, fw, fh)
             ok = np.zeros(a.sum(), bool)
             if b.any():
-                bFx, bFy = _bil(bu, xt[b], yt[b], ew), _bil(bv, xt[b], yt[b], ew)
+                bFx, bFy = lookup(bu, xt[b], yt[b], ew), lookup(bv, xt[b], yt[b], ew)
                 fby, fbx = bFy + Fy[b], bFx + Fx[b]
                 ok[b] = (np.sqrt(fby * fby + fbx * fbx) < np.float64(p.occlusion_fb_threshold)) & (
                     np.sqrt(ysq[b] * ysq[b] + xsq[b] * xsq[b]) < np.float64(p.occlusion_threshold))
@@ -155,13 +175,14 @@ def energies(p, r_Jets, acc_u, acc_v, tracked, frames, dx, dy, flows, off=()):
     for j in range(J):
         u_j, v_j = U[j], V[j]
         u_jm1, v_jm1 = (U[j - 1], V[j - 1]) if j > 0 else (np.zeros(H), np.zeros(H))
-        alive &= ~((u_j > 1e9) | (v_j > 1e9))                   # break
+        if "unknown_break" not in off:
+            alive &= ~((u_j > 1e9) | (v_j > 1e9))               # break
         xi, yi = px + u_jm1, py + v_jm1
         ins = alive & inside(xi, yi, fw, fh)
         skipped = ins & (occ[j] | occ[j + 1])
         use = ins & ~skipped
         if use.any():
-            Ix, Iy = _bil(flows[0][j], xi[use], yi[use], ew), _bil(flows[1][j], xi[use], yi[use], ew)
+            Ix, Iy = lookup(flows[0][j], xi[use], yi[use], ew), lookup(flows[1][j], xi[use], yi[use], ew)
             du, dv = u_j[use] - u_jm1[use] - Ix, v_j[use] - v_jm1[use] - Iy
             arg = (du * du + dv * dv).astype(F32)
             jen[use] = jen[use] + 0.5 * np.array([np.float64(phi(p.penalty, p.penalty_eps, x)) for x in arg])
@@ -207,7 +228,7 @@ def energies(p, r_Jets, acc_u, acc_v, tracked, frames, dx, dy, flows, off=()):
             xj, yj = X0[sel] + U[j - 1][hi][sel], Y0[sel] + V[j - 1][hi][sel]
             for q, pl in enumerate((frames, dx, dy)):
                 for c, ch in enumerate(chans):
-                    vals[j, 3 * q + c, sel] = _bil(pl[j, ch], xj, yj, ew)
+                    vals[j, 3 * q + c, sel] = lookup(pl[j, ch], xj, yj, ew)
     occR = occ[:, hi]
     bcw, gcw = np.float64(p.acc_bc) * 0.3334, np.float64(p.acc_gc) * 0.3334
     e_p, cnt = np.zeros(R), np.zeros(R, np.int64)

@@ -20,6 +20,9 @@ from accum_ref import grid
 
 QUIRKS = ("nms_break", "float_score", "img_norm_keys", "acc_unnormalised", "occ_jets_plus_1", "fp32_weight_sum", "float_dist")
 
+# this project's own rule (the reference's std::sort on a NaN score is undefined): a hypothesis whose energy is NaN is absent, as +Inf is
+VALUE_QUIRKS = ("nan_energy_absent",)
+
 F32 = np.float32
 INF = np.inf
 UNKNOWN_FLOW = 1e10
@@ -133,8 +136,12 @@ def labels(U, V, energy, method, thres, off=()):
     N = gh * gw
     Uf, Vf = U.reshape(K, J, N), V.reshape(K, J, N)
     e = energy.reshape(K, N).T
-    absent = e == INF
-    key = e if "float_score" in off else e.astype(F32).astype(np.float64)
+    absent = ~(e < INF)                                                         # +Inf: no hypothesis; a NaN energy is absent too
+    if "nan_energy_absent" in off:                                              # the rule before: only +Inf is absent
+        absent = e == INF
+    with np.errstate(over="ignore"):                                            # (float) of a score beyond FLT_MAX is +-Inf, as in C
+        key32 = e.astype(F32).astype(np.float64)
+    key = e if "float_score" in off else key32
     slots = np.broadcast_to(np.arange(K), (N, K))
     order = np.lexsort((slots, np.where(absent, 0, key), absent), axis=-1)      # present first, by score, ties: the lower slot
     m = (~absent).sum(1)
@@ -167,18 +174,21 @@ def popcount(x):
     return np.unpackbits(x.view(np.uint8).reshape(x.shape + (8,)), axis=-1).sum(-1)
 
 
-def pair_cost(ua, va, oa, ub, vb, ob, w1, w2, J, p, off=()):
-    """P(h1, h2) of :1752-1766 for arrays of pairs"""
+def pair_cost(ua, va, oa, ub, vb, ob, w1, w2, J, p, off=(), trace=None):
+    """P(h1, h2) of :1752-1766 for arrays of pairs.  trace: a list that receives the distances before their rounding to float"""
     dist = distance(ua, va, ub, vb, p.traj_sim_method, off)
+    if trace is not None:
+        trace.append(dist.copy())
     if "float_dist" not in off:
-        dist = dist.astype(F32).astype(np.float64)
+        with np.errstate(over="ignore"):                                    # (float) of a distance beyond FLT_MAX is +Inf, as in C
+            dist = dist.astype(F32).astype(np.float64)
     nb = J + 1 if "occ_jets_plus_1" not in off else J
     smooth = popcount(np.bitwise_xor(oa, ob) & np.uint64((1 << nb) - 1)).astype(np.float64)
     wsum = (np.float64(w1) + np.float64(w2)) if "fp32_weight_sum" in off else (F32(w1) + F32(w2)).astype(np.float64)
     return wsum * (p.acc_beta * dist + p.acc_spatial_occ * smooth)
 
 
-def pairwise(U, V, occ, weight, lab, p, w, off=()):
+def pairwise(U, V, occ, weight, lab, p, w, off=(), trace=None):
     """PR, PD of one segment: lists over the pixels of (n1, n2) arrays or None.  All pairs of a direction in one vectorised evaluation."""
     K, J, gh, gw = U.shape
     N = gh * gw
@@ -205,7 +215,8 @@ def pairwise(U, V, occ, weight, lab, p, w, off=()):
             y, x = pi_ // gw, pi_ % gw
             o1 = (y * incr + start) * w + x * incr + start
             o2 = ((y + dy) * incr + start) * w + (x + dx) * incr + start
-            c = pair_cost(Uf[a_, :, pi_], Vf[a_, :, pi_], Of[a_, pi_], Uf[b_, :, t_], Vf[b_, :, t_], Of[b_, t_], W[o1], W[o2], J, p, off)
+            assert np.all((o1 >= 0) & (o1 < W.size) & (o2 >= 0) & (o2 < W.size)), "weight lookup outside the plane"
+            c = pair_cost(Uf[a_, :, pi_], Vf[a_, :, pi_], Of[a_, pi_], Uf[b_, :, t_], Vf[b_, :, t_], Of[b_, t_], W[o1], W[o2], J, p, off, trace)
             for pi in np.unique(pi_):
                 P[pi] = np.zeros((len(lab[pi]), len(lab[pi + dx + dy * gw])))
             for k in range(len(rows)):
@@ -473,13 +484,13 @@ def trws_diag(theta, PR, PD, gw, gh, eps, max_iter):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # the whole fusion of one segment
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-def fuse(U, V, energy, occ, weight, p, w, off=(), solver=trws_diag):
+def fuse(U, V, energy, occ, weight, p, w, off=(), solver=trws_diag, trace=None):
     """one segment: U, V (K, Jets, gh, gw) float64; energy (K, gh, gw) (+Inf: none); occ uint64 (K, gh, gw); weight (h, w) fp32.  Returns a dict like
     Context.fuse_hypotheses' for n = 1 (without the leading axis)"""
     K, J, gh, gw = U.shape
     _, _, incr, _ = grid(w, weight.shape[0], p.skip)
     lab = labels(U, V, energy, p.traj_sim_method, p.traj_sim_thres, off)
-    PR, PD = pairwise(U, V, occ, weight, lab, p, w, off)
+    PR, PD = pairwise(U, V, occ, weight, lab, p, w, off, trace)
     theta = [np.array([energy[k, pi // gw, pi % gw] for k in lab[pi]], dtype=np.float64) for pi in range(gh * gw)]
     x, E, lb, its = solver(theta, PR, PD, gw, gh, p.trws_eps, p.trws_max_iter)
     slot = np.full((gh, gw), -1, np.int32)

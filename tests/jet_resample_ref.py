@@ -52,8 +52,12 @@ def _linear_taps(n_dst, n_src, scale):
     return idx, frac
 
 
-def resize_linear_64f(src, rescale):
-    """cv::resize(src, dst, Size(0, 0), rescale, rescale, INTER_LINEAR) of one float64 plane; scale = 1.0 / (double)rescale"""
+def resize_linear_64f(src, rescale, zero_taps=True):
+    """cv::resize(src, dst, Size(0, 0), rescale, rescale, INTER_LINEAR) of one float64 plane; scale = 1.0 / (double)rescale.  A tap of weight zero (the
+    clamped last row / column, an exact sample position) is still multiplied: 0 * Inf = NaN.  zero_taps=False: the slip that leaves it out (tests only)"""
+    def mul(v, wgt):
+        return v * wgt if zero_taps or wgt != 0 else 0.0
+
     src = np.asarray(src, np.float64)
     sh, sw = src.shape
     dw, dh = target_size(sw, sh, rescale)
@@ -69,16 +73,17 @@ def resize_linear_64f(src, rescale):
             sx = int(xo[dx])
             sx1 = sx + 1 if sx + 1 < sw else sx
             a0, a1 = np.float64(f32(1) - xa[dx]), np.float64(xa[dx])
-            h0 = src[sy, sx] * a0 + src[sy, sx1] * a1                    # the row pass of both rows
-            h1 = src[sy1, sx] * a0 + src[sy1, sx1] * a1
-            out[dy, dx] = h0 * b0 + h1 * b1                              # the column pass
+            assert 0 <= sy <= sy1 < sh and 0 <= sx <= sx1 < sw, "tap outside the plane"
+            h0 = mul(src[sy, sx], a0) + mul(src[sy, sx1], a1)            # the row pass of both rows
+            h1 = mul(src[sy1, sx], a0) + mul(src[sy1, sx1], a1)
+            out[dy, dx] = mul(h0, b0) + mul(h1, b1)                      # the column pass
     return out
 
 
-def resample_flow(u, v, rescale, crop=None):
+def resample_flow(u, v, rescale, crop=None, zero_taps=True):
     """one flow field as dense_tracking reads it (:1131-1146): widened to double, cropped to crop = (x0, y0, cw, ch), resized, multiplied by
     (double)rescale.  u, v: fp32 (sh, sw) planes (only the valid columns).  -> float64 (h, w) planes"""
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         out = []
         for p in (u, v):
             p = np.asarray(p, np.float32).astype(np.float64)
@@ -86,7 +91,7 @@ def resample_flow(u, v, rescale, crop=None):
                 x0, y0, cw, ch = crop
                 assert x0 >= 0 and y0 >= 0 and cw >= 1 and ch >= 1 and x0 + cw <= p.shape[1] and y0 + ch <= p.shape[0], "the crop leaves the flow"
                 p = p[y0:y0 + ch, x0:x0 + cw]
-            out.append(resize_linear_64f(p, rescale) * np.float64(f32(rescale)))
+            out.append(resize_linear_64f(p, rescale, zero_taps) * np.float64(f32(rescale)))
     return out[0], out[1]
 
 

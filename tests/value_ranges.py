@@ -134,3 +134,179 @@ def guard_classes(D, w=None):
 
 def class_counts(classes):
     return {k: int((classes == k).sum()) for k in ("mixed", "all", "none")}
+
+
+# ------------------------------------------------------------------------------------------------------
+# the tracking stage (tests/test_track_value_ranges.py): flows whose trajectories take every branch of the position guards of accumulate.hip and energy.hip,
+# double-precision special values for accumulated flows and energies, and the classes an input reaches, computed from the restatements' intermediates
+# ------------------------------------------------------------------------------------------------------
+SMALL = (5, 4)                                  # smaller than every tile and block
+TRAJ_MAGS = np.array([2.0 ** -140, 2.0 ** -20, 1.0, 2.0 ** 31, 2.0 ** 63, FLT_MAX, 1e10, -1e10], np.float32)   # eight bands: all of them in any 64 columns
+F64_SPECIALS = np.array([0.0, -0.0, 5e-324, 2.0 ** -1022, 1e9, np.nextafter(1e9, np.inf), 1e10, -1e10, float(FLT_MAX), np.inf, -np.inf, np.nan])
+INT_RANGE = 2.0 ** 31                           # from here on (int) of a double is no index at all
+
+
+def traj_flows(FF, h, w, seed, band=8, sprinkle_seed=None, mags=TRAJ_MAGS):
+    """the flow ladder for trajectories: (fu, fv, bu, bv), fp32 (FF, h, w).  A smooth field of a pixel or two (the backward one its negative plus noise) times
+    TRAJ_MAGS in bands of `band` columns, the bands moving on by one per step, so that a trajectory that stays in the image at step f meets the next magnitude at
+    step f + 1: subnormal, 2^-20, O(1), 2^31, 2^63, +-FLT_MAX, and exactly +-1e10 (UNKNOWN_FLOW).  sprinkle_seed: SPECIALS sprinkled into every plane;
+    mags: other magnitudes (one of 1: the smooth field alone, whose trajectories stay in the image and meet the sprinkle)"""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    out = np.zeros((4, FF, h, w), np.float32)
+    with np.errstate(all="ignore"):
+        for f in range(FF):
+            a, p = rng.uniform(0.5, 3, 4), rng.uniform(0, 6.3, 4)
+            u = 1.5 * np.sin(a[0] * x / w * 6.3 + p[0]) * np.cos(a[1] * y / h * 6.3 + p[1])
+            v = 1.5 * np.cos(a[2] * x / w * 6.3 + p[2]) * np.sin(a[3] * y / h * 6.3 + p[3])
+            noise = rng.standard_normal((2, h, w)) * rng.choice([0.01, 0.3])
+            mag = np.asarray(mags, np.float32)[((np.arange(w) // band) + f) % len(mags)][None, :]
+            for k, (fld, sign) in enumerate(((u, 1.0), (v, 1.0), (-u + noise[0], -1.0), (-v + noise[1], -1.0))):
+                val = (fld * mag.astype(np.float64)).astype(np.float32)
+                val = np.where(np.abs(mag) == FLT_MAX, np.where(fld < 0, -FLT_MAX, FLT_MAX), val)
+                out[k, f] = np.where(np.abs(mag) == np.float32(1e10), np.float32(sign) * mag, val)
+    if sprinkle_seed is not None:
+        for k in range(4):
+            sprinkle(out[k], sprinkle_seed + k)
+    return out[0], out[1], out[2], out[3]
+
+
+def ulp_below(n):
+    """n - the largest double below n"""
+    return float(n) - float(np.nextafter(np.float64(n), 0.0))
+
+
+def _landing(n, band):
+    """step 0's flow along one axis of extent n, by bands of `band` pixels: the pixel c lands on c + 1 (an integer; n from the last pixel), n - 1, n - 1.5,
+    +0.0 (c + (-c)), c itself (the flow is -0.0), -1, n, c + 0.5; pixel 0 lands on -2^-149, the negative value nearest zero"""
+    c = np.arange(n, dtype=np.float64)
+    kind = (np.arange(n) // band) % 8
+    t = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 4, kind == 5, kind == 6, kind == 7],
+                  [np.ones(n), (n - 1) - c, (n - 1.5) - c, -c, np.full(n, -0.0), -c - 1, n - c, np.full(n, 0.5)])
+    t = np.where(kind == 4, -0.0, t)                                           # np.select keeps the sign; so does this
+    t[0] = -float(SUB_MIN)
+    assert np.array_equal(t.astype(np.float32).astype(np.float64), t)
+    return t.astype(np.float32)
+
+
+def edge_landing(FF, h, w, band_x=8, band_y=3):
+    """the edge-landing field: (fu, fv, bu, bv), fp32 (FF, h, w), FF >= 3.  Step 0 moves pixel (x, y) by _landing(w)[x], _landing(h)[y]: positions that are an
+    integer, exactly w - 1 / h - 1, exactly +0.0, w and h themselves (outside by one ulp), -1, and -2^-149 from pixel 0.
+    An integer pixel plus an fp32 flow is exact in a double, so neither -0.0 (a sum is -0.0 only when both terms are) nor the largest double below w can be a
+    position after step 0.  The second comes after step 1: the pixels that landed on w - 1.5 interpolate step 1's columns w - 2 (3.0) and w - 1 (-2 ulp) with
+    weight 1/2 each, 1.5 - ulp, and land on w - ulp; those on +0.0 read column 0 (-2^-149) and land on the negative value nearest zero.  Rows alike.
+    The backward flows are the exact negatives, except on alternate groups of four columns of step 2"""
+    assert FF >= 3 and w >= 3 and h >= 3
+    fu, fv = np.zeros((FF, h, w), np.float32), np.zeros((FF, h, w), np.float32)
+    fu[0], fv[0] = _landing(w, band_x)[None, :], _landing(h, band_y)[:, None]
+    fu[1], fv[1] = 0.25, 0.125
+    fu[1][:, 0], fu[1][:, w - 2], fu[1][:, w - 1] = -SUB_MIN, 3.0, -2 * ulp_below(w)
+    fv[1][0, :], fv[1][h - 2, :], fv[1][h - 1, :] = -SUB_MIN, 3.0, -2 * ulp_below(h)
+    fu[2:], fv[2:] = 0.25, 0.125
+    bu, bv = -fu, -fv
+    bu[2][:, (np.arange(w) // 4) % 2 == 1] += 2.0
+    return fu, fv, bu, bv
+
+
+def specials64(a, seed, values=F64_SPECIALS):
+    """F64_SPECIALS (+-0, 5e-324, 2^-1022, 1e9 and the next double, +-1e10, FLT_MAX, +-Inf, NaN) sprinkled into every (h, w) plane of a float64 array, in place"""
+    return sprinkle(a, seed, values=values)
+
+
+def position_classes(tested, y, x, h, w):
+    """what the in-image test `y >= 0 && y < h && x >= 0 && x < w` on doubles meets, as boolean arrays over the positions `tested`:
+    fail_nan (a NaN coordinate), fail_magnitude (a coordinate that (int) cannot hold: |c| >= 2^31 or Inf), fail_ulp (outside by the least amount: exactly w or h,
+    or the negative fp32 value nearest zero), pass_ulp (the largest double below w or h), pass_zero, pass_last (exactly w - 1 or h - 1), pass_integer"""
+    with np.errstate(invalid="ignore"):
+        y, x = np.asarray(y, np.float64), np.asarray(x, np.float64)
+        ok = tested & (y >= 0) & (y < h) & (x >= 0) & (x < w)
+        bad = tested & ~ok
+        nan = np.isnan(y) | np.isnan(x)
+        return dict(fail_nan=bad & nan,
+                    fail_magnitude=bad & ~nan & ((np.abs(y) >= INT_RANGE) | (np.abs(x) >= INT_RANGE)),
+                    fail_ulp=bad & ~nan & ((x == w) | (y == h) | (x == -float(SUB_MIN)) | (y == -float(SUB_MIN))),
+                    pass_ulp=ok & ((x == np.nextafter(np.float64(w), 0)) | (y == np.nextafter(np.float64(h), 0))),
+                    pass_zero=ok & ((x == 0) | (y == 0)),
+                    pass_last=ok & ((x == w - 1) | (y == h - 1)),
+                    pass_integer=ok & (x == np.floor(x)) & (y == np.floor(y)))
+
+
+def tap_classes(planes, ok, y, x):
+    """bilinearInterp's four taps at the in-image positions `ok` of (h, w) planes (utils.h:182-217): where a tap that is Inf or NaN in one of the planes
+    carries the weight zero.  edge_zero_tap: on the last row or column, where the weight is zero by rule; zero_tap: anywhere (an integer coordinate as well)"""
+    h, w = planes[0].shape
+    y, x = np.where(ok, y, 0.0), np.where(ok, x, 0.0)
+    x0, y0 = x.astype(np.int64), y.astype(np.int64)
+    assert np.all((x0 >= 0) & (x0 < w) & (y0 >= 0) & (y0 < h))
+    wx, wy = np.where(x0 + 1 < w, x - x0, 0.0), np.where(y0 + 1 < h, y - y0, 0.0)
+    x1, y1 = np.minimum(x0 + 1, w - 1), np.minimum(y0 + 1, h - 1)
+    hit = np.zeros(np.shape(ok), bool)
+    for p in planes:
+        p = np.asarray(p, np.float64)
+        for wgt, val in (((1 - wy) * (1 - wx), p[y0, x0]), ((1 - wy) * wx, p[y0, x1]), (wy * (1 - wx), p[y1, x0]), (wy * wx, p[y1, x1])):
+            hit |= (wgt == 0) & ~np.isfinite(val)
+    hit &= ok
+    return dict(zero_tap=hit, edge_zero_tap=hit & ((x0 == w - 1) | (y0 == h - 1)))
+
+
+def float_overflow(a):
+    """finite doubles whose conversion to float is not: |a| rounds beyond FLT_MAX"""
+    a = np.asarray(a, np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.isfinite(a) & ~np.isfinite(a.astype(np.float32))
+
+
+def segments_reached(mask, columns):
+    """the 64-column segments in which a class occurs: mask over positions whose image column is `columns` (broadcast against it)"""
+    mask = np.asarray(mask, bool)
+    cols = np.broadcast_to(np.asarray(columns), mask.shape)
+    return sorted(set((cols[mask] // 64).tolist()))
+
+
+def accumulate_classes(trace, flows, h, w, gw, incr, start):
+    """the classes one accumulate() call reached, from its trace (accum_ref.accumulate(trace=[...])): {class: sorted 64-column segments of the start pixel}.
+    Positions (the test before a step) and targets (the test before the backward lookup) are classified alike, under 'pos_' and 'tgt_'; 'fwd_' and 'bwd_'
+    carry the zero-weight taps of the forward lookup at the position and of the backward one at the target"""
+    fu, fv, bu, bv = flows
+    col = (np.arange(len(trace[0]["cx"])) % gw) * incr + start
+    out = {}
+
+    def note(prefix, classes):
+        for k, m in classes.items():
+            out.setdefault(prefix + k, set()).update(segments_reached(m, col))
+
+    for f, t in enumerate(trace):
+        note("pos_", position_classes(t["act"], t["cy"], t["cx"], h, w))
+        note("tgt_", position_classes(t["tgt"], t["ny"], t["nx"], h, w))
+        note("fwd_", tap_classes((fu[f], fv[f]), t["ins"], t["cy"], t["cx"]))
+        note("bwd_", tap_classes((bu[f], bv[f]), t["tgt_in"], t["ny"], t["nx"]))
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def energy_classes(terms, flows, frames, h, w, incr, start):
+    """the classes one energies() call reached, from its terms: {class: sorted 64-column segments of the hypothesis' pixel}.  'pos_': the positions p + U[t - 1] that
+    setOcclusions, addJC and addBCGC test (the latter at the hypothesis' own pixel); 'tgt_': p + U[t]; 'break': addJC's `> 1e9`; 'flow_' / 'frame_': zero-weight
+    taps of the flow lookups (flows given) and of the frame lookups"""
+    U, V = terms["U"], terms["V"]
+    J, H = U.shape
+    px, py = (terms["hx"] * incr + start).astype(np.float64), (terms["hy"] * incr + start).astype(np.float64)
+    out = {}
+
+    def note(prefix, classes):
+        for k, m in classes.items():
+            out.setdefault(prefix + k, set()).update(segments_reached(m, px.astype(np.int64)))
+
+    every = np.ones(H, bool)
+    with np.errstate(invalid="ignore"):
+        note("", dict(unknown_break=((U > 1e9) | (V > 1e9)).any(0)))
+        for t in range(J):
+            xm, ym = (px + U[t - 1], py + V[t - 1]) if t > 0 else (px + 0, py + 0)
+            xt, yt = px + U[t], py + V[t]
+            note("pos_", position_classes(every, ym, xm, h, w))
+            note("tgt_", position_classes(every, yt, xt, h, w))
+            ok_t = (yt >= 0) & (yt < h) & (xt >= 0) & (xt < w)
+            note("frame_", tap_classes(tuple(frames[t + 1]), ok_t, yt, xt))
+            if flows is not None:
+                ok_m = (ym >= 0) & (ym < h) & (xm >= 0) & (xm < w) & ~terms["occ"][t]
+                note("flow_", tap_classes((flows[0][t], flows[1][t]), ok_m, ym, xm))
+    return {k: sorted(v) for k, v in out.items()}
