@@ -148,6 +148,46 @@ int sfa_epic_interpolate_batch(sfa_ctx *ctx, int n, int w, int h, int method, co
 /* The kernel time of the context's last sfa_epic_interpolate_batch in milliseconds, from HIP events, summed over its sub-batches: ms[0] the fit, ms[1] the
  * dense application.  Copies and allocations are not in it (tools/bench_epic_fit.py). */
 int sfa_epic_fit_stage_ms(sfa_ctx *ctx, float ms[2]);
+/* epic_params_t's numeric fields (host/epic.h, epic_flow_extended/epic.h:6-15); method 0: locally-weighted affine (LA), 1: Nadaraya-Watson (NW).  euc is
+ * carried for completeness: sfa_epic_batch takes cost maps that already hold it. */
+typedef struct sfa_epic_params {
+    int method;
+    float saliency_th;
+    int pref_nn;
+    float pref_th;
+    int nn;
+    float coef_kernel;
+    float euc;
+} sfa_epic_params;
+/* epic() (epic_flow_extended/epic.cpp:147-235; host/epic.cpp) for n images of one size w x h as one chain on the GPU (csrc/epic_batch.hip,
+ * csrc/epic_filter.hip): nothing but the inputs goes up, nothing but the two flow planes (and the survivors, if asked for) comes down, and the planes equal
+ * epic()'s bit for bit.  Image i: lab[i] = 3 planes of h * lab_stride floats (read only when saliency_th != 0; lab may be NULL otherwise); cost[i] = w * h
+ * floats, euc already added; matches[i] = 4 * nm[i] floats (x1 y1 x2 y2), nm[i] may be 0; flow_x[i], flow_y[i] (out) = h rows of flow_stride floats,
+ * columns >= w are not written.  Per sub-batch, in epic()'s order: the clamp of the matches to the image; if saliency_th != 0 the saliency
+ * (image.c:729-791, sigma 0.8 and 1.0) and its filter, whose index is the host's float expression (int)(y1 * stride + x1) with stride = ceil(w / 4) * 4;
+ * if pref_nn != 0 the nearest seeds with min(pref_nn + 1, count) neighbours, the kernel weights expf(-coef_kernel * d) + 1e-08, the Nadaraya-Watson
+ * estimate and the consistency filter |estimate - vector|^2 < pref_th^2; then for the images with matches left the nearest seeds with min(nn, count)
+ * neighbours, the weights, the fit of `method` and its dense application.  The neighbour count is per image.
+ * rc[i] (out) = epic()'s return value: 0, or 1 = no match (left): the flow planes of such an image are untouched and it takes no further part.  counts
+ * (or NULL): per image the matches that came in, that passed the saliency filter, that passed the consistency filter (a filter that is off passes all).
+ * kept_matches (or NULL): kept_matches[i] receives the 4 * counts[i][2] floats of the survivors in list order (room for 4 * nm[i]).
+ * Sub-batches, workspace_bytes and status as for sfa_epic_nearest_seeds_batch: nothing allocated exceeds workspace_bytes (0: half of the GPU's free memory);
+ * status[i] = 1: image i does not fit even alone -- rc[i], counts[i] and its outputs are untouched and the caller computes it on the host.  No result depends
+ * on the sub-batch cut or on an image's place in the batch.
+ * Refused with SFA_ERR_ARG, the argument named and nothing launched: n < 1, w or h < 1, nn < 1, pref_nn < 0, a method other than 0 or 1, flow_stride < w,
+ * with the saliency filter lab_stride < w or w or h <= 8 (its Gaussian), nm[i] < 0, a null pointer that is needed, a match coordinate that is not finite,
+ * w * h > 2^29, nm[i] * nn > 2^31 - 1, min(w, h) > 4000. */
+int sfa_epic_batch(sfa_ctx *ctx, int n, int w, int h, const sfa_epic_params *p, const float *const *lab, int lab_stride, const float *const *cost,
+                   const float *const *matches, const int *nm, float *const *flow_x, float *const *flow_y, int flow_stride, int *rc, int (*counts)[3],
+                   float *const *kept_matches, size_t workspace_bytes, int *status);
+/* The saliency of n Lab images of one size (image.c:729-791; host/epic.cpp: saliency()) in one call, every step on the GPU: out[i] = h * stride floats, the
+ * smallest eigenvalue of the smoothed autocorrelation matrix, columns >= w zero.  lab[i] = 3 planes of h * stride floats.  Refused: n outside 1 .. 4096, an
+ * image not larger than either Gaussian (sfa_gaussian_presmooth's rule), h < 2, stride < w, a sigma that is not positive, a null pointer. */
+int sfa_epic_saliency_batch(sfa_ctx *ctx, int n, int w, int h, const float *const *lab, int stride, float sigma_image, float sigma_matrix, float *const *out);
+/* The kernel time of the context's last sfa_epic_batch in milliseconds, from HIP events, summed over its sub-batches: ms[0] saliency, ms[1] clamp, filters,
+ * compactions, seeds and vectors, ms[2] the first nearest-seeds stage, ms[3] its weights and estimate, ms[4] the second nearest-seeds stage, ms[5] its
+ * weights, ms[6] the fit, ms[7] the dense application.  A refused call leaves them as they were. */
+int sfa_epic_batch_stage_ms(sfa_ctx *ctx, float ms[8]);
 /* adaptiveFR's flow-magnitude quantile (adaptiveFR.cpp:644-668) on the GPU.  n host fields (u[i], v[i]: w x h, row stride `stride`); every value is scaled
  * by flow_scale first (one fp32 multiply, image_mul_scalar), m = sqrtf(u*u + v*v) in IEEE fp32; the order statistics are found by an exact radix select
  * over the bit patterns of m.  NaN magnitudes sort above +Inf (their bit order; std::sort has no defined order for them), Inf where it belongs.

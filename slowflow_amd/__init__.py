@@ -117,6 +117,18 @@ def fuse_params(**kw):
     return p
 
 
+class EpicParams(C.Structure):
+    """sfa_epic_params: epic_params_t's numeric fields (epic_flow_extended/epic.h:6-15), method 0 = LA, 1 = NW"""
+    _fields_ = [("method", C.c_int), ("saliency_th", C.c_float), ("pref_nn", C.c_int), ("pref_th", C.c_float), ("nn", C.c_int), ("coef_kernel", C.c_float),
+                ("euc", C.c_float)]
+
+
+def epic_params(method="LA", saliency_th=0.045, pref_nn=25, pref_th=5.0, nn=100, coef_kernel=0.8, euc=0.001):
+    """sfa_epic_params with epic_params_default's values (epic.cpp:127-136) unless given; method "LA" / "NW" (or the number the library takes)"""
+    method = {"LA": 0, "NW": 1}.get(method, method)
+    return EpicParams(int(method), float(saliency_th), int(pref_nn), float(pref_th), int(nn), float(coef_kernel), float(euc))
+
+
 class TrackParams(C.Structure):
     """sfa_track_params: a resident track job's shape, its rates and the keys of the three stages (include/slowflow_amd.h)"""
     _fields_ = [("n", C.c_int), ("K", C.c_int), ("Jets", C.c_int), ("w", C.c_int), ("h", C.c_int), ("min_fps_idx", C.c_int), ("do_fuse", C.c_int),
@@ -168,7 +180,7 @@ def track_job_bytes(params):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "sfa_consistent_regions", "sfa_fill_samples", "sfa_fill_matches", "sfa_fill_trajectories", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_epic_batch", "sfa_epic_saliency_batch", "sfa_epic_batch_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "sfa_consistent_regions", "sfa_fill_samples", "sfa_fill_matches", "sfa_fill_trajectories", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_grid_cut_batch", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_pyramid_down", "sfa_resize_flow", "sfa_job_download_level_frame",
@@ -608,6 +620,78 @@ class Context:
         ms = (C.c_float * 2)()
         self._ck(lib().sfa_epic_fit_stage_ms(self.h, ms), "sfa_epic_fit_stage_ms")
         return dict(zip(("fit", "apply"), [float(v) for v in ms]))
+
+    def epic_batch(self, labs, costs, matches, params, workspace_bytes=0, with_status=False, stride=None):
+        """epic() for a batch of images of one size as one chain on the GPU (sfa_epic_batch).  labs: n fp32 (3, h, lab_stride) Lab images, or None when
+        params.saliency_th == 0; costs: n fp32 (h, w) cost maps, euc already added; matches: n fp32 (nm_i, 4) arrays of x1 y1 x2 y2 (nm_i may be 0); params:
+        epic_params(...).  Returns (flow_x, flow_y, rc, counts, kept): lists of fp32 (h, stride) planes (stride: w unless given; columns >= w, and the
+        planes of an image with rc 1, hold NaN), epic()'s return values, (3,) int arrays (matches in, after the saliency filter, after the consistency
+        filter) and the surviving matches (k, 4).  An image that does not fit workspace_bytes even alone raises, unless with_status: then a sixth list of
+        ints is returned, 1 for such an image (its entries in the other lists are None)"""
+        n = len(costs)
+        costs = [np.ascontiguousarray(c, dtype=np.float32) for c in costs]
+        matches = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 4) for m in matches]
+        assert len(matches) == n, "one match array per cost map"
+        h, w = costs[0].shape if n else (0, 0)
+        for c in costs:
+            assert c.shape == (h, w), "every cost map of the batch has one shape"
+        lab_stride = 0
+        if labs is not None:
+            labs = [np.ascontiguousarray(a, dtype=np.float32) for a in labs]
+            assert len(labs) == n, "one Lab image per cost map"
+            for a in labs:
+                assert a.ndim == 3 and a.shape[:2] == (3, h) and a.shape == labs[0].shape, "Lab images (3, h, lab_stride) of one shape"
+            lab_stride = labs[0].shape[2] if n else 0
+        stride = w if stride is None else int(stride)
+        nm = [len(m) for m in matches]
+        fx = [np.full((h, max(stride, 0)), np.nan, np.float32) for _ in range(n)]
+        fy = [np.full((h, max(stride, 0)), np.nan, np.float32) for _ in range(n)]
+        kept = [np.zeros((max(k, 1), 4), np.float32) for k in nm]
+        k = max(n, 1)
+        rc = (C.c_int * k)(*([-9] * k))
+        counts = ((C.c_int * 3) * k)()
+        status = (C.c_int * k)()
+        L = lib()
+        _i = C.POINTER(C.c_int)
+        L.sfa_epic_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(EpicParams), C.POINTER(_f), C.c_int, C.POINTER(_f), C.POINTER(_f), _i,
+                                     C.POINTER(_f), C.POINTER(_f), C.c_int, _i, C.POINTER(C.c_int * 3), C.POINTER(_f), C.c_size_t, _i]
+        self._ck(L.sfa_epic_batch(self.h, n, w, h, C.byref(params), (_f * k)(*[fptr(a) for a in labs]) if labs is not None else None, lab_stride,
+                                  (_f * k)(*[fptr(c) for c in costs]), (_f * k)(*[fptr(m) for m in matches]), (C.c_int * k)(*nm),
+                                  (_f * k)(*[fptr(a) for a in fx]), (_f * k)(*[fptr(a) for a in fy]), stride, rc, counts, (_f * k)(*[fptr(a) for a in kept]),
+                                  int(workspace_bytes), status), "sfa_epic_batch")
+        status = list(status[:n])
+        rc = [int(v) for v in rc[:n]]
+        counts = [np.array(list(c), np.int32) for c in counts[:n]]
+        kept = [a[:int(c[2])] for a, c in zip(kept, counts)]
+        if with_status:
+            pick = lambda xs: [None if s else x for x, s in zip(xs, status)]
+            return pick(fx), pick(fy), pick(rc), pick(counts), pick(kept), status
+        if any(status):
+            raise SlowflowError("sfa_epic_batch: images %s do not fit a workspace of %d bytes" % ([i for i, s in enumerate(status) if s], workspace_bytes))
+        return fx, fy, rc, counts, kept
+
+    def epic_saliency(self, labs, sigma_image=0.8, sigma_matrix=1.0, w=None):
+        """the saliency of n Lab images (3, h, stride) of one shape (sfa_epic_saliency_batch): n fp32 (h, stride) planes, the bits of the host's saliency(),
+        padding columns 0.  w: the images' width inside rows of `stride` floats (None: the whole row)"""
+        n = len(labs)
+        labs = [np.ascontiguousarray(a, dtype=np.float32) for a in labs]
+        for a in labs:
+            assert a.ndim == 3 and a.shape[0] == 3 and a.shape == labs[0].shape, "Lab images (3, h, stride) of one shape"
+        h, stride = labs[0].shape[1:] if n else (0, 0)
+        w = stride if w is None else int(w)
+        out = [np.full((h, stride), np.nan, np.float32) for _ in range(n)]
+        L = lib()
+        L.sfa_epic_saliency_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(_f), C.c_int, C.c_float, C.c_float, C.POINTER(_f)]
+        k = max(n, 1)
+        self._ck(L.sfa_epic_saliency_batch(self.h, n, w, h, (_f * k)(*[fptr(a) for a in labs]), stride, float(sigma_image), float(sigma_matrix),
+                                           (_f * k)(*[fptr(a) for a in out])), "sfa_epic_saliency_batch")
+        return out
+
+    def epic_batch_stage_ms(self):
+        """the kernel milliseconds of the last epic_batch by stage (sfa_epic_batch_stage_ms)"""
+        ms = (C.c_float * 8)()
+        self._ck(lib().sfa_epic_batch_stage_ms(self.h, ms), "sfa_epic_batch_stage_ms")
+        return dict(zip(("saliency", "filters", "nn_prefilter", "estimate", "nn", "weights", "fit", "apply"), [float(v) for v in ms]))
 
     def flow_magnitude_quantile(self, us, vs, w, flow_scale, q):
         """adaptiveFR's quantile (sfa_flow_magnitude_quantile): the fields' magnitudes after scaling by flow_scale, the rank rule of

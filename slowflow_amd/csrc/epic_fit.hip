@@ -30,11 +30,7 @@ constexpr int kFitTile = 32, kFitRow = kFitTile + 1;                 // columns 
 constexpr int kMaxSubBatch = 4096;                                   // images per launch (the grids' second dimension)
 constexpr long long kMaxPixels = 1ll << 29;                          // as sfa_epic_nearest_seeds_batch, whose labels these are
 
-// What the kernels know of one image: all pointers device memory
-struct FitImg {
-    const int2 *seeds; const float2 *vects; const int *index; const float *weight; const int *lab;
-    float *model, *fx, *fy; int ns;
-};
+using FitImg = EpicFitImg;                                           // what the kernels know of one image (sfa_internal.h)
 
 // f(s, coef, seeds[s], vects[s]) for every entry of seed i's row with 0 <= s < ns, in list order.  Every lane of the workgroup calls this (the barriers);
 // `live` says whether the lane has a seed.  The gathers of a tile's entries do not wait for the entry before them: an entry that is skipped reads seed 0
@@ -122,8 +118,9 @@ __device__ inline void solve3_pair(const double m[6], const double rx[3], const 
 }
 
 template <int kMethod, bool kStaged>
-__global__ void __launch_bounds__(kFitLanes) k_epic_fit(const FitImg *imgs, int nn) {
+__global__ void __launch_bounds__(kFitLanes) k_epic_fit(const FitImg *imgs) {
     const FitImg im = imgs[blockIdx.y];
+    const int nn = im.nn;
     const int seed0 = blockIdx.x * kFitLanes, lane = threadIdx.x, i = seed0 + lane;
     if (seed0 >= im.ns) return;                                      // (the whole workgroup)
     const bool live = i < im.ns;
@@ -196,6 +193,22 @@ struct Bump {
 };
 
 }  // namespace
+
+// The two launches on records already in device memory (sfa_internal.h): no allocation, no copy, no wait
+void epic_fit_device(sfa_ctx *ctx, int method, int m, int ns_max, const EpicFitImg *d_imgs) {
+    const bool plain = sw_int(Switches::EPIC_FIT_PLAIN, 0) != 0;     // the lists read row by row from global memory (the release build: constant false)
+    const dim3 grid(blocks(ns_max, kFitLanes), m), wave(kFitLanes);
+    hipStream_t st = ctx->stream;
+    if (method == 0 && !plain) hipLaunchKernelGGL((k_epic_fit<0, true>), grid, wave, 0, st, d_imgs);
+    if (method == 1 && !plain) hipLaunchKernelGGL((k_epic_fit<1, true>), grid, wave, 0, st, d_imgs);
+    SFA_FULL(if (method == 0 && plain) hipLaunchKernelGGL((k_epic_fit<0, false>), grid, wave, 0, st, d_imgs);)
+    SFA_FULL(if (method == 1 && plain) hipLaunchKernelGGL((k_epic_fit<1, false>), grid, wave, 0, st, d_imgs);)
+}
+void epic_apply_device(sfa_ctx *ctx, int method, int m, int w, int h, const EpicFitImg *d_imgs) {
+    const size_t npix = (size_t)w * h;
+    hipLaunchKernelGGL(k_epic_apply, dim3(blocks(npix, 256), m), dim3(256), 0, ctx->stream, d_imgs, w, (int)npix, method);
+}
+
 }  // namespace sfa
 
 using namespace sfa;
@@ -247,7 +260,6 @@ int sfa_epic_interpolate_batch(sfa_ctx *ctx, int n, int w, int h, int method, co
     } ev;
     for (hipEvent_t &v : ev.e) SFA_HIP(ctx, hipEventCreate(&v));
     ctx->epic_fit_ms[0] = ctx->epic_fit_ms[1] = 0.f;
-    const bool plain = sw_int(Switches::EPIC_FIT_PLAIN, 0) != 0;     // the lists read row by row from global memory (the release build: constant false)
     int first = 0;
     while (first < n) {
         if (need(first) > budget) { status[first++] = 1; continue; } // not even alone: flagged, its outputs untouched
@@ -269,7 +281,7 @@ int sfa_epic_interpolate_batch(sfa_ctx *ctx, int n, int w, int h, int method, co
             float2 *v = b.take<float2>(ns[i]);
             int *ix = b.take<int>(list);
             float *wt = b.take<float>(list);
-            im.seeds = s; im.vects = v; im.index = ix; im.weight = wt; im.ns = ns[i];
+            im.seeds = s; im.vects = v; im.index = ix; im.weight = wt; im.ns = ns[i]; im.nn = nn;
             im.model = b.take<float>((size_t)ns[i] * mf);
             SFA_HIP(ctx, hipMemcpyAsync(s, seeds_xy[i], (size_t)ns[i] * 8, hipMemcpyHostToDevice, st));
             SFA_HIP(ctx, hipMemcpyAsync(v, vects[i], (size_t)ns[i] * 8, hipMemcpyHostToDevice, st));
@@ -283,14 +295,10 @@ int sfa_epic_interpolate_batch(sfa_ctx *ctx, int n, int w, int h, int method, co
             ns_max = std::max(ns_max, ns[i]);
         }
         SFA_HIP(ctx, hipMemcpyAsync(d_imgs, imgs.data(), (size_t)m * sizeof(FitImg), hipMemcpyHostToDevice, st));
-        const dim3 grid(blocks(ns_max, kFitLanes), m), wave(kFitLanes);
         (void)hipEventRecord(ev.e[0], st);
-        if (method == 0 && !plain) hipLaunchKernelGGL((k_epic_fit<0, true>), grid, wave, 0, st, d_imgs, nn);
-        if (method == 1 && !plain) hipLaunchKernelGGL((k_epic_fit<1, true>), grid, wave, 0, st, d_imgs, nn);
-        SFA_FULL(if (method == 0 && plain) hipLaunchKernelGGL((k_epic_fit<0, false>), grid, wave, 0, st, d_imgs, nn);)
-        SFA_FULL(if (method == 1 && plain) hipLaunchKernelGGL((k_epic_fit<1, false>), grid, wave, 0, st, d_imgs, nn);)
+        epic_fit_device(ctx, method, m, ns_max, d_imgs);
         (void)hipEventRecord(ev.e[1], st);
-        if (flows) hipLaunchKernelGGL(k_epic_apply, dim3(blocks(npix, 256), m), dim3(256), 0, st, d_imgs, w, (int)npix, method);
+        if (flows) epic_apply_device(ctx, method, m, w, h, d_imgs);
         (void)hipEventRecord(ev.e[2], st);
         SFA_HIP(ctx, hipGetLastError());
         for (int k = 0; k < m; k++) {

@@ -12,7 +12,8 @@
 //   k_epic_dijkstra      one thread per (image, seed): `done` a dense row of ns floats, the heap (epic_heap.h: libstdc++'s push_heap / pop_heap) in global memory,
 //                        its capacity the bound 1 + min((nn - 1) maxdeg, 2 E): every push follows the expansion of one directed edge, at most nn - 1 nodes expand
 //   k_epic_assemble      query q takes the list of the seed whose region its pixel lies in, plus its own distance
-// The host side runs the batch in sub-batches that fit a workspace budget; an image that does not fit alone is flagged, never truncated.
+// epic_nn_device (sfa_internal.h) is the stage on buffers already in device memory, with the neighbour count per image; the entry point wraps it (allocate, upload,
+// call, download, wait) and runs the batch in sub-batches that fit a workspace budget; an image that does not fit alone is flagged, never truncated.
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -33,7 +34,7 @@ constexpr long long kMaxPixels = 1ll << 29;                           // twice t
 
 // What the kernels know of one image: all pointers device memory
 struct EpicImg {
-    const float *cost; float *dmap; int *lab; const int *seeds; int ns;
+    const float *cost; float *dmap; int *lab; const int *seeds; int ns, nn;
     unsigned *cnt;                                                   // [0] border pairs, [1] edges E, [2] largest degree, [3] heap overflow (never, by the bound)
     unsigned long long *keys; unsigned *lens; int log_cap;           // the table: 1 << log_cap slots
     int *deg, *rowptr, *cursor; int *adj_n; float *adj_l;
@@ -260,8 +261,9 @@ struct StridedHeap {                                                 // entry k 
     __device__ epic_heap_item &operator[](int k) const { return p[(size_t)k * stride]; }
 };
 
-__global__ void __launch_bounds__(64) k_epic_dijkstra(const EpicImg *imgs, int nn) {          // epic_aux.cpp:44-87
+__global__ void __launch_bounds__(64) k_epic_dijkstra(const EpicImg *imgs) {                  // epic_aux.cpp:44-87
     const EpicImg im = imgs[blockIdx.y];
+    const int nn = im.nn;
     const int seed = blockIdx.x * blockDim.x + threadIdx.x;
     if (seed >= im.ns) return;
     float *done = im.done + (size_t)seed * im.ns;                    // cleared to 0x7F bytes by the host
@@ -286,8 +288,9 @@ __global__ void __launch_bounds__(64) k_epic_dijkstra(const EpicImg *imgs, int n
     }
 }
 
-__global__ void k_epic_assemble(const EpicImg *imgs, int tx, int nn) {        // epic_aux.cpp:366-374
+__global__ void k_epic_assemble(const EpicImg *imgs, int tx) {                // epic_aux.cpp:366-374
     const EpicImg im = imgs[blockIdx.y];
+    const int nn = im.nn;
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= (size_t)im.ns * nn) return;
     const int q = (int)(k / nn), j = (int)(k % nn);
@@ -312,6 +315,157 @@ struct Bump {
 
 using namespace sfa;
 
+// The stage on buffers already in device memory (sfa_internal.h).  What it allocates besides -- the records, dmap, the search's own lists, then the table and
+// rows, then `done` and the heaps, each sized by the counts the host reads in between -- stays within `budget`; the leading *done images that fit whole are
+// computed, and when the call returns the stream has been waited for
+int sfa::epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const EpicNnIo *io, size_t budget, int *done_out, size_t *estimate, float ms_out[5]) {
+    *done_out = 0;
+    const size_t npix = (size_t)w * h;
+    hipStream_t st = ctx->stream;
+    // what an image needs here: before anything ran (record, dmap, the search's lists, counters), once its border pairs are counted (table, degrees), once
+    // its graph is known (rows, search)
+    auto need1 = [&](int k) { return al(sizeof(EpicImg)) + al(npix * 4) + 2 * al((size_t)io[k].ns * io[k].nn * 4) + al(16); };
+    auto log_cap_of = [](unsigned pairs) { int l = 4; while (l < 31 && (1ull << l) < 2ull * pairs) l++; return l; };
+    auto need2 = [&](int k, unsigned pairs) { return al((size_t)8 << log_cap_of(pairs)) + al((size_t)4 << log_cap_of(pairs)) + 2 * al((size_t)io[k].ns * 4) + al(((size_t)io[k].ns + 1) * 4); };
+    auto heap_cap_of = [&](int k, unsigned E, unsigned maxdeg) { return (size_t)1 + std::min((size_t)(io[k].nn - 1) * maxdeg, (size_t)2 * E); };
+    auto need3 = [&](int k, unsigned E, unsigned maxdeg) {
+        return 2 * al((size_t)2 * E * 4 + 4) + al((size_t)io[k].ns * io[k].ns * 4) + al((size_t)io[k].ns * heap_cap_of(k, E, maxdeg) * sizeof(epic_heap_item));
+    };
+    // the kernels' time by group (sfa_epic_nn_stage_ms): events around them, read after each stage's wait
+    struct Events {
+        hipEvent_t e[10] = {};
+        ~Events() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
+    } ev;
+    for (hipEvent_t &v : ev.e) SFA_HIP(ctx, hipEventCreate(&v));
+    auto mark = [&](int k) { (void)hipEventRecord(ev.e[k], st); };
+    auto spent = [&](int slot, int k) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]) == hipSuccess) ms_out[slot] += ms; };
+    // ---- stage 1: seeds, sweeps, border pairs ---------------------------------------------------------------------------------------------------------
+    DevMem mem1, mem2, mem3;
+    size_t bytes1 = 0;
+    for (int k = 0; k < m; k++) bytes1 += need1(k);
+    if (bytes1 > budget) return SFA_OK;
+    SFA_TRY(mem1.alloc(ctx, bytes1));
+    Bump b1{static_cast<char *>(mem1.p)};
+    EpicImg *d_imgs = b1.take<EpicImg>(m);
+    std::vector<EpicImg> imgs(m);
+    std::vector<unsigned *> cnts(m);
+    int ns_max = 0;
+    for (int k = 0; k < m; k++) {
+        EpicImg &im = imgs[k];
+        memset(&im, 0, sizeof im);
+        const size_t list = (size_t)io[k].ns * io[k].nn;
+        im.cost = io[k].cost; im.seeds = io[k].seeds; im.ns = io[k].ns; im.nn = io[k].nn;
+        im.dmap = b1.take<float>(npix); im.lab = io[k].lab;
+        im.nnf = b1.take<int>(list); im.dis = b1.take<float>(list);
+        im.out_index = io[k].index; im.out_dist = io[k].dist;
+        im.cnt = cnts[k] = b1.take<unsigned>(4);
+        SFA_HIP(ctx, hipMemsetAsync(im.nnf, 0xFF, list * 4, st));                     // -1
+        SFA_HIP(ctx, hipMemsetAsync(im.dis, 0x7F, list * 4, st));                     // 0x7F7F7F7F
+        ns_max = std::max(ns_max, im.ns);
+    }
+    auto put_imgs = [&](int count) { return hipMemcpyAsync(d_imgs, imgs.data(), (size_t)count * sizeof(EpicImg), hipMemcpyHostToDevice, st); };
+    SFA_HIP(ctx, put_imgs(m));
+    mark(0);
+    hipLaunchKernelGGL(k_epic_init, dim3(blocks(std::max(npix, (size_t)4), 256), m), dim3(256), 0, st, d_imgs, (int)npix);
+    hipLaunchKernelGGL(k_epic_seed_label, dim3(blocks(ns_max, 256), m), dim3(256), 0, st, d_imgs, w);
+    hipLaunchKernelGGL(k_epic_seed_cost, dim3(blocks(ns_max, 256), m), dim3(256), 0, st, d_imgs, w);
+    mark(1);
+    hipLaunchKernelGGL(k_epic_sweeps, dim3(m), dim3(kSweepThreads), (size_t)16 * std::min(w, h), st, d_imgs, w, h);
+    mark(2);
+    const size_t inner = (size_t)(w - 1) * (h - 1);                  // pixels with a left and an upper neighbour
+    if (inner) hipLaunchKernelGGL(k_epic_count_borders, dim3(blocks(inner, 256), m), dim3(256), 0, st, d_imgs, w, h);
+    mark(3);
+    std::vector<unsigned> cnt((size_t)4 * m);
+    for (int k = 0; k < m; k++) SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
+    SFA_TRY(sfa_ctx_sync(ctx));
+    spent(0, 0); spent(1, 1); spent(2, 2);
+    // ---- stage 2: the region graph of the images whose tables fit too ----------------------------------------------------------------------------------
+    int k1 = 0;
+    size_t bytes2 = 0;
+    for (; k1 < m; k1++) {
+        const size_t add = need2(k1, cnt[4 * k1]);
+        if (bytes1 + bytes2 + add > budget) break;
+        bytes2 += add;
+    }
+    if (k1 == 0) return SFA_OK;
+    SFA_TRY(mem2.alloc(ctx, bytes2));
+    Bump b2{static_cast<char *>(mem2.p)};
+    int log_cap_max = 0;
+    for (int k = 0; k < k1; k++) {
+        EpicImg &im = imgs[k];
+        im.log_cap = log_cap_of(cnt[4 * k]);
+        log_cap_max = std::max(log_cap_max, im.log_cap);
+        im.keys = b2.take<unsigned long long>((size_t)1 << im.log_cap);
+        im.lens = b2.take<unsigned>((size_t)1 << im.log_cap);
+        im.deg = b2.take<int>(im.ns); im.cursor = b2.take<int>(im.ns); im.rowptr = b2.take<int>((size_t)im.ns + 1);
+        SFA_HIP(ctx, hipMemsetAsync(im.keys, 0xFF, (size_t)8 << im.log_cap, st));         // kEmptyKey
+        SFA_HIP(ctx, hipMemsetAsync(im.lens, 0xFF, (size_t)4 << im.log_cap, st));         // above every length
+        SFA_HIP(ctx, hipMemsetAsync(im.deg, 0, (size_t)im.ns * 4, st));
+    }
+    SFA_HIP(ctx, put_imgs(k1));
+    const int slot_blocks = blocks((size_t)1 << log_cap_max, 256);
+    mark(4);
+    if (inner) hipLaunchKernelGGL(k_epic_insert, dim3(blocks(inner, 256), k1), dim3(256), 0, st, d_imgs, w, h);
+    hipLaunchKernelGGL(k_epic_degrees, dim3(slot_blocks, k1), dim3(256), 0, st, d_imgs);
+    hipLaunchKernelGGL(k_epic_rows, dim3(k1), dim3(256), 0, st, d_imgs);
+    mark(5);
+    for (int k = 0; k < k1; k++) SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
+    SFA_TRY(sfa_ctx_sync(ctx));
+    spent(2, 4);
+    // ---- stage 3: rows, the search, the lists of the images that fit whole ------------------------------------------------------------------------------
+    int k2 = 0;
+    size_t bytes3 = 0;
+    for (; k2 < k1; k2++) {
+        if (heap_cap_of(k2, cnt[4 * k2 + 1], cnt[4 * k2 + 2]) > (size_t)INT_MAX) break;   // (a heap the search could not index: far beyond any budget)
+        const size_t add = need3(k2, cnt[4 * k2 + 1], cnt[4 * k2 + 2]);
+        if (estimate) *estimate = std::max(*estimate, need1(k2) + need2(k2, cnt[4 * k2]) + add);
+        if (bytes1 + bytes2 + bytes3 + add > budget) break;
+        bytes3 += add;
+    }
+    if (k2 == 0) return SFA_OK;
+    SFA_TRY(mem3.alloc(ctx, bytes3));
+    Bump b3{static_cast<char *>(mem3.p)};
+    for (int k = 0; k < k2; k++) {
+        EpicImg &im = imgs[k];
+        const unsigned E = cnt[4 * k + 1];
+        im.adj_n = b3.take<int>((size_t)2 * E + 1); im.adj_l = b3.take<float>((size_t)2 * E + 1);
+        im.done = b3.take<float>((size_t)im.ns * im.ns);
+        im.heap_cap = (int)heap_cap_of(k, E, cnt[4 * k + 2]);
+        im.heap = b3.take<epic_heap_item>((size_t)im.ns * im.heap_cap);
+        SFA_HIP(ctx, hipMemsetAsync(im.done, 0x7F, (size_t)im.ns * im.ns * 4, st));
+    }
+    SFA_HIP(ctx, put_imgs(k2));
+    mark(6);
+    hipLaunchKernelGGL(k_epic_fill, dim3(slot_blocks, k2), dim3(256), 0, st, d_imgs);
+    hipLaunchKernelGGL(k_epic_sort_rows, dim3(blocks(ns_max, 64), k2), dim3(64), 0, st, d_imgs);
+    mark(7);
+    hipLaunchKernelGGL(k_epic_dijkstra, dim3(blocks(ns_max, 64), k2), dim3(64), 0, st, d_imgs);
+    mark(8);
+    size_t list_max = 0;
+    for (int k = 0; k < k2; k++) list_max = std::max(list_max, (size_t)imgs[k].ns * imgs[k].nn);
+    hipLaunchKernelGGL(k_epic_assemble, dim3(blocks(list_max, 256), k2), dim3(256), 0, st, d_imgs, w);
+    mark(9);
+    for (int k = 0; k < k2; k++) SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
+    SFA_TRY(sfa_ctx_sync(ctx));
+    spent(2, 6); spent(3, 7); spent(4, 8);
+    for (int k = 0; k < k2; k++)
+        if (cnt[4 * k + 3]) return set_error(ctx, SFA_ERR_HIP, "%s: image %d of the sub-batch: the search's heap met its capacity of %d entries", fn, k, imgs[k].heap_cap);
+    *done_out = k2;
+    return SFA_OK;
+}
+
+// what epic_nn_device allocates for an image before it has seen it: the part known beforehand and `done`
+size_t sfa::epic_nn_need0(int w, int h, int ns, int nn) {
+    return al(sizeof(EpicImg)) + al((size_t)w * h * 4) + 2 * al((size_t)ns * nn * 4) + al(16) + al((size_t)ns * ns * 4);
+}
+
+// the image sizes the kernels take, refused in the name of entry point `fn`
+int sfa::epic_nn_check_sizes(sfa_ctx *ctx, const char *fn, int w, int h) {
+    if ((long long)w * h > kMaxPixels) REFUSE("%s: w * h = %lld pixels (at most 2^29: pixels and the border table are indexed with 32 bits)", fn, (long long)w * h);
+    if (std::min(w, h) > kMaxShortSide) REFUSE("%s: w x h = %d x %d (the shorter side is at most %d: two diagonals of the sweep live in LDS)", fn, w, h, kMaxShortSide);
+    return SFA_OK;
+}
+
 int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float *const *cost, const int *const *seeds_xy, const int *ns, int nn,
                                  int *const *labels, int *const *nn_index, float *const *nn_dist, size_t workspace_bytes, int *status) {
     const char *fn = __func__;
@@ -322,8 +476,7 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
     if (!cost || !seeds_xy || !ns || !labels || !nn_index || !nn_dist || !status) {
         REFUSE("%s: %s is null", fn, !cost ? "cost" : !seeds_xy ? "seeds_xy" : !ns ? "ns" : !labels ? "labels" : !nn_index ? "nn_index" : !nn_dist ? "nn_dist" : "status");
     }
-    if ((long long)w * h > kMaxPixels) REFUSE("%s: w * h = %lld pixels (at most 2^29: pixels and the border table are indexed with 32 bits)", fn, (long long)w * h);
-    if (std::min(w, h) > kMaxShortSide) REFUSE("%s: w x h = %d x %d (the shorter side is at most %d: two diagonals of the sweep live in LDS)", fn, w, h, kMaxShortSide);
+    SFA_TRY(epic_nn_check_sizes(ctx, fn, w, h));
     for (int i = 0; i < n; i++) {
         if (ns[i] < 1) REFUSE("%s: ns[%d] = %d (at least one seed)", fn, i, ns[i]);
         if (!cost[i] || !seeds_xy[i] || !labels[i] || !nn_index[i] || !nn_dist[i]) {
@@ -344,165 +497,56 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
     }
     const size_t npix = (size_t)w * h;
     hipStream_t st = ctx->stream;
-    // what an image needs: before anything ran (planes, seeds, lists), once its border pairs are counted (table, degrees), once its graph is known (rows, search)
-    auto need1 = [&](int i) { return al(sizeof(EpicImg)) + 3 * al(npix * 4) + al((size_t)ns[i] * 8) + 4 * al((size_t)ns[i] * nn * 4) + al(16); };
-    auto log_cap_of = [](unsigned pairs) { int l = 4; while (l < 31 && (1ull << l) < 2ull * pairs) l++; return l; };
-    auto need2 = [&](int i, unsigned pairs) { return al((size_t)8 << log_cap_of(pairs)) + al((size_t)4 << log_cap_of(pairs)) + 2 * al((size_t)ns[i] * 4) + al(((size_t)ns[i] + 1) * 4); };
-    auto heap_cap_of = [&](unsigned E, unsigned maxdeg) { return (size_t)1 + std::min((size_t)(nn - 1) * maxdeg, (size_t)2 * E); };
-    auto need3 = [&](int i, unsigned E, unsigned maxdeg) {
-        return 2 * al((size_t)2 * E * 4 + 4) + al((size_t)ns[i] * ns[i] * 4) + al((size_t)ns[i] * heap_cap_of(E, maxdeg) * sizeof(epic_heap_item));
-    };
+    // what the call itself holds of an image: cost, labels, seeds, the two lists
+    auto need_io = [&](int i) { return 2 * al(npix * 4) + al((size_t)ns[i] * 8) + 2 * al((size_t)ns[i] * nn * 4); };
     for (int i = 0; i < n; i++) status[i] = 0;
-    // the kernels' time by group (sfa_epic_nn_stage_ms): events around them, read after each stage's wait
-    struct Events {
-        hipEvent_t e[10] = {};
-        ~Events() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
-    } ev;
-    for (hipEvent_t &v : ev.e) SFA_HIP(ctx, hipEventCreate(&v));
     for (float &v : ctx->epic_ms) v = 0.f;
-    auto mark = [&](int k) { (void)hipEventRecord(ev.e[k], st); };
-    auto spent = [&](int slot, int k) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]) == hipSuccess) ctx->epic_ms[slot] += ms; };
     // A sub-batch is sized by what is known beforehand (planes, lists, `done`) or, once an image has been through, by the largest whole need seen.  What is
     // allocated never exceeds the budget: where the tables or heaps of a sub-batch's first image do not fit beside what the sub-batch already holds, that
     // image is tried alone before it is flagged
-    auto need0 = [&](int i) { return need1(i) + al((size_t)ns[i] * ns[i] * 4); };
-    size_t estimate = 0;
+    auto need0 = [&](int i) { return need_io(i) + epic_nn_need0(w, h, ns[i], nn); };
+    size_t estimate = 0;                                             // (of epic_nn_device's part)
     bool alone = false;
     int first = 0;
     while (first < n) {
         int m = 0;
         for (size_t used = 0; first + m < n && m < kMaxSubBatch && !(alone && m == 1); m++) {
-            used += std::max(need0(first + m), estimate);
+            used += std::max(need0(first + m), estimate ? estimate + need_io(first + m) : 0);
             if (used > budget) break;
         }
         if (m == 0 && need0(first) > budget) { status[first++] = 1; alone = false; continue; }
         m = std::max(m, 1);                                          // (the estimate is another image's: this one may still fit)
-        auto no_room = [&]() {                                       // for the first image of the sub-batch: alone next time, or flagged if it was alone
-            if (m > 1) alone = true;
-            else { status[first++] = 1; alone = false; }
-        };
-        // ---- stage 1: planes, seeds, sweeps, border pairs -----------------------------------------------------------------------------------------------
-        DevMem mem1, mem2, mem3;
-        size_t bytes1 = 0;
-        for (int k = 0; k < m; k++) bytes1 += need1(first + k);
-        SFA_TRY(mem1.alloc(ctx, bytes1));
-        Bump b1{static_cast<char *>(mem1.p)};
-        EpicImg *d_imgs = b1.take<EpicImg>(m);
-        std::vector<EpicImg> imgs(m);
-        std::vector<unsigned *> cnts(m);
+        DevMem mem;
+        size_t bytes = 0;
+        for (int k = 0; k < m; k++) bytes += need_io(first + k);
+        SFA_TRY(mem.alloc(ctx, bytes));
+        Bump b{static_cast<char *>(mem.p)};
+        std::vector<EpicNnIo> io(m);
         for (int k = 0; k < m; k++) {
             const int i = first + k;
-            EpicImg &im = imgs[k];
-            memset(&im, 0, sizeof im);
-            float *c = b1.take<float>(npix);
-            int *s = b1.take<int>((size_t)ns[i] * 2);
-            im.cost = c; im.seeds = s; im.ns = ns[i];
-            im.dmap = b1.take<float>(npix); im.lab = b1.take<int>(npix);
-            im.nnf = b1.take<int>((size_t)ns[i] * nn); im.dis = b1.take<float>((size_t)ns[i] * nn);
-            im.out_index = b1.take<int>((size_t)ns[i] * nn); im.out_dist = b1.take<float>((size_t)ns[i] * nn);
-            im.cnt = cnts[k] = b1.take<unsigned>(4);
+            float *c = b.take<float>(npix);
+            int *s = b.take<int>((size_t)ns[i] * 2);
+            io[k].cost = c; io[k].seeds = s; io[k].ns = ns[i]; io[k].nn = nn;
+            io[k].lab = b.take<int>(npix);
+            io[k].index = b.take<int>((size_t)ns[i] * nn); io[k].dist = b.take<float>((size_t)ns[i] * nn);
             SFA_HIP(ctx, hipMemcpyAsync(c, cost[i], npix * 4, hipMemcpyHostToDevice, st));
             SFA_HIP(ctx, hipMemcpyAsync(s, seeds_xy[i], (size_t)ns[i] * 8, hipMemcpyHostToDevice, st));
-            SFA_HIP(ctx, hipMemsetAsync(im.nnf, 0xFF, (size_t)ns[i] * nn * 4, st));       // -1
-            SFA_HIP(ctx, hipMemsetAsync(im.dis, 0x7F, (size_t)ns[i] * nn * 4, st));       // 0x7F7F7F7F
         }
-        int ns_max = 0;
-        for (int k = 0; k < m; k++) ns_max = std::max(ns_max, ns[first + k]);
-        auto put_imgs = [&](int count) { return hipMemcpyAsync(d_imgs, imgs.data(), (size_t)count * sizeof(EpicImg), hipMemcpyHostToDevice, st); };
-        SFA_HIP(ctx, put_imgs(m));
-        mark(0);
-        hipLaunchKernelGGL(k_epic_init, dim3(blocks(std::max(npix, (size_t)4), 256), m), dim3(256), 0, st, d_imgs, (int)npix);
-        hipLaunchKernelGGL(k_epic_seed_label, dim3(blocks(ns_max, 256), m), dim3(256), 0, st, d_imgs, w);
-        hipLaunchKernelGGL(k_epic_seed_cost, dim3(blocks(ns_max, 256), m), dim3(256), 0, st, d_imgs, w);
-        mark(1);
-        hipLaunchKernelGGL(k_epic_sweeps, dim3(m), dim3(kSweepThreads), (size_t)16 * std::min(w, h), st, d_imgs, w, h);
-        mark(2);
-        const size_t inner = (size_t)(w - 1) * (h - 1);              // pixels with a left and an upper neighbour
-        if (inner) hipLaunchKernelGGL(k_epic_count_borders, dim3(blocks(inner, 256), m), dim3(256), 0, st, d_imgs, w, h);
-        mark(3);
-        std::vector<unsigned> cnt((size_t)4 * m);
-        for (int k = 0; k < m; k++) SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
-        SFA_TRY(sfa_ctx_sync(ctx));
-        spent(0, 0); spent(1, 1); spent(2, 2);
-        // ---- stage 2: the region graph of the images whose tables fit too ------------------------------------------------------------------------------
-        int k1 = 0;
-        size_t bytes2 = 0;
-        for (; k1 < m; k1++) {
-            const size_t add = need2(first + k1, cnt[4 * k1]);
-            if (bytes1 + bytes2 + add > budget) break;
-            bytes2 += add;
+        int done = 0;
+        SFA_TRY(epic_nn_device(ctx, fn, m, w, h, io.data(), budget - bytes, &done, &estimate, ctx->epic_ms));
+        if (done == 0) {                                             // the first image of the sub-batch: alone next time, or flagged if it was alone
+            if (m > 1) alone = true;
+            else { status[first++] = 1; alone = false; }
+            continue;
         }
-        if (k1 == 0) { no_room(); continue; }
-        SFA_TRY(mem2.alloc(ctx, bytes2));
-        Bump b2{static_cast<char *>(mem2.p)};
-        int log_cap_max = 0;
-        for (int k = 0; k < k1; k++) {
-            EpicImg &im = imgs[k];
-            im.log_cap = log_cap_of(cnt[4 * k]);
-            log_cap_max = std::max(log_cap_max, im.log_cap);
-            im.keys = b2.take<unsigned long long>((size_t)1 << im.log_cap);
-            im.lens = b2.take<unsigned>((size_t)1 << im.log_cap);
-            im.deg = b2.take<int>(im.ns); im.cursor = b2.take<int>(im.ns); im.rowptr = b2.take<int>((size_t)im.ns + 1);
-            SFA_HIP(ctx, hipMemsetAsync(im.keys, 0xFF, (size_t)8 << im.log_cap, st));     // kEmptyKey
-            SFA_HIP(ctx, hipMemsetAsync(im.lens, 0xFF, (size_t)4 << im.log_cap, st));     // above every length
-            SFA_HIP(ctx, hipMemsetAsync(im.deg, 0, (size_t)im.ns * 4, st));
-        }
-        SFA_HIP(ctx, put_imgs(k1));
-        const int slot_blocks = blocks((size_t)1 << log_cap_max, 256);
-        mark(4);
-        if (inner) hipLaunchKernelGGL(k_epic_insert, dim3(blocks(inner, 256), k1), dim3(256), 0, st, d_imgs, w, h);
-        hipLaunchKernelGGL(k_epic_degrees, dim3(slot_blocks, k1), dim3(256), 0, st, d_imgs);
-        hipLaunchKernelGGL(k_epic_rows, dim3(k1), dim3(256), 0, st, d_imgs);
-        mark(5);
-        for (int k = 0; k < k1; k++) SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
-        SFA_TRY(sfa_ctx_sync(ctx));
-        spent(2, 4);
-        // ---- stage 3: rows, the search, the lists of the images that fit whole --------------------------------------------------------------------------
-        int k2 = 0;
-        size_t bytes3 = 0;
-        for (; k2 < k1; k2++) {
-            const int i = first + k2;
-            if (heap_cap_of(cnt[4 * k2 + 1], cnt[4 * k2 + 2]) > (size_t)INT_MAX) break;   // (a heap the search could not index: far beyond any budget)
-            const size_t add = need3(i, cnt[4 * k2 + 1], cnt[4 * k2 + 2]);
-            estimate = std::max(estimate, need1(i) + need2(i, cnt[4 * k2]) + add);
-            if (bytes1 + bytes2 + bytes3 + add > budget) break;
-            bytes3 += add;
-        }
-        if (k2 == 0) { no_room(); continue; }
-        SFA_TRY(mem3.alloc(ctx, bytes3));
-        Bump b3{static_cast<char *>(mem3.p)};
-        for (int k = 0; k < k2; k++) {
-            EpicImg &im = imgs[k];
-            const unsigned E = cnt[4 * k + 1];
-            im.adj_n = b3.take<int>((size_t)2 * E + 1); im.adj_l = b3.take<float>((size_t)2 * E + 1);
-            im.done = b3.take<float>((size_t)im.ns * im.ns);
-            im.heap_cap = (int)heap_cap_of(E, cnt[4 * k + 2]);
-            im.heap = b3.take<epic_heap_item>((size_t)im.ns * im.heap_cap);
-            SFA_HIP(ctx, hipMemsetAsync(im.done, 0x7F, (size_t)im.ns * im.ns * 4, st));
-        }
-        SFA_HIP(ctx, put_imgs(k2));
-        mark(6);
-        hipLaunchKernelGGL(k_epic_fill, dim3(slot_blocks, k2), dim3(256), 0, st, d_imgs);
-        hipLaunchKernelGGL(k_epic_sort_rows, dim3(blocks(ns_max, 64), k2), dim3(64), 0, st, d_imgs);
-        mark(7);
-        hipLaunchKernelGGL(k_epic_dijkstra, dim3(blocks(ns_max, 64), k2), dim3(64), 0, st, d_imgs, nn);
-        mark(8);
-        size_t list_max = 0;
-        for (int k = 0; k < k2; k++) list_max = std::max(list_max, (size_t)imgs[k].ns * nn);
-        hipLaunchKernelGGL(k_epic_assemble, dim3(blocks(list_max, 256), k2), dim3(256), 0, st, d_imgs, w, nn);
-        mark(9);
-        for (int k = 0; k < k2; k++) {
+        for (int k = 0; k < done; k++) {
             const int i = first + k;
-            SFA_HIP(ctx, hipMemcpyAsync(labels[i], imgs[k].lab, npix * 4, hipMemcpyDeviceToHost, st));
-            SFA_HIP(ctx, hipMemcpyAsync(nn_index[i], imgs[k].out_index, (size_t)ns[i] * nn * 4, hipMemcpyDeviceToHost, st));
-            SFA_HIP(ctx, hipMemcpyAsync(nn_dist[i], imgs[k].out_dist, (size_t)ns[i] * nn * 4, hipMemcpyDeviceToHost, st));
-            SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
+            SFA_HIP(ctx, hipMemcpyAsync(labels[i], io[k].lab, npix * 4, hipMemcpyDeviceToHost, st));
+            SFA_HIP(ctx, hipMemcpyAsync(nn_index[i], io[k].index, (size_t)ns[i] * nn * 4, hipMemcpyDeviceToHost, st));
+            SFA_HIP(ctx, hipMemcpyAsync(nn_dist[i], io[k].dist, (size_t)ns[i] * nn * 4, hipMemcpyDeviceToHost, st));
         }
         SFA_TRY(sfa_ctx_sync(ctx));
-        spent(2, 6); spent(3, 7); spent(4, 8);
-        for (int k = 0; k < k2; k++)
-            if (cnt[4 * k + 3]) return set_error(ctx, SFA_ERR_HIP, "%s: image %d: the search's heap met its capacity of %d entries", fn, first + k, imgs[k].heap_cap);
-        first += k2;
+        first += done;
         alone = false;
     }
     return SFA_OK;

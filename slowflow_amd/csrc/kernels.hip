@@ -2585,4 +2585,19 @@ void launch_normalize_apply(sfa_ctx *c, const Geo &g, float *frames3, const doub
     hipLaunchKernelGGL(k_norm_apply, grid, block2d(), 0, c->stream, frames3, g, avg[0], avg[1], avg[2], stdv[0], stdv[1], stdv[2]);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// EpicFlow's kernel weights (host/epic.cpp: kernel(), epic.cpp:196-198) for the chain of epic_batch.hip: w = (float)((double)expf(-coef * d) + 1e-08) over the
+// whole ns x nn list of every image, padding entries included -- the host's `expf(..) + 1e-08` forms the sum in double.  The kernel lives here, beside
+// k_dpsis_tiled, because expf_glibc and its table do: one restatement of glibc's expf, in the file tests/test_oracle_pin.py::test_expf_restatement reads
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_epic_weights(const EpicFilterImg *imgs, float coef) {
+    const EpicFilterImg im = imgs[blockIdx.y];
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= (size_t)im.count * im.nn) return;
+    im.dist[k] = (float)((double)expf_glibc(-coef * im.dist[k]) + 1e-08);
+}
+void epic_weights_device(sfa_ctx *ctx, int m, size_t list_max, float coef, const EpicFilterImg *d_imgs) {
+    if (list_max > 0) hipLaunchKernelGGL(k_epic_weights, dim3((unsigned)((list_max + 255) / 256), m), dim3(256), 0, ctx->stream, d_imgs, coef);
+}
+
 }  // namespace sfa

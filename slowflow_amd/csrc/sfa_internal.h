@@ -98,6 +98,7 @@ struct sfa_ctx {
     size_t q_tmp_bytes = 0;
     float epic_ms[5] = {};        // sfa_epic_nearest_seeds_batch (epic_nn.hip): the last call's kernel time by group (sfa_epic_nn_stage_ms)
     float epic_fit_ms[2] = {};    // sfa_epic_interpolate_batch (epic_fit.hip): the last call's fit and apply kernel time (sfa_epic_fit_stage_ms)
+    float epic_batch_ms[8] = {};  // sfa_epic_batch (epic_batch.hip): the last call's kernel time by stage (sfa_epic_batch_stage_ms)
     hipEvent_t t0 = nullptr, t1 = nullptr;
     hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // sfa_ctx_wait_stream / sfa_ctx_signal_stream: recorded on the caller's / the context's stream
     // the reference's per-iteration "avg change" lines (variational_mt.cpp:404-405, 431-432): sfa_ctx_set_verbose; costs a host round trip per iteration
@@ -267,6 +268,44 @@ int fill_matches_device(sfa_ctx *ctx, int n, int J, int w, int h, const double *
 // flow_x, flow_y: [n J][h][stride]; acc_u, acc_v: [n][J][h][w]; tracked: [n][h][w]
 int fill_trajectories_device(sfa_ctx *ctx, int n, int J, int w, int h, int stride, const float *flow_x, const float *flow_y, int scale, double *acc_u,
                              double *acc_v, int *tracked);
+
+// ---- EpicFlow's interpolation at device level (epic_nn.hip, epic_fit.hip, epic_filter.hip), in the same form: device pointers in, launches on the context's
+// stream out.  The sfa_epic_nearest_seeds_batch / sfa_epic_interpolate_batch entry points wrap them, sfa_epic_batch (epic_batch.hip) chains them ----------
+// One image of the nearest-seeds stage.  cost: w * h; seeds: 2 ns ints; out: lab w * h, index and dist ns * nn
+struct EpicNnIo { const float *cost; const int *seeds; int ns, nn; int *lab; int *index; float *dist; };
+// The stage for m images.  It keeps its two host reads of counts (border pairs; edges and the largest degree), which size what cannot be bounded beforehand,
+// and allocates that itself, within `budget` bytes: *done leading images fit and are computed (0: not even the first), the rest are untouched.  Returns
+// after waiting for the stream.  estimate (or null): raised to the largest whole need of an image seen; ms[5]: the kernel time by group, added to
+int epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const EpicNnIo *io, size_t budget, int *done, size_t *estimate, float ms[5]);
+// what epic_nn_device allocates for an image at least: everything known beforehand
+size_t epic_nn_need0(int w, int h, int ns, int nn);
+int epic_nn_check_sizes(sfa_ctx *ctx, const char *fn, int w, int h);
+// One image of the fit and its application.  seeds, vects: ns; index, weight: ns * nn; lab, fx, fy: w * h packed (apply only); model: 6 ns (LA) or 2 ns (NW)
+struct EpicFitImg {
+    const int2 *seeds; const float2 *vects; const int *index; const float *weight; const int *lab;
+    float *model, *fx, *fy; int ns, nn;
+};
+// k_epic_fit (method 0 LA, 1 NW) and k_epic_apply over the m records d_imgs (device memory); ns_max: the largest ns among them
+void epic_fit_device(sfa_ctx *ctx, int method, int m, int ns_max, const EpicFitImg *d_imgs);
+void epic_apply_device(sfa_ctx *ctx, int method, int m, int w, int h, const EpicFitImg *d_imgs);
+// One image of the steps between the stages (epic_filter.hip).  in, out: match lists (x1 y1 x2 y2) of capacity nm; count: the matches of `in`; flag: nm
+// bytes; block_off: ceil(nm / 256) ints; kept: one int (device); sal: the saliency plane at `pitch`; index, dist: the lists the weights are applied to
+struct EpicFilterImg {
+    float4 *in, *out; int count; unsigned char *flag; int *block_off; int *kept;
+    const float *sal; int2 *seeds; float2 *vects; const float *est; float *dist; int nn;
+};
+// each runs one grid over the m records d_imgs; count_max: the largest count among them
+void epic_clamp_device(sfa_ctx *ctx, int m, int count_max, int w, int h, const EpicFilterImg *d_imgs);
+void epic_saliency_flags_device(sfa_ctx *ctx, int m, int count_max, int w, int h, int pitch, float th, const EpicFilterImg *d_imgs);
+void epic_consistency_flags_device(sfa_ctx *ctx, int m, int count_max, float th2, const EpicFilterImg *d_imgs);
+void epic_compact_device(sfa_ctx *ctx, int m, int count_max, const EpicFilterImg *d_imgs);        // flag -> out, kept
+void epic_seeds_vects_device(sfa_ctx *ctx, int m, int count_max, const EpicFilterImg *d_imgs);    // of `in`
+void epic_weights_device(sfa_ctx *ctx, int m, size_t list_max, float coef, const EpicFilterImg *d_imgs);    // (kernels.hip: beside expf_glibc)
+// image.c:729-791 for g.nb images.  planes: kEpicSaliencyPlanes planes per image at g (es = kEpicSaliencyPlanes * pl), of which the first three hold the
+// Lab image and are overwritten; the result is plane kEpicSaliencyOut of every image
+struct Geo;
+constexpr int kEpicSaliencyPlanes = 15, kEpicSaliencyOut = 9;
+void epic_saliency_device(sfa_ctx *ctx, const Geo &g, float *planes, float sigma_image, float sigma_matrix);
 
 // ---------------------------------------------------------------------------------------------------
 // kernel launchers (kernels.hip).  All planes are device pointers of batch element 0; element b lives

@@ -528,23 +528,20 @@ bool interpolate_batch(sfa_ctx *ctx, const std::vector<int> &which, epic_edges *
 }
 }  // namespace
 
-void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flowy, const color_image_t *const *im, const epic_matches *const *input,
-                epic_edges *const *edges, const epic_params_t *params, int *rc, size_t workspace_bytes) {
+// epic_batch stage by stage over the images `todo` (rc[i] == 0, euc already added to edges[i]): the two graph searches and the fit with its application
+// each as one library call per group, everything between them on the host.  The path of an image sfa_epic_batch flags, and of what it does not take
+static void epic_batch_staged(sfa_ctx *ctx, int n, const std::vector<int> &todo, image_t *const *flowx, image_t *const *flowy, const color_image_t *const *im,
+                              const epic_matches *const *input, epic_edges *const *edges, const epic_params_t *params, int *rc, size_t workspace_bytes) {
     std::vector<BatchItem> it((size_t)std::max(n, 0));
     std::vector<int> live;                                                   // images still on their way: rc[i] == 0
-    for (int i = 0; i < n; i++) {                                            // epic.cpp:15-28, :155-163, :59-74
-        rc[i] = 0;
+    for (int i : todo) {                                                     // epic.cpp:15-28, :59-74
         const int w = im[i]->width, h = im[i]->height;
-        if (edges[i]->width != w || edges[i]->height != h) { rc[i] = 2; continue; }
-        if (!ctx) { rc[i] = -1; continue; }
         std::vector<float> &m = it[i].m;
         m = input[i]->m;
         for (size_t k = 0; k + 3 < m.size(); k += 4) {
             m[k] = std::max(0.f, std::min(m[k], (float)(w - 1)));         m[k + 1] = std::max(0.f, std::min(m[k + 1], (float)(h - 1)));
             m[k + 2] = std::max(0.f, std::min(m[k + 2], (float)(w - 1))); m[k + 3] = std::max(0.f, std::min(m[k + 3], (float)(h - 1)));
         }
-        if (params->verbose) printf("%d input matches\n", (int)(m.size() / 4));
-        if (params->euc) for (float &c : edges[i]->cost) c += params->euc;
         if (params->saliency_th) {
             image_t *s = saliency(ctx, im[i], 0.8f, 1.0f);
             if (!s) { rc[i] = -1; continue; }
@@ -608,4 +605,75 @@ void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flow
     }
     if (!fit.empty() && !interpolate_batch(ctx, fit, edges, it, la, flowx, flowy, workspace_bytes))
         for (int i : fit) rc[i] = -1;
+}
+
+void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flowy, const color_image_t *const *im, const epic_matches *const *input,
+                epic_edges *const *edges, const epic_params_t *params, int *rc, size_t workspace_bytes) {
+    std::vector<int> live;                                                   // images still on their way: rc[i] == 0
+    for (int i = 0; i < n; i++) {                                            // epic.cpp:155-163
+        rc[i] = 0;
+        const int w = im[i]->width, h = im[i]->height;
+        if (edges[i]->width != w || edges[i]->height != h) { rc[i] = 2; continue; }
+        if (!ctx) { rc[i] = -1; continue; }
+        if (params->verbose) printf("%d input matches\n", input[i]->count());
+        if (params->euc) for (float &c : edges[i]->cost) c += params->euc;
+        live.push_back(i);
+    }
+    const bool la = !strcmp(params->method, "LA");
+    std::vector<int> staged;                                                 // what the library's chain does not take, and what it flags
+    std::vector<char> taken((size_t)std::max(n, 0), 0);
+    std::vector<std::vector<int>> counts((size_t)std::max(n, 0), std::vector<int>(3, -1));     // of the images the chain computed
+    for (size_t a = 0; a < live.size(); a++) {
+        const int i0 = live[a];
+        if (taken[i0]) continue;
+        const int w = im[i0]->width, h = im[i0]->height;
+        std::vector<int> group;                                              // images of one size (and one row stride of each kind) share a call
+        for (size_t b = a; b < live.size(); b++) {
+            const int i = live[b];
+            if (taken[i] || im[i]->width != w || im[i]->height != h || im[i]->stride != im[i0]->stride || flowx[i]->stride != flowx[i0]->stride) continue;
+            taken[i] = 1;
+            // an unknown method is reported by the staged path after its filters, as epic() does; it also keeps epic()'s answers for an image too small
+            // for the saliency's filters, for planes the chain cannot address as one color_image_t, and for two flow images of different strides
+            const bool planes = im[i]->c2 == im[i]->c1 + (size_t)im[i]->stride * h && im[i]->c3 == im[i]->c2 + (size_t)im[i]->stride * h;
+            if ((!la && strcmp(params->method, "NW")) || (params->saliency_th && (w <= 8 || h <= 8 || !planes)) || flowy[i]->stride != flowx[i]->stride) staged.push_back(i);
+            else group.push_back(i);
+        }
+        const size_t g = group.size();
+        if (!g) continue;
+        sfa_epic_params p;
+        p.method = la ? 0 : 1; p.saliency_th = params->saliency_th; p.pref_nn = params->pref_nn; p.pref_th = params->pref_th; p.nn = params->nn;
+        p.coef_kernel = params->coef_kernel; p.euc = params->euc;
+        std::vector<const float *> lab(g), cost(g), matches(g);
+        std::vector<float *> fx(g), fy(g);
+        std::vector<int> nm(g), rcs(g, 0), status(g, 0);
+        std::vector<int> cnt(3 * g, 0);
+        for (size_t b = 0; b < g; b++) {
+            const int i = group[b];
+            lab[b] = im[i]->c1; cost[b] = edges[i]->cost.data(); matches[b] = input[i]->m.data(); nm[b] = input[i]->count();
+            fx[b] = flowx[i]->data; fy[b] = flowy[i]->data;
+        }
+        if (sfa_epic_batch(ctx, (int)g, w, h, &p, lab.data(), im[i0]->stride, cost.data(), matches.data(), nm.data(), fx.data(), fy.data(), flowx[i0]->stride, rcs.data(),
+                           reinterpret_cast<int(*)[3]>(cnt.data()), nullptr, workspace_bytes, status.data()) != SFA_OK) {
+            for (int i : group) rc[i] = -1;
+            continue;
+        }
+        for (size_t b = 0; b < g; b++) {
+            if (status[b]) { staged.push_back(group[b]); continue; }
+            rc[group[b]] = rcs[b];
+            counts[group[b]].assign(cnt.begin() + 3 * b, cnt.begin() + 3 * b + 3);
+        }
+    }
+    // what epic() says on the way, from the counts, stage by stage as the staged path says it
+    if (params->saliency_th && params->verbose)
+        for (int i : live) if (counts[i][0] >= 0) printf("Saliency filtering, remaining %d matches\n", counts[i][1]);
+    if (params->pref_nn) {
+        for (int i : live) if (counts[i][1] > 0 && std::min(params->pref_nn + 1, counts[i][1]) != params->pref_nn + 1) fprintf(stderr, "Warning: not enough matches for prefiltering\n");
+        if (params->verbose)
+            for (int i : live) if (counts[i][1] > 0) printf("Consistenct filter, remaining %d matches\n", counts[i][2]);
+    }
+    for (int i : live) if (counts[i][2] > 0 && std::min(params->nn, counts[i][2]) < params->nn) fprintf(stderr, "Warning: not enough matches for interpolating\n");
+    if (!staged.empty()) {
+        std::sort(staged.begin(), staged.end());
+        epic_batch_staged(ctx, n, staged, flowx, flowy, im, input, edges, params, rc, workspace_bytes);
+    }
 }

@@ -49,12 +49,13 @@ image_t *saliency(sfa_ctx *ctx, const color_image_t *im, float sigma_image, floa
  * 0 on success, < 0 on a GPU error (sfa_last_error(ctx)), > 0: no usable match. */
 int epic(sfa_ctx *ctx, image_t *flowx, image_t *flowy, const color_image_t *im_lab, const epic_matches &matches, epic_edges &edges, const epic_params_t *params);
 
-/* epic() for n images at once, stage by stage over the batch: the same steps and the same results, bit for bit, with the two epic_nearest_seeds calls of
- * every image replaced by two sfa_epic_nearest_seeds_batch calls on the GPU of ctx, and the final model fit and dense application by one
- * sfa_epic_interpolate_batch call (images of one size and one neighbour count share a call; an image the library reports as too large for its workspace
- * goes through the host code of that stage).  The kernel weights (expf), the consistency filter's estimate and the compaction of the matches stay on the
- * host.  rc[i]: what epic() returns for image i; an image left without matches
- * drops out with 1 before the second call.  workspace_bytes: the library's device-memory budget per sub-batch (0: its default).  Needs a context (rc -1 without one). */
+/* epic() for n images at once: the same steps and the same results, bit for bit.  After the checks epic() makes first (rc 2 for an edge map of another
+ * size) and the in-place addition of euc to edges[i], the images of one size go through one sfa_epic_batch call on the GPU of ctx: clamp, saliency filter,
+ * consistency filter, both graph searches, kernel weights, fit and dense application as one chain in device memory.  The warnings and verbose lines of
+ * epic() are written from the call's counts.  An image the library reports as too large for its workspace, and what the call does not take (an unknown
+ * method, an image too small for the saliency's filters, flow images of two strides), goes stage by stage instead: two sfa_epic_nearest_seeds_batch calls
+ * and one sfa_epic_interpolate_batch call, everything between them on the host.  rc[i]: what epic() returns for image i; an image left without matches
+ * drops out with 1.  workspace_bytes: the library's device-memory budget per sub-batch (0: its default).  Needs a context (rc -1 without one). */
 void epic_batch(sfa_ctx *ctx, int n, image_t *const *flowx, image_t *const *flowy, const color_image_t *const *im_lab, const epic_matches *const *matches,
                 epic_edges *const *edges, const epic_params_t *params, int *rc, size_t workspace_bytes = 0);
 
