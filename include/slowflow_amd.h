@@ -117,9 +117,11 @@ int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *c
  * seed on the same pixel wins; labels[i] (out) = w * h ints, the closest seed of every pixel, -1 where none reaches; nn_index[i], nn_dist[i] (out) =
  * ns[i] * nn entries, seed q's neighbours in the order the reference's search finds them and their raw geodesic distances (no kernel applied), -1 /
  * 0x7F7F7F7F where fewer than nn exist.  Every output equals the host function's bit for bit, whatever n and the image's position; costs are non-negative.
- * Host pointers; the call waits for its results.  The batch runs in sub-batches whose device memory (planes, the border table, ns * ns floats and the
- * search's heaps, sized from the counted graph: 1 + min((nn - 1) * largest degree, 2 * edges) entries per seed) stays within workspace_bytes (0: half of the
- * GPU's free memory); status[i] = 0: computed, 1: image i does not fit the budget even alone -- its outputs are untouched and the caller computes it on the host.
+ * Host pointers; the call waits for its results.  The batch runs in sub-batches whose device memory (planes, the border table, the search's visited
+ * sets and heaps, the heaps sized from the counted graph: 1 + min((nn - 1) * largest degree, 2 * edges) entries per seed) stays within workspace_bytes (0:
+ * half of the GPU's free memory); status[i] = 0: computed, 1: image i does not fit the budget even alone -- its outputs are untouched and the caller
+ * computes it on the host.  In the default mode the visited sets of an image are ns * ns floats, held for all its seeds at once; in the compact mode
+ * (sfa_ctx_set_epic_search) an image is flagged only if its planes, table, rows and the search of one 64-seed workgroup exceed the budget.
  * Refused with SFA_ERR_ARG, the argument named and nothing launched: n < 1, w or h < 1, nn < 1, an ns[i] < 1, a null pointer, a seed outside the image,
  * w * h > 2^29 or ns[i] * nn > 2^31 - 1 (32-bit indices), min(w, h) > 4000 (two diagonals of the sweep live in LDS). */
 int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float *const *cost, const int *const *seeds_xy, const int *ns, int nn,
@@ -128,6 +130,22 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
  * ms[0] initial state and seeds, ms[1] the sweeps, ms[2] the region graph (border count, table, rows), ms[3] the graph search, ms[4] the lists.
  * Copies, allocations and the waits between the stages are not in it (tools/bench_epic_nn.py). */
 int sfa_epic_nn_stage_ms(sfa_ctx *ctx, float ms[5]);
+/* How the graph search of the nearest-seeds stage holds its state, per context; it applies to sfa_epic_nearest_seeds_batch and sfa_epic_batch and so to
+ * everything above them, and never changes a bit of any output.
+ *   SFA_EPIC_SEARCH_DENSE (the default)  every seed of an image owns a row of ns floats, and an image is computed only if all its rows and heaps fit the
+ *     budget at once.
+ *   SFA_EPIC_SEARCH_COMPACT  the seeds of an image are searched in slices -- runs of whole 64-seed workgroups, in (image, seed) order -- that share one
+ *     workspace as large as the largest slice, and an image takes the smaller of two forms of visited set: the dense row, 4 * ns bytes per seed, or an
+ *     open-addressing map of node -> distance, 8 bytes per slot, its slots the smallest power of two >= twice the heap's bound (dense on a tie).  An image
+ *     whose whole search fits is one slice.  ms[3] of sfa_epic_nn_stage_ms sums the slices, the clearing of their workspace included.
+ * Any other mode: SFA_ERR_ARG, `mode` named, nothing changed. */
+#define SFA_EPIC_SEARCH_DENSE 0
+#define SFA_EPIC_SEARCH_COMPACT 1
+int sfa_ctx_set_epic_search(sfa_ctx *ctx, int mode);
+/* The graph search of the context's last nearest-seeds stage (the last sfa_epic_nearest_seeds_batch, or the interpolation's search of the last
+ * sfa_epic_batch), summed over its sub-batches: info[0] slices launched (the default mode: one per image), info[1] images searched with the dense set,
+ * info[2] images searched with the sparse set, info[3] the largest search workspace in bytes (visited sets and heaps). */
+int sfa_epic_nn_search_info(sfa_ctx *ctx, long long info[4]);
 /* EpicFlow's per-seed model fit and its dense application (epic_aux.cpp:386-497; host/epic.cpp: epic_fit_localaffine, epic_fit_nadarayawatson and the apply
  * loops of epic()) for n images of one size w x h in one call, on the GPU (csrc/epic_fit.hip).  method 0: locally-weighted affine (LA), 1: Nadaraya-Watson
  * (NW).  Image i: seeds_xy[i] = 2 * ns[i] ints (x, y); vects[i] = 2 * ns[i] floats; nn_index[i], nn_weight[i] = ns[i] * nn entries, the lists of
@@ -172,6 +190,7 @@ typedef struct sfa_epic_params {
  * (or NULL): per image the matches that came in, that passed the saliency filter, that passed the consistency filter (a filter that is off passes all).
  * kept_matches (or NULL): kept_matches[i] receives the 4 * counts[i][2] floats of the survivors in list order (room for 4 * nm[i]).
  * Sub-batches, workspace_bytes and status as for sfa_epic_nearest_seeds_batch: nothing allocated exceeds workspace_bytes (0: half of the GPU's free memory);
+ * both searches run in the context's mode (sfa_ctx_set_epic_search: the ns * ns floats per image are the default mode's only);
  * status[i] = 1: image i does not fit even alone -- rc[i], counts[i] and its outputs are untouched and the caller computes it on the host.  No result depends
  * on the sub-batch cut or on an image's place in the batch.
  * Refused with SFA_ERR_ARG, the argument named and nothing launched: n < 1, w or h < 1, nn < 1, pref_nn < 0, a method other than 0 or 1, flow_stride < w,

@@ -180,7 +180,7 @@ def track_job_bytes(params):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_epic_batch", "sfa_epic_saliency_batch", "sfa_epic_batch_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "sfa_consistent_regions", "sfa_fill_samples", "sfa_fill_matches", "sfa_fill_trajectories", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_ctx_set_epic_search", "sfa_epic_nn_search_info", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_epic_batch", "sfa_epic_saliency_batch", "sfa_epic_batch_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "sfa_consistent_regions", "sfa_fill_samples", "sfa_fill_matches", "sfa_fill_trajectories", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_grid_cut_batch", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_pyramid_down", "sfa_resize_flow", "sfa_job_download_level_frame",
@@ -561,6 +561,23 @@ class Context:
         ms = (C.c_float * 5)()
         self._ck(lib().sfa_epic_nn_stage_ms(self.h, ms), "sfa_epic_nn_stage_ms")
         return dict(zip(("seeds", "sweeps", "graph", "search", "lists"), [float(v) for v in ms]))
+
+    def set_epic_search(self, mode):
+        """how the nearest-seeds stage's graph search holds its state (sfa_ctx_set_epic_search): "dense" (the default: ns * ns floats per image, all seeds at
+        once) or "compact" (slices of 64-seed workgroups in one shared workspace, dense rows or sparse maps per image).  Same bits either way.  An int is
+        passed through as the C constant."""
+        if isinstance(mode, str):
+            if mode not in ("dense", "compact"):
+                raise SlowflowError("set_epic_search: mode = %r (\"dense\" or \"compact\")" % (mode,))
+            mode = ("dense", "compact").index(mode)
+        self._ck(lib().sfa_ctx_set_epic_search(self.h, int(mode)), "sfa_ctx_set_epic_search")
+
+    def epic_nn_search_info(self):
+        """the graph search of the last nearest-seeds stage (sfa_epic_nn_search_info): slices launched, images searched dense, images searched sparse, the
+        largest search workspace in bytes"""
+        info = (C.c_longlong * 4)()
+        self._ck(lib().sfa_epic_nn_search_info(self.h, info), "sfa_epic_nn_search_info")
+        return dict(zip(("slices", "dense", "sparse", "workspace_bytes"), [int(v) for v in info]))
 
     def epic_interpolate(self, labels, seeds, vects, index, weight, method="LA", stride=None, workspace_bytes=0, with_status=False):
         """EpicFlow's model fit and dense application of a batch (sfa_epic_interpolate_batch).  labels: n int32 (h, w) label maps of one size, or None for

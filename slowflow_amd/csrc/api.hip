@@ -22,12 +22,13 @@ static const char *const kSwitchNames[Switches::N] = {
     "SFA_SOR_CHAIN", "SFA_SOR_BAND", "SFA_SOR_F", "SFA_SOR_CH", "SFA_SOR_LEAD", "SFA_CHAIN_LDS", "SFA_RB_TILE", "SFA_WARP_ALLJ", "SFA_NO_WARP_SMOOTH",
     "SFA_ASSEMBLE_GENERIC", "SFA_EXACT_DIV", "SFA_ASM_XCD", "SFA_NO_DIRECT_OPERANDS", "SFA_NO_UV_ALIAS", "SFA_DEBUG_ACTIVE", "SFA_UNFUSED", "SFA_SHARE_SOR",
     "SFA_PYRAMID_UNFUSED", "SFA_CUT_DISCHARGE", "SFA_CUT_INNER", "SFA_CUT_SUPER", "SFA_CUT_TAIL_INNER", "SFA_CUT_PER", "SFA_CUT_TAIL_PER", "SFA_CUT_TAIL_SUPER",
-    "SFA_CUT_DEBUG", "SFA_CUT_NO_TAIL", "SFA_CUT_TAIL", "SFA_NO_EXACT_BREAK", "SFA_PAIR_UNFUSED", "SFA_EPIC_FIT_PLAIN"};
+    "SFA_CUT_DEBUG", "SFA_CUT_NO_TAIL", "SFA_CUT_TAIL", "SFA_NO_EXACT_BREAK", "SFA_PAIR_UNFUSED", "SFA_EPIC_FIT_PLAIN", "SFA_EPIC_NN_SET", "SFA_EPIC_NN_SLICE"};
 static int set_switch(const char *name, const char *value) {
     for (int i = 0; i < Switches::N; i++)
         if (!strcmp(name, kSwitchNames[i])) {
             g_switches.given[i] = value != nullptr;
             g_switches.value[i] = value ? atoi(value) : 0;
+            if (i == Switches::EPIC_NN_SET && value) g_switches.value[i] = !strcmp(value, "sparse") ? 1 : !strcmp(value, "dense") ? 0 : -1;      // (else: no form forced)
             return SFA_OK;
         }
     return SFA_ERR_ARG;
@@ -259,6 +260,12 @@ int sfa_debug_set(const char *name, const char *value) {
     if (set_switch(name, value) != SFA_OK) return set_error(nullptr, SFA_ERR_ARG, "sfa_debug_set: unknown switch '%s'", name);
     return SFA_OK;
 #endif
+}
+int sfa_ctx_set_epic_search(sfa_ctx *ctx, int mode) {
+    if (!ctx) return set_error(nullptr, SFA_ERR_ARG, "%s: ctx is null", __func__);
+    if (mode != SFA_EPIC_SEARCH_DENSE && mode != SFA_EPIC_SEARCH_COMPACT) REFUSE("%s: mode = %d (SFA_EPIC_SEARCH_DENSE = 0 or SFA_EPIC_SEARCH_COMPACT = 1)", __func__, mode);
+    ctx->epic_search = mode;
+    return SFA_OK;
 }
 int sfa_ctx_set_verbose(sfa_ctx *c, int on) {
     if (!c) return SFA_ERR_ARG;

@@ -78,6 +78,7 @@ struct Call {
     const float *const *lab; int lab_stride; const float *const *cost; const float *const *matches; const int *nm;
     float *const *flow_x, *const *flow_y; int flow_stride; int *rc; int (*counts)[3]; float *const *kept_matches;
     size_t budget; size_t estimate;                                  // of the nearest-seeds stage's own part, per image
+    long long info[4];                                               // sfa_epic_nn_search_info of the sub-batch's last search
 };
 
 // The chain for the images `which` (all with matches).  *fit: how many of them, from the first, the sub-batch can hold (== which.size(): done and written)
@@ -88,6 +89,7 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
     hipStream_t st = ctx->stream;
     const int m = (int)which.size();
     *fit = 0;
+    for (long long &v : c.info) v = 0;
     size_t bytes = 0;
     for (int i : which) bytes += persistent_bytes(z, p, c.nm[i]);
     DevMem mem, sal_mem;
@@ -147,7 +149,7 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
     auto still_live = [&](const std::vector<int> &live) { std::vector<int> r; for (int k : live) if (items[k].count > 0) r.push_back(k); return r; };
     // nearest seeds, kernel weights and the fit of `method` for the images `live`, each with min(nn_cap, count) neighbours
     std::vector<EpicFitImg> fitrec;
-    auto search_and_fit = [&](const std::vector<int> &live, int nn_cap, int method, int slot_nn, int slot_w, int slot_fit, int *done) {
+    auto search_and_fit = [&](const std::vector<int> &live, int nn_cap, int method, int slot_nn, int slot_w, int slot_fit, int *done, long long *info) {
         const int L = (int)live.size(), cm = count_max_of(live);
         SFA_HIP(ctx, put_filter(live, nullptr, nn_cap));
         timer.begin(1);
@@ -161,7 +163,7 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
             list_max = std::max(list_max, (size_t)io[k].ns * io[k].nn);
         }
         float nn_ms[5] = {};
-        SFA_TRY(epic_nn_device(ctx, c.fn, L, z.w, z.h, io.data(), c.budget - bytes, done, &c.estimate, nn_ms));
+        SFA_TRY(epic_nn_device(ctx, c.fn, L, z.w, z.h, io.data(), c.budget - bytes, done, &c.estimate, nn_ms, info));
         for (float v : nn_ms) ms[slot_nn] += v;
         timer.collect(ms);
         if (*done < L) return (int)SFA_OK;
@@ -216,7 +218,7 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
         return (int)SFA_OK;
     };
     if (p.pref_nn && !live.empty()) {
-        SFA_TRY(search_and_fit(live, p.pref_nn + 1, 1, 2, 3, 3, &done));
+        SFA_TRY(search_and_fit(live, p.pref_nn + 1, 1, 2, 3, 3, &done, nullptr));
         if (done < (int)live.size()) return partial(done);
         timer.begin(1);
         epic_consistency_flags_device(ctx, (int)live.size(), count_max_of(live), p.pref_th * p.pref_th, d_filter);
@@ -227,7 +229,7 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
     }
     // ---- interpolation ---------------------------------------------------------------------------------------------------------------------------------------
     if (!live.empty()) {
-        SFA_TRY(search_and_fit(live, p.nn, p.method, 4, 5, 6, &done));
+        SFA_TRY(search_and_fit(live, p.nn, p.method, 4, 5, 6, &done, c.info));
         if (done < (int)live.size()) return partial(done);
         timer.begin(7);
         epic_apply_device(ctx, p.method, (int)live.size(), z.w, z.h, d_fit);
@@ -295,10 +297,11 @@ int sfa_epic_batch(sfa_ctx *ctx, int n, int w, int h, const sfa_epic_params *p, 
     }
     for (float &v : ctx->epic_batch_ms) v = 0.f;
     Call c{ctx, fn, Sizes{w, h, dev_pitch(w), (size_t)w * h, (size_t)dev_pitch(w) * h, saliency}, p, lab, lab_stride, cost, matches, nm,
-           flow_x, flow_y, flow_stride, rc, counts, kept_matches, budget, 0};
+           flow_x, flow_y, flow_stride, rc, counts, kept_matches, budget, 0, {}};
+    for (long long &v : ctx->epic_info) v = 0;
     // what an image needs at least: what it owns for the whole chain, and beside that the larger of the saliency's planes and the search's known part
     auto need0 = [&](int i) {
-        return persistent_bytes(c.z, *p, nm[i]) + std::max(saliency_bytes(c.z), std::max(epic_nn_need0(w, h, nm[i], nn_max_of(*p, nm[i])), c.estimate));
+        return persistent_bytes(c.z, *p, nm[i]) + std::max(saliency_bytes(c.z), std::max(epic_nn_need0(ctx, w, h, nm[i], nn_max_of(*p, nm[i])), c.estimate));
     };
     for (int i = 0; i < n; i++) status[i] = 0;
     int first = 0, cap = kMaxSubBatch;                               // cap: what the sub-batch before this attempt showed to fit
@@ -318,7 +321,7 @@ int sfa_epic_batch(sfa_ctx *ctx, int n, int w, int h, const sfa_epic_params *p, 
             which.push_back(next);
         }
         if (which.empty()) {
-            if (persistent_bytes(c.z, *p, nm[first]) + std::max(saliency_bytes(c.z), epic_nn_need0(w, h, nm[first], nn_max_of(*p, nm[first]))) > budget) {
+            if (persistent_bytes(c.z, *p, nm[first]) + std::max(saliency_bytes(c.z), epic_nn_need0(ctx, w, h, nm[first], nn_max_of(*p, nm[first]))) > budget) {
                 status[first++] = 1;                                 // not even alone: flagged, its outputs untouched
                 cap = kMaxSubBatch;
                 continue;
@@ -327,7 +330,12 @@ int sfa_epic_batch(sfa_ctx *ctx, int n, int w, int h, const sfa_epic_params *p, 
         }
         int fit = 0;
         SFA_TRY(run_sub_batch(c, which, &fit));
-        if (fit == (int)which.size()) { first = which.back() + 1; cap = kMaxSubBatch; continue; }
+        if (fit == (int)which.size()) {                              // (a sub-batch that is run again counts once)
+            for (int k = 0; k < 3; k++) ctx->epic_info[k] += c.info[k];
+            ctx->epic_info[3] = std::max(ctx->epic_info[3], c.info[3]);
+            first = which.back() + 1; cap = kMaxSubBatch;
+            continue;
+        }
         if (which.size() == 1) { status[first++] = 1; cap = kMaxSubBatch; continue; }
         cap = std::max(fit, 1);                                      // again, with the images that fit
     }

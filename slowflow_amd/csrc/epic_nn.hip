@@ -11,14 +11,18 @@
 //                        order the atomics ran in), the largest degree
 //   k_epic_dijkstra      one thread per (image, seed): `done` a dense row of ns floats, the heap (epic_heap.h: libstdc++'s push_heap / pop_heap) in global memory,
 //                        its capacity the bound 1 + min((nn - 1) maxdeg, 2 E): every push follows the expansion of one directed edge, at most nn - 1 nodes expand
+//   k_epic_search        the compact mode's search (sfa_ctx_set_epic_search): the same walk for one slice of an image's seeds, over a dense row or a sparse
+//                        open-addressing map per seed; the slices of a sub-batch run one after the other in one workspace (epic_nn_plan.h)
 //   k_epic_assemble      query q takes the list of the seed whose region its pixel lies in, plus its own distance
 // epic_nn_device (sfa_internal.h) is the stage on buffers already in device memory, with the neighbour count per image; the entry point wraps it (allocate, upload,
-// call, download, wait) and runs the batch in sub-batches that fit a workspace budget; an image that does not fit alone is flagged, never truncated.
+// call, download, wait) and runs the batch in sub-batches that fit a workspace budget; an image that does not fit alone is flagged, never truncated.  In the
+// default mode an image fits when its ns * ns floats and all its heaps do; in the compact mode when one 64-seed workgroup's search does.
 #include <algorithm>
 #include <climits>
 #include <cstring>
 
 #include "epic_heap.h"
+#include "epic_nn_plan.h"
 #include "sfa_device.h"
 #include "sfa_internal.h"
 
@@ -288,6 +292,76 @@ __global__ void __launch_bounds__(64) k_epic_dijkstra(const EpicImg *imgs) {    
     }
 }
 
+// ---- the compact search (sfa_ctx_set_epic_search, epic_nn_plan.h): k_epic_dijkstra's walk, statement for statement, for the seeds first .. first + count - 1
+// of one image, over a visited set of either form.  A set answers find(node) with the place of the node's distance and the distance held there, 0x7F7F7F7F
+// for a node never written, so every comparison -- and with them the heap's order and every output bit -- is the default kernel's.
+struct DenseSet {                                                    // the default mode's row, of this slice
+    float *row;
+    struct Ref { float *p; float value; };
+    __device__ DenseSet(void *ws, int local, int, int ns, int) : row(static_cast<float *>(ws) + (size_t)local * ns) {}
+    __device__ Ref find(int node) const { return Ref{row + node, row[node]}; }
+    __device__ bool store(const Ref &r, int, float d) const { *r.p = d; return true; }
+};
+#ifndef SFA_EPIC_NN_INTERLEAVED
+#define SFA_EPIC_NN_INTERLEAVED 0
+#endif
+// node -> distance bits: the key in a slot's upper half, all ones = empty; a multiplicative hash and linear probing.  A thread's slots lie together, so a
+// probe sequence stays in one or two cache lines.  SFA_EPIC_NN_INTERLEAVED (what-if): slot k of a thread lies `count` slots after its slot k - 1, like
+// StridedHeap's entries; DESIGN.md 8 holds both measurements
+struct SparseSet {
+    unsigned long long *slot; size_t stride; unsigned mask; int shift;           // 1 <= log_slots <= 31 (epic_nn_plan.h: searchable)
+    struct Ref { unsigned long long *p; float value; };
+    __device__ SparseSet(void *ws, int local, int count, int, int log_slots)
+        : slot(static_cast<unsigned long long *>(ws) + (SFA_EPIC_NN_INTERLEAVED ? (size_t)local : (size_t)local << log_slots)),
+          stride(SFA_EPIC_NN_INTERLEAVED ? (size_t)count : 1), mask((1u << log_slots) - 1), shift(32 - log_slots) {}
+    __device__ Ref find(int node) const {
+        unsigned h = ((unsigned)node * 0x9E3779B1u) >> shift;
+        for (unsigned probe = 0; probe <= mask; probe++, h = (h + 1) & mask) {  // bounded by the capacity
+            unsigned long long *p = slot + h * stride;
+            const unsigned long long s = *p;
+            const unsigned key = (unsigned)(s >> 32);
+            if (key == (unsigned)node) return Ref{p, __uint_as_float((unsigned)s)};
+            if (key == 0xFFFFFFFFu) return Ref{p, __uint_as_float(kHugeBits)};
+        }
+        return Ref{nullptr, __uint_as_float(kHugeBits)};             // a full map without the node (the load is at most 1/2: never)
+    }
+    __device__ bool store(const Ref &r, int node, float d) const {
+        if (!r.p) return false;
+        *r.p = ((unsigned long long)(unsigned)node << 32) | __float_as_uint(d);
+        return true;
+    }
+};
+
+template <class Set>
+__global__ void __launch_bounds__(kEpicNnGroup) k_epic_search(const EpicImg *imgs, int image, int first, int count, void *ws, epic_heap_item *heaps, int log_slots) {
+    const EpicImg im = imgs[image];
+    const int nn = im.nn;
+    const int local = blockIdx.x * blockDim.x + threadIdx.x;
+    if (local >= count) return;
+    const int seed = first + local;
+    const Set done(ws, local, count, im.ns, log_slots);              // cleared by the host: 0x7F bytes (dense), 0xFF bytes (sparse)
+    StridedHeap heap{heaps + local, (size_t)count};
+    int size = 0, n = 0;
+    epic_heap_push(heap, size, epic_heap_item{seed, 0.f});
+    if (!done.store(done.find(seed), seed, 0)) { atomicAdd(&im.cnt[3], 1u); return; }
+    while (size > 0) {
+        const epic_heap_item cur = epic_heap_pop(heap, size);
+        if (cur.dis > done.find(cur.node).value) continue;
+        im.nnf[(size_t)seed * nn + n] = cur.node;
+        im.dis[(size_t)seed * nn + n] = cur.dis;
+        if (++n >= nn) break;
+        for (int e = im.rowptr[cur.node]; e < im.rowptr[cur.node + 1]; e++) {
+            const int to = im.adj_n[e];
+            const float newd = cur.dis + im.adj_l[e];
+            const typename Set::Ref r = done.find(to);
+            if (newd >= r.value) continue;
+            if (size >= im.heap_cap || !r.p) { atomicAdd(&im.cnt[3], 1u); return; }      // cannot happen (the bounds of epic_nn_plan.h); reported, never written past the end
+            epic_heap_push(heap, size, epic_heap_item{to, newd});
+            done.store(r, to, newd);
+        }
+    }
+}
+
 __global__ void k_epic_assemble(const EpicImg *imgs, int tx) {                // epic_aux.cpp:366-374
     const EpicImg im = imgs[blockIdx.y];
     const int nn = im.nn;
@@ -318,7 +392,7 @@ using namespace sfa;
 // The stage on buffers already in device memory (sfa_internal.h).  What it allocates besides -- the records, dmap, the search's own lists, then the table and
 // rows, then `done` and the heaps, each sized by the counts the host reads in between -- stays within `budget`; the leading *done images that fit whole are
 // computed, and when the call returns the stream has been waited for
-int sfa::epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const EpicNnIo *io, size_t budget, int *done_out, size_t *estimate, float ms_out[5]) {
+int sfa::epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const EpicNnIo *io, size_t budget, int *done_out, size_t *estimate, float ms_out[5], long long info[4]) {
     *done_out = 0;
     const size_t npix = (size_t)w * h;
     hipStream_t st = ctx->stream;
@@ -412,6 +486,60 @@ int sfa::epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const
     for (int k = 0; k < k1; k++) SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
     SFA_TRY(sfa_ctx_sync(ctx));
     spent(2, 4);
+    // ---- stage 3, compact mode: rows, the search slice by slice in one shared workspace, the lists (epic_nn_plan.h) -----------------------------------------
+    if (ctx->epic_search == SFA_EPIC_SEARCH_COMPACT) {
+        std::vector<EpicNnGraph> graphs(k1);
+        for (int k = 0; k < k1; k++) graphs[k] = EpicNnGraph{io[k].ns, io[k].nn, cnt[4 * k + 1], cnt[4 * k + 2]};
+        const int slice_cap = sw_given(Switches::EPIC_NN_SLICE) ? std::max(kEpicNnGroup, sw_int(Switches::EPIC_NN_SLICE, 0) / kEpicNnGroup * kEpicNnGroup) : 0;
+        const EpicNnPlan plan = epic_nn_plan(graphs.data(), k1, budget - bytes1 - bytes2, sw_int(Switches::EPIC_NN_SET, -1), slice_cap);
+        for (int k = 0; k < k1 && estimate; k++)
+            if (plan.img[k].searchable) *estimate = std::max(*estimate, need1(k) + need2(k, cnt[4 * k]) + epic_nn_rows_bytes(graphs[k].E) + plan.img[k].group_bytes);
+        const int kc = plan.images;
+        if (kc == 0) return SFA_OK;
+        SFA_TRY(mem3.alloc(ctx, plan.rows + plan.workspace));
+        Bump b3{static_cast<char *>(mem3.p)};
+        for (int k = 0; k < kc; k++) {
+            EpicImg &im = imgs[k];
+            im.adj_n = b3.take<int>((size_t)2 * graphs[k].E + 1); im.adj_l = b3.take<float>((size_t)2 * graphs[k].E + 1);
+            im.heap_cap = (int)plan.img[k].heap_cap;
+        }
+        char *ws = b3.base + b3.used;                                // plan.workspace bytes, every slice's in turn
+        SFA_HIP(ctx, put_imgs(kc));
+        mark(6);
+        hipLaunchKernelGGL(k_epic_fill, dim3(slot_blocks, kc), dim3(256), 0, st, d_imgs);
+        hipLaunchKernelGGL(k_epic_sort_rows, dim3(blocks(ns_max, 64), kc), dim3(64), 0, st, d_imgs);
+        mark(7);
+        for (const EpicNnSlice &s : plan.slices) {                   // (in stream order: a slice has finished with the workspace before the next one clears it)
+            const EpicNnImage &pi = plan.img[s.image];
+            const size_t set_bytes = (size_t)s.count * pi.set_bytes;
+            epic_heap_item *heaps = reinterpret_cast<epic_heap_item *>(ws + al(set_bytes));
+            const dim3 grid(blocks(s.count, kEpicNnGroup));
+            if (pi.form == EPIC_NN_SPARSE) {
+                SFA_HIP(ctx, hipMemsetAsync(ws, 0xFF, set_bytes, st));                     // the empty key
+                hipLaunchKernelGGL(k_epic_search<SparseSet>, grid, dim3(kEpicNnGroup), 0, st, d_imgs, s.image, s.first, s.count, (void *)ws, heaps, pi.log_slots);
+            } else {
+                SFA_HIP(ctx, hipMemsetAsync(ws, 0x7F, set_bytes, st));
+                hipLaunchKernelGGL(k_epic_search<DenseSet>, grid, dim3(kEpicNnGroup), 0, st, d_imgs, s.image, s.first, s.count, (void *)ws, heaps, 0);
+            }
+        }
+        mark(8);
+        size_t list_max = 0;
+        for (int k = 0; k < kc; k++) list_max = std::max(list_max, (size_t)imgs[k].ns * imgs[k].nn);
+        hipLaunchKernelGGL(k_epic_assemble, dim3(blocks(list_max, 256), kc), dim3(256), 0, st, d_imgs, w);
+        mark(9);
+        for (int k = 0; k < kc; k++) SFA_HIP(ctx, hipMemcpyAsync(&cnt[4 * k], cnts[k], 16, hipMemcpyDeviceToHost, st));
+        SFA_TRY(sfa_ctx_sync(ctx));
+        spent(2, 6); spent(3, 7); spent(4, 8);
+        for (int k = 0; k < kc; k++)
+            if (cnt[4 * k + 3]) return set_error(ctx, SFA_ERR_HIP, "%s: image %d of the sub-batch: the search's heap met its capacity of %d entries, or its visited set its 2^%d slots", fn, k, imgs[k].heap_cap, plan.img[k].log_slots);
+        if (info) {
+            info[0] += (long long)plan.slices.size();
+            for (int k = 0; k < kc; k++) info[plan.img[k].form == EPIC_NN_SPARSE ? 2 : 1]++;
+            info[3] = std::max(info[3], (long long)plan.workspace);
+        }
+        *done_out = kc;
+        return SFA_OK;
+    }
     // ---- stage 3: rows, the search, the lists of the images that fit whole ------------------------------------------------------------------------------
     int k2 = 0;
     size_t bytes3 = 0;
@@ -450,13 +578,20 @@ int sfa::epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const
     spent(2, 6); spent(3, 7); spent(4, 8);
     for (int k = 0; k < k2; k++)
         if (cnt[4 * k + 3]) return set_error(ctx, SFA_ERR_HIP, "%s: image %d of the sub-batch: the search's heap met its capacity of %d entries", fn, k, imgs[k].heap_cap);
+    if (info) {                                                      // one slice per image, all dense; the workspace: `done` and the heaps of the sub-batch
+        info[0] += k2; info[1] += k2;
+        size_t held = bytes3;
+        for (int k = 0; k < k2; k++) held -= epic_nn_rows_bytes(cnt[4 * k + 1]);
+        info[3] = std::max(info[3], (long long)held);
+    }
     *done_out = k2;
     return SFA_OK;
 }
 
-// what epic_nn_device allocates for an image before it has seen it: the part known beforehand and `done`
-size_t sfa::epic_nn_need0(int w, int h, int ns, int nn) {
-    return al(sizeof(EpicImg)) + al((size_t)w * h * 4) + 2 * al((size_t)ns * nn * 4) + al(16) + al((size_t)ns * ns * 4);
+// what epic_nn_device allocates for an image before it has seen it: the part known beforehand and, in the default mode, `done`
+size_t sfa::epic_nn_need0(const sfa_ctx *ctx, int w, int h, int ns, int nn) {
+    const size_t known = al(sizeof(EpicImg)) + al((size_t)w * h * 4) + 2 * al((size_t)ns * nn * 4) + al(16);
+    return ctx->epic_search == SFA_EPIC_SEARCH_COMPACT ? known : known + al((size_t)ns * ns * 4);
 }
 
 // the image sizes the kernels take, refused in the name of entry point `fn`
@@ -501,10 +636,11 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
     auto need_io = [&](int i) { return 2 * al(npix * 4) + al((size_t)ns[i] * 8) + 2 * al((size_t)ns[i] * nn * 4); };
     for (int i = 0; i < n; i++) status[i] = 0;
     for (float &v : ctx->epic_ms) v = 0.f;
+    for (long long &v : ctx->epic_info) v = 0;
     // A sub-batch is sized by what is known beforehand (planes, lists, `done`) or, once an image has been through, by the largest whole need seen.  What is
     // allocated never exceeds the budget: where the tables or heaps of a sub-batch's first image do not fit beside what the sub-batch already holds, that
     // image is tried alone before it is flagged
-    auto need0 = [&](int i) { return need_io(i) + epic_nn_need0(w, h, ns[i], nn); };
+    auto need0 = [&](int i) { return need_io(i) + epic_nn_need0(ctx, w, h, ns[i], nn); };
     size_t estimate = 0;                                             // (of epic_nn_device's part)
     bool alone = false;
     int first = 0;
@@ -533,7 +669,7 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
             SFA_HIP(ctx, hipMemcpyAsync(s, seeds_xy[i], (size_t)ns[i] * 8, hipMemcpyHostToDevice, st));
         }
         int done = 0;
-        SFA_TRY(epic_nn_device(ctx, fn, m, w, h, io.data(), budget - bytes, &done, &estimate, ctx->epic_ms));
+        SFA_TRY(epic_nn_device(ctx, fn, m, w, h, io.data(), budget - bytes, &done, &estimate, ctx->epic_ms, ctx->epic_info));
         if (done == 0) {                                             // the first image of the sub-batch: alone next time, or flagged if it was alone
             if (m > 1) alone = true;
             else { status[first++] = 1; alone = false; }
@@ -549,6 +685,12 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
         first += done;
         alone = false;
     }
+    return SFA_OK;
+}
+
+int sfa_epic_nn_search_info(sfa_ctx *ctx, long long info[4]) {
+    if (!ctx || !info) return set_error(ctx, SFA_ERR_ARG, "%s: %s is null", __func__, !ctx ? "ctx" : "info");
+    for (int k = 0; k < 4; k++) info[k] = ctx->epic_info[k];
     return SFA_OK;
 }
 

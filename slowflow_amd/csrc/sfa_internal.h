@@ -97,6 +97,8 @@ struct sfa_ctx {
     void *q_tmp = nullptr;        // sfa_flow_magnitude_quantiles_device (quantile.hip): group records, histograms and keys, kept from call to call, grown on demand
     size_t q_tmp_bytes = 0;
     float epic_ms[5] = {};        // sfa_epic_nearest_seeds_batch (epic_nn.hip): the last call's kernel time by group (sfa_epic_nn_stage_ms)
+    int epic_search = 0;          // sfa_ctx_set_epic_search: SFA_EPIC_SEARCH_DENSE (the default) or SFA_EPIC_SEARCH_COMPACT (epic_nn.hip, epic_nn_plan.h)
+    long long epic_info[4] = {};  // sfa_epic_nn_search_info: slices, images searched dense, images searched sparse, the largest slice workspace of the last stage
     float epic_fit_ms[2] = {};    // sfa_epic_interpolate_batch (epic_fit.hip): the last call's fit and apply kernel time (sfa_epic_fit_stage_ms)
     float epic_batch_ms[8] = {};  // sfa_epic_batch (epic_batch.hip): the last call's kernel time by stage (sfa_epic_batch_stage_ms)
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -123,7 +125,7 @@ struct Switches {
     enum Id {
         SOR_CHAIN, SOR_BAND, SOR_F, SOR_CH, SOR_LEAD, CHAIN_LDS, RB_TILE, WARP_ALLJ, NO_WARP_SMOOTH, ASSEMBLE_GENERIC, EXACT_DIV, ASM_XCD, NO_DIRECT_OPERANDS,
         NO_UV_ALIAS, DEBUG_ACTIVE, UNFUSED, SHARE_SOR, PYRAMID_UNFUSED, CUT_DISCHARGE, CUT_INNER, CUT_SUPER, CUT_TAIL_INNER, CUT_PER, CUT_TAIL_PER, CUT_TAIL_SUPER,
-        CUT_DEBUG, CUT_NO_TAIL, CUT_TAIL, NO_EXACT_BREAK, PAIR_UNFUSED, EPIC_FIT_PLAIN, N
+        CUT_DEBUG, CUT_NO_TAIL, CUT_TAIL, NO_EXACT_BREAK, PAIR_UNFUSED, EPIC_FIT_PLAIN, EPIC_NN_SET, EPIC_NN_SLICE, N
     };
     bool given[N] = {};
     int value[N] = {};
@@ -275,10 +277,12 @@ int fill_trajectories_device(sfa_ctx *ctx, int n, int J, int w, int h, int strid
 struct EpicNnIo { const float *cost; const int *seeds; int ns, nn; int *lab; int *index; float *dist; };
 // The stage for m images.  It keeps its two host reads of counts (border pairs; edges and the largest degree), which size what cannot be bounded beforehand,
 // and allocates that itself, within `budget` bytes: *done leading images fit and are computed (0: not even the first), the rest are untouched.  Returns
-// after waiting for the stream.  estimate (or null): raised to the largest whole need of an image seen; ms[5]: the kernel time by group, added to
-int epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const EpicNnIo *io, size_t budget, int *done, size_t *estimate, float ms[5]);
-// what epic_nn_device allocates for an image at least: everything known beforehand
-size_t epic_nn_need0(int w, int h, int ns, int nn);
+// after waiting for the stream.  estimate (or null): raised to the largest need of an image seen -- the whole search in the default mode, one workgroup's
+// in the compact mode (ctx->epic_search), where the search runs in slices that share a workspace; ms[5]: the kernel time by group, added to; info (or
+// null): the four numbers of sfa_epic_nn_search_info, added to (the workspace: raised to)
+int epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const EpicNnIo *io, size_t budget, int *done, size_t *estimate, float ms[5], long long info[4]);
+// what epic_nn_device allocates for an image at least: everything known beforehand (the default mode: `done` among it)
+size_t epic_nn_need0(const sfa_ctx *ctx, int w, int h, int ns, int nn);
 int epic_nn_check_sizes(sfa_ctx *ctx, const char *fn, int w, int h);
 // One image of the fit and its application.  seeds, vects: ns; index, weight: ns * nn; lab, fx, fy: w * h packed (apply only); model: 6 ns (LA) or 2 ns (NW)
 struct EpicFitImg {

@@ -91,7 +91,9 @@ static void usage() {
     printf("every acc_epic_skip-th pixel, one batch of EpicFlow interpolations per rate) to the fusion: slot 2 r is rate r's accumulated hypothesis, slot\n");
     printf("2 r + 1 its fill-in; labels_<start>.pgm holds the slot.  Reads <output>/accumulated/tmp/edges_<start>.dat (w * h floats; a missing one exits\n");
     printf("with status 2), so the output folder exists beforehand: run it with -resume.  Key: acc_epic_skip (2).  Refused: acc_skip_pixel other than 0,\n");
-    printf("more than 8 rates, acc_epic_interpolation 0.  The neighbour proposals are not run.\n");
+    printf("more than 8 rates, acc_epic_interpolation 0.  The neighbour proposals are not run.  acc_gpu_epic_search (0): 1 runs the fill-in's graph searches in\n");
+    printf("the library's compact mode (slices of seeds in one shared workspace: the same bits, and match counts whose ns * ns table would not fit, such as\n");
+    printf("acc_epic_skip 2 on a full frame, stay on the GPU); any other value exits with status 1.\n");
 }
 
 // dense_tracking.cpp:1183-1193 for a file of the flows' size: medianBlur(3) with OpenCV's border for ksize 3 (replicate; OpenCV is absent here, so this
@@ -691,6 +693,8 @@ static int run_fill(ParameterList &params, const Run &run, vector<Segment> &segs
     epic_fill_params(&eparams);
     sfa_ctx *ctx = nullptr;
     if (!segs.empty() && !sfa_ok(nullptr, sfa_ctx_create(0, &ctx))) return 1;
+    const int epic_search = params.parameter<int>("acc_gpu_epic_search", "0");                // 0 or 1 (refusal()): the graph searches of the fill-in, compact
+    if (ctx && epic_search && !sfa_ok(ctx, sfa_ctx_set_epic_search(ctx, SFA_EPIC_SEARCH_COMPACT))) { sfa_ctx_destroy(ctx); return 1; }
     struct RateFill { unsigned seq_start; int r; epic_fill_stats st; };
     vector<RateFill> fills;
     const int K = (int)run.rates, S = 2 * K, J = (int)run.Jets;
@@ -834,7 +838,7 @@ static int run_fill(ParameterList &params, const Run &run, vector<Segment> &segs
     std::ostringstream tail;
     tail.precision(17);
     const sfa_fuse_params &fup = fz.fup;
-    tail << ",\n  \"fused\": true, \"epic_fill\": true, \"epic_interpolation\": true, \"neighbour_proposals\": false, \"acc_epic_skip\": " << (double)epic_skip
+    tail << ",\n  \"fused\": true, \"epic_fill\": true, \"epic_interpolation\": true, \"neighbour_proposals\": false, \"acc_epic_skip\": " << (double)epic_skip << ", \"acc_gpu_epic_search\": " << epic_search
          << ", \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": " << fup.acc_spatial_occ << ", \"acc_traj_sim_method\": " << fup.traj_sim_method
          << ", \"acc_traj_sim_thres\": " << fup.traj_sim_thres << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter
          << ",\n  \"slots\": [";
@@ -945,6 +949,8 @@ static int refusal(ParameterList &params, const Run &run) {
                       : run.rates > 8 ? "more than 8 rates (jet_estimation lines; two of the 16 slots each)"
                       : !params.parameter<bool>("acc_epic_interpolation", "1") ? "acc_epic_interpolation 0" : nullptr;
             if (refused) { std::cerr << "-fill: " << refused << " is not supported" << std::endl; return 1; }
+            const int search = params.parameter<int>("acc_gpu_epic_search", "0");
+            if (search != 0 && search != 1) { std::cerr << "-fill: acc_gpu_epic_search " << search << " is neither 0 (the default search) nor 1 (the compact search)" << std::endl; return 1; }
         } else if (params.parameter<bool>("acc_epic_interpolation", "1"))
             std::cout << "-fuse: acc_epic_interpolation 1, but EpicFlow's fill-in and the neighbour proposals are not run (pixels without a hypothesis "
                          "stay UNKNOWN_FLOW)" << std::endl;

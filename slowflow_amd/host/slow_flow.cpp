@@ -46,7 +46,9 @@ static void usage() {
            "-jet [select one specific high speed flow]\n\n"
            "    -deep_settings is accepted and ignored: the reference passes it to the DeepMatching binary it starts (slow_flow.cpp:180-181, :768); this build does\n"
            "    not start DeepMatching or the MATLAB edge detector -- with deep_matching 1 it reads their outputs from <output>tmp/ (matches_<a>_<b>.dat, edges_<n>.dat).\n"
-           "    raw_demosaicing 1 (Hamilton-Adams, third-party code absent from the reference tree) is rejected; 0 (bilinear) and 2 (OpenCV's 8-bit conversion) work.\n\n");
+           "    raw_demosaicing 1 (Hamilton-Adams, third-party code absent from the reference tree) is rejected; 0 (bilinear) and 2 (OpenCV's 8-bit conversion) work.\n"
+           "    cfg keys of this build: gpu_epic 1 interpolates a batch's matches on the GPU (deep_matching 1); with it, gpu_epic_search 1 runs EpicFlow's graph searches\n"
+           "    in the library's compact mode (slices of seeds in one shared workspace; the same bits).  gpu_epic_search other than 0 or 1 exits with status 1.\n\n");
 }
 
 static void setDefault(ParameterList &p) {        // slow_flow.cpp:64-128
@@ -150,6 +152,7 @@ struct Run {
     const int streams = std::max(1, std::min(4, p.parameter<int>("gpu_streams", "2")));
     const bool deep_matching = p.parameter<bool>("deep_matching");
     const bool gpu_epic = p.parameter<bool>("gpu_epic", "0");                       // additive: deep_matching 1 interpolates a batch's matches through epic_batch (the graph searches on the GPU)
+    const int gpu_epic_search = p.parameter<int>("gpu_epic_search", "0");          // additive, with gpu_epic 1: 1 = those searches in the library's compact mode (main() refuses other values)
     // dm_scale (:396-402, :571-586, :801-843): DeepMatching and the edge detector ran on frames blurred (sigma = 1 / sqrt(2 dm_scale)) and resized by dm_scale; the
     // interpolation then runs at that resolution (the saliency image, the edge map, the matches' coordinates) and its flow is resized to the frames and multiplied by the
     // INTEGER ratio of the widths (:827-828: `float fx = im[ref]->width / wx->width` divides two ints).  dm_scale_run = dm_scale, halved by main() when max_flow > 150
@@ -721,6 +724,7 @@ static void refine_worker(Refinement &rf, const WorkerPlan &wp) {
     const Ctx ectx = ctx && run.deep_matching ? new_ctx(run.device_of(wp.gpu)) : Ctx();   // the EpicFlow helper's context (deep_matching 1 only)
     if (!ctx || (run.deep_matching && !ectx)) return rf.fail(sfa_last_error(nullptr));
     (void)sfa_ctx_set_verbose(ctx.get(), run.verbose_changes ? 1 : 0);
+    if (ectx && run.gpu_epic && run.gpu_epic_search && sfa_ctx_set_epic_search(ectx.get(), SFA_EPIC_SEARCH_COMPACT) != SFA_OK) return rf.fail(sfa_last_error(ectx.get()));
     if (!rf.seq.wait_gpu(wp.gpu)) { rf.failed = true; return; }
     ParameterList tp(run.p);                                                         // one copy per thread (:708), with the published normalisation
     for (int dirpass = 0; dirpass < (run.forward_only ? 2 : 1) && !rf.failed; dirpass++) {
@@ -742,7 +746,7 @@ static void write_timings(const Run &run, const std::vector<Window> &todo, const
     tj << "\n]\n";
     std::ofstream rj((run.output + "run.json").c_str());
     rj << "{\"windows\": " << todo.size() << ", \"gpus\": " << run.ngpu << ", \"streams\": " << run.streams << ", \"batch\": " << run.batch << ", \"io_threads\": " << run.io_threads
-       << ", \"ingest_path\": \"" << (run.gpu_ingest ? "gpu" : "host") << "\", \"decode_seconds\": " << decode << ", \"normalize_seconds\": " << normalize << ", \"ingest_seconds\": " << ingest << ", \"refine_seconds\": " << refine << ", \"total_seconds\": " << total;
+       << ", \"ingest_path\": \"" << (run.gpu_ingest ? "gpu" : "host") << "\", \"gpu_epic_search\": " << run.gpu_epic_search << ", \"decode_seconds\": " << decode << ", \"normalize_seconds\": " << normalize << ", \"ingest_seconds\": " << ingest << ", \"refine_seconds\": " << refine << ", \"total_seconds\": " << total;
     // per GPU: the frames it was sent (its windows' frames + halo), when the last of them had arrived, when its frames were normalised and when its first worker
     // began to refine -- all in seconds since the run began.  The whole sequence is "sequence_bytes"
     double last_upload = 0, first_refine = -1;
@@ -849,6 +853,11 @@ int main(int argc, char **argv) {
         std::cerr << "raw_demosaicing 1 (Hamilton-Adams, P. Getreuer's dmha) is third-party code absent from the reference tree: use raw_demosaicing 0 "
                      "(the reference's own bilinear / green-ratio routine), 2 (OpenCV's 8-bit bilinear conversion, restated) or provide demosaiced frames with raw 0" << std::endl;
         return 2;
+    }
+    const int epic_search = params.parameter<int>("gpu_epic_search", "0");
+    if (epic_search != 0 && epic_search != 1) {
+        std::cerr << "gpu_epic_search " << epic_search << " is neither 0 (the default search) nor 1 (the compact search of the library, with gpu_epic 1)" << std::endl;
+        return 1;
     }
 
     const int steps = params.parameter<int>("slow_flow_S") - 1;                      // :208
