@@ -66,6 +66,22 @@ def fill_matches(acc_u, acc_v, mask, xs, ys, divisor):
     return out
 
 
+def fill_matches_vec(acc_u, acc_v, mask, xs, ys, divisor):
+    """fill_matches without its Python loops, for the sample counts of the workload: the samples in raster order (rows ys, columns xs), the same
+    fp64 sum and division and the same conversion to float per element.  tests/test_second_trips.py holds it to the loop on the 70 x 45 scene"""
+    xs, ys = np.asarray(xs, np.int64), np.asarray(ys, np.int64)
+    yy, xx = np.repeat(ys, len(xs)), np.tile(xs, len(ys))
+    sel = mask[yy, xx] == 1
+    x, y = xx[sel], yy[sel]
+    div = np.float64(divisor)
+    out = []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(acc_u.shape[0]):
+            tx, ty = x.astype(np.float64) + acc_u[j, y, x] / div, y.astype(np.float64) + acc_v[j, y, x] / div
+            out.append(np.stack([x.astype(np.float32), y.astype(np.float32), tx.astype(np.float32), ty.astype(np.float32)], 1).reshape(-1, 4))
+    return out
+
+
 def fill_trajectories(flow_x, flow_y, w, scale):
     """flow_x, flow_y: fp32 (J, h, stride).  Returns acc_u, acc_v float64 (J, h, w) = (double)(plane * (float) scale) and tracked int32 (h, w) = J"""
     with np.errstate(all="ignore"):
