@@ -470,6 +470,50 @@ int  sfa_track_job_download_best_device(sfa_track_job *job, int s0, int ns, unsi
  * weight (its kernel alone), labels, pairwise, TRW-S, output; the last five are 0 on a job with do_fuse 0.  Slot 0 is NOT a pack + resample time: the flows are packed
  * and resampled by the uploads, outside the run. */
 int  sfa_track_job_stage_ms(sfa_track_job *job, float ms[8]);
+/* ---- a track job that fills in: dense_tracking's EpicFlow fill-in hypothesis of every rate (dense_tracking.cpp:1265-1350), resident ----------
+ * A job made by sfa_track_job_create_fill holds, beside the planes of a plain job, each start_jet's edge cost map and the saliency of its Lab image, and
+ * its fusion runs over S = 2 K slots: slot 2 r is rate r's accumulated hypothesis, slot 2 r + 1 its fill-in (the reference's push order), and that is the
+ * index sfa_track_job_download_fused returns as `slot`.  best, occluded and sfa_track_job_download_rate keep describing the accumulated hypotheses only.
+ * sfa_track_job_run, after the accumulation of every rate, does rate by rate: removeSmallSegments on tracked == r_Jets[r] and the matches at the sampled
+ * pixels (sfa_consistent_regions, sfa_fill_matches with divisor skip + 1 on the positions of sfa_fill_samples(epic_skip)); the edge costs of every step
+ * (start_jet s, step j of rate r reads the uploaded map after c_r + j + 1 sequential fp32 additions of epic.euc, c_r = r_Jets[0] + .. + r_Jets[r - 1]:
+ * the map is shared by all epic() calls of a start_jet in the reference, each of which adds euc on entry, filled or not; euc == 0 adds nothing); the
+ * interpolation of all ns * r_Jets[r] images by sfa_epic_batch's chain on these device planes, the saliency shared; sfa_fill_trajectories with scale
+ * skip + 1.  Then the energies of both kinds with the rate's weight, and the fusion.  A start_jet without a sample, without a match, or with a step whose
+ * matches the filters remove entirely is not filled for that rate: its odd slot holds energy +Inf, occlusion word 0 and adapted flows 0.
+ * A RUN WITH FILL WAITS FOR THE STREAM where the fill-in does: once per rate for the ns match counts, and wherever the interpolation reads its
+ * survivors.  An image that does not fit the interpolation's workspace even alone fails the run with an error naming start_jet, rate and step; there
+ * is no host path.  The match targets are not tested for finite values (sfa_epic_batch refuses those on the host).
+ * sfa_track_fill_params_default: epic_skip 2, min_size 100, epic = epic_fill_params (epic_params_default with pref_nn 25, nn 160, coef_kernel 1.1,
+ * LA), workspace_bytes 0 = half of what is free at run time. */
+typedef struct sfa_track_fill_params {
+    float epic_skip;            /* acc_epic_skip: the sampling step of the matches, >= 1 */
+    int min_size;               /* removeSmallSegments' smallest region */
+    sfa_epic_params epic;
+    size_t workspace_bytes;     /* the interpolation's workspace (not part of the job's allocation); 0: half of the free device memory at run time */
+} sfa_track_fill_params;
+void sfa_track_fill_params_default(sfa_track_fill_params *fill);
+/* Host only: the fixed allocation of a fill job.  Both refuse, by the argument's name, what sfa_track_job_create refuses and: K > 8; epic.nn < 1,
+ * epic.pref_nn < 0, epic.method outside 0 and 1; epic_skip not finite or < 1; min_size < 1; a grid of 8 columns or rows or fewer with
+ * epic.saliency_th != 0; a grid the nearest-seeds stage cannot index. */
+int  sfa_track_job_bytes_fill(const sfa_track_params *p, const sfa_track_fill_params *fill, size_t *bytes);
+int  sfa_track_job_create_fill(sfa_ctx *ctx, const sfa_track_params *p, const sfa_track_fill_params *fill, sfa_track_job **out);
+/* start_jet s of a fill job: lab = the Lab image at the grid's size, 3 planes of gh rows of lab_stride floats (NULL where epic.saliency_th == 0);
+ * edges = gh * gw floats, the cost map as the edge file holds it (euc not added).  Waits: the caller's planes are free on return. */
+int  sfa_track_job_upload_fill(sfa_track_job *job, int s, const float *lab, int lab_stride, const float *edges);
+/* The same for start_jets s0 .. s0+ns-1 from GPU memory, in stream order and without a host wait: lab_dev fp32 [ns][3][gh][gw] at lab_strides[4] (NULL
+ * where epic.saliency_th == 0), edges_dev fp32 [ns][gh][gw] at edge_strides[3]. */
+int  sfa_track_job_upload_fill_device(sfa_track_job *job, int s0, int ns, const float *lab_dev, const long long lab_strides[4], const float *edges_dev,
+                                      const long long edge_strides[3]);
+/* Rate r's fill-in of segment s after a run: the trajectories fill_u, fill_v [r_Jets[r]][gh][gw] (0 where not filled), energy and occ_bits [gh][gw] (slot
+ * 2 r + 1), stats[3] = {kept_pixels, matches, filled}.  NULL skips an output.  Waits for the run. */
+int  sfa_track_job_download_fill(sfa_track_job *job, int s, int r, double *fill_u, double *fill_v, double *energy, unsigned long long *occ_bits, int *stats);
+/* The last run's fill-in times in ms (HIP events, summed over the rates; waits for the run): regions and matches, the edge costs, the interpolation chain
+ * (with its host reads), trajectories.  On a fill job sfa_track_job_stage_ms' energies slot begins where the last rate's fill-in ends. */
+int  sfa_track_job_fill_ms(sfa_track_job *job, float ms[4]);
+/* How the last run's interpolation was cut, summed over the rates: info[0] the sub-batches that ran to their end, info[1] those that were cut short by the
+ * workspace and run again with the images that fit.  No result depends on the cut. */
+int  sfa_track_job_fill_info(sfa_track_job *job, int info[2]);
 /* ---- resident pair jobs: the two-frame refinement of pairs that stay in GPU memory (csrc/two_frame.hip) -------------------------------
  * A pair job owns the planes of n pairs of one size (24 per pair: those of sfa_variational_2frame without its 24-plane derivative stack) and one solver
  * workspace, across any number of uploads and runs.  sfa_pair_job_run enqueues variational()'s launch sequence (variational.c:19-82) for all n pairs on the

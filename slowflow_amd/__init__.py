@@ -168,13 +168,33 @@ def track_params(w, h, Jets, r_Jets, n=1, sources=None, weights=None, energy=Non
     return p
 
 
-def track_job_bytes(params):
-    """sfa_track_job_bytes (host only, no GPU): the device bytes a TrackJob of these parameters allocates"""
+class TrackFillParams(C.Structure):
+    """sfa_track_fill_params: what a track job that fills in takes beside its TrackParams (include/slowflow_amd.h)"""
+    _fields_ = [("epic_skip", C.c_float), ("min_size", C.c_int), ("epic", EpicParams), ("workspace_bytes", C.c_size_t)]
+
+
+def track_fill_params(**kw):
+    """sfa_track_fill_params_default (epic_skip 2, min_size 100, epic = epic_params(pref_nn=25, nn=160, coef_kernel=1.1), workspace_bytes 0 = half of the
+    free device memory at run time) with the given fields replaced; epic: an EpicParams"""
+    f = TrackFillParams()
+    lib().sfa_track_fill_params_default(C.byref(f))
+    for k, v in kw.items():
+        assert k in ("epic_skip", "min_size", "epic", "workspace_bytes"), k
+        setattr(f, k, v)
+    return f
+
+
+def track_job_bytes(params, fill=None):
+    """sfa_track_job_bytes / sfa_track_job_bytes_fill (host only, no GPU): the device bytes a TrackJob of these parameters allocates; fill: None or a
+    TrackFillParams (the interpolation's workspace is not part of it)"""
     L = lib()
     L.sfa_track_job_bytes.argtypes = [C.POINTER(TrackParams), C.POINTER(C.c_size_t)]
+    L.sfa_track_job_bytes_fill.argtypes = [C.POINTER(TrackParams), C.POINTER(TrackFillParams), C.POINTER(C.c_size_t)]
     b = C.c_size_t()
-    if L.sfa_track_job_bytes(C.byref(params), C.byref(b)) != 0:
-        raise SlowflowError("sfa_track_job_bytes: %s" % L.sfa_last_error(None).decode())
+    name = "sfa_track_job_bytes" if fill is None else "sfa_track_job_bytes_fill"
+    rc = L.sfa_track_job_bytes(C.byref(params), C.byref(b)) if fill is None else L.sfa_track_job_bytes_fill(C.byref(params), C.byref(fill), C.byref(b))
+    if rc != 0:
+        raise SlowflowError("%s: %s" % (name, L.sfa_last_error(None).decode()))
     return b.value
 
 
@@ -190,6 +210,7 @@ EXPORTS = [
     "sfa_demosaic_device", "sfa_sequence_upload_mosaic_device", "sfa_sequence_upload_mosaic", "sfa_job_set_raw_weights", "sfa_sequence_rescale",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
     "sfa_track_params_default", "sfa_track_job_bytes", "sfa_track_job_create", "sfa_track_job_destroy", "sfa_track_job_upload_flows", "sfa_track_job_upload_frames", "sfa_track_job_upload_flows_device", "sfa_track_job_upload_frames_device", "sfa_track_job_run", "sfa_track_job_download_rate", "sfa_track_job_download_fused", "sfa_track_job_download_best", "sfa_ctx_free_bytes", "sfa_track_job_download_device", "sfa_track_job_stage_ms", "sfa_track_job_upload_occlusions_device", "sfa_track_job_download_rate_device", "sfa_track_job_download_best_device",
+    "sfa_track_fill_params_default", "sfa_track_job_bytes_fill", "sfa_track_job_create_fill", "sfa_track_job_upload_fill", "sfa_track_job_upload_fill_device", "sfa_track_job_download_fill", "sfa_track_job_fill_ms", "sfa_track_job_fill_info",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
 
@@ -1166,10 +1187,13 @@ class PairJob:
 class TrackJob:
     """sfa_track_job: dense_tracking's accumulation, energies and fusion of up to params.n start_jets x params.K rates, resident in HBM.  run() only
     enqueues the whole chain and returns at once; the downloads wait.  Segment s comes out bit-identical to Context.accumulate_consistent(all_steps) ->
-    hypothesis_energies(adapted=True) -> smoothness_weight -> fuse_hypotheses on that segment alone."""
+    hypothesis_energies(adapted=True) -> smoothness_weight -> fuse_hypotheses on that segment alone.  fill: a TrackFillParams makes it a job that also
+    forms every rate's EpicFlow fill-in hypothesis (upload_fill, download_fill) and fuses 2 K slots, slot 2 r + 1 the fill-in of rate r; its run() waits
+    where the fill-in reads its counts."""
 
-    def __init__(self, ctx, params):
+    def __init__(self, ctx, params, fill=None):
         self.ctx, self.params = ctx, TrackParams.from_buffer_copy(params)
+        self.fill = TrackFillParams.from_buffer_copy(fill) if fill is not None else None
         self.n, self.K, self.Jets, self.w, self.h = params.n, params.K, params.Jets, params.w, params.h
         self.h_ = C.c_void_p()
         L = lib()
@@ -1181,7 +1205,14 @@ class TrackJob:
         L.sfa_track_job_download_rate.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
         L.sfa_track_job_download_fused.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.sfa_track_job_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        ctx._ck(L.sfa_track_job_create(ctx.h, C.byref(self.params), C.byref(self.h_)), "sfa_track_job_create")
+        L.sfa_track_job_create_fill.argtypes = [C.c_void_p, C.POINTER(TrackParams), C.POINTER(TrackFillParams), C.POINTER(C.c_void_p)]
+        L.sfa_track_job_upload_fill.argtypes = [C.c_void_p, C.c_int, _f, C.c_int, _f]
+        L.sfa_track_job_download_fill.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.sfa_track_job_fill_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        if self.fill is None:
+            ctx._ck(L.sfa_track_job_create(ctx.h, C.byref(self.params), C.byref(self.h_)), "sfa_track_job_create")
+        else:
+            ctx._ck(L.sfa_track_job_create_fill(ctx.h, C.byref(self.params), C.byref(self.fill), C.byref(self.h_)), "sfa_track_job_create_fill")
         self.gw, self.gh = accumulate_grid(self.w, self.h, params.skip)
         ctx._children.add(self)
 
@@ -1208,7 +1239,49 @@ class TrackJob:
         fp = (_f * (self.Jets + 1))(*[fptr(frames[k]) for k in range(self.Jets + 1)])
         self.ctx._ck(lib().sfa_track_job_upload_frames(self.h_, int(s), fp, frames.shape[3]), "sfa_track_job_upload_frames")
 
+    def upload_fill(self, s, lab, edges):
+        """segment s of a fill job: lab = the Lab image at the grid's size, fp32 (3, gh, stride) (None where epic.saliency_th == 0); edges = the edge
+        cost map fp32 (gh, gw), euc not added"""
+        edges = np.ascontiguousarray(edges, dtype=np.float32)
+        assert edges.shape == (self.gh, self.gw), "edges are (gh, gw)"
+        stride = 0
+        if lab is not None:
+            lab = np.ascontiguousarray(lab, dtype=np.float32)
+            assert lab.ndim == 3 and lab.shape[:2] == (3, self.gh), "lab is (3, gh, stride)"
+            stride = lab.shape[2]
+        self.ctx._ck(lib().sfa_track_job_upload_fill(self.h_, int(s), fptr(lab) if lab is not None else None, stride, fptr(edges)), "sfa_track_job_upload_fill")
+
+    def download_fill(self, s, r):
+        """rate r's fill-in of segment s: a dict of u, v float64 (r_Jets[r], gh, gw), energy float64 and occ_bits uint64 (gh, gw) (slot 2 r + 1), and the
+        ints kept_pixels, matches, filled"""
+        rJ, g = self.params.r_Jets[r] if 0 <= r < self.K else 1, (self.gh, self.gw)
+        out = dict(u=np.zeros((rJ,) + g, np.float64), v=np.zeros((rJ,) + g, np.float64), energy=np.zeros(g, np.float64), occ_bits=np.zeros(g, np.uint64))
+        st = (C.c_int * 3)()
+        self.ctx._ck(lib().sfa_track_job_download_fill(self.h_, int(s), int(r), *[out[k].ctypes.data for k in ("u", "v", "energy", "occ_bits")], C.addressof(st)),
+                     "sfa_track_job_download_fill")
+        out.update(kept_pixels=st[0], matches=st[1], filled=st[2])
+        return out
+
+    def fill_ms(self):
+        """the last run's fill-in times in ms, summed over the rates: regions and matches, edge costs, the interpolation chain, trajectories (waits)"""
+        ms = (C.c_float * 4)()
+        self.ctx._ck(lib().sfa_track_job_fill_ms(self.h_, ms), "sfa_track_job_fill_ms")
+        return list(ms)
+
+    def fill_info(self):
+        """(sub-batches of the last run's interpolation that ran to their end, sub-batches cut short by the workspace and run again), over all rates"""
+        info = (C.c_int * 2)()
+        L = lib()
+        L.sfa_track_job_fill_info.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        self.ctx._ck(L.sfa_track_job_fill_info(self.h_, info), "sfa_track_job_fill_info")
+        return info[0], info[1]
+
     # ---- the device seam (slowflow_amd/device.py): objects with __cuda_array_interface__, asynchronous on the context's stream ----
+    def upload_fill_device(self, lab, edges, s0=0):
+        """lab: fp32 [ns, 3, gh, gw] (None where epic.saliency_th == 0), edges: fp32 [ns, gh, gw] in device memory (any strides) -> segments s0 .."""
+        from . import device
+        device.track_job_upload_fill_device(self, lab, edges, s0)
+
     def upload_flows_device(self, r, fwd, bwd, s0=0):
         """fwd, bwd: fp32 [ns, r_Jets[r], 2, sh, sw] in device memory (any strides) -> rate r of segments s0 .. s0 + ns - 1"""
         from . import device

@@ -16,6 +16,9 @@
 #include "sfa_device.h"
 #include "sfa_internal.h"
 
+// This file holds no kernel: sizing, records, copies and launches around the stages' own launch functions.  Compiled for size (see track.hip).
+#pragma clang attribute push(__attribute__((minsize)), apply_to = function)
+
 namespace sfa {
 namespace {
 
@@ -62,7 +65,7 @@ struct Item {
     int count, cnt[3];
 };
 
-struct Sizes { int w, h, pitch; size_t npix, pl; bool saliency; };
+struct Sizes { int w, h, pitch; size_t npix, pl; bool saliency, sal_own; };       // sal_own: the chain computes the saliency planes itself (and holds them)
 
 int nn_max_of(const sfa_epic_params &p, int nm) { return std::max(p.pref_nn ? std::min(p.pref_nn + 1, nm) : 1, std::min(p.nn, nm)); }
 
@@ -71,7 +74,7 @@ size_t persistent_bytes(const Sizes &z, const sfa_epic_params &p, int nm) {
     return al(sizeof(EpicFilterImg)) + al(sizeof(EpicFitImg)) + 4 * al(z.npix * 4) + 2 * al((size_t)nm * 16) + 2 * al((size_t)nm * 8) + 2 * al(list * 4) +
            al((size_t)nm * 24) + al((size_t)nm) + al(((size_t)nm + kEfThreads - 1) / kEfThreads * 4) + al(4);
 }
-size_t saliency_bytes(const Sizes &z) { return z.saliency ? al((size_t)kEpicSaliencyPlanes * z.pl * 4) : 0; }
+size_t saliency_bytes(const Sizes &z) { return z.sal_own ? al((size_t)kEpicSaliencyPlanes * z.pl * 4) : 0; }
 
 struct Call {
     sfa_ctx *ctx; const char *fn; Sizes z; const sfa_epic_params *p;
@@ -79,6 +82,10 @@ struct Call {
     float *const *flow_x, *const *flow_y; int flow_stride; int *rc; int (*counts)[3]; float *const *kept_matches;
     size_t budget; size_t estimate;                                  // of the nearest-seeds stage's own part, per image
     long long info[4];                                               // sfa_epic_nn_search_info of the sub-batch's last search
+    // dev: cost, matches, flow_x and flow_y point into device memory (packed w x h planes, nm rows) and sal[i] is image i's saliency plane at the device
+    // pitch, computed by the caller; lab is not read.  The costs are read in place and the matches copied, so a sub-batch that is run again finds both as
+    // they were; the flows are left in the caller's planes by copies on the stream
+    bool dev; const float *const *sal;
 };
 
 // The chain for the images `which` (all with matches).  *fit: how many of them, from the first, the sub-batch can hold (== which.size(): done and written)
@@ -113,20 +120,22 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
         t.block_off = b.take<int>(((size_t)nm + kEfThreads - 1) / kEfThreads);
         t.kept = b.take<int>(1);
         t.count = nm; t.cnt[0] = t.cnt[1] = t.cnt[2] = nm;
-        SFA_HIP(ctx, hipMemcpyAsync(t.cost, c.cost[t.i], z.npix * 4, hipMemcpyHostToDevice, st));
-        SFA_HIP(ctx, hipMemcpyAsync(t.list[0], c.matches[t.i], (size_t)nm * 16, hipMemcpyHostToDevice, st));
+        if (c.dev) t.cost = const_cast<float *>(c.cost[t.i]);                              // (read only: EpicNnIo::cost)
+        else SFA_HIP(ctx, hipMemcpyAsync(t.cost, c.cost[t.i], z.npix * 4, hipMemcpyHostToDevice, st));
+        SFA_HIP(ctx, hipMemcpyAsync(t.list[0], c.matches[t.i], (size_t)nm * 16, c.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     }
     StageTimer timer(st);
     float *ms = ctx->epic_batch_ms;
     // the records of the images `live` (positions in items), with the saliency plane and the neighbour count of the stage
     std::vector<EpicFilterImg> frec;
-    auto put_filter = [&](const std::vector<int> &live, const float *sal_planes, int nn_cap) {
+    float *sal_planes = nullptr;
+    auto put_filter = [&](const std::vector<int> &live, bool sal, int nn_cap) {
         frec.assign(live.size(), EpicFilterImg{});
         for (size_t k = 0; k < live.size(); k++) {
             const Item &t = items[live[k]];
             EpicFilterImg &r = frec[k];
             r.in = t.list[0]; r.out = t.list[1]; r.count = t.count; r.flag = t.flag; r.block_off = t.block_off; r.kept = t.kept;
-            r.sal = sal_planes ? sal_planes + (size_t)live[k] * kEpicSaliencyPlanes * z.pl + (size_t)kEpicSaliencyOut * z.pl : nullptr;
+            r.sal = !sal ? nullptr : c.dev ? c.sal[t.i] : sal_planes + (size_t)live[k] * kEpicSaliencyPlanes * z.pl + (size_t)kEpicSaliencyOut * z.pl;
             r.seeds = t.seeds; r.vects = t.vects; r.est = t.model; r.dist = t.dist; r.nn = std::min(nn_cap, t.count);
         }
         return hipMemcpyAsync(d_filter, frec.data(), frec.size() * sizeof(EpicFilterImg), hipMemcpyHostToDevice, st);
@@ -151,7 +160,7 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
     std::vector<EpicFitImg> fitrec;
     auto search_and_fit = [&](const std::vector<int> &live, int nn_cap, int method, int slot_nn, int slot_w, int slot_fit, int *done, long long *info) {
         const int L = (int)live.size(), cm = count_max_of(live);
-        SFA_HIP(ctx, put_filter(live, nullptr, nn_cap));
+        SFA_HIP(ctx, put_filter(live, false, nn_cap));
         timer.begin(1);
         epic_seeds_vects_device(ctx, L, cm, d_filter);
         timer.end();
@@ -184,8 +193,7 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
     std::vector<int> live(m);
     for (int k = 0; k < m; k++) live[k] = k;
     // ---- clamp, saliency filter --------------------------------------------------------------------------------------------------------------------------
-    float *sal_planes = nullptr;
-    if (z.saliency) {
+    if (z.sal_own) {
         SFA_TRY(sal_mem.alloc(ctx, (size_t)m * saliency_bytes(z)));
         sal_planes = sal_mem.f();
         for (int k = 0; k < m; k++)
@@ -194,15 +202,17 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
                                      c.lab_stride, z.w, z.h));
             }
     }
-    SFA_HIP(ctx, put_filter(live, sal_planes, 1));
+    SFA_HIP(ctx, put_filter(live, z.saliency, 1));
     timer.begin(1);
     epic_clamp_device(ctx, m, count_max_of(live), z.w, z.h, d_filter);
     timer.end();
     if (z.saliency) {
-        const Geo g{z.w, z.h, z.pitch, (long)z.pl, (long)(kEpicSaliencyPlanes * z.pl), m, WMask::first(std::min(m, kMaxBatch)), nullptr};
-        timer.begin(0);
-        epic_saliency_device(ctx, g, sal_planes, 0.8f, 1.0f);
-        timer.end();
+        if (z.sal_own) {
+            const Geo g{z.w, z.h, z.pitch, (long)z.pl, (long)(kEpicSaliencyPlanes * z.pl), m, WMask::first(std::min(m, kMaxBatch)), nullptr};
+            timer.begin(0);
+            epic_saliency_device(ctx, g, sal_planes, 0.8f, 1.0f);
+            timer.end();
+        }
         timer.begin(1);
         epic_saliency_flags_device(ctx, m, count_max_of(live), z.w, z.h, z.pitch, p.saliency_th, d_filter);
         epic_compact_device(ctx, m, count_max_of(live), d_filter);
@@ -237,6 +247,11 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
         SFA_HIP(ctx, hipGetLastError());
         for (int k : live) {
             const Item &t = items[k];
+            if (c.dev) {
+                SFA_HIP(ctx, hipMemcpyAsync(c.flow_x[t.i], t.fx, z.npix * 4, hipMemcpyDeviceToDevice, st));
+                SFA_HIP(ctx, hipMemcpyAsync(c.flow_y[t.i], t.fy, z.npix * 4, hipMemcpyDeviceToDevice, st));
+                continue;
+            }
             SFA_TRY(download_plane(ctx, c.flow_x[t.i], c.flow_stride, t.fx, z.w, z.w, z.h));      // the valid columns only
             SFA_TRY(download_plane(ctx, c.flow_y[t.i], c.flow_stride, t.fy, z.w, z.w, z.h));
             if (c.kept_matches) SFA_HIP(ctx, hipMemcpyAsync(c.kept_matches[t.i], t.list[0], (size_t)t.count * 16, hipMemcpyDeviceToHost, st));
@@ -253,7 +268,73 @@ int run_sub_batch(Call &c, const std::vector<int> &which, int *fit) {
     return SFA_OK;
 }
 
+// the sub-batches of a call over its n images, in order
+int run_chain(Call &c, int n, int *status) {
+    sfa_ctx *ctx = c.ctx;
+    for (float &v : ctx->epic_batch_ms) v = 0.f;
+    for (long long &v : ctx->epic_info) v = 0;
+    ctx->epic_chain_runs[0] = ctx->epic_chain_runs[1] = 0;
+    // what an image needs at least: what it owns for the whole chain, and beside that the larger of the saliency's planes and the search's known part
+    auto need0 = [&](int i) {
+        return persistent_bytes(c.z, *c.p, c.nm[i]) + std::max(saliency_bytes(c.z), std::max(epic_nn_need0(ctx, c.z.w, c.z.h, c.nm[i], nn_max_of(*c.p, c.nm[i])), c.estimate));
+    };
+    for (int i = 0; i < n; i++) status[i] = 0;
+    int first = 0, cap = kMaxSubBatch;                               // cap: what the sub-batch before this attempt showed to fit
+    while (first < n) {
+        if (c.nm[first] == 0) {                                        // no match: epic() returns 1 before it computes anything
+            c.rc[first] = 1;
+            if (c.counts) c.counts[first][0] = c.counts[first][1] = c.counts[first][2] = 0;
+            first++;
+            continue;
+        }
+        std::vector<int> which;
+        int next = first;
+        for (size_t used = 0; next < n && (int)which.size() < cap; next++) {
+            if (c.nm[next] == 0) break;                                // (handled above, in order)
+            used += need0(next);
+            if (used > c.budget) break;
+            which.push_back(next);
+        }
+        if (which.empty()) {
+            if (persistent_bytes(c.z, *c.p, c.nm[first]) + std::max(saliency_bytes(c.z), epic_nn_need0(ctx, c.z.w, c.z.h, c.nm[first], nn_max_of(*c.p, c.nm[first]))) > c.budget) {
+                status[first++] = 1;                                 // not even alone: flagged, its outputs untouched
+                cap = kMaxSubBatch;
+                continue;
+            }
+            which.push_back(first);                                  // (the estimate is another image's: this one may still fit)
+        }
+        int fit = 0;
+        SFA_TRY(run_sub_batch(c, which, &fit));
+        if (fit == (int)which.size()) {                              // (a sub-batch that is run again counts once)
+            for (int k = 0; k < 3; k++) ctx->epic_info[k] += c.info[k];
+            ctx->epic_info[3] = std::max(ctx->epic_info[3], c.info[3]);
+            first = which.back() + 1; cap = kMaxSubBatch;
+            ctx->epic_chain_runs[0]++;
+            continue;
+        }
+        if (which.size() == 1) { status[first++] = 1; cap = kMaxSubBatch; continue; }
+        cap = std::max(fit, 1);                                      // again, with the images that fit
+        ctx->epic_chain_runs[1]++;
+    }
+    return SFA_OK;
+}
+
 }  // namespace
+
+int epic_chain_device(sfa_ctx *ctx, const char *fn, int n, int w, int h, const sfa_epic_params *p, const EpicChainDev &io, int *rc, int (*counts)[3],
+                      size_t workspace_bytes, int *status) {
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    size_t budget = workspace_bytes;
+    if (!budget) {                                                   // half of what the GPU has free now
+        size_t free_b = 0, total_b = 0;
+        SFA_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+        budget = free_b / 2;
+    }
+    Call c{ctx, fn, Sizes{w, h, dev_pitch(w), (size_t)w * h, (size_t)dev_pitch(w) * h, p->saliency_th != 0, false}, p, nullptr, 0, io.cost, io.matches, io.nm,
+           io.fx, io.fy, w, rc, counts, nullptr, budget, 0, {}, true, io.sal};
+    return run_chain(c, n, status);
+}
+
 }  // namespace sfa
 
 using namespace sfa;
@@ -295,51 +376,9 @@ int sfa_epic_batch(sfa_ctx *ctx, int n, int w, int h, const sfa_epic_params *p, 
         SFA_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
         budget = free_b / 2;
     }
-    for (float &v : ctx->epic_batch_ms) v = 0.f;
-    Call c{ctx, fn, Sizes{w, h, dev_pitch(w), (size_t)w * h, (size_t)dev_pitch(w) * h, saliency}, p, lab, lab_stride, cost, matches, nm,
-           flow_x, flow_y, flow_stride, rc, counts, kept_matches, budget, 0, {}};
-    for (long long &v : ctx->epic_info) v = 0;
-    // what an image needs at least: what it owns for the whole chain, and beside that the larger of the saliency's planes and the search's known part
-    auto need0 = [&](int i) {
-        return persistent_bytes(c.z, *p, nm[i]) + std::max(saliency_bytes(c.z), std::max(epic_nn_need0(ctx, w, h, nm[i], nn_max_of(*p, nm[i])), c.estimate));
-    };
-    for (int i = 0; i < n; i++) status[i] = 0;
-    int first = 0, cap = kMaxSubBatch;                               // cap: what the sub-batch before this attempt showed to fit
-    while (first < n) {
-        if (nm[first] == 0) {                                        // no match: epic() returns 1 before it computes anything
-            rc[first] = 1;
-            if (counts) counts[first][0] = counts[first][1] = counts[first][2] = 0;
-            first++;
-            continue;
-        }
-        std::vector<int> which;
-        int next = first;
-        for (size_t used = 0; next < n && (int)which.size() < cap; next++) {
-            if (nm[next] == 0) break;                                // (handled above, in order)
-            used += need0(next);
-            if (used > budget) break;
-            which.push_back(next);
-        }
-        if (which.empty()) {
-            if (persistent_bytes(c.z, *p, nm[first]) + std::max(saliency_bytes(c.z), epic_nn_need0(ctx, w, h, nm[first], nn_max_of(*p, nm[first]))) > budget) {
-                status[first++] = 1;                                 // not even alone: flagged, its outputs untouched
-                cap = kMaxSubBatch;
-                continue;
-            }
-            which.push_back(first);                                  // (the estimate is another image's: this one may still fit)
-        }
-        int fit = 0;
-        SFA_TRY(run_sub_batch(c, which, &fit));
-        if (fit == (int)which.size()) {                              // (a sub-batch that is run again counts once)
-            for (int k = 0; k < 3; k++) ctx->epic_info[k] += c.info[k];
-            ctx->epic_info[3] = std::max(ctx->epic_info[3], c.info[3]);
-            first = which.back() + 1; cap = kMaxSubBatch;
-            continue;
-        }
-        if (which.size() == 1) { status[first++] = 1; cap = kMaxSubBatch; continue; }
-        cap = std::max(fit, 1);                                      // again, with the images that fit
-    }
-    return SFA_OK;
+    Call c{ctx, fn, Sizes{w, h, dev_pitch(w), (size_t)w * h, (size_t)dev_pitch(w) * h, saliency, saliency}, p, lab, lab_stride, cost, matches, nm,
+           flow_x, flow_y, flow_stride, rc, counts, kept_matches, budget, 0, {}, false, nullptr};
+    return run_chain(c, n, status);
 }
 
 int sfa_epic_saliency_batch(sfa_ctx *ctx, int n, int w, int h, const float *const *lab, int stride, float sigma_image, float sigma_matrix, float *const *out) {
@@ -379,3 +418,5 @@ int sfa_epic_batch_stage_ms(sfa_ctx *ctx, float ms[8]) {
     for (int k = 0; k < 8; k++) ms[k] = ctx->epic_batch_ms[k];
     return SFA_OK;
 }
+
+#pragma clang attribute pop

@@ -134,7 +134,40 @@ __global__ void __launch_bounds__(kEfThreads) k_ef_seeds_vects(const EpicFilterI
     im.vects[k] = make_float2(m.z - m.x, m.w - m.y);
 }
 
+// The edge costs of the epic() calls of one rate's steps (the track job's fill-in, track.hip).  host/epic_fill.cpp:47-56 with epic()'s own addition (host/epic.cpp:342): the map is shared by every epic() call of
+// a start_jet, and each call adds euc to it on entry, so step j of a rate whose first call has index c reads the file's map after c + j + 1 sequential fp32
+// additions -- repeated additions, never a product.  run: [ns][cpl], the map after the c additions of the calls before this rate, left after c + rJ; cost:
+// [ns][rJ][cpl], the planes the interpolation reads.  cpl is a multiple of 4 and the bases are 256-byte aligned: one thread carries four pixels of segment
+// blockIdx.y through the steps with 16-byte accesses, the thread at a plane's end its 1 .. 3 pixels one by one.  euc == 0 adds nothing (`if (params->euc)`)
+__global__ void __launch_bounds__(kEfThreads) k_ef_edge_costs(float *__restrict__ run, float *__restrict__ cost, int rJ, size_t cpl, int gpl, float euc) {
+    const size_t i = ((size_t)blockIdx.x * kEfThreads + threadIdx.x) * 4;
+    if (i >= (size_t)gpl) return;
+    float *r = run + (size_t)blockIdx.y * cpl, *c = cost + (size_t)blockIdx.y * rJ * cpl;
+    if (i + 4 <= (size_t)gpl) {
+        float4 v = *reinterpret_cast<const float4 *>(r + i);
+#pragma unroll 1
+        for (int j = 0; j < rJ; j++) {
+            if (euc != 0.0f) { v.x += euc; v.y += euc; v.z += euc; v.w += euc; }
+            *reinterpret_cast<float4 *>(c + (size_t)j * cpl + i) = v;
+        }
+        *reinterpret_cast<float4 *>(r + i) = v;
+        return;
+    }
+    for (size_t k = i; k < (size_t)gpl; k++) {
+        float v = r[k];
+#pragma unroll 1
+        for (int j = 0; j < rJ; j++) {
+            if (euc != 0.0f) v += euc;
+            c[(size_t)j * cpl + k] = v;
+        }
+        r[k] = v;
+    }
+}
+
 }  // namespace
+
+// the launch functions: compiled for size (see track.hip)
+#pragma clang attribute push(__attribute__((minsize)), apply_to = function)
 
 void epic_clamp_device(sfa_ctx *ctx, int m, int count_max, int w, int h, const EpicFilterImg *d_imgs) {
     if (count_max > 0) hipLaunchKernelGGL(k_ef_clamp, dim3(blocks(count_max, kEfThreads), m), dim3(kEfThreads), 0, ctx->stream, d_imgs, w, h);
@@ -166,5 +199,14 @@ void epic_saliency_device(sfa_ctx *ctx, const Geo &g, float *planes, float sigma
     launch_presmooth(ctx, g, sim, tmp, lab, 3, sigma_matrix);        // integrate it
     hipLaunchKernelGGL(k_ef_eigen, grid2d(g), block2d(), 0, ctx->stream, sim, planes + (size_t)kEpicSaliencyOut * g.pl, g);
 }
+
+int epic_edge_costs_device(sfa_ctx *ctx, int ns, int rJ, size_t cpl, int gpl, float euc, float *run, float *cost) {
+    const unsigned quads = (unsigned)(((size_t)gpl + 3) / 4);
+    hipLaunchKernelGGL(k_ef_edge_costs, dim3(blocks(quads, kEfThreads), (unsigned)ns), dim3(kEfThreads), 0, ctx->stream, run, cost, rJ, cpl, gpl, euc);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+#pragma clang attribute pop
 
 }  // namespace sfa

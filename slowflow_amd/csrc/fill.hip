@@ -257,6 +257,9 @@ int fill_trajectories_device(sfa_ctx *ctx, int n, int J, int w, int h, int strid
 
 using namespace sfa;
 
+// the entry points: argument checks, allocations, copies around the launch functions above.  Compiled for size (see track.hip)
+#pragma clang attribute push(__attribute__((minsize)), apply_to = function)
+
 constexpr int kMaxFillMaps = 65535;             // a map (or a plane) is a grid row
 
 int sfa_fill_samples(int extent, float epic_skip, int *out, int *count) {
@@ -383,3 +386,5 @@ int sfa_fill_trajectories(sfa_ctx *ctx, int n, int J, int w, int h, int stride, 
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;
 }
+
+#pragma clang attribute pop

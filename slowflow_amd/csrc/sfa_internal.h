@@ -101,6 +101,7 @@ struct sfa_ctx {
     long long epic_info[4] = {};  // sfa_epic_nn_search_info: slices, images searched dense, images searched sparse, the largest slice workspace of the last stage
     float epic_fit_ms[2] = {};    // sfa_epic_interpolate_batch (epic_fit.hip): the last call's fit and apply kernel time (sfa_epic_fit_stage_ms)
     float epic_batch_ms[8] = {};  // sfa_epic_batch (epic_batch.hip): the last call's kernel time by stage (sfa_epic_batch_stage_ms)
+    int epic_chain_runs[2] = {};  // the last chain's sub-batches: those that ran to their end, those that were cut short and run again with fewer images
     hipEvent_t t0 = nullptr, t1 = nullptr;
     hipEvent_t ev_wait = nullptr, ev_signal = nullptr;   // sfa_ctx_wait_stream / sfa_ctx_signal_stream: recorded on the caller's / the context's stream
     // the reference's per-iteration "avg change" lines (variational_mt.cpp:404-405, 431-432): sfa_ctx_set_verbose; costs a host round trip per iteration
@@ -310,6 +311,16 @@ void epic_weights_device(sfa_ctx *ctx, int m, size_t list_max, float coef, const
 struct Geo;
 constexpr int kEpicSaliencyPlanes = 15, kEpicSaliencyOut = 9;
 void epic_saliency_device(sfa_ctx *ctx, const Geo &g, float *planes, float sigma_image, float sigma_matrix);
+// k_ef_edge_costs (epic_filter.hip): run [ns][cpl], the edge maps as the epic() calls so far left them, advanced by rJ additions of euc; cost [ns][rJ][cpl], the
+// map each of the rJ calls reads.  cpl: a multiple of 4, at least gpl; both bases 16-byte aligned
+int epic_edge_costs_device(sfa_ctx *ctx, int ns, int rJ, size_t cpl, int gpl, float euc, float *run, float *cost);
+// sfa_epic_batch's chain (epic_batch.hip) for n images whose inputs are in device memory already.  cost[i]: w * h packed, euc added, read in place;
+// matches[i]: nm[i] rows of x1 y1 x2 y2, copied before the chain touches them; sal[i]: the image's saliency plane at dev_pitch(w) (read where
+// p->saliency_th != 0; images may share one); fx[i], fy[i]: w * h packed, written by copies on the stream once image i's sub-batch has finished.  rc,
+// counts, status and workspace_bytes as sfa_epic_batch has them; sub-batches, their re-runs and the compact search likewise.  Waits for the stream
+struct EpicChainDev { const float *const *cost; const float *const *matches; const int *nm; const float *const *sal; float *const *fx; float *const *fy; };
+int epic_chain_device(sfa_ctx *ctx, const char *fn, int n, int w, int h, const sfa_epic_params *p, const EpicChainDev &io, int *rc, int (*counts)[3],
+                      size_t workspace_bytes, int *status);
 
 // ---------------------------------------------------------------------------------------------------
 // kernel launchers (kernels.hip).  All planes are device pointers of batch element 0; element b lives

@@ -8,6 +8,9 @@
 // Segment s of a run comes out with the bits of the staged calls on that segment alone: the same kernels over the same planes, blockIdx.y = s.
 // The device entry points describe their arguments as views and leave every check of them to check_view / check_disjoint (api.hip on dev_view.h).
 #include <algorithm>
+#include <cmath>
+#include <memory>
+#include <vector>
 
 #include "sfa_device.h"
 
@@ -74,7 +77,8 @@ __global__ void __launch_bounds__(kTrThreads) k_track_pack_frames(const float *_
 
 // per grid pixel of segment blockIdx.y: best = the rate of the lowest fp32 energy, ties to the lower rate, 255 for none; occluded[k] = popcount of rate k's bits
 // (the host loop of the accumulate program).  E, O: [n][K][gpl]; best: [n][gpl]; occluded: [K][cap][gpl]
-__global__ void __launch_bounds__(kTrThreads) k_track_best(const double *__restrict__ E, const unsigned long long *__restrict__ O, int K, int gpl, int cap,
+// On a fill job E and O hold S = 2 K slots per segment and rate k sits in slot k * step, step = 2 (a plain job: S = K, step = 1)
+__global__ void __launch_bounds__(kTrThreads) k_track_best(const double *__restrict__ E, const unsigned long long *__restrict__ O, int K, int S, int step, int gpl, int cap,
                                                            unsigned char *__restrict__ best, unsigned char *__restrict__ occluded) {
     const int i = blockIdx.x * kTrThreads + threadIdx.x;
     if (i >= gpl) return;
@@ -82,7 +86,7 @@ __global__ void __launch_bounds__(kTrThreads) k_track_best(const double *__restr
     float be = __int_as_float(0x7f800000);
     int b = 255;
     for (int k = 0; k < K; k++) {
-        const size_t o = ((size_t)s * K + k) * gpl + i;
+        const size_t o = ((size_t)s * S + (size_t)k * step) * gpl + i;
         const float e = (float)E[o];                                            // an fp32 sum stored in a double: exact
         if (e < be) { be = e; b = k; }                                          // strict: ties keep the lower rate
         occluded[((size_t)k * cap + s) * gpl + i] = (unsigned char)__popcll(O[o]);
@@ -138,13 +142,25 @@ inline unsigned blocks_of(size_t total) { return (unsigned)((total + kTrThreads 
 
 using namespace sfa;
 
+// Everything below is launch orchestration: argument checks, layout arithmetic, copies and launches, a few microseconds per call beside milliseconds of
+// kernels.  It is compiled for size, so that the release build stays under the share of the full build tests/test_abi.py holds it to.
+#pragma clang attribute push(__attribute__((minsize)), apply_to = function)
+
 // Every plane of the job inside one allocation; this struct is the only statement of the list (sfa_track_job_bytes walks it without a device)
 struct TrackPlanes {
     struct Rate { size_t fw, bw, mask, acc_u, acc_v, tracked; } rate[kTrMaxK];
     size_t occluded, stage, occ_stage, frames, der, rec, wU, wV, wocc, jc, oc, ep, E, O, best;
     size_t aU, aV, weight, nl, lab, theta, P, M, xcur, xbest, slot, fu, fv, out_occ, seg_energy, seg_bound, seg_iters;
+    // a fill job only: the saliency's workspace of one start_jet (15 planes at the device pitch), sal [n][plp], edges (as uploaded) and run_cost (the map
+    // as the calls so far left it) [n][cpl], cost [n][rJmax][cpl], full [K][n], the regions' T, P, S [n][gpl] and mask, kept and count [n], the sample
+    // positions, block_count, matches [n][rJmax][nx ny][4], fx, fy [n][rJmax][gpl], inf [gpl] doubles of +Inf; per rate the fill-in's trajectories [n][rJ][gpl] and tracked [n][gpl]
+    size_t lab_stage, sal, edges, run_cost, cost, full, cT, cP, cS, mask, kept, count, xs, ys, block_count, matches, fx, fy, inf;
+    struct Fill { size_t u, v, tracked; } fill[kTrMaxK];
     size_t total;
 };
+
+// what a fill job derives from its parameters besides the planes: the sample positions, the longest rate, the planes' strides
+struct FillGeo { std::unique_ptr<int[]> xs, ys; int nx = 0, ny = 0, rJmax = 0, pitch = 0; size_t cpl = 0, plp = 0; };
 
 struct sfa_track_job {
     sfa_ctx *ctx = nullptr;
@@ -156,6 +172,20 @@ struct sfa_track_job {
     DevMem mem;
     hipEvent_t ev[10] = {};             // [9]: after the smoothness weight, before the fusion's clears
     bool timed = false, timed_fuse = false;
+    bool fill = false;                  // made by sfa_track_job_create_fill
+    sfa_track_fill_params fp{};
+    FillGeo fg;
+    std::unique_ptr<int[]> full, stats; // [K][n] r_Jets[r]; [K][n][3] kept_pixels, matches, filled of the last run
+    std::unique_ptr<double[]> inf;      // [gpl] +Inf, the source of at.inf
+    // the interpolation's images of one rate, n * rJmax entries each: EpicChainDev's arrays, their counts, start_jets and steps, rc and status
+    std::unique_ptr<const float *[]> c_in;   // cost, matches, sal
+    std::unique_ptr<float *[]> c_out;        // fx, fy
+    std::unique_ptr<int[]> c_int;            // nm, start_jet, step, rc, status, then kept and count [n]
+    int chain_runs[2] = {};             // the last run's interpolation sub-batches over all rates: completed, cut short and run again
+    hipEvent_t fev[kTrMaxK][5] = {};    // per rate: before the regions, after the matches, the edge costs, the chain, the trajectories
+    hipEvent_t ev_energy = nullptr;     // a fill job: after the last rate's fill-in, where the energies begin
+    int slots() const { return fill ? 2 * p.K : p.K; }
+    int step() const { return fill ? 2 : 1; }
     template <class T> T *ptr(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(mem.p) + off); }
 };
 
@@ -194,11 +224,37 @@ static int track_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, 
     return SFA_OK;
 }
 
-static void track_layout(const sfa_track_params &p, int gw, int gh, const bool *identity, int NN, TrackPlanes *out) {
+// the checks of a fill job beyond track_check's, by the name of the argument, and what the layout needs of it
+static int fill_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, const sfa_track_fill_params *f, int gw, int gh, FillGeo *g) {
+    if (!f) REFUSE("%s: fill is null", fn);
+    if (p->K > kTrMaxK / 2) REFUSE("%s: K = %d (a fill job fuses 2 K slots: at most %d rates)", fn, p->K, kTrMaxK / 2);
+    if (f->epic.nn < 1) REFUSE("%s: epic.nn = %d (at least one neighbour)", fn, f->epic.nn);
+    if (f->epic.pref_nn < 0) REFUSE("%s: epic.pref_nn = %d (0: no consistency filter, else its neighbours)", fn, f->epic.pref_nn);
+    if (f->epic.method != 0 && f->epic.method != 1) REFUSE("%s: epic.method = %d (0: locally-weighted affine, 1: Nadaraya-Watson)", fn, f->epic.method);
+    if (!std::isfinite(f->epic_skip) || f->epic_skip < 1) REFUSE("%s: epic_skip = %g (finite, at least 1)", fn, (double)f->epic_skip);
+    if (f->min_size < 1) REFUSE("%s: min_size = %d (>= 1)", fn, f->min_size);
+    if (f->epic.saliency_th != 0 && (gw <= 8 || gh <= 8))
+        REFUSE("%s: gw x gh = %d x %d with epic.saliency_th != 0 (the saliency's Gaussian of sigma 1.0 needs more than 8 columns and rows)", fn, gw, gh);
+    SFA_TRY(epic_nn_check_sizes(ctx, fn, gw, gh));
+    if (((size_t)gw * gh * 4 * p->K * p->K + kTrThreads - 1) / kTrThreads > 0x7fffffffull) REFUSE("%s: grid too large for 2 K slots", fn);
+    g->xs.reset(new int[gw]()); g->ys.reset(new int[gh]());
+    if (sfa_fill_samples(gw, f->epic_skip, g->xs.get(), &g->nx) != SFA_OK || sfa_fill_samples(gh, f->epic_skip, g->ys.get(), &g->ny) != SFA_OK)
+        REFUSE("%s: epic_skip: %s", fn, sfa_last_error(nullptr));
+    g->rJmax = 0;
+    for (int r = 0; r < p->K; r++) g->rJmax = std::max(g->rJmax, p->r_Jets[r]);
+    g->pitch = dev_pitch(gw);
+    g->plp = (size_t)g->pitch * gh;
+    g->cpl = ((size_t)gw * gh + 3) / 4 * 4;
+    return SFA_OK;
+}
+
+static void track_layout(const sfa_track_params &p, int gw, int gh, const bool *identity, int NN, const sfa_track_fill_params *fill, const FillGeo *fg,
+                         TrackPlanes *out) {
     TrackPlanes &a = *out;
     size_t top = 0;
     auto take = [&](size_t bytes) { const size_t o = top; top += (bytes + 255) / 256 * 256; return o; };
     const size_t n = p.n, K = p.K, J = p.Jets, pl = (size_t)p.w * p.h, gpl = (size_t)gw * gh;
+    const size_t S = fill ? 2 * K : K;                                          // the fusion's slots
     size_t stage = 0, occ_stage = 0;
     for (int r = 0; r < p.K; r++) {
         const size_t rJ = p.r_Jets[r], tap = identity[r] ? 8 : 16, spl = identity[r] ? pl : (size_t)p.source[r].cw * p.source[r].ch;
@@ -219,13 +275,28 @@ static void track_layout(const sfa_track_params &p, int gw, int gh, const bool *
     a.rec = take(n * (J + 1) * pl * 48);
     a.wU = take(n * J * gpl * 8); a.wV = take(n * J * gpl * 8); a.wocc = take(n * gpl * 8);
     a.jc = take(n * gpl * 4); a.oc = take(n * gpl * 4); a.ep = take(n * gpl * NN * 8);
-    a.E = take(n * K * gpl * 8); a.O = take(n * K * gpl * 8); a.best = take(n * gpl);
+    a.E = take(n * S * gpl * 8); a.O = take(n * S * gpl * 8); a.best = take(n * gpl);
     if (p.do_fuse) {
-        a.aU = take(n * K * J * gpl * 8); a.aV = take(n * K * J * gpl * 8); a.weight = take(n * pl * 4);
-        a.nl = take(n * gpl); a.lab = take(n * gpl * 16); a.theta = take(n * gpl * 16 * 8); a.P = take(n * 2 * gpl * K * K * 8);
+        a.aU = take(n * S * J * gpl * 8); a.aV = take(n * S * J * gpl * 8); a.weight = take(n * pl * 4);
+        a.nl = take(n * gpl); a.lab = take(n * gpl * 16); a.theta = take(n * gpl * 16 * 8); a.P = take(n * 2 * gpl * S * S * 8);
         a.M = take(n * gpl * 4 * 16 * 8); a.xcur = take(n * gpl); a.xbest = take(n * gpl);
         a.slot = take(n * gpl * 4); a.fu = take(n * gpl * 8); a.fv = take(n * gpl * 8); a.out_occ = take(n * gpl);
         a.seg_energy = take(n * 8); a.seg_bound = take(n * 8); a.seg_iters = take(n * 4);
+    }
+    if (fill) {
+        const size_t rJm = fg->rJmax, samples = (size_t)fg->nx * fg->ny;
+        a.lab_stage = fill->epic.saliency_th != 0 ? take((size_t)kEpicSaliencyPlanes * fg->plp * 4) : 0;
+        a.sal = fill->epic.saliency_th != 0 ? take(n * fg->plp * 4) : 0;
+        a.edges = take(n * fg->cpl * 4); a.run_cost = take(n * fg->cpl * 4); a.cost = take(n * rJm * fg->cpl * 4);
+        a.full = take(K * n * 4);
+        a.cT = take(n * gpl * 4); a.cP = take(n * gpl * 4); a.cS = take(n * gpl * 4); a.mask = take(n * gpl); a.kept = take(n * 4); a.count = take(n * 4);
+        a.xs = take((size_t)gw * 4); a.ys = take((size_t)gh * 4);
+        a.block_count = take(n * std::max<size_t>(fill_matches_blocks(fg->nx, fg->ny), 1) * 4);
+        a.matches = take(n * rJm * std::max<size_t>(samples, 1) * 16);
+        a.fx = take(n * rJm * gpl * 4); a.fy = take(n * rJm * gpl * 4); a.inf = take(gpl * 8);
+        for (int r = 0; r < p.K; r++) {
+            a.fill[r].u = take(n * p.r_Jets[r] * gpl * 8); a.fill[r].v = take(n * p.r_Jets[r] * gpl * 8); a.fill[r].tracked = take(n * gpl * 4);
+        }
     }
     a.total = top;
 }
@@ -244,36 +315,94 @@ void sfa_track_params_default(sfa_track_params *p) {
     for (int r = 0; r < kTrMaxK; r++) { p->r_Jets[r] = 1; p->weight[r] = (float)r; }   // weight_jet_estimation[r] = r where none is given
 }
 
-int sfa_track_job_bytes(const sfa_track_params *p, size_t *bytes) {
+void sfa_track_fill_params_default(sfa_track_fill_params *fill) {
+    if (!fill) return;
+    *fill = sfa_track_fill_params{};
+    fill->epic_skip = 2.0f;                                                     // acc_epic_skip (:651)
+    fill->min_size = 100;                                                       // removeSmallSegments(r_consistent, 0.1, 100) (:1265)
+    // epic_params_default (epic.cpp:127-136), then dense_tracking.cpp:652-656
+    fill->epic.method = 0; fill->epic.saliency_th = 0.045f; fill->epic.pref_nn = 25; fill->epic.pref_th = 5.0f; fill->epic.nn = 160;
+    fill->epic.coef_kernel = 1.1f; fill->epic.euc = 0.001f;
+}
+
+// one-line forms of the stream calls the fill-in makes many of
+static int copy_on(sfa_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+    SFA_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
+    return SFA_OK;
+}
+static int zero_on(sfa_ctx *ctx, void *dst, size_t bytes) {
+    SFA_HIP(ctx, hipMemsetAsync(dst, 0, bytes, ctx->stream));
+    return SFA_OK;
+}
+static int mark(sfa_ctx *ctx, hipEvent_t e) {
+    SFA_HIP(ctx, hipEventRecord(e, ctx->stream));
+    return SFA_OK;
+}
+
+// fill: null for a plain job
+static int track_bytes(const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, size_t *bytes) {
     sfa_ctx *ctx = nullptr;
-    if (!bytes) REFUSE("%s: bytes is null", __func__);
+    if (!bytes) REFUSE("%s: bytes is null", fn);
     int gw, gh;
     bool identity[kTrMaxK];
     EnergyPlan plan[kTrMaxK];
-    SFA_TRY(track_check(ctx, __func__, p, &gw, &gh, identity, plan));
+    SFA_TRY(track_check(ctx, fn, p, &gw, &gh, identity, plan));
+    FillGeo fg;
+    if (with_fill) SFA_TRY(fill_check(ctx, fn, p, fill, gw, gh, &fg));
     TrackPlanes at{};
-    track_layout(*p, gw, gh, identity, plan[0].NN, &at);
+    track_layout(*p, gw, gh, identity, plan[0].NN, with_fill ? fill : nullptr, &fg, &at);
     *bytes = at.total;
     return SFA_OK;
 }
 
-int sfa_track_job_create(sfa_ctx *ctx, const sfa_track_params *p, sfa_track_job **out) {
-    if (!ctx || !out) REFUSE("%s: ctx or job is null", __func__);
+int sfa_track_job_bytes(const sfa_track_params *p, size_t *bytes) { return track_bytes(__func__, p, nullptr, false, bytes); }
+int sfa_track_job_bytes_fill(const sfa_track_params *p, const sfa_track_fill_params *fill, size_t *bytes) { return track_bytes(__func__, p, fill, true, bytes); }
+
+static int track_create(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, sfa_track_job **out) {
+    if (!ctx || !out) REFUSE("%s: ctx or job is null", fn);
     *out = nullptr;
     sfa_track_job *j = new sfa_track_job;
     struct Guard { sfa_track_job *j; ~Guard() { if (j) sfa_track_job_destroy(j); } } guard{j};
     j->ctx = ctx;
-    SFA_TRY(track_check(ctx, __func__, p, &j->gw, &j->gh, j->identity, j->plan));
+    SFA_TRY(track_check(ctx, fn, p, &j->gw, &j->gh, j->identity, j->plan));
+    if (with_fill) {
+        SFA_TRY(fill_check(ctx, fn, p, fill, j->gw, j->gh, &j->fg));
+        j->fill = true;
+        j->fp = *fill;
+    }
     j->p = *p;
     j->p.energy.skip = j->p.fuse.skip = p->skip;
-    track_layout(j->p, j->gw, j->gh, j->identity, j->plan[0].NN, &j->at);
+    track_layout(j->p, j->gw, j->gh, j->identity, j->plan[0].NN, with_fill ? &j->fp : nullptr, &j->fg, &j->at);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     SFA_TRY(j->mem.alloc(ctx, j->at.total));
     SFA_HIP(ctx, hipMemsetAsync(j->mem.p, 0, j->at.total, ctx->stream));        // a run before an upload reads zeros, not another job's planes
     for (auto &e : j->ev) SFA_HIP(ctx, hipEventCreate(&e));
+    if (with_fill) {
+        for (int r = 0; r < p->K; r++)
+            for (auto &e : j->fev[r]) SFA_HIP(ctx, hipEventCreate(&e));
+        SFA_HIP(ctx, hipEventCreate(&j->ev_energy));
+        const size_t rates = (size_t)p->K * p->n, images = (size_t)p->n * j->fg.rJmax, gpl = (size_t)j->gw * j->gh;
+        j->full.reset(new int[rates]);
+        for (size_t k = 0; k < rates; k++) j->full[k] = p->r_Jets[k / p->n];
+        j->stats.reset(new int[3 * rates]());
+        j->c_in.reset(new const float *[3 * images]()); j->c_out.reset(new float *[2 * images]()); j->c_int.reset(new int[5 * images + 2 * (size_t)p->n]());
+        j->inf.reset(new double[gpl]);
+        for (size_t k = 0; k < gpl; k++) j->inf[k] = (double)__builtin_inff();
+        SFA_TRY(copy_on(ctx, j->ptr<double>(j->at.inf), j->inf.get(), gpl * 8, hipMemcpyHostToDevice));
+        // (the host arrays live as long as the job, and the wait below is before anything can change them)
+        SFA_TRY(copy_on(ctx, j->ptr<int>(j->at.full), j->full.get(), rates * 4, hipMemcpyHostToDevice));
+        SFA_TRY(copy_on(ctx, j->ptr<int>(j->at.xs), j->fg.xs.get(), (size_t)j->gw * 4, hipMemcpyHostToDevice));
+        SFA_TRY(copy_on(ctx, j->ptr<int>(j->at.ys), j->fg.ys.get(), (size_t)j->gh * 4, hipMemcpyHostToDevice));
+        SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     guard.j = nullptr;
     *out = j;
     return SFA_OK;
+}
+
+int sfa_track_job_create(sfa_ctx *ctx, const sfa_track_params *p, sfa_track_job **out) { return track_create(ctx, __func__, p, nullptr, false, out); }
+int sfa_track_job_create_fill(sfa_ctx *ctx, const sfa_track_params *p, const sfa_track_fill_params *fill, sfa_track_job **out) {
+    return track_create(ctx, __func__, p, fill, true, out);
 }
 
 void sfa_track_job_destroy(sfa_track_job *job) {
@@ -281,6 +410,10 @@ void sfa_track_job_destroy(sfa_track_job *job) {
     if (job->ctx && job->ctx->stream) (void)hipStreamSynchronize(job->ctx->stream);
     for (auto &e : job->ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto &rate : job->fev)
+        for (auto &e : rate)
+            if (e) (void)hipEventDestroy(e);
+    if (job->ev_energy) (void)hipEventDestroy(job->ev_energy);
     delete job;
 }
 
@@ -423,6 +556,84 @@ int sfa_track_job_upload_frames_device(sfa_track_job *job, int s0, int ns, const
     return SFA_OK;
 }
 
+// The fill-in of every rate of segments 0 .. ns-1, between the accumulation and the energies (the header's description).  It leaves the trajectories in the
+// rates' fill planes and {kept_pixels, matches, filled} in job->stats
+static int track_run_fill(sfa_track_job *job, int ns) {
+    TRACK_JOB(job);
+    const TrackPlanes &at = job->at;
+    const FillGeo &g = job->fg;
+    const sfa_track_fill_params &fp = job->fp;
+    hipStream_t st = ctx->stream;
+    const int gw = job->gw, gh = job->gh, n = p.n;
+    const size_t samples = (size_t)g.nx * g.ny;
+    float *run_cost = job->ptr<float>(at.run_cost), *cost = job->ptr<float>(at.cost), *matches = job->ptr<float>(at.matches);
+    float *fx = job->ptr<float>(at.fx), *fy = job->ptr<float>(at.fy);
+    // the running maps start from the maps as uploaded: a run leaves them advanced by all its calls
+    SFA_TRY(copy_on(ctx, run_cost, job->ptr<float>(at.edges), (size_t)ns * g.cpl * 4, hipMemcpyDeviceToDevice));
+    const size_t images = (size_t)n * g.rJmax;
+    const float **c_cost = job->c_in.get(), **c_matches = c_cost + images, **c_sal = c_matches + images;
+    float **c_fx = job->c_out.get(), **c_fy = c_fx + images;
+    int *c_nm = job->c_int.get(), *seg_of = c_nm + images, *step_of = seg_of + images, *rc = step_of + images, *status = rc + images, *kept = status + images,
+        *count = kept + n;
+    job->chain_runs[0] = job->chain_runs[1] = 0;
+    for (int r = 0; r < p.K; r++) {
+        const int rJ = p.r_Jets[r];
+        hipEvent_t *ev = job->fev[r];
+        int *stats = job->stats.get() + (size_t)r * n * 3;
+        const double *acc_u = job->ptr<double>(at.rate[r].acc_u), *acc_v = job->ptr<double>(at.rate[r].acc_v);
+        // ---- r_consistent after removeSmallSegments, the matches of every step; the one host read this stage adds
+        SFA_TRY(mark(ctx, ev[0]));
+        SFA_TRY(consistent_regions_device(ctx, ns, gw, gh, job->ptr<int>(at.rate[r].tracked), job->ptr<int>(at.full) + (size_t)r * n, fp.min_size, job->ptr<int>(at.cT),
+                                          job->ptr<int>(at.cP), job->ptr<int>(at.cS), job->ptr<unsigned char>(at.mask), job->ptr<int>(at.kept)));
+        if (samples)
+            SFA_TRY(fill_matches_device(ctx, ns, rJ, gw, gh, acc_u, acc_v, job->ptr<unsigned char>(at.mask), job->ptr<int>(at.xs), g.nx, job->ptr<int>(at.ys), g.ny,
+                                        p.skip + 1, job->ptr<int>(at.block_count), matches, job->ptr<int>(at.count)));
+        SFA_TRY(copy_on(ctx, kept, job->ptr<int>(at.kept), (size_t)ns * 4, hipMemcpyDeviceToHost));
+        if (samples) SFA_TRY(copy_on(ctx, count, job->ptr<int>(at.count), (size_t)ns * 4, hipMemcpyDeviceToHost));
+        SFA_TRY(mark(ctx, ev[1]));
+        SFA_HIP(ctx, hipStreamSynchronize(st));
+        if (!samples) std::fill(count, count + ns, 0);                 // no sample on the grid: no match
+        // ---- the edge costs of the rate's steps, for every segment: the calls count whether or not a rate is filled
+        SFA_TRY(epic_edge_costs_device(ctx, ns, rJ, g.cpl, (int)gpl, fp.epic.euc, run_cost, cost));
+        SFA_TRY(mark(ctx, ev[2]));
+        // ---- the interpolation of the images of every segment with a match, segment-major
+        int m = 0;
+        for (int s = 0; s < ns; s++) {
+            stats[3 * s] = kept[s]; stats[3 * s + 1] = count[s]; stats[3 * s + 2] = count[s] > 0;
+            for (int j = 0; j < rJ && count[s] > 0; j++, m++) {
+                const size_t k = (size_t)s * rJ + j;
+                c_cost[m] = cost + k * g.cpl; c_matches[m] = matches + k * samples * 4; c_nm[m] = count[s];
+                c_sal[m] = fp.epic.saliency_th != 0 ? job->ptr<float>(at.sal) + (size_t)s * g.plp : nullptr;
+                c_fx[m] = fx + k * gpl; c_fy[m] = fy + k * gpl;
+                seg_of[m] = s; step_of[m] = j;
+            }
+        }
+        if (m) {
+            const EpicChainDev io{c_cost, c_matches, c_nm, c_sal, c_fx, c_fy};
+            SFA_TRY(epic_chain_device(ctx, "sfa_track_job_run", m, gw, gh, &fp.epic, io, rc, nullptr, fp.workspace_bytes, status));
+            for (int k = 0; k < 2; k++) job->chain_runs[k] += ctx->epic_chain_runs[k];
+            for (int k = 0; k < m; k++) {
+                if (status[k])
+                    REFUSE("sfa_track_job_run: the fill-in image of start_jet %d, rate %d, step %d (%d matches) does not fit the interpolation's workspace even alone",
+                           seg_of[k], r, step_of[k], c_nm[k]);
+                if (rc[k] > 0) stats[3 * seg_of[k] + 2] = 0;                     // a step without a usable match: no fill-in hypothesis for the rate
+            }
+        }
+        SFA_TRY(mark(ctx, ev[3]));
+        // ---- the planes as trajectories; a segment that is not filled gets zeros (its slot is emptied after the energies)
+        for (int s = 0; s < ns; s++) {
+            if (stats[3 * s + 2]) continue;
+            SFA_TRY(zero_on(ctx, fx + (size_t)s * rJ * gpl, (size_t)rJ * gpl * 4));
+            SFA_TRY(zero_on(ctx, fy + (size_t)s * rJ * gpl, (size_t)rJ * gpl * 4));
+        }
+        SFA_TRY(fill_trajectories_device(ctx, ns, rJ, gw, gh, gw, fx, fy, p.skip + 1, job->ptr<double>(at.fill[r].u), job->ptr<double>(at.fill[r].v),
+                                         job->ptr<int>(at.fill[r].tracked)));
+        SFA_TRY(mark(ctx, ev[4]));
+    }
+    SFA_TRY(mark(ctx, job->ev_energy));
+    return SFA_OK;
+}
+
 int sfa_track_job_run(sfa_track_job *job, int ns) {
     TRACK_JOB(job);
     if (ns < 1 || ns > p.n) REFUSE("%s: ns = %d (1 <= ns <= n = %d, the job's start_jets)", __func__, ns, p.n);
@@ -439,6 +650,8 @@ int sfa_track_job_run(sfa_track_job *job, int ns) {
                                   job->ptr<void>(at.rate[r].bw), p.use_occlusions ? job->ptr<unsigned char>(at.rate[r].mask) : nullptr, p.epsilon, p.discard, 1,
                                   job->ptr<double>(at.rate[r].acc_u), job->ptr<double>(at.rate[r].acc_v), job->ptr<int>(at.rate[r].tracked)));
     SFA_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+    if (job->fill) SFA_TRY(track_run_fill(job, ns));
+    const int S = job->slots(), step = job->step();                            // rate r's accumulated hypothesis is slot r * step, its fill-in the next
     EnergyWork wk;
     wk.U = job->ptr<double>(at.wU); wk.V = job->ptr<double>(at.wV); wk.occ = job->ptr<unsigned long long>(at.wocc);
     wk.jc = job->ptr<float>(at.jc); wk.oc = job->ptr<float>(at.oc); wk.ep = job->ptr<double>(at.ep);
@@ -448,12 +661,27 @@ int sfa_track_job_run(sfa_track_job *job, int ns) {
         const bool flows = r >= mf;                                             // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
         SFA_TRY(energies_device(ctx, job->plan[r], ns, job->ptr<double>(at.rate[r].acc_u), job->ptr<double>(at.rate[r].acc_v), job->ptr<int>(at.rate[r].tracked),
                                 job->ptr<void>(at.rec), job->identity[mf], flows ? job->ptr<void>(at.rate[mf].fw) : nullptr,
-                                flows ? job->ptr<void>(at.rate[mf].bw) : nullptr, wk, E + (size_t)r * gpl, O + (size_t)r * gpl, (size_t)K * gpl,
-                                p.do_fuse ? job->ptr<double>(at.aU) + (size_t)r * J * gpl : nullptr, p.do_fuse ? job->ptr<double>(at.aV) + (size_t)r * J * gpl : nullptr,
-                                (size_t)K * J * gpl));
+                                flows ? job->ptr<void>(at.rate[mf].bw) : nullptr, wk, E + (size_t)r * step * gpl, O + (size_t)r * step * gpl, (size_t)S * gpl,
+                                p.do_fuse ? job->ptr<double>(at.aU) + (size_t)r * step * J * gpl : nullptr,
+                                p.do_fuse ? job->ptr<double>(at.aV) + (size_t)r * step * J * gpl : nullptr, (size_t)S * J * gpl));
+        if (!job->fill) continue;
+        const size_t slot = 2 * (size_t)r + 1;                                  // the fill-in: the rate's plan and weight, the same flows
+        double *aU = p.do_fuse ? job->ptr<double>(at.aU) + slot * J * gpl : nullptr, *aV = p.do_fuse ? job->ptr<double>(at.aV) + slot * J * gpl : nullptr;
+        SFA_TRY(energies_device(ctx, job->plan[r], ns, job->ptr<double>(at.fill[r].u), job->ptr<double>(at.fill[r].v), job->ptr<int>(at.fill[r].tracked),
+                                job->ptr<void>(at.rec), job->identity[mf], flows ? job->ptr<void>(at.rate[mf].fw) : nullptr,
+                                flows ? job->ptr<void>(at.rate[mf].bw) : nullptr, wk, E + slot * gpl, O + slot * gpl, (size_t)S * gpl, aU, aV, (size_t)S * J * gpl));
+        for (int s = 0; s < ns; s++) {
+            if (job->stats[((size_t)r * p.n + s) * 3 + 2]) continue;
+            const size_t so = (size_t)s * S * gpl, sa = (size_t)s * S * J * gpl;
+            // the slot of a hypothesis that does not exist: energy +Inf, occlusion word 0, adapted flows 0
+            SFA_TRY(copy_on(ctx, E + slot * gpl + so, job->ptr<double>(at.inf), gpl * 8, hipMemcpyDeviceToDevice));
+            SFA_TRY(zero_on(ctx, O + slot * gpl + so, gpl * 8));
+            if (aU) SFA_TRY(zero_on(ctx, aU + sa, (size_t)J * gpl * 8));
+            if (aV) SFA_TRY(zero_on(ctx, aV + sa, (size_t)J * gpl * 8));
+        }
     }
     const dim3 pix(blocks_of(gpl), (unsigned)ns);
-    hipLaunchKernelGGL(k_track_best, pix, dim3(kTrThreads), 0, ctx->stream, E, O, K, (int)gpl, p.n, job->ptr<unsigned char>(at.best),
+    hipLaunchKernelGGL(k_track_best, pix, dim3(kTrThreads), 0, ctx->stream, E, O, K, S, step, (int)gpl, p.n, job->ptr<unsigned char>(at.best),
                        job->ptr<unsigned char>(at.occluded));
     SFA_HIP(ctx, hipGetLastError());
     SFA_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
@@ -471,7 +699,7 @@ int sfa_track_job_run(sfa_track_job *job, int ns) {
     f.M = job->ptr<double>(at.M); f.xcur = job->ptr<unsigned char>(at.xcur); f.xbest = job->ptr<unsigned char>(at.xbest);
     f.slot = job->ptr<int>(at.slot); f.fu = job->ptr<double>(at.fu); f.fv = job->ptr<double>(at.fv); f.out_occ = job->ptr<unsigned char>(at.out_occ);
     f.seg_energy = job->ptr<double>(at.seg_energy); f.seg_bound = job->ptr<double>(at.seg_bound); f.seg_iters = job->ptr<int>(at.seg_iters);
-    SFA_TRY(fuse_device(ctx, &p.fuse, ns, K, J, p.w, p.h, job->gw, job->gh, f, ev + 4));
+    SFA_TRY(fuse_device(ctx, &p.fuse, ns, S, J, p.w, p.h, job->gw, job->gh, f, ev + 4));
     job->timed_fuse = true;
     return SFA_OK;
 }
@@ -482,7 +710,7 @@ int sfa_track_job_download_rate(sfa_track_job *job, int s, int r, double *acc_u_
     SFA_TRY(track_range(ctx, __func__, p, s, 1, r));
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const TrackPlanes::Rate &a = job->at.rate[r];
-    const size_t last = ((size_t)s * p.r_Jets[r] + (p.r_Jets[r] - 1)) * gpl, sk = ((size_t)s * p.K + r) * gpl;
+    const size_t last = ((size_t)s * p.r_Jets[r] + (p.r_Jets[r] - 1)) * gpl, sk = ((size_t)s * job->slots() + (size_t)r * job->step()) * gpl;
     auto get = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
     SFA_HIP(ctx, get(acc_u_last, job->ptr<double>(a.acc_u) + last, gpl * 8));
     SFA_HIP(ctx, get(acc_v_last, job->ptr<double>(a.acc_v) + last, gpl * 8));
@@ -578,12 +806,12 @@ static int track_unpack_rate(sfa_track_job *job, const char *fn, int s0, int ns,
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const TrackPlanes &at = job->at;
     const TrackPlanes::Rate &a = at.rate[r];
-    const size_t rJ = p.r_Jets[r], last = ((size_t)s0 * rJ + (rJ - 1)) * gpl, sk = ((size_t)s0 * p.K + r) * gpl;
+    const size_t rJ = p.r_Jets[r], last = ((size_t)s0 * rJ + (rJ - 1)) * gpl, sk = ((size_t)s0 * job->slots() + (size_t)r * job->step()) * gpl;
     const unsigned char *from = best ? job->ptr<unsigned char>(at.best) + (size_t)s0 * gpl : job->ptr<unsigned char>(at.occluded) + ((size_t)r * p.n + s0) * gpl;
     const long long none[4] = {0, 0, 0, 0}, *st = acc_dev ? strides : none;
     hipLaunchKernelGGL(k_track_unpack_rate, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr<double>(a.acc_u) + last,
                        job->ptr<double>(a.acc_v) + last, rJ * gpl, job->ptr<int>(a.tracked) + (size_t)s0 * gpl, gpl, job->ptr<double>(at.E) + sk,
-                       job->ptr<unsigned long long>(at.O) + sk, (size_t)p.K * gpl, from, gpl, job->gw, (int)gpl, acc_dev, st[0], st[1], st[2], st[3], tracked_dev,
+                       job->ptr<unsigned long long>(at.O) + sk, (size_t)job->slots() * gpl, from, gpl, job->gw, (int)gpl, acc_dev, st[0], st[1], st[2], st[3], tracked_dev,
                        energy_dev, occ_bits_dev, bytes_dev);
     SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;
@@ -612,6 +840,112 @@ int sfa_track_job_stage_ms(sfa_track_job *job, float ms[8]) {
     for (int i = 0; i < 8; i++) ms[i] = 0;
     const int last = job->timed_fuse ? 8 : 3;
     for (int i = 0; i < last; i++)                                              // ms[3]: the weight kernel alone, without the fusion's clears behind it
-        SFA_HIP(ctx, hipEventElapsedTime(&ms[i], job->ev[i], job->ev[i == 3 ? 9 : i + 1]));
+        SFA_HIP(ctx, hipEventElapsedTime(&ms[i], i == 2 && job->fill ? job->ev_energy : job->ev[i], job->ev[i == 3 ? 9 : i + 1]));
     return SFA_OK;
 }
+
+// ---- a fill job's own entry points ------------------------------------------------------------------------------------------------------------------------
+#define FILL_JOB(job) \
+    TRACK_JOB(job); \
+    if (!(job)->fill) REFUSE("%s: the job was not created by sfa_track_job_create_fill: it holds no fill-in", __func__); \
+    const FillGeo &g = (job)->fg; \
+    const bool saliency = (job)->fp.epic.saliency_th != 0; \
+    (void)g; (void)saliency
+
+// the saliency of the Lab image in the workspace's first three planes -> segment s's plane
+static int track_saliency(sfa_track_job *job, int s) {
+    sfa_ctx *ctx = job->ctx;
+    const FillGeo &g = job->fg;
+    float *stage = job->ptr<float>(job->at.lab_stage);
+    const Geo geo{job->gw, job->gh, g.pitch, (long)g.plp, (long)(kEpicSaliencyPlanes * g.plp), 1, WMask::first(1), nullptr};
+    epic_saliency_device(ctx, geo, stage, 0.8f, 1.0f);                          // epic()'s saliency(im, 0.8f, 1.0f)
+    SFA_HIP(ctx, hipGetLastError());
+    SFA_TRY(copy_on(ctx, job->ptr<float>(job->at.sal) + (size_t)s * g.plp, stage + (size_t)kEpicSaliencyOut * g.plp, g.plp * 4, hipMemcpyDeviceToDevice));
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_fill(sfa_track_job *job, int s, const float *lab, int lab_stride, const float *edges) {
+    FILL_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, 0));
+    if (!edges) REFUSE("%s: edges is null", __func__);
+    if (saliency && !lab) REFUSE("%s: lab is null (epic.saliency_th != 0: the saliency filter reads the Lab image)", __func__);
+    if (saliency && lab_stride < job->gw) REFUSE("%s: lab_stride = %d < gw = %d", __func__, lab_stride, job->gw);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    if (saliency) {
+        for (int c = 0; c < 3; c++)
+            SFA_TRY(upload_plane(ctx, job->ptr<float>(job->at.lab_stage) + (size_t)c * g.plp, g.pitch, lab + (size_t)c * job->gh * lab_stride, lab_stride, job->gw, job->gh));
+        SFA_TRY(track_saliency(job, s));
+    }
+    SFA_TRY(copy_on(ctx, job->ptr<float>(job->at.edges) + (size_t)s * g.cpl, edges, gpl * 4, hipMemcpyHostToDevice));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // the caller's planes are free again
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_fill_device(sfa_track_job *job, int s0, int ns, const float *lab_dev, const long long lab_strides[4], const float *edges_dev,
+                                     const long long edge_strides[3]) {
+    FILL_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
+    if (saliency) SFA_TRY(check_view(ctx, __func__, View{"lab_dev", lab_dev, sizeof(float), 4, {ns, 3, job->gh, job->gw}, lab_strides}));
+    SFA_TRY(check_view(ctx, __func__, View{"edges_dev", edges_dev, sizeof(float), 3, {ns, job->gh, job->gw}, edge_strides}));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    for (int s = 0; saliency && s < ns; s++) {                                  // segment by segment through the one workspace, in stream order
+        // packed by the frames' kernel (one frame of three channels) into planes the saliency only uses as scratch, then row by row to the device pitch
+        const size_t total = 3 * gpl;
+        float *stage = job->ptr<float>(job->at.lab_stage), *packed = stage + 3 * g.plp;
+        hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, lab_dev + (long long)s * lab_strides[0], 0ll, 0ll, lab_strides[1],
+                           lab_strides[2], lab_strides[3], job->gw, job->gh, 1, packed, total);
+        SFA_HIP(ctx, hipGetLastError());
+        for (int c = 0; c < 3; c++)
+            SFA_HIP(ctx, hipMemcpy2DAsync(stage + (size_t)c * g.plp, (size_t)g.pitch * 4, packed + (size_t)c * gpl, (size_t)job->gw * 4, (size_t)job->gw * 4, job->gh,
+                                          hipMemcpyDeviceToDevice, ctx->stream));
+        SFA_TRY(track_saliency(job, s0 + s));
+    }
+    for (int s = 0; s < ns; s++) {                                              // the frames' kernel again: one frame, its first channel alone
+        hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(gpl)), dim3(kTrThreads), 0, ctx->stream, edges_dev + (long long)s * edge_strides[0], 0ll, 0ll, 0ll,
+                           edge_strides[1], edge_strides[2], job->gw, job->gh, 1, job->ptr<float>(job->at.edges) + (size_t)(s0 + s) * g.cpl, gpl);
+        SFA_HIP(ctx, hipGetLastError());
+    }
+    return SFA_OK;
+}
+
+int sfa_track_job_download_fill(sfa_track_job *job, int s, int r, double *fill_u, double *fill_v, double *energy, unsigned long long *occ_bits, int *stats) {
+    FILL_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, r));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t rJ = p.r_Jets[r], sk = ((size_t)s * job->slots() + 2 * (size_t)r + 1) * gpl;
+    auto get = [&](void *dst, const void *src, size_t bytes) { return dst ? copy_on(ctx, dst, src, bytes, hipMemcpyDeviceToHost) : (int)SFA_OK; };
+    SFA_TRY(get(fill_u, job->ptr<double>(job->at.fill[r].u) + (size_t)s * rJ * gpl, rJ * gpl * 8));
+    SFA_TRY(get(fill_v, job->ptr<double>(job->at.fill[r].v) + (size_t)s * rJ * gpl, rJ * gpl * 8));
+    SFA_TRY(get(energy, job->ptr<double>(job->at.E) + sk, gpl * 8));
+    SFA_TRY(get(occ_bits, job->ptr<unsigned long long>(job->at.O) + sk, gpl * 8));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats)
+        for (int k = 0; k < 3; k++) stats[k] = job->stats[((size_t)r * p.n + s) * 3 + k];
+    return SFA_OK;
+}
+
+int sfa_track_job_fill_info(sfa_track_job *job, int info[2]) {
+    FILL_JOB(job);
+    if (!info) REFUSE("%s: info is null", __func__);
+    if (!job->timed) REFUSE("%s: the job has not run", __func__);
+    info[0] = job->chain_runs[0]; info[1] = job->chain_runs[1];
+    return SFA_OK;
+}
+
+int sfa_track_job_fill_ms(sfa_track_job *job, float ms[4]) {
+    FILL_JOB(job);
+    if (!ms) REFUSE("%s: ms is null", __func__);
+    if (!job->timed) REFUSE("%s: the job has not run", __func__);
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 4; i++) ms[i] = 0;
+    for (int r = 0; r < p.K; r++)
+        for (int i = 0; i < 4; i++) {
+            float v = 0;
+            SFA_HIP(ctx, hipEventElapsedTime(&v, job->fev[r][i], job->fev[r][i + 1]));
+            ms[i] += v;
+        }
+    return SFA_OK;
+}
+
+#pragma clang attribute pop

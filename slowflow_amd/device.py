@@ -155,6 +155,7 @@ def _lib():
         L.sfa_track_job_upload_occlusions_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.sfa_track_job_download_rate_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
         L.sfa_track_job_download_best_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.sfa_track_job_upload_fill_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sfa_flow_magnitude_quantiles_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                           C.c_float, C.c_float, C.c_void_p]
         _bound = True
@@ -501,7 +502,14 @@ def track_job_download_best_device(job, best, s0=0):
     job.ctx._ck(_lib().sfa_track_job_download_best_device(job.h_, int(s0), v.shape[0], C.c_void_p(v.ptr)), "sfa_track_job_download_best_device")
 
 
-def track(ctx, params, flows, frames, *, occlusions=None, rates=False, stream=None):
+def track_job_upload_fill_device(job, lab, edges, s0=0):
+    ev = device_view(edges, name="edges", kinds=("f4",), shape=("ns", job.gh, job.gw))
+    lv = device_view(lab, name="lab", kinds=("f4",), shape=(ev.shape[0], 3, job.gh, job.gw)) if lab is not None else None
+    job.ctx._ck(_lib().sfa_track_job_upload_fill_device(job.h_, int(s0), ev.shape[0], C.c_void_p(lv.ptr) if lv else None, _LL4(*lv.strides) if lv else None,
+                                                        C.c_void_p(ev.ptr), _LL3(*ev.strides)), "sfa_track_job_upload_fill_device")
+
+
+def track(ctx, params, flows, frames, *, occlusions=None, rates=False, stream=None, fill=None, lab=None, edges=None):
     """dense_tracking's accumulation, energies and fusion of ns start_jets whose inputs live on the context's GPU.  params: sfa.track_params(...) with
     do_fuse 1, n >= ns; flows = [(fwd_r, bwd_r), ...], one pair of fp32 tensors [ns, r_Jets[r], 2, sh, sw] per rate; frames = an fp32 tensor
     [ns, Jets + 1, 3, h, w] of normalised frames; any strides with a positive column stride.  occlusions: with params.use_occlusions one tensor
@@ -510,7 +518,10 @@ def track(ctx, params, flows, frames, *, occlusions=None, rates=False, stream=No
     as new tensors on that device; with rates=True a fifth value, dict(rate=[one dict per rate of new tensors acc float64 [ns,2,gh,gw] (the last
     accumulated step), tracked int32, energy float64 (+Inf: no hypothesis), occ_bits uint64, occluded uint8 [ns,gh,gw]], best=uint8 [ns,gh,gw]): what
     TrackJob.download_rate and download_best give.  The work is ordered after what `stream` (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it afterwards; the call only enqueues (a job of new
-    parameters is created first, which waits).  The job stays on the context for the next call (ctx.close() frees it)."""
+    parameters is created first, which waits).  The job stays on the context for the next call (ctx.close() frees it).
+    fill: a sfa.track_fill_params(...) makes it a job that fills in (at most 8 rates): lab = an fp32 tensor [ns, 3, gh, gw] of the Lab images at the
+    grid's size (None where fill.epic.saliency_th == 0) and edges = an fp32 tensor [ns, gh, gw] of edge cost maps; slot then counts 2 K slots, slot
+    2 r + 1 the fill-in of rate r, and the call waits where the fill-in reads its counts."""
     import torch
     if len(flows) != params.K:
         raise sfa.SlowflowError(f"flows: {len(flows)} (fwd, bwd) pairs for {params.K} rates")
@@ -530,7 +541,11 @@ def track(ctx, params, flows, frames, *, occlusions=None, rates=False, stream=No
             device_view(a, name=nm, kinds=("f4",), shape=(ns, params.r_Jets[r], 2, src.sh, src.sw))
         if occlusions is not None:
             device_view(occlusions[r], name="occlusions[%d]" % r, kinds=("u1", "f4"), shape=(ns, params.r_Jets[r], src.sh, src.sw))
-    job = _cached_job(ctx, "_track_jobs", bytes(params), lambda: sfa.TrackJob(ctx, params))     # creating a job waits for the context's stream: before the bracket
+    if fill is None and (lab is not None or edges is not None):
+        raise sfa.SlowflowError("lab / edges: given without fill: the job would not read them")
+    if fill is not None and edges is None:
+        raise sfa.SlowflowError("edges: None, but fill is given: one edge cost map per start_jet")
+    job = _cached_job(ctx, "_track_jobs", bytes(params) + (bytes(fill) if fill is not None else b""), lambda: sfa.TrackJob(ctx, params, fill))     # creating a job waits for the context's stream: before the bracket
     g = (ns, job.gh, job.gw)
     def outputs(dev):
         out = (torch.empty((ns, 2, job.gh, job.gw), dtype=torch.float64, device=dev), torch.empty(g, dtype=torch.int32, device=dev),
@@ -547,6 +562,8 @@ def track(ctx, params, flows, frames, *, occlusions=None, rates=False, stream=No
             if occlusions is not None:
                 track_job_upload_occlusions_device(job, r, occlusions[r])
         track_job_upload_frames_device(job, frames)
+        if fill is not None:
+            track_job_upload_fill_device(job, lab, edges)
         job.run(ns)
         track_job_download_device(job, *out[:4])
         if rates:

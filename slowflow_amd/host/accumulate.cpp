@@ -31,8 +31,9 @@
 // With -fill (implies -fuse) every rate also gets dense_tracking's EpicFlow fill-in hypothesis (:1265-1350): the rate's consistent trajectories,
 // interpolated to every pixel at every step (epic_fill_rate, host/epic_fill.h), scored like any other hypothesis and fused with the accumulated ones in
 // the reference's push order (slot 2 r: rate r accumulated, slot 2 r + 1: rate r filled in), so that the fused flow has no holes.  It reads
-// <output>/accumulated/tmp/edges_<sequence_start>.dat (the reference's name, :945; read_edges' format) and runs start_jet by start_jet through the
-// library's stage calls, not through the track job.  acc_skip_pixel 0 only; at most 8 rates.
+// <output>/accumulated/tmp/edges_<sequence_start>.dat (the reference's name, :945; read_edges' format) and runs through the same track job, created with
+// sfa_track_job_create_fill, in the same groups of acc_gpu_batch: the Lab image of the 8-bit frame 0 and the edge map go up with each start_jet, and
+// the fill-in of a whole group is one launch sequence per rate.  acc_skip_pixel 0 only; at most 8 rates.
 //
 // Out of scope (FLANN, GSL, OpenCV are not in this tree): the neighbour proposals.
 #include <algorithm>
@@ -438,7 +439,7 @@ static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run,
     vector<double> flu(gpl), flv(gpl);
     vector<unsigned char> oc(gpl);
     if (!sfa_ok(ctx, sfa_track_job_download_fused(job, k, slot.data(), flu.data(), flv.data(), oc.data(), nullptr, &fu.energy, &fu.bound, &fu.iters))) return false;
-    return write_fused_planes(run, fz, fu, gw, gh, (int)run.rates, slot, flu, flv, oc);
+    return write_fused_planes(run, fz, fu, gw, gh, (int)run.rates * (run.fill ? 2 : 1), slot, flu, flv, oc);
 }
 
 // the energies' keys: setDefault (:118-165), in the types of :606-623 and :661-675
@@ -475,14 +476,17 @@ static void read_fusion(ParameterList &params, const Run &run, Fusion &fz) {
 }
 
 // the track job of the run: B start_jets x all rates.  acc_gpu_batch given: that B or status 1; absent: the largest B <= 16 and <= todo whose job takes at most
-// half of the device memory that is free now
-static sfa_track_job *create_job(ParameterList &params, sfa_ctx *ctx, sfa_track_params tp, size_t todo, int &B) {
+// half of the device memory that is free now.  fill: null, or the parameters of a job that fills in -- its bytes count the fill planes, and the half
+// that stays free is what the interpolation takes its workspace from at run time
+static sfa_track_job *create_job(ParameterList &params, sfa_ctx *ctx, sfa_track_params tp, const sfa_track_fill_params *fill, size_t todo, int &B) {
     sfa_track_job *job = nullptr;
     size_t bytes = 0;
+    auto job_bytes = [&](size_t *b) { return fill ? sfa_track_job_bytes_fill(&tp, fill, b) : sfa_track_job_bytes(&tp, b); };
+    auto job_create = [&]() { return fill ? sfa_track_job_create_fill(ctx, &tp, fill, &job) : sfa_track_job_create(ctx, &tp, &job); };
     if (params.exists("acc_gpu_batch")) {
         tp.n = B = params.parameter<int>("acc_gpu_batch");
-        const bool sized = sfa_track_job_bytes(&tp, &bytes) == SFA_OK;
-        if (!sized || sfa_track_job_create(ctx, &tp, &job) != SFA_OK) {
+        const bool sized = job_bytes(&bytes) == SFA_OK;
+        if (!sized || job_create() != SFA_OK) {
             std::cerr << "acc_gpu_batch " << B << ": the track job cannot be created";
             if (sized) std::cerr << " (" << bytes << " bytes of device memory needed)";
             std::cerr << ": " << sfa_last_error(sized ? ctx : nullptr) << std::endl;
@@ -493,19 +497,23 @@ static sfa_track_job *create_job(ParameterList &params, sfa_ctx *ctx, sfa_track_
         if (!sfa_ok(ctx, sfa_ctx_free_bytes(ctx, &free_bytes))) return nullptr;
         for (B = (int)std::min<size_t>(16, todo); B >= 1; B--) {
             tp.n = B;
-            if (sfa_track_job_bytes(&tp, &bytes) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; return nullptr; }
+            if (job_bytes(&bytes) != SFA_OK) { std::cerr << sfa_last_error(nullptr) << std::endl; return nullptr; }
             if (bytes <= free_bytes / 2 || B == 1) break;
         }
-        if (!sfa_ok(ctx, sfa_track_job_create(ctx, &tp, &job))) return nullptr;
+        if (!sfa_ok(ctx, job_create())) return nullptr;
     }
     std::cout << "gpu batch: " << B << " start_jet(s) per run (" << bytes << " bytes of device memory" << (params.exists("acc_gpu_batch") ? ", acc_gpu_batch" : ", chosen")
               << ")" << std::endl;
     return job;
 }
 
+// the edge map of a start_jet (:945)
+static string edges_file(const Run &run, unsigned seq_start) { return run.acc_dir + "tmp/edges_" + std::to_string(seq_start) + ".dat"; }
+
 // -energies / -fuse: the start_jets in groups of B through one resident track job (sfa_track_job): per start_jet the frames are ingested and normalised and
 // every rate's jets read and uploaded; one run accumulates (all steps), scores (:1219-1257) and, with -fuse, fuses the whole group on the GPU; then the
-// outputs of each start_jet are written in cfg order
+// outputs of each start_jet are written in cfg order.  -fill: the job fills in (sfa_track_job_create_fill); each start_jet also uploads the Lab image of its
+// 8-bit frame 0 and its edge map, the fusion runs over 2 x rates slots, and the fill-in's figures go into run.json
 static int run_energies(ParameterList &params, const Run &run, vector<Segment> &segs, const vector<string> &skipped,
                         const std::map<unsigned, vector<string>> &frame_files, vector<sfa_jet_source> &geo) {
     sfa_track_params tp;
@@ -521,13 +529,20 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     tp.coef = 5.0f;                                                       // :969-981
     sfa_ctx *ctx = nullptr;
     if (!segs.empty() && !sfa_ok(nullptr, sfa_ctx_create(0, &ctx))) return 1;
+    sfa_track_fill_params fill;
+    sfa_track_fill_params_default(&fill);                                  // epic_fill_params (:652-656), removeSmallSegments' 100 (:1265)
+    fill.epic_skip = params.parameter<float>("acc_epic_skip", "2");        // :651
+    const int epic_search = run.fill ? params.parameter<int>("acc_gpu_epic_search", "0") : 0;   // 0 or 1 (refusal()): the graph searches of the fill-in, compact
+    if (ctx && epic_search && !sfa_ok(ctx, sfa_ctx_set_epic_search(ctx, SFA_EPIC_SEARCH_COMPACT))) { sfa_ctx_destroy(ctx); return 1; }
+    struct RateFill { unsigned seq_start; int r; int st[3]; };              // kept_pixels, matches, filled
+    vector<RateFill> fills;
     sfa_track_job *job = nullptr;
-    double t_frames = 0, t_acc = 0, t_energy = 0, t_io = 0, t_fuse = 0;
+    double t_frames = 0, t_acc = 0, t_energy = 0, t_io = 0, t_fuse = 0, t_fill = 0;
     const double t0 = now_s();
     int width = 0, height = 0, status = 0, B = 0, gw = 0, gh = 0;
     vector<unsigned> starts;                                              // the start_jets to do, in order; each has a segment of every rate
     for (auto it = frame_files.begin(); it != frame_files.end(); ++it) starts.push_back(it->first);
-    struct Group { int size; float ms[8]; };
+    struct Group { int size; float ms[8]; float fill_ms[4]; };
     vector<Group> groups;
     for (size_t g0 = 0; g0 < starts.size() && status == 0; g0 += (size_t)B) {
         int ng = 0;
@@ -556,6 +571,8 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
             const int stride = fr.empty() ? 0 : fr[0]->stride;
             vector<float *> fp;
             for (color_image_t *c : fr) fp.push_back(c->c1);
+            // :931, 947-955: the Lab image of the 8-bit copy of frame 0, before the normalisation
+            struct Lab { color_image_t *im; ~Lab() { if (im) color_image_delete(im); } } lab{status == 0 && run.fill ? rgb8_to_lab(fr[0], fz.hbit ? 1.0f / 255 : 1.0f) : nullptr};
             double avg[3], sd[3];
             if (status == 0 && !sfa_ok(ctx, sfa_normalize(ctx, fp.data(), (int)fp.size(), width, height, stride, avg, sd))) status = 1;   // normalize(data, Jets + 1) (:916)
             if (status == 0 && !sfa_ok(nullptr, sfa_accumulate_grid(width, height, run.skip_pixel, &gw, &gh))) status = 1;
@@ -564,6 +581,11 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                 // stride == width
                 std::cerr << "-fuse: width " << width << " is not a multiple of 4 (the reference's smoothness-weight index reads padding)" << std::endl;
                 status = 1;
+            }
+            epic_edges edges;
+            if (status == 0 && run.fill && !read_edges(edges_file(run, seq_start).c_str(), gw, gh, edges)) {
+                std::cerr << edges_file(run, seq_start) << " does not hold " << gw << " x " << gh << " floats" << std::endl;
+                status = 2;
             }
             t_frames += now_s() - ta;
             // every rate of the start_jet is read before anything is uploaded: read_segment fills the rates' row strides, which the job's sources carry
@@ -581,7 +603,7 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                     tp.weight[r] = run.jet_weight.size() > r ? (float)run.jet_weight[r] : (float)r;   // weight_jet_estimation, vector<float> (:489-495)
                 }
                 for (size_t m = 0; m < mine.size(); m++) tp.r_Jets[segs[mine[m]].r] = segs[mine[m]].FF;
-                job = create_job(params, ctx, tp, starts.size(), B);
+                job = create_job(params, ctx, tp, run.fill ? &fill : nullptr, starts.size(), B);
                 if (!job) status = 1;
             }
             for (size_t k = 0; k < mine.size() && status == 0; k++)
@@ -590,13 +612,16 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                     status = 1;
             vector<const float *> cfp(fp.begin(), fp.end());
             if (status == 0 && !sfa_ok(ctx, sfa_track_job_upload_frames(job, ng, cfp.data(), stride))) status = 1;
+            if (status == 0 && run.fill && !sfa_ok(ctx, sfa_track_job_upload_fill(job, ng, lab.im->c1, lab.im->stride, edges.cost.data()))) status = 1;
             for (color_image_t *c : fr) color_image_delete(c);
         }
         if (status) break;
         // ---- one run for the group
-        Group grp{ng, {}};
+        Group grp{ng, {}, {}};
         if (!sfa_ok(ctx, sfa_track_job_run(job, ng)) || !sfa_ok(ctx, sfa_track_job_stage_ms(job, grp.ms))) { status = 1; break; }
+        if (run.fill && !sfa_ok(ctx, sfa_track_job_fill_ms(job, grp.fill_ms))) { status = 1; break; }
         groups.push_back(grp);
+        for (float v : grp.fill_ms) t_fill += 1e-3 * v;
         t_acc += 1e-3 * grp.ms[1];
         t_energy += 1e-3 * (grp.ms[0] + grp.ms[2]);
         t_fuse += 1e-3 * (grp.ms[3] + grp.ms[4] + grp.ms[5] + grp.ms[6] + grp.ms[7]);
@@ -621,6 +646,12 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                     std::cerr << "cannot write the outputs of rate " << s.r << " under " << dir << std::endl;
                     status = 1;
                 }
+                if (status || !run.fill) continue;
+                RateFill rf{seq_start, s.r, {0, 0, 0}};
+                if (!sfa_ok(ctx, sfa_track_job_download_fill(job, k, s.r, nullptr, nullptr, nullptr, nullptr, rf.st))) { status = 1; break; }
+                fills.push_back(rf);
+                std::cout << "rate " << s.r << ", start " << seq_start << ": fill-in from " << rf.st[0] << " consistent pixels, " << rf.st[1] << " matches per step"
+                          << (rf.st[2] ? "" : ": no fill-in hypothesis") << std::endl;
             }
             if (status == 0 && run.fuse) {
                 Fusion::Record fu{};
@@ -648,14 +679,37 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     for (size_t i = 0; i < groups.size(); i++) {
         tail << (i ? ", " : "") << "{\"group\": " << i << ", \"group_size\": " << groups[i].size << ", \"stage_ms\": [";
         for (int m = 0; m < 8; m++) tail << (m ? ", " : "") << groups[i].ms[m];
-        tail << "]}";
+        tail << "]";
+        if (run.fill) {                                                   // regions and matches, edge costs, the interpolation chain, trajectories
+            tail << ", \"fill_ms\": [";
+            for (int m = 0; m < 4; m++) tail << (m ? ", " : "") << groups[i].fill_ms[m];
+            tail << "]";
+        }
+        tail << "}";
     }
     tail << "]";
     if (run.fuse) {
         const sfa_fuse_params &fup = fz.fup;
-        tail << ",\n  \"fused\": true, \"epic_interpolation\": false, \"neighbour_proposals\": false, \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": "
+        tail << ",\n  \"fused\": true, ";
+        if (run.fill)
+            tail << "\"epic_fill\": true, \"fill_path\": \"track_job\", \"epic_interpolation\": true, \"neighbour_proposals\": false, \"acc_epic_skip\": "
+                 << (double)fill.epic_skip << ", \"acc_gpu_epic_search\": " << epic_search;
+        else
+            tail << "\"epic_interpolation\": false, \"neighbour_proposals\": false";
+        tail << ", \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": "
              << fup.acc_spatial_occ << ", \"acc_traj_sim_method\": " << fup.traj_sim_method << ", \"acc_traj_sim_thres\": " << fup.traj_sim_thres
-             << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter << ",\n  \"fusion\": [";
+             << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter;
+        if (run.fill) {
+            tail << ",\n  \"slots\": [";
+            for (unsigned k = 0; k < 2 * run.rates; k++)
+                tail << (k ? ", " : "") << "{\"slot\": " << k << ", \"rate\": " << k / 2 << ", \"kind\": \"" << (k % 2 ? "epic_fill" : "accumulated") << "\"}";
+            tail << "],\n  \"fill\": [";
+            for (size_t i = 0; i < fills.size(); i++)
+                tail << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << fills[i].seq_start << ", \"rate\": " << fills[i].r << ", \"kept_pixels\": " << fills[i].st[0]
+                     << ", \"matches\": " << fills[i].st[1] << ", \"filled\": " << (fills[i].st[2] ? "true" : "false") << "}";
+            tail << "]";
+        }
+        tail << ",\n  \"fusion\": [";
         for (size_t i = 0; i < fz.done.size(); i++) {
             const Fusion::Record &f = fz.done[i];
             tail << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << f.seq_start << ", \"nodes\": " << f.nodes << ", \"energy\": " << f.energy
@@ -666,199 +720,14 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
         }
         tail << "]";
     }
-    tail << ",\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc << ", \"energy_call\": " << t_energy << ", \"write\": " << t_io;
+    tail << ",\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc;
+    if (run.fill) tail << ", \"epic_fill\": " << t_fill;
+    tail << ", \"energy_call\": " << t_energy << ", \"write\": " << t_io;
     if (run.fuse) tail << ", \"fuse\": " << t_fuse;
     tail << ", \"total\": " << now_s() - t0 << "}";
     const bool ok = write_run_json(run, segs, skipped, geo, width, height, tail.str());
-    std::cout << "wrote the energies of " << segs.size() << " segment(s) to " << run.acc_dir << std::endl;
-    return ok ? 0 : 1;
-}
-
-// the edge map of a start_jet (:945)
-static string edges_file(const Run &run, unsigned seq_start) { return run.acc_dir + "tmp/edges_" + std::to_string(seq_start) + ".dat"; }
-
-// -fill: start_jet by start_jet through the stage calls.  Per rate: accumulation with all steps, the fill-in trajectories (epic_fill_rate), the energies
-// of both with the rate's weight and rate acc_min_fps's flows; then one fusion over 2 x rates slots in the reference's push order (:1242, 1322).  A rate
-// whose fill-in keeps no match leaves its odd slot empty (+Inf).  Writes what -fuse writes, and the fill-in's figures into run.json
-static int run_fill(ParameterList &params, const Run &run, vector<Segment> &segs, const vector<string> &skipped,
-                    const std::map<unsigned, vector<string>> &frame_files, vector<sfa_jet_source> &geo) {
-    sfa_energy_params ep;
-    sfa_energy_params_default(&ep);
-    read_energy_params(params, ep);
-    ep.skip = run.skip_pixel;
-    Fusion fz;
-    read_fusion(params, run, fz);
-    const float epic_skip = params.parameter<float>("acc_epic_skip", "2");   // :651
-    epic_params_t eparams;
-    epic_fill_params(&eparams);
-    sfa_ctx *ctx = nullptr;
-    if (!segs.empty() && !sfa_ok(nullptr, sfa_ctx_create(0, &ctx))) return 1;
-    const int epic_search = params.parameter<int>("acc_gpu_epic_search", "0");                // 0 or 1 (refusal()): the graph searches of the fill-in, compact
-    if (ctx && epic_search && !sfa_ok(ctx, sfa_ctx_set_epic_search(ctx, SFA_EPIC_SEARCH_COMPACT))) { sfa_ctx_destroy(ctx); return 1; }
-    struct RateFill { unsigned seq_start; int r; epic_fill_stats st; };
-    vector<RateFill> fills;
-    const int K = (int)run.rates, S = 2 * K, J = (int)run.Jets;
-    int width = 0, height = 0, status = 0, gw = 0, gh = 0;
-    double t_frames = 0, t_acc = 0, t_fill = 0, t_energy = 0, t_fuse = 0, t_io = 0;
-    const double t0 = now_s();
-    for (auto it = frame_files.begin(); it != frame_files.end() && status == 0; ++it) {
-        const unsigned seq_start = it->first;
-        vector<size_t> mine;
-        for (size_t i = 0; i < segs.size(); i++)
-            if (segs[i].seq_start == seq_start) mine.push_back(i);
-        double ta = now_s();
-        vector<color_image_t *> fr;
-        struct Frames { vector<color_image_t *> &f; color_image_t *lab; ~Frames() { for (color_image_t *c : f) color_image_delete(c); if (lab) color_image_delete(lab); } } frames{fr, nullptr};
-        for (const string &name : it->second) {
-            color_image_t *img = ingest_frame(params, run, ctx, name);
-            if (!img) { status = 1; break; }
-            fr.push_back(img);
-            if (fr.size() == 1 && width == 0) { width = img->width; height = img->height; }
-            if (img->width != width || img->height != height) {
-                std::cerr << name << " is " << img->width << " x " << img->height << ", not " << width << " x " << height << " like the first frame" << std::endl;
-                status = 1;
-                break;
-            }
-        }
-        if (status) break;
-        if (!fit_rates(geo, width, height)) { status = 1; break; }
-        if ((int)mine.size() != K) { std::cerr << "start " << seq_start << ": " << mine.size() << " of " << K << " rates to do" << std::endl; status = 1; break; }
-        if (width % 4 != 0) { std::cerr << "-fuse: width " << width << " is not a multiple of 4 (the reference's smoothness-weight index reads padding)" << std::endl; status = 1; break; }
-        frames.lab = rgb8_to_lab(fr[0], fz.hbit ? 1.0f / 255 : 1.0f);         // :931, 947-955: the 8-bit copy of frame 0, before the normalisation
-        const int stride = fr[0]->stride;
-        vector<float *> fp;
-        for (color_image_t *c : fr) fp.push_back(c->c1);
-        double avg[3], sd[3];
-        if (!sfa_ok(ctx, sfa_normalize(ctx, fp.data(), (int)fp.size(), width, height, stride, avg, sd)) ||
-            !sfa_ok(nullptr, sfa_accumulate_grid(width, height, run.skip_pixel, &gw, &gh))) { status = 1; break; }
-        vector<const float *> cfp(fp.begin(), fp.end());
-        epic_edges edges;
-        if (!read_edges(edges_file(run, seq_start).c_str(), gw, gh, edges)) {
-            std::cerr << edges_file(run, seq_start) << " does not hold " << gw << " x " << gh << " floats" << std::endl;
-            status = 2;
-            break;
-        }
-        t_frames += now_s() - ta;
-        double tb = now_s();
-        vector<SegmentInput> in(mine.size());
-        for (size_t k = 0; k < mine.size() && status == 0; k++)
-            if (!read_segment(segs[mine[k]], run.use_occ, geo[segs[mine[k]].r], in[k]) || in[k].fu.empty()) status = 1;
-        t_io += now_s() - tb;
-        if (status) break;
-        const size_t gpl = (size_t)gw * gh;
-        const double inf = std::numeric_limits<double>::infinity();
-        vector<double> U((size_t)S * J * gpl, 0.0), V((size_t)S * J * gpl, 0.0), E((size_t)S * gpl, inf);
-        vector<unsigned long long> O((size_t)S * gpl, 0);
-        const SegmentInput &mf = in[(size_t)run.min_fps_idx];                // mine is in rate order: rate acc_min_fps's flows
-        int call_index = 0;
-        for (size_t k = 0; k < mine.size() && status == 0; k++) {
-            Segment &s = segs[mine[k]];
-            const int r = s.r, FF = s.FF;
-            vector<double> au((size_t)FF * gpl), av((size_t)FF * gpl), hu((size_t)FF * gpl), hv((size_t)FF * gpl);
-            vector<int> tracked(gpl), htracked(gpl);
-            double tc = now_s();
-            if (!sfa_ok(ctx, sfa_accumulate_consistent_scaled(ctx, 1, FF, width, height, &geo[r], in[k].fu.data(), in[k].fv.data(), in[k].bu.data(), in[k].bv.data(),
-                                                              run.use_occ ? in[k].mp.data() : nullptr, run.threshold, run.skip_pixel, run.discard ? 1 : 0, 1,
-                                                              au.data(), av.data(), tracked.data(), nullptr))) { status = 1; break; }
-            t_acc += now_s() - tc;
-            tc = now_s();
-            RateFill rf{seq_start, r, {0, 0, 0}};
-            call_index = epic_fill_rate(ctx, gw, gh, FF, run.skip_pixel, epic_skip, au.data(), av.data(), tracked.data(), frames.lab, edges, &eparams, call_index,
-                                        hu.data(), hv.data(), htracked.data(), &rf.st);
-            if (call_index < 0) { std::cerr << "the fill-in of rate " << r << ", start " << seq_start << " failed: " << sfa_last_error(ctx) << std::endl; status = 1; break; }
-            fills.push_back(rf);
-            t_fill += now_s() - tc;
-            tc = now_s();
-            ep.weight = run.jet_weight.size() > (size_t)r ? (float)run.jet_weight[r] : (float)r;   // weight_jet_estimation, vector<float> (:489-495)
-            const bool flows = r >= run.min_fps_idx;                          // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
-            for (int kind = 0; kind < 2 && status == 0; kind++) {             // the accumulated hypothesis (:1242), then the fill-in (:1322)
-                if (kind == 1 && !rf.st.filled) continue;
-                const size_t slot = 2 * (size_t)r + kind;
-                if (!sfa_ok(ctx, sfa_hypothesis_energies_scaled(ctx, &ep, 1, FF, J, width, height, stride, kind ? hu.data() : au.data(), kind ? hv.data() : av.data(),
-                                                                kind ? htracked.data() : tracked.data(), cfp.data(), &geo[(size_t)run.min_fps_idx],
-                                                                flows ? mf.fu.data() : nullptr, flows ? mf.fv.data() : nullptr, flows ? mf.bu.data() : nullptr,
-                                                                flows ? mf.bv.data() : nullptr, E.data() + slot * gpl, O.data() + slot * gpl,
-                                                                U.data() + slot * J * gpl, V.data() + slot * J * gpl))) status = 1;
-            }
-            t_energy += now_s() - tc;
-            if (status) break;
-            // the rate's own files, as -energies writes them
-            double td = now_s();
-            vector<float> ef(gpl);
-            vector<unsigned char> oc(gpl);
-            for (size_t p = 0; p < gpl; p++) {
-                ef[p] = (float)E[2 * (size_t)r * gpl + p];
-                oc[p] = (unsigned char)__builtin_popcountll(O[2 * (size_t)r * gpl + p]);
-            }
-            const string dir = run.acc_dir + std::to_string(r) + "/";
-            if (!write_last_step(s, au.data() + (size_t)(FF - 1) * gpl, av.data() + (size_t)(FF - 1) * gpl, tracked.data(), gw, gh) ||
-                !write_pfm(dir + "energy_" + std::to_string(seq_start) + ".pfm", gw, gh, ef.data()) ||
-                !write_pgm8(dir + "occluded_" + std::to_string(seq_start) + ".pgm", gw, gh, oc.data(), gw)) {
-                std::cerr << "cannot write the outputs of rate " << r << " under " << dir << std::endl;
-                status = 1;
-            }
-            std::cout << "rate " << r << ", start " << seq_start << ": fill-in from " << rf.st.kept_pixels << " consistent pixels, " << rf.st.matches << " matches per step"
-                      << (rf.st.filled ? "" : ": no fill-in hypothesis") << std::endl;
-            t_io += now_s() - td;
-        }
-        if (status) break;
-        // the fusion over the 2 K slots
-        double te = now_s();
-        vector<float> weight((size_t)width * height);
-        vector<int> slot(gpl);
-        vector<double> flu(gpl), flv(gpl);
-        vector<unsigned char> foc(gpl);
-        Fusion::Record fu{};
-        fu.seq_start = seq_start; fu.group = (int)fz.done.size(); fu.group_size = 1;
-        double tw = now_s();
-        if (!sfa_ok(ctx, sfa_dt_smoothness_weight(ctx, width, height, stride, fr[0]->c1, 5.0f, fz.nav, fz.nsd, fz.hbit, weight.data()))) { status = 1; break; }
-        fu.t_weight = now_s() - tw;
-        if (!sfa_ok(ctx, sfa_fuse_hypotheses(ctx, &fz.fup, 1, S, J, width, height, U.data(), V.data(), E.data(), O.data(), weight.data(), slot.data(), flu.data(),
-                                             flv.data(), foc.data(), &fu.energy, &fu.bound, &fu.iters, fu.stage_ms))) { status = 1; break; }
-        fu.t_fuse = now_s() - te - fu.t_weight;
-        t_fuse += now_s() - te;
-        double td = now_s();
-        if (!write_fused_planes(run, fz, fu, gw, gh, S, slot, flu, flv, foc)) { status = 1; break; }
-        vector<unsigned char> best(gpl, 255);                                // the rate of the lowest fp32 energy among the accumulated hypotheses, ties to the lower
-        for (size_t p = 0; p < gpl; p++) {
-            float lowest = std::numeric_limits<float>::infinity();
-            for (int r = 0; r < K; r++) {
-                const float e = (float)E[2 * (size_t)r * gpl + p];
-                if (e < lowest) { lowest = e; best[p] = (unsigned char)r; }
-            }
-        }
-        if (!write_pgm8(run.acc_dir + "best_" + std::to_string(seq_start) + ".pgm", gw, gh, best.data(), gw)) {
-            std::cerr << "cannot write " << run.acc_dir << "best_" << seq_start << ".pgm" << std::endl;
-            status = 1;
-        }
-        t_io += now_s() - td;
-    }
-    if (ctx) sfa_ctx_destroy(ctx);
-    if (status) return status;
-    std::ostringstream tail;
-    tail.precision(17);
-    const sfa_fuse_params &fup = fz.fup;
-    tail << ",\n  \"fused\": true, \"epic_fill\": true, \"epic_interpolation\": true, \"neighbour_proposals\": false, \"acc_epic_skip\": " << (double)epic_skip << ", \"acc_gpu_epic_search\": " << epic_search
-         << ", \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": " << fup.acc_spatial_occ << ", \"acc_traj_sim_method\": " << fup.traj_sim_method
-         << ", \"acc_traj_sim_thres\": " << fup.traj_sim_thres << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter
-         << ",\n  \"slots\": [";
-    for (int k = 0; k < S; k++) tail << (k ? ", " : "") << "{\"slot\": " << k << ", \"rate\": " << k / 2 << ", \"kind\": \"" << (k % 2 ? "epic_fill" : "accumulated") << "\"}";
-    tail << "],\n  \"fill\": [";
-    for (size_t i = 0; i < fills.size(); i++)
-        tail << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << fills[i].seq_start << ", \"rate\": " << fills[i].r << ", \"kept_pixels\": " << fills[i].st.kept_pixels
-             << ", \"matches\": " << fills[i].st.matches << ", \"filled\": " << (fills[i].st.filled ? "true" : "false") << "}";
-    tail << "],\n  \"fusion\": [";
-    for (size_t i = 0; i < fz.done.size(); i++) {
-        const Fusion::Record &f = fz.done[i];
-        tail << (i ? ",\n    " : "\n    ") << "{\"sequence_start\": " << f.seq_start << ", \"nodes\": " << f.nodes << ", \"energy\": " << f.energy
-             << ", \"lower_bound\": " << f.bound << ", \"iterations\": " << f.iters << ", \"weight_s\": " << f.t_weight << ", \"fuse_call_s\": " << f.t_fuse
-             << ", \"kernels_ms\": {\"labels\": " << f.stage_ms[0] << ", \"pairwise\": " << f.stage_ms[1] << ", \"trws\": " << f.stage_ms[2]
-             << ", \"output\": " << f.stage_ms[3] << "}}";
-    }
-    tail << "],\n  \"timings_s\": {\"frames\": " << t_frames << ", \"accumulate\": " << t_acc << ", \"epic_fill\": " << t_fill << ", \"energy_call\": " << t_energy
-         << ", \"fuse\": " << t_fuse << ", \"write\": " << t_io << ", \"total\": " << now_s() - t0 << "}";
-    const bool ok = write_run_json(run, segs, skipped, geo, width, height, tail.str());
-    std::cout << "wrote the fused flows with fill-in of " << fz.done.size() << " start_jet(s) to " << run.acc_dir << std::endl;
+    if (run.fill) std::cout << "wrote the fused flows with fill-in of " << fz.done.size() << " start_jet(s) to " << run.acc_dir << std::endl;
+    else std::cout << "wrote the energies of " << segs.size() << " segment(s) to " << run.acc_dir << std::endl;
     return ok ? 0 : 1;
 }
 
@@ -1091,6 +960,5 @@ int main(int argc, char **argv) {
     }
     mkdirs(run.acc_dir);
     for (unsigned r = 0; r < run.rates; r++) mkdirs(run.acc_dir + std::to_string(r) + "/");
-    if (run.fill) return run_fill(params, run, segs, skipped, frame_files, geo);
     return run.energies ? run_energies(params, run, segs, skipped, frame_files, geo) : run_accumulate(params, run, segs, skipped, geo);
 }
