@@ -794,7 +794,7 @@ int sfa_normalize(sfa_ctx *ctx, float *const *frames, int F, int w, int h, int s
 // ---- the argument checks of the device seam (include/slowflow_amd.h; kernels: device_io.hip, mosaic.hip, track.hip, quantile.hip) -------------------
 // A view's strides, extent, nesting and byte range are dev_view.h's arithmetic; here it meets the HIP runtime (check_device_pointer) and the messages.
 // Every check is taken on the host before anything is launched; a refusal names the argument (REFUSE: sfa_internal.h).  Those declared in sfa_internal.h are
-// shared with job.hip, two_frame.hip, track.hip and quantile.hip.
+// shared with job.hip, two_frame.hip, track.hip, track_fill.hip and quantile.hip.
 namespace sfa {
 
 // `p` must be device memory of the context's GPU, and the view (its last element `last` elements of `elem` bytes further) must lie inside p's allocation

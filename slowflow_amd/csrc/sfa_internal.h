@@ -210,7 +210,7 @@ int launch_jet_resample(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, cons
 int launch_jet_occ_decode(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const unsigned char *stage, int w, int h, unsigned char *out);
 
 // ---- dense_tracking's three stages at device level (accumulate.hip, energy.hip, fuse.hip): device pointers and a caller-owned workspace in, launches on the
-// context's stream out; no allocation, no copy, no wait.  The sfa_* entry points wrap them (allocate, upload, call, download, wait), the track job (track.hip)
+// context's stream out; no allocation, no copy, no wait.  The sfa_* entry points wrap them (allocate, upload, call, download, wait), the track job (track.hip, track_fill.hip)
 // chains them ------------------------------------------------------------------------------------------------------------------------------------------
 // n float planes u, v -> n float2 planes (total n elements)
 void launch_interleave(sfa_ctx *ctx, const float *u, const float *v, float2 *out, size_t n);
@@ -506,7 +506,7 @@ int sor_rb_run(sfa_ctx *c, const Geo &g, float *du, float *dv, float *a11, float
 int sor_run(sfa_ctx *c, SorWorkspace &ws, const Geo &g, float *du, float *dv, float *a11, float *a12, float *a22, const float *b1, const float *b2,
             const float *sh, const float *sv, int K, float omega, bool inv_out);
 
-// ---- the device seam's argument checks, shared by every entry point that takes device memory (job.hip, two_frame.hip, track.hip, quantile.hip, api.hip).
+// ---- the device seam's argument checks, shared by every entry point that takes device memory (job.hip, two_frame.hip, track.hip, track_fill.hip, quantile.hip, api.hip).
 // The arithmetic -- View, the sign and extent rule, strides_nest, byte ranges and their overlap -- is dev_view.h's, host code a CPU test compiles; what asks
 // the HIP runtime is api.hip's.  Each refuses with SFA_ERR_ARG and a message that names `fn` and the argument; nothing is launched on a refusal ------------
 // a view: refuses a null pointer or null strides, then what view_extent refuses, then what check_device_pointer does

@@ -7,12 +7,14 @@
 // planes: a copy and the stage wrappers' kernels; device memory: the pack kernels below; occlusion images likewise), so a run reads only what the job holds.
 // Segment s of a run comes out with the bits of the staged calls on that segment alone: the same kernels over the same planes, blockIdx.y = s.
 // The device entry points describe their arguments as views and leave every check of them to check_view / check_disjoint (api.hip on dev_view.h).
+// The job and its plane table are track_job.h's; what a fill job adds between the accumulation and the energies is track_fill.hip.
 #include <algorithm>
 #include <cmath>
 #include <memory>
 #include <vector>
 
 #include "sfa_device.h"
+#include "track_job.h"
 
 #pragma clang fp contract(off)
 
@@ -142,52 +144,11 @@ inline unsigned blocks_of(size_t total) { return (unsigned)((total + kTrThreads 
 
 using namespace sfa;
 
+static_assert(kTrMaxK == kTrackMaxRates && kTrThreads == kTrackThreads, "track_job.h restates the two for track_fill.hip");
+
 // Everything below is launch orchestration: argument checks, layout arithmetic, copies and launches, a few microseconds per call beside milliseconds of
 // kernels.  It is compiled for size, so that the release build stays under the share of the full build tests/test_abi.py holds it to.
 #pragma clang attribute push(__attribute__((minsize)), apply_to = function)
-
-// Every plane of the job inside one allocation; this struct is the only statement of the list (sfa_track_job_bytes walks it without a device)
-struct TrackPlanes {
-    struct Rate { size_t fw, bw, mask, acc_u, acc_v, tracked; } rate[kTrMaxK];
-    size_t occluded, stage, occ_stage, frames, der, rec, wU, wV, wocc, jc, oc, ep, E, O, best;
-    size_t aU, aV, weight, nl, lab, theta, P, M, xcur, xbest, slot, fu, fv, out_occ, seg_energy, seg_bound, seg_iters;
-    // a fill job only: the saliency's workspace of one start_jet (15 planes at the device pitch), sal [n][plp], edges (as uploaded) and run_cost (the map
-    // as the calls so far left it) [n][cpl], cost [n][rJmax][cpl], full [K][n], the regions' T, P, S [n][gpl] and mask, kept and count [n], the sample
-    // positions, block_count, matches [n][rJmax][nx ny][4], fx, fy [n][rJmax][gpl], inf [gpl] doubles of +Inf; per rate the fill-in's trajectories [n][rJ][gpl] and tracked [n][gpl]
-    size_t lab_stage, sal, edges, run_cost, cost, full, cT, cP, cS, mask, kept, count, xs, ys, block_count, matches, fx, fy, inf;
-    struct Fill { size_t u, v, tracked; } fill[kTrMaxK];
-    size_t total;
-};
-
-// what a fill job derives from its parameters besides the planes: the sample positions, the longest rate, the planes' strides
-struct FillGeo { std::unique_ptr<int[]> xs, ys; int nx = 0, ny = 0, rJmax = 0, pitch = 0; size_t cpl = 0, plp = 0; };
-
-struct sfa_track_job {
-    sfa_ctx *ctx = nullptr;
-    sfa_track_params p;
-    int gw = 0, gh = 0;
-    bool identity[kTrMaxK] = {};
-    EnergyPlan plan[kTrMaxK];
-    TrackPlanes at;
-    DevMem mem;
-    hipEvent_t ev[10] = {};             // [9]: after the smoothness weight, before the fusion's clears
-    bool timed = false, timed_fuse = false;
-    bool fill = false;                  // made by sfa_track_job_create_fill
-    sfa_track_fill_params fp{};
-    FillGeo fg;
-    std::unique_ptr<int[]> full, stats; // [K][n] r_Jets[r]; [K][n][3] kept_pixels, matches, filled of the last run
-    std::unique_ptr<double[]> inf;      // [gpl] +Inf, the source of at.inf
-    // the interpolation's images of one rate, n * rJmax entries each: EpicChainDev's arrays, their counts, start_jets and steps, rc and status
-    std::unique_ptr<const float *[]> c_in;   // cost, matches, sal
-    std::unique_ptr<float *[]> c_out;        // fx, fy
-    std::unique_ptr<int[]> c_int;            // nm, start_jet, step, rc, status, then kept and count [n]
-    int chain_runs[2] = {};             // the last run's interpolation sub-batches over all rates: completed, cut short and run again
-    hipEvent_t fev[kTrMaxK][5] = {};    // per rate: before the regions, after the matches, the edge costs, the chain, the trajectories
-    hipEvent_t ev_energy = nullptr;     // a fill job: after the last rate's fill-in, where the energies begin
-    int slots() const { return fill ? 2 * p.K : p.K; }
-    int step() const { return fill ? 2 : 1; }
-    template <class T> T *ptr(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(mem.p) + off); }
-};
 
 // the argument checks of create and bytes (no device): everything the three stages refuse, by the name of the argument
 static int track_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, int *gw, int *gh, bool *identity, EnergyPlan *plan) {
@@ -224,81 +185,40 @@ static int track_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, 
     return SFA_OK;
 }
 
-// the checks of a fill job beyond track_check's, by the name of the argument, and what the layout needs of it
-static int fill_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, const sfa_track_fill_params *f, int gw, int gh, FillGeo *g) {
-    if (!f) REFUSE("%s: fill is null", fn);
-    if (p->K > kTrMaxK / 2) REFUSE("%s: K = %d (a fill job fuses 2 K slots: at most %d rates)", fn, p->K, kTrMaxK / 2);
-    if (f->epic.nn < 1) REFUSE("%s: epic.nn = %d (at least one neighbour)", fn, f->epic.nn);
-    if (f->epic.pref_nn < 0) REFUSE("%s: epic.pref_nn = %d (0: no consistency filter, else its neighbours)", fn, f->epic.pref_nn);
-    if (f->epic.method != 0 && f->epic.method != 1) REFUSE("%s: epic.method = %d (0: locally-weighted affine, 1: Nadaraya-Watson)", fn, f->epic.method);
-    if (!std::isfinite(f->epic_skip) || f->epic_skip < 1) REFUSE("%s: epic_skip = %g (finite, at least 1)", fn, (double)f->epic_skip);
-    if (f->min_size < 1) REFUSE("%s: min_size = %d (>= 1)", fn, f->min_size);
-    if (f->epic.saliency_th != 0 && (gw <= 8 || gh <= 8))
-        REFUSE("%s: gw x gh = %d x %d with epic.saliency_th != 0 (the saliency's Gaussian of sigma 1.0 needs more than 8 columns and rows)", fn, gw, gh);
-    SFA_TRY(epic_nn_check_sizes(ctx, fn, gw, gh));
-    if (((size_t)gw * gh * 4 * p->K * p->K + kTrThreads - 1) / kTrThreads > 0x7fffffffull) REFUSE("%s: grid too large for 2 K slots", fn);
-    g->xs.reset(new int[gw]()); g->ys.reset(new int[gh]());
-    if (sfa_fill_samples(gw, f->epic_skip, g->xs.get(), &g->nx) != SFA_OK || sfa_fill_samples(gh, f->epic_skip, g->ys.get(), &g->ny) != SFA_OK)
-        REFUSE("%s: epic_skip: %s", fn, sfa_last_error(nullptr));
-    g->rJmax = 0;
-    for (int r = 0; r < p->K; r++) g->rJmax = std::max(g->rJmax, p->r_Jets[r]);
-    g->pitch = dev_pitch(gw);
-    g->plp = (size_t)g->pitch * gh;
-    g->cpl = ((size_t)gw * gh + 3) / 4 * 4;
-    return SFA_OK;
-}
-
+// the planes in TrackPlanes' order, counted in elements; fill, fg: null for a plain job
 static void track_layout(const sfa_track_params &p, int gw, int gh, const bool *identity, int NN, const sfa_track_fill_params *fill, const FillGeo *fg,
                          TrackPlanes *out) {
     TrackPlanes &a = *out;
-    size_t top = 0;
-    auto take = [&](size_t bytes) { const size_t o = top; top += (bytes + 255) / 256 * 256; return o; };
+    a = TrackPlanes{};                                                          // a plane the job does not have stays at offset 0
+    PlaneCursor c;
     const size_t n = p.n, K = p.K, J = p.Jets, pl = (size_t)p.w * p.h, gpl = (size_t)gw * gh;
     const size_t S = fill ? 2 * K : K;                                          // the fusion's slots
     size_t stage = 0, occ_stage = 0;
     for (int r = 0; r < p.K; r++) {
-        const size_t rJ = p.r_Jets[r], tap = identity[r] ? 8 : 16, spl = identity[r] ? pl : (size_t)p.source[r].cw * p.source[r].ch;
-        a.rate[r].fw = take(n * rJ * pl * tap);
-        a.rate[r].bw = take(n * rJ * pl * tap);
-        a.rate[r].mask = p.use_occlusions ? take(n * rJ * pl) : 0;
-        a.rate[r].acc_u = take(n * rJ * gpl * 8);
-        a.rate[r].acc_v = take(n * rJ * gpl * 8);
-        a.rate[r].tracked = take(n * gpl * 4);
-        stage = std::max(stage, 2 * rJ * spl * 4);                              // one segment's u and v planes of one direction
+        TrackPlanes::Rate &t = a.rate[r];
+        const size_t rJ = p.r_Jets[r], tap = identity[r] ? sizeof(float2) : sizeof(double2), spl = identity[r] ? pl : (size_t)p.source[r].cw * p.source[r].ch;
+        c.take(t.fw, n * rJ * pl * tap); c.take(t.bw, n * rJ * pl * tap);
+        if (p.use_occlusions) c.take(t.mask, n * rJ * pl);
+        c.take(t.acc_u, n * rJ * gpl); c.take(t.acc_v, n * rJ * gpl); c.take(t.tracked, n * gpl);
+        stage = std::max(stage, 2 * rJ * spl);                                  // one segment's u and v planes of one direction
         occ_stage = std::max(occ_stage, rJ * (size_t)p.source[r].sw * p.source[r].sh);
     }
-    a.occluded = take(K * n * gpl);                                             // [K][n][gpl]
-    a.stage = take(stage);
-    a.occ_stage = p.use_occlusions ? take(occ_stage) : 0;
-    a.frames = take(n * (J + 1) * 3 * pl * 4);
-    a.der = take(n * (J + 1) * 6 * pl * 4);
-    a.rec = take(n * (J + 1) * pl * 48);
-    a.wU = take(n * J * gpl * 8); a.wV = take(n * J * gpl * 8); a.wocc = take(n * gpl * 8);
-    a.jc = take(n * gpl * 4); a.oc = take(n * gpl * 4); a.ep = take(n * gpl * NN * 8);
-    a.E = take(n * S * gpl * 8); a.O = take(n * S * gpl * 8); a.best = take(n * gpl);
+    c.take(a.occluded, K * n * gpl);                                            // [K][n][gpl]
+    c.take(a.stage, stage);
+    if (p.use_occlusions) c.take(a.occ_stage, occ_stage);
+    c.take(a.frames, n * (J + 1) * 3 * pl); c.take(a.der, n * (J + 1) * 6 * pl); c.take(a.rec, n * (J + 1) * pl * 48);
+    c.take(a.wU, n * J * gpl); c.take(a.wV, n * J * gpl); c.take(a.wocc, n * gpl);
+    c.take(a.jc, n * gpl); c.take(a.oc, n * gpl); c.take(a.ep, n * gpl * NN);
+    c.take(a.E, n * S * gpl); c.take(a.O, n * S * gpl); c.take(a.best, n * gpl);
     if (p.do_fuse) {
-        a.aU = take(n * S * J * gpl * 8); a.aV = take(n * S * J * gpl * 8); a.weight = take(n * pl * 4);
-        a.nl = take(n * gpl); a.lab = take(n * gpl * 16); a.theta = take(n * gpl * 16 * 8); a.P = take(n * 2 * gpl * S * S * 8);
-        a.M = take(n * gpl * 4 * 16 * 8); a.xcur = take(n * gpl); a.xbest = take(n * gpl);
-        a.slot = take(n * gpl * 4); a.fu = take(n * gpl * 8); a.fv = take(n * gpl * 8); a.out_occ = take(n * gpl);
-        a.seg_energy = take(n * 8); a.seg_bound = take(n * 8); a.seg_iters = take(n * 4);
+        c.take(a.aU, n * S * J * gpl); c.take(a.aV, n * S * J * gpl); c.take(a.weight, n * pl);
+        c.take(a.nl, n * gpl); c.take(a.lab, n * gpl * 16); c.take(a.theta, n * gpl * 16); c.take(a.P, n * 2 * gpl * S * S);
+        c.take(a.M, n * gpl * 4 * 16); c.take(a.xcur, n * gpl); c.take(a.xbest, n * gpl);
+        c.take(a.slot, n * gpl); c.take(a.fu, n * gpl); c.take(a.fv, n * gpl); c.take(a.out_occ, n * gpl);
+        c.take(a.seg_energy, n); c.take(a.seg_bound, n); c.take(a.seg_iters, n);
     }
-    if (fill) {
-        const size_t rJm = fg->rJmax, samples = (size_t)fg->nx * fg->ny;
-        a.lab_stage = fill->epic.saliency_th != 0 ? take((size_t)kEpicSaliencyPlanes * fg->plp * 4) : 0;
-        a.sal = fill->epic.saliency_th != 0 ? take(n * fg->plp * 4) : 0;
-        a.edges = take(n * fg->cpl * 4); a.run_cost = take(n * fg->cpl * 4); a.cost = take(n * rJm * fg->cpl * 4);
-        a.full = take(K * n * 4);
-        a.cT = take(n * gpl * 4); a.cP = take(n * gpl * 4); a.cS = take(n * gpl * 4); a.mask = take(n * gpl); a.kept = take(n * 4); a.count = take(n * 4);
-        a.xs = take((size_t)gw * 4); a.ys = take((size_t)gh * 4);
-        a.block_count = take(n * std::max<size_t>(fill_matches_blocks(fg->nx, fg->ny), 1) * 4);
-        a.matches = take(n * rJm * std::max<size_t>(samples, 1) * 16);
-        a.fx = take(n * rJm * gpl * 4); a.fy = take(n * rJm * gpl * 4); a.inf = take(gpl * 8);
-        for (int r = 0; r < p.K; r++) {
-            a.fill[r].u = take(n * p.r_Jets[r] * gpl * 8); a.fill[r].v = take(n * p.r_Jets[r] * gpl * 8); a.fill[r].tracked = take(n * gpl * 4);
-        }
-    }
-    a.total = top;
+    if (fill) fill_layout(c, p, gw, gh, *fill, *fg, &a);
+    a.total = c.top;
 }
 
 void sfa_track_params_default(sfa_track_params *p) {
@@ -315,31 +235,25 @@ void sfa_track_params_default(sfa_track_params *p) {
     for (int r = 0; r < kTrMaxK; r++) { p->r_Jets[r] = 1; p->weight[r] = (float)r; }   // weight_jet_estimation[r] = r where none is given
 }
 
-void sfa_track_fill_params_default(sfa_track_fill_params *fill) {
-    if (!fill) return;
-    *fill = sfa_track_fill_params{};
-    fill->epic_skip = 2.0f;                                                     // acc_epic_skip (:651)
-    fill->min_size = 100;                                                       // removeSmallSegments(r_consistent, 0.1, 100) (:1265)
-    // epic_params_default (epic.cpp:127-136), then dense_tracking.cpp:652-656
-    fill->epic.method = 0; fill->epic.saliency_th = 0.045f; fill->epic.pref_nn = 25; fill->epic.pref_th = 5.0f; fill->epic.nn = 160;
-    fill->epic.coef_kernel = 1.1f; fill->epic.euc = 0.001f;
-}
-
-// one-line forms of the stream calls the fill-in makes many of
-static int copy_on(sfa_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+int sfa::copy_on(sfa_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
     SFA_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
     return SFA_OK;
 }
-static int zero_on(sfa_ctx *ctx, void *dst, size_t bytes) {
+int sfa::zero_on(sfa_ctx *ctx, void *dst, size_t bytes) {
     SFA_HIP(ctx, hipMemsetAsync(dst, 0, bytes, ctx->stream));
     return SFA_OK;
 }
-static int mark(sfa_ctx *ctx, hipEvent_t e) {
+int sfa::mark(sfa_ctx *ctx, hipEvent_t e) {
     SFA_HIP(ctx, hipEventRecord(e, ctx->stream));
     return SFA_OK;
 }
+int sfa::copy_rows_on(sfa_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t row, size_t h, hipMemcpyKind kind) {
+    SFA_HIP(ctx, hipMemcpy2DAsync(dst, dpitch, src, spitch, row, h, kind, ctx->stream));
+    return SFA_OK;
+}
+int sfa::download(sfa_ctx *ctx, void *dst, const void *src, size_t bytes) { return dst ? copy_on(ctx, dst, src, bytes, hipMemcpyDeviceToHost) : (int)SFA_OK; }
 
-// fill: null for a plain job
+// with_fill: the call is a fill job's, and a null fill is refused under its name
 static int track_bytes(const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, size_t *bytes) {
     sfa_ctx *ctx = nullptr;
     if (!bytes) REFUSE("%s: bytes is null", fn);
@@ -349,7 +263,7 @@ static int track_bytes(const char *fn, const sfa_track_params *p, const sfa_trac
     SFA_TRY(track_check(ctx, fn, p, &gw, &gh, identity, plan));
     FillGeo fg;
     if (with_fill) SFA_TRY(fill_check(ctx, fn, p, fill, gw, gh, &fg));
-    TrackPlanes at{};
+    TrackPlanes at;
     track_layout(*p, gw, gh, identity, plan[0].NN, with_fill ? fill : nullptr, &fg, &at);
     *bytes = at.total;
     return SFA_OK;
@@ -366,35 +280,18 @@ static int track_create(sfa_ctx *ctx, const char *fn, const sfa_track_params *p,
     j->ctx = ctx;
     SFA_TRY(track_check(ctx, fn, p, &j->gw, &j->gh, j->identity, j->plan));
     if (with_fill) {
-        SFA_TRY(fill_check(ctx, fn, p, fill, j->gw, j->gh, &j->fg));
-        j->fill = true;
-        j->fp = *fill;
+        j->fill.reset(new TrackFill);
+        SFA_TRY(fill_check(ctx, fn, p, fill, j->gw, j->gh, &j->fill->g));
+        j->fill->fp = *fill;
     }
     j->p = *p;
     j->p.energy.skip = j->p.fuse.skip = p->skip;
-    track_layout(j->p, j->gw, j->gh, j->identity, j->plan[0].NN, with_fill ? &j->fp : nullptr, &j->fg, &j->at);
+    track_layout(j->p, j->gw, j->gh, j->identity, j->plan[0].NN, with_fill ? &j->fill->fp : nullptr, with_fill ? &j->fill->g : nullptr, &j->at);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     SFA_TRY(j->mem.alloc(ctx, j->at.total));
-    SFA_HIP(ctx, hipMemsetAsync(j->mem.p, 0, j->at.total, ctx->stream));        // a run before an upload reads zeros, not another job's planes
+    SFA_TRY(zero_on(ctx, j->mem.p, j->at.total));                               // a run before an upload reads zeros, not another job's planes
     for (auto &e : j->ev) SFA_HIP(ctx, hipEventCreate(&e));
-    if (with_fill) {
-        for (int r = 0; r < p->K; r++)
-            for (auto &e : j->fev[r]) SFA_HIP(ctx, hipEventCreate(&e));
-        SFA_HIP(ctx, hipEventCreate(&j->ev_energy));
-        const size_t rates = (size_t)p->K * p->n, images = (size_t)p->n * j->fg.rJmax, gpl = (size_t)j->gw * j->gh;
-        j->full.reset(new int[rates]);
-        for (size_t k = 0; k < rates; k++) j->full[k] = p->r_Jets[k / p->n];
-        j->stats.reset(new int[3 * rates]());
-        j->c_in.reset(new const float *[3 * images]()); j->c_out.reset(new float *[2 * images]()); j->c_int.reset(new int[5 * images + 2 * (size_t)p->n]());
-        j->inf.reset(new double[gpl]);
-        for (size_t k = 0; k < gpl; k++) j->inf[k] = (double)__builtin_inff();
-        SFA_TRY(copy_on(ctx, j->ptr<double>(j->at.inf), j->inf.get(), gpl * 8, hipMemcpyHostToDevice));
-        // (the host arrays live as long as the job, and the wait below is before anything can change them)
-        SFA_TRY(copy_on(ctx, j->ptr<int>(j->at.full), j->full.get(), rates * 4, hipMemcpyHostToDevice));
-        SFA_TRY(copy_on(ctx, j->ptr<int>(j->at.xs), j->fg.xs.get(), (size_t)j->gw * 4, hipMemcpyHostToDevice));
-        SFA_TRY(copy_on(ctx, j->ptr<int>(j->at.ys), j->fg.ys.get(), (size_t)j->gh * 4, hipMemcpyHostToDevice));
-        SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if (with_fill) SFA_TRY(track_fill_create(j));
     guard.j = nullptr;
     *out = j;
     return SFA_OK;
@@ -410,21 +307,10 @@ void sfa_track_job_destroy(sfa_track_job *job) {
     if (job->ctx && job->ctx->stream) (void)hipStreamSynchronize(job->ctx->stream);
     for (auto &e : job->ev)
         if (e) (void)hipEventDestroy(e);
-    for (auto &rate : job->fev)
-        for (auto &e : rate)
-            if (e) (void)hipEventDestroy(e);
-    if (job->ev_energy) (void)hipEventDestroy(job->ev_energy);
-    delete job;
+    delete job;                                                                 // a fill job's events go with its TrackFill
 }
 
-#define TRACK_JOB(job) \
-    if (!(job)) return sfa::set_error(nullptr, SFA_ERR_ARG, "%s: job is null", __func__); \
-    sfa_ctx *ctx = (job)->ctx; \
-    const sfa_track_params &p = (job)->p; \
-    const size_t pl = (size_t)p.w * p.h, gpl = (size_t)(job)->gw * (job)->gh; \
-    (void)pl; (void)gpl
-
-static int track_range(sfa_ctx *ctx, const char *fn, const sfa_track_params &p, int s0, int ns, int r) {
+int sfa::track_range(sfa_ctx *ctx, const char *fn, const sfa_track_params &p, int s0, int ns, int r) {
     if (s0 < 0 || ns < 1 || (long)s0 + ns > p.n) {
         if (ns == 1) REFUSE("%s: s = %d lies outside the job's %d start_jets", fn, s0, p.n);
         REFUSE("%s: s0 = %d, ns = %d lie outside the job's %d start_jets", fn, s0, ns, p.n);
@@ -443,28 +329,27 @@ int sfa_track_job_upload_flows(sfa_track_job *job, int s, int r, const float *co
     for (int k = 0; k < rJ; k++)
         if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k] || (p.use_occlusions && !occ[k])) REFUSE("%s: null plane %d", __func__, k);
     const sfa_jet_source &src = p.source[r];
+    const TrackPlanes::Rate &a = job->at.rate[r];
     const bool identity = job->identity[r];
-    const size_t tap = identity ? 8 : 16, seg = (size_t)s * rJ * pl;
+    const size_t tap = identity ? sizeof(float2) : sizeof(double2), seg = (size_t)s * rJ * pl;
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    float *stage = job->ptr<float>(job->at.stage);
+    float *stage = job->ptr(job->at.stage);
     for (int dir = 0; dir < 2; dir++) {
         const float *const *U = dir ? bwd_u : fwd_u, *const *V = dir ? bwd_v : fwd_v;
-        char *dst = job->ptr<char>(dir ? job->at.rate[r].bw : job->at.rate[r].fw) + seg * tap;
+        char *dst = job->ptr(dir ? a.bw : a.fw) + seg * tap;
         if (!identity) {
             SFA_TRY(jet_resample_flows(ctx, src, (size_t)rJ, U, V, p.w, p.h, stage, reinterpret_cast<double2 *>(dst), nullptr, nullptr));
             continue;
         }
         float *su = stage, *sv = stage + (size_t)rJ * pl;
         for (int k = 0; k < rJ; k++) {                                          // the valid columns of each plane, packed, then interleaved
-            SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)p.w * 4, U[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice, ctx->stream));
-            SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)p.w * 4, V[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice, ctx->stream));
+            SFA_TRY(copy_rows_on(ctx, su + k * pl, (size_t)p.w * 4, U[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice));
+            SFA_TRY(copy_rows_on(ctx, sv + k * pl, (size_t)p.w * 4, V[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice));
         }
         launch_interleave(ctx, su, sv, reinterpret_cast<float2 *>(dst), (size_t)rJ * pl);
         SFA_HIP(ctx, hipGetLastError());
     }
-    if (p.use_occlusions)
-        SFA_TRY(jet_decode_occlusions(ctx, src, (size_t)rJ, occ, p.w, p.h, job->ptr<unsigned char>(job->at.occ_stage),
-                                      job->ptr<unsigned char>(job->at.rate[r].mask) + seg));
+    if (p.use_occlusions) SFA_TRY(jet_decode_occlusions(ctx, src, (size_t)rJ, occ, p.w, p.h, job->ptr(job->at.occ_stage), job->ptr(a.mask) + seg));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // the caller's planes are free again
     return SFA_OK;
 }
@@ -477,11 +362,11 @@ int sfa_track_job_upload_frames(sfa_track_job *job, int s, const float *const *f
     for (int k = 0; k <= p.Jets; k++)
         if (!frames[k]) REFUSE("%s: null frame %d", __func__, k);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    float *dst = job->ptr<float>(job->at.frames) + (size_t)s * (p.Jets + 1) * 3 * pl;
+    float *dst = job->ptr(job->at.frames) + (size_t)s * (p.Jets + 1) * 3 * pl;
     for (int k = 0; k <= p.Jets; k++)
         for (int c = 0; c < 3; c++)
-            SFA_HIP(ctx, hipMemcpy2DAsync(dst + ((size_t)k * 3 + c) * pl, (size_t)p.w * 4, frames[k] + (size_t)c * p.h * stride, (size_t)stride * 4, (size_t)p.w * 4,
-                                          p.h, hipMemcpyHostToDevice, ctx->stream));
+            SFA_TRY(copy_rows_on(ctx, dst + ((size_t)k * 3 + c) * pl, (size_t)p.w * 4, frames[k] + (size_t)c * p.h * stride, (size_t)stride * 4, (size_t)p.w * 4, p.h,
+                                 hipMemcpyHostToDevice));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;
 }
@@ -495,10 +380,10 @@ int sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r,
     SFA_TRY(check_view(ctx, __func__, View{"bwd_dev", bwd_dev, sizeof(float), 5, {ns, rJ, 2, src.sh, src.sw}, strides}));
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const bool identity = job->identity[r];
-    const size_t tap = identity ? 8 : 16, seg = (size_t)rJ * pl;
+    const size_t tap = identity ? sizeof(float2) : sizeof(double2), seg = (size_t)rJ * pl;
     for (int dir = 0; dir < 2; dir++) {
         const float *from = dir ? bwd_dev : fwd_dev;
-        char *dst = job->ptr<char>(dir ? job->at.rate[r].bw : job->at.rate[r].fw) + (size_t)s0 * seg * tap;
+        char *dst = job->ptr(dir ? job->at.rate[r].bw : job->at.rate[r].fw) + (size_t)s0 * seg * tap;
         if (identity) {
             const size_t total = (size_t)ns * seg;
             hipLaunchKernelGGL(k_track_pack_flow, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, from, strides[0], strides[1], strides[2], strides[3],
@@ -507,7 +392,7 @@ int sfa_track_job_upload_flows_device(sfa_track_job *job, int s0, int ns, int r,
             continue;
         }
         const size_t spl = (size_t)src.cw * src.ch, total = (size_t)rJ * spl;   // segment by segment through the one-segment stage, in stream order
-        float *su = job->ptr<float>(job->at.stage), *sv = su + total;
+        float *su = job->ptr(job->at.stage), *sv = su + total;
         for (int s = 0; s < ns; s++) {
             hipLaunchKernelGGL(k_track_pack_planes, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, from + (long long)s * strides[0], strides[1], strides[2],
                                strides[3], strides[4], src.x0, src.y0, src.cw, src.ch, su, sv, total);
@@ -530,7 +415,7 @@ int sfa_track_job_upload_occlusions_device(sfa_track_job *job, int s0, int ns, i
     SFA_TRY(check_view(ctx, __func__, View{"occ_dev", occ_dev, dtype == SFA_DEV_F32 ? sizeof(float) : 1, 4, {ns, rJ, src.sh, src.sw}, strides}));
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const size_t total = (size_t)rJ * src.sw * src.sh;                          // segment by segment through the one-segment stage, in stream order
-    unsigned char *stage = job->ptr<unsigned char>(job->at.occ_stage), *mask = job->ptr<unsigned char>(job->at.rate[r].mask) + (size_t)s0 * rJ * pl;
+    unsigned char *stage = job->ptr(job->at.occ_stage), *mask = job->ptr(job->at.rate[r].mask) + (size_t)s0 * rJ * pl;
     for (int s = 0; s < ns; s++) {
         if (dtype == SFA_DEV_F32)
             hipLaunchKernelGGL(k_track_pack_occ<float>, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream,
@@ -551,155 +436,139 @@ int sfa_track_job_upload_frames_device(sfa_track_job *job, int s0, int ns, const
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const size_t total = (size_t)ns * (p.Jets + 1) * 3 * pl;
     hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, frames_dev, strides[0], strides[1], strides[2], strides[3],
-                       strides[4], p.w, p.h, p.Jets + 1, job->ptr<float>(job->at.frames) + (size_t)s0 * (p.Jets + 1) * 3 * pl, total);
+                       strides[4], p.w, p.h, p.Jets + 1, job->ptr(job->at.frames) + (size_t)s0 * (p.Jets + 1) * 3 * pl, total);
     SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;
 }
 
-// The fill-in of every rate of segments 0 .. ns-1, between the accumulation and the energies (the header's description).  It leaves the trajectories in the
-// rates' fill planes and {kept_pixels, matches, filled} in job->stats
-static int track_run_fill(sfa_track_job *job, int ns) {
+// k_track_pack_frames reads element ((segment, frame), channel, row, column): with one frame and no more than three planes, segment and frame are 0 for every
+// element, their strides are never multiplied by anything else, and the kernel packs the nc channel planes of one image
+int sfa::pack_strided_planes(sfa_ctx *ctx, const float *src, long long s_c, long long s_row, long long s_col, int w, int h, int nc, float *out) {
+    const size_t total = (size_t)nc * w * h;
+    hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, src, 0ll, 0ll, s_c, s_row, s_col, w, h, 1, out, total);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
+// ---- the stages of a run: each enqueues its part on the context's stream and records the event behind it ----------------------------------------------------
+static int run_records(sfa_track_job *job, int ns) {
     TRACK_JOB(job);
     const TrackPlanes &at = job->at;
-    const FillGeo &g = job->fg;
-    const sfa_track_fill_params &fp = job->fp;
-    hipStream_t st = ctx->stream;
-    const int gw = job->gw, gh = job->gh, n = p.n;
-    const size_t samples = (size_t)g.nx * g.ny;
-    float *run_cost = job->ptr<float>(at.run_cost), *cost = job->ptr<float>(at.cost), *matches = job->ptr<float>(at.matches);
-    float *fx = job->ptr<float>(at.fx), *fy = job->ptr<float>(at.fy);
-    // the running maps start from the maps as uploaded: a run leaves them advanced by all its calls
-    SFA_TRY(copy_on(ctx, run_cost, job->ptr<float>(at.edges), (size_t)ns * g.cpl * 4, hipMemcpyDeviceToDevice));
-    const size_t images = (size_t)n * g.rJmax;
-    const float **c_cost = job->c_in.get(), **c_matches = c_cost + images, **c_sal = c_matches + images;
-    float **c_fx = job->c_out.get(), **c_fy = c_fx + images;
-    int *c_nm = job->c_int.get(), *seg_of = c_nm + images, *step_of = seg_of + images, *rc = step_of + images, *status = rc + images, *kept = status + images,
-        *count = kept + n;
-    job->chain_runs[0] = job->chain_runs[1] = 0;
+    energy_records_device(ctx, (size_t)ns * (p.Jets + 1), p.w, p.h, job->ptr(at.frames), job->ptr(at.der), job->ptr(at.rec));
+    SFA_HIP(ctx, hipGetLastError());
+    return mark(ctx, job->ev[kEvRecords]);
+}
+
+static int run_accumulation(sfa_track_job *job, int ns) {
+    TRACK_JOB(job);
     for (int r = 0; r < p.K; r++) {
-        const int rJ = p.r_Jets[r];
-        hipEvent_t *ev = job->fev[r];
-        int *stats = job->stats.get() + (size_t)r * n * 3;
-        const double *acc_u = job->ptr<double>(at.rate[r].acc_u), *acc_v = job->ptr<double>(at.rate[r].acc_v);
-        // ---- r_consistent after removeSmallSegments, the matches of every step; the one host read this stage adds
-        SFA_TRY(mark(ctx, ev[0]));
-        SFA_TRY(consistent_regions_device(ctx, ns, gw, gh, job->ptr<int>(at.rate[r].tracked), job->ptr<int>(at.full) + (size_t)r * n, fp.min_size, job->ptr<int>(at.cT),
-                                          job->ptr<int>(at.cP), job->ptr<int>(at.cS), job->ptr<unsigned char>(at.mask), job->ptr<int>(at.kept)));
-        if (samples)
-            SFA_TRY(fill_matches_device(ctx, ns, rJ, gw, gh, acc_u, acc_v, job->ptr<unsigned char>(at.mask), job->ptr<int>(at.xs), g.nx, job->ptr<int>(at.ys), g.ny,
-                                        p.skip + 1, job->ptr<int>(at.block_count), matches, job->ptr<int>(at.count)));
-        SFA_TRY(copy_on(ctx, kept, job->ptr<int>(at.kept), (size_t)ns * 4, hipMemcpyDeviceToHost));
-        if (samples) SFA_TRY(copy_on(ctx, count, job->ptr<int>(at.count), (size_t)ns * 4, hipMemcpyDeviceToHost));
-        SFA_TRY(mark(ctx, ev[1]));
-        SFA_HIP(ctx, hipStreamSynchronize(st));
-        if (!samples) std::fill(count, count + ns, 0);                 // no sample on the grid: no match
-        // ---- the edge costs of the rate's steps, for every segment: the calls count whether or not a rate is filled
-        SFA_TRY(epic_edge_costs_device(ctx, ns, rJ, g.cpl, (int)gpl, fp.epic.euc, run_cost, cost));
-        SFA_TRY(mark(ctx, ev[2]));
-        // ---- the interpolation of the images of every segment with a match, segment-major
-        int m = 0;
-        for (int s = 0; s < ns; s++) {
-            stats[3 * s] = kept[s]; stats[3 * s + 1] = count[s]; stats[3 * s + 2] = count[s] > 0;
-            for (int j = 0; j < rJ && count[s] > 0; j++, m++) {
-                const size_t k = (size_t)s * rJ + j;
-                c_cost[m] = cost + k * g.cpl; c_matches[m] = matches + k * samples * 4; c_nm[m] = count[s];
-                c_sal[m] = fp.epic.saliency_th != 0 ? job->ptr<float>(at.sal) + (size_t)s * g.plp : nullptr;
-                c_fx[m] = fx + k * gpl; c_fy[m] = fy + k * gpl;
-                seg_of[m] = s; step_of[m] = j;
-            }
-        }
-        if (m) {
-            const EpicChainDev io{c_cost, c_matches, c_nm, c_sal, c_fx, c_fy};
-            SFA_TRY(epic_chain_device(ctx, "sfa_track_job_run", m, gw, gh, &fp.epic, io, rc, nullptr, fp.workspace_bytes, status));
-            for (int k = 0; k < 2; k++) job->chain_runs[k] += ctx->epic_chain_runs[k];
-            for (int k = 0; k < m; k++) {
-                if (status[k])
-                    REFUSE("sfa_track_job_run: the fill-in image of start_jet %d, rate %d, step %d (%d matches) does not fit the interpolation's workspace even alone",
-                           seg_of[k], r, step_of[k], c_nm[k]);
-                if (rc[k] > 0) stats[3 * seg_of[k] + 2] = 0;                     // a step without a usable match: no fill-in hypothesis for the rate
-            }
-        }
-        SFA_TRY(mark(ctx, ev[3]));
-        // ---- the planes as trajectories; a segment that is not filled gets zeros (its slot is emptied after the energies)
-        for (int s = 0; s < ns; s++) {
-            if (stats[3 * s + 2]) continue;
-            SFA_TRY(zero_on(ctx, fx + (size_t)s * rJ * gpl, (size_t)rJ * gpl * 4));
-            SFA_TRY(zero_on(ctx, fy + (size_t)s * rJ * gpl, (size_t)rJ * gpl * 4));
-        }
-        SFA_TRY(fill_trajectories_device(ctx, ns, rJ, gw, gh, gw, fx, fy, p.skip + 1, job->ptr<double>(at.fill[r].u), job->ptr<double>(at.fill[r].v),
-                                         job->ptr<int>(at.fill[r].tracked)));
-        SFA_TRY(mark(ctx, ev[4]));
+        const TrackPlanes::Rate &a = job->at.rate[r];
+        SFA_TRY(accumulate_device(ctx, ns, p.r_Jets[r], p.w, p.h, job->gw, job->gh, p.skip, job->identity[r], job->ptr(a.fw), job->ptr(a.bw),
+                                  p.use_occlusions ? job->ptr(a.mask) : nullptr, p.epsilon, p.discard, 1, job->ptr(a.acc_u), job->ptr(a.acc_v), job->ptr(a.tracked)));
     }
-    SFA_TRY(mark(ctx, job->ev_energy));
+    return mark(ctx, job->ev[kEvAccumulated]);
+}
+
+static EnergyWork energy_work(const sfa_track_job *job) {
+    const TrackPlanes &at = job->at;
+    EnergyWork wk;
+    wk.U = job->ptr(at.wU); wk.V = job->ptr(at.wV); wk.occ = job->ptr(at.wocc);
+    wk.jc = job->ptr(at.jc); wk.oc = job->ptr(at.oc); wk.ep = job->ptr(at.ep);
+    return wk;
+}
+
+// The energies, occlusion words and adapted flows of one hypothesis of rate r -- the trajectories u, v [ns][r_Jets[r]][gpl] and tracked -- into slot `slot` of
+// the fusion's planes: the rate's plan and weight, and rate min_fps_idx's flows
+static int slot_energies(sfa_track_job *job, int ns, int r, Plane<double> u, Plane<double> v, Plane<int> tracked, size_t slot) {
+    TRACK_JOB(job);
+    const TrackPlanes &at = job->at;
+    const TrackPlanes::Rate &mf = at.rate[p.min_fps_idx];
+    const size_t S = job->slots(), J = p.Jets;
+    const bool flows = r >= p.min_fps_idx;                                      // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
+    return energies_device(ctx, job->plan[r], ns, job->ptr(u), job->ptr(v), job->ptr(tracked), job->ptr(at.rec), job->identity[p.min_fps_idx],
+                           flows ? job->ptr(mf.fw) : nullptr, flows ? job->ptr(mf.bw) : nullptr, energy_work(job), job->ptr(at.E) + slot * gpl,
+                           job->ptr(at.O) + slot * gpl, S * gpl, p.do_fuse ? job->ptr(at.aU) + slot * J * gpl : nullptr,
+                           p.do_fuse ? job->ptr(at.aV) + slot * J * gpl : nullptr, S * J * gpl);
+}
+
+// segment s's slot of a hypothesis that does not exist: energy +Inf, occlusion word 0, adapted flows 0
+static int empty_slot(sfa_track_job *job, int s, size_t slot) {
+    TRACK_JOB(job);
+    const TrackPlanes &at = job->at;
+    const size_t J = p.Jets, o = ((size_t)s * job->slots() + slot) * gpl;
+    SFA_TRY(copy_on(ctx, job->ptr(at.E) + o, job->ptr(at.inf), gpl * sizeof(double), hipMemcpyDeviceToDevice));
+    SFA_TRY(zero_on(ctx, job->ptr(at.O) + o, gpl * sizeof(unsigned long long)));
+    if (!p.do_fuse) return SFA_OK;
+    SFA_TRY(zero_on(ctx, job->ptr(at.aU) + o * J, J * gpl * sizeof(double)));
+    return zero_on(ctx, job->ptr(at.aV) + o * J, J * gpl * sizeof(double));
+}
+
+// rate r's accumulated hypothesis is slot r * step; on a fill job its fill-in is the next, emptied for the segments the last fill-in left unfilled
+static int run_energies(sfa_track_job *job, int ns) {
+    const sfa_track_params &p = job->p;
+    for (int r = 0; r < p.K; r++) {
+        const TrackPlanes::Rate &a = job->at.rate[r];
+        const TrackPlanes::Fill &f = job->at.fill[r];
+        const size_t slot = (size_t)r * job->step();
+        SFA_TRY(slot_energies(job, ns, r, a.acc_u, a.acc_v, a.tracked, slot));
+        if (!job->fill) continue;
+        SFA_TRY(slot_energies(job, ns, r, f.u, f.v, f.tracked, slot + 1));
+        for (int s = 0; s < ns; s++)
+            if (!job->fill->stats[((size_t)r * p.n + s) * 3 + 2]) SFA_TRY(empty_slot(job, s, slot + 1));
+    }
     return SFA_OK;
+}
+
+static int run_best(sfa_track_job *job, int ns) {
+    TRACK_JOB(job);
+    const TrackPlanes &at = job->at;
+    hipLaunchKernelGGL(k_track_best, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr(at.E), job->ptr(at.O), p.K, job->slots(), job->step(),
+                       (int)gpl, p.n, job->ptr(at.best), job->ptr(at.occluded));
+    SFA_HIP(ctx, hipGetLastError());
+    return mark(ctx, job->ev[kEvBest]);
+}
+
+// computeSmoothnessWeight of every segment's normalised frame 0 (sfa_dt_smoothness_weight's kernel) on the packed planes
+static int run_weight(sfa_track_job *job, int ns) {
+    TRACK_JOB(job);
+    Geo g{p.w, p.h, p.w, (long)pl, (long)pl, ns, WMask::first(ns), nullptr};
+    launch_dpsis(ctx, g, job->ptr(job->at.weight), job->ptr(job->at.frames), (long)((size_t)(p.Jets + 1) * 3 * pl), p.coef, p.avg, p.std_dev, p.hbit);
+    SFA_HIP(ctx, hipGetLastError());
+    return mark(ctx, job->ev[kEvWeight]);
+}
+
+static FuseWork fuse_work(const sfa_track_job *job) {
+    const TrackPlanes &at = job->at;
+    FuseWork f;
+    f.U = job->ptr(at.aU); f.V = job->ptr(at.aV); f.energy = job->ptr(at.E); f.occ = job->ptr(at.O); f.weight = job->ptr(at.weight);
+    f.nl = job->ptr(at.nl); f.lab = job->ptr(at.lab); f.theta = job->ptr(at.theta); f.P = job->ptr(at.P);
+    f.M = job->ptr(at.M); f.xcur = job->ptr(at.xcur); f.xbest = job->ptr(at.xbest);
+    f.slot = job->ptr(at.slot); f.fu = job->ptr(at.fu); f.fv = job->ptr(at.fv); f.out_occ = job->ptr(at.out_occ);
+    f.seg_energy = job->ptr(at.seg_energy); f.seg_bound = job->ptr(at.seg_bound); f.seg_iters = job->ptr(at.seg_iters);
+    return f;
+}
+
+// labels -> pairwise -> TRW-S -> output; fuse_device records kEvFuse .. kEvFuseEnd around the four
+static int run_fusion(sfa_track_job *job, int ns) {
+    TRACK_JOB(job);
+    return fuse_device(ctx, &p.fuse, ns, job->slots(), p.Jets, p.w, p.h, job->gw, job->gh, fuse_work(job), job->ev + kEvFuse);
 }
 
 int sfa_track_job_run(sfa_track_job *job, int ns) {
     TRACK_JOB(job);
     if (ns < 1 || ns > p.n) REFUSE("%s: ns = %d (1 <= ns <= n = %d, the job's start_jets)", __func__, ns, p.n);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    const TrackPlanes &at = job->at;
-    const int K = p.K, J = p.Jets, mf = p.min_fps_idx;
-    hipEvent_t *ev = job->ev;
-    SFA_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
-    energy_records_device(ctx, (size_t)ns * (J + 1), p.w, p.h, job->ptr<float>(at.frames), job->ptr<float>(at.der), job->ptr<void>(at.rec));
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-    for (int r = 0; r < K; r++)
-        SFA_TRY(accumulate_device(ctx, ns, p.r_Jets[r], p.w, p.h, job->gw, job->gh, p.skip, job->identity[r], job->ptr<void>(at.rate[r].fw),
-                                  job->ptr<void>(at.rate[r].bw), p.use_occlusions ? job->ptr<unsigned char>(at.rate[r].mask) : nullptr, p.epsilon, p.discard, 1,
-                                  job->ptr<double>(at.rate[r].acc_u), job->ptr<double>(at.rate[r].acc_v), job->ptr<int>(at.rate[r].tracked)));
-    SFA_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+    SFA_TRY(mark(ctx, job->ev[kEvStart]));
+    SFA_TRY(run_records(job, ns));
+    SFA_TRY(run_accumulation(job, ns));
     if (job->fill) SFA_TRY(track_run_fill(job, ns));
-    const int S = job->slots(), step = job->step();                            // rate r's accumulated hypothesis is slot r * step, its fill-in the next
-    EnergyWork wk;
-    wk.U = job->ptr<double>(at.wU); wk.V = job->ptr<double>(at.wV); wk.occ = job->ptr<unsigned long long>(at.wocc);
-    wk.jc = job->ptr<float>(at.jc); wk.oc = job->ptr<float>(at.oc); wk.ep = job->ptr<double>(at.ep);
-    double *E = job->ptr<double>(at.E);
-    unsigned long long *O = job->ptr<unsigned long long>(at.O);
-    for (int r = 0; r < K; r++) {
-        const bool flows = r >= mf;                                             // a rate before acc_min_fps sees empty flow Mats (:786, :1148-1151)
-        SFA_TRY(energies_device(ctx, job->plan[r], ns, job->ptr<double>(at.rate[r].acc_u), job->ptr<double>(at.rate[r].acc_v), job->ptr<int>(at.rate[r].tracked),
-                                job->ptr<void>(at.rec), job->identity[mf], flows ? job->ptr<void>(at.rate[mf].fw) : nullptr,
-                                flows ? job->ptr<void>(at.rate[mf].bw) : nullptr, wk, E + (size_t)r * step * gpl, O + (size_t)r * step * gpl, (size_t)S * gpl,
-                                p.do_fuse ? job->ptr<double>(at.aU) + (size_t)r * step * J * gpl : nullptr,
-                                p.do_fuse ? job->ptr<double>(at.aV) + (size_t)r * step * J * gpl : nullptr, (size_t)S * J * gpl));
-        if (!job->fill) continue;
-        const size_t slot = 2 * (size_t)r + 1;                                  // the fill-in: the rate's plan and weight, the same flows
-        double *aU = p.do_fuse ? job->ptr<double>(at.aU) + slot * J * gpl : nullptr, *aV = p.do_fuse ? job->ptr<double>(at.aV) + slot * J * gpl : nullptr;
-        SFA_TRY(energies_device(ctx, job->plan[r], ns, job->ptr<double>(at.fill[r].u), job->ptr<double>(at.fill[r].v), job->ptr<int>(at.fill[r].tracked),
-                                job->ptr<void>(at.rec), job->identity[mf], flows ? job->ptr<void>(at.rate[mf].fw) : nullptr,
-                                flows ? job->ptr<void>(at.rate[mf].bw) : nullptr, wk, E + slot * gpl, O + slot * gpl, (size_t)S * gpl, aU, aV, (size_t)S * J * gpl));
-        for (int s = 0; s < ns; s++) {
-            if (job->stats[((size_t)r * p.n + s) * 3 + 2]) continue;
-            const size_t so = (size_t)s * S * gpl, sa = (size_t)s * S * J * gpl;
-            // the slot of a hypothesis that does not exist: energy +Inf, occlusion word 0, adapted flows 0
-            SFA_TRY(copy_on(ctx, E + slot * gpl + so, job->ptr<double>(at.inf), gpl * 8, hipMemcpyDeviceToDevice));
-            SFA_TRY(zero_on(ctx, O + slot * gpl + so, gpl * 8));
-            if (aU) SFA_TRY(zero_on(ctx, aU + sa, (size_t)J * gpl * 8));
-            if (aV) SFA_TRY(zero_on(ctx, aV + sa, (size_t)J * gpl * 8));
-        }
-    }
-    const dim3 pix(blocks_of(gpl), (unsigned)ns);
-    hipLaunchKernelGGL(k_track_best, pix, dim3(kTrThreads), 0, ctx->stream, E, O, K, S, step, (int)gpl, p.n, job->ptr<unsigned char>(at.best),
-                       job->ptr<unsigned char>(at.occluded));
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
+    SFA_TRY(run_energies(job, ns));
+    SFA_TRY(run_best(job, ns));
     job->timed = true;
     job->timed_fuse = false;
     if (!p.do_fuse) return SFA_OK;
-    // computeSmoothnessWeight of every segment's normalised frame 0 (sfa_dt_smoothness_weight's kernel) on the packed planes
-    Geo g{p.w, p.h, p.w, (long)pl, (long)pl, ns, WMask::first(ns), nullptr};
-    launch_dpsis(ctx, g, job->ptr<float>(at.weight), job->ptr<float>(at.frames), (long)((size_t)(J + 1) * 3 * pl), p.coef, p.avg, p.std_dev, p.hbit);
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, hipEventRecord(ev[9], ctx->stream));
-    FuseWork f;
-    f.U = job->ptr<double>(at.aU); f.V = job->ptr<double>(at.aV); f.energy = E; f.occ = O; f.weight = job->ptr<float>(at.weight);
-    f.nl = job->ptr<unsigned char>(at.nl); f.lab = job->ptr<unsigned char>(at.lab); f.theta = job->ptr<double>(at.theta); f.P = job->ptr<double>(at.P);
-    f.M = job->ptr<double>(at.M); f.xcur = job->ptr<unsigned char>(at.xcur); f.xbest = job->ptr<unsigned char>(at.xbest);
-    f.slot = job->ptr<int>(at.slot); f.fu = job->ptr<double>(at.fu); f.fv = job->ptr<double>(at.fv); f.out_occ = job->ptr<unsigned char>(at.out_occ);
-    f.seg_energy = job->ptr<double>(at.seg_energy); f.seg_bound = job->ptr<double>(at.seg_bound); f.seg_iters = job->ptr<int>(at.seg_iters);
-    SFA_TRY(fuse_device(ctx, &p.fuse, ns, S, J, p.w, p.h, job->gw, job->gh, f, ev + 4));
+    SFA_TRY(run_weight(job, ns));
+    SFA_TRY(run_fusion(job, ns));
     job->timed_fuse = true;
     return SFA_OK;
 }
@@ -711,13 +580,12 @@ int sfa_track_job_download_rate(sfa_track_job *job, int s, int r, double *acc_u_
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const TrackPlanes::Rate &a = job->at.rate[r];
     const size_t last = ((size_t)s * p.r_Jets[r] + (p.r_Jets[r] - 1)) * gpl, sk = ((size_t)s * job->slots() + (size_t)r * job->step()) * gpl;
-    auto get = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    SFA_HIP(ctx, get(acc_u_last, job->ptr<double>(a.acc_u) + last, gpl * 8));
-    SFA_HIP(ctx, get(acc_v_last, job->ptr<double>(a.acc_v) + last, gpl * 8));
-    SFA_HIP(ctx, get(tracked, job->ptr<int>(a.tracked) + (size_t)s * gpl, gpl * 4));
-    SFA_HIP(ctx, get(energy, job->ptr<double>(job->at.E) + sk, gpl * 8));
-    SFA_HIP(ctx, get(occ_bits, job->ptr<unsigned long long>(job->at.O) + sk, gpl * 8));
-    SFA_HIP(ctx, get(occluded, job->ptr<unsigned char>(job->at.occluded) + ((size_t)r * p.n + s) * gpl, gpl));
+    SFA_TRY(download(ctx, acc_u_last, job->ptr(a.acc_u) + last, gpl * 8));
+    SFA_TRY(download(ctx, acc_v_last, job->ptr(a.acc_v) + last, gpl * 8));
+    SFA_TRY(download(ctx, tracked, job->ptr(a.tracked) + (size_t)s * gpl, gpl * 4));
+    SFA_TRY(download(ctx, energy, job->ptr(job->at.E) + sk, gpl * 8));
+    SFA_TRY(download(ctx, occ_bits, job->ptr(job->at.O) + sk, gpl * 8));
+    SFA_TRY(download(ctx, occluded, job->ptr(job->at.occluded) + ((size_t)r * p.n + s) * gpl, gpl));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;
 }
@@ -730,15 +598,14 @@ int sfa_track_job_download_fused(sfa_track_job *job, int s, int *slot, double *f
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const TrackPlanes &at = job->at;
     const size_t o = (size_t)s * gpl;
-    auto get = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    SFA_HIP(ctx, get(slot, job->ptr<int>(at.slot) + o, gpl * 4));
-    SFA_HIP(ctx, get(flow_u, job->ptr<double>(at.fu) + o, gpl * 8));
-    SFA_HIP(ctx, get(flow_v, job->ptr<double>(at.fv) + o, gpl * 8));
-    SFA_HIP(ctx, get(occ, job->ptr<unsigned char>(at.out_occ) + o, gpl));
-    SFA_HIP(ctx, get(best, job->ptr<unsigned char>(at.best) + o, gpl));
-    SFA_HIP(ctx, get(energy, job->ptr<double>(at.seg_energy) + s, 8));
-    SFA_HIP(ctx, get(bound, job->ptr<double>(at.seg_bound) + s, 8));
-    SFA_HIP(ctx, get(iters, job->ptr<int>(at.seg_iters) + s, 4));
+    SFA_TRY(download(ctx, slot, job->ptr(at.slot) + o, gpl * 4));
+    SFA_TRY(download(ctx, flow_u, job->ptr(at.fu) + o, gpl * 8));
+    SFA_TRY(download(ctx, flow_v, job->ptr(at.fv) + o, gpl * 8));
+    SFA_TRY(download(ctx, occ, job->ptr(at.out_occ) + o, gpl));
+    SFA_TRY(download(ctx, best, job->ptr(at.best) + o, gpl));
+    SFA_TRY(download(ctx, energy, job->ptr(at.seg_energy) + s, 8));
+    SFA_TRY(download(ctx, bound, job->ptr(at.seg_bound) + s, 8));
+    SFA_TRY(download(ctx, iters, job->ptr(at.seg_iters) + s, 4));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;
 }
@@ -748,7 +615,7 @@ int sfa_track_job_download_best(sfa_track_job *job, int s, unsigned char *best) 
     SFA_TRY(track_range(ctx, __func__, p, s, 1, 0));
     if (!best) REFUSE("%s: best is null", __func__);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    SFA_HIP(ctx, hipMemcpyAsync(best, job->ptr<unsigned char>(job->at.best) + (size_t)s * gpl, gpl, hipMemcpyDeviceToHost, ctx->stream));
+    SFA_TRY(download(ctx, best, job->ptr(job->at.best) + (size_t)s * gpl, gpl));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;
 }
@@ -779,9 +646,9 @@ int sfa_track_job_download_device(sfa_track_job *job, int s0, int ns, double *fl
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     const TrackPlanes &at = job->at;
     const size_t o = (size_t)s0 * gpl;
-    hipLaunchKernelGGL(k_track_unpack, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr<double>(at.fu) + o, job->ptr<double>(at.fv) + o,
-                       job->ptr<int>(at.slot) + o, job->ptr<unsigned char>(at.out_occ) + o, job->ptr<double>(at.seg_energy) + s0, job->ptr<double>(at.seg_bound) + s0,
-                       job->ptr<int>(at.seg_iters) + s0, job->gw, (int)gpl, flow_dev, strides[0], strides[1], strides[2], strides[3], slot_dev, occ_dev, stats_dev);
+    hipLaunchKernelGGL(k_track_unpack, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr(at.fu) + o, job->ptr(at.fv) + o,
+                       job->ptr(at.slot) + o, job->ptr(at.out_occ) + o, job->ptr(at.seg_energy) + s0, job->ptr(at.seg_bound) + s0, job->ptr(at.seg_iters) + s0, job->gw,
+                       (int)gpl, flow_dev, strides[0], strides[1], strides[2], strides[3], slot_dev, occ_dev, stats_dev);
     SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;
 }
@@ -807,12 +674,11 @@ static int track_unpack_rate(sfa_track_job *job, const char *fn, int s0, int ns,
     const TrackPlanes &at = job->at;
     const TrackPlanes::Rate &a = at.rate[r];
     const size_t rJ = p.r_Jets[r], last = ((size_t)s0 * rJ + (rJ - 1)) * gpl, sk = ((size_t)s0 * job->slots() + (size_t)r * job->step()) * gpl;
-    const unsigned char *from = best ? job->ptr<unsigned char>(at.best) + (size_t)s0 * gpl : job->ptr<unsigned char>(at.occluded) + ((size_t)r * p.n + s0) * gpl;
+    const unsigned char *from = best ? job->ptr(at.best) + (size_t)s0 * gpl : job->ptr(at.occluded) + ((size_t)r * p.n + s0) * gpl;
     const long long none[4] = {0, 0, 0, 0}, *st = acc_dev ? strides : none;
-    hipLaunchKernelGGL(k_track_unpack_rate, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr<double>(a.acc_u) + last,
-                       job->ptr<double>(a.acc_v) + last, rJ * gpl, job->ptr<int>(a.tracked) + (size_t)s0 * gpl, gpl, job->ptr<double>(at.E) + sk,
-                       job->ptr<unsigned long long>(at.O) + sk, (size_t)job->slots() * gpl, from, gpl, job->gw, (int)gpl, acc_dev, st[0], st[1], st[2], st[3], tracked_dev,
-                       energy_dev, occ_bits_dev, bytes_dev);
+    hipLaunchKernelGGL(k_track_unpack_rate, dim3(blocks_of(gpl), (unsigned)ns), dim3(kTrThreads), 0, ctx->stream, job->ptr(a.acc_u) + last, job->ptr(a.acc_v) + last,
+                       rJ * gpl, job->ptr(a.tracked) + (size_t)s0 * gpl, gpl, job->ptr(at.E) + sk, job->ptr(at.O) + sk, (size_t)job->slots() * gpl, from, gpl, job->gw,
+                       (int)gpl, acc_dev, st[0], st[1], st[2], st[3], tracked_dev, energy_dev, occ_bits_dev, bytes_dev);
     SFA_HIP(ctx, hipGetLastError());
     return SFA_OK;
 }
@@ -837,114 +703,17 @@ int sfa_track_job_stage_ms(sfa_track_job *job, float ms[8]) {
     if (!job->timed) REFUSE("%s: the job has not run", __func__);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const hipEvent_t *e = job->ev;
+    const hipEvent_t span[8][2] = {
+        {e[kEvStart], e[kEvRecords]},                                           // derivatives and records
+        {e[kEvRecords], e[kEvAccumulated]},                                     // accumulation
+        {job->fill ? job->fill->ev_energy : e[kEvAccumulated], e[kEvBest]},     // energies, best / occluded: on a fill job from where its fill-in ends
+        {e[kEvBest], e[kEvWeight]},                                             // the weight kernel alone, without the fusion's clears behind it
+        {e[kEvFuse], e[kEvFuse + 1]}, {e[kEvFuse + 1], e[kEvFuse + 2]}, {e[kEvFuse + 2], e[kEvFuse + 3]}, {e[kEvFuse + 3], e[kEvFuseEnd]},
+    };
     for (int i = 0; i < 8; i++) ms[i] = 0;
     const int last = job->timed_fuse ? 8 : 3;
-    for (int i = 0; i < last; i++)                                              // ms[3]: the weight kernel alone, without the fusion's clears behind it
-        SFA_HIP(ctx, hipEventElapsedTime(&ms[i], i == 2 && job->fill ? job->ev_energy : job->ev[i], job->ev[i == 3 ? 9 : i + 1]));
-    return SFA_OK;
-}
-
-// ---- a fill job's own entry points ------------------------------------------------------------------------------------------------------------------------
-#define FILL_JOB(job) \
-    TRACK_JOB(job); \
-    if (!(job)->fill) REFUSE("%s: the job was not created by sfa_track_job_create_fill: it holds no fill-in", __func__); \
-    const FillGeo &g = (job)->fg; \
-    const bool saliency = (job)->fp.epic.saliency_th != 0; \
-    (void)g; (void)saliency
-
-// the saliency of the Lab image in the workspace's first three planes -> segment s's plane
-static int track_saliency(sfa_track_job *job, int s) {
-    sfa_ctx *ctx = job->ctx;
-    const FillGeo &g = job->fg;
-    float *stage = job->ptr<float>(job->at.lab_stage);
-    const Geo geo{job->gw, job->gh, g.pitch, (long)g.plp, (long)(kEpicSaliencyPlanes * g.plp), 1, WMask::first(1), nullptr};
-    epic_saliency_device(ctx, geo, stage, 0.8f, 1.0f);                          // epic()'s saliency(im, 0.8f, 1.0f)
-    SFA_HIP(ctx, hipGetLastError());
-    SFA_TRY(copy_on(ctx, job->ptr<float>(job->at.sal) + (size_t)s * g.plp, stage + (size_t)kEpicSaliencyOut * g.plp, g.plp * 4, hipMemcpyDeviceToDevice));
-    return SFA_OK;
-}
-
-int sfa_track_job_upload_fill(sfa_track_job *job, int s, const float *lab, int lab_stride, const float *edges) {
-    FILL_JOB(job);
-    SFA_TRY(track_range(ctx, __func__, p, s, 1, 0));
-    if (!edges) REFUSE("%s: edges is null", __func__);
-    if (saliency && !lab) REFUSE("%s: lab is null (epic.saliency_th != 0: the saliency filter reads the Lab image)", __func__);
-    if (saliency && lab_stride < job->gw) REFUSE("%s: lab_stride = %d < gw = %d", __func__, lab_stride, job->gw);
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    if (saliency) {
-        for (int c = 0; c < 3; c++)
-            SFA_TRY(upload_plane(ctx, job->ptr<float>(job->at.lab_stage) + (size_t)c * g.plp, g.pitch, lab + (size_t)c * job->gh * lab_stride, lab_stride, job->gw, job->gh));
-        SFA_TRY(track_saliency(job, s));
-    }
-    SFA_TRY(copy_on(ctx, job->ptr<float>(job->at.edges) + (size_t)s * g.cpl, edges, gpl * 4, hipMemcpyHostToDevice));
-    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // the caller's planes are free again
-    return SFA_OK;
-}
-
-int sfa_track_job_upload_fill_device(sfa_track_job *job, int s0, int ns, const float *lab_dev, const long long lab_strides[4], const float *edges_dev,
-                                     const long long edge_strides[3]) {
-    FILL_JOB(job);
-    SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
-    if (saliency) SFA_TRY(check_view(ctx, __func__, View{"lab_dev", lab_dev, sizeof(float), 4, {ns, 3, job->gh, job->gw}, lab_strides}));
-    SFA_TRY(check_view(ctx, __func__, View{"edges_dev", edges_dev, sizeof(float), 3, {ns, job->gh, job->gw}, edge_strides}));
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    for (int s = 0; saliency && s < ns; s++) {                                  // segment by segment through the one workspace, in stream order
-        // packed by the frames' kernel (one frame of three channels) into planes the saliency only uses as scratch, then row by row to the device pitch
-        const size_t total = 3 * gpl;
-        float *stage = job->ptr<float>(job->at.lab_stage), *packed = stage + 3 * g.plp;
-        hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(total)), dim3(kTrThreads), 0, ctx->stream, lab_dev + (long long)s * lab_strides[0], 0ll, 0ll, lab_strides[1],
-                           lab_strides[2], lab_strides[3], job->gw, job->gh, 1, packed, total);
-        SFA_HIP(ctx, hipGetLastError());
-        for (int c = 0; c < 3; c++)
-            SFA_HIP(ctx, hipMemcpy2DAsync(stage + (size_t)c * g.plp, (size_t)g.pitch * 4, packed + (size_t)c * gpl, (size_t)job->gw * 4, (size_t)job->gw * 4, job->gh,
-                                          hipMemcpyDeviceToDevice, ctx->stream));
-        SFA_TRY(track_saliency(job, s0 + s));
-    }
-    for (int s = 0; s < ns; s++) {                                              // the frames' kernel again: one frame, its first channel alone
-        hipLaunchKernelGGL(k_track_pack_frames, dim3(blocks_of(gpl)), dim3(kTrThreads), 0, ctx->stream, edges_dev + (long long)s * edge_strides[0], 0ll, 0ll, 0ll,
-                           edge_strides[1], edge_strides[2], job->gw, job->gh, 1, job->ptr<float>(job->at.edges) + (size_t)(s0 + s) * g.cpl, gpl);
-        SFA_HIP(ctx, hipGetLastError());
-    }
-    return SFA_OK;
-}
-
-int sfa_track_job_download_fill(sfa_track_job *job, int s, int r, double *fill_u, double *fill_v, double *energy, unsigned long long *occ_bits, int *stats) {
-    FILL_JOB(job);
-    SFA_TRY(track_range(ctx, __func__, p, s, 1, r));
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t rJ = p.r_Jets[r], sk = ((size_t)s * job->slots() + 2 * (size_t)r + 1) * gpl;
-    auto get = [&](void *dst, const void *src, size_t bytes) { return dst ? copy_on(ctx, dst, src, bytes, hipMemcpyDeviceToHost) : (int)SFA_OK; };
-    SFA_TRY(get(fill_u, job->ptr<double>(job->at.fill[r].u) + (size_t)s * rJ * gpl, rJ * gpl * 8));
-    SFA_TRY(get(fill_v, job->ptr<double>(job->at.fill[r].v) + (size_t)s * rJ * gpl, rJ * gpl * 8));
-    SFA_TRY(get(energy, job->ptr<double>(job->at.E) + sk, gpl * 8));
-    SFA_TRY(get(occ_bits, job->ptr<unsigned long long>(job->at.O) + sk, gpl * 8));
-    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (stats)
-        for (int k = 0; k < 3; k++) stats[k] = job->stats[((size_t)r * p.n + s) * 3 + k];
-    return SFA_OK;
-}
-
-int sfa_track_job_fill_info(sfa_track_job *job, int info[2]) {
-    FILL_JOB(job);
-    if (!info) REFUSE("%s: info is null", __func__);
-    if (!job->timed) REFUSE("%s: the job has not run", __func__);
-    info[0] = job->chain_runs[0]; info[1] = job->chain_runs[1];
-    return SFA_OK;
-}
-
-int sfa_track_job_fill_ms(sfa_track_job *job, float ms[4]) {
-    FILL_JOB(job);
-    if (!ms) REFUSE("%s: ms is null", __func__);
-    if (!job->timed) REFUSE("%s: the job has not run", __func__);
-    SFA_HIP(ctx, hipSetDevice(ctx->device));
-    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 4; i++) ms[i] = 0;
-    for (int r = 0; r < p.K; r++)
-        for (int i = 0; i < 4; i++) {
-            float v = 0;
-            SFA_HIP(ctx, hipEventElapsedTime(&v, job->fev[r][i], job->fev[r][i + 1]));
-            ms[i] += v;
-        }
+    for (int i = 0; i < last; i++) SFA_HIP(ctx, hipEventElapsedTime(&ms[i], span[i][0], span[i][1]));
     return SFA_OK;
 }
 

@@ -1,4 +1,4 @@
-"""The track job that fills in (sfa_track_job_create_fill, csrc/track.hip): every segment of a run equals, bit for bit, the library's stage calls on that
+"""The track job that fills in (sfa_track_job_create_fill, csrc/track_fill.hip beside csrc/track.hip): every segment of a run equals, bit for bit, the library's stage calls on that
 segment alone -- accumulate_consistent(all_steps) -> consistent_regions -> fill_matches -> the fp32 additions of euc in numpy -> epic_batch ->
 fill_trajectories -> hypothesis_energies(adapted=True) of both kinds -> smoothness_weight -> fuse_hypotheses with 2 K slots -- and one segment also equals
 tests/host/epic_fill_tool.cpp's chain of single host epic() calls on one shared edge map, so that the comparison is not library against library only.

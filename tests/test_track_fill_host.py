@@ -1,4 +1,4 @@
-"""The host side of the track job that fills in (sfa_track_job_create_fill, csrc/track.hip): its fixed allocation against the plain job's, the refusals
+"""The host side of the track job that fills in (sfa_track_job_create_fill, csrc/track_fill.hip on csrc/track_job.h): its fixed allocation against the plain job's, the refusals
 by name, and -- on the restatements tests/accum_ref.py and tests/fill_ref.py -- that the scenes of tests/fill_inputs.py are what tests/test_track_fill.py
 takes them for: at least 100 kept pixels and 160 matches per step (the interpolation's nn: no other path of epic() is taken) where a rate is claimed to
 be filled, none where it is not."""
@@ -30,11 +30,16 @@ def test_entry_points_are_declared_and_bound():
     assert [getattr(e, k) for k, _ in sfa.EpicParams._fields_] == [getattr(d, k) for k, _ in sfa.EpicParams._fields_] and e.method == 0
 
 
+# the fill jobs' bytes of the three scenes, pinned like the plain total below: a change of the plane table (csrc/track_job.h) must not move them unseen
+FILL_BYTES = {"base": 40651264, "skip1": 6154496, "tail": 28627968}
+
+
 def test_bytes_count_the_fill_planes_and_leave_the_plain_job_alone():
     for case in (fi.BASE, fi.SKIP1, fi.TAIL):
         p = case.params()
         plain, fill = sfa.track_job_bytes(p), sfa.track_job_bytes(p, case.fill())
         assert fill > plain > 0
+        assert fill == FILL_BYTES[case.name], (case.name, fill)
         gpl = case.gw * case.gh
         # at least: the slots' energies, occlusion words and adapted flows twice, the fill-in's trajectories, the cost planes of the longest rate
         extra = case.n * gpl * (case.K * 16 + case.K * fi.JETS * 16 + sum(fi.RATES) * 16 + max(fi.RATES) * 4)
