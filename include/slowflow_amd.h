@@ -116,14 +116,18 @@ int sfa_variational_2frame_batch(sfa_ctx *ctx, int n, float *const *wx, float *c
  * nn nearest seeds on that graph.  Image i: cost[i] = w * h floats, row-major, the constant `euc` already added; seeds_xy[i] = 2 * ns[i] ints (x, y), a later
  * seed on the same pixel wins; labels[i] (out) = w * h ints, the closest seed of every pixel, -1 where none reaches; nn_index[i], nn_dist[i] (out) =
  * ns[i] * nn entries, seed q's neighbours in the order the reference's search finds them and their raw geodesic distances (no kernel applied), -1 /
- * 0x7F7F7F7F where fewer than nn exist.  Every output equals the host function's bit for bit, whatever n and the image's position; costs are non-negative.
+ * 0x7F7F7F7F where fewer than nn exist.  Every output equals the host function's bit for bit, whatever n and the image's position.
+ * THE DOMAIN of a cost is +0 ... +Inf, subnormals, FLT_MAX and +Inf included (a pixel of cost +Inf is never reached; a seed on one has every distance +Inf); -0.0
+ * counts as +0.0 and gives the bits +0.0 gives.  A NaN or a cost below 0 is refused (the host function itself is undefined there: its sort of the border lengths
+ * loses its ordering, and the search the bound its heap is sized by).  tests/test_epic_value_ranges.py walks the domain.
  * Host pointers; the call waits for its results.  The batch runs in sub-batches whose device memory (planes, the border table, the search's visited
  * sets and heaps, the heaps sized from the counted graph: 1 + min((nn - 1) * largest degree, 2 * edges) entries per seed) stays within workspace_bytes (0:
  * half of the GPU's free memory); status[i] = 0: computed, 1: image i does not fit the budget even alone -- its outputs are untouched and the caller
  * computes it on the host.  In the default mode the visited sets of an image are ns * ns floats, held for all its seeds at once; in the compact mode
  * (sfa_ctx_set_epic_search) an image is flagged only if its planes, table, rows and the search of one 64-seed workgroup exceed the budget.
  * Refused with SFA_ERR_ARG, the argument named and nothing launched: n < 1, w or h < 1, nn < 1, an ns[i] < 1, a null pointer, a seed outside the image,
- * w * h > 2^29 or ns[i] * nn > 2^31 - 1 (32-bit indices), min(w, h) > 4000 (two diagonals of the sweep live in LDS). */
+ * a cost that is NaN or below 0 (image and pixel named), w * h > 2^29 or ns[i] * nn > 2^31 - 1 (32-bit indices), min(w, h) > 4000 (two diagonals of the sweep
+ * live in LDS). */
 int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float *const *cost, const int *const *seeds_xy, const int *ns, int nn,
                                  int *const *labels, int *const *nn_index, float *const *nn_dist, size_t workspace_bytes, int *status);
 /* The kernel time of the context's last sfa_epic_nearest_seeds_batch in milliseconds, from HIP events around the launches, summed over its sub-batches:
@@ -195,6 +199,7 @@ typedef struct sfa_epic_params {
  * on the sub-batch cut or on an image's place in the batch.
  * Refused with SFA_ERR_ARG, the argument named and nothing launched: n < 1, w or h < 1, nn < 1, pref_nn < 0, a method other than 0 or 1, flow_stride < w,
  * with the saliency filter lab_stride < w or w or h <= 8 (its Gaussian), nm[i] < 0, a null pointer that is needed, a match coordinate that is not finite,
+ * a cost that is NaN or below 0 (image and pixel named; the domain of cost[i] is sfa_epic_nearest_seeds_batch's: +0 ... +Inf, -0.0 counts as +0.0),
  * w * h > 2^29, nm[i] * nn > 2^31 - 1, min(w, h) > 4000. */
 int sfa_epic_batch(sfa_ctx *ctx, int n, int w, int h, const sfa_epic_params *p, const float *const *lab, int lab_stride, const float *const *cost,
                    const float *const *matches, const int *nm, float *const *flow_x, float *const *flow_y, int flow_stride, int *rc, int (*counts)[3],
@@ -499,10 +504,13 @@ void sfa_track_fill_params_default(sfa_track_fill_params *fill);
 int  sfa_track_job_bytes_fill(const sfa_track_params *p, const sfa_track_fill_params *fill, size_t *bytes);
 int  sfa_track_job_create_fill(sfa_ctx *ctx, const sfa_track_params *p, const sfa_track_fill_params *fill, sfa_track_job **out);
 /* start_jet s of a fill job: lab = the Lab image at the grid's size, 3 planes of gh rows of lab_stride floats (NULL where epic.saliency_th == 0);
- * edges = gh * gw floats, the cost map as the edge file holds it (euc not added).  Waits: the caller's planes are free on return. */
+ * edges = gh * gw floats, the cost map as the edge file holds it (euc not added), every cost +0 ... +Inf (-0.0 counts as +0.0; sfa_epic_nearest_seeds_batch's domain): a NaN
+ * or a cost below 0 is refused with SFA_ERR_ARG, start_jet and pixel named, before anything is copied or launched.  Waits: the caller's planes are free on return. */
 int  sfa_track_job_upload_fill(sfa_track_job *job, int s, const float *lab, int lab_stride, const float *edges);
 /* The same for start_jets s0 .. s0+ns-1 from GPU memory, in stream order and without a host wait: lab_dev fp32 [ns][3][gh][gw] at lab_strides[4] (NULL
- * where epic.saliency_th == 0), edges_dev fp32 [ns][gh][gw] at edge_strides[3]. */
+ * where epic.saliency_th == 0), edges_dev fp32 [ns][gh][gw] at edge_strides[3].  The planes are not read on the host, so nothing here can
+ * test them: THE CALLER GUARANTEES that every cost is +0 ... +Inf or -0.0, never NaN or below 0 (outside it a run may end in SFA_ERR_HIP, "the search's heap met
+ * its capacity", or in lists the reference does not define). */
 int  sfa_track_job_upload_fill_device(sfa_track_job *job, int s0, int ns, const float *lab_dev, const long long lab_strides[4], const float *edges_dev,
                                       const long long edge_strides[3]);
 /* Rate r's fill-in of segment s after a run: the trajectories fill_u, fill_v [r_Jets[r]][gh][gw] (0 where not filled), energy and occ_bits [gh][gw] (slot

@@ -368,6 +368,7 @@ int sfa_epic_batch(sfa_ctx *ctx, int n, int w, int h, const sfa_epic_params *p, 
         for (size_t k = 0; k < (size_t)4 * nm[i]; k++) {
             if (!std::isfinite(matches[i][k])) REFUSE("%s: matches[%d]: match %zu holds a coordinate that is not finite", fn, i, k / 4);
         }
+        SFA_TRY(epic_check_costs(ctx, fn, "cost[%d]", i, cost[i], w, h));
     }
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     size_t budget = workspace_bytes;

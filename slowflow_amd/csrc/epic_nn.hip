@@ -6,7 +6,7 @@
 //                        of k_trws, fuse.hip).  A diagonal hands its (distance, label) on through LDS; cost and the old value of a thread's first cell are fetched
 //                        one diagonal ahead (a diagonal longer than the workgroup loads its further cells in place).  The largest decrease of a sweep is a maximum (order-independent), and the `end_iter` rule is applied by the workgroup itself
 //   k_epic_count_borders, k_epic_insert    the region graph: border pairs counted, then inserted into an open-addressing table sized from that count -- a 64-bit
-//                        key CAS plus atomicMin on the length's bit pattern (lengths are sums of distances, non-negative: unsigned order = float order)
+//                        key CAS plus atomicMin on the length's bit pattern (lengths are sums of distances, +0 and above once border_pairs has turned a -0.0 into +0.0: unsigned order = float order)
 //   k_epic_degrees, k_epic_rows, k_epic_fill, k_epic_sort_rows   adjacency rows in ascending neighbour index (keys are unique: the result does not depend on the
 //                        order the atomics ran in), the largest degree
 //   k_epic_dijkstra      one thread per (image, seed): `done` a dense row of ns floats, the heap (epic_heap.h: libstdc++'s push_heap / pop_heap) in global memory,
@@ -147,7 +147,7 @@ __device__ inline int border_pairs(const EpicImg &im, int tx, int o, unsigned lo
         const int l = im.lab[nb[k]];
         if (l == l0 || l < 0 || l >= im.ns) continue;
         key[n] = (unsigned long long)min(l0, l) | ((unsigned long long)max(l0, l) << 32);
-        len[n] = im.dmap[o] + im.dmap[nb[k]];
+        len[n] = (im.dmap[o] + im.dmap[nb[k]]) + 0.0f;                // -0.0 (two seeds' pixels of cost -0.0) becomes +0.0: k_epic_insert orders lengths by their bits
         n++;
     }
     return n;
@@ -601,6 +601,18 @@ int sfa::epic_nn_check_sizes(sfa_ctx *ctx, const char *fn, int w, int h) {
     return SFA_OK;
 }
 
+// Outside +0 ... +Inf the reference itself is undefined (a NaN among the border lengths breaks its sort's ordering) and the search loses the bound its heap
+// is sized by: `newd >= done[to]` no longer stops a walk that a negative length shortens or a NaN never compares
+int sfa::epic_check_costs(sfa_ctx *ctx, const char *fn, const char *what, int image, const float *cost, int w, int h) {
+    for (size_t p = 0; p < (size_t)w * h; p++) {
+        if (cost[p] >= 0) continue;                                  // -0.0 passes: border_pairs and the sweep treat it as +0
+        char name[64];
+        snprintf(name, sizeof name, what, image);
+        REFUSE("%s: %s: pixel (%d, %d) holds the cost %g (costs are +0 ... +Inf: not NaN, not below 0)", fn, name, (int)(p % w), (int)(p / w), (double)cost[p]);
+    }
+    return SFA_OK;
+}
+
 int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float *const *cost, const int *const *seeds_xy, const int *ns, int nn,
                                  int *const *labels, int *const *nn_index, float *const *nn_dist, size_t workspace_bytes, int *status) {
     const char *fn = __func__;
@@ -622,6 +634,7 @@ int sfa_epic_nearest_seeds_batch(sfa_ctx *ctx, int n, int w, int h, const float 
             const int x = seeds_xy[i][2 * k], y = seeds_xy[i][2 * k + 1];
             if (x < 0 || x >= w || y < 0 || y >= h) REFUSE("%s: seeds_xy[%d]: seed %d = (%d, %d) lies outside the %d x %d image", fn, i, k, x, y, w, h);
         }
+        SFA_TRY(epic_check_costs(ctx, fn, "cost[%d]", i, cost[i], w, h));
     }
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     size_t budget = workspace_bytes;

@@ -285,6 +285,9 @@ int epic_nn_device(sfa_ctx *ctx, const char *fn, int m, int w, int h, const Epic
 // what epic_nn_device allocates for an image at least: everything known beforehand (the default mode: `done` among it)
 size_t epic_nn_need0(const sfa_ctx *ctx, int w, int h, int ns, int nn);
 int epic_nn_check_sizes(sfa_ctx *ctx, const char *fn, int w, int h);
+// the domain of a host cost map, w * h floats: +0 ... +Inf, -0.0 taken as +0.  A NaN or a cost below 0 is refused in the name of `fn`, the map named by `what`
+// (a printf format that takes `image`) and the pixel by its coordinates
+int epic_check_costs(sfa_ctx *ctx, const char *fn, const char *what, int image, const float *cost, int w, int h) __attribute__((format(printf, 3, 0)));
 // One image of the fit and its application.  seeds, vects: ns; index, weight: ns * nn; lab, fx, fy: w * h packed (apply only); model: 6 ns (LA) or 2 ns (NW)
 struct EpicFitImg {
     const int2 *seeds; const float2 *vects; const int *index; const float *weight; const int *lab;

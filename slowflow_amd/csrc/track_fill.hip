@@ -213,6 +213,7 @@ int sfa_track_job_upload_fill(sfa_track_job *job, int s, const float *lab, int l
     if (!edges) REFUSE("%s: edges is null", __func__);
     if (saliency && !lab) REFUSE("%s: lab is null (epic.saliency_th != 0: the saliency filter reads the Lab image)", __func__);
     if (saliency && lab_stride < job->gw) REFUSE("%s: lab_stride = %d < gw = %d", __func__, lab_stride, job->gw);
+    SFA_TRY(epic_check_costs(ctx, __func__, "edges of start_jet %d", s, edges, job->gw, job->gh));
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     if (saliency) {
         for (int c = 0; c < 3; c++)
@@ -240,6 +241,7 @@ int sfa_track_job_upload_fill_device(sfa_track_job *job, int s0, int ns, const f
                                  hipMemcpyDeviceToDevice));
         SFA_TRY(track_saliency(job, s0 + s));
     }
+    // the edge planes stay on the device, so their domain (+0 ... +Inf, -0.0 for +0: sfa_track_job_upload_fill refuses the rest) is the caller's to guarantee
     for (int s = 0; s < ns; s++)
         SFA_TRY(pack_strided_planes(ctx, edges_dev + (long long)s * edge_strides[0], 0, edge_strides[1], edge_strides[2], job->gw, job->gh, 1,
                                     job->ptr(job->at.edges) + (size_t)(s0 + s) * g.cpl));

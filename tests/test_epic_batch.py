@@ -78,10 +78,10 @@ def workdir(tmp_path_factory):
 _runs = {}
 
 
-def host_run(tool, workdir, key, scenes, method, sal, pref_nn, nn, coef=0.8, budget=None):
+def host_run(tool, workdir, key, scenes, method, sal, pref_nn, nn, coef=0.8, budget=None, euc=EUC):
     """the tool's `run` on the scenes [(rgb, edges, m, w, h)], once per key: a list of dicts per scene (lab, sal, keep1, keep2, fx, fy, bfx, bfy, rc, brc) and
-    the stage times of the library's chain after epic_batch"""
-    full = (key, method, sal, pref_nn, nn, coef, budget)
+    the stage times of the library's chain after epic_batch.  euc = 0: epic() adds nothing to the edges"""
+    full = (key, method, sal, pref_nn, nn, coef, budget, euc)
     if full in _runs:
         return _runs[full]
     d = str(workdir / ("run%d" % len(_runs)))
@@ -92,7 +92,7 @@ def host_run(tool, workdir, key, scenes, method, sal, pref_nn, nn, coef=0.8, bud
             rgb.tofile(os.path.join(d, "rgb_%d.bin" % k))
             edges.tofile(os.path.join(d, "edges_%d.bin" % k))
             np.ascontiguousarray(m, np.float32).tofile(os.path.join(d, "matches_%d.bin" % k))
-    r = subprocess.run([tool, "run", d, str(len(scenes)), method, repr(sal), str(pref_nn), "5.0", str(nn), repr(coef), repr(EUC)] + ([str(budget)] if budget else []),
+    r = subprocess.run([tool, "run", d, str(len(scenes)), method, repr(sal), str(pref_nn), "5.0", str(nn), repr(coef), repr(euc)] + ([str(budget)] if budget else []),
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     rcs = re.findall(r"^rc (\d+) (-?\d+) (-?\d+)$", r.stdout, flags=re.M)
@@ -120,12 +120,12 @@ def same(a, b):
     return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
-def lib_batch(ctx, scenes, host, method, sal, pref_nn, nn, coef=0.8, **kw):
-    """ctx.epic_batch on scenes of ONE size with the Lab images the tool wrote"""
+def lib_batch(ctx, scenes, host, method, sal, pref_nn, nn, coef=0.8, euc=EUC, **kw):
+    """ctx.epic_batch on scenes of ONE size with the Lab images the tool wrote.  euc = 0: the edges as they are (epic()'s `if (euc)`; -0.0 + 0.0 would be +0.0)"""
     import slowflow_amd as sfa
     w = scenes[0][3]
-    costs = [s[1] + np.float32(EUC) for s in scenes]                   # epic()'s in-place `c += euc`, one fp32 addition
-    p = sfa.epic_params(method=method, saliency_th=sal, pref_nn=pref_nn, nn=nn, coef_kernel=coef, euc=EUC)
+    costs = [s[1] + np.float32(euc) if euc else s[1] for s in scenes]    # epic()'s in-place `c += euc`, one fp32 addition
+    p = sfa.epic_params(method=method, saliency_th=sal, pref_nn=pref_nn, nn=nn, coef_kernel=coef, euc=euc)
     return ctx.epic_batch([o["lab"] for o in host], costs, [s[2] for s in scenes], p, stride=stride_of(w), **kw)
 
 

@@ -310,3 +310,84 @@ def energy_classes(terms, flows, frames, h, w, incr, start):
                 ok_m = (ym >= 0) & (ym < h) & (xm >= 0) & (xm < w) & ~terms["occ"][t]
                 note("flow_", tap_classes((flows[0][t], flows[1][t]), ok_m, ym, xm))
     return {k: sorted(v) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------------------------------------------
+# the EpicFlow chain (tests/test_epic_value_ranges.py): edge-cost planes over the whole domain +0 ... +Inf of sfa_epic_nearest_seeds_batch / sfa_epic_batch,
+# the seeds that meet their special pixels, and matches at the edges of the clamp
+# ------------------------------------------------------------------------------------------------------
+EPIC_SIZES = ((136, 24, 300), (12, 10, 26), SMALL + (6,))      # (w, h, seeds): one sweep workgroup each, diagonals of 24, 10 and 4 cells
+EPIC_EXPS = (-140, -70, -20, 0, 14, 40, 60)                     # capped at 2^60: 2 * C * C of arg_sweep's two-sided update overflows from C = 2^64
+EPIC_TOP = 127                                                  # the sprinkled plane's extra band: two such costs sum past 0x7F7F7F7F and stay finite
+EPIC_SPECIALS = np.array([0.0, np.inf, FLT_MAX, SUB_MIN, SUB_MAX, FLT_MIN], np.float32)      # the domain's own: no -0, -Inf, NaN.  In the order seeds are moved onto them
+
+
+def cost_plain(w, h, seed):
+    """uniform(0.05, 1): the magnitudes the rest of the suite feeds the search"""
+    return np.random.default_rng(seed).uniform(0.05, 1, (h, w)).astype(np.float32)
+
+
+def cost_ladder(w, h, seed, exps=EPIC_EXPS, band=None):
+    """uniform(0.05, 1) * 2^e, e from `exps` in bands of `band` columns that move on by one band every eight rows: every diagonal of the sweep and every 64
+    consecutive pixels mix the magnitudes.  band: eight columns, or as many as still let a narrower plane hold every exponent (one column at 12 x 10 and
+    5 x 4).  The smallest band is subnormal and never 0 (0.05 * 2^-140 > 2^-145)"""
+    band = band or min(8, max(1, w // len(exps)))
+    e = np.asarray(exps, np.float64)[((np.arange(w)[None, :] // band) + (np.arange(h)[:, None] // 8)) % len(exps)]
+    return (cost_plain(w, h, seed).astype(np.float64) * np.exp2(e)).astype(np.float32)
+
+
+def cost_ladder_sprinkled(w, h, seed):
+    """cost_ladder with a further band of 2^127, and EPIC_SPECIALS (+0, +Inf, FLT_MAX, 2^-149, the largest subnormal, FLT_MIN) on one pixel in sixteen -- each of
+    them at least once, whatever the size"""
+    c = cost_ladder(w, h, seed, EPIC_EXPS + (EPIC_TOP,))
+    rng = np.random.default_rng(seed + 1000)
+    pos = rng.choice(w * h, max(len(EPIC_SPECIALS), (w * h) // 16), replace=False)
+    c.reshape(-1)[pos] = EPIC_SPECIALS[np.arange(len(pos)) % len(EPIC_SPECIALS)]
+    return c
+
+
+def cost_zeros(w, h, seed, zero=0.0):
+    """cost_plain with a third of the pixels `zero`"""
+    c = cost_plain(w, h, seed)
+    c[np.random.default_rng(seed + 2000).uniform(0, 1, (h, w)) < 1.0 / 3] = np.float32(zero)
+    return c
+
+
+def cost_minus_zeros(w, h, seed):
+    """cost_zeros with -0.0 for +0.0, from the same random stream"""
+    return cost_zeros(w, h, seed, zero=-0.0)
+
+
+def epic_seeds(w, h, ns, seed, cost=None):
+    """(ns, 2) int32 random (x, y).  cost: the leading seeds are moved onto the first pixel of each EPIC_SPECIALS value the plane holds -- of the first
+    ns // 2 kinds where the seeds are few"""
+    rng = np.random.default_rng(seed + 3000)
+    s = np.stack([rng.integers(0, w, ns), rng.integers(0, h, ns)], 1).astype(np.int32)
+    if cost is not None:
+        bits = np.ascontiguousarray(cost, np.float32).view(np.uint32).reshape(-1)
+        k = 0
+        for v in EPIC_SPECIALS[:max(1, ns // 2)]:
+            at = np.flatnonzero(bits == v.view(np.uint32))
+            if len(at):
+                s[k] = (at[0] % w, at[0] // w)
+                k += 1
+    return s
+
+
+def epic_edge_matches(w, h):
+    """matches (x1 y1 x2 y2) at the edges of the clamp to [0, w - 1] x [0, h - 1], all finite: +-FLT_MAX, -0.0 (max(0.f, -0.f) is +0), subnormal coordinates,
+    w - 1 and h - 1 and the floats after them"""
+    f = np.float32
+    wx, hy = f(w - 1), f(h - 1)
+    return np.array([[FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX], [-FLT_MAX, FLT_MAX, 3, 2], [FLT_MAX, -FLT_MAX, 1, 1], [-0.0, -0.0, 2.5, 1.5], [-0.0, 3, -0.0, 2],
+                     [SUB_MIN, SUB_MAX, 1.25, 0.75], [-SUB_MIN, -SUB_MAX, SUB_MAX, SUB_MIN], [wx, hy, wx - 1, hy - 1], [np.nextafter(wx, f(np.inf)), 1, wx, 2],
+                     [2, np.nextafter(hy, f(np.inf)), 3, hy], [np.nextafter(wx, f(0)), np.nextafter(hy, f(0)), wx, hy]], np.float32)
+
+
+def list_classes(index, dist):
+    """what a nearest-seeds result holds, as counts: exact zeros, subnormals, +Inf, absent entries (-1 / 0x7F7F7F7F), and neighbouring entries of a row that tie"""
+    bits = np.ascontiguousarray(dist, np.float32).view(np.uint32)
+    present = index >= 0
+    tie = (bits[:, 1:] == bits[:, :-1]) & present[:, 1:] & present[:, :-1]
+    return dict(zero=int((present & (dist == 0)).sum()), subnormal=int((present & is_subnormal(dist)).sum()), inf=int((present & (dist == np.inf)).sum()),
+                absent=int((~present).sum()), ties=int(tie.sum()))
