@@ -739,6 +739,71 @@ int  sfa_job_set_raw_weights(sfa_job *job, int b0, int n, int red_x, int red_y, 
  * sfa_resize_linear_fx, device to device: bit-equal to those two calls per channel.  Both sequences on one context; dst_seq of lrint(w scale) x lrint(h scale)
  * (SFA_ERR_ARG naming dst_seq otherwise); scale > 0 with a blur of at most 17 taps (scale >= 0.125).  Asynchronous. */
 int  sfa_sequence_rescale(sfa_sequence *dst_seq, int f_dst, sfa_sequence *src_seq, int f_src, int n, float scale);
+/* ---- EpicFlow's initialisation on resident data (csrc/epic_init.hip, csrc/lab_math.h) -------------------------------------------------------
+ * deep_matching 1 starts every window from EpicFlow's interpolation of its matches (slow_flow.cpp:744-863).  The calls below keep that stage's planes in
+ * GPU memory: the L*a*b* image, the chain of sfa_epic_batch, and the step from its field to a job's initial flow.
+ * The Lab image of the driver (slow_flow.cpp:472-474, 578-586 + image.c:694-726; host/epic.cpp: rgb8_to_lab): every sample times `norm`, rounded to
+ * nearest (ties to even) and saturated to 0 .. 255, then rgb_to_lab; out: L, a c, b c.  The arithmetic is csrc/lab_math.h, one function for host and device
+ * code whose cube root and exponential are written from IEEE fp64 operations; tests/host/test_lab_math.cpp walks all 2^24 8-bit triples through it against the
+ * host function, and the kernel is that function: the planes equal rgb8_to_lab's bit for bit.  +Inf saturates to 255, -Inf to 0, a NaN sample gives NaN
+ * in all three planes of its pixel.
+ * n fp32 images [n][3][h][w] at rgb_strides[4] = element strides of (image, channel, row, column) -> lab_dev at lab_strides[4]; columns >= w of the
+ * destination are not written.  One thread per pixel; asynchronous on the context's stream, never waits.  Refused with SFA_ERR_ARG, the argument named,
+ * nothing launched: n, w or h < 1, a NaN norm, every pointer or view the device seam refuses, a destination whose strides let two of its elements share
+ * memory, a destination that overlaps the source. */
+int  sfa_rgb8_to_lab_device(sfa_ctx *ctx, int n, int w, int h, const float *rgb_dev, const long long rgb_strides[4], float norm, float *lab_dev,
+                            const long long lab_strides[4]);
+/* The same kernel between two resident sequences of one size and one context: src_seq's frames [f_src, f_src + n) -> dst_seq's [f_dst, f_dst + n).  The
+ * source frames must still hold the samples as they were read: the caller orders this call before sfa_sequence_apply_normalization.  src_seq == dst_seq
+ * is taken where the two frame ranges lie apart. */
+int  sfa_sequence_lab(sfa_sequence *dst_seq, int f_dst, sfa_sequence *src_seq, int f_src, int n, float norm);
+/* A resident EpicFlow batch: the inputs of epic() (epic_flow_extended/epic.cpp:147-235) for n images of one size w x h, and the fields it leaves, in GPU
+ * memory.  params as for sfa_epic_batch, with one difference: the job adds params->euc to the cost maps itself, once and in fp32, as epic() does on entry
+ * (epic.cpp:160).  Refused at creation: what sfa_epic_batch refuses of n, w, h and params (n at most 4096). */
+typedef struct sfa_epic_job sfa_epic_job;
+int  sfa_epic_job_create(sfa_ctx *ctx, const sfa_epic_params *params, int w, int h, int n, sfa_epic_job **out);
+void sfa_epic_job_destroy(sfa_epic_job *job);
+/* Image i from host memory, as the match and edge files hold it: matches = 4 * nm floats (x1 y1 x2 y2), nm may be 0; edges = w * h floats WITHOUT euc,
+ * which is added on the device.  Refused: a coordinate that is not finite, an edge cost that is NaN or below 0 (sfa_epic_nearest_seeds_batch's domain;
+ * image and pixel named), nm * nn beyond 2^31 - 1.  Waits for its copies: the buffers are free on return. */
+int  sfa_epic_job_upload(sfa_epic_job *job, int i, const float *matches, int nm, const float *edges);
+/* The Lab images of [i0, i0 + n) from a resident sequence of the job's size on the job's GPU (slow_flow.cpp:809: un_seq[ref]): frame_index[k] is image
+ * i0 + k's frame.  Device to device on the JOB's stream; a sequence of another context is ordered by the caller (its frames are final before the call, as
+ * for sfa_job_upload_resident).  What the job keeps is the image's saliency (image.c:729-791, sigma 0.8 and 1.0), the only reader of the Lab image; with
+ * saliency_th == 0 nothing is read.  Asynchronous. */
+int  sfa_epic_job_set_lab(sfa_epic_job *job, int i0, int n, const sfa_sequence *lab_seq, const int *frame_index);
+/* Lab images and / or cost maps of [i0, i0 + n) from fp32 device memory: lab_dev [n][3][h][w] at lab_strides[4] (or NULL: not set by this call), cost_dev
+ * [n][h][w] at cost_strides[3] (or NULL).  cost_has_euc 0: euc is added on the device, as for the host upload; 1: the maps hold it already.
+ * THE DOMAIN of a cost that arrives in device memory is the caller's responsibility: +0 ... +Inf (sfa_epic_nearest_seeds_batch); a NaN or a negative cost is
+ * not looked for -- there is no read-back -- and the search has no defined result on one.  Asynchronous. */
+int  sfa_epic_job_upload_device(sfa_epic_job *job, int i0, int n, const float *lab_dev, const long long lab_strides[4], const float *cost_dev,
+                                const long long cost_strides[3], int cost_has_euc);
+/* Image i's matches from device memory: nm contiguous rows of x1 y1 x2 y2, copied on the stream.  The coordinates are not tested for finite values
+ * (sfa_epic_job_upload does that on the host).  Asynchronous: matches_dev must stay valid, and unchanged, until the context's stream has passed the copy
+ * (sfa_ctx_signal_stream, or the wait of sfa_epic_job_run). */
+int  sfa_epic_job_set_matches_device(sfa_epic_job *job, int i, const float *matches_dev, int nm);
+/* epic() for the images [0, n): the saliency filter on the planes the job holds, then sfa_epic_batch's chain on its device planes -- the same sub-batches
+ * within workspace_bytes (0: half of the GPU's free memory), the context's search mode (sfa_ctx_set_epic_search), rc[n], counts[n][3] (or NULL) and
+ * status[n] as sfa_epic_batch has them, and fields that equal its planes bit for bit.  An image with rc 1 (no match, or none left) holds a field of zeros
+ * afterwards, which is what the driver starts such a window from (slow_flow.cpp:529 of the host program); an image with status 1 holds no field.
+ * LIKE THE CHAIN THIS CALL WAITS FOR THE STREAM: the chain reads the survivors of its filters on the host.  Refused: an image of [0, n) without matches,
+ * cost map or (saliency_th != 0) Lab image. */
+int  sfa_epic_job_run(sfa_epic_job *job, int n, int *rc, int (*counts)[3], size_t workspace_bytes, int *status);
+/* Image i's field to host planes of `stride` floats per row (columns >= w not written; waits).  Refused: an image without a field (not run, or status 1). */
+int  sfa_epic_job_download(sfa_epic_job *job, int i, float *fx, float *fy, int stride);
+/* The fields of [i0, i0 + n) to flow_dev [n][2][h][w] at strides[4] = element strides of (image, u|v, row, column); asynchronous.  Refused: an image
+ * without a field, a destination the device seam refuses or whose strides let two of its elements share memory. */
+int  sfa_epic_job_download_device(sfa_epic_job *job, int i0, int n, float *flow_dev, const long long strides[4]);
+/* Image i's field from host planes of `stride` floats per row, in place of a run's: what the driver does with an image the run flagged (status 1), after
+ * epic() of the host program has computed it.  The image holds a field afterwards (rc 0).  Waits for its copies.  (This entry and sfa_sequence_lab's
+ * Python form are what the driver needs beyond the list of create / upload / set_lab / upload_device / set_matches_device / run / download.) */
+int  sfa_epic_job_upload_flow(sfa_epic_job *job, int i, const float *fx, const float *fy, int stride);
+/* epic_to_initial_flow of the driver (slow_flow.cpp:826-843) on the GPU: the fields of the epic job's images [i0, i0 + n) become the initial flow of the
+ * job's windows [b0, b0 + n), written where sfa_job_set_flow_device writes.  Fields of the job's size: one fp32 multiplication by mul_u / mul_v
+ * (image_mul_scalar; the driver passes fx / steps, fy / steps).  Fields of a size that divides the job's in both directions: sfa_resize_linear's arithmetic
+ * per plane, then that multiplication.  Any other size is refused: the reference keeps a field of the reduced size there (:538-544 of the host program).
+ * Both jobs on ONE context (one stream orders the run before this call); refused otherwise, and for an image without a field.  One launch; asynchronous. */
+int  sfa_job_set_flow_epic(sfa_job *job, int b0, int n, const sfa_epic_job *epic_job, int i0, float mul_u, float mul_v);
 
 /* Ordering against a stream of the caller (a hipStream_t; NULL = the device's null stream, which is torch's default stream).  wait: the context's
  * stream waits for everything submitted to `stream` so far; signal: `stream` waits for everything submitted to the context's stream so far.  Both

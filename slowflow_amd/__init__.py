@@ -208,6 +208,7 @@ EXPORTS = [
     "sfa_job_create", "sfa_job_destroy", "sfa_job_upload", "sfa_job_upload_resident", "sfa_job_reset_flow", "sfa_job_run", "sfa_job_download", "sfa_job_download_occlusions", "sfa_job_keep_alternation_occlusions", "sfa_job_download_alternation_occlusions", "sfa_job_mpix_iters", "sfa_job_device_bytes",
     "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_pair_job_upload_device", "sfa_pair_job_set_flow_device", "sfa_pair_job_download_device", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
     "sfa_demosaic_device", "sfa_sequence_upload_mosaic_device", "sfa_sequence_upload_mosaic", "sfa_job_set_raw_weights", "sfa_sequence_rescale",
+    "sfa_rgb8_to_lab_device", "sfa_sequence_lab", "sfa_epic_job_create", "sfa_epic_job_destroy", "sfa_epic_job_upload", "sfa_epic_job_set_lab", "sfa_epic_job_upload_device", "sfa_epic_job_set_matches_device", "sfa_epic_job_run", "sfa_epic_job_download", "sfa_epic_job_upload_flow", "sfa_epic_job_download_device", "sfa_job_set_flow_epic",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
     "sfa_track_params_default", "sfa_track_job_bytes", "sfa_track_job_create", "sfa_track_job_destroy", "sfa_track_job_upload_flows", "sfa_track_job_upload_frames", "sfa_track_job_upload_flows_device", "sfa_track_job_upload_frames_device", "sfa_track_job_run", "sfa_track_job_download_rate", "sfa_track_job_download_fused", "sfa_track_job_download_best", "sfa_ctx_free_bytes", "sfa_track_job_download_device", "sfa_track_job_stage_ms", "sfa_track_job_upload_occlusions_device", "sfa_track_job_download_rate_device", "sfa_track_job_download_best_device",
     "sfa_track_fill_params_default", "sfa_track_job_bytes_fill", "sfa_track_job_create_fill", "sfa_track_job_upload_fill", "sfa_track_job_upload_fill_device", "sfa_track_job_download_fill", "sfa_track_job_fill_ms", "sfa_track_job_fill_info",
@@ -231,7 +232,7 @@ def lib():
         L.sfa_job_mpix_iters.argtypes = [C.c_void_p]
         L.sfa_job_device_bytes.restype = C.c_double
         L.sfa_job_device_bytes.argtypes = [C.c_void_p]
-        for name in ("sfa_ctx_destroy", "sfa_job_destroy", "sfa_pair_job_destroy", "sfa_track_job_destroy", "sfa_sor_batch_destroy", "sfa_sequence_destroy"):
+        for name in ("sfa_ctx_destroy", "sfa_job_destroy", "sfa_pair_job_destroy", "sfa_track_job_destroy", "sfa_sor_batch_destroy", "sfa_sequence_destroy", "sfa_epic_job_destroy"):
             if hasattr(L, name):                # an SFA_LIB build of an earlier C-ABI (tools/bench_track.py's baseline) lacks the newest object
                 getattr(L, name).restype = None
                 getattr(L, name).argtypes = [C.c_void_p]
@@ -708,6 +709,10 @@ class Context:
             raise SlowflowError("sfa_epic_batch: images %s do not fit a workspace of %d bytes" % ([i for i, s in enumerate(status) if s], workspace_bytes))
         return fx, fy, rc, counts, kept
 
+    def epic_job(self, params, w, h, n=1):
+        """a resident EpicFlow batch (sfa_epic_job): n images of w x h, their inputs and fields in GPU memory; params: epic_params(...)"""
+        return EpicJob(self, params, w, h, n)
+
     def epic_saliency(self, labs, sigma_image=0.8, sigma_matrix=1.0, w=None):
         """the saliency of n Lab images (3, h, stride) of one shape (sfa_epic_saliency_batch): n fp32 (h, stride) planes, the bits of the host's saliency(),
         padding columns 0.  w: the images' width inside rows of `stride` floats (None: the whole row)"""
@@ -1052,6 +1057,14 @@ class Job:
         from . import device
         return device.job_changes(self, b0, n)
 
+    def set_flow_epic(self, epic_job, mul_u=1.0, mul_v=1.0, b0=0, n=None, i0=0):
+        """the initial flow of windows b0 .. b0 + n - 1 from the fields of epic_job's images i0 .. (sfa_job_set_flow_epic): resized to the job's size where
+        the field's size divides it, then multiplied by mul_u / mul_v (the driver's fx / steps, fy / steps).  n default: every window from b0"""
+        n = self.batch - b0 if n is None else n
+        L = lib()
+        L.sfa_job_set_flow_epic.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float]
+        self.ctx._ck(L.sfa_job_set_flow_epic(self.h_, int(b0), int(n), epic_job.h_, int(i0), float(mul_u), float(mul_v)), "sfa_job_set_flow_epic")
+
     def set_raw_weights(self, red, weight, b0=0, n=None):
         """rawWeighting (utils.cpp:1336-1374) for the windows b0 .. b0 + n - 1 (default: all from b0), formed on the GPU: the bits of passing its planes as
         chw.  red = (red_x, red_y), the cfg's raw_red_loc.  Call it AFTER the window's upload: an upload without chw sets the weights back to ones."""
@@ -1108,6 +1121,96 @@ class Job:
         if self.h_:
             if self.ctx.h:                      # a context finalised first (cyclic garbage, interpreter shutdown) took its stream along: nothing to call into
                 lib().sfa_job_destroy(self.h_)
+            self.h_ = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EpicJob:
+    """sfa_epic_job: the inputs of epic() for n images of one size and the fields it leaves, resident in GPU memory.  The job adds params.euc to the cost
+    maps itself (cost_has_euc=False), as epic() does on entry."""
+
+    def __init__(self, ctx, params, w, h, n=1):
+        self.ctx, self.w, self.h, self.n, self.params = ctx, w, h, n, params
+        self.h_ = C.c_void_p()
+        L = lib()
+        L.sfa_epic_job_create.argtypes = [C.c_void_p, C.POINTER(EpicParams), C.c_int, C.c_int, C.c_int, C.c_void_p]
+        ctx._ck(L.sfa_epic_job_create(ctx.h, C.byref(params), int(w), int(h), int(n), C.byref(self.h_)), "sfa_epic_job_create")
+        ctx._children.add(self)
+
+    def upload(self, i, matches, edges):
+        """image i from host arrays: matches (nm, 4) of x1 y1 x2 y2, edges (h, w) WITHOUT euc"""
+        m = np.ascontiguousarray(matches, dtype=np.float32).reshape(-1, 4)
+        e = np.ascontiguousarray(edges, dtype=np.float32)
+        assert e.shape == (self.h, self.w), "edges: (h, w)"
+        L = lib()
+        L.sfa_epic_job_upload.argtypes = [C.c_void_p, C.c_int, _f, C.c_int, _f]
+        self.ctx._ck(L.sfa_epic_job_upload(self.h_, int(i), fptr(m) if len(m) else None, len(m), fptr(e)), "sfa_epic_job_upload")
+
+    def set_lab(self, lab_seq, frame_index, i0=0):
+        """the Lab images of i0 .. from frames of a resident sequence of the job's size (sfa_epic_job_set_lab)"""
+        idx = (C.c_int * len(frame_index))(*[int(f) for f in frame_index])
+        L = lib()
+        L.sfa_epic_job_set_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        self.ctx._ck(L.sfa_epic_job_set_lab(self.h_, int(i0), len(frame_index), lab_seq.h_, idx), "sfa_epic_job_set_lab")
+
+    def upload_device(self, lab=None, cost=None, i0=0, cost_has_euc=False):
+        """Lab images [n,3,h,w] and / or cost maps [n,h,w] (fp32, any strides) in device memory -> images i0 .."""
+        from . import device
+        device.epic_job_upload_device(self, lab, cost, i0, cost_has_euc)
+
+    def set_matches_device(self, i, matches):
+        """image i's matches from a contiguous fp32 device array [nm,4]; None or an empty host array: no match"""
+        from . import device
+        device.epic_job_set_matches_device(self, i, matches)
+
+    def run(self, n=None, workspace_bytes=0, with_status=False):
+        """epic() for the images [0, n) (default: all).  Returns (rc, counts): epic()'s values and (n, 3) int32 survivors; waits for the stream.  An image
+        that does not fit workspace_bytes even alone raises, unless with_status: then (rc, counts, status)"""
+        n = self.n if n is None else int(n)
+        k = max(n, 1)
+        rc, counts, status = (C.c_int * k)(*([-9] * k)), ((C.c_int * 3) * k)(), (C.c_int * k)()
+        L = lib()
+        L.sfa_epic_job_run.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int * 3), C.c_size_t, C.POINTER(C.c_int)]
+        self.ctx._ck(L.sfa_epic_job_run(self.h_, n, rc, counts, int(workspace_bytes), status), "sfa_epic_job_run")
+        status = [int(v) for v in status[:n]]
+        out = [int(v) for v in rc[:n]], np.array([list(c) for c in counts[:n]], np.int32).reshape(n, 3)
+        if with_status:
+            return out + (status,)
+        if any(status):
+            raise SlowflowError("sfa_epic_job_run: images %s do not fit a workspace of %d bytes" % ([i for i, s in enumerate(status) if s], workspace_bytes))
+        return out
+
+    def download(self, i, stride=None):
+        """image i's field as two host planes (h, stride) (stride default w; columns >= w hold NaN)"""
+        stride = self.w if stride is None else int(stride)
+        fx, fy = np.full((self.h, max(stride, 1)), np.nan, np.float32), np.full((self.h, max(stride, 1)), np.nan, np.float32)
+        L = lib()
+        L.sfa_epic_job_download.argtypes = [C.c_void_p, C.c_int, _f, _f, C.c_int]
+        self.ctx._ck(L.sfa_epic_job_download(self.h_, int(i), fptr(fx), fptr(fy), stride), "sfa_epic_job_download")
+        return fx, fy
+
+    def upload_flow(self, i, fx, fy):
+        """image i's field from two host planes (h, stride), in place of a run's (sfa_epic_job_upload_flow)"""
+        fx, fy = np.ascontiguousarray(fx, dtype=np.float32), np.ascontiguousarray(fy, dtype=np.float32)
+        assert fx.shape == fy.shape and fx.shape[0] == self.h, "two planes (h, stride)"
+        L = lib()
+        L.sfa_epic_job_upload_flow.argtypes = [C.c_void_p, C.c_int, _f, _f, C.c_int]
+        self.ctx._ck(L.sfa_epic_job_upload_flow(self.h_, int(i), fptr(fx), fptr(fy), fx.shape[1]), "sfa_epic_job_upload_flow")
+
+    def download_device(self, out_flow, i0=0):
+        """the fields of images i0 .. into the fp32 device array out_flow [n,2,h,w]"""
+        from . import device
+        device.epic_job_download_device(self, out_flow, i0)
+
+    def close(self):
+        if self.h_:
+            if self.ctx.h:
+                lib().sfa_epic_job_destroy(self.h_)
             self.h_ = C.c_void_p()
 
     def __del__(self):
@@ -1414,6 +1517,14 @@ class Sequence:
         L = lib()
         L.sfa_sequence_rescale.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float]
         self.ctx._ck(L.sfa_sequence_rescale(self.h_, int(f_dst), src.h_, int(f_src), int(n), float(scale)), "sfa_sequence_rescale")
+
+    def lab_from(self, src, norm=1.0, f_dst=0, f_src=0, n=None):
+        """the driver's Lab images of resident frames (sfa_sequence_lab): src's frames f_src .. (not yet normalised) times `norm`, rounded to 8 bits and
+        converted become this sequence's frames f_dst ..; both sequences of one size on one context"""
+        n = min(src.n - f_src, self.n - f_dst) if n is None else n
+        L = lib()
+        L.sfa_sequence_lab.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float]
+        self.ctx._ck(L.sfa_sequence_lab(self.h_, int(f_dst), src.h_, int(f_src), int(n), float(norm)), "sfa_sequence_lab")
 
     def download(self, f):
         a = np.zeros((3, self.h, stride_of(self.w)), np.float32)

@@ -726,6 +726,29 @@ int sfa_job_set_flow_device(sfa_job *j, int b0, int n, const float *flow_dev, co
     return SFA_OK;
 }
 
+// epic_to_initial_flow (kernel: epic_init.hip) from an epic job's fields into the initial flow of windows [b0, b0 + n)
+int sfa_job_set_flow_epic(sfa_job *j, int b0, int n, const sfa_epic_job *e, int i0, float mul_u, float mul_v) {
+    sfa_ctx *ctx = j ? j->ctx : nullptr;
+    CHECK_ARGS(j, "job is null");
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    SFA_TRY(job_windows(ctx, __func__, j, b0, n));
+    if (!e) REFUSE("%s: epic_job is null", __func__);
+    if (e->ctx != ctx) REFUSE("%s: epic_job lives on another context than the job: one stream orders its run before this call", __func__);
+    SFA_TRY(check_batch_range(ctx, __func__, "images of epic_job", i0, n, e->n));
+    const bool same = e->w == j->w && e->h == j->h;
+    if (!same && (j->w % e->w != 0 || j->h % e->h != 0))
+        REFUSE("%s: epic_job's fields are %d x %d, the job's frames %d x %d: neither the same size nor a divisor of it in both directions (the reference rescales by the "
+               "integer ratio of the widths, slow_flow.cpp:827, and keeps a field of the reduced size where that is 1)", __func__, e->w, e->h, j->w, j->h);
+    if (j->h > 65535) REFUSE("%s: h = %d (at most 65535: a row per block)", __func__, j->h);
+    for (int k = 0; k < n; k++)
+        if (e->rc[i0 + k] < 0) REFUSE("%s: image %d of epic_job holds no field (not run since its inputs changed, or flagged by the run)", __func__, i0 + k);
+    Level L0 = j->level(0);
+    launch_epic_initial_flow(ctx, j->init_flow.f() + (long)b0 * 2 * L0.pl, 2 * L0.pl, L0.pl, L0.pitch, j->w, j->h, n, e->u(i0), e->v(i0), (long)(2 * e->npix), e->w, e->h,
+                             mul_u, mul_v);
+    SFA_HIP(ctx, hipGetLastError());
+    return SFA_OK;
+}
+
 int sfa_job_download_device(sfa_job *j, int b0, int n, float *flow_dev, const long long strides[4], float *occ_dev, const long long occ_strides[3]) {
     sfa_ctx *ctx = j ? j->ctx : nullptr;
     CHECK_ARGS(j, "job is null");

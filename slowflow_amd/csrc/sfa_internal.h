@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -529,6 +530,41 @@ int check_batch_range(sfa_ctx *ctx, const char *fn, const char *what, int b0, in
 __attribute__((visibility("hidden"))) int check_mosaic_method(sfa_ctx *ctx, const char *fn, int method, int red_x, int red_y);
 
 }  // namespace sfa
+
+namespace sfa {
+// ---- epic_init.hip: EpicFlow's initialisation on resident data (sfa_rgb8_to_lab_device, sfa_sequence_lab, sfa_epic_job_*, sfa_job_set_flow_epic) -------
+// n fp32 images of w x h, element (image, channel, row, column) at p + the strides: rgb8_to_lab (host/epic.cpp:19-28) of every pixel, csrc/lab_math.h.
+// Columns >= w of the destination are not written
+struct LabSrc { const float *p; long long sn, sc, sr, sx; };
+struct LabDst { float *p; long long sn, sc, sr, sx; };
+void launch_rgb8_to_lab(sfa_ctx *c, const LabSrc &src, const LabDst &dst, int n, int w, int h, float norm);
+// epic_to_initial_flow (host/slow_flow.cpp:530-546) for nwin windows: the packed sw x sh fields src_u (v: src_v; the next window src_es floats further)
+// -> dst (u plane of the first window, v one pl further, the next window dst_es) of w x h at `pitch`.  Sizes equal: one fp32 multiplication by mul_u /
+// mul_v (image_mul_scalar); else k_resize itself (sfa_resize_linear's kernel) with that multiplication as its post_scale.  Columns >= w are not written
+void launch_epic_initial_flow(sfa_ctx *c, float *dst, long dst_es, long pl, int pitch, int w, int h, int nwin, const float *src_u, const float *src_v, long src_es,
+                              int sw, int sh, float mul_u, float mul_v);
+
+}  // namespace sfa
+
+// ---- sfa_epic_job: the inputs and fields of epic() for n images of one size, resident (epic_init.hip) ----
+struct sfa_epic_job {
+    sfa_ctx *ctx = nullptr;
+    sfa_epic_params p;
+    int w = 0, h = 0, n = 0, pitch = 0;
+    size_t npix = 0, pl = 0;                // w * h (the chain's packed planes); pitch * h (the saliency's)
+    bool saliency = false;
+    sfa::DevMem cost;                       // n packed planes, euc added
+    sfa::DevMem flow;                       // n x (u, v) packed planes
+    sfa::DevMem sal;                        // n saliency planes at the device pitch (saliency_th != 0)
+    sfa::DevMem stage;                      // the saliency's work planes for stage_images images; their first three take the Lab image
+    int stage_images = 0;
+    std::vector<std::unique_ptr<sfa::DevMem>> matches;   // per image: nm rows of x1 y1 x2 y2
+    std::vector<int> nm;                    // -1: no matches given yet
+    std::vector<char> have_cost, have_lab;
+    std::vector<int> rc;                    // the last run's epic() value per image: 0 a field, 1 zeros (no match left); -1: none (not run, or flagged)
+    float *u(int i) const { return flow.f() + (size_t)i * 2 * npix; }
+    float *v(int i) const { return u(i) + npix; }
+};
 
 // ---- sfa_pair_job: n frame pairs of one size in HBM for the two-frame refinement (two_frame.hip: the one launch sequence, the resident jobs, the host calls) ----
 // Pair b owns the planes [b * NPL, (b + 1) * NPL) of one allocation; this enum is the only statement of the plane list.  IM1 and IM2 lie next to each other

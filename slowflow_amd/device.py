@@ -2,7 +2,7 @@
 and results that live in GPU memory go in and out of a job without a host copy.
 
 The core takes any object with `__cuda_array_interface__` (torch-ROCm tensors, cupy arrays ...) and needs no torch; `import slowflow_amd` does not
-import this module, and this module imports torch only inside demosaic(), refine(), refine_pairs(), track() and flow_quantiles(), to allocate the outputs
+import this module, and this module imports torch only inside demosaic(), rgb8_to_lab(), epic(), refine(), refine_pairs(), track() and flow_quantiles(), to allocate the outputs
 and to find the caller's current stream (on_stream, the one stream bracket of the five).  device_view is the one place an argument's element type, rank
 and shape are checked.  refine() is the multi-frame path on resident jobs; refine_pairs() the two-frame path on resident pair jobs, which
 never waits for the GPU; track() dense_tracking's accumulation, energies and fusion on a resident track job, which does not wait either;
@@ -158,6 +158,10 @@ def _lib():
         L.sfa_track_job_upload_fill_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sfa_flow_magnitude_quantiles_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                           C.c_float, C.c_float, C.c_void_p]
+        L.sfa_rgb8_to_lab_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.sfa_epic_job_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.sfa_epic_job_set_matches_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.sfa_epic_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _bound = True
     return L
 
@@ -295,6 +299,81 @@ def demosaic(ctx, mosaic, red=(1, 0), method=0, origin=(0, 0), size=None, *, str
     return out
 
 
+def rgb8_to_lab(ctx, rgb, norm=1.0, *, stream=None, out=None):
+    """The L*a*b* image EpicFlow's saliency reads (host/epic.cpp: rgb8_to_lab; csrc/lab_math.h) of n frames that live on the context's GPU: rgb = a torch
+    fp32 tensor [n,3,h,w] of any strides holding the samples as they were read; every sample times `norm` (1/255 for 16-bit frames) is rounded to 8 bits
+    first.  Returns a new fp32 tensor [n,3,h,w] (L, a c, b c), or fills `out` (any strides that keep its elements apart, no overlap with rgb) and returns
+    it; the bits of the host function.  Ordered after what `stream` (default: torch.cuda.current_stream) holds at the call, and `stream` waits for it
+    afterwards; the call only enqueues."""
+    import torch
+    v = device_view(rgb, name="rgb", kinds=("f4",), shape=("n", 3, None, None))
+    n, _, h, w = v.shape
+    with on_stream(torch, ctx, rgb, stream, lambda dev: torch.empty((n, 3, h, w), dtype=torch.float32, device=dev) if out is None else out) as (_, res):
+        ov = device_view(res, writable=True, name="out", shape=(n, 3, h, w))
+        ctx._ck(_lib().sfa_rgb8_to_lab_device(ctx.h, n, w, h, C.c_void_p(v.ptr), _LL4(*v.strides), float(norm), C.c_void_p(ov.ptr), _LL4(*ov.strides)),
+                "sfa_rgb8_to_lab_device")
+    return res
+
+
+def epic_job_upload_device(job, lab=None, cost=None, i0=0, cost_has_euc=False):
+    lv = device_view(lab, name="lab", kinds=("f4",), shape=("n", 3, job.h, job.w)) if lab is not None else None
+    cv = device_view(cost, name="cost", kinds=("f4",), shape=("n", job.h, job.w)) if cost is not None else None
+    if lv is not None and cv is not None and lv.shape[0] != cv.shape[0]:
+        raise sfa.SlowflowError(f"cost: {cv.shape[0]} maps for {lv.shape[0]} Lab images")
+    n = lv.shape[0] if lv is not None else cv.shape[0] if cv is not None else 0
+    job.ctx._ck(_lib().sfa_epic_job_upload_device(job.h_, int(i0), n, C.c_void_p(lv.ptr) if lv else None, _LL4(*lv.strides) if lv else None,
+                                                  C.c_void_p(cv.ptr) if cv else None, _LL3(*cv.strides) if cv else None, int(bool(cost_has_euc))),
+                "sfa_epic_job_upload_device")
+
+
+def epic_job_set_matches_device(job, i, matches):
+    if matches is None or (hasattr(matches, "shape") and matches.shape[0] == 0):
+        job.ctx._ck(_lib().sfa_epic_job_set_matches_device(job.h_, int(i), None, 0), "sfa_epic_job_set_matches_device")
+        return
+    v = device_view(matches, name="matches", kinds=("f4",), shape=("nm", 4), contiguous=True)
+    job.ctx._ck(_lib().sfa_epic_job_set_matches_device(job.h_, int(i), C.c_void_p(v.ptr), v.shape[0]), "sfa_epic_job_set_matches_device")
+
+
+def epic_job_download_device(job, out_flow, i0=0):
+    v = device_view(out_flow, writable=True, name="out_flow", shape=("n", 2, job.h, job.w))
+    job.ctx._ck(_lib().sfa_epic_job_download_device(job.h_, int(i0), v.shape[0], C.c_void_p(v.ptr), _LL4(*v.strides)), "sfa_epic_job_download_device")
+
+
+def epic(ctx, params, lab, cost, matches, *, cost_has_euc=False, stream=None, workspace_bytes=0):
+    """EpicFlow's interpolation (epic(), epic_flow_extended/epic.cpp:147-235) of n images whose inputs live on the context's GPU, on a resident epic job:
+    lab = a torch fp32 tensor [n,3,h,w] (rgb8_to_lab's; None with params.saliency_th == 0), cost = [n,h,w] edge costs (cost_has_euc: params.euc is in
+    them already; else the job adds it), matches = a list of n [nm_i,4] arrays of x1 y1 x2 y2: torch tensors on the GPU (contiguous fp32) or host arrays
+    (those are tested for finite values).  Returns (flow, rc): a new fp32 tensor [n,2,h,w] on the GPU that refine(flow=) and refine_pairs(flow0=) take as
+    it is, and epic()'s return value per image (1: no match left, a field of zeros).  The planes equal Context.epic_batch's bit for bit.  The call
+    WAITS for the GPU where the chain reads the survivors of its filters; an image that does not fit workspace_bytes even alone raises."""
+    import torch
+    cv = device_view(cost, name="cost", kinds=("f4",), shape=("n", None, None))
+    n, h, w = cv.shape
+    if len(matches) != n:
+        raise sfa.SlowflowError(f"matches: {len(matches)} lists for {n} cost maps")
+    if lab is None and params.saliency_th != 0:                   # (the job is kept between calls, and with it the last call's saliency planes)
+        raise sfa.SlowflowError("lab: None with saliency_th != 0: the saliency filter reads the Lab images")
+    if stream is None:
+        stream = torch.cuda.current_stream(cost.device)
+    staged = []
+    with torch.cuda.stream(stream):                               # host match lists go up on the caller's stream, which the context then waits for
+        for i, m in enumerate(matches):
+            if m is not None and not hasattr(m, "__cuda_array_interface__") and not getattr(m, "is_cuda", False):
+                a = np.ascontiguousarray(m, dtype=np.float32).reshape(-1, 4)
+                if not np.isfinite(a).all():
+                    raise sfa.SlowflowError(f"matches[{i}]: a coordinate that is not finite")
+                m = torch.from_numpy(a).to(cost.device) if len(a) else None
+            staged.append(m)
+    job = _cached_job(ctx, "_epic_jobs", (w, h, n, bytes(params)), lambda: sfa.EpicJob(ctx, params, w, h, n))
+    with on_stream(torch, ctx, cost, stream, lambda dev: torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)) as (_, flow):
+        epic_job_upload_device(job, lab if params.saliency_th != 0 else None, cost, 0, cost_has_euc)
+        for i, m in enumerate(staged):
+            epic_job_set_matches_device(job, i, m)
+        rc, _ = job.run(n, workspace_bytes)
+        epic_job_download_device(job, flow, 0)
+    return flow, rc
+
+
 def pair_sizes(B):
     """a batch of B windows or pairs as jobs of at most MAX_BATCH each, of equal or nearly equal size: the split of refine() and refine_pairs()"""
     pieces = -(-B // MAX_BATCH)
@@ -322,6 +401,8 @@ def _job_for(ctx, params, w, h, nb):
 def release_jobs(ctx):
     """closes the jobs refine() and refine_pairs() keep on the context (they hold their device memory between calls)"""
     for job in ctx.__dict__.pop("_refine_jobs", {}).values():
+        job.close()
+    for job in ctx.__dict__.pop("_epic_jobs", {}).values():
         job.close()
     for job in ctx.__dict__.pop("_refine_pair_jobs", {}).values():
         job.close()

@@ -82,6 +82,7 @@ typedef std::unique_ptr<color_image_t, Release<color_image_t, color_image_delete
 typedef std::unique_ptr<sfa_ctx, Release<sfa_ctx, sfa_ctx_destroy>> Ctx;
 typedef std::unique_ptr<sfa_job, Release<sfa_job, sfa_job_destroy>> Job;
 typedef std::unique_ptr<sfa_sequence, Release<sfa_sequence, sfa_sequence_destroy>> DeviceSequence;
+typedef std::unique_ptr<sfa_epic_job, Release<sfa_epic_job, sfa_epic_job_destroy>> EpicJob;
 typedef std::pair<Image, Image> Flow;
 
 static Image zero_image(int w, int h) {
@@ -153,6 +154,9 @@ struct Run {
     const bool deep_matching = p.parameter<bool>("deep_matching");
     const bool gpu_epic = p.parameter<bool>("gpu_epic", "0");                       // additive: deep_matching 1 interpolates a batch's matches through epic_batch (the graph searches on the GPU)
     const int gpu_epic_search = p.parameter<int>("gpu_epic_search", "0");          // additive, with gpu_epic 1: 1 = those searches in the library's compact mode (main() refuses other values)
+    // gpu_ingest 1 + deep_matching 1 + gpu_epic 1: the initialisation stays on the GPU from the frames to the job's initial flow (sfa_sequence_lab, sfa_epic_job,
+    // sfa_job_set_flow_epic); only the match and edge files are read on the host
+    const bool resident_epic = gpu_ingest && deep_matching && gpu_epic;
     // dm_scale (:396-402, :571-586, :801-843): DeepMatching and the edge detector ran on frames blurred (sigma = 1 / sqrt(2 dm_scale)) and resized by dm_scale; the
     // interpolation then runs at that resolution (the saliency image, the edge map, the matches' coordinates) and its flow is resized to the frames and multiplied by the
     // INTEGER ratio of the widths (:827-828: `float fx = im[ref]->width / wx->width` divides two ints).  dm_scale_run = dm_scale, halved by main() when max_flow > 150
@@ -215,14 +219,16 @@ static bool deep_matching_inputs_exist(const Run &run, bool resume) {
 // the sums of the frames it does not hold itself.  A GPU without windows only creates its context: with nothing to refine nobody waits for statistics.
 class Sequence {
 public:
-    struct Gpu { Ctx ctx; DeviceSequence resident; string err; bool ready = false; double upload_bytes = 0, upload_done_s = 0, ready_s = 0, first_refine_s = -1; };   // (resident goes before ctx; s since the run began)
+    struct Gpu { Ctx ctx; DeviceSequence resident, lab; string err; bool ready = false; double upload_bytes = 0, upload_done_s = 0, ready_s = 0, first_refine_s = -1; };   // (resident and lab go before ctx; s since the run began; lab: the L*a*b* images of the reference frames of the GPU's windows at the interpolation's size, one frame each (lab_slot; resident_epic))
     std::vector<ColorImage> frames;              // by frame of the pass (only [start_f, end_f) is loaded); width x height: published with the first frame
     std::vector<int> maxval;                     // 255 / 65535 per frame: the 8-bit copy EpicFlow's saliency works on divides 16-bit samples by 255 (:472-474, :578)
     std::vector<Mosaic> mosaics;                 // gpu_ingest 1: the decoded mosaics instead of `frames`; the GPUs demosaic, crop and rescale them
     int width = 0, height = 0, stride = 0;       // the frames the solver sees (after crop and rescale), and the row stride of their host images
     const std::vector<FrameRange> &gpu_frames;
-    Sequence(const Run &run, const std::vector<FrameRange> &gpu_frames_, double t_begin)
-        : frames(run.layout.frames), maxval(run.layout.frames, 255), mosaics(run.gpu_ingest ? run.layout.frames : 0), gpu_frames(gpu_frames_), run_(run), t_begin_(t_begin), n_loaded_((int)(run.layout.end_f - run.layout.start_f)),
+    const std::vector<std::vector<char>> &lab_frames_;
+    // lab_frames[g][f] (resident_epic; else empty): loaded frame f is the reference frame of one of GPU g's windows
+    Sequence(const Run &run, const std::vector<FrameRange> &gpu_frames_, const std::vector<std::vector<char>> &lab_frames, double t_begin)
+        : frames(run.layout.frames), maxval(run.layout.frames, 255), mosaics(run.gpu_ingest ? run.layout.frames : 0), gpu_frames(gpu_frames_), lab_frames_(lab_frames), run_(run), t_begin_(t_begin), n_loaded_((int)(run.layout.end_f - run.layout.start_f)),
           frame_ready_(run.layout.frames, 0), have_sums_(n_loaded_, 0), frame_sums_((size_t)6 * n_loaded_, 0.0), gpus_(run.ngpu) {
         for (int g = 0; g < run.ngpu; g++) up_.emplace_back(&Sequence::upload, this, g);
     }
@@ -287,6 +293,13 @@ public:
         return true;
     }
     const Gpu &gpu(int g) const { return gpus_[g]; }                              // resident: after wait_gpu(g); times: once the threads have ended
+    // resident_epic: where GPU g's Lab sequence holds the Lab image of loaded frame f (a reference frame of one of its windows): the sequence has one frame
+    // per such frame, in frame order
+    int lab_slot(int g, int f) const {
+        int slot = 0;
+        for (int k = 0; k < f; k++) slot += lab_frames_[g][k] != 0;
+        return slot;
+    }
     bool report_errors() {                                                           // joins the uploaders, prints each GPU's error; true if there was one
         join();
         bool any = false;
@@ -329,6 +342,19 @@ private:
             rc = sfa_sequence_create(gpu.ctx.get(), src_width_, src_height_, 1, &t);
             full.reset(t);
         }
+        // resident_epic: the Lab image of every reference frame, from the frame as it was read (before the normalisation), at the interpolation's size
+        // (:571-573, 578-586: blur and resize by dm_scale, convertTo(CV_8U, norm), rgb_to_lab)
+        DeviceSequence dm;
+        const int ew = run_.dm_scale != 1 ? (int)std::lrint(width * run_.dm_scale) : width, eh = run_.dm_scale != 1 ? (int)std::lrint(height * run_.dm_scale) : height;
+        if (run_.resident_epic && rc == SFA_OK && ew >= 1 && eh >= 1) {
+            sfa_sequence *t = nullptr;
+            rc = sfa_sequence_create(gpu.ctx.get(), ew, eh, std::max(1, lab_slot(g, (int)lab_frames_[g].size())), &t);
+            gpu.lab.reset(t);
+            if (rc == SFA_OK && run_.dm_scale != 1) {
+                rc = sfa_sequence_create(gpu.ctx.get(), ew, eh, 1, &t);
+                dm.reset(t);
+            }
+        }
         double sent = 0;
         for (int f = fr.lo; f < fr.hi && rc == SFA_OK; f++) {
             if (!wait([&] { return frame_ready_[start_f + f] != 0; })) return;
@@ -341,6 +367,10 @@ private:
             } else {
                 rc = sfa_sequence_upload(s, f - fr.lo, frames[start_f + f]->c1, frames[start_f + f]->stride);
                 sent += (double)3 * width * height * sizeof(float);
+            }
+            if (rc == SFA_OK && gpu.lab && lab_frames_[g][start_f + f]) {
+                if (dm) rc = sfa_sequence_rescale(dm.get(), 0, s, f - fr.lo, 1, (float)run_.dm_scale);
+                if (rc == SFA_OK) rc = sfa_sequence_lab(gpu.lab.get(), lab_slot(g, start_f + f), dm ? dm.get() : s, dm ? 0 : f - fr.lo, 1, maxval[start_f + f] > 255 ? 1.0f / 255 : 1.0f);
             }
         }
         std::vector<double> mine((size_t)6 * n_mine);
@@ -465,7 +495,7 @@ static int load_ground_truth(const Run &run, std::vector<Flow> &gt) {
     return 0;
 }
 
-struct EpicInit { Image wx, wy; int rc = SFA_OK; };     // the initial flow of one window (deep_matching 1)
+struct EpicInit { Image wx, wy; int rc = SFA_OK, er = 0; };     // the initial flow of one window (deep_matching 1); er: what epic() returned for it (1: no match left, zeros)
 // what epic() reads for one window: the matches, the edge map and the L*a*b* frame at the interpolation's resolution ew x eh
 struct EpicInput { epic_matches mt; epic_edges ed; ColorImage lab; int ew = 0, eh = 0; };
 static epic_params_t driver_epic_params() {
@@ -475,15 +505,12 @@ static epic_params_t driver_epic_params() {
     return ep;
 }
 
-// the inputs of EpicFlow's interpolation of the matches of one window (:801-863 / :960-1004); SFA_OK or the error
-static int epic_inputs(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, EpicInput &in) {
+// the match and edge files of one window, read at the interpolation's size ew x eh; SFA_OK or the error
+static int epic_files(const Run &run, const Sequence &seq, const Window &wd, std::mutex &io_mu, epic_matches &mt, epic_edges &ed, int *ew_out, int *eh_out) {
     const int width = seq.width, height = seq.height;
     const double dm_scale = run.dm_scale;
     const JetFrames n = jet_frames(run.start, wd.jet, run.steps, run.skip);
-    const int a = n.from, b = n.to, fi = window_tap(wd.jet, wd.backward, run.steps, run.steps, 0);   // fi: un_im[ref] / un_im_back[ref], the reference frame, not normalised
-    const color_image_t *un_ref = seq.frames[fi].get();
-    epic_matches &mt = in.mt;
-    epic_edges &ed = in.ed;
+    const int a = n.from, b = n.to;
     // the resolution the interpolation runs at: cv::resize(img, img, Size(0, 0), dm_scale, dm_scale) makes cvRound(cols * dm_scale) x cvRound(rows * dm_scale)
     const int ew = dm_scale != 1 ? (int)std::lrint(width * dm_scale) : width, eh = dm_scale != 1 ? (int)std::lrint(height * dm_scale) : height;
     // ... while the reference allocates un_seq / wx and sizes the edge file with the TRUNCATED product (`color_image_new(width*dm_scale, height*dm_scale)`,
@@ -498,6 +525,18 @@ static int epic_inputs(const Run &run, const Sequence &seq, const Window &wd, sf
     }
     if (ew < 1 || eh < 1 || !read_matches((wd.backward ? matches_file(run, b, a) : matches_file(run, a, b)).c_str(), mt) ||
         !read_edges((wd.backward ? edges_file(run, b) : edges_file(run, a)).c_str(), ew, eh, ed)) return SFA_ERR_ARG;
+    *ew_out = ew; *eh_out = eh;
+    return SFA_OK;
+}
+
+// the inputs of EpicFlow's interpolation of the matches of one window (:801-863 / :960-1004); SFA_OK or the error
+static int epic_inputs(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, EpicInput &in) {
+    const double dm_scale = run.dm_scale;
+    const int fi = window_tap(wd.jet, wd.backward, run.steps, run.steps, 0);   // fi: un_im[ref] / un_im_back[ref], the reference frame, not normalised
+    const color_image_t *un_ref = seq.frames[fi].get();
+    int ew = 0, eh = 0;
+    const int frc = epic_files(run, seq, wd, io_mu, in.mt, in.ed, &ew, &eh);
+    if (frc != SFA_OK) return frc;
     // the reference hands epic() un_seq: the frame after img.convertTo(CV_8U, norm), i.e. rounded to nearest and saturated to 0..255,
     // 16-bit samples scaled by 1/255 first (slow_flow.cpp:472-474, :578-586) -- not the float frame the refinement reads
     // :571-573: GaussianBlur(sigma = 1 / sqrt(2 dm_scale), BORDER_REPLICATE) then resize by dm_scale, on the float frame (the pyramid's two
@@ -520,10 +559,19 @@ static int epic_inputs(const Run &run, const Sequence &seq, const Window &wd, sf
     return SFA_OK;
 }
 
+// a field of ew x eh for frames whose width is less than twice ew: the reference would hand a field of the reduced size to a solver of the frames' size
+// (1 < width ratio < 2): it has no defined result, refused by name
+static bool reduced_field_kept(const Run &run, const Sequence &seq, int ew, int eh, std::mutex &io_mu) {
+    if (seq.width / ew != 1 || (ew == seq.width && eh == seq.height)) return false;
+    std::lock_guard<std::mutex> l(io_mu);
+    std::cerr << "dm_scale " << run.dm_scale << ": the frames are " << seq.width << " wide, the interpolation " << ew << " -- the reference rescales by the integer ratio "
+              << seq.width / ew << " (slow_flow.cpp:827) and would keep the reduced field; use a dm_scale of 1 / n" << std::endl;
+    return true;
+}
+
 // epic()'s field wx, wy (ew x eh; er: what epic() returned for it) -> the window's initial flow per single frame step; SFA_OK or the error
 static int epic_to_initial_flow(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, int er, Image &wx, Image &wy) {
     const int width = seq.width, height = seq.height, ew = wx->width, eh = wx->height;
-    const double dm_scale = run.dm_scale;
     const int a = jet_frames(run.start, wd.jet, run.steps, run.skip).from;
     if (er < 0) return SFA_ERR_HIP;
     if (er > 0) { image_erase(wx.get()); image_erase(wy.get()); }                   // no usable match: start from zero like deep_matching 0
@@ -535,11 +583,7 @@ static int epic_to_initial_flow(const Run &run, const Sequence &seq, const Windo
         if (rc == SFA_OK) rc = sfa_resize_linear(ctx, fwy->data, width, height, fwy->stride, wy->data, ew, eh, wy->stride);
         if (rc != SFA_OK) return rc;
         wx = std::move(fwx); wy = std::move(fwy);
-    } else if (ew != width || eh != height) {
-        // the reference would hand a field of the reduced size to a solver of the frames' size here (1 < width ratio < 2): it has no defined result
-        std::lock_guard<std::mutex> l(io_mu);
-        std::cerr << "dm_scale " << dm_scale << ": the frames are " << width << " wide, the interpolation " << ew << " -- the reference rescales by the integer ratio "
-                  << width / ew << " (slow_flow.cpp:827) and would keep the reduced field; use a dm_scale of 1 / n" << std::endl;
+    } else if (reduced_field_kept(run, seq, ew, eh, io_mu)) {
         return SFA_ERR_ARG;
     }
     image_mul_scalar(wx.get(), fx / run.steps);                                      // :842-843
@@ -550,13 +594,14 @@ static int epic_to_initial_flow(const Run &run, const Sequence &seq, const Windo
 }
 
 // EpicFlow's interpolation of the matches of one window, per single frame step, into wx, wy; SFA_OK or the error
-static int interpolate_matches(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, Image &wx, Image &wy) {
+static int interpolate_matches(const Run &run, const Sequence &seq, const Window &wd, sfa_ctx *ctx, std::mutex &io_mu, Image &wx, Image &wy, int *er) {
     EpicInput in;
     const int rc = epic_inputs(run, seq, wd, ctx, io_mu, in);
     if (rc != SFA_OK) return rc;
     const epic_params_t ep = driver_epic_params();
     wx = zero_image(in.ew, in.eh); wy = zero_image(in.ew, in.eh);
-    return epic_to_initial_flow(run, seq, wd, ctx, io_mu, epic(ctx, wx.get(), wy.get(), in.lab.get(), in.mt, in.ed, &ep), wx, wy);
+    *er = epic(ctx, wx.get(), wy.get(), in.lab.get(), in.mt, in.ed, &ep);
+    return epic_to_initial_flow(run, seq, wd, ctx, io_mu, *er, wx, wy);
 }
 
 // the same for the windows [b0, b0 + v.size()) of `mine` at once, through epic_batch: the graph searches of the whole batch in two GPU calls (gpu_epic 1)
@@ -577,6 +622,7 @@ static void interpolate_matches_batch(const Run &run, const Sequence &seq, const
     std::vector<int> er(use.size());
     const epic_params_t ep = driver_epic_params();
     epic_batch(ctx, (int)use.size(), fx.data(), fy.data(), lab.data(), mt.data(), ed.data(), &ep, er.data());
+    for (size_t k = 0; k < use.size(); k++) v[use[k]].er = er[k];
     for (size_t k = 0; k < use.size(); k++) v[use[k]].rc = epic_to_initial_flow(run, seq, todo[mine[b0 + use[k]]], ctx, io_mu, er[k], v[use[k]].wx, v[use[k]].wy);
 }
 
@@ -618,12 +664,76 @@ struct Refinement {
     TaskPool &out_pool;
     std::mutex io_mu;
     std::atomic<bool> failed;
+    std::atomic<int> init_from_matches, init_from_zero;   // deep_matching 1: the windows whose interpolation gave a field (epic() returned 0) / had no match left (1)
+    int search_mode;                             // resident_epic: the search mode of the contexts the epic jobs ran on (-1: none ran), and sfa_epic_nn_search_info summed over their runs
+    long long search_info[4];
+    std::mutex lab_mu;                           // resident_epic: a GPU's Lab sequence lives on its uploader's context, which takes one caller at a time
     void fail(const string &message) {           // on stderr; the pass ends with exit code 5
         std::lock_guard<std::mutex> l(io_mu);
         std::cerr << message << std::endl;
         failed = true;
     }
 };
+
+// resident_epic: what the match and edge files of one window hold
+struct EpicFiles { epic_matches mt; epic_edges ed; int ew = 0, eh = 0, rc = SFA_OK; };
+static sfa_epic_params library_epic_params(const epic_params_t &ep) {
+    sfa_epic_params p;
+    p.method = strcmp(ep.method, "LA") ? 1 : 0; p.saliency_th = ep.saliency_th; p.pref_nn = ep.pref_nn; p.pref_th = ep.pref_th; p.nn = ep.nn;
+    p.coef_kernel = ep.coef_kernel; p.euc = ep.euc;
+    return p;
+}
+
+// resident_epic: the fields of a batch's windows on the worker's context -- the files' matches and edges go up, the Lab frames come from the GPU's Lab
+// sequence, sfa_epic_job_run interpolates; an image the run flags takes epic() of the host on its Lab frame, downloaded (the same bits), and its field goes
+// back into the epic job.  `lab_index[e]`: window e's reference frame in the Lab sequence.  SFA_OK or the error
+static int resident_epic_fields(Refinement &rf, const WorkerPlan &wp, sfa_ctx *ctx, sfa_ctx *ectx, EpicJob &ejob, int &ejob_n, std::vector<EpicFiles> &files,
+                                const std::vector<int> &lab_index) {
+    const Run &run = rf.run;
+    const int nb = (int)files.size(), ew = files[0].ew, eh = files[0].eh;
+    for (const EpicFiles &f : files)
+        if (f.rc != SFA_OK) return f.rc;
+    if (reduced_field_kept(run, rf.seq, ew, eh, rf.io_mu)) return SFA_ERR_ARG;
+    const epic_params_t ep = driver_epic_params();
+    int rc = SFA_OK;
+    if (!ejob || ejob_n != nb) {
+        ejob.reset();
+        const sfa_epic_params lp = library_epic_params(ep);
+        sfa_epic_job *j = nullptr;
+        rc = sfa_epic_job_create(ctx, &lp, ew, eh, nb, &j);
+        ejob.reset(j);
+        ejob_n = nb;
+    }
+    for (int e = 0; e < nb && rc == SFA_OK; e++) rc = sfa_epic_job_upload(ejob.get(), e, files[e].mt.m.data(), files[e].mt.count(), files[e].ed.cost.data());
+    sfa_sequence *lab_seq = rf.seq.gpu(wp.gpu).lab.get();
+    if (rc == SFA_OK) rc = sfa_epic_job_set_lab(ejob.get(), 0, nb, lab_seq, lab_index.data());
+    std::vector<int> er(nb, 0), status(nb, 0);
+    if (rc == SFA_OK) rc = sfa_epic_job_run(ejob.get(), nb, er.data(), nullptr, 0, status.data());
+    long long info[4] = {0, 0, 0, 0};                                                // the last search of the run, as the library counted it
+    if (rc == SFA_OK) rc = sfa_epic_nn_search_info(ctx, info);
+    if (rc == SFA_OK) {
+        std::lock_guard<std::mutex> l(rf.lab_mu);
+        rf.search_mode = run.gpu_epic_search;                                        // (set on `ctx` by refine_worker before its first batch)
+        for (int k = 0; k < 3; k++) rf.search_info[k] += info[k];
+        rf.search_info[3] = std::max(rf.search_info[3], info[3]);
+    }
+    for (int e = 0; e < nb && rc == SFA_OK; e++) {
+        if (status[e]) {                                                             // does not fit the interpolation's workspace even alone: the host's epic()
+            ColorImage lab(color_image_new(ew, eh));
+            {
+                std::lock_guard<std::mutex> l(rf.lab_mu);
+                rc = sfa_sequence_download(lab_seq, lab_index[e], lab->c1, lab->stride);
+            }
+            Image wx = zero_image(ew, eh), wy = zero_image(ew, eh);
+            if (rc == SFA_OK) er[e] = epic(ectx, wx.get(), wy.get(), lab.get(), files[e].mt, files[e].ed, &ep);
+            if (rc == SFA_OK && er[e] < 0) rc = SFA_ERR_HIP;
+            if (rc == SFA_OK && er[e] > 0) { image_erase(wx.get()); image_erase(wy.get()); }
+            if (rc == SFA_OK) rc = sfa_epic_job_upload_flow(ejob.get(), e, wx->data, wy->data, wx->stride);
+        }
+        if (rc == SFA_OK) (er[e] == 0 ? rf.init_from_matches : rf.init_from_zero)++;
+    }
+    return rc;
+}
 
 // the windows `mine` of one worker in lockstep batches of gpu_batch on ONE resident job (re-created only for a shorter last batch); with deep_matching 1 the initial flows are
 // prepared one batch ahead on a helper thread (ectx: the library's contexts are thread-compatible, not thread-safe); the results go to the output pool meanwhile
@@ -637,18 +747,37 @@ static void refine_windows(Refinement &rf, const WorkerPlan &wp, sfa_ctx *ctx, s
         std::vector<EpicInit> v(std::min((size_t)run.batch, mine.size() - b0));
         if (run.gpu_epic) interpolate_matches_batch(run, rf.seq, rf.todo, mine, b0, ectx, rf.io_mu, v);
         for (size_t e = 0; e < v.size(); e++)
-            if ((run.gpu_epic ? v[e].rc : v[e].rc = interpolate_matches(run, rf.seq, rf.todo[mine[b0 + e]], ectx, rf.io_mu, v[e].wx, v[e].wy)) != SFA_OK) {
+            if ((run.gpu_epic ? v[e].rc : v[e].rc = interpolate_matches(run, rf.seq, rf.todo[mine[b0 + e]], ectx, rf.io_mu, v[e].wx, v[e].wy, &v[e].er)) != SFA_OK) {
                 std::lock_guard<std::mutex> l(rf.io_mu);
                 std::cerr << "EpicFlow initialisation of jet " << rf.todo[mine[b0 + e]].jet << " failed" << std::endl;
             }
         return v;
     };
+    // resident_epic: only the files are read ahead (the helper touches no GPU); the interpolation runs on the worker's own context, whose stream orders it
+    // before sfa_job_set_flow_epic
+    auto batch_files = [&](size_t b0) {
+        std::vector<EpicFiles> v(std::min((size_t)run.batch, mine.size() - b0));
+        for (size_t e = 0; e < v.size(); e++)
+            if ((v[e].rc = epic_files(run, rf.seq, rf.todo[mine[b0 + e]], rf.io_mu, v[e].mt, v[e].ed, &v[e].ew, &v[e].eh)) != SFA_OK) {
+                std::lock_guard<std::mutex> l(rf.io_mu);
+                std::cerr << "EpicFlow initialisation of jet " << rf.todo[mine[b0 + e]].jet << " failed" << std::endl;
+            }
+        return v;
+    };
+    EpicJob ejob;
+    int ejob_n = 0;
     std::future<std::vector<EpicInit>> next_inits;                                   // (a batch prepared ahead and not used is released with it)
-    if (run.deep_matching) next_inits = std::async(std::launch::async, batch_inits, (size_t)0);
+    std::future<std::vector<EpicFiles>> next_files;
+    if (run.resident_epic) next_files = std::async(std::launch::async, batch_files, (size_t)0);
+    else if (run.deep_matching) next_inits = std::async(std::launch::async, batch_inits, (size_t)0);
     for (size_t b0 = 0; b0 < mine.size() && rc == SFA_OK && !rf.failed; b0 += run.batch) {
         const int nb = (int)std::min((size_t)run.batch, mine.size() - b0);
         std::vector<EpicInit> inits;
-        if (run.deep_matching) {
+        std::vector<EpicFiles> files;
+        if (run.resident_epic) {
+            files = next_files.get();
+            if (b0 + run.batch < mine.size()) next_files = std::async(std::launch::async, batch_files, b0 + run.batch);
+        } else if (run.deep_matching) {
             inits = next_inits.get();
             if (b0 + run.batch < mine.size()) next_inits = std::async(std::launch::async, batch_inits, b0 + run.batch);
         }
@@ -661,14 +790,21 @@ static void refine_windows(Refinement &rf, const WorkerPlan &wp, sfa_ctx *ctx, s
             job_nb = nb;
             if (rc == SFA_OK && run.out_alt_occ) rc = sfa_job_keep_alternation_occlusions(j, 1);
         }
+        if (rc == SFA_OK && run.resident_epic) {
+            std::vector<int> lab_index(nb);
+            for (int e = 0; e < nb; e++) lab_index[e] = rf.seq.lab_slot(wp.gpu, window_tap(rf.todo[mine[b0 + e]].jet, rf.todo[mine[b0 + e]].backward, run.steps, run.steps, 0));
+            rc = resident_epic_fields(rf, wp, ctx, ectx, ejob, ejob_n, files, lab_index);
+        }
         for (int e = 0; e < nb && rc == SFA_OK; e++) {
             const Window &wd = rf.todo[mine[b0 + e]];
             std::vector<int> idx(F);
             for (int k = 0; k < F; k++) idx[k] = window_tap(wd.jet, wd.backward, run.steps, k, first);
             const color_image_t *cw = rf.channel_weights;                            // (null with gpu_ingest 1)
             const float *chw[3] = {cw ? cw->c1 : nullptr, cw ? cw->c2 : nullptr, cw ? cw->c3 : nullptr};
-            const image_t *iwx = run.deep_matching ? inits[e].wx.get() : nullptr, *iwy = run.deep_matching ? inits[e].wy.get() : nullptr;
-            if (run.deep_matching) rc = inits[e].rc;
+            const bool host_init = run.deep_matching && !run.resident_epic;          // resident_epic: NULL here, sfa_job_set_flow_epic below
+            const image_t *iwx = host_init ? inits[e].wx.get() : nullptr, *iwy = host_init ? inits[e].wy.get() : nullptr;
+            if (host_init) rc = inits[e].rc;
+            if (host_init && rc == SFA_OK) (inits[e].er == 0 ? rf.init_from_matches : rf.init_from_zero)++;
             // only the forward solver gets the channel weights (:876 vs :1018); without raw weighting they are all ones (:597-598), which is
             // what a NULL pointer means to the library (x * 1.0f is exact: same bits, three planes less to read per pixel)
             if (rc == SFA_OK)
@@ -677,6 +813,10 @@ static void refine_windows(Refinement &rf, const WorkerPlan &wp, sfa_ctx *ctx, s
             // gpu_ingest 1: the same weights, formed on the GPU (after the upload, which sets the window's weights to ones).  raw_weight 1 gives
             // all ones (rawWeighting: weight 1, the others 0.5 * (3 - 1)), which is what the NULL above already means: no planes, same bits
             if (rc == SFA_OK && run.gpu_ingest && !wd.backward && run.raw_weight != 1.0f) rc = sfa_job_set_raw_weights(job.get(), e, 1, run.red_x, run.red_y, run.raw_weight);
+        }
+        if (rc == SFA_OK && run.resident_epic) {                                     // epic_to_initial_flow on the GPU: fx / steps, fy / steps (:826-843)
+            const float fx = (float)(width / files[0].ew), fy = (float)(height / files[0].eh);
+            rc = sfa_job_set_flow_epic(job.get(), 0, nb, ejob.get(), 0, fx / run.steps, fy / run.steps);
         }
         if (rc == SFA_OK) rc = sfa_job_run(job.get());
         std::vector<std::shared_ptr<WindowResult>> results;
@@ -724,7 +864,10 @@ static void refine_worker(Refinement &rf, const WorkerPlan &wp) {
     const Ctx ectx = ctx && run.deep_matching ? new_ctx(run.device_of(wp.gpu)) : Ctx();   // the EpicFlow helper's context (deep_matching 1 only)
     if (!ctx || (run.deep_matching && !ectx)) return rf.fail(sfa_last_error(nullptr));
     (void)sfa_ctx_set_verbose(ctx.get(), run.verbose_changes ? 1 : 0);
+    // gpu_epic_search 1: on the context that runs the interpolation's searches -- the helper's, and on the resident route the worker's own (which also keeps
+    // the helper's for the host epic() of an image the run flags)
     if (ectx && run.gpu_epic && run.gpu_epic_search && sfa_ctx_set_epic_search(ectx.get(), SFA_EPIC_SEARCH_COMPACT) != SFA_OK) return rf.fail(sfa_last_error(ectx.get()));
+    if (run.resident_epic && run.gpu_epic_search && sfa_ctx_set_epic_search(ctx.get(), SFA_EPIC_SEARCH_COMPACT) != SFA_OK) return rf.fail(sfa_last_error(ctx.get()));
     if (!rf.seq.wait_gpu(wp.gpu)) { rf.failed = true; return; }
     ParameterList tp(run.p);                                                         // one copy per thread (:708), with the published normalisation
     for (int dirpass = 0; dirpass < (run.forward_only ? 2 : 1) && !rf.failed; dirpass++) {
@@ -736,7 +879,7 @@ static void refine_worker(Refinement &rf, const WorkerPlan &wp) {
 }
 
 // the gathered per-window timings (the only cross-GPU exchange of the path) and where the wall time of the run went (seconds)
-static void write_timings(const Run &run, const std::vector<Window> &todo, const Sequence &seq, double decode, double normalize, double ingest, double refine, double total) {
+static void write_timings(const Run &run, const std::vector<Window> &todo, const Sequence &seq, const Refinement &rf, double decode, double normalize, double ingest, double refine, double total) {
     std::ofstream tj((run.output + "timings.json").c_str());
     tj << "[";
     for (size_t i = 0; i < todo.size(); i++)
@@ -746,7 +889,9 @@ static void write_timings(const Run &run, const std::vector<Window> &todo, const
     tj << "\n]\n";
     std::ofstream rj((run.output + "run.json").c_str());
     rj << "{\"windows\": " << todo.size() << ", \"gpus\": " << run.ngpu << ", \"streams\": " << run.streams << ", \"batch\": " << run.batch << ", \"io_threads\": " << run.io_threads
-       << ", \"ingest_path\": \"" << (run.gpu_ingest ? "gpu" : "host") << "\", \"gpu_epic_search\": " << run.gpu_epic_search << ", \"decode_seconds\": " << decode << ", \"normalize_seconds\": " << normalize << ", \"ingest_seconds\": " << ingest << ", \"refine_seconds\": " << refine << ", \"total_seconds\": " << total;
+       << ", \"ingest_path\": \"" << (run.gpu_ingest ? "gpu" : "host") << "\", \"gpu_epic_search\": " << run.gpu_epic_search << ", \"epic_init_path\": \"" << (run.resident_epic ? "resident" : "host") << "\", \"epic_init_from_matches\": " << rf.init_from_matches
+       << ", \"epic_init_from_zero\": " << rf.init_from_zero << ", \"epic_init_search\": {\"mode\": " << rf.search_mode << ", \"slices\": " << rf.search_info[0] << ", \"dense\": " << rf.search_info[1]
+       << ", \"sparse\": " << rf.search_info[2] << ", \"workspace_bytes\": " << rf.search_info[3] << "}" << ", \"decode_seconds\": " << decode << ", \"normalize_seconds\": " << normalize << ", \"ingest_seconds\": " << ingest << ", \"refine_seconds\": " << refine << ", \"total_seconds\": " << total;
     // per GPU: the frames it was sent (its windows' frames + halo), when the last of them had arrived, when its frames were normalised and when its first worker
     // began to refine -- all in seconds since the run began.  The whole sequence is "sequence_bytes"
     double last_upload = 0, first_refine = -1;
@@ -771,7 +916,7 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     }
     if (run.gpu_ingest) {                                                            // the runs that need the RGB frames on the host: refused by name, never a silent host path
         const char *why = !run.raw ? "raw 0: the frames are no mosaics, there is nothing to demosaic on the GPU"
-                          : run.deep_matching ? "deep_matching 1: EpicFlow's initialisation reads the RGB frames on the host"
+                          : run.deep_matching && !run.gpu_epic ? "deep_matching 1: EpicFlow's initialisation reads the RGB frames on the host unless gpu_epic 1 keeps it on the GPU (set gpu_epic 1)"
                           : run.write_files ? "verbose: this verbosity writes sequence/frame_*.png and the tmp/ images from the RGB frames on the host"
                                             : nullptr;
         if (why) { std::cerr << "gpu_ingest 1 is refused with " << why << "; set gpu_ingest 0" << std::endl; return 1; }
@@ -789,9 +934,22 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     for (const Window &wd : todo) spans.push_back(window_span(wd.jet, wd.backward, run.steps, (int)run.layout.start_f));
     const std::vector<FrameRange> gpu_frames = plan_frames(spans, plan, run.ngpu, (int)(run.layout.end_f - run.layout.start_f));
 
-    Sequence seq(run, gpu_frames, t_begin);                                          // one uploader thread per GPU, from now on
+    // resident_epic: the frames whose Lab image a GPU needs -- the reference frames of its windows (un_seq[ref], :809)
+    std::vector<std::vector<char>> lab_frames(run.resident_epic ? run.ngpu : 0, std::vector<char>(run.layout.frames, 0));
+    if (run.resident_epic)
+        for (const WorkerPlan &wp : plan)
+            for (size_t i = wp.lo; i < wp.hi; i++) lab_frames[wp.gpu][window_tap(todo[i].jet, todo[i].backward, run.steps, run.steps, 0)] = 1;
+    Sequence seq(run, gpu_frames, lab_frames, t_begin);                                          // one uploader thread per GPU, from now on
     double decoded_at = 0;
     if (const int rc = read_frames(run, sequence_path, format, seq, decoded_at)) return rc;
+    if (run.resident_epic && run.dm_scale != 1) {                                    // sfa_job_set_flow_epic takes fields whose size divides the frames' in both directions
+        const int ew = (int)std::lrint(seq.width * run.dm_scale), eh = (int)std::lrint(seq.height * run.dm_scale);
+        if (ew < 1 || eh < 1 || seq.width % ew != 0 || seq.height % eh != 0) {
+            std::cerr << "gpu_ingest 1 is refused with deep_matching 1 and dm_scale " << run.dm_scale << " on " << seq.width << " x " << seq.height << " frames: the interpolation's " << ew << " x " << eh
+                      << " does not divide them, and the resident initialisation resizes only by whole factors; crop the frames to a multiple of 1 / dm_scale, or set gpu_ingest 0" << std::endl;
+            return 1;
+        }
+    }
     ColorImage channel_weights(run.gpu_ingest ? nullptr : color_image_new(seq.width, seq.height));   // :597-598 (all ones without raw weighting); gpu_ingest 1: the GPUs form them
     if (channel_weights) {
         std::fill(channel_weights->c1, channel_weights->c1 + (size_t)3 * channel_weights->stride * seq.height, 1.0f);
@@ -813,7 +971,7 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     if (run.out_occ) mkdirs(run.output + "occlusion/");                              // :676-677
     if (run.out_alt_occ || run.deep_matching) mkdirs(run.output + "tmp/");
     TaskPool out_pool(run.io_threads);
-    Refinement rf{run, seq, channel_weights.get(), gt, todo, out_pool, {}, {false}};
+    Refinement rf{run, seq, channel_weights.get(), gt, todo, out_pool, {}, {false}, {0}, {0}, -1, {0, 0, 0, 0}, {}};
     const double t_compute = now_s();
     std::vector<std::thread> th;
     for (const WorkerPlan &wp : plan) th.emplace_back(refine_worker, std::ref(rf), wp);
@@ -821,7 +979,7 @@ static int run_sequence(ParameterList &params, const string &sequence_path, cons
     const double compute_seconds = now_s() - t_compute;
     if (seq.report_errors()) rf.failed = true;
     out_pool.wait_all();
-    write_timings(run, todo, seq, decoded_at - t_begin, normalize_seconds, ingest_seconds, compute_seconds, now_s() - t_begin);
+    write_timings(run, todo, seq, rf, decoded_at - t_begin, normalize_seconds, ingest_seconds, compute_seconds, now_s() - t_begin);
     return rf.failed ? 5 : 0;
 }
 
