@@ -337,6 +337,11 @@ typedef struct sfa_fuse_params {
     double acc_beta;                /* acc_beta ("10.0") */
     double acc_spatial_occ;         /* acc_spatial_occ (10.0; setDefault's key is misspelt acc_satial_occ and never read) */
     int    traj_sim_method;         /* acc_traj_sim_method ("1"): 0 ADJ, 1 ACC; 2 FINAL is refused (it reads flow_y[Jets], past the array) */
+    int    pin_first;               /* 0 (the default: every slot is sorted).  1: slot 0, where present, stays the first label whatever its energy -- the
+                                     * alternation's rounds p > 0, whose sort covers positions 1 onward (:1601-1602); the NMS then measures the others
+                                     * against it.  The field takes the four bytes of padding the struct had here: sizes and offsets are unchanged.
+                                     * A CALLER THAT FILLS THE STRUCT FIELD BY FIELD WITHOUT sfa_fuse_params_default now passes indeterminate bytes
+                                     * here: call the default first, or set the field.  The track jobs refuse pin_first != 0 at creation */
     double traj_sim_thres;          /* acc_traj_sim_thres ("0.1") */
     double trws_eps;                /* acc_trws_eps ("1e-5") */
     int    trws_max_iter;           /* acc_trws_max_iter ("10") */
@@ -355,6 +360,61 @@ void sfa_fuse_params_default(sfa_fuse_params *p);
 int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, const double *U, const double *V, const double *energy,
                         const unsigned long long *occ_bits, const float *weight, int *slot, double *flow_u, double *flow_v, unsigned char *occ,
                         double *seg_energy, double *seg_bound, int *seg_iters, float *stage_ms);
+/* ---- dense_tracking's alternation around the fusion (dense_tracking.cpp:1381-1583) on the GPU (csrc/neigh.hip), as INTEGRATION.md 4d defines it: the
+ * reference's own result depends on FLANN's result order, on one random engine consumed pixel after pixel and on an out-of-bounds read, so the stage is
+ * pinned to a restatement (tests/neigh_ref.py), like the fusion.  Host pointers; each call waits for its results.
+ * A pixel's hypothesis list has 16 positions: U, V [n][16][Jets][gh][gw] adapted flows, energy [n][16][gh][gw] (+Inf or NaN: no hypothesis at that
+ * position), occ_bits [n][16][gh][gw], origin [n][16][gh][gw]: the slot the hypothesis was born in, | 0x80 once it has arrived as a neighbour's proposal. */
+typedef struct sfa_hyp_lists {
+    double *U, *V, *energy;
+    unsigned long long *occ_bits;
+    unsigned char *origin;
+} sfa_hyp_lists;
+/* The keys of the neighbour proposals with setDefault's values (:136-159); seed: the reference takes the clock, here 0. */
+typedef struct sfa_neigh_params {
+    double traj_sim_thres;          /* acc_traj_sim_thres ("0.1") */
+    int    traj_sim_method;         /* acc_traj_sim_method ("1"): 0 ADJ, 1 ACC */
+    int    neigh_hyp;               /* acc_neigh_hyp ("5"): set t may bring the round's proposals to (t + 1) * acc_neigh_hyp */
+    float  neigh_hyp_radius;        /* acc_neigh_hyp_radius ("100.0", read as an int into a float, :631): FLANN's L2 radius, a SQUARED distance */
+    int    neigh_skip1, neigh_skip2;/* acc_neigh_skip1 ("2"), acc_neigh_skip2 ("4"): the candidate lattices */
+    int    hyp_neigh_tryouts;       /* acc_hyp_neigh_tryouts ("20") per set */
+    unsigned seed;                  /* seed: round p draws with the Philox key (seed + p, sequence_start) */
+    int    slots;                   /* (4) round 0: the lists hold hypotheses at positions 0 .. slots - 1 only (2 K under -fill) */
+    int    perturb_keep;            /* acc_perturb_keep (no default: -1 = not set, refused from round 1 on): later rounds' lists end at position perturb_keep */
+} sfa_neigh_params;
+void sfa_neigh_params_default(sfa_neigh_params *p);
+/* The prune of rounds p > 0 (:1384-1416): position 0 of `out` is the position `selected` [n][gh][gw] names (the fusion's slot; -1 or an absent position:
+ * none), then the other present positions by (float) energy, ties to the lower position, while the list holds at most perturb_keep entries -- at most
+ * perturb_keep + 1 in all; every later position is absent (+Inf, zeros).  in and out must not overlap.  stage_ms: NULL or 2 floats, the milliseconds of
+ * the map and the gather kernel (HIP events).  Refused: perturb_keep + 1 outside 1 .. 16. */
+int sfa_prune_hypotheses(sfa_ctx *ctx, int n, int Jets, int gw, int gh, int perturb_keep, const int *selected, const sfa_hyp_lists *in,
+                         const sfa_hyp_lists *out, float *stage_ms);
+/* The neighbour proposals of round `round` (:1432-1583).  out = in with the accepted proposals at the lowest absent positions.  A proposal is a copy of
+ * the drawn candidate pixel's source hypothesis in `in` (round 0: the lowest (float) energy, ties to the lower position; later: position 0): its flows,
+ * its origin | 0x80 and, until the caller has scored it at its new place, the source's energy and occlusion word.  It is discarded when
+ * !(distance(h, proposal) > traj_sim_thres) for a hypothesis h of the list as it stands.  consistent [n][gh][gw] (1 = some rate is tracked over its
+ * whole length) is read in round 0 only and may be NULL later.  sequence_start [n]: the second key word of the segment's draws.  src_pixel, src_position
+ * [n][16][gh][gw]: for a position filled in this call the source's pixel index y * gw + x and position, -1 / 0 elsewhere; accepted [n]: their count;
+ * stage_ms: NULL or 3 floats, the milliseconds of the flag, the search-draw-accept and the gather kernel (HIP events).
+ * Refused by the key's name, before anything is copied: acc_neigh_hyp_radius <= 0 or NaN, acc_neigh_skip1/2 < 1, acc_hyp_neigh_tryouts < 0,
+ * acc_neigh_hyp < 0, acc_traj_sim_method other than 0 or 1; round 0: slots + 2 * acc_neigh_hyp > 16; later rounds: acc_perturb_keep not set,
+ * acc_perturb_keep + 1 + 2 * acc_neigh_hyp > 16; a hypothesis at a position beyond those the round's limit counts (so no list can fill up); a grid side beyond 2896 (d^2 would no longer be exact in fp32). */
+int sfa_neighbour_proposals(sfa_ctx *ctx, const sfa_neigh_params *p, int n, int Jets, int gw, int gh, int round, const unsigned *sequence_start,
+                            const unsigned char *consistent, const sfa_hyp_lists *in, const sfa_hyp_lists *out, int *src_pixel,
+                            unsigned char *src_position, int *accepted, float *stage_ms);
+/* The rescoring of a round's accepted proposals (:1549-1553): each is a trajectory of Jets steps at its new pixel; its occlusions are set from rate
+ * acc_min_fps's flows and its energy is JC + BC/GC + OC + slot_weight[origin & 0x7f] in fp32 -- sfa_hypothesis_energies' kernels on the lists' own flow
+ * planes (r_Jets = Jets, where adaptFPS is the identity), p->weight ignored.  frames, fwd_u .. bwd_v, w, h, stride: as sfa_hypothesis_energies takes
+ * them (flows of the frames' size); the lists are on the grid of (w, h, p->skip).  slot_weight: 16 floats, weight_jet_estimation of the rate each slot
+ * belongs to.  src_pixel: as sfa_neighbour_proposals returned it; positions with src_pixel >= 0 get their energy and occ_bits replaced in `lists`, every
+ * other value is left as it is.  stage_ms: NULL or 1 float, the milliseconds of the scoring launches (the frames' records and the uploads are not in
+ * it).  Refused: what sfa_hypothesis_energies refuses of the sizes; a proposal whose origin names no slot below 16. */
+int sfa_rescore_proposals(sfa_ctx *ctx, const sfa_energy_params *p, int n, int Jets, int w, int h, int stride, const float *const *frames,
+                          const float *const *fwd_u, const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v,
+                          const float *slot_weight, const int *src_pixel, const sfa_hyp_lists *lists, float *stage_ms);
+/* Philox4x32-10 (Salmon et al., SC'11) as the draws use it: on the host, and n (counter, key) pairs through the device function the kernel calls. */
+void sfa_philox4x32_10(const unsigned ctr[4], const unsigned key[2], unsigned out[4]);
+int sfa_philox4x32_10_device(sfa_ctx *ctx, int n, const unsigned *ctr, const unsigned *key, unsigned *out);
 /* ---- the steps around dense_tracking's EpicFlow fill-in (dense_tracking.cpp:1265-1310) for n maps of one size w x h in one call, on the GPU
  * (csrc/fill.hip).  Host pointers; each call waits for its results.  Each refuses with SFA_ERR_ARG, the argument named and nothing launched: n, w or h < 1,
  * a null pointer, w * h > 2^29 (32-bit pixel indices), more than 65535 maps (planes) in a call, and what is listed with it. -------------------------------
@@ -522,6 +582,29 @@ int  sfa_track_job_fill_ms(sfa_track_job *job, float ms[4]);
 /* How the last run's interpolation was cut, summed over the rates: info[0] the sub-batches that ran to their end, info[1] those that were cut short by the
  * workspace and run again with the images that fit.  No result depends on the cut. */
 int  sfa_track_job_fill_info(sfa_track_job *job, int info[2]);
+/* ---- A track job that ALTERNATES (csrc/track_alt.hip): in place of the one fusion it runs `rounds` (acc_alternate) rounds of prune (rounds
+ * p > 0) -> neighbour proposals -> rescoring -> fusion (position 0 pinned in rounds p > 0) on lists of 16 positions made of the job's slots (K, or 2 K with
+ * fill-in), all enqueued by sfa_track_job_run without a host wait between the rounds.  Each step is the stage call's own device function, so start_jet s has the
+ * bits of sfa_prune_hypotheses / sfa_neighbour_proposals / sfa_rescore_proposals / sfa_fuse_hypotheses chained on that start_jet alone, whatever the group.
+ * neigh: the proposals' keys; its slots and traj_sim_* are taken from the job (slots, fuse.traj_sim_*), perturb_keep is needed when rounds > 1.  fill: NULL, or
+ * the parameters of a job that also fills in.  consistent (round 0) = some rate's accumulated hypothesis is tracked over its whole length.  The existing
+ * creators, their byte counts and results are unchanged.  Refused by name, before anything is allocated: rounds < 1, do_fuse 0, what the creators refuse, and
+ * the proposals' limits -- slots + 2 * acc_neigh_hyp > 16, acc_perturb_keep not set or acc_perturb_keep + 1 + 2 * acc_neigh_hyp > 16 with rounds > 1,
+ * acc_neigh_skip1/2 < 1, acc_hyp_neigh_tryouts < 0, acc_neigh_hyp_radius <= 0. */
+typedef struct sfa_track_alt_params {
+    int rounds;                     /* acc_alternate ("5") */
+    sfa_neigh_params neigh;
+} sfa_track_alt_params;
+void sfa_track_alt_params_default(sfa_track_alt_params *a);
+int  sfa_track_job_bytes_alternate(const sfa_track_params *p, const sfa_track_fill_params *fill, const sfa_track_alt_params *alt, size_t *bytes);
+int  sfa_track_job_create_alternate(sfa_ctx *ctx, const sfa_track_params *p, const sfa_track_fill_params *fill, const sfa_track_alt_params *alt,
+                                    sfa_track_job **job);
+/* sequence_start of start_jets 0 .. n-1, the second key word of their draws (0 until set); copied before the call returns. */
+int  sfa_track_job_set_sequence_starts(sfa_track_job *job, const unsigned *sequence_start);
+/* Start_jet s of the last run: sfa_track_job_download_fused gives the last round's flow, occlusions, energy, bound and iterations, with slot = the chosen
+ * POSITION; this call gives origin [gh][gw]: the slot the chosen hypothesis was born in, | 0x80 if it arrived as a proposal (255: no node), and per round
+ * [rounds]: energy, bound, iterations, node count and accepted proposals.  NULL skips an output.  Waits. */
+int  sfa_track_job_download_alternation(sfa_track_job *job, int s, unsigned char *origin, double *energy, double *bound, int *iters, int *nodes, int *accepted);
 /* ---- resident pair jobs: the two-frame refinement of pairs that stay in GPU memory (csrc/two_frame.hip) -------------------------------
  * A pair job owns the planes of n pairs of one size (24 per pair: those of sfa_variational_2frame without its 24-plane derivative stack) and one solver
  * workspace, across any number of uploads and runs.  sfa_pair_job_run enqueues variational()'s launch sequence (variational.c:19-82) for all n pairs on the

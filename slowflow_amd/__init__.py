@@ -103,7 +103,7 @@ def jet_source(sw, sh, stride=None, crop=None, rescale=None, w=None):
 
 class FuseParams(C.Structure):
     """sfa_fuse_params: dense_tracking's fusion keys (setDefault, dense_tracking.cpp:136-152) in the C types the reference reads them in"""
-    _fields_ = [("acc_beta", C.c_double), ("acc_spatial_occ", C.c_double), ("traj_sim_method", C.c_int), ("traj_sim_thres", C.c_double),
+    _fields_ = [("acc_beta", C.c_double), ("acc_spatial_occ", C.c_double), ("traj_sim_method", C.c_int), ("pin_first", C.c_int), ("traj_sim_thres", C.c_double),
                 ("trws_eps", C.c_double), ("trws_max_iter", C.c_int), ("skip", C.c_int)]
 
 
@@ -115,6 +115,66 @@ def fuse_params(**kw):
         assert hasattr(p, k), k
         setattr(p, k, v)
     return p
+
+
+class NeighParams(C.Structure):
+    """sfa_neigh_params: the keys of dense_tracking's neighbour proposals (setDefault, dense_tracking.cpp:136-159) and the seed"""
+    _fields_ = [("traj_sim_thres", C.c_double), ("traj_sim_method", C.c_int), ("neigh_hyp", C.c_int), ("neigh_hyp_radius", C.c_float),
+                ("neigh_skip1", C.c_int), ("neigh_skip2", C.c_int), ("hyp_neigh_tryouts", C.c_int), ("seed", C.c_uint), ("slots", C.c_int), ("perturb_keep", C.c_int)]
+
+
+def neigh_params(**kw):
+    """sfa_neigh_params_default (setDefault's values, seed 0, slots 4, perturb_keep -1 = not set) with the given fields replaced"""
+    p = NeighParams()
+    lib().sfa_neigh_params_default(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+class TrackAltParams(C.Structure):
+    """sfa_track_alt_params: the rounds (acc_alternate) and the proposals' keys of a track job that alternates"""
+    _fields_ = [("rounds", C.c_int), ("neigh", NeighParams)]
+
+
+def track_alt_params(rounds=5, **kw):
+    """sfa_track_alt_params_default with `rounds` and the given fields of its NeighParams replaced (slots and traj_sim_* come from the job)"""
+    a = TrackAltParams()
+    lib().sfa_track_alt_params_default(C.byref(a))
+    a.rounds = int(rounds)
+    for k, v in kw.items():
+        assert hasattr(a.neigh, k), k
+        setattr(a.neigh, k, v)
+    return a
+
+
+class HypLists(C.Structure):
+    """sfa_hyp_lists: the five host planes of n segments' hypothesis lists of 16 positions"""
+    _fields_ = [("U", C.c_void_p), ("V", C.c_void_p), ("energy", C.c_void_p), ("occ_bits", C.c_void_p), ("origin", C.c_void_p)]
+
+
+LIST_POSITIONS = 16
+_LIST_TYPES = (("U", np.float64), ("V", np.float64), ("energy", np.float64), ("occ", np.uint64), ("origin", np.uint8))
+
+
+def hyp_lists(U, V, energy, occ_bits, origin=None):
+    """K <= 16 slots -> a hypothesis list of 16 positions (a dict U, V (n, 16, Jets, gh, gw), energy, occ, origin (n, 16, gh, gw)): slot k at
+    position k, origin k unless given, every further position absent (+Inf, zeros)"""
+    n, K, J, gh, gw = U.shape
+    assert K <= LIST_POSITIONS
+    out = dict(U=np.zeros((n, LIST_POSITIONS, J, gh, gw)), V=np.zeros((n, LIST_POSITIONS, J, gh, gw)), energy=np.full((n, LIST_POSITIONS, gh, gw), np.inf),
+               occ=np.zeros((n, LIST_POSITIONS, gh, gw), np.uint64), origin=np.zeros((n, LIST_POSITIONS, gh, gw), np.uint8))
+    out["U"][:, :K], out["V"][:, :K], out["energy"][:, :K], out["occ"][:, :K] = U, V, energy, occ_bits
+    out["origin"][:, :K] = np.arange(K, dtype=np.uint8).reshape(1, K, 1, 1) if origin is None else origin
+    return out
+
+
+def philox4x32_10(ctr, key):
+    """sfa_philox4x32_10 on the host (no GPU): counter (4 words), key (2 words) -> 4 words"""
+    c, k, o = (C.c_uint * 4)(*ctr), (C.c_uint * 2)(*key), (C.c_uint * 4)()
+    lib().sfa_philox4x32_10(c, k, o)
+    return list(o)
 
 
 class EpicParams(C.Structure):
@@ -200,7 +260,7 @@ def track_job_bytes(params, fill=None):
 
 EXPORTS = [
     "sfa_device_count", "sfa_ctx_create", "sfa_ctx_destroy", "sfa_last_error", "sfa_ctx_sync", "sfa_params_default",
-    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_ctx_set_epic_search", "sfa_epic_nn_search_info", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_epic_batch", "sfa_epic_saliency_batch", "sfa_epic_batch_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "sfa_consistent_regions", "sfa_fill_samples", "sfa_fill_matches", "sfa_fill_trajectories", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
+    "sfa_variational", "sfa_variational_2frame", "sfa_variational_2frame_batch", "sfa_epic_nearest_seeds_batch", "sfa_epic_nn_stage_ms", "sfa_ctx_set_epic_search", "sfa_epic_nn_search_info", "sfa_epic_interpolate_batch", "sfa_epic_fit_stage_ms", "sfa_epic_batch", "sfa_epic_saliency_batch", "sfa_epic_batch_stage_ms", "sfa_params_2frame_default", "sfa_pair_job_create", "sfa_pair_job_destroy", "sfa_pair_job_upload", "sfa_pair_job_run", "sfa_pair_job_download", "sfa_pair_job_download_system", "sfa_flow_magnitude_quantile", "sfa_quantile_ranks", "sfa_flow_magnitude_quantiles_device", "sfa_accumulate_consistent", "sfa_accumulate_consistent_scaled", "sfa_jet_source_default", "sfa_jet_flow_resample", "sfa_jet_occlusion_decode", "sfa_hypothesis_energies_scaled", "sfa_accumulate_grid", "sfa_energy_params_default", "sfa_hypothesis_energies", "sfa_hypothesis_energies_ex", "sfa_dt_smoothness_weight", "sfa_fuse_params_default", "sfa_fuse_hypotheses", "sfa_neigh_params_default", "sfa_prune_hypotheses", "sfa_neighbour_proposals", "sfa_rescore_proposals", "sfa_philox4x32_10", "sfa_philox4x32_10_device", "sfa_consistent_regions", "sfa_fill_samples", "sfa_fill_matches", "sfa_fill_trajectories", "variational", "sfa_compute_one_level", "sfa_normalize", "sfa_sor_coupled", "sfa_sor_red_black", "sor_coupled",
     "sfa_image_warp", "sfa_derivative_stack", "sfa_convolve", "sfa_dpsis_weight", "sfa_smoothness", "sfa_sub_laplacian",
     "sfa_add_data_and_match", "sfa_occlusion_costs", "sfa_grid_cut", "sfa_grid_cut_batch", "sfa_gaussian_blur", "sfa_resize_linear", "sfa_resize_linear_fx", "sfa_gaussian_presmooth", "sfa_pyramid_sizes",
     "sfa_pyramid_down", "sfa_resize_flow", "sfa_job_download_level_frame",
@@ -212,6 +272,7 @@ EXPORTS = [
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
     "sfa_track_params_default", "sfa_track_job_bytes", "sfa_track_job_create", "sfa_track_job_destroy", "sfa_track_job_upload_flows", "sfa_track_job_upload_frames", "sfa_track_job_upload_flows_device", "sfa_track_job_upload_frames_device", "sfa_track_job_run", "sfa_track_job_download_rate", "sfa_track_job_download_fused", "sfa_track_job_download_best", "sfa_ctx_free_bytes", "sfa_track_job_download_device", "sfa_track_job_stage_ms", "sfa_track_job_upload_occlusions_device", "sfa_track_job_download_rate_device", "sfa_track_job_download_best_device",
     "sfa_track_fill_params_default", "sfa_track_job_bytes_fill", "sfa_track_job_create_fill", "sfa_track_job_upload_fill", "sfa_track_job_upload_fill_device", "sfa_track_job_download_fill", "sfa_track_job_fill_ms", "sfa_track_job_fill_info",
+    "sfa_track_alt_params_default", "sfa_track_job_bytes_alternate", "sfa_track_job_create_alternate", "sfa_track_job_set_sequence_starts", "sfa_track_job_download_alternation",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
 
@@ -909,6 +970,100 @@ class Context:
             out["stage_ms"] = ms
         return out
 
+    @staticmethod
+    def _lists(d, shape=None):
+        """a list dict (hyp_lists) as contiguous arrays of the C types and its sfa_hyp_lists; shape: make an empty one of (n, Jets, gh, gw)"""
+        if shape is not None:
+            n, J, gh, gw = shape
+            d = dict(U=np.zeros((n, LIST_POSITIONS, J, gh, gw)), V=np.zeros((n, LIST_POSITIONS, J, gh, gw)), energy=np.zeros((n, LIST_POSITIONS, gh, gw)),
+                     occ=np.zeros((n, LIST_POSITIONS, gh, gw), np.uint64), origin=np.zeros((n, LIST_POSITIONS, gh, gw), np.uint8))
+        d = {k: np.ascontiguousarray(d[k], dtype=t) for k, t in _LIST_TYPES}
+        n, P, J, gh, gw = d["U"].shape
+        assert P == LIST_POSITIONS and d["V"].shape == d["U"].shape, "U, V: (n, 16, Jets, gh, gw)"
+        assert all(d[k].shape == (n, P, gh, gw) for k in ("energy", "occ", "origin")), "energy, occ, origin: (n, 16, gh, gw)"
+        return d, HypLists(*[d[k].ctypes.data for k, _ in _LIST_TYPES])
+
+    def prune_hypotheses(self, lists, selected, perturb_keep, stage_ms=False):
+        """the prune of the alternation's rounds p > 0 (sfa_prune_hypotheses).  lists: a dict as hyp_lists makes it; selected int32 (n, gh, gw): the
+        position the last fusion chose, -1 none.  Returns the pruned lists: the selection at position 0, then the best by (float) energy while the
+        list holds at most perturb_keep entries; with stage_ms also the 2 kernels' ms."""
+        d, hin = self._lists(lists)
+        n, _, J, gh, gw = d["U"].shape
+        out, hout = self._lists(None, (n, J, gh, gw))
+        selected = np.ascontiguousarray(selected, dtype=np.int32)
+        assert selected.shape == (n, gh, gw), "selected: (n, gh, gw)"
+        L = lib()
+        L.sfa_prune_hypotheses.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.POINTER(HypLists), C.POINTER(HypLists), C.c_void_p]
+        ms = np.zeros(2, np.float32)
+        self._ck(L.sfa_prune_hypotheses(self.h, n, J, gw, gh, int(perturb_keep), selected.ctypes.data, C.byref(hin), C.byref(hout),
+                                        ms.ctypes.data if stage_ms else None), "sfa_prune_hypotheses")
+        return (out, ms) if stage_ms else out
+
+    def neighbour_proposals(self, p, lists, round, sequence_start, consistent=None, stage_ms=False):
+        """the neighbour proposals of one round (sfa_neighbour_proposals).  p: NeighParams; lists: a dict as hyp_lists makes it; sequence_start: one
+        uint32 per segment; consistent uint8 (n, gh, gw), needed in round 0.  Returns (lists, src_pixel, src_position, accepted): the lists with the
+        accepted proposals at the lowest absent positions; int32 / uint8 (n, 16, gh, gw): the source pixel y * gw + x and position of a position
+        filled in this call, -1 / 0 elsewhere; int32 (n,): their count.  With stage_ms a fifth value: the 3 kernels' ms."""
+        d, hin = self._lists(lists)
+        n, P, J, gh, gw = d["U"].shape
+        out, hout = self._lists(None, (n, J, gh, gw))
+        seq = np.ascontiguousarray(sequence_start, dtype=np.uint32)
+        assert seq.shape == (n,), "sequence_start: one per segment"
+        if consistent is not None:
+            consistent = np.ascontiguousarray(consistent, dtype=np.uint8)
+            assert consistent.shape == (n, gh, gw), "consistent: (n, gh, gw)"
+        src_pixel, src_pos, acc = np.zeros((n, P, gh, gw), np.int32), np.zeros((n, P, gh, gw), np.uint8), np.zeros(n, np.int32)
+        L = lib()
+        L.sfa_neighbour_proposals.argtypes = [C.c_void_p, C.POINTER(NeighParams)] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.POINTER(HypLists)] * 2 + [C.c_void_p] * 4
+        ms = np.zeros(3, np.float32)
+        self._ck(L.sfa_neighbour_proposals(self.h, C.byref(p), n, J, gw, gh, int(round), seq.ctypes.data, None if consistent is None else consistent.ctypes.data,
+                                           C.byref(hin), C.byref(hout), src_pixel.ctypes.data, src_pos.ctypes.data, acc.ctypes.data,
+                                           ms.ctypes.data if stage_ms else None), "sfa_neighbour_proposals")
+        return (out, src_pixel, src_pos, acc, ms) if stage_ms else (out, src_pixel, src_pos, acc)
+
+    def rescore_proposals(self, p, lists, src_pixel, frames, w, flows=None, slot_weight=None, stage_ms=False):
+        """the accepted proposals of a round scored at their new place (sfa_rescore_proposals).  p: EnergyParams (its weight is ignored); lists,
+        src_pixel: as neighbour_proposals returned them; frames fp32 (n, Jets + 1, 3, h, stride); flows: None or (fwd_u, fwd_v, bwd_u, bwd_v), fp32
+        (n, Jets, h, stride) each; slot_weight: up to 16 floats, weight_jet_estimation of the rate each slot belongs to (default 0).  Returns the
+        lists with energy and occ replaced where src_pixel >= 0; with stage_ms also the scoring launches' ms."""
+        d, hl = self._lists(lists)
+        d = {k: v.copy() for k, v in d.items()}
+        hl = HypLists(*[d[k].ctypes.data for k, _ in _LIST_TYPES])
+        n, P, J, gh, gw = d["U"].shape
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        assert frames.ndim == 5 and frames.shape[:3] == (n, J + 1, 3), "frames are (n, Jets + 1, 3, h, stride)"
+        h, stride = frames.shape[3:]
+        assert accumulate_grid(w, h, p.skip) == (gw, gh), "the lists are not on the grid of (w, h, p.skip)"
+        src_pixel = np.ascontiguousarray(src_pixel, dtype=np.int32)
+        assert src_pixel.shape == (n, P, gh, gw), "src_pixel: (n, 16, gh, gw)"
+        fp = (_f * (n * (J + 1)))(*[fptr(frames[s, f]) for s in range(n) for f in range(J + 1)])
+        if flows is not None:
+            flows = [np.ascontiguousarray(a, dtype=np.float32) for a in flows]
+            for a in flows:
+                assert a.shape == (n, J, h, stride), "flows are (n, Jets, h, stride)"
+            fl = [(_f * (n * J))(*[fptr(a[s, t]) for s in range(n) for t in range(J)]) for a in flows]
+        else:
+            fl = [None] * 4
+        wt = (C.c_float * LIST_POSITIONS)(*([float(v) for v in slot_weight] if slot_weight is not None else []))
+        L = lib()
+        L.sfa_rescore_proposals.argtypes = [C.c_void_p, C.POINTER(EnergyParams)] + [C.c_int] * 5 + [C.POINTER(_f)] * 5 + [C.POINTER(C.c_float), C.c_void_p,
+                                                                                                                       C.POINTER(HypLists), C.c_void_p]
+        ms = np.zeros(1, np.float32)
+        self._ck(L.sfa_rescore_proposals(self.h, C.byref(p), n, J, int(w), h, stride, fp, fl[0], fl[1], fl[2], fl[3], wt, src_pixel.ctypes.data, C.byref(hl),
+                                         ms.ctypes.data if stage_ms else None), "sfa_rescore_proposals")
+        return (d, float(ms[0])) if stage_ms else d
+
+    def philox4x32_10(self, ctr, key):
+        """Philox4x32-10 through the device function the proposals' kernel calls: ctr uint32 (n, 4), key uint32 (n, 2) -> uint32 (n, 4)"""
+        ctr, key = np.ascontiguousarray(ctr, dtype=np.uint32), np.ascontiguousarray(key, dtype=np.uint32)
+        n = ctr.shape[0]
+        assert ctr.shape == (n, 4) and key.shape == (n, 2)
+        out = np.zeros((n, 4), np.uint32)
+        L = lib()
+        L.sfa_philox4x32_10_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        self._ck(L.sfa_philox4x32_10_device(self.h, n, ctr.ctypes.data, key.ctypes.data, out.ctypes.data), "sfa_philox4x32_10_device")
+        return out
+
     def consistent_regions(self, tracked, full, min_size=100):
         """dense_tracking's removeSmallSegments on (tracked == r_Jets) (sfa_consistent_regions) for n maps in one call.  tracked: int32 (n, h, w);
         full: one int per map, its r_Jets.  Returns (mask, kept): uint8 (n, h, w), 1 where tracked == full and the pixel's 4-connected component of
@@ -1294,9 +1449,12 @@ class TrackJob:
     forms every rate's EpicFlow fill-in hypothesis (upload_fill, download_fill) and fuses 2 K slots, slot 2 r + 1 the fill-in of rate r; its run() waits
     where the fill-in reads its counts."""
 
-    def __init__(self, ctx, params, fill=None):
+    def __init__(self, ctx, params, fill=None, alt=None):
+        """alt: a TrackAltParams makes it a job that alternates (sfa_track_job_create_alternate): run() does alt.rounds rounds of prune, proposals,
+        rescoring and fusion in place of the one fusion; set_sequence_starts, download_alternation"""
         self.ctx, self.params = ctx, TrackParams.from_buffer_copy(params)
         self.fill = TrackFillParams.from_buffer_copy(fill) if fill is not None else None
+        self.alt = TrackAltParams.from_buffer_copy(alt) if alt is not None else None
         self.n, self.K, self.Jets, self.w, self.h = params.n, params.K, params.Jets, params.w, params.h
         self.h_ = C.c_void_p()
         L = lib()
@@ -1312,12 +1470,35 @@ class TrackJob:
         L.sfa_track_job_upload_fill.argtypes = [C.c_void_p, C.c_int, _f, C.c_int, _f]
         L.sfa_track_job_download_fill.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.sfa_track_job_fill_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        if self.fill is None:
+        L.sfa_track_job_create_alternate.argtypes = [C.c_void_p, C.POINTER(TrackParams), C.POINTER(TrackFillParams), C.POINTER(TrackAltParams),
+                                                     C.POINTER(C.c_void_p)]
+        L.sfa_track_job_set_sequence_starts.argtypes = [C.c_void_p, C.c_void_p]
+        L.sfa_track_job_download_alternation.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        if self.alt is not None:
+            ctx._ck(L.sfa_track_job_create_alternate(ctx.h, C.byref(self.params), C.byref(self.fill) if self.fill is not None else None, C.byref(self.alt),
+                                                     C.byref(self.h_)), "sfa_track_job_create_alternate")
+        elif self.fill is None:
             ctx._ck(L.sfa_track_job_create(ctx.h, C.byref(self.params), C.byref(self.h_)), "sfa_track_job_create")
         else:
             ctx._ck(L.sfa_track_job_create_fill(ctx.h, C.byref(self.params), C.byref(self.fill), C.byref(self.h_)), "sfa_track_job_create_fill")
         self.gw, self.gh = accumulate_grid(self.w, self.h, params.skip)
         ctx._children.add(self)
+
+    def set_sequence_starts(self, sequence_start):
+        """a job that alternates: one uint32 per start_jet of the job, the second key word of its draws"""
+        seq = np.zeros(self.n, np.uint32)
+        seq[:len(sequence_start)] = sequence_start
+        self.ctx._ck(lib().sfa_track_job_set_sequence_starts(self.h_, seq.ctypes.data), "sfa_track_job_set_sequence_starts")
+
+    def download_alternation(self, s):
+        """a job that alternates: origin uint8 (gh, gw) of the chosen hypotheses (slot it was born in, | 0x80 a proposal, 255 none) and per round
+        energy, bound float64, iters, nodes, accepted int32 (rounds,)"""
+        R = self.alt.rounds
+        out = dict(origin=np.zeros((self.gh, self.gw), np.uint8), energy=np.zeros(R), bound=np.zeros(R), iters=np.zeros(R, np.int32),
+                   nodes=np.zeros(R, np.int32), accepted=np.zeros(R, np.int32))
+        self.ctx._ck(lib().sfa_track_job_download_alternation(self.h_, int(s), *[out[k].ctypes.data for k in ("origin", "energy", "bound", "iters", "nodes",
+                                                                                                               "accepted")]), "sfa_track_job_download_alternation")
+        return out
 
     def upload_flows(self, s, r, fwd_u, fwd_v, bwd_u, bwd_v, occ=None):
         """rate r of segment s: fp32 (r_Jets[r], sh, stride) arrays as params.source[r] describes them; occ: the raw uint8 occlusion images of that

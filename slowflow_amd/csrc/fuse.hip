@@ -18,7 +18,7 @@
 // iteration at K 2 / 4 / 8 (one workgroup, 1 458 barrier steps per iteration); 16 segments side by side take 30 / 39 / 71 ms per iteration.  The pairwise
 // kernel takes 0.05 / 0.18 / 0.68 ms at n = 1, Jets 16 (under 1 % of the call), so the per-edge shape with the labels in registers was not built.  A
 // cross-workgroup pipeline of the diagonals, like sor_chain.hip's, is the step this measurement points to.
-#include "sfa_device.h"
+#include "hyp_device.h"
 
 #pragma clang fp contract(off)
 
@@ -34,38 +34,9 @@ struct FuseDims {
     int n, K, J, gw, gh, gpl, w, h, incr, start;
 };
 
-// +Inf marks "no hypothesis"; a NaN energy is absent too, as it is for k_track_best's `e < be` (track.hip): the reference's std::sort on a NaN score is
-// undefined, so no parity is lost
-__device__ __forceinline__ bool present(double e) { return e < __longlong_as_double(0x7ff0000000000000ll); }
-
-// hypothesis::distance (utils/hypothesis.cpp:223-285) of two hypotheses after adaptFPS (startF 0, endF Jets: first 0, length Jets, prev_flow (0, 0)).
-// a, b: the first of Jets doubles `step` apart.  ACC: sum sqrt(dx^2 + dy^2) / l; ADJ: the adjacent-step form, / length.  x - 0.0 is x, so the
-// subtraction of prev_flow is left out.
-__device__ double traj_distance(const double *__restrict__ ua, const double *__restrict__ va, const double *__restrict__ ub, const double *__restrict__ vb,
-                                size_t step, int J, int method) {
-    double sum = 0;
-    double pua = 0, pva = 0, pub = 0, pvb = 0;
-    for (int f = 0; f < J; f++) {
-        const double a_u = ua[f * step], a_v = va[f * step], b_u = ub[f * step], b_v = vb[f * step];
-        double xsq, ysq;
-        if (method == 1) {                                                      // ACC
-            ysq = a_v - b_v;
-            xsq = a_u - b_u;
-            sum += sqrt(xsq * xsq + ysq * ysq) / (f + 1);
-        } else {                                                                // ADJ; flow_fm1 = (0, 0) at f == first
-            ysq = ((a_v - pva) - (b_v - pvb));
-            xsq = ((a_u - pua) - (b_u - pub));
-            sum += sqrt(xsq * xsq + ysq * ysq);
-            pua = a_u; pva = a_v; pub = b_u; pvb = b_v;
-        }
-    }
-    if (method != 1) sum = sum / J;
-    return sum;
-}
-
 // labels: lab[(s, p)][i] = slot of label i, nl = label count, theta[(s, p)][i] = its energy (the unary term e_mex[h], :1680-1683)
 __global__ void __launch_bounds__(kFuThreads) k_fuse_labels(const double *__restrict__ U, const double *__restrict__ V, const double *__restrict__ energy,
-                                                            FuseDims d, int method, double thres, unsigned char *__restrict__ nl,
+                                                            FuseDims d, int method, double thres, int pin, unsigned char *__restrict__ nl,
                                                             unsigned char *__restrict__ lab, double *__restrict__ theta) {
     const int p = blockIdx.x * kFuThreads + threadIdx.x;
     if (p >= d.gpl) return;
@@ -75,12 +46,15 @@ __global__ void __launch_bounds__(kFuThreads) k_fuse_labels(const double *__rest
     int order[kFuMaxK];
     float key[kFuMaxK];
     int m = 0;
-    for (int k = 0; k < d.K; k++) {
+    // pin: slot 0, where present, is the first label and the sort covers the others (:1601-1602); without it first = 0 and the code is what it was
+    const int first = pin && present(energy[(size_t)s * d.K * d.gpl + p]) ? 1 : 0;
+    if (first) { key[0] = 0; order[0] = 0; m = 1; }
+    for (int k = first; k < d.K; k++) {
         const double e = energy[((size_t)s * d.K + k) * d.gpl + p];
         if (!present(e)) continue;
         const float f = (float)e;
         int j = m;
-        while (j > 0 && f < key[j - 1]) { key[j] = key[j - 1]; order[j] = order[j - 1]; j--; }
+        while (j > first && f < key[j - 1]) { key[j] = key[j - 1]; order[j] = order[j - 1]; j--; }
         key[j] = f;
         order[j] = k;
         m++;
@@ -378,7 +352,7 @@ int fuse_device(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, 
     auto mark = [&](int i) { return ev ? hipEventRecord(ev[i], ctx->stream) : hipSuccess; };
     const dim3 pix((unsigned)((gpl + kFuThreads - 1) / kFuThreads), (unsigned)n);
     SFA_HIP(ctx, mark(0));
-    hipLaunchKernelGGL(k_fuse_labels, pix, dim3(kFuThreads), 0, ctx->stream, f.U, f.V, f.energy, d, p->traj_sim_method, p->traj_sim_thres, f.nl, f.lab, f.theta);
+    hipLaunchKernelGGL(k_fuse_labels, pix, dim3(kFuThreads), 0, ctx->stream, f.U, f.V, f.energy, d, p->traj_sim_method, p->traj_sim_thres, p->pin_first != 0, f.nl, f.lab, f.theta);
     SFA_HIP(ctx, hipGetLastError());
     SFA_HIP(ctx, mark(1));
     hipLaunchKernelGGL(k_fuse_pairwise, dim3((unsigned)((gpl * KK + kFuThreads - 1) / kFuThreads), (unsigned)(2 * n)), dim3(kFuThreads), 0, ctx->stream, f.U, f.V,

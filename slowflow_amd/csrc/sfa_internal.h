@@ -258,6 +258,28 @@ struct FuseWork {
 // zeroes the messages and labellings of the n segments, then k_fuse_labels, k_fuse_pairwise, k_trws, k_fuse_output.  ev: null or 5 events recorded around the four
 int fuse_device(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, int w, int h, int gw, int gh, const FuseWork &f, hipEvent_t *ev);
 
+// ---- the alternation's steps at device level (neigh.hip), in the same form.  A list plane set: U, V [n][16][J][gpl], energy, occ, origin [n][16][gpl]
+struct NeighPlanes { double *U, *V, *energy; unsigned long long *occ; unsigned char *origin; };
+// scratch: flags, srcpos [n][gpl], total [n][2], map [n][16][gpl]
+struct NeighWork { unsigned char *flags, *srcpos; int *total; int *map; };
+// what the proposals' entry point and a job refuse alike, by the key's name
+int neigh_check(sfa_ctx *ctx, const char *fn, const sfa_neigh_params *p, int gw, int gh, int round);
+// k_neigh_prune, k_neigh_gather: in -> out by sel [n][gpl]; map: [n][16][gpl] scratch.  ev: null, or 3 (the proposals: 4) events recorded around the kernels
+int neigh_prune_device(sfa_ctx *ctx, int n, int Jets, int gw, int gh, int keep, const int *sel, const NeighPlanes &in, const NeighPlanes &out, int *map,
+                       hipEvent_t *ev);
+// k_neigh_flags, k_neigh_propose, k_neigh_gather: in -> out; wk.map is left as the propose kernel wrote it (bit 30: accepted in this call)
+int neigh_propose_device(sfa_ctx *ctx, const sfa_neigh_params *p, int n, int Jets, int gw, int gh, int round, const unsigned *seq_start,
+                         const unsigned char *consistent, const NeighPlanes &in, const NeighPlanes &out, const NeighWork &wk,
+                         hipEvent_t *ev);
+
+// the weight a proposal's energy ends with, by the slot it was born in
+struct NeighWeights { float w[16]; };
+// The accepted proposals of a round scored at their new place: per segment and position of todo [n][16] (host), energies_device on the list's flow planes
+// (plan: r_Jets = Jets, weight 0; tracked [n][16][gpl]: Jets where the position was filled in this round) into E, O [gpl], then k_neigh_rescored into the
+// list's energy and occ.  rec: [n][J + 1][pl] records; fwd, bwd: [n][J] planes of pairs or null; wk: the scratch of ONE segment
+int neigh_rescore_device(sfa_ctx *ctx, const EnergyPlan &plan, int n, const int *tracked, const unsigned char *todo, const void *rec, bool identity, const void *fwd,
+                         const void *bwd, const EnergyWork &wk, double *E, unsigned long long *O, const NeighWeights &wt, const NeighPlanes &lists);
+
 // ---- the steps around dense_tracking's EpicFlow fill-in at device level (fill.hip), in the same form: device pointers in, launches on the context's
 // stream out; no allocation, no copy, no wait.  The sfa_consistent_regions / sfa_fill_matches / sfa_fill_trajectories entry points wrap them -------------
 // tracked: [n][h][w], full: [n] (device); scratch T, P, S: [n][h][w] ints each; mask: [n][h][w] bytes, kept: [n]

@@ -167,6 +167,7 @@ static int track_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, 
         if (p->fuse.traj_sim_method != 0 && p->fuse.traj_sim_method != 1)
             REFUSE("%s: fuse.traj_sim_method %d (0 ADJ, 1 ACC; 2 FINAL reads flow_y[Jets], past the array)", fn, p->fuse.traj_sim_method);
         if (p->fuse.trws_max_iter < 1) REFUSE("%s: fuse.trws_max_iter %d < 1", fn, p->fuse.trws_max_iter);
+        if (p->fuse.pin_first != 0) REFUSE("%s: fuse.pin_first %d: the job's one fusion sorts every slot (call sfa_fuse_params_default first)", fn, p->fuse.pin_first);
     }
     if (sfa_accumulate_grid(p->w, p->h, p->skip, gw, gh) != SFA_OK) REFUSE("%s: skip: %s", fn, sfa_last_error(nullptr));
     if (((size_t)*gw * *gh * p->K * p->K + kTrThreads - 1) / kTrThreads > 0x7fffffffull) REFUSE("%s: grid too large", fn);
@@ -187,7 +188,7 @@ static int track_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, 
 
 // the planes in TrackPlanes' order, counted in elements; fill, fg: null for a plain job
 static void track_layout(const sfa_track_params &p, int gw, int gh, const bool *identity, int NN, const sfa_track_fill_params *fill, const FillGeo *fg,
-                         TrackPlanes *out) {
+                         const sfa_track_alt_params *alt, TrackPlanes *out) {
     TrackPlanes &a = *out;
     a = TrackPlanes{};                                                          // a plane the job does not have stays at offset 0
     PlaneCursor c;
@@ -218,6 +219,7 @@ static void track_layout(const sfa_track_params &p, int gw, int gh, const bool *
         c.take(a.seg_energy, n); c.take(a.seg_bound, n); c.take(a.seg_iters, n);
     }
     if (fill) fill_layout(c, p, gw, gh, *fill, *fg, &a);
+    if (alt) alt_layout(c, p, gw, gh, *alt, &a);
     a.total = c.top;
 }
 
@@ -254,7 +256,8 @@ int sfa::copy_rows_on(sfa_ctx *ctx, void *dst, size_t dpitch, const void *src, s
 int sfa::download(sfa_ctx *ctx, void *dst, const void *src, size_t bytes) { return dst ? copy_on(ctx, dst, src, bytes, hipMemcpyDeviceToHost) : (int)SFA_OK; }
 
 // with_fill: the call is a fill job's, and a null fill is refused under its name
-static int track_bytes(const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, size_t *bytes) {
+int sfa::track_bytes(const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, const sfa_track_alt_params *alt, bool with_alt,
+                     size_t *bytes) {
     sfa_ctx *ctx = nullptr;
     if (!bytes) REFUSE("%s: bytes is null", fn);
     int gw, gh;
@@ -263,16 +266,20 @@ static int track_bytes(const char *fn, const sfa_track_params *p, const sfa_trac
     SFA_TRY(track_check(ctx, fn, p, &gw, &gh, identity, plan));
     FillGeo fg;
     if (with_fill) SFA_TRY(fill_check(ctx, fn, p, fill, gw, gh, &fg));
+    if (with_alt) SFA_TRY(alt_check(ctx, fn, p, alt, with_fill, gw, gh, nullptr));
     TrackPlanes at;
-    track_layout(*p, gw, gh, identity, plan[0].NN, with_fill ? fill : nullptr, &fg, &at);
+    track_layout(*p, gw, gh, identity, plan[0].NN, with_fill ? fill : nullptr, &fg, with_alt ? alt : nullptr, &at);
     *bytes = at.total;
     return SFA_OK;
 }
 
-int sfa_track_job_bytes(const sfa_track_params *p, size_t *bytes) { return track_bytes(__func__, p, nullptr, false, bytes); }
-int sfa_track_job_bytes_fill(const sfa_track_params *p, const sfa_track_fill_params *fill, size_t *bytes) { return track_bytes(__func__, p, fill, true, bytes); }
+int sfa_track_job_bytes(const sfa_track_params *p, size_t *bytes) { return track_bytes(__func__, p, nullptr, false, nullptr, false, bytes); }
+int sfa_track_job_bytes_fill(const sfa_track_params *p, const sfa_track_fill_params *fill, size_t *bytes) {
+    return track_bytes(__func__, p, fill, true, nullptr, false, bytes);
+}
 
-static int track_create(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, sfa_track_job **out) {
+int sfa::track_create(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, const sfa_track_alt_params *alt,
+                      bool with_alt, sfa_track_job **out) {
     if (!ctx || !out) REFUSE("%s: ctx or job is null", fn);
     *out = nullptr;
     sfa_track_job *j = new sfa_track_job;
@@ -284,9 +291,14 @@ static int track_create(sfa_ctx *ctx, const char *fn, const sfa_track_params *p,
         SFA_TRY(fill_check(ctx, fn, p, fill, j->gw, j->gh, &j->fill->g));
         j->fill->fp = *fill;
     }
+    if (with_alt) {
+        j->alt.reset(new TrackAlt);
+        SFA_TRY(alt_check(ctx, fn, p, alt, with_fill, j->gw, j->gh, j->alt.get()));
+    }
     j->p = *p;
     j->p.energy.skip = j->p.fuse.skip = p->skip;
-    track_layout(j->p, j->gw, j->gh, j->identity, j->plan[0].NN, with_fill ? &j->fill->fp : nullptr, with_fill ? &j->fill->g : nullptr, &j->at);
+    track_layout(j->p, j->gw, j->gh, j->identity, j->plan[0].NN, with_fill ? &j->fill->fp : nullptr, with_fill ? &j->fill->g : nullptr,
+                 with_alt ? &j->alt->ap : nullptr, &j->at);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     SFA_TRY(j->mem.alloc(ctx, j->at.total));
     SFA_TRY(zero_on(ctx, j->mem.p, j->at.total));                               // a run before an upload reads zeros, not another job's planes
@@ -297,9 +309,9 @@ static int track_create(sfa_ctx *ctx, const char *fn, const sfa_track_params *p,
     return SFA_OK;
 }
 
-int sfa_track_job_create(sfa_ctx *ctx, const sfa_track_params *p, sfa_track_job **out) { return track_create(ctx, __func__, p, nullptr, false, out); }
+int sfa_track_job_create(sfa_ctx *ctx, const sfa_track_params *p, sfa_track_job **out) { return track_create(ctx, __func__, p, nullptr, false, nullptr, false, out); }
 int sfa_track_job_create_fill(sfa_ctx *ctx, const sfa_track_params *p, const sfa_track_fill_params *fill, sfa_track_job **out) {
-    return track_create(ctx, __func__, p, fill, true, out);
+    return track_create(ctx, __func__, p, fill, true, nullptr, false, out);
 }
 
 void sfa_track_job_destroy(sfa_track_job *job) {
@@ -469,7 +481,7 @@ static int run_accumulation(sfa_track_job *job, int ns) {
     return mark(ctx, job->ev[kEvAccumulated]);
 }
 
-static EnergyWork energy_work(const sfa_track_job *job) {
+EnergyWork sfa::energy_work(const sfa_track_job *job) {
     const TrackPlanes &at = job->at;
     EnergyWork wk;
     wk.U = job->ptr(at.wU); wk.V = job->ptr(at.wV); wk.occ = job->ptr(at.wocc);
@@ -537,7 +549,7 @@ static int run_weight(sfa_track_job *job, int ns) {
     return mark(ctx, job->ev[kEvWeight]);
 }
 
-static FuseWork fuse_work(const sfa_track_job *job) {
+FuseWork sfa::fuse_work(const sfa_track_job *job) {
     const TrackPlanes &at = job->at;
     FuseWork f;
     f.U = job->ptr(at.aU); f.V = job->ptr(at.aV); f.energy = job->ptr(at.E); f.occ = job->ptr(at.O); f.weight = job->ptr(at.weight);
@@ -568,7 +580,7 @@ int sfa_track_job_run(sfa_track_job *job, int ns) {
     job->timed_fuse = false;
     if (!p.do_fuse) return SFA_OK;
     SFA_TRY(run_weight(job, ns));
-    SFA_TRY(run_fusion(job, ns));
+    SFA_TRY(job->alt ? track_run_alternation(job, ns) : run_fusion(job, ns));   // a job that alternates fuses once per round
     job->timed_fuse = true;
     return SFA_OK;
 }

@@ -56,6 +56,14 @@ struct TrackPlanes {
     Plane<float> lab_stage, sal, edges, run_cost, cost; Plane<int> full, cT, cP, cS; Plane<unsigned char> mask; Plane<int> kept, count, xs, ys, block_count;
     Plane<float> matches, fx, fy; Plane<double> inf;
     struct Fill { Plane<double> u, v; Plane<int> tracked; } fill[kTrackMaxRates];
+    // a job that alternates only (track_alt.hip): two sets of hypothesis lists of 16 positions ([n][16][J][gpl], [n][16][gpl]) that the rounds' stages
+    // read and write in turn; flags, srcpos, consistent, chosen [n][gpl]; total [n][2]; map, trk [n][16][gpl]; seq [n]; E1, O1 [gpl]; P16 [n][2][gpl][256];
+    // per round and start_jet [rounds][n]: energy, bound, iterations, nodes, accepted proposals
+    struct Alt {
+        Plane<double> U[2], V[2], energy[2]; Plane<unsigned long long> occ[2]; Plane<unsigned char> origin[2];
+        Plane<unsigned char> flags, srcpos, consistent, chosen; Plane<int> total, map, trk; Plane<unsigned> seq; Plane<double> E1; Plane<unsigned long long> O1;
+        Plane<double> P16, r_energy, r_bound; Plane<int> r_iters, r_nodes, r_accepted;
+    } alt;
     size_t total;
 };
 
@@ -82,6 +90,14 @@ struct TrackFill {
     ~TrackFill();
 };
 
+// What a job that alternates (sfa_track_job_create_alternate) holds besides the planes: its parameters with slots and the similarity keys filled in from
+// the job's, the plan that scores a proposal (r_Jets = Jets, weight 0), and which of the two list sets the last run left its result in
+struct TrackAlt {
+    sfa_track_alt_params ap{};
+    EnergyPlan plan{};
+    int cur = 0;
+};
+
 // the marks of a run, in stream order (the fusion records its five itself: fuse_device)
 enum TrackEvent { kEvStart, kEvRecords, kEvAccumulated, kEvBest, kEvFuse, kEvFuseEnd = kEvFuse + 4, kEvWeight /* before the fusion's clears */, kTrackEvents };
 
@@ -98,6 +114,7 @@ struct sfa_track_job {
     hipEvent_t ev[sfa::kTrackEvents] = {};
     bool timed = false, timed_fuse = false;
     std::unique_ptr<sfa::TrackFill> fill;       // null for a plain job
+    std::unique_ptr<sfa::TrackAlt> alt;         // null for a job that fuses once
     int slots() const { return fill ? 2 * p.K : p.K; }
     int step() const { return fill ? 2 : 1; }
     // the one place a plane's offset becomes a pointer
@@ -127,6 +144,23 @@ int copy_rows_on(sfa_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t
 // k_track_pack_frames (track.hip) with one frame: nc <= 3 channel planes of w x h in device memory, element (channel, row, column) at src + the element strides
 // -> out: [nc][h][w] packed.  How a fill job packs its Lab images and edge maps
 int pack_strided_planes(sfa_ctx *ctx, const float *src, long long s_c, long long s_row, long long s_col, int w, int h, int nc, float *out);
+
+// ---- create and bytes for every kind of job, and the scratch the stages share (track.hip)
+int track_bytes(const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, const sfa_track_alt_params *alt, bool with_alt,
+                size_t *bytes);
+int track_create(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, const sfa_track_alt_params *alt,
+                 bool with_alt, sfa_track_job **out);
+EnergyWork energy_work(const sfa_track_job *job);
+FuseWork fuse_work(const sfa_track_job *job);
+
+// ---- the alternating job's half (track_alt.hip)
+// the checks beyond the plain job's, by the key's name; out (or null): the parameters as the job uses them and the rescoring plan
+int alt_check(sfa_ctx *ctx, const char *fn, const sfa_track_params *p, const sfa_track_alt_params *alt, bool with_fill, int gw, int gh, TrackAlt *out);
+// the alternation's planes, behind every other plane
+void alt_layout(PlaneCursor &c, const sfa_track_params &p, int gw, int gh, const sfa_track_alt_params &alt, TrackPlanes *a);
+// The rounds of segments 0 .. ns-1 in place of the one fusion: lists from the slots, then per round prune (p > 0), propose, rescore, fuse -- all enqueued,
+// no host wait.  The last round's result lies where the fusion's does (slot = the chosen POSITION), its origin in alt.chosen
+int track_run_alternation(sfa_track_job *job, int ns);
 
 // ---- the fill job's half (track_fill.hip), as create, bytes and run call it
 // the checks of a fill job beyond the plain job's, by the name of the argument, and what the layout needs of it

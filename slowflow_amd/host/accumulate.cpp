@@ -35,7 +35,8 @@
 // sfa_track_job_create_fill, in the same groups of acc_gpu_batch: the Lab image of the 8-bit frame 0 and the edge map go up with each start_jet, and
 // the fill-in of a whole group is one launch sequence per rate.  acc_skip_pixel 0 only; at most 8 rates.
 //
-// Out of scope (FLANN, GSL, OpenCV are not in this tree): the neighbour proposals.
+// With -alternate (implies -fill) the job alternates (sfa_track_job_create_alternate): acc_alternate rounds of prune, neighbour proposals, rescoring and
+// fusion as INTEGRATION.md 4d defines them (FLANN and GSL are not in this tree); labels hold origin slots, proposed_<sequence_start>.pgm is written.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -63,7 +64,7 @@ using std::vector;
 
 static void usage() {
     printf("usage:\n");
-    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies -fuse -fill\n");
+    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies -fuse -fill -alternate\n");
     printf("    ./accumulate -decode_occlusion [occlusion .pgm / .pbm] [mask .pgm]   (the mask this program uses: median 3x3, 255 - x; 0 = occluded)\n");
     printf("\n");
     printf("Runs dense_tracking's first stage only: consistent accumulation of the jets (accumulateConsistentBatches).  cfg keys read: jet_estimation\n");
@@ -95,6 +96,13 @@ static void usage() {
     printf("more than 8 rates, acc_epic_interpolation 0.  The neighbour proposals are not run.  acc_gpu_epic_search (0): 1 runs the fill-in's graph searches in\n");
     printf("the library's compact mode (slices of seeds in one shared workspace: the same bits, and match counts whose ns * ns table would not fit, such as\n");
     printf("acc_epic_skip 2 on a full frame, stay on the GPU); any other value exits with status 1.\n");
+    printf("\n");
+    printf("-alternate: implies -fill, and runs acc_alternate (5) rounds of prune (to the last selection plus acc_perturb_keep), neighbour proposals, their\n");
+    printf("rescoring and the fusion in place of the one fusion (the track job that alternates; INTEGRATION.md 4d defines the rounds).  Keys: acc_perturb_keep\n");
+    printf("(no default: needed when acc_alternate > 1), acc_neigh_hyp (5), acc_neigh_hyp_radius (100), acc_neigh_skip1 (2), acc_neigh_skip2 (4),\n");
+    printf("acc_hyp_neigh_tryouts (20), seed (0, recorded in run.json; the reference takes the clock).  labels_<start>.pgm holds the slot the chosen hypothesis\n");
+    printf("was born in, the new proposed_<start>.pgm 255 where it arrived from a neighbour; run.json gains the rounds.  Refused by name with status 1:\n");
+    printf("slots + 2 acc_neigh_hyp > 16, acc_perturb_keep + 1 + 2 acc_neigh_hyp > 16, acc_neigh_skip1/2 < 1, acc_hyp_neigh_tryouts < 0, acc_neigh_hyp_radius <= 0.\n");
 }
 
 // dense_tracking.cpp:1183-1193 for a file of the flows' size: medianBlur(3) with OpenCV's border for ksize 3 (replicate; OpenCV is absent here, so this
@@ -127,6 +135,7 @@ struct Run {
     bool discard = true, use_occ = false, sintel = false;
     bool energies = false, fuse = false;     // -energies, -fuse (implies -energies)
     bool fill = false;                       // -fill (implies -fuse)
+    bool alternate = false;                  // -alternate (implies -fill): the reference's rounds of prune, neighbour proposals and fusion
     string flow_format, acc_dir;             // flow_format without its extension; <output>/accumulated/
     bool crop_flows = false, crop_frames = false;   // center.x > 0 (:1135); extent.x > 0 || extent.y > 0 (:876)
     int cx = 0, cy = 0, ex = 0, ey = 0;      // center, extent
@@ -399,7 +408,8 @@ struct Fusion {
     float nav[3], nsd[3];                    // the statistics the smoothness weight de-normalises with (img_norm_avg_* / img_norm_std_*)
     int hbit = 0;
     // t_weight, t_fuse and stage_ms exist per group of start_jets only: each of its start_jets carries the group's value
-    struct Record { unsigned seq_start; int nodes, iters, group, group_size; double energy, bound, t_weight, t_fuse; float stage_ms[4]; };
+    struct Round { double energy, bound; int iters, nodes, accepted; };
+    struct Record { unsigned seq_start; int nodes, iters, group, group_size; double energy, bound, t_weight, t_fuse; float stage_ms[4]; vector<Round> rounds; };
     vector<Record> done;
 };
 
@@ -433,12 +443,30 @@ static bool write_fused_planes(const Run &run, Fusion &fz, Fusion::Record fu, in
     return ok;
 }
 
-static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run, Fusion &fz, Fusion::Record fu, int gw, int gh) {
+static bool write_fused(sfa_ctx *ctx, sfa_track_job *job, int k, const Run &run, Fusion &fz, Fusion::Record fu, int gw, int gh, int rounds) {
     const size_t gpl = (size_t)gw * gh;
     vector<int> slot(gpl);
     vector<double> flu(gpl), flv(gpl);
     vector<unsigned char> oc(gpl);
     if (!sfa_ok(ctx, sfa_track_job_download_fused(job, k, slot.data(), flu.data(), flv.data(), oc.data(), nullptr, &fu.energy, &fu.bound, &fu.iters))) return false;
+    if (run.alternate) {
+        // the job's slot is a position of the last round's list: labels_<n>.pgm takes the slot the chosen hypothesis was born in, proposed_<n>.pgm whether it
+        // arrived from a neighbour (0 / 255)
+        const int R = rounds;
+        vector<unsigned char> origin(gpl), prop(gpl);
+        vector<double> e(R), b(R);
+        vector<int> it(R), nd(R), ac(R);
+        if (!sfa_ok(ctx, sfa_track_job_download_alternation(job, k, origin.data(), e.data(), b.data(), it.data(), nd.data(), ac.data()))) return false;
+        for (size_t i = 0; i < gpl; i++) {
+            prop[i] = slot[i] >= 0 && (origin[i] & 0x80) ? 255 : 0;
+            slot[i] = slot[i] < 0 ? -1 : (origin[i] & 0x7f);
+        }
+        for (int r = 0; r < R; r++) fu.rounds.push_back(Fusion::Round{e[r], b[r], it[r], nd[r], ac[r]});
+        if (!write_pgm8(run.acc_dir + "proposed_" + std::to_string(fu.seq_start) + ".pgm", gw, gh, prop.data(), gw)) {
+            std::cerr << "cannot write " << run.acc_dir << "proposed_" << fu.seq_start << ".pgm" << std::endl;
+            return false;
+        }
+    }
     return write_fused_planes(run, fz, fu, gw, gh, (int)run.rates * (run.fill ? 2 : 1), slot, flu, flv, oc);
 }
 
@@ -475,14 +503,32 @@ static void read_fusion(ParameterList &params, const Run &run, Fusion &fz) {
     fz.hbit = params.parameter<bool>("16bit", "0") ? 1 : 0;
 }
 
+// -alternate: acc_alternate and the proposals' keys (setDefault :153-159, read as at :626-637); seed: the reference takes the clock, here the key or 0
+static void read_alternation(ParameterList &params, sfa_track_alt_params &alt) {
+    sfa_track_alt_params_default(&alt);
+    alt.rounds = params.parameter<int>("acc_alternate", "5");
+    alt.neigh.perturb_keep = params.exists("acc_perturb_keep") ? params.parameter<int>("acc_perturb_keep") : -1;   // no default in setDefault
+    alt.neigh.neigh_hyp = params.parameter<int>("acc_neigh_hyp", "5");
+    alt.neigh.neigh_hyp_radius = (float)params.parameter<int>("acc_neigh_hyp_radius", "100");   // parameter<int> into a float (:631)
+    alt.neigh.neigh_skip1 = params.parameter<int>("acc_neigh_skip1", "2");
+    alt.neigh.neigh_skip2 = params.parameter<int>("acc_neigh_skip2", "4");
+    alt.neigh.hyp_neigh_tryouts = params.parameter<int>("acc_hyp_neigh_tryouts", "20");
+    alt.neigh.seed = (unsigned)params.parameter<int>("seed", "0");
+}
+
 // the track job of the run: B start_jets x all rates.  acc_gpu_batch given: that B or status 1; absent: the largest B <= 16 and <= todo whose job takes at most
 // half of the device memory that is free now.  fill: null, or the parameters of a job that fills in -- its bytes count the fill planes, and the half
 // that stays free is what the interpolation takes its workspace from at run time
-static sfa_track_job *create_job(ParameterList &params, sfa_ctx *ctx, sfa_track_params tp, const sfa_track_fill_params *fill, size_t todo, int &B) {
+static sfa_track_job *create_job(ParameterList &params, sfa_ctx *ctx, sfa_track_params tp, const sfa_track_fill_params *fill, const sfa_track_alt_params *alt,
+                                 size_t todo, int &B) {
     sfa_track_job *job = nullptr;
     size_t bytes = 0;
-    auto job_bytes = [&](size_t *b) { return fill ? sfa_track_job_bytes_fill(&tp, fill, b) : sfa_track_job_bytes(&tp, b); };
-    auto job_create = [&]() { return fill ? sfa_track_job_create_fill(ctx, &tp, fill, &job) : sfa_track_job_create(ctx, &tp, &job); };
+    auto job_bytes = [&](size_t *b) {
+        return alt ? sfa_track_job_bytes_alternate(&tp, fill, alt, b) : fill ? sfa_track_job_bytes_fill(&tp, fill, b) : sfa_track_job_bytes(&tp, b);
+    };
+    auto job_create = [&]() {
+        return alt ? sfa_track_job_create_alternate(ctx, &tp, fill, alt, &job) : fill ? sfa_track_job_create_fill(ctx, &tp, fill, &job) : sfa_track_job_create(ctx, &tp, &job);
+    };
     if (params.exists("acc_gpu_batch")) {
         tp.n = B = params.parameter<int>("acc_gpu_batch");
         const bool sized = job_bytes(&bytes) == SFA_OK;
@@ -532,6 +578,8 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     sfa_track_fill_params fill;
     sfa_track_fill_params_default(&fill);                                  // epic_fill_params (:652-656), removeSmallSegments' 100 (:1265)
     fill.epic_skip = params.parameter<float>("acc_epic_skip", "2");        // :651
+    sfa_track_alt_params alt;
+    read_alternation(params, alt);
     const int epic_search = run.fill ? params.parameter<int>("acc_gpu_epic_search", "0") : 0;   // 0 or 1 (refusal()): the graph searches of the fill-in, compact
     if (ctx && epic_search && !sfa_ok(ctx, sfa_ctx_set_epic_search(ctx, SFA_EPIC_SEARCH_COMPACT))) { sfa_ctx_destroy(ctx); return 1; }
     struct RateFill { unsigned seq_start; int r; int st[3]; };              // kept_pixels, matches, filled
@@ -603,7 +651,7 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                     tp.weight[r] = run.jet_weight.size() > r ? (float)run.jet_weight[r] : (float)r;   // weight_jet_estimation, vector<float> (:489-495)
                 }
                 for (size_t m = 0; m < mine.size(); m++) tp.r_Jets[segs[mine[m]].r] = segs[mine[m]].FF;
-                job = create_job(params, ctx, tp, run.fill ? &fill : nullptr, starts.size(), B);
+                job = create_job(params, ctx, tp, run.fill ? &fill : nullptr, run.alternate ? &alt : nullptr, starts.size(), B);
                 if (!job) status = 1;
             }
             for (size_t k = 0; k < mine.size() && status == 0; k++)
@@ -618,6 +666,11 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
         if (status) break;
         // ---- one run for the group
         Group grp{ng, {}, {}};
+        if (run.alternate) {                                              // the second key word of each start_jet's draws
+            vector<unsigned> seq((size_t)B, 0u);
+            for (int k = 0; k < ng; k++) seq[k] = starts[g0 + k];
+            if (!sfa_ok(ctx, sfa_track_job_set_sequence_starts(job, seq.data()))) { status = 1; break; }
+        }
         if (!sfa_ok(ctx, sfa_track_job_run(job, ng)) || !sfa_ok(ctx, sfa_track_job_stage_ms(job, grp.ms))) { status = 1; break; }
         if (run.fill && !sfa_ok(ctx, sfa_track_job_fill_ms(job, grp.fill_ms))) { status = 1; break; }
         groups.push_back(grp);
@@ -659,7 +712,7 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                 fu.t_weight = 1e-3 * grp.ms[3];
                 fu.t_fuse = 1e-3 * (grp.ms[4] + grp.ms[5] + grp.ms[6] + grp.ms[7]);
                 for (int m = 0; m < 4; m++) fu.stage_ms[m] = grp.ms[4 + m];
-                if (!write_fused(ctx, job, k, run, fz, fu, gw, gh)) status = 1;
+                if (!write_fused(ctx, job, k, run, fz, fu, gw, gh, alt.rounds)) status = 1;
             }
             vector<unsigned char> best(gpl);                              // the rate of the lowest fp32 energy, ties to the lower rate, formed on the GPU
             if (status == 0 && !sfa_ok(ctx, sfa_track_job_download_best(job, k, best.data()))) status = 1;
@@ -692,10 +745,15 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
         const sfa_fuse_params &fup = fz.fup;
         tail << ",\n  \"fused\": true, ";
         if (run.fill)
-            tail << "\"epic_fill\": true, \"fill_path\": \"track_job\", \"epic_interpolation\": true, \"neighbour_proposals\": false, \"acc_epic_skip\": "
-                 << (double)fill.epic_skip << ", \"acc_gpu_epic_search\": " << epic_search;
+            tail << "\"epic_fill\": true, \"fill_path\": \"track_job\", \"epic_interpolation\": true, \"neighbour_proposals\": " << (run.alternate ? "true" : "false")
+                 << ", \"acc_epic_skip\": " << (double)fill.epic_skip << ", \"acc_gpu_epic_search\": " << epic_search;
         else
             tail << "\"epic_interpolation\": false, \"neighbour_proposals\": false";
+        if (run.alternate)
+            tail << ", \"acc_alternate\": " << alt.rounds << ", \"acc_perturb_keep\": " << alt.neigh.perturb_keep << ", \"acc_neigh_hyp\": " << alt.neigh.neigh_hyp
+                 << ", \"acc_neigh_hyp_radius\": " << (double)alt.neigh.neigh_hyp_radius << ", \"acc_neigh_skip1\": " << alt.neigh.neigh_skip1
+                 << ", \"acc_neigh_skip2\": " << alt.neigh.neigh_skip2 << ", \"acc_hyp_neigh_tryouts\": " << alt.neigh.hyp_neigh_tryouts << ", \"seed\": "
+                 << alt.neigh.seed;
         tail << ", \"acc_beta\": " << fup.acc_beta << ", \"acc_spatial_occ\": "
              << fup.acc_spatial_occ << ", \"acc_traj_sim_method\": " << fup.traj_sim_method << ", \"acc_traj_sim_thres\": " << fup.traj_sim_thres
              << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter;
@@ -716,7 +774,15 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                  << ", \"lower_bound\": " << f.bound << ", \"iterations\": " << f.iters << ", \"group\": " << f.group << ", \"group_size\": " << f.group_size
                  << ", \"weight_s\": " << f.t_weight << ", \"fuse_call_s\": " << f.t_fuse
                  << ", \"kernels_ms\": {\"labels\": " << f.stage_ms[0] << ", \"pairwise\": " << f.stage_ms[1] << ", \"trws\": " << f.stage_ms[2]
-                 << ", \"output\": " << f.stage_ms[3] << "}}";
+                 << ", \"output\": " << f.stage_ms[3] << "}";
+            if (run.alternate) {                                          // per round: the fusion's figures and the proposals accepted before it
+                tail << ", \"rounds\": [";
+                for (size_t r = 0; r < f.rounds.size(); r++)
+                    tail << (r ? ", " : "") << "{\"round\": " << r << ", \"energy\": " << f.rounds[r].energy << ", \"lower_bound\": " << f.rounds[r].bound
+                         << ", \"iterations\": " << f.rounds[r].iters << ", \"nodes\": " << f.rounds[r].nodes << ", \"accepted_proposals\": " << f.rounds[r].accepted << "}";
+                tail << "]";
+            }
+            tail << "}";
         }
         tail << "]";
     }
@@ -726,7 +792,8 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
     if (run.fuse) tail << ", \"fuse\": " << t_fuse;
     tail << ", \"total\": " << now_s() - t0 << "}";
     const bool ok = write_run_json(run, segs, skipped, geo, width, height, tail.str());
-    if (run.fill) std::cout << "wrote the fused flows with fill-in of " << fz.done.size() << " start_jet(s) to " << run.acc_dir << std::endl;
+    if (run.alternate) std::cout << "wrote the flows of " << alt.rounds << " round(s) of proposals and fusion of " << fz.done.size() << " start_jet(s) to " << run.acc_dir << std::endl;
+    else if (run.fill) std::cout << "wrote the fused flows with fill-in of " << fz.done.size() << " start_jet(s) to " << run.acc_dir << std::endl;
     else std::cout << "wrote the energies of " << segs.size() << " segment(s) to " << run.acc_dir << std::endl;
     return ok ? 0 : 1;
 }
@@ -820,6 +887,23 @@ static int refusal(ParameterList &params, const Run &run) {
             if (refused) { std::cerr << "-fill: " << refused << " is not supported" << std::endl; return 1; }
             const int search = params.parameter<int>("acc_gpu_epic_search", "0");
             if (search != 0 && search != 1) { std::cerr << "-fill: acc_gpu_epic_search " << search << " is neither 0 (the default search) nor 1 (the compact search)" << std::endl; return 1; }
+            if (run.alternate) {                                          // the library's limits, named here before anything is read or written
+                sfa_track_alt_params alt;
+                read_alternation(params, alt);
+                const int slots = 2 * (int)run.rates, hyp = alt.neigh.neigh_hyp, keep = alt.neigh.perturb_keep;
+                std::ostringstream why;
+                if (alt.rounds < 1) why << "acc_alternate " << alt.rounds << " < 1";
+                else if (alt.rounds > 1 && !params.exists("acc_perturb_keep")) why << "acc_perturb_keep is not set (it has no default; acc_alternate > 1 needs it)";
+                else if (alt.rounds > 1 && keep < 0) why << "acc_perturb_keep " << keep << " < 0";
+                else if (hyp < 0) why << "acc_neigh_hyp " << hyp << " < 0";
+                else if (slots + 2 * hyp > 16) why << "slots + 2 * acc_neigh_hyp = " << slots << " + 2 * " << hyp << " > 16";
+                else if (alt.rounds > 1 && keep + 1 + 2 * hyp > 16) why << "acc_perturb_keep + 1 + 2 * acc_neigh_hyp = " << keep << " + 1 + 2 * " << hyp << " > 16";
+                else if (alt.neigh.neigh_skip1 < 1) why << "acc_neigh_skip1 " << alt.neigh.neigh_skip1 << " < 1";
+                else if (alt.neigh.neigh_skip2 < 1) why << "acc_neigh_skip2 " << alt.neigh.neigh_skip2 << " < 1";
+                else if (alt.neigh.hyp_neigh_tryouts < 0) why << "acc_hyp_neigh_tryouts " << alt.neigh.hyp_neigh_tryouts << " < 0";
+                else if (!(alt.neigh.neigh_hyp_radius > 0)) why << "acc_neigh_hyp_radius " << alt.neigh.neigh_hyp_radius << " <= 0 (the knnSearch(acc_neigh_draws) branch)";
+                if (!why.str().empty()) { std::cerr << "-alternate: " << why.str() << " is not supported" << std::endl; return 1; }
+            }
         } else if (params.parameter<bool>("acc_epic_interpolation", "1"))
             std::cout << "-fuse: acc_epic_interpolation 1, but EpicFlow's fill-in and the neighbour proposals are not run (pixels without a hypothesis "
                          "stay UNKNOWN_FLOW)" << std::endl;
@@ -934,6 +1018,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "-energies")) run.energies = true;
         else if (!strcmp(a, "-fuse")) run.fuse = run.energies = true;
         else if (!strcmp(a, "-fill")) run.fill = run.fuse = run.energies = true;
+        else if (!strcmp(a, "-alternate")) run.alternate = run.fill = run.fuse = run.energies = true;
         else if (!strcmp(a, "-select") && i + 1 < argc) { selected = (unsigned)atoi(argv[++i]); selected_end = selected + 1; }
         else { fprintf(stderr, "unknown argument %s\n", a); usage(); return 1; }
     }
