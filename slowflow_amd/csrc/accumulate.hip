@@ -82,11 +82,6 @@ __global__ void __launch_bounds__(kAccThreads) k_accumulate(const T2 *__restrict
     tracked[(size_t)s * gpl + i] = tr;
 }
 
-// (u, v) planes -> float2 planes, n planes of pl values each
-__global__ void __launch_bounds__(kAccThreads) k_interleave(const float *__restrict__ u, const float *__restrict__ v, float2 *__restrict__ out, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * kAccThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kAccThreads) out[i] = make_float2(u[i], v[i]);
-}
-
 }  // namespace sfa
 
 using namespace sfa;
@@ -106,11 +101,6 @@ int sfa_accumulate_grid(int w, int h, int skip, int *gw, int *gh) {
 }
 
 namespace sfa {
-
-void launch_interleave(sfa_ctx *ctx, const float *u, const float *v, float2 *out, size_t n) {
-    const int blocks = (int)std::min<size_t>((n + kAccThreads - 1) / kAccThreads, (size_t)ctx->cu_count * 8);
-    hipLaunchKernelGGL(k_interleave, dim3(blocks), dim3(kAccThreads), 0, ctx->stream, u, v, out, n);
-}
 
 int accumulate_device(sfa_ctx *ctx, int n, int FF, int w, int h, int gw, int gh, int skip, bool identity, const void *fwd, const void *bwd,
                       const unsigned char *masks, double epsilon, int discard, int all_steps, double *acc_u, double *acc_v, int *tracked) {
@@ -146,7 +136,7 @@ static int accumulate_run(sfa_ctx *ctx, const char *fn, int n, int FF, int w, in
     const size_t np = (size_t)n * FF, pl = (size_t)w * h, spl = identity ? pl : (size_t)src->cw * src->ch;
     for (size_t k = 0; k < np; k++)
         if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k] || (masks && !masks[k])) return set_error(ctx, SFA_ERR_ARG, "%s: null plane %zu", fn, k);
-    const int S = all_steps ? FF : 1, stride = src->stride;
+    const int S = all_steps ? FF : 1;
     const size_t tap = identity ? 8 : 16;                                       // float2 or double2
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     DevMem dfw, dbw, dstage, dm, dms, dau, dav, dtr;
@@ -155,46 +145,27 @@ static int accumulate_run(sfa_ctx *ctx, const char *fn, int n, int FF, int w, in
     if (masks && raw_occ) SFA_TRY(dms.alloc(ctx, np * (size_t)src->sw * src->sh));
     const size_t gpl = (size_t)gw * gh;
     SFA_TRY(dau.alloc(ctx, (size_t)n * S * gpl * 8)); SFA_TRY(dav.alloc(ctx, (size_t)n * S * gpl * 8)); SFA_TRY(dtr.alloc(ctx, (size_t)n * gpl * 4));
-    hipEvent_t ev[6] = {};                                                      // around the forward and the backward flows' kernel and k_accumulate
-    if (stage_ms)
-        for (auto &e : ev) SFA_HIP(ctx, hipEventCreate(&e));
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 6; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
-    float *su = dstage.f(), *sv = dstage.f() + np * spl;
-    for (int dir = 0; dir < 2; dir++) {
-        const float *const *U = dir ? bwd_u : fwd_u, *const *V = dir ? bwd_v : fwd_v;
-        if (!identity) {
-            SFA_TRY(jet_resample_flows(ctx, *src, np, U, V, w, h, dstage.f(), static_cast<double2 *>(dir ? dbw.p : dfw.p), ev[2 * dir], ev[2 * dir + 1]));
-            continue;
-        }
-        for (size_t k = 0; k < np; k++) {                                       // the valid columns of each plane, packed, then interleaved
-            SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)w * 4, U[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-            SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, V[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-        }
-        if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[2 * dir], ctx->stream));
-        launch_interleave(ctx, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), np * pl);
-        if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[2 * dir + 1], ctx->stream));
-    }
+    StageEvents ev;                                                             // around the forward and the backward flows' kernel and k_accumulate
+    if (stage_ms) SFA_TRY(ev.make(ctx, 6));
+    SFA_TRY(upload_flow_pairs(ctx, *src, identity, np, fwd_u, fwd_v, w, h, dstage.f(), dfw.p, ev.e[0], ev.e[1]));
+    SFA_TRY(upload_flow_pairs(ctx, *src, identity, np, bwd_u, bwd_v, w, h, dstage.f(), dbw.p, ev.e[2], ev.e[3]));
     if (masks && raw_occ)
         SFA_TRY(jet_decode_occlusions(ctx, *src, np, masks, w, h, static_cast<unsigned char *>(dms.p), static_cast<unsigned char *>(dm.p)));
     else if (masks)
-        for (size_t k = 0; k < np; k++)
-            SFA_HIP(ctx, hipMemcpy2DAsync(static_cast<unsigned char *>(dm.p) + k * pl, (size_t)w, masks[k], (size_t)stride, (size_t)w, h, hipMemcpyHostToDevice,
-                                          ctx->stream));
-    const unsigned char *dmp = masks ? static_cast<const unsigned char *>(dm.p) : nullptr;
-    double *pau = static_cast<double *>(dau.p), *pav = static_cast<double *>(dav.p);
-    if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[4], ctx->stream));
-    SFA_TRY(accumulate_device(ctx, n, FF, w, h, gw, gh, skip, identity, dfw.p, dbw.p, dmp, epsilon, discard, all_steps, pau, pav, static_cast<int *>(dtr.p)));
-    if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev[5], ctx->stream));
+        SFA_TRY(upload_masks(ctx, np, masks, src->stride, w, h, static_cast<unsigned char *>(dm.p)));
+    SFA_TRY(ev.mark(ctx, 4));
+    SFA_TRY(accumulate_device(ctx, n, FF, w, h, gw, gh, skip, identity, dfw.p, dbw.p, static_cast<const unsigned char *>(dm.p), epsilon, discard, all_steps,
+                              static_cast<double *>(dau.p), static_cast<double *>(dav.p), static_cast<int *>(dtr.p)));
+    SFA_TRY(ev.mark(ctx, 5));
     SFA_HIP(ctx, hipMemcpyAsync(acc_u, dau.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(acc_v, dav.p, (size_t)n * S * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(tracked, dtr.p, (size_t)n * gpl * 4, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (stage_ms) {
-        float fw_ms = 0, bw_ms = 0;
-        SFA_HIP(ctx, hipEventElapsedTime(&fw_ms, ev[0], ev[1]));
-        SFA_HIP(ctx, hipEventElapsedTime(&bw_ms, ev[2], ev[3]));
-        SFA_HIP(ctx, hipEventElapsedTime(&stage_ms[1], ev[4], ev[5]));
-        stage_ms[0] = fw_ms + bw_ms;
+        float span[5];                                                          // forward, (between), backward, (masks), accumulation
+        SFA_TRY(ev.read(ctx, 6, span));
+        stage_ms[0] = span[0] + span[2];
+        stage_ms[1] = span[4];
     }
     return SFA_OK;
 }

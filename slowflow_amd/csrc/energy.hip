@@ -49,11 +49,6 @@ __device__ __forceinline__ float phi_apply(int kind, double eps_sq, float xsq) {
     return (float)log(1 + 0.5 * xsq / eps_sq);                                  // Lorentzian: 1 + ((0.5 * xsq) / eps_sq)
 }
 
-// fp32 (u, v) planes -> float2 planes
-__global__ void __launch_bounds__(kEnThreads) k_energy_interleave(const float *__restrict__ u, const float *__restrict__ v, float2 *__restrict__ out, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * kEnThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kEnThreads) out[i] = make_float2(u[i], v[i]);
-}
-
 // frame k (3 planes c1, c2, c3 of pl floats), dx_k, dy_k -> one record of 12 floats per pixel: I c3, c2, c1, dx c3, c2, c1, dy c3, c2, c1, 0, 0, 0 (the
 // reference reads the channels in the order c3, c2, c1, dense_tracking.cpp:266-274)
 __global__ void __launch_bounds__(kEnThreads) k_energy_records(const float *__restrict__ fr, const float *__restrict__ dx, const float *__restrict__ dy,
@@ -364,6 +359,42 @@ int energies_adapted_device(sfa_ctx *ctx, const EnergyPlan &e, int n, const int 
     return SFA_OK;
 }
 
+int EnergyMem::alloc(sfa_ctx *ctx, const EnergyPlan &e, int n, int work_n, const sfa_jet_source *flow_src, bool is_identity) {
+    const size_t nf = (size_t)n * (e.J + 1), pl = (size_t)e.w * e.h, wg = (size_t)work_n * e.gw * e.gh;
+    SFA_TRY(frames.alloc(ctx, nf * 3 * pl * 4)); SFA_TRY(der.alloc(ctx, nf * 6 * pl * 4)); SFA_TRY(rec.alloc(ctx, nf * pl * 48));
+    SFA_TRY(U.alloc(ctx, wg * e.J * 8)); SFA_TRY(V.alloc(ctx, wg * e.J * 8)); SFA_TRY(occ.alloc(ctx, wg * 8));
+    SFA_TRY(jc.alloc(ctx, wg * 4)); SFA_TRY(oc.alloc(ctx, wg * 4)); SFA_TRY(ep.alloc(ctx, wg * e.NN * 8));
+    segments = n;
+    if (flow_src) { flows = true; src = *flow_src; identity = is_identity; }
+    return SFA_OK;
+}
+
+int EnergyMem::upload(sfa_ctx *ctx, const EnergyPlan &e, const float *const *host_frames, int stride, const float *const *fwd_u, const float *const *fwd_v,
+                      const float *const *bwd_u, const float *const *bwd_v) {
+    const size_t nf = (size_t)segments * (e.J + 1), nj = (size_t)segments * e.J, pl = (size_t)e.w * e.h;
+    SFA_TRY(upload_frames(ctx, nf, host_frames, stride, e.w, e.h, frames.f()));
+    energy_records_device(ctx, nf, e.w, e.h, frames.f(), der.f(), rec.p);
+    SFA_HIP(ctx, hipGetLastError());
+    if (!flows) return SFA_OK;
+    const size_t tap = identity ? 8 : 16, spl = identity ? pl : (size_t)src.cw * src.ch;   // float2 or double2
+    SFA_TRY(fwd.alloc(ctx, nj * pl * tap)); SFA_TRY(bwd.alloc(ctx, nj * pl * tap));   // while the records' kernels run: hipMalloc stays off the critical path
+    SFA_TRY(stage.alloc(ctx, nj * spl * 8));
+    // not the identity: r_forward_flow, resized and multiplied by rescale (:1142-1151)
+    SFA_TRY(upload_flow_pairs(ctx, src, identity, nj, fwd_u, fwd_v, e.w, e.h, stage.f(), fwd.p, nullptr, nullptr));
+    return upload_flow_pairs(ctx, src, identity, nj, bwd_u, bwd_v, e.w, e.h, stage.f(), bwd.p, nullptr, nullptr);
+}
+
+int energy_planes_check(sfa_ctx *ctx, const char *fn, bool with_index, size_t nf, const float *const *frames, size_t nj, const float *const *fwd_u,
+                        const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v, bool *flows) {
+    *flows = fwd_u != nullptr;
+    CHECK_ARGS_FN(fn, *flows == (fwd_v != nullptr) && *flows == (bwd_u != nullptr) && *flows == (bwd_v != nullptr), "the four flow arrays are all given or all null");
+    for (size_t k = 0; k < nf; k++)
+        if (!frames[k]) { if (with_index) REFUSE("%s: null frame %zu", fn, k); REFUSE("%s: null frame", fn); }
+    for (size_t k = 0; *flows && k < nj; k++)
+        if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k]) { if (with_index) REFUSE("%s: null flow plane %zu", fn, k); REFUSE("%s: null flow plane", fn); }
+    return SFA_OK;
+}
+
 }  // namespace sfa
 
 using namespace sfa;
@@ -408,68 +439,32 @@ int sfa_hypothesis_energies_scaled(sfa_ctx *ctx, const sfa_energy_params *p, int
                                    double *energy, unsigned long long *occ_bits, double *adapted_u, double *adapted_v) {
     if (!(ctx && p && acc_u && acc_v && tracked && frames && energy && occ_bits)) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: null argument");
     if ((adapted_u != nullptr) != (adapted_v != nullptr)) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies_ex: adapted_u and adapted_v are both given or both null");
-    const bool flows = fwd_u != nullptr;
-    if (flows != (fwd_v != nullptr) || flows != (bwd_u != nullptr) || flows != (bwd_v != nullptr))
-        return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: the four flow arrays are all given or all null");
     if (!(n >= 1 && r_Jets >= 1 && Jets >= 1 && Jets <= kEnMaxJets && (long)n * (Jets + 1) * 3 <= 65535 && w >= 1 && stride >= w))
         return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: bad sizes (n >= 1 with n (Jets + 1) <= 21845, r_Jets >= 1, 1 <= Jets <= %d, w >= 1, stride >= w)",
                          kEnMaxJets);
     if (h < 4)   // convolve_vert_fast_5 (image.c:425-458) runs its middle-row loop from height - 3 down through zero: undefined below 4 rows
         return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: h = %d; the reference's vertical 5-tap derivative needs h >= 4", h);
-    bool identity = true;                                                       // the flows are w x h float planes of the frames' stride
+    const size_t nf = (size_t)n * (Jets + 1), nj = (size_t)n * Jets;
+    bool flows, identity = true;                                                // without a source the flows are w x h float planes of the frames' stride
+    SFA_TRY(energy_planes_check(ctx, "sfa_hypothesis_energies", true, nf, frames, nj, fwd_u, fwd_v, bwd_u, bwd_v, &flows));
     if (flows) SFA_TRY(jet_source_check(ctx, "sfa_hypothesis_energies: flow_src", flow_src, w, h, &identity));
     EnergyPlan plan;
     SFA_TRY(energy_plan(ctx, p, r_Jets, Jets, w, h, &plan));
-    const int gw = plan.gw, gh = plan.gh, NN = plan.NN;
-    const size_t nf = (size_t)n * (Jets + 1), nj = (size_t)n * Jets, pl = (size_t)w * h, gpl = (size_t)gw * gh;
-    for (size_t k = 0; k < nf; k++)
-        if (!frames[k]) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: null frame %zu", k);
-    if (flows)
-        for (size_t k = 0; k < nj; k++)
-            if (!fwd_u[k] || !fwd_v[k] || !bwd_u[k] || !bwd_v[k]) return set_error(ctx, SFA_ERR_ARG, "sfa_hypothesis_energies: null flow plane %zu", k);
+    const size_t gpl = (size_t)plan.gw * plan.gh;
 
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    DevMem dfr, dder, drec, dfw, dbw, dstage, dau, dav, dtr, dU, dV, docc, djc, doc, dep, den, docc_out, dad;
-    SFA_TRY(dfr.alloc(ctx, nf * 3 * pl * 4)); SFA_TRY(dder.alloc(ctx, nf * 6 * pl * 4)); SFA_TRY(drec.alloc(ctx, nf * pl * 48));
+    EnergyMem in;
+    DevMem dau, dav, dtr, den, docc_out, dad;
+    SFA_TRY(in.alloc(ctx, plan, n, n, flows ? flow_src : nullptr, identity));
     SFA_TRY(dau.alloc(ctx, (size_t)n * r_Jets * gpl * 8)); SFA_TRY(dav.alloc(ctx, (size_t)n * r_Jets * gpl * 8)); SFA_TRY(dtr.alloc(ctx, (size_t)n * gpl * 4));
-    SFA_TRY(dU.alloc(ctx, nj * gpl * 8)); SFA_TRY(dV.alloc(ctx, nj * gpl * 8)); SFA_TRY(docc.alloc(ctx, (size_t)n * gpl * 8));
-    SFA_TRY(djc.alloc(ctx, (size_t)n * gpl * 4)); SFA_TRY(doc.alloc(ctx, (size_t)n * gpl * 4)); SFA_TRY(dep.alloc(ctx, (size_t)n * gpl * NN * 8));
     SFA_TRY(den.alloc(ctx, (size_t)n * gpl * 8)); SFA_TRY(docc_out.alloc(ctx, (size_t)n * gpl * 8));
-    const int blocks_cap = ctx->cu_count * 8;
-    // frames: the valid columns of each plane, packed
-    for (size_t k = 0; k < nf; k++)
-        for (int c = 0; c < 3; c++)
-            SFA_HIP(ctx, hipMemcpy2DAsync(dfr.f() + (k * 3 + c) * pl, (size_t)w * 4, frames[k] + (size_t)c * h * stride, (size_t)stride * 4, (size_t)w * 4, h,
-                                          hipMemcpyHostToDevice, ctx->stream));
-    energy_records_device(ctx, nf, w, h, dfr.f(), dder.f(), drec.p);
-    if (flows) {
-        const size_t tap = identity ? 8 : 16, spl = identity ? pl : (size_t)flow_src->cw * flow_src->ch;   // float2 or double2
-        const int fstride = flow_src->stride;
-        SFA_TRY(dfw.alloc(ctx, nj * pl * tap)); SFA_TRY(dbw.alloc(ctx, nj * pl * tap)); SFA_TRY(dstage.alloc(ctx, nj * spl * 8));
-        float *su = dstage.f(), *sv = dstage.f() + nj * pl;
-        for (int dir = 0; dir < 2; dir++) {
-            const float *const *Uh = dir ? bwd_u : fwd_u, *const *Vh = dir ? bwd_v : fwd_v;
-            if (!identity) {                                                    // r_forward_flow: resized and multiplied by rescale (:1142-1151)
-                SFA_TRY(jet_resample_flows(ctx, *flow_src, nj, Uh, Vh, w, h, dstage.f(), static_cast<double2 *>(dir ? dbw.p : dfw.p), nullptr, nullptr));
-                continue;
-            }
-            for (size_t k = 0; k < nj; k++) {
-                SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)w * 4, Uh[k], (size_t)fstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-                SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, Vh[k], (size_t)fstride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-            }
-            hipLaunchKernelGGL(k_energy_interleave, dim3((unsigned)std::min<size_t>((nj * pl + kEnThreads - 1) / kEnThreads, blocks_cap)), dim3(kEnThreads), 0,
-                               ctx->stream, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), nj * pl);
-        }
-    }
-    SFA_HIP(ctx, hipMemcpyAsync(dau.p, acc_u, (size_t)n * r_Jets * gpl * 8, hipMemcpyHostToDevice, ctx->stream));
-    SFA_HIP(ctx, hipMemcpyAsync(dav.p, acc_v, (size_t)n * r_Jets * gpl * 8, hipMemcpyHostToDevice, ctx->stream));
-    SFA_HIP(ctx, hipMemcpyAsync(dtr.p, tracked, (size_t)n * gpl * 4, hipMemcpyHostToDevice, ctx->stream));
-    EnergyWork wk;
-    wk.U = static_cast<double *>(dU.p); wk.V = static_cast<double *>(dV.p); wk.occ = static_cast<unsigned long long *>(docc.p);
-    wk.jc = djc.f(); wk.oc = doc.f(); wk.ep = static_cast<double *>(dep.p);
-    SFA_TRY(energies_device(ctx, plan, n, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), static_cast<const int *>(dtr.p), drec.p, identity,
-                            flows ? dfw.p : nullptr, flows ? dbw.p : nullptr, wk, static_cast<double *>(den.p), static_cast<unsigned long long *>(docc_out.p), gpl, nullptr,
-                            nullptr, 0));
+    SFA_TRY(in.upload(ctx, plan, frames, stride, fwd_u, fwd_v, bwd_u, bwd_v));
+    SFA_TRY(copy_on(ctx, dau.p, acc_u, (size_t)n * r_Jets * gpl * 8, hipMemcpyHostToDevice));
+    SFA_TRY(copy_on(ctx, dav.p, acc_v, (size_t)n * r_Jets * gpl * 8, hipMemcpyHostToDevice));
+    SFA_TRY(copy_on(ctx, dtr.p, tracked, (size_t)n * gpl * 4, hipMemcpyHostToDevice));
+    const EnergyWork wk = in.work();
+    SFA_TRY(energies_device(ctx, plan, n, static_cast<const double *>(dau.p), static_cast<const double *>(dav.p), static_cast<const int *>(dtr.p), in.rec.p, identity,
+                            in.fwd.p, in.bwd.p, wk, static_cast<double *>(den.p), static_cast<unsigned long long *>(docc_out.p), gpl, nullptr, nullptr, 0));
     SFA_HIP(ctx, hipMemcpyAsync(energy, den.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(occ_bits, docc_out.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (adapted_u) {                                                            // allocated while the kernels above run: hipMalloc stays off the critical path

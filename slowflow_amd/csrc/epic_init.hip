@@ -61,11 +61,6 @@ __global__ void __launch_bounds__(kEiThreads) k_epic_flow_unpack(float *dst, lon
 // what follows holds no kernel: checks, copies and launches.  Compiled for size (see track.hip)
 #pragma clang attribute push(__attribute__((minsize)), apply_to = function)
 
-int copy_on(sfa_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
-    SFA_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
-    return SFA_OK;
-}
-
 // images [i0, i0 + n) of an epic job
 int job_images(sfa_ctx *ctx, const char *fn, const sfa_epic_job *j, int i0, int n) { return check_batch_range(ctx, fn, "images", i0, n, j->n); }
 

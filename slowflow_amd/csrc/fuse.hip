@@ -349,16 +349,15 @@ int fuse_device(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, 
     SFA_HIP(ctx, hipMemsetAsync(f.M, 0, (size_t)n * gpl * 4 * kFuMaxK * 8, ctx->stream));
     SFA_HIP(ctx, hipMemsetAsync(f.xcur, 0, (size_t)n * gpl, ctx->stream));
     SFA_HIP(ctx, hipMemsetAsync(f.xbest, 0, (size_t)n * gpl, ctx->stream));
-    auto mark = [&](int i) { return ev ? hipEventRecord(ev[i], ctx->stream) : hipSuccess; };
     const dim3 pix((unsigned)((gpl + kFuThreads - 1) / kFuThreads), (unsigned)n);
-    SFA_HIP(ctx, mark(0));
+    SFA_TRY(mark_if(ctx, ev, 0));
     hipLaunchKernelGGL(k_fuse_labels, pix, dim3(kFuThreads), 0, ctx->stream, f.U, f.V, f.energy, d, p->traj_sim_method, p->traj_sim_thres, p->pin_first != 0, f.nl, f.lab, f.theta);
     SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(1));
+    SFA_TRY(mark_if(ctx, ev, 1));
     hipLaunchKernelGGL(k_fuse_pairwise, dim3((unsigned)((gpl * KK + kFuThreads - 1) / kFuThreads), (unsigned)(2 * n)), dim3(kFuThreads), 0, ctx->stream, f.U, f.V,
                        f.occ, f.weight, d, p->traj_sim_method, p->acc_beta, p->acc_spatial_occ, f.nl, f.lab, f.P);
     SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(2));
+    SFA_TRY(mark_if(ctx, ev, 2));
     TrwsBufs tb;
     tb.nl = f.nl; tb.theta = f.theta; tb.P = f.P; tb.M = f.M;
     tb.xcur = f.xcur; tb.xbest = f.xbest; tb.seg_energy = f.seg_energy; tb.seg_bound = f.seg_bound; tb.seg_iters = f.seg_iters;
@@ -366,10 +365,10 @@ int fuse_device(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, int Jets, 
     else if (K <= 8) hipLaunchKernelGGL(k_trws<8>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
     else hipLaunchKernelGGL(k_trws<16>, dim3(n), dim3(kTrwsThreads), 0, ctx->stream, tb, d, p->trws_eps, p->trws_max_iter);
     SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(3));
+    SFA_TRY(mark_if(ctx, ev, 3));
     hipLaunchKernelGGL(k_fuse_output, pix, dim3(kFuThreads), 0, ctx->stream, f.U, f.V, f.occ, d, f.nl, f.lab, f.xbest, f.slot, f.fu, f.fv, f.out_occ);
     SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(4));
+    SFA_TRY(mark_if(ctx, ev, 4));
     return SFA_OK;
 }
 
@@ -427,11 +426,9 @@ int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, in
     f.P = static_cast<double *>(dP.p); f.M = static_cast<double *>(dM.p); f.xcur = px; f.xbest = px + (size_t)n * gpl;
     f.slot = static_cast<int *>(dslot.p); f.fu = static_cast<double *>(dfu.p); f.fv = static_cast<double *>(dfv.p); f.out_occ = static_cast<unsigned char *>(dout_occ.p);
     f.seg_energy = pseg; f.seg_bound = pseg + n; f.seg_iters = reinterpret_cast<int *>(pseg + 2 * n);
-    hipEvent_t ev[5] = {};
-    if (stage_ms)
-        for (auto &e : ev) SFA_HIP(ctx, hipEventCreate(&e));
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 5; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
-    SFA_TRY(fuse_device(ctx, p, n, K, Jets, w, h, gw, gh, f, stage_ms ? ev : nullptr));
+    StageEvents ev;
+    if (stage_ms) SFA_TRY(ev.make(ctx, 5));
+    SFA_TRY(fuse_device(ctx, p, n, K, Jets, w, h, gw, gh, f, stage_ms ? ev.e : nullptr));
     SFA_HIP(ctx, hipMemcpyAsync(slot, dslot.p, (size_t)n * gpl * 4, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(flow_u, dfu.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(flow_v, dfv.p, (size_t)n * gpl * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -440,7 +437,6 @@ int sfa_fuse_hypotheses(sfa_ctx *ctx, const sfa_fuse_params *p, int n, int K, in
     SFA_HIP(ctx, hipMemcpyAsync(seg_bound, pseg + n, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(seg_iters, pseg + 2 * n, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (stage_ms)
-        for (int i = 0; i < 4; i++) SFA_HIP(ctx, hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
+    if (stage_ms) SFA_TRY(ev.read(ctx, 5, stage_ms));
     return SFA_OK;
 }

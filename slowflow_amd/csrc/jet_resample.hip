@@ -149,9 +149,7 @@ int launch_jet_occ_decode(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, cons
 }
 
 int jet_decode_occlusions(sfa_ctx *ctx, const sfa_jet_source &s, size_t np, const unsigned char *const *occ, int w, int h, unsigned char *stage, unsigned char *out) {
-    const size_t spl = (size_t)s.sw * s.sh;
-    for (size_t k = 0; k < np; k++)
-        SFA_HIP(ctx, hipMemcpy2DAsync(stage + k * spl, (size_t)s.sw, occ[k], (size_t)s.stride, (size_t)s.sw, s.sh, hipMemcpyHostToDevice, ctx->stream));
+    SFA_TRY(upload_masks(ctx, np, occ, s.stride, s.sw, s.sh, stage));             // the images as read, packed
     return launch_jet_occ_decode(ctx, s, np, stage, w, h, out);
 }
 

@@ -317,14 +317,13 @@ static int neigh_gather(sfa_ctx *ctx, const NeighDims &d, const NeighPlanes &in,
 int neigh_prune_device(sfa_ctx *ctx, int n, int Jets, int gw, int gh, int keep, const int *sel, const NeighPlanes &in, const NeighPlanes &out, int *map,
                        hipEvent_t *ev) {
     const NeighDims d{n, Jets, gw, gh, gw * gh};
-    auto mark = [&](int i) { return ev ? hipEventRecord(ev[i], ctx->stream) : hipSuccess; };
-    SFA_HIP(ctx, mark(0));
+    SFA_TRY(mark_if(ctx, ev, 0));
     hipLaunchKernelGGL(k_neigh_prune, dim3((unsigned)((d.gpl + kNeighThreads - 1) / kNeighThreads), (unsigned)n), dim3(kNeighThreads), 0, ctx->stream, in.energy, sel,
                        d, keep, map);
     SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(1));
+    SFA_TRY(mark_if(ctx, ev, 1));
     SFA_TRY(neigh_gather(ctx, d, in, out, map));
-    SFA_HIP(ctx, mark(2));
+    SFA_TRY(mark_if(ctx, ev, 2));
     return SFA_OK;
 }
 
@@ -353,7 +352,6 @@ int neigh_check(sfa_ctx *ctx, const char *fn, const sfa_neigh_params *p, int gw,
 int neigh_propose_device(sfa_ctx *ctx, const sfa_neigh_params *p, int n, int Jets, int gw, int gh, int round, const unsigned *seq_start,
                          const unsigned char *consistent, const NeighPlanes &in, const NeighPlanes &out, const NeighWork &wk, hipEvent_t *ev) {
     const NeighDims d{n, Jets, gw, gh, gw * gh};
-    auto mark = [&](int i) { return ev ? hipEventRecord(ev[i], ctx->stream) : hipSuccess; };
     NeighSearch q;
     q.skip[0] = p->neigh_skip1; q.skip[1] = p->neigh_skip2;
     for (int t = 0; t < 2; t++) {
@@ -365,16 +363,16 @@ int neigh_propose_device(sfa_ctx *ctx, const sfa_neigh_params *p, int n, int Jet
     q.key0 = p->seed + (unsigned)round;
     SFA_HIP(ctx, hipMemsetAsync(wk.total, 0, (size_t)n * 2 * sizeof(int), ctx->stream));
     const dim3 pix((unsigned)((d.gpl + kNeighThreads - 1) / kNeighThreads), (unsigned)n);
-    SFA_HIP(ctx, mark(0));
+    SFA_TRY(mark_if(ctx, ev, 0));
     hipLaunchKernelGGL(k_neigh_flags, pix, dim3(kNeighThreads), 0, ctx->stream, in.energy, consistent, d, round, q.skip[0], q.skip[1], wk.flags, wk.srcpos, wk.total);
     SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(1));
+    SFA_TRY(mark_if(ctx, ev, 1));
     hipLaunchKernelGGL(k_neigh_propose, dim3((unsigned)((d.gpl + kNeighWaves - 1) / kNeighWaves), (unsigned)n), dim3(kNeighThreads), 0, ctx->stream, in.U, in.V,
                        in.energy, wk.flags, wk.srcpos, wk.total, seq_start, d, q, wk.map);
     SFA_HIP(ctx, hipGetLastError());
-    SFA_HIP(ctx, mark(2));
+    SFA_TRY(mark_if(ctx, ev, 2));
     SFA_TRY(neigh_gather(ctx, d, in, out, wk.map));
-    SFA_HIP(ctx, mark(3));
+    SFA_TRY(mark_if(ctx, ev, 3));
     return SFA_OK;
 }
 
@@ -474,20 +472,6 @@ struct ListMem {
     }
 };
 
-// up to four events around a stage's kernels, made only where the caller asks for the times
-struct StageEvents {
-    hipEvent_t e[4] = {};
-    int make(sfa_ctx *ctx, int n) {
-        for (int i = 0; i < n; i++) SFA_HIP(ctx, hipEventCreate(&e[i]));
-        return SFA_OK;
-    }
-    int read(sfa_ctx *ctx, int n, float *ms) {
-        for (int i = 0; i + 1 < n; i++) SFA_HIP(ctx, hipEventElapsedTime(&ms[i], e[i], e[i + 1]));
-        return SFA_OK;
-    }
-    ~StageEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 bool lists_given(const sfa_hyp_lists *h) { return h && h->U && h->V && h->energy && h->occ_bits && h->origin; }
 
 }  // namespace
@@ -572,18 +556,15 @@ int sfa_rescore_proposals(sfa_ctx *ctx, const sfa_energy_params *p, int n, int J
                           const float *const *fwd_u, const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v, const float *slot_weight,
                           const int *src_pixel, const sfa_hyp_lists *lists, float *stage_ms) {
     CHECK_ARGS(ctx && p && frames && slot_weight && src_pixel && lists_given(lists), "null argument");
-    const bool flows = fwd_u != nullptr;
-    CHECK_ARGS(flows == (fwd_v != nullptr) && flows == (bwd_u != nullptr) && flows == (bwd_v != nullptr), "the four flow arrays are all given or all null");
     CHECK_ARGS(n >= 1 && Jets >= 1 && Jets <= 32 && (long)n * (Jets + 1) * 3 <= 65535 && w >= 1 && stride >= w,
                "bad sizes (n >= 1 with n (Jets + 1) <= 21845, 1 <= Jets <= 32, w >= 1, stride >= w)");
     CHECK_ARGS(h >= 4, "the reference's vertical 5-tap derivative needs h >= 4");
+    bool flows;
+    SFA_TRY(energy_planes_check(ctx, __func__, false, (size_t)n * (Jets + 1), frames, (size_t)n * Jets, fwd_u, fwd_v, bwd_u, bwd_v, &flows));
     EnergyPlan plan;
     SFA_TRY(energy_plan(ctx, p, Jets, Jets, w, h, &plan));
     plan.a.weight = 0.0f;                                                       // the rate's weight is added per pixel, by the origin
-    const size_t gpl = (size_t)plan.gw * plan.gh, pl = (size_t)w * h, nf = (size_t)n * (Jets + 1), nj = (size_t)n * Jets, nk = (size_t)n * kNeighK * gpl;
-    for (size_t k = 0; k < nf; k++) CHECK_ARGS(frames[k], "null frame");
-    if (flows)
-        for (size_t k = 0; k < nj; k++) CHECK_ARGS(fwd_u[k] && fwd_v[k] && bwd_u[k] && bwd_v[k], "null flow plane");
+    const size_t gpl = (size_t)plan.gw * plan.gh, nk = (size_t)n * kNeighK * gpl;
     // which positions were filled in this round, and by hypotheses born in which slot
     std::vector<int> tracked(nk);
     std::vector<unsigned char> todo((size_t)n * kNeighK, 0);
@@ -598,44 +579,23 @@ int sfa_rescore_proposals(sfa_ctx *ctx, const sfa_energy_params *p, int n, int J
     for (int k = 0; k < kNeighK; k++) wt.w[k] = slot_weight[k];
 
     SFA_HIP(ctx, hipSetDevice(ctx->device));
+    sfa_jet_source src;                                                         // the flows are w x h float planes of the frames' stride
+    sfa_jet_source_default(&src, w, h, stride);
     ListMem a;
-    DevMem dfr, dder, drec, dfw, dbw, dstage, dtr, dU, dV, docc, djc, doc, dep, dE, dO;
+    EnergyMem in;                                                               // the scratch of one segment: the positions are scored one at a time
+    DevMem dtr, dE, dO;
     SFA_TRY(a.alloc(ctx, n, Jets, gpl));
-    SFA_TRY(dfr.alloc(ctx, nf * 3 * pl * 4)); SFA_TRY(dder.alloc(ctx, nf * 6 * pl * 4)); SFA_TRY(drec.alloc(ctx, nf * pl * 48)); SFA_TRY(dtr.alloc(ctx, nk * 4));
-    SFA_TRY(dU.alloc(ctx, (size_t)Jets * gpl * 8)); SFA_TRY(dV.alloc(ctx, (size_t)Jets * gpl * 8)); SFA_TRY(docc.alloc(ctx, gpl * 8));
-    SFA_TRY(djc.alloc(ctx, gpl * 4)); SFA_TRY(doc.alloc(ctx, gpl * 4)); SFA_TRY(dep.alloc(ctx, gpl * plan.NN * 8)); SFA_TRY(dE.alloc(ctx, gpl * 8)); SFA_TRY(dO.alloc(ctx, gpl * 8));
+    SFA_TRY(in.alloc(ctx, plan, n, 1, flows ? &src : nullptr, true));
+    SFA_TRY(dtr.alloc(ctx, nk * 4)); SFA_TRY(dE.alloc(ctx, gpl * 8)); SFA_TRY(dO.alloc(ctx, gpl * 8));
     SFA_TRY(a.copy(ctx, *lists, true));
-    SFA_HIP(ctx, hipMemcpyAsync(dtr.p, tracked.data(), nk * 4, hipMemcpyHostToDevice, ctx->stream));
-    for (size_t k = 0; k < nf; k++)                                             // frames: the valid columns of each plane, packed
-        for (int c = 0; c < 3; c++)
-            SFA_HIP(ctx, hipMemcpy2DAsync(dfr.f() + (k * 3 + c) * pl, (size_t)w * 4, frames[k] + (size_t)c * h * stride, (size_t)stride * 4, (size_t)w * 4, h,
-                                          hipMemcpyHostToDevice, ctx->stream));
-    energy_records_device(ctx, nf, w, h, dfr.f(), dder.f(), drec.p);
-    SFA_HIP(ctx, hipGetLastError());
-    if (flows) {
-        SFA_TRY(dfw.alloc(ctx, nj * pl * 8)); SFA_TRY(dbw.alloc(ctx, nj * pl * 8)); SFA_TRY(dstage.alloc(ctx, nj * pl * 8));
-        float *su = dstage.f(), *sv = dstage.f() + nj * pl;
-        for (int dir = 0; dir < 2; dir++) {
-            const float *const *Uh = dir ? bwd_u : fwd_u, *const *Vh = dir ? bwd_v : fwd_v;
-            for (size_t k = 0; k < nj; k++) {
-                SFA_HIP(ctx, hipMemcpy2DAsync(su + k * pl, (size_t)w * 4, Uh[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-                SFA_HIP(ctx, hipMemcpy2DAsync(sv + k * pl, (size_t)w * 4, Vh[k], (size_t)stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, ctx->stream));
-            }
-            launch_interleave(ctx, su, sv, static_cast<float2 *>(dir ? dbw.p : dfw.p), nj * pl);
-            SFA_HIP(ctx, hipGetLastError());
-        }
-    }
-    EnergyWork wk;
-    wk.U = static_cast<double *>(dU.p); wk.V = static_cast<double *>(dV.p); wk.occ = static_cast<unsigned long long *>(docc.p);
-    wk.jc = djc.f(); wk.oc = doc.f(); wk.ep = static_cast<double *>(dep.p);
+    SFA_TRY(copy_on(ctx, dtr.p, tracked.data(), nk * 4, hipMemcpyHostToDevice));
+    SFA_TRY(in.upload(ctx, plan, frames, stride, fwd_u, fwd_v, bwd_u, bwd_v));
     StageEvents ev;
-    if (stage_ms) {
-        SFA_TRY(ev.make(ctx, 2));
-        SFA_HIP(ctx, hipEventRecord(ev.e[0], ctx->stream));
-    }
-    SFA_TRY(neigh_rescore_device(ctx, plan, n, static_cast<const int *>(dtr.p), todo.data(), drec.p, true, flows ? dfw.p : nullptr, flows ? dbw.p : nullptr, wk,
+    if (stage_ms) SFA_TRY(ev.make(ctx, 2));
+    SFA_TRY(ev.mark(ctx, 0));
+    SFA_TRY(neigh_rescore_device(ctx, plan, n, static_cast<const int *>(dtr.p), todo.data(), in.rec.p, true, in.fwd.p, in.bwd.p, in.work(),
                                  static_cast<double *>(dE.p), static_cast<unsigned long long *>(dO.p), wt, a.planes()));
-    if (stage_ms) SFA_HIP(ctx, hipEventRecord(ev.e[1], ctx->stream));
+    SFA_TRY(ev.mark(ctx, 1));
     SFA_HIP(ctx, hipMemcpyAsync(lists->energy, a.energy.p, a.energy.bytes, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipMemcpyAsync(lists->occ_bits, a.occ.p, a.occ.bytes, hipMemcpyDeviceToHost, ctx->stream));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -210,11 +210,46 @@ int launch_jet_resample(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, cons
 // jet_decode_occlusions' kernel alone: stage holds np packed sw x sh images already in device memory
 int launch_jet_occ_decode(sfa_ctx *ctx, const sfa_jet_source &src, size_t np, const unsigned char *stage, int w, int h, unsigned char *out);
 
-// ---- dense_tracking's three stages at device level (accumulate.hip, energy.hip, fuse.hip): device pointers and a caller-owned workspace in, launches on the
-// context's stream out; no allocation, no copy, no wait.  The sfa_* entry points wrap them (allocate, upload, call, download, wait), the track job (track.hip, track_fill.hip)
-// chains them ------------------------------------------------------------------------------------------------------------------------------------------
+// ---- stage_io.hip: the host side of dense_tracking's stages, shared by the sfa_* stage wrappers and the track job.  Everything enqueues on the context's
+// stream and returns without waiting --------------------------------------------------------------------------------------------------------------------
 // n float planes u, v -> n float2 planes (total n elements)
 void launch_interleave(sfa_ctx *ctx, const float *u, const float *v, float2 *out, size_t n);
+#pragma GCC visibility push(hidden)   // nothing from here to the pop is part of the library's interface
+// one-line forms of the stream calls; download: a result to the host, or nothing where the caller passes no dst
+int copy_on(sfa_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+int zero_on(sfa_ctx *ctx, void *dst, size_t bytes);
+int mark(sfa_ctx *ctx, hipEvent_t e);
+int download(sfa_ctx *ctx, void *dst, const void *src, size_t bytes);
+// h rows of `row` bytes, the rows dpitch and spitch bytes apart
+int copy_rows_on(sfa_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t row, size_t h, hipMemcpyKind kind);
+// event i of a device-level function's `ev`, where the caller gave events
+inline int mark_if(sfa_ctx *ctx, hipEvent_t *ev, int i) { return ev ? mark(ctx, ev[i]) : (int)SFA_OK; }
+// nf host frames [3][h][stride] -> dst: [nf][3][h][w] packed; np host byte planes [h][stride] (decoded masks, raw occlusion images) -> dst: [np][h][w] packed
+int upload_frames(sfa_ctx *ctx, size_t nf, const float *const *frames, int stride, int w, int h, float *dst);
+int upload_masks(sfa_ctx *ctx, size_t np, const unsigned char *const *masks, int stride, int w, int h, unsigned char *dst);
+// np host fields u[k], v[k] of one direction, as src describes them -> np planes of pairs at dst.  identity: the valid columns packed into stage (u, then v
+// np * w * h floats further) and interleaved to float2; else jet_resample_flows to double2, stage and events as there
+int upload_flow_pairs(sfa_ctx *ctx, const sfa_jet_source &src, bool identity, size_t np, const float *const *u, const float *const *v, int w, int h, float *stage,
+                      void *dst, hipEvent_t before, hipEvent_t after);
+// up to six events around a stage's kernels, made only where the caller asks for the times (e[i] stays null otherwise); read: ms[i] = e[i] to e[i + 1]
+struct StageEvents {
+    hipEvent_t e[6] = {};
+    int make(sfa_ctx *ctx, int n) {
+        for (int i = 0; i < n; i++) SFA_HIP(ctx, hipEventCreate(&e[i]));
+        return SFA_OK;
+    }
+    int mark(sfa_ctx *ctx, int i) { return e[i] ? sfa::mark(ctx, e[i]) : (int)SFA_OK; }   // where made
+    int read(sfa_ctx *ctx, int n, float *ms) {
+        for (int i = 0; i + 1 < n; i++) SFA_HIP(ctx, hipEventElapsedTime(&ms[i], e[i], e[i + 1]));
+        return SFA_OK;
+    }
+    ~StageEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+#pragma GCC visibility pop
+
+// ---- dense_tracking's three stages at device level (accumulate.hip, energy.hip, fuse.hip): device pointers and a caller-owned workspace in, launches on the
+// context's stream out; no allocation, no copy, no wait.  The sfa_* entry points wrap them (allocate, upload through stage_io.hip, call, download, wait), the
+// track job (track.hip, track_fill.hip, track_alt.hip) chains them -------------------------------------------------------------------------------------------
 // k_accumulate over n segments of FF steps.  fwd, bwd: [n][FF] planes of float2 (identity) or double2; masks: [n][FF] decoded masks or null;
 // acc_u, acc_v: [n][S][gpl], S = FF (all_steps) or 1; tracked: [n][gpl]
 int accumulate_device(sfa_ctx *ctx, int n, int FF, int w, int h, int gw, int gh, int skip, bool identity, const void *fwd, const void *bwd,
@@ -248,6 +283,24 @@ int energies_device(sfa_ctx *ctx, const EnergyPlan &pl, int n, const double *acc
                     double *adapted_v, size_t adapted_seg);
 // energies_device's last launch alone (k_hyp_adapted), for a caller that provides the adapted planes after the other kernels are enqueued
 int energies_adapted_device(sfa_ctx *ctx, const EnergyPlan &pl, int n, const int *tracked, const EnergyWork &wk, double *adapted_u, double *adapted_v, size_t adapted_seg);
+#pragma GCC visibility push(hidden)
+// What the energy kernels read, for the entry points that bring it from the host (sfa_hypothesis_energies*, sfa_rescore_proposals; the track job keeps
+// the same planes in its own allocation): n segments' frames [n][J + 1][3][pl], derivatives and records, both directions' [n][J] planes of pairs with
+// their stage where flow_src is given (null: no flows; is_identity: what jet_source_check said of it), and energies_device's scratch for work_n segments
+struct EnergyMem {
+    DevMem frames, der, rec, fwd, bwd, stage, U, V, occ, jc, oc, ep;            // fwd.p, bwd.p stay null without flows: what energies_device takes then
+    int segments = 0; bool flows = false, identity = true; sfa_jet_source src{};   // as alloc was called
+    int alloc(sfa_ctx *ctx, const EnergyPlan &e, int n, int work_n, const sfa_jet_source *flow_src, bool is_identity);
+    // the frames at `stride`, energy_records_device, and the four flow arrays where alloc had a flow_src (their planes are allocated here); does not wait
+    int upload(sfa_ctx *ctx, const EnergyPlan &e, const float *const *host_frames, int stride, const float *const *fwd_u, const float *const *fwd_v,
+               const float *const *bwd_u, const float *const *bwd_v);
+    EnergyWork work() const { return EnergyWork{static_cast<double *>(U.p), static_cast<double *>(V.p), static_cast<unsigned long long *>(occ.p), jc.f(), oc.f(), static_cast<double *>(ep.p)}; }
+};
+// What the two refuse alike in the caller's name: flow arrays given in part, a null frame among the nf or a null flow plane among the nj (with_index: the
+// text names the plane's index).  *flows: the arrays are given
+int energy_planes_check(sfa_ctx *ctx, const char *fn, bool with_index, size_t nf, const float *const *frames, size_t nj, const float *const *fwd_u,
+                        const float *const *fwd_v, const float *const *bwd_u, const float *const *bwd_v, bool *flows);
+#pragma GCC visibility pop
 // The fusion's planes for n segments: inputs U, V [n][K][J][gpl], energy, occ [n][K][gpl], weight [n][h][w]; scratch nl [n][gpl], lab [n][gpl][16], theta
 // [n][gpl][16], P [n][2][gpl][K K], M [n][gpl][4][16], xcur, xbest [n][gpl]; outputs slot, fu, fv, out_occ [n][gpl], seg_energy, seg_bound, seg_iters [n]
 struct FuseWork {

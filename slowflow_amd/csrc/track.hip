@@ -4,7 +4,7 @@
 //     -> labels -> pairwise -> TRW-S -> output
 // on the context's stream through the stages' device-level functions (sfa_internal.h) and returns: TRW-S's stopping rule lives inside k_trws, so nothing in
 // the chain needs a host decision, and no stage boundary crosses the host.  The flows are brought into the kernels' layout when they are uploaded (host
-// planes: a copy and the stage wrappers' kernels; device memory: the pack kernels below; occlusion images likewise), so a run reads only what the job holds.
+// planes: stage_io.hip's uploads, the stage wrappers' own; device memory: the pack kernels below; occlusion images likewise), so a run reads only what the job holds.
 // Segment s of a run comes out with the bits of the staged calls on that segment alone: the same kernels over the same planes, blockIdx.y = s.
 // The device entry points describe their arguments as views and leave every check of them to check_view / check_disjoint (api.hip on dev_view.h).
 // The job and its plane table are track_job.h's; what a fill job adds between the accumulation and the energies is track_fill.hip.
@@ -237,24 +237,6 @@ void sfa_track_params_default(sfa_track_params *p) {
     for (int r = 0; r < kTrMaxK; r++) { p->r_Jets[r] = 1; p->weight[r] = (float)r; }   // weight_jet_estimation[r] = r where none is given
 }
 
-int sfa::copy_on(sfa_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
-    SFA_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
-    return SFA_OK;
-}
-int sfa::zero_on(sfa_ctx *ctx, void *dst, size_t bytes) {
-    SFA_HIP(ctx, hipMemsetAsync(dst, 0, bytes, ctx->stream));
-    return SFA_OK;
-}
-int sfa::mark(sfa_ctx *ctx, hipEvent_t e) {
-    SFA_HIP(ctx, hipEventRecord(e, ctx->stream));
-    return SFA_OK;
-}
-int sfa::copy_rows_on(sfa_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t row, size_t h, hipMemcpyKind kind) {
-    SFA_HIP(ctx, hipMemcpy2DAsync(dst, dpitch, src, spitch, row, h, kind, ctx->stream));
-    return SFA_OK;
-}
-int sfa::download(sfa_ctx *ctx, void *dst, const void *src, size_t bytes) { return dst ? copy_on(ctx, dst, src, bytes, hipMemcpyDeviceToHost) : (int)SFA_OK; }
-
 // with_fill: the call is a fill job's, and a null fill is refused under its name
 int sfa::track_bytes(const char *fn, const sfa_track_params *p, const sfa_track_fill_params *fill, bool with_fill, const sfa_track_alt_params *alt, bool with_alt,
                      size_t *bytes) {
@@ -346,21 +328,8 @@ int sfa_track_job_upload_flows(sfa_track_job *job, int s, int r, const float *co
     const size_t tap = identity ? sizeof(float2) : sizeof(double2), seg = (size_t)s * rJ * pl;
     SFA_HIP(ctx, hipSetDevice(ctx->device));
     float *stage = job->ptr(job->at.stage);
-    for (int dir = 0; dir < 2; dir++) {
-        const float *const *U = dir ? bwd_u : fwd_u, *const *V = dir ? bwd_v : fwd_v;
-        char *dst = job->ptr(dir ? a.bw : a.fw) + seg * tap;
-        if (!identity) {
-            SFA_TRY(jet_resample_flows(ctx, src, (size_t)rJ, U, V, p.w, p.h, stage, reinterpret_cast<double2 *>(dst), nullptr, nullptr));
-            continue;
-        }
-        float *su = stage, *sv = stage + (size_t)rJ * pl;
-        for (int k = 0; k < rJ; k++) {                                          // the valid columns of each plane, packed, then interleaved
-            SFA_TRY(copy_rows_on(ctx, su + k * pl, (size_t)p.w * 4, U[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice));
-            SFA_TRY(copy_rows_on(ctx, sv + k * pl, (size_t)p.w * 4, V[k], (size_t)src.stride * 4, (size_t)p.w * 4, p.h, hipMemcpyHostToDevice));
-        }
-        launch_interleave(ctx, su, sv, reinterpret_cast<float2 *>(dst), (size_t)rJ * pl);
-        SFA_HIP(ctx, hipGetLastError());
-    }
+    SFA_TRY(upload_flow_pairs(ctx, src, identity, (size_t)rJ, fwd_u, fwd_v, p.w, p.h, stage, job->ptr(a.fw) + seg * tap, nullptr, nullptr));
+    SFA_TRY(upload_flow_pairs(ctx, src, identity, (size_t)rJ, bwd_u, bwd_v, p.w, p.h, stage, job->ptr(a.bw) + seg * tap, nullptr, nullptr));
     if (p.use_occlusions) SFA_TRY(jet_decode_occlusions(ctx, src, (size_t)rJ, occ, p.w, p.h, job->ptr(job->at.occ_stage), job->ptr(a.mask) + seg));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // the caller's planes are free again
     return SFA_OK;
@@ -374,11 +343,7 @@ int sfa_track_job_upload_frames(sfa_track_job *job, int s, const float *const *f
     for (int k = 0; k <= p.Jets; k++)
         if (!frames[k]) REFUSE("%s: null frame %d", __func__, k);
     SFA_HIP(ctx, hipSetDevice(ctx->device));
-    float *dst = job->ptr(job->at.frames) + (size_t)s * (p.Jets + 1) * 3 * pl;
-    for (int k = 0; k <= p.Jets; k++)
-        for (int c = 0; c < 3; c++)
-            SFA_TRY(copy_rows_on(ctx, dst + ((size_t)k * 3 + c) * pl, (size_t)p.w * 4, frames[k] + (size_t)c * p.h * stride, (size_t)stride * 4, (size_t)p.w * 4, p.h,
-                                 hipMemcpyHostToDevice));
+    SFA_TRY(upload_frames(ctx, (size_t)p.Jets + 1, frames, stride, p.w, p.h, job->ptr(job->at.frames) + (size_t)s * (p.Jets + 1) * 3 * pl));
     SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SFA_OK;
 }
@@ -483,10 +448,7 @@ static int run_accumulation(sfa_track_job *job, int ns) {
 
 EnergyWork sfa::energy_work(const sfa_track_job *job) {
     const TrackPlanes &at = job->at;
-    EnergyWork wk;
-    wk.U = job->ptr(at.wU); wk.V = job->ptr(at.wV); wk.occ = job->ptr(at.wocc);
-    wk.jc = job->ptr(at.jc); wk.oc = job->ptr(at.oc); wk.ep = job->ptr(at.ep);
-    return wk;
+    return EnergyWork{job->ptr(at.wU), job->ptr(at.wV), job->ptr(at.wocc), job->ptr(at.jc), job->ptr(at.oc), job->ptr(at.ep)};
 }
 
 // The energies, occlusion words and adapted flows of one hypothesis of rate r -- the trajectories u, v [ns][r_Jets[r]][gpl] and tracked -- into slot `slot` of

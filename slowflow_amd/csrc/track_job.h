@@ -1,5 +1,5 @@
 // track_job.h -- what the two halves of the resident track job share: track.hip (the kernels, the job, its uploads, run and downloads) and track_fill.hip (a fill
-// job's checks, planes, fill-in stage and entry points).  The plane table, the job and a fill job's state, the entry points' preamble, one-line stream calls.
+// job's checks, planes, fill-in stage and entry points).  The plane table, the job and a fill job's state, the entry points' preamble (stream calls: stage_io.hip).
 #pragma once
 #include <memory>
 
@@ -132,14 +132,6 @@ namespace sfa {
     (void)pl; (void)gpl
 
 int track_range(sfa_ctx *ctx, const char *fn, const sfa_track_params &p, int s0, int ns, int r);
-
-// one-line forms of the stream calls the job makes many of (track.hip); download: a result to the host, or nothing where the caller passes no dst
-int copy_on(sfa_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
-int zero_on(sfa_ctx *ctx, void *dst, size_t bytes);
-int mark(sfa_ctx *ctx, hipEvent_t e);
-int download(sfa_ctx *ctx, void *dst, const void *src, size_t bytes);
-// h rows of `row` bytes, the rows dpitch and spitch bytes apart
-int copy_rows_on(sfa_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t row, size_t h, hipMemcpyKind kind);
 
 // k_track_pack_frames (track.hip) with one frame: nc <= 3 channel planes of w x h in device memory, element (channel, row, column) at src + the element strides
 // -> out: [nc][h][w] packed.  How a fill job packs its Lab images and edge maps

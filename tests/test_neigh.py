@@ -523,3 +523,34 @@ def test_gpu_rounds_as_stage_calls(ctx, oracle):
         if rnd == 0:
             assert (~(l["energy"] < np.inf).any(0)).any() and (gf["slot"][0] >= 0).all()
         gsel, rsel = gf["slot"], rf["slot"]
+
+
+@pytest.mark.gpu
+def test_gpu_rescore_nan_in_the_stride_padding_changes_nothing(ctx):
+    """frames and flows at a row stride of w + 3: the columns past w are never read.  The smallest shape the kernels take (h >= 4), odd width and stride
+    so that no alignment hides a wrong pitch; the proposals are named by hand, a handful over four positions"""
+    import energy_ref as er
+    import slowflow_amd as sfa
+    J, skip, w, h = 2, 1, 13, 9
+    stride = w + 3
+    gw, gh = sfa.accumulate_grid(w, h, skip)
+    l = make_lists(61, gw, gh, J=J, pruned=True)
+    l["U"], l["V"] = l["U"] / 2, l["V"] / 2
+    pix = np.full((1, K16, gh, gw), -1, np.int32)
+    for k, y, x in [(0, 0, 0), (1, 1, 2), (1, 3, 5), (2, 2, 1), (3, 0, 4), (3, 3, 3)]:
+        pix[0, k, y, x] = (gh - 1 - y) * gw + x                                 # any source pixel: the rescoring asks only whether there is one
+    new = pix[0] >= 0
+    rng = np.random.default_rng(7)
+    valid_frames = rng.normal(0, 1, (1, J + 1, 3, h, w))
+    valid_flows = rng.normal(0, 1.5, (4, 1, J, h, w))
+    out = []
+    for pad in (0.0, np.nan):
+        frames = np.full((1, J + 1, 3, h, stride), pad, np.float32)
+        frames[..., :w] = valid_frames
+        flows = [np.full((1, J, h, stride), pad, np.float32) for _ in range(4)]
+        for a, v in zip(flows, valid_flows):
+            a[..., :w] = v
+        out.append(ctx.rescore_proposals(er.Params(skip=skip).to_c(sfa), batch(l), pix, frames, w, flows, SLOT_WEIGHT))
+    zero, nan = out
+    assert np.isfinite(zero["energy"][0][new]).all() and not np.array_equal(zero["energy"][0][new], l["energy"][new])   # they were scored
+    assert np.array_equal(zero["energy"].view(np.uint64), nan["energy"].view(np.uint64)) and np.array_equal(zero["occ"], nan["occ"])

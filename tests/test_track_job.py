@@ -166,3 +166,33 @@ def test_refusals_name_their_argument(ctx, segments):
     with pytest.raises(sfa.SlowflowError, match="s = 3"):
         job.upload_flows(3, 0, *seg["flows"][0])
     job.close()
+
+
+def test_nan_in_the_stride_padding_changes_nothing(ctx):
+    """the host uploads at a row stride of w + 3: a plain job (K = 1, fused) fed zero padding and NaN padding gives the same rate and fused results.
+    The smallest shape the kernels take (h >= 4), odd width and stride so that no alignment hides a wrong pitch"""
+    J, w, h = 2, 13, 9
+    stride = w + 3
+    rng = np.random.default_rng(3)
+    valid_frames = rng.normal(0, 1, (J + 1, 3, h, w))
+    drift = np.array([0.5, 0.25]).reshape(2, 1, 1, 1) + rng.normal(0, 0.01, (2, J, h, w))   # forward; backward = -forward: consistent within epsilon
+    p = sfa.track_params(w, h, J, [J], sources=[sfa.jet_source(w, h, stride)], fuse=sfa.fuse_params(trws_max_iter=4), skip=1, epsilon=ti.EPSILON)
+    job = sfa.TrackJob(ctx, p)
+    out = []
+    for pad in (0.0, np.nan):
+        frames = np.full((J + 1, 3, h, stride), pad, np.float32)
+        frames[..., :w] = valid_frames
+        flows = [np.full((J, h, stride), pad, np.float32) for _ in range(4)]
+        for a, v in zip(flows, (drift[0], drift[1], -drift[0], -drift[1])):
+            a[..., :w] = v
+        job.upload_flows(0, 0, *flows)
+        job.upload_frames(0, frames)
+        job.run(1)
+        out.append((job.download_rate(0, 0), job.download_fused(0)))
+    job.close()
+    (rate0, fused0), (rate1, fused1) = out
+    assert (rate0["tracked"] == J).any() and np.isfinite(rate0["energy"][rate0["tracked"] == J]).all()   # there are hypotheses, and they were scored
+    for got, want in ((rate1, rate0), (fused1, fused0)):
+        assert got.keys() == want.keys()
+        for k in want:
+            assert same(got[k], want[k]), k

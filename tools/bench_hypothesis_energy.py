@@ -24,7 +24,7 @@ import slowflow_amd as sfa  # noqa: E402
 
 W, H, SKIP = 1024, 436, 1
 CONFIGS = [(J, rates) for J in (4, 8, 16, 32) for rates in (1, 2)]
-KERNELS = ("k_energy_interleave", "k_convolve", "k_energy_records", "k_hyp_serial", "k_hyp_bcgc", "k_hyp_sum")
+KERNELS = ("k_interleave", "k_convolve", "k_energy_records", "k_hyp_serial", "k_hyp_bcgc", "k_hyp_sum")
 
 
 def inputs(J, rJ, rng):
