@@ -573,6 +573,14 @@ int  sfa_track_job_upload_fill(sfa_track_job *job, int s, const float *lab, int 
  * its capacity", or in lists the reference does not define). */
 int  sfa_track_job_upload_fill_device(sfa_track_job *job, int s0, int ns, const float *lab_dev, const long long lab_strides[4], const float *edges_dev,
                                       const long long edge_strides[3]);
+/* The same two uploads from frame 0 itself (dense_tracking.cpp:931-955): rgb = the frame as read, before the normalisation, at the FRAMES' size -- 3
+ * planes of h rows of `stride` floats (rgb_dev: fp32 [ns][3][h][w] at strides[4]) -- and norm as sfa_reference_lab_device takes it.  The Lab image at the
+ * grid's size is formed in GPU memory by that stage's kernel, straight into the job's plane; nothing of it passes through the host.  Refused beside what
+ * the forms above refuse: a job whose skip the stage does not serve, a size OpenCV's resize rounds to another grid (sfa_reference_grid), a NaN norm.  The
+ * edge-cost checks are those of the forms above.  The host form keeps a device copy of one frame (3 w h floats) beside the job's allocation. */
+int  sfa_track_job_upload_fill_reference(sfa_track_job *job, int s, const float *rgb, int stride, float norm, const float *edges);
+int  sfa_track_job_upload_fill_reference_device(sfa_track_job *job, int s0, int ns, const float *rgb_dev, const long long strides[4], float norm,
+                                                const float *edges_dev, const long long edge_strides[3]);
 /* Rate r's fill-in of segment s after a run: the trajectories fill_u, fill_v [r_Jets[r]][gh][gw] (0 where not filled), energy and occ_bits [gh][gw] (slot
  * 2 r + 1), stats[3] = {kept_pixels, matches, filled}.  NULL skips an output.  Waits for the run. */
 int  sfa_track_job_download_fill(sfa_track_job *job, int s, int r, double *fill_u, double *fill_v, double *energy, unsigned long long *occ_bits, int *stats);
@@ -836,7 +844,29 @@ int  sfa_sequence_rescale(sfa_sequence *dst_seq, int f_dst, sfa_sequence *src_se
  * memory, a destination that overlaps the source. */
 int  sfa_rgb8_to_lab_device(sfa_ctx *ctx, int n, int w, int h, const float *rgb_dev, const long long rgb_strides[4], float norm, float *lab_dev,
                             const long long lab_strides[4]);
-/* The same kernel between two resident sequences of one size and one context: src_seq's frames [f_src, f_src + n) -> dst_seq's [f_dst, f_dst + n).  The
+/* ---- dense_tracking's reduced reference image (dense_tracking.cpp:931-955; csrc/ref_image.hip, csrc/ref_image.h) --------------------------------
+ * With acc_skip_pixel > 0 the reference converts frame 0 to 8 bits, blurs it with OpenCV's 8-bit GaussianBlur (sigma = 1 / sqrt(2 / (skip + 1))) and
+ * reduces it with resize(INTER_LINEAR) to the accumulation grid; EpicFlow's Lab image (:947-955) and the file its edge detector reads
+ * (tmp/frame_epic_<start>.png, :944, 960) come from that image.  OpenCV is not in this tree: INTEGRATION.md 4c' defines the stage's integer arithmetic,
+ * restated from OpenCV 2.4's x86-64 source, and the stage is PARITY-UNPINNED against OpenCV itself.  Served: skip 0 (the 8-bit step
+ * alone: sfa_rgb8_to_lab_device bit for bit), 1 (7 taps) and 3 (9 taps); every other skip is refused by name.
+ * sfa_reference_grid (dense_tracking.cpp:931-955; host only): the grid of sfa_accumulate_grid, refused with SFA_ERR_ARG where skip is not served or
+ * where OpenCV's own size, cvRound(w / (skip + 1)) x cvRound(h / (skip + 1)) with ties to even, is another (w = 7 at skip 1).
+ * sfa_reference_taps (dense_tracking.cpp:931-955; host only): the blur's taps in 8 fractional bits, *n of them (at most 9; skip 0: none); taps may
+ * be NULL. */
+int  sfa_reference_grid(int w, int h, int skip, int *gw, int *gh);
+int  sfa_reference_taps(int skip, int *taps, int *n);
+/* dense_tracking.cpp:931-955 for n frames in GPU memory: rgb_dev fp32 [n][3][h][w] at rgb_strides[4] (the samples as read; norm 1/255 for 16-bit
+ * input, else 1) -> lab_dev fp32 [n][3][gh][gw] at lab_strides[4] and, where rgb8_dev is not NULL, the reduced 8-bit RGB image [n][3][gh][gw] at
+ * rgb8_strides[4] (in bytes).  One kernel from the samples to the Lab planes, no plane in memory in between; asynchronous on the context's stream.  A
+ * NaN sample counts as 0 where skip > 0.  Refused with SFA_ERR_ARG, the argument named, nothing launched: what sfa_reference_grid refuses, n < 1, a NaN
+ * norm, every pointer or view the device seam refuses, destinations whose strides let two elements share memory, views that overlap. */
+int  sfa_reference_lab_device(sfa_ctx *ctx, int n, int w, int h, int skip, const float *rgb_dev, const long long rgb_strides[4], float norm, float *lab_dev,
+                              const long long lab_strides[4], unsigned char *rgb8_dev, const long long rgb8_strides[4]);
+/* dense_tracking.cpp:931-955 for one frame in host memory: rgb = 3 planes of h rows of `stride` floats -> lab = 3 planes of gh rows of lab_stride floats
+ * and, where not NULL, rgb8 = [3][gh][gw] bytes.  Allocates, uploads, launches, downloads and waits. */
+int  sfa_reference_lab(sfa_ctx *ctx, int w, int h, int skip, const float *rgb, int stride, float norm, float *lab, int lab_stride, unsigned char *rgb8);
+/* sfa_rgb8_to_lab_device's kernel between two resident sequences of one size and one context: src_seq's frames [f_src, f_src + n) -> dst_seq's [f_dst, f_dst + n).  The
  * source frames must still hold the samples as they were read: the caller orders this call before sfa_sequence_apply_normalization.  src_seq == dst_seq
  * is taken where the two frame ranges lie apart. */
 int  sfa_sequence_lab(sfa_sequence *dst_seq, int f_dst, sfa_sequence *src_seq, int f_src, int n, float norm);

@@ -269,9 +269,10 @@ EXPORTS = [
     "sfa_dev_layout_default", "sfa_job_upload_device", "sfa_job_set_flow_device", "sfa_job_download_device", "sfa_job_changes", "sfa_pair_job_upload_device", "sfa_pair_job_set_flow_device", "sfa_pair_job_download_device", "sfa_sequence_upload_device", "sfa_ctx_wait_stream", "sfa_ctx_signal_stream",
     "sfa_demosaic_device", "sfa_sequence_upload_mosaic_device", "sfa_sequence_upload_mosaic", "sfa_job_set_raw_weights", "sfa_sequence_rescale",
     "sfa_rgb8_to_lab_device", "sfa_sequence_lab", "sfa_epic_job_create", "sfa_epic_job_destroy", "sfa_epic_job_upload", "sfa_epic_job_set_lab", "sfa_epic_job_upload_device", "sfa_epic_job_set_matches_device", "sfa_epic_job_run", "sfa_epic_job_download", "sfa_epic_job_upload_flow", "sfa_epic_job_download_device", "sfa_job_set_flow_epic",
+    "sfa_reference_grid", "sfa_reference_taps", "sfa_reference_lab_device", "sfa_reference_lab",
     "sfa_sor_batch_create", "sfa_sor_batch_destroy", "sfa_sor_batch_upload", "sfa_sor_batch_run", "sfa_sor_batch_download",
     "sfa_track_params_default", "sfa_track_job_bytes", "sfa_track_job_create", "sfa_track_job_destroy", "sfa_track_job_upload_flows", "sfa_track_job_upload_frames", "sfa_track_job_upload_flows_device", "sfa_track_job_upload_frames_device", "sfa_track_job_run", "sfa_track_job_download_rate", "sfa_track_job_download_fused", "sfa_track_job_download_best", "sfa_ctx_free_bytes", "sfa_track_job_download_device", "sfa_track_job_stage_ms", "sfa_track_job_upload_occlusions_device", "sfa_track_job_download_rate_device", "sfa_track_job_download_best_device",
-    "sfa_track_fill_params_default", "sfa_track_job_bytes_fill", "sfa_track_job_create_fill", "sfa_track_job_upload_fill", "sfa_track_job_upload_fill_device", "sfa_track_job_download_fill", "sfa_track_job_fill_ms", "sfa_track_job_fill_info",
+    "sfa_track_fill_params_default", "sfa_track_job_bytes_fill", "sfa_track_job_create_fill", "sfa_track_job_upload_fill", "sfa_track_job_upload_fill_device", "sfa_track_job_upload_fill_reference", "sfa_track_job_upload_fill_reference_device", "sfa_track_job_download_fill", "sfa_track_job_fill_ms", "sfa_track_job_fill_info",
     "sfa_track_alt_params_default", "sfa_track_job_bytes_alternate", "sfa_track_job_create_alternate", "sfa_track_job_set_sequence_starts", "sfa_track_job_download_alternation",
     "sfa_division_chain", "sfa_ctx_set_wait_bound", "sfa_debug_set", "sfa_ctx_set_verbose", "sfa_profile_enable", "sfa_profile_read", "sfa_profile_read_kernels", "sfa_timer_start", "sfa_timer_stop",
 ]
@@ -351,6 +352,27 @@ def fill_samples(extent, epic_skip):
     if rc != 0:
         raise SlowflowError("sfa_fill_samples(%d, %r): %s" % (extent, epic_skip, L.sfa_last_error(None).decode()))
     return out[:c.value].copy()
+
+
+def reference_grid(w, h, skip):
+    """the grid of dense_tracking's reduced reference image (sfa_reference_grid; host only, no GPU): accumulate_grid's (gw, gh), refused where skip is not
+    served (0, 1 and 3 are) or where OpenCV's resize would round the size to another grid"""
+    L = lib()
+    L.sfa_reference_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    gw, gh = C.c_int(), C.c_int()
+    if L.sfa_reference_grid(int(w), int(h), int(skip), C.byref(gw), C.byref(gh)) != 0:
+        raise SlowflowError("sfa_reference_grid(%d, %d, %d): %s" % (w, h, skip, L.sfa_last_error(None).decode()))
+    return gw.value, gh.value
+
+
+def reference_taps(skip):
+    """the taps of the reference image's 8-bit Gaussian blur in 8 fractional bits (sfa_reference_taps; host only, no GPU) as an int32 array; skip 0: none"""
+    L = lib()
+    L.sfa_reference_taps.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    out, n = np.zeros(16, np.int32), C.c_int()
+    if L.sfa_reference_taps(int(skip), out.ctypes.data, C.byref(n)) != 0:
+        raise SlowflowError("sfa_reference_taps(%d): %s" % (skip, L.sfa_last_error(None).decode()))
+    return out[:n.value].copy()
 
 
 def default_params():
@@ -790,6 +812,20 @@ class Context:
         self._ck(L.sfa_epic_saliency_batch(self.h, n, w, h, (_f * k)(*[fptr(a) for a in labs]), stride, float(sigma_image), float(sigma_matrix),
                                            (_f * k)(*[fptr(a) for a in out])), "sfa_epic_saliency_batch")
         return out
+
+    def reference_lab(self, rgb, skip, norm=1.0, return_rgb8=False):
+        """dense_tracking's reduced reference image of one frame (sfa_reference_lab; dense_tracking.cpp:931-955): rgb fp32 (3, h, w) as read -> the Lab image
+        fp32 (3, gh, gw) on the grid of reference_grid(w, h, skip); with return_rgb8 also the reduced 8-bit RGB image uint8 (3, gh, gw)"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        assert rgb.ndim == 3 and rgb.shape[0] == 3, "rgb is (3, h, w)"
+        _, h, w = rgb.shape
+        gw, gh = reference_grid(w, h, skip)
+        lab = np.zeros((3, gh, gw), np.float32)
+        rgb8 = np.zeros((3, gh, gw), np.uint8) if return_rgb8 else None
+        L = lib()
+        L.sfa_reference_lab.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _f, C.c_int, C.c_float, _f, C.c_int, C.c_void_p]
+        self._ck(L.sfa_reference_lab(self.h, w, h, int(skip), fptr(rgb), w, float(norm), fptr(lab), gw, rgb8.ctypes.data if return_rgb8 else None), "sfa_reference_lab")
+        return (lab, rgb8) if return_rgb8 else lab
 
     def epic_batch_stage_ms(self):
         """the kernel milliseconds of the last epic_batch by stage (sfa_epic_batch_stage_ms)"""
@@ -1535,6 +1571,21 @@ class TrackJob:
             stride = lab.shape[2]
         self.ctx._ck(lib().sfa_track_job_upload_fill(self.h_, int(s), fptr(lab) if lab is not None else None, stride, fptr(edges)), "sfa_track_job_upload_fill")
 
+    def upload_fill_reference(self, s, rgb, edges, norm=1.0):
+        """segment s of a fill job from frame 0 itself: rgb = the frame as read, before the normalisation, fp32 (3, h, stride) at the FRAMES' size (None where
+        epic.saliency_th == 0); its Lab image at the grid's size is formed on the GPU (Context.reference_lab's kernel).  edges as upload_fill takes them"""
+        edges = np.ascontiguousarray(edges, dtype=np.float32)
+        assert edges.shape == (self.gh, self.gw), "edges are (gh, gw)"
+        stride = 0
+        if rgb is not None:
+            rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+            assert rgb.ndim == 3 and rgb.shape[:2] == (3, self.h), "rgb is (3, h, stride)"
+            stride = rgb.shape[2]
+        L = lib()
+        L.sfa_track_job_upload_fill_reference.argtypes = [C.c_void_p, C.c_int, _f, C.c_int, C.c_float, _f]
+        self.ctx._ck(L.sfa_track_job_upload_fill_reference(self.h_, int(s), fptr(rgb) if rgb is not None else None, stride, float(norm), fptr(edges)),
+                     "sfa_track_job_upload_fill_reference")
+
     def download_fill(self, s, r):
         """rate r's fill-in of segment s: a dict of u, v float64 (r_Jets[r], gh, gw), energy float64 and occ_bits uint64 (gh, gw) (slot 2 r + 1), and the
         ints kept_pixels, matches, filled"""
@@ -1565,6 +1616,12 @@ class TrackJob:
         """lab: fp32 [ns, 3, gh, gw] (None where epic.saliency_th == 0), edges: fp32 [ns, gh, gw] in device memory (any strides) -> segments s0 .."""
         from . import device
         device.track_job_upload_fill_device(self, lab, edges, s0)
+
+    def upload_fill_reference_device(self, rgb, edges, norm=1.0, s0=0):
+        """rgb: fp32 [ns, 3, h, w], frame 0 of each start_jet as read (None where epic.saliency_th == 0), edges: fp32 [ns, gh, gw] in device memory (any
+        strides) -> segments s0 ..; the Lab images are formed on the grid in GPU memory"""
+        from . import device
+        device.track_job_upload_fill_reference_device(self, rgb, edges, norm, s0)
 
     def upload_flows_device(self, r, fwd, bwd, s0=0):
         """fwd, bwd: fp32 [ns, r_Jets[r], 2, sh, sw] in device memory (any strides) -> rate r of segments s0 .. s0 + ns - 1"""

@@ -88,13 +88,15 @@ SFA_LAB_FN double exp_neg(double z) {
     return tab[n][0] + (tab[n][1] + tab[n][0] * p);
 }
 
+// a sample as the 8-bit copy holds it (epic.cpp:22-23): times norm, cvRound (to nearest, ties to even), saturate_cast<uchar>; NaN stays NaN
+SFA_LAB_FN float sample_8bit(float s, float norm) {
+    const float v = round_even(s * norm);
+    return v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+}
+
 // One pixel of rgb8_to_lab(rgb, norm): (r, g, b) as the frame holds them -> L, a c, b c with c the colour attenuation of dark and light areas.
 SFA_LAB_FN void rgb8_to_lab_pixel(float r_in, float g_in, float b_in, float norm, float *out_L, float *out_a, float *out_b) {
-    float c8[3] = {r_in, g_in, b_in};
-    for (int k = 0; k < 3; k++) {                                      // epic.cpp:22-23
-        const float v = round_even(c8[k] * norm);                      // cvRound: to nearest, ties to even
-        c8[k] = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);           // saturate_cast<uchar>
-    }
+    const float c8[3] = {sample_8bit(r_in, norm), sample_8bit(g_in, norm), sample_8bit(b_in, norm)};
     const float T = 0.008856;                                          // :55-73, the statements in their order
     const float color_attenuation = 1.5f;
     const float r = c8[0] / 255.f, g = c8[1] / 255.f, b = c8[2] / 255.f;

@@ -619,6 +619,16 @@ void launch_rgb8_to_lab(sfa_ctx *c, const LabSrc &src, const LabDst &dst, int n,
 void launch_epic_initial_flow(sfa_ctx *c, float *dst, long dst_es, long pl, int pitch, int w, int h, int nwin, const float *src_u, const float *src_v, long src_es,
                               int sw, int sh, float mul_u, float mul_v);
 
+// ---- ref_image.hip: dense_tracking's reduced reference image (sfa_reference_lab_device, sfa_track_job_upload_fill_reference*) ---------------------------
+// n 8-bit images, element (image, channel, row, column) at p + the strides; p null: not wanted
+struct Rgb8Dst { unsigned char *p; long long sn, sc, sr, sx; };
+// what the stage refuses of a size and a skip, in the name of `fn`: a skip that is not served (csrc/ref_image.h), an empty grid, a size OpenCV's resize
+// rounds to another grid.  *gw, *gh: the accumulation grid
+__attribute__((visibility("hidden"))) int reference_check(sfa_ctx *ctx, const char *fn, int w, int h, int skip, int *gw, int *gh);
+// n frames of w x h as read -> their Lab images (and 8-bit RGB images) on the grid of a size and skip reference_check passed.  skip 0: k_rgb8_to_lab
+__attribute__((visibility("hidden"))) void launch_reference_lab(sfa_ctx *c, int n, int w, int h, int skip, const LabSrc &src, float norm, const LabDst &dst,
+                                                                const Rgb8Dst &rgb8);
+
 }  // namespace sfa
 
 // ---- sfa_epic_job: the inputs and fields of epic() for n images of one size, resident (epic_init.hip) ----

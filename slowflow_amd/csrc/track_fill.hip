@@ -248,6 +248,56 @@ int sfa_track_job_upload_fill_device(sfa_track_job *job, int s0, int ns, const f
     return SFA_OK;
 }
 
+// frame 0 of one start_jet, in device memory at the frames' size, -> its Lab image on the grid in the saliency's workspace -> segment s's saliency
+static int track_reference_saliency(sfa_track_job *job, int s, const LabSrc &src, float norm) {
+    const FillGeo &g = job->fill->g;
+    launch_reference_lab(job->ctx, 1, job->p.w, job->p.h, job->p.skip, src, norm, LabDst{job->ptr(job->at.lab_stage), 0, (long long)g.plp, g.pitch, 1},
+                         Rgb8Dst{nullptr, 0, 0, 0, 0});
+    SFA_HIP(job->ctx, hipGetLastError());
+    return track_saliency(job, s);
+}
+
+int sfa_track_job_upload_fill_reference(sfa_track_job *job, int s, const float *rgb, int stride, float norm, const float *edges) {
+    FILL_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s, 1, 0));
+    if (!edges) REFUSE("%s: edges is null", __func__);
+    if (saliency && !rgb) REFUSE("%s: rgb is null (epic.saliency_th != 0: the saliency filter reads the Lab image)", __func__);
+    if (saliency && stride < p.w) REFUSE("%s: stride = %d < w = %d", __func__, stride, p.w);
+    if (!(norm == norm)) REFUSE("%s: norm is NaN", __func__);
+    int gw = 0, gh = 0;
+    SFA_TRY(reference_check(ctx, __func__, p.w, p.h, p.skip, &gw, &gh));
+    SFA_TRY(epic_check_costs(ctx, __func__, "edges of start_jet %d", s, edges, job->gw, job->gh));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    if (saliency) {
+        DevMem &stage = job->fill->ref_stage;                                   // the frame as read: made by the first call, gone with the job
+        if (!stage.p) SFA_TRY(stage.alloc(ctx, 3 * pl * sizeof(float)));
+        for (int c = 0; c < 3; c++) SFA_TRY(upload_plane(ctx, stage.f() + c * pl, p.w, rgb + (size_t)c * p.h * stride, stride, p.w, p.h));
+        SFA_TRY(track_reference_saliency(job, s, LabSrc{stage.f(), 0, (long long)pl, p.w, 1}, norm));
+    }
+    SFA_TRY(copy_on(ctx, job->ptr(job->at.edges) + (size_t)s * g.cpl, edges, gpl * sizeof(float), hipMemcpyHostToDevice));
+    SFA_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // the caller's planes are free again
+    return SFA_OK;
+}
+
+int sfa_track_job_upload_fill_reference_device(sfa_track_job *job, int s0, int ns, const float *rgb_dev, const long long strides[4], float norm,
+                                               const float *edges_dev, const long long edge_strides[3]) {
+    FILL_JOB(job);
+    SFA_TRY(track_range(ctx, __func__, p, s0, ns, 0));
+    if (!(norm == norm)) REFUSE("%s: norm is NaN", __func__);
+    int gw = 0, gh = 0;
+    SFA_TRY(reference_check(ctx, __func__, p.w, p.h, p.skip, &gw, &gh));
+    if (saliency) SFA_TRY(check_view(ctx, __func__, View{"rgb_dev", rgb_dev, sizeof(float), 4, {ns, 3, p.h, p.w}, strides}, 0));
+    SFA_TRY(check_view(ctx, __func__, View{"edges_dev", edges_dev, sizeof(float), 3, {ns, job->gh, job->gw}, edge_strides}));
+    SFA_HIP(ctx, hipSetDevice(ctx->device));
+    for (int s = 0; saliency && s < ns; s++)                                    // segment by segment through the one workspace, in stream order
+        SFA_TRY(track_reference_saliency(job, s0 + s, LabSrc{rgb_dev + (long long)s * strides[0], 0, strides[1], strides[2], strides[3]}, norm));
+    // (the edge planes' domain is the caller's to guarantee, as in sfa_track_job_upload_fill_device)
+    for (int s = 0; s < ns; s++)
+        SFA_TRY(pack_strided_planes(ctx, edges_dev + (long long)s * edge_strides[0], 0, edge_strides[1], edge_strides[2], job->gw, job->gh, 1,
+                                    job->ptr(job->at.edges) + (size_t)(s0 + s) * g.cpl));
+    return SFA_OK;
+}
+
 int sfa_track_job_download_fill(sfa_track_job *job, int s, int r, double *fill_u, double *fill_v, double *energy, unsigned long long *occ_bits, int *stats) {
     FILL_JOB(job);
     SFA_TRY(track_range(ctx, __func__, p, s, 1, r));

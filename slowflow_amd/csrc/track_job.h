@@ -84,6 +84,7 @@ struct TrackFill {
     HostArray<float *> fx, fy;
     HostArray<int> nm, seg_of, step_of, rc, status;
     HostArray<int> kept, count;                 // [n]: the host's copy of the planes kept and count
+    DevMem ref_stage;                           // sfa_track_job_upload_fill_reference: frame 0 as read, 3 w h floats beside the job's allocation, made by its first call
     int chain_runs[2] = {};                     // the last run's interpolation sub-batches over all rates: completed, cut short and run again
     hipEvent_t ev[kTrackMaxRates][kFillEvents] = {};
     hipEvent_t ev_energy = nullptr;             // after the last rate's fill-in, where the energies begin

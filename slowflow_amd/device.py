@@ -159,6 +159,8 @@ def _lib():
         L.sfa_flow_magnitude_quantiles_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                           C.c_float, C.c_float, C.c_void_p]
         L.sfa_rgb8_to_lab_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.sfa_reference_lab_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sfa_track_job_upload_fill_reference_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         L.sfa_epic_job_upload_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.sfa_epic_job_set_matches_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.sfa_epic_job_download_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -313,6 +315,30 @@ def rgb8_to_lab(ctx, rgb, norm=1.0, *, stream=None, out=None):
         ctx._ck(_lib().sfa_rgb8_to_lab_device(ctx.h, n, w, h, C.c_void_p(v.ptr), _LL4(*v.strides), float(norm), C.c_void_p(ov.ptr), _LL4(*ov.strides)),
                 "sfa_rgb8_to_lab_device")
     return res
+
+
+def reference_lab(ctx, rgb, skip, norm=1.0, *, return_rgb8=False, stream=None, out=None, out_rgb8=None):
+    """dense_tracking's reduced reference image (dense_tracking.cpp:931-955; csrc/ref_image.hip) of n frames that live on the context's GPU: rgb = a torch
+    fp32 tensor [n,3,h,w] of any strides holding the samples as they were read; 8 bits, OpenCV's 8-bit Gaussian blur and its bilinear reduction to the grid
+    of sfa.reference_grid(w, h, skip), then the Lab image, in one kernel.  Returns a new fp32 tensor [n,3,gh,gw] (or fills `out`); with return_rgb8 (or
+    out_rgb8) also the reduced 8-bit RGB image, uint8 [n,3,gh,gw], the edge detector's input.  skip 0 is rgb8_to_lab.  Stream order as rgb8_to_lab."""
+    import torch
+    v = device_view(rgb, name="rgb", kinds=("f4",), shape=("n", 3, None, None))
+    n, _, h, w = v.shape
+    gw, gh = sfa.reference_grid(w, h, skip)
+    want8 = return_rgb8 or out_rgb8 is not None
+
+    def alloc(dev):
+        res = torch.empty((n, 3, gh, gw), dtype=torch.float32, device=dev) if out is None else out
+        r8 = (torch.empty((n, 3, gh, gw), dtype=torch.uint8, device=dev) if out_rgb8 is None else out_rgb8) if want8 else None
+        return res, r8
+
+    with on_stream(torch, ctx, rgb, stream, alloc) as (_, (res, r8)):
+        ov = device_view(res, writable=True, name="out", shape=(n, 3, gh, gw))
+        qv = device_view(r8, writable=True, name="out_rgb8", kinds=("u1",), shape=(n, 3, gh, gw)) if want8 else None
+        ctx._ck(_lib().sfa_reference_lab_device(ctx.h, n, w, h, int(skip), C.c_void_p(v.ptr), _LL4(*v.strides), float(norm), C.c_void_p(ov.ptr), _LL4(*ov.strides),
+                                                C.c_void_p(qv.ptr) if qv else None, _LL4(*qv.strides) if qv else None), "sfa_reference_lab_device")
+    return (res, r8) if want8 else res
 
 
 def epic_job_upload_device(job, lab=None, cost=None, i0=0, cost_has_euc=False):
@@ -588,6 +614,13 @@ def track_job_upload_fill_device(job, lab, edges, s0=0):
     lv = device_view(lab, name="lab", kinds=("f4",), shape=(ev.shape[0], 3, job.gh, job.gw)) if lab is not None else None
     job.ctx._ck(_lib().sfa_track_job_upload_fill_device(job.h_, int(s0), ev.shape[0], C.c_void_p(lv.ptr) if lv else None, _LL4(*lv.strides) if lv else None,
                                                         C.c_void_p(ev.ptr), _LL3(*ev.strides)), "sfa_track_job_upload_fill_device")
+
+
+def track_job_upload_fill_reference_device(job, rgb, edges, norm=1.0, s0=0):
+    ev = device_view(edges, name="edges", kinds=("f4",), shape=("ns", job.gh, job.gw))
+    rv = device_view(rgb, name="rgb", kinds=("f4",), shape=(ev.shape[0], 3, job.h, job.w)) if rgb is not None else None
+    job.ctx._ck(_lib().sfa_track_job_upload_fill_reference_device(job.h_, int(s0), ev.shape[0], C.c_void_p(rv.ptr) if rv else None, _LL4(*rv.strides) if rv else None,
+                                                                  float(norm), C.c_void_p(ev.ptr), _LL3(*ev.strides)), "sfa_track_job_upload_fill_reference_device")
 
 
 def track(ctx, params, flows, frames, *, occlusions=None, rates=False, stream=None, fill=None, lab=None, edges=None):

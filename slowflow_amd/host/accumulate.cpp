@@ -33,7 +33,12 @@
 // the reference's push order (slot 2 r: rate r accumulated, slot 2 r + 1: rate r filled in), so that the fused flow has no holes.  It reads
 // <output>/accumulated/tmp/edges_<sequence_start>.dat (the reference's name, :945; read_edges' format) and runs through the same track job, created with
 // sfa_track_job_create_fill, in the same groups of acc_gpu_batch: the Lab image of the 8-bit frame 0 and the edge map go up with each start_jet, and
-// the fill-in of a whole group is one launch sequence per rate.  acc_skip_pixel 0 only; at most 8 rates.
+// the fill-in of a whole group is one launch sequence per rate.  acc_skip_pixel 0; with acc_gpu_reference_image 1 also 1 and 3 (the reference's blurred
+// and resized 8-bit image of frame 0, :931-936, is formed on the GPU as INTEGRATION.md 4c' defines it: sfa_track_job_upload_fill_reference; the
+// restatement is parity-unpinned against OpenCV, hence the key); at most 8 rates.
+//
+// With -reference the program writes <output>/accumulated/tmp/frame_epic_<sequence_start>.png (the reference's name, :944) for every start_jet and exits:
+// the reduced 8-bit RGB image of frame 0 on the grid, the image an edge detector has to see to produce the edges_<sequence_start>.dat that -fill reads.
 //
 // With -alternate (implies -fill) the job alternates (sfa_track_job_create_alternate): acc_alternate rounds of prune, neighbour proposals, rescoring and
 // fusion as INTEGRATION.md 4d defines them (FLANN and GSL are not in this tree); labels hold origin slots, proposed_<sequence_start>.pgm is written.
@@ -56,6 +61,7 @@
 #include "ingest.h"
 #include "io.h"
 #include "parameter_list.h"
+#include "png.h"
 #include "util.h"
 #include "../../include/slowflow_amd.h"
 
@@ -64,7 +70,7 @@ using std::vector;
 
 static void usage() {
     printf("usage:\n");
-    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies -fuse -fill -alternate\n");
+    printf("    ./accumulate [cfg] -select [estimation for one specific final pair] -resume -energies -fuse -fill -alternate -reference\n");
     printf("    ./accumulate -decode_occlusion [occlusion .pgm / .pbm] [mask .pgm]   (the mask this program uses: median 3x3, 255 - x; 0 = occluded)\n");
     printf("\n");
     printf("Runs dense_tracking's first stage only: consistent accumulation of the jets (accumulateConsistentBatches).  cfg keys read: jet_estimation\n");
@@ -92,10 +98,17 @@ static void usage() {
     printf("-fill: implies -fuse, and adds EpicFlow's fill-in hypothesis of every rate (removeSmallSegments on the consistent pixels, their matches at\n");
     printf("every acc_epic_skip-th pixel, one batch of EpicFlow interpolations per rate) to the fusion: slot 2 r is rate r's accumulated hypothesis, slot\n");
     printf("2 r + 1 its fill-in; labels_<start>.pgm holds the slot.  Reads <output>/accumulated/tmp/edges_<start>.dat (w * h floats; a missing one exits\n");
-    printf("with status 2), so the output folder exists beforehand: run it with -resume.  Key: acc_epic_skip (2).  Refused: acc_skip_pixel other than 0,\n");
-    printf("more than 8 rates, acc_epic_interpolation 0.  The neighbour proposals are not run.  acc_gpu_epic_search (0): 1 runs the fill-in's graph searches in\n");
+    printf("with status 2), so the output folder exists beforehand: run it with -resume.  Key: acc_epic_skip (2).  acc_skip_pixel 0 is served; with\n");
+    printf("acc_gpu_reference_image 1 (default 0) also 1 and 3: the reference's 8-bit, blurred and resized image of frame 0 is then formed on the GPU\n");
+    printf("(INTEGRATION.md 4c'; OpenCV's arithmetic restated, parity-unpinned against OpenCV).  Refused: acc_skip_pixel other than 0 without that key,\n");
+    printf("any other acc_skip_pixel with it, a frame size OpenCV's resize rounds to another grid (width 7 at acc_skip_pixel 1), more than 8 rates,\n");
+    printf("acc_epic_interpolation 0.  The neighbour proposals are not run.  acc_gpu_epic_search (0): 1 runs the fill-in's graph searches in\n");
     printf("the library's compact mode (slices of seeds in one shared workspace: the same bits, and match counts whose ns * ns table would not fit, such as\n");
     printf("acc_epic_skip 2 on a full frame, stay on the GPU); any other value exits with status 1.\n");
+    printf("\n");
+    printf("-reference: writes <output>/accumulated/tmp/frame_epic_<start>.png for every start_jet (with -select: that one) and exits with status 0: the\n");
+    printf("reduced 8-bit RGB image of frame 0 on the grid (acc_skip_pixel 0, 1, 3), what an edge detector has to read to write the edges_<start>.dat of\n");
+    printf("-fill.  Keys: file, start, 16bit, scale, center / extent, raw.  Every other flag but -select and -resume is ignored.\n");
     printf("\n");
     printf("-alternate: implies -fill, and runs acc_alternate (5) rounds of prune (to the last selection plus acc_perturb_keep), neighbour proposals, their\n");
     printf("rescoring and the fusion in place of the one fusion (the track job that alternates; INTEGRATION.md 4d defines the rounds).  Keys: acc_perturb_keep\n");
@@ -136,6 +149,7 @@ struct Run {
     bool energies = false, fuse = false;     // -energies, -fuse (implies -energies)
     bool fill = false;                       // -fill (implies -fuse)
     bool alternate = false;                  // -alternate (implies -fill): the reference's rounds of prune, neighbour proposals and fusion
+    bool reference = false;                  // -reference: write each start_jet's reduced 8-bit image and exit
     string flow_format, acc_dir;             // flow_format without its extension; <output>/accumulated/
     bool crop_flows = false, crop_frames = false;   // center.x > 0 (:1135); extent.x > 0 || extent.y > 0 (:876)
     int cx = 0, cy = 0, ex = 0, ey = 0;      // center, extent
@@ -619,11 +633,15 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
             const int stride = fr.empty() ? 0 : fr[0]->stride;
             vector<float *> fp;
             for (color_image_t *c : fr) fp.push_back(c->c1);
-            // :931, 947-955: the Lab image of the 8-bit copy of frame 0, before the normalisation
-            struct Lab { color_image_t *im; ~Lab() { if (im) color_image_delete(im); } } lab{status == 0 && run.fill ? rgb8_to_lab(fr[0], fz.hbit ? 1.0f / 255 : 1.0f) : nullptr};
+            // :931-955: frame 0 as read, before the normalisation: its 8-bit, blurred and resized copy and the Lab image of that are formed on the GPU
+            struct Raw { color_image_t *im; ~Raw() { if (im) color_image_delete(im); } } raw{status == 0 && run.fill ? color_image_cpy(fr[0]) : nullptr};
             double avg[3], sd[3];
             if (status == 0 && !sfa_ok(ctx, sfa_normalize(ctx, fp.data(), (int)fp.size(), width, height, stride, avg, sd))) status = 1;   // normalize(data, Jets + 1) (:916)
             if (status == 0 && !sfa_ok(nullptr, sfa_accumulate_grid(width, height, run.skip_pixel, &gw, &gh))) status = 1;
+            if (status == 0 && run.fill && sfa_reference_grid(width, height, run.skip_pixel, &gw, &gh) != SFA_OK) {
+                std::cerr << "-fill: acc_skip_pixel " << run.skip_pixel << " on " << width << " x " << height << " frames is not supported: " << sfa_last_error(nullptr) << std::endl;
+                status = 1;
+            }
             if (status == 0 && run.fuse && width % 4 != 0) {
                 // the reference indexes its stride-pitched weight image as (y * xy_incr + xy_start) * owidth + ... (:1722, 1733, 1737): exact only where
                 // stride == width
@@ -660,7 +678,9 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
                     status = 1;
             vector<const float *> cfp(fp.begin(), fp.end());
             if (status == 0 && !sfa_ok(ctx, sfa_track_job_upload_frames(job, ng, cfp.data(), stride))) status = 1;
-            if (status == 0 && run.fill && !sfa_ok(ctx, sfa_track_job_upload_fill(job, ng, lab.im->c1, lab.im->stride, edges.cost.data()))) status = 1;
+            if (status == 0 && run.fill &&
+                !sfa_ok(ctx, sfa_track_job_upload_fill_reference(job, ng, raw.im->c1, raw.im->stride, fz.hbit ? 1.0f / 255 : 1.0f, edges.cost.data())))
+                status = 1;
             for (color_image_t *c : fr) color_image_delete(c);
         }
         if (status) break;
@@ -758,6 +778,11 @@ static int run_energies(ParameterList &params, const Run &run, vector<Segment> &
              << fup.acc_spatial_occ << ", \"acc_traj_sim_method\": " << fup.traj_sim_method << ", \"acc_traj_sim_thres\": " << fup.traj_sim_thres
              << ", \"acc_trws_eps\": " << fup.trws_eps << ", \"acc_trws_max_iter\": " << fup.trws_max_iter;
         if (run.fill) {
+            int taps[16], ntaps = 0;
+            sfa_reference_taps(run.skip_pixel, taps, &ntaps);             // (refusal() passed: the skip is served)
+            tail << ",\n  \"reference_image\": {\"skip\": " << run.skip_pixel << ", \"taps\": [";
+            for (int i = 0; i < ntaps; i++) tail << (i ? ", " : "") << taps[i];
+            tail << "], \"size\": [" << gw << ", " << gh << "]}";
             tail << ",\n  \"slots\": [";
             for (unsigned k = 0; k < 2 * run.rates; k++)
                 tail << (k ? ", " : "") << "{\"slot\": " << k << ", \"rate\": " << k / 2 << ", \"kind\": \"" << (k % 2 ? "epic_fill" : "accumulated") << "\"}";
@@ -880,9 +905,22 @@ static int refusal(ParameterList &params, const Run &run) {
                               : run.rates > 16 ? "more than 16 rates" : nullptr;
         if (refused) { std::cerr << "-fuse: " << refused << " is not supported" << std::endl; return 1; }
         if (run.fill) {
-            // the reference blurs and resizes its 8-bit image with OpenCV for acc_skip_pixel > 0 (:932-936), which is not restated; 16 slots = 8 rates x 2
-            refused = run.skip_pixel != 0 ? "acc_skip_pixel other than 0 (the reference's resized reference image is not restated)"
-                      : run.rates > 8 ? "more than 8 rates (jet_estimation lines; two of the 16 slots each)"
+            // the reference blurs and resizes its 8-bit image with OpenCV for acc_skip_pixel > 0 (:932-936): restated for 1 and 3 (INTEGRATION.md 4c')
+            // The restatement is parity-unpinned against OpenCV, so it is the cfg's choice: acc_gpu_reference_image 1.  Without the key -fill serves what it
+            // served before the restatement existed, acc_skip_pixel 0, and refuses the rest as it did
+            const bool restated = params.parameter<bool>("acc_gpu_reference_image", "0");
+            if (run.skip_pixel != 0 && !restated) {
+                std::cerr << "-fill: acc_skip_pixel other than 0 (the reference's resized reference image is OpenCV's; acc_gpu_reference_image 1 takes its restatement, "
+                             "INTEGRATION.md 4c', for acc_skip_pixel 1 and 3) is not supported" << std::endl;
+                return 1;
+            }
+            int ntaps = 0;
+            if (sfa_reference_taps(run.skip_pixel, nullptr, &ntaps) != SFA_OK) {
+                std::cerr << "-fill: acc_skip_pixel other than 0, 1 and 3 (the reference's resized reference image is not restated: " << sfa_last_error(nullptr)
+                          << ") is not supported" << std::endl;
+                return 1;
+            }
+            refused = run.rates > 8 ? "more than 8 rates (jet_estimation lines; two of the 16 slots each)"   // 16 slots = 8 rates x 2
                       : !params.parameter<bool>("acc_epic_interpolation", "1") ? "acc_epic_interpolation 0" : nullptr;
             if (refused) { std::cerr << "-fill: " << refused << " is not supported" << std::endl; return 1; }
             const int search = params.parameter<int>("acc_gpu_epic_search", "0");
@@ -993,6 +1031,58 @@ static int check_inputs(const ParameterList &params, const Run &run, vector<Segm
     return 0;
 }
 
+// -reference: the reduced 8-bit image of frame 0 of every start_jet (:931-936) as <output>/accumulated/tmp/frame_epic_<sequence_start>.png (:944, 960), the
+// file the reference hands to its edge detector.  sfa_reference_lab forms it on the GPU
+static int run_reference(ParameterList &params, const Run &run, unsigned selected, unsigned selected_end) {
+    int ntaps = 0;
+    if (sfa_reference_taps(run.skip_pixel, nullptr, &ntaps) != SFA_OK) {
+        std::cerr << "-reference: acc_skip_pixel other than 0, 1 and 3 is not supported: " << sfa_last_error(nullptr) << std::endl;
+        return 1;
+    }
+    if (params.file.empty()) { std::cerr << "-reference: `file` (the frames) missing from " << run.cfg << std::endl; return 1; }
+    const size_t sf = params.file.find_last_of('/') + 1;                 // :740-751, as check_inputs
+    string sequence_path = params.file.substr(0, sf);
+    if (!sequence_path.empty() && sequence_path.back() != '/') sequence_path += "/";
+    const string format = sequence_path + params.file.substr(sf);
+    vector<std::pair<unsigned, string>> todo;
+    for (unsigned start_jet = selected; start_jet < selected_end; start_jet++) {
+        const unsigned seq_start = run.sequence_start + start_jet * run.Jets * run.steps * run.skip;   // :735
+        todo.emplace_back(seq_start, sequence_frame_name(format, (int)seq_start, 0, run.sintel));
+        if (!file_exists(todo.back().second)) { std::cerr << todo.back().second << " does not exist!" << std::endl; return 2; }
+    }
+    sfa_ctx *ctx = nullptr;
+    if (!sfa_ok(nullptr, sfa_ctx_create(0, &ctx))) return 1;
+    mkdirs(run.acc_dir + "tmp/");
+    const float norm = params.parameter<bool>("16bit", "0") ? 1.0f / 255 : 1.0f;
+    int status = 0;
+    for (size_t i = 0; i < todo.size() && status == 0; i++) {
+        color_image_t *img = ingest_frame(params, run, ctx, todo[i].second);
+        if (!img) { status = 1; break; }
+        int gw = 0, gh = 0;
+        if (sfa_reference_grid(img->width, img->height, run.skip_pixel, &gw, &gh) != SFA_OK) {
+            std::cerr << "-reference: acc_skip_pixel " << run.skip_pixel << " on " << img->width << " x " << img->height << " frames is not supported: "
+                      << sfa_last_error(nullptr) << std::endl;
+            status = 1;
+        }
+        const size_t gpl = (size_t)gw * gh;
+        vector<float> lab(3 * gpl);
+        vector<unsigned char> rgb8(3 * gpl);
+        if (status == 0 && !sfa_ok(ctx, sfa_reference_lab(ctx, img->width, img->height, run.skip_pixel, img->c1, img->stride, norm, lab.data(), gw, rgb8.data()))) status = 1;
+        color_image_delete(img);
+        if (status) break;
+        png_image png;
+        png.width = gw; png.height = gh; png.channels = 3; png.depth = 8;
+        png.samples.resize(3 * gpl);
+        for (size_t k = 0; k < gpl; k++)
+            for (int c = 0; c < 3; c++) png.samples[3 * k + c] = rgb8[c * gpl + k];
+        const string out = run.acc_dir + "tmp/frame_epic_" + std::to_string(todo[i].first) + ".png";
+        if (!png_write(out.c_str(), png)) { std::cerr << "cannot write " << out << std::endl; status = 1; break; }
+        std::cout << "start " << todo[i].first << ": wrote the " << gw << " x " << gh << " reference image " << out << std::endl;
+    }
+    sfa_ctx_destroy(ctx);
+    return status;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "-decode_occlusion")) {
         if (argc != 4) { usage(); return 1; }
@@ -1019,12 +1109,17 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "-fuse")) run.fuse = run.energies = true;
         else if (!strcmp(a, "-fill")) run.fill = run.fuse = run.energies = true;
         else if (!strcmp(a, "-alternate")) run.alternate = run.fill = run.fuse = run.energies = true;
+        else if (!strcmp(a, "-reference")) run.reference = true;
         else if (!strcmp(a, "-select") && i + 1 < argc) { selected = (unsigned)atoi(argv[++i]); selected_end = selected + 1; }
         else { fprintf(stderr, "unknown argument %s\n", a); usage(); return 1; }
     }
     ParameterList params;
     params.read(run.cfg);
     if (int status = read_run(params, run)) return status;
+    if (run.reference) {
+        if (int status = choose_output(params, resume, run)) return status;
+        return run_reference(params, run, selected, selected_end ? selected_end : run.start_jets);
+    }
     if (int status = refusal(params, run)) return status;
     if (int status = choose_output(params, resume, run)) return status;
     vector<Segment> segs;
